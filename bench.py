@@ -7,8 +7,12 @@ A "step" = one pass of the hot path over one batch of synthetic, HBM-resident in
 One process per GPU; frames are independent, so ranks hold disjoint frame ranges (index split, weak scaling)
 and the data path has no collective.  torch.distributed (RCCL) is only the barrier / max-time reduction.
 
-Prints ONE compact JSON line (< 4 KB) on rank 0 -- the headline with its `roofline` and `cpu_baseline` objects plus ms / fraction
-of the other BASELINE configurations (`configs`) -- and writes the full record of every block to --detail (bench_detail.json).
+A plain run sets up, warms up, times --steps steps and prints ONE compact JSON line on rank 0: the headline only.
+--dump-outputs DIR writes what the last timed step computed (a fixed sample of the decoded bytes plus a per-frame checksum of all
+of them) as float .npy files.  --full adds everything else, after the timed steps: the BER check against the transmitted payload,
+the `roofline` (with this box's read / write / copy probes) and `cpu_baseline` objects, the ms / fraction of the other BASELINE
+configurations (`configs`), the host-buffer blocks and the per-length sweep; the line stays < 4 KB and the full record of every
+block goes to --detail (bench_detail.json).
 """
 import argparse
 import json
@@ -27,20 +31,25 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: BER check, roofline + box probes, CPU baseline, configs 3 / 4 / 5, host-buffer and "
+                         "per-length blocks, detail file (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, rank 0's frames)")
     ap.add_argument("--frames", type=int, default=1_000_000, help="frames per GPU (BASELINE config 2: 1M)")
     ap.add_argument("--snr-db", type=float, default=30.0)
     ap.add_argument("--cpu-frames", type=int, default=0, help="frames in the CPU-baseline sample (0 = auto)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-cfg3", action="store_true", help="skip the config 3 / 4 / 5 reports (headline only)")
-    ap.add_argument("--no-shapes", action="store_true", help="skip the per-length shapes block (N = 1 diagnostic)")
-    ap.add_argument("--no-host", action="store_true", help="skip the host-buffer / long-capture blocks (N = 1 diagnostic)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-cfg3", action="store_true", help="--full: skip the config 3 / 4 / 5 reports")
+    ap.add_argument("--no-shapes", action="store_true", help="--full: skip the per-length shapes block (N = 1 diagnostic)")
+    ap.add_argument("--no-host", action="store_true", help="--full: skip the host-buffer / long-capture blocks (N = 1 diagnostic)")
     ap.add_argument("--cfg3-frames", type=int, default=1_000_000, help="BASELINE config 3: 1M frames")
     ap.add_argument("--cfg4-ring", type=int, default=65536, help="config 4: frames in the resident ring")
     ap.add_argument("--cfg4-frames", type=int, default=10_000_000, help="config 4: frames counted (BASELINE: 10M-frame stream)")
     ap.add_argument("--cfg5-symbols", type=int, default=65536)
     ap.add_argument("--cpu-seconds", type=float, default=2.5, help="wall time of each CPU-baseline leg")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
-                    help="where the full record goes (every block of every configuration); stdout carries the compact line only")
+                    help="--full: where the full record goes (every block of every configuration); stdout carries the compact line only")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / reduction plumbing only: no GPU work, value null (CPU tests)")
     return ap.parse_args()
@@ -200,8 +209,8 @@ def dry_run(a):
            "backend": grp.backend, "ms_per_step_per_rank": per_rank}
     # the config 3 / 4 / 5 blocks run on EVERY rank (each its own frames / ring / symbol stream) through the same barrier +
     # max-over-ranks reduction; here with sleeps in place of the kernels, so that the N-rank flow of those blocks is rehearsed
-    # without a GPU (tests/test_dist_cpu.py)
-    if not a.no_cfg3:
+    # without a GPU (tests/test_dist_cpu.py); like the real blocks, only under --full
+    if a.full and not a.no_cfg3:
         from ofdm_amd.dist import shard_range
         for name in ("cfg3", "cfg5", "cfg4"):
             grp.barrier()
@@ -218,9 +227,29 @@ def dry_run(a):
                 blk["stream_frames_all_ranks"] = int(tot)
             res[name] = blk
     if grp.rank == 0:
-        Detail(a.detail, 0).write(res)
+        if a.full:
+            Detail(a.detail, 0).write(res)
         print(json.dumps(compact_line(res)))
     grp.close()
+
+
+DUMP_FRAMES = 16384  # frames of the decoded-bytes sample: 16384 x 576 B as float32 = 38 MB
+DUMP_SEED = 0x0FD3
+
+
+def dump_outputs(d, out, torch, np):
+    """What the last timed step handed its caller -- the packed bytes `out` [F, 576] -- as float .npy files: the rows of a fixed,
+    seeded sample of frames (the same frames for the same --frames), and a position-weighted checksum of every frame's bytes so
+    that no frame goes unchecked.  Both are exact integers in their float type."""
+    os.makedirs(d, exist_ok=True)
+    F, B = out.shape
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(F, size=min(F, DUMP_FRAMES), replace=False))
+    sample = out.index_select(0, torch.from_numpy(rows).to(out.device)).cpu().numpy()
+    np.save(os.path.join(d, "rx_bytes_sample.npy"), sample.astype(np.float32))
+    np.save(os.path.join(d, "rx_bytes_sample_frames.npy"), rows.astype(np.float64))
+    w = torch.arange(1, B + 1, dtype=torch.int64, device=out.device)
+    chk = torch.cat([(out[lo:lo + 65536].to(torch.int64) * w).sum(dim=1) for lo in range(0, F, 65536)])
+    np.save(os.path.join(d, "rx_bytes_frame_checksum.npy"), chk.cpu().numpy().astype(np.float64))
 
 
 def _r(v, n=4):
@@ -299,6 +328,8 @@ def main():
     a = parse()
     if a.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if a.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(a)
     if a.dry_run:
@@ -359,6 +390,28 @@ def main():
     dt = time.perf_counter() - t0
     per_rank_ms = grp.gather_floats(ev_ms / a.steps)  # every rank's own kernel time per step
     dt, ev_ms = grp.reduce_max(dt, ev_ms)  # the slowest rank defines the step time
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out, torch, np)
+
+    samples_per_step = F * syms * ctx.S
+    value = n_gpus * samples_per_step * a.steps / dt / 1e6
+    res = {
+        "metric": "complex IQ Msamples/s through RX demod", "value": value, "unit": "Msamples/s", "n_gpus": n_gpus,
+        "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt * 1e3 / a.steps, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "cfg2: 64-subcarrier 64QAM guard-band frames, RX demod only (CP strip+FFT64+pilot phase+demap)",
+                   "frames_per_gpu": F, "symbols_per_frame": syms, "samples_per_frame": syms * ctx.S,
+                   "snr_db": a.snr_db, "parallelism": f"frame-index split x{n_gpus}, no collective",
+                   "parity": "FFT / CP strip / pilot phase follow src/receiver.rs:99-145; the 64-QAM demap is a north-star extension the reference "
+                             "lacks (EXT-1): parity unpinned by the reference, the oracle is the definition"},
+        "world_size_seen": world, "backend": grp.backend, "kernel_ms_per_rank": per_rank_ms,
+    }
+    if not a.full:  # a plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(compact_line(res)), flush=True)
+        grp.close()
+        return
+
     solo_ms = None
     if n_gpus > 1:  # the N = 1 reference of THIS run: rank 0 repeats the K steps alone while the others idle at a barrier
         if rank == 0:
@@ -377,8 +430,6 @@ def main():
     bits, nerr = (int(v) for v in grp.reduce_sum(bits, nerr))
     ber = bits / (n_gpus * F * payload.shape[1] * 8)
 
-    samples_per_step = F * syms * ctx.S
-    value = n_gpus * samples_per_step * a.steps / dt / 1e6
     kern_s = ev_ms / 1e3 / a.steps
     alg_bytes = F * (syms * ctx.S * 8 + syms * ctx.bytes_per_symbol)  # 8 B/sample read + packed bytes written
     # HBM bytes per launch from the committed PMC passes (profiles/r0N_pmc_traffic.json, newest round), scaled to F: collected in
@@ -425,18 +476,7 @@ def main():
     if traffic:  # the same launch priced on the bytes the counters saw move (the cyclic prefix of a symbol is never fetched)
         roof["frac_moved"] = traffic / kern_s / 1e9 / HBM_PEAK_GBS
 
-    res = {
-        "metric": "complex IQ Msamples/s through RX demod", "value": value, "unit": "Msamples/s", "n_gpus": n_gpus,
-        "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt * 1e3 / a.steps, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "cfg2: 64-subcarrier 64QAM guard-band frames, RX demod only (CP strip+FFT64+pilot phase+demap)",
-                   "frames_per_gpu": F, "symbols_per_frame": syms, "samples_per_frame": syms * ctx.S,
-                   "snr_db": a.snr_db, "parallelism": f"frame-index split x{n_gpus}, no collective",
-                   "parity": "FFT / CP strip / pilot phase follow src/receiver.rs:99-145; the 64-QAM demap is a north-star extension the reference "
-                             "lacks (EXT-1): parity unpinned by the reference, the oracle is the definition"},
-        "ber_vs_tx_payload": ber, "frames_with_errors": nerr, "roofline": roof,
-        "world_size_seen": world, "backend": grp.backend, "kernel_ms_per_rank": per_rank_ms,
-    }
+    res.update({"ber_vs_tx_payload": ber, "frames_with_errors": nerr, "roofline": roof})
     if solo_ms:  # informational (the driver computes scaling from its own N = 1 run): N ranks' aggregate over N x rank 0 alone
         res["in_run_single_rank_kernel_ms"] = solo_ms
         res["weak_scaling_efficiency_in_run"] = (n_gpus * samples_per_step / (dt / a.steps)) / (n_gpus * samples_per_step / (solo_ms / 1e3))

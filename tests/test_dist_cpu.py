@@ -273,7 +273,7 @@ def test_bench_gpus_n_starts_n_ranks():
     import tempfile
     with tempfile.TemporaryDirectory() as td:
         det = os.path.join(td, "detail.json")
-        rc, recs, lines, err = _run_bench("--gpus", "2", "--dry-run", "--steps", "2", "--detail", det, env={"OFDM_DIST_BACKEND": "gloo"})
+        rc, recs, lines, err = _run_bench("--gpus", "2", "--dry-run", "--full", "--steps", "2", "--detail", det, env={"OFDM_DIST_BACKEND": "gloo"})
         assert rc == 0, err
         full = json.load(open(det))       # the full record: per-rank times of every block
     assert len(lines) == 1 and len(recs) == 1, lines   # ONE JSON line on stdout
@@ -316,6 +316,22 @@ def test_bench_gpus_1_is_single_rank():
     rc, recs, lines, err = _run_bench("--gpus", "1", "--dry-run", "--steps", "2")
     assert rc == 0, err
     assert recs[0]["n_gpus"] == 1 and recs[0]["ranks_seen"] == 1
+
+
+def test_bench_plain_run_is_headline_only():
+    """Without --full the bench times the headline and prints it: no config blocks, no detail file; the steps asked for are
+    the steps timed."""
+    import tempfile
+    with tempfile.TemporaryDirectory() as td:
+        det = os.path.join(td, "detail.json")
+        rc, recs, lines, err = _run_bench("--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "1", "--detail", det,
+                                          env={"OFDM_DIST_BACKEND": "gloo"})
+        assert rc == 0, err
+        assert not os.path.exists(det)
+    assert len(lines) == 1 and len(recs) == 1, lines
+    rec = recs[0]
+    assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+    assert "configs" not in rec and "detail" not in rec
 
 
 def test_bench_refuses_a_mismatched_world():

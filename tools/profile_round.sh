@@ -10,7 +10,7 @@ set -o pipefail
 ROUND=${ROUND:-r05}
 OUT="$PWD/gpurun_out/prof"; mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH_ARGS=${BENCH_ARGS:-}
+BENCH_ARGS="--full ${BENCH_ARGS:-}"   # every block of the bench (roofline, CPU baseline, configs 3 / 4 / 5, ...), not the headline alone
 if [ -z "$SKIP_BENCH" ]; then
 timeout -k 10 900 python3 bench.py --detail "$OUT/${ROUND}_bench_detail.json" $BENCH_ARGS > "$OUT/${ROUND}_bench.json" 2> "$OUT/${ROUND}_bench.err" || exit 1
 echo "bench done"
