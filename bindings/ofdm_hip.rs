@@ -30,6 +30,11 @@ pub const OFDM_MOD_BPSK: i32 = 1;
 pub const OFDM_MOD_QPSK: i32 = 2;
 pub const OFDM_MOD_QAM16: i32 = 4;
 pub const OFDM_MOD_QAM64: i32 = 6;
+pub const OFDM_ECC_NONE: i32 = 0;
+pub const OFDM_ECC_HAMMING74: i32 = 1;
+// same frames on the wire as OFDM_ECC_HAMMING74; decode ML-decodes the code from int8 LLRs (include/ofdm_hip.h)
+pub const OFDM_ECC_HAMMING74_SOFT: i32 = 2;
+pub const OFDM_SOFT_LLR_SCALE: f32 = 32.0;
 
 /// The crate's own `ModulationScheme` (src/transmitter.rs:98-104) is what `encode` / `decode` keep taking.  Its `Qam` arm is
 /// empty in the reference (transmitter.rs:135-136, receiver.rs:185: "Only 16 qam is implemented"); here it selects 16-QAM.
@@ -85,6 +90,7 @@ extern "C" {
     pub fn ofdm_normalize_batch(ctx: *mut ofdm_ctx, x_dev: *mut ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64) -> c_int;
     pub fn ofdm_hamming74_encode(ctx: *mut ofdm_ctx, in_dev: *const u8, n_bytes: i64, out_dev: *mut u8) -> c_int;
     pub fn ofdm_hamming74_decode(ctx: *mut ofdm_ctx, in_dev: *const u8, n_bytes: i64, out_dev: *mut u8, corrected_dev: *mut u32) -> c_int;
+    pub fn ofdm_hamming74_decode_soft(ctx: *mut ofdm_ctx, llr_dev: *const i8, n_bits: i64, out_dev: *mut u8) -> c_int;
     pub fn ofdm_sc_correlate_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,
                                    n_lags: i64, d_hat_dev: *mut i32, f_delta_dev: *mut f64, metric_dev: *mut f32) -> c_int;
     pub fn ofdm_frequency_correction_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_pairs: i64, stride: i64,
@@ -96,6 +102,9 @@ extern "C" {
     pub fn ofdm_rx_demod_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,
                                first_symbol: i32, syms_per_frame: i32, offset_dev: *const i32, f_delta_dev: *const f64,
                                hk_dev: *const ofdm_fc32, hk_stride: i64, out_dev: *mut u8, out_stride: i64, soft_dev: *mut ofdm_fc32) -> c_int;
+    pub fn ofdm_rx_llr_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,
+                             first_symbol: i32, syms_per_frame: i32, offset_dev: *const i32, f_delta_dev: *const f64,
+                             hk_dev: *const ofdm_fc32, hk_stride: i64, llr_scale: f32, llr_dev: *mut i8, llr_stride: i64) -> c_int;
     pub fn ofdm_tx_encode_batch(ctx: *mut ofdm_ctx, payload_dev: *const u8, n_frames: i64, payload_stride: i64,
                                 payload_len_dev: *const i32, payload_bytes: i32, out_dev: *mut ofdm_fc32, out_stride: i64) -> c_int;
     pub fn ofdm_rx_decode_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,

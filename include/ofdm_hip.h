@@ -62,7 +62,12 @@ enum {
 
 /* ModulationScheme (src/transmitter.rs:98-104) as bits per constellation point */
 enum { OFDM_MOD_BPSK = 1, OFDM_MOD_QPSK = 2, OFDM_MOD_QAM16 = 4, OFDM_MOD_QAM64 = 6, OFDM_MOD_QAM256 = 8 };
-enum { OFDM_ECC_NONE = 0, OFDM_ECC_HAMMING74 = 1 };
+/* ecc: OFDM_ECC_HAMMING74_SOFT transmits exactly what OFDM_ECC_HAMMING74 transmits (coded_len, data_symbols, frame_samples and the
+ * samples of every encode entry point are the same); only decode differs: the 16-byte length header is still read from hard bits, the
+ * coded body is decoded by maximum likelihood from int8 LLRs (see "soft decisions" below) instead of by syndrome.  ecc >= 3: invalid. */
+enum { OFDM_ECC_NONE = 0, OFDM_ECC_HAMMING74 = 1, OFDM_ECC_HAMMING74_SOFT = 2 };
+/* llr_scale of the OFDM_ECC_HAMMING74_SOFT decode chain (chosen from the measured BER curves) */
+#define OFDM_SOFT_LLR_SCALE 32.0f
 enum { OFDM_CFO_OFF = 0, OFDM_CFO_SIGNED = 1, OFDM_CFO_ABS = 2 }; /* ABS = reference's abs() (receiver.rs:239) */
 /* timing / CFO detector of decode: the north star's Schmidl-Cox (default), or the reference's own pair -- cross-correlation
  * with the locking signal (xcorr_fft, src/signals/mod.rs:186-217; offset = idx_max - N = lag - 1, src/receiver.rs:20-25) and
@@ -240,6 +245,28 @@ int ofdm_rx_demod_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames
                         const int32_t *offset_dev, const double *f_delta_dev, const ofdm_fc32 *hk_dev,
                         int64_t hk_stride, uint8_t *out_dev, int64_t out_stride, ofdm_fc32 *soft_dev);
 
+/* ------------------------------------------------------------------ soft decisions (north-star extension)
+ * LLR definition, shared by the kernels and tests/soft_ref.py.  A point's bps bits are in demap_point's stream order: the I-axis
+ * bits, then the Q-axis bits (BPSK: the I bit only); each axis carries m bits on M = 2^m levels.  With x the equalised,
+ * pilot-phase-corrected coordinate, v = x (M - 1) and the levels are the odd integers a_l = 2 l - (M - 1), l in [0, M).  Axis bit b
+ * (b = 0 is the Gray MSB) of level l is bit (m - 1 - b) of l ^ (l >> 1), and
+ *     Lambda_b(v) = ( min_{l: bit = 0} (v - a_l)^2 - min_{l: bit = 1} (v - a_l)^2 ) / 4          POSITIVE MEANS BIT 1
+ * (BPSK / QPSK: Lambda = v, the sign convention of the hard decisions; a noiseless point's weakest bit has |Lambda| = 1).
+ * Channel weight w_k = |H_k|^2 / (mean of |H|^2 over the data carriers), per frame or over the shared H; w = 1 without H.
+ * Stored: int8 L = clamp(rint(llr_scale * w_k * Lambda), -127, 127), 0 when the product is not finite.
+ * The true LLR is L / llr_scale * 4 mean|H|^2 / ((M - 1)^2 sigma^2), sigma^2 = the complex noise variance of a received bin; the
+ * library does not estimate sigma^2. */
+/* ofdm_rx_demod_batch with int8 LLRs out instead of hard bytes: arguments as there; llr_dev[f*llr_stride ..] receives
+ * syms_per_frame * data_carriers * bps LLRs, LLR j = bit j of the stream rx_demod packs LSB-first.  llr_scale must be finite and
+ * > 0, llr_stride >= syms_per_frame * data_carriers * bps (OFDM_ERR_INVALID otherwise). */
+int ofdm_rx_llr_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                      int32_t first_symbol, int32_t syms_per_frame, const int32_t *offset_dev, const double *f_delta_dev,
+                      const ofdm_fc32 *hk_dev, int64_t hk_stride, float llr_scale, int8_t *llr_dev, int64_t llr_stride);
+/* Soft Hamming(7,4): floor(n_bits / 56) blocks of 8 codewords in ofdm_hamming74_encode's bit layout (7 bits per nibble, low nibble
+ * first) -> 4 bytes per block.  Per codeword the c of the 16 that maximises sum_i (2 c_i - 1) L_i, in exact integer arithmetic;
+ * ties go to the smallest data nibble. */
+int ofdm_hamming74_decode_soft(ofdm_ctx *ctx, const int8_t *llr_dev, int64_t n_bits, uint8_t *out_dev);
+
 /* ------------------------------------------------------------------ pipelines */
 
 /* encode (src/transmitter.rs:11-58) for a batch: frame f = [lock][preamble x4][training x5][data symbols],
@@ -248,7 +275,7 @@ int ofdm_rx_demod_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames
  * kernels prefetch whole rows and mask afterwards): payload_stride >= payload_bytes (OFDM_ERR_INVALID otherwise when n_frames > 1),
  * and the buffer ends no earlier than the last row's payload_bytes.  Every frame is laid out for payload_bytes (D = ofdm_data_symbols(payload_bytes))
  * and written to out_dev[f*out_stride ..] (out_stride >= ofdm_frame_samples(payload_bytes)).
- * With ECC the payload is Hamming(7,4)-encoded first and the header carries the coded length. */
+ * With ECC the payload is Hamming(7,4)-encoded first and the header carries the coded length (HAMMING74 and HAMMING74_SOFT alike). */
 int ofdm_tx_encode_batch(ofdm_ctx *ctx, const uint8_t *payload_dev, int64_t n_frames, int64_t payload_stride,
                          const int32_t *payload_len_dev, int32_t payload_bytes, ofdm_fc32 *out_dev,
                          int64_t out_stride);
@@ -258,7 +285,10 @@ int ofdm_tx_encode_batch(ofdm_ctx *ctx, const uint8_t *payload_dev, int64_t n_fr
  * per symbol FFT / equalise / pilot phase / demap -> 16-byte length header -> truncate [-> Hamming decode].
  * At most max_symbols data symbols per frame are demodulated (fewer if the frame is shorter).
  * out_dev[f*out_stride ..] receives out_len_dev[f] bytes (out_stride >= max_symbols*bytes_per_symbol).
- * status/offset/f_delta/metric are per-frame outputs; any of offset/f_delta/metric may be NULL. */
+ * status/offset/f_delta/metric are per-frame outputs; any of offset/f_delta/metric may be NULL.
+ * ecc = OFDM_ECC_HAMMING74_SOFT (here and in every decode entry point that wraps this one: _host, _long, _long_host): the header is
+ * read from hard bits as with HAMMING74, the body from LLR 128 on is ML-decoded from ofdm_rx_llr_batch's LLRs at
+ * OFDM_SOFT_LLR_SCALE with the frame's channel estimate; out_len = floor(coded / 7) * 4 as with HAMMING74. */
 int ofdm_rx_decode_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t frame_stride,
                          int64_t frame_len, int64_t n_lags, int32_t max_symbols, uint8_t *out_dev,
                          int64_t out_stride, int32_t *out_len_dev, int32_t *status_dev, int32_t *offset_dev,

@@ -18,7 +18,8 @@ import torch
 from . import _lib
 
 BPSK, QPSK, QAM16, QAM64, QAM256 = 1, 2, 4, 6, 8  # ModulationScheme (src/transmitter.rs:98-104) as bits/point
-ECC_NONE, ECC_HAMMING74 = 0, 1
+ECC_NONE, ECC_HAMMING74, ECC_HAMMING74_SOFT = 0, 1, 2
+SOFT_LLR_SCALE = 32.0  # OFDM_SOFT_LLR_SCALE (include/ofdm_hip.h): the llr_scale of the soft decode chain
 CFO_OFF, CFO_SIGNED, CFO_ABS = 0, 1, 2
 FRAME_OK, FRAME_SHORT, FRAME_NOSYNC, FRAME_BADTIMING, FRAME_HEADER = 0, -1, -2, -3, -4
 SYNC_SCHMIDL_COX, SYNC_REFERENCE = 0, 1
@@ -334,6 +335,14 @@ class Context:
                  "hamming74_decode")
         return out, fixed
 
+    def hamming74_decode_soft(self, llr: torch.Tensor) -> torch.Tensor:
+        """ofdm_hamming74_decode_soft: int8 LLRs (positive = bit 1), floor(n / 56) blocks of 8 codewords -> 4 bytes per block (ML)."""
+        if llr.dtype != torch.int8 or not llr.is_contiguous() or llr.device != self.device:
+            raise OfdmError("expected a contiguous int8 tensor on the context's device")
+        out = self.empty((llr.numel() // 56 * 4,), torch.uint8)
+        self._ck(self.lib.ofdm_hamming74_decode_soft(self.h, _dev(llr), llr.numel(), _dev(out)), "hamming74_decode_soft")
+        return out
+
     def sc_correlate(self, frames: torch.Tensor, frame_len: Optional[int] = None, n_lags: int = 0):
         """Schmidl-Cox timing / CFO per row of `frames` [n_frames, stride] -> (d_hat i32, f_delta f64, metric f32)."""
         frames = self._cx(frames)
@@ -410,6 +419,26 @@ class Context:
                                               first_symbol, syms_per_frame, _dev(offset), _dev(f_delta), _dev(hk),
                                               hk_stride, _dev(out), nb, _dev(soft)), "rx_demod")
         return (out, soft) if want_soft else out
+
+    def rx_llr(self, frames: torch.Tensor, syms_per_frame: int, first_symbol: int = 0, offset: Optional[torch.Tensor] = None,
+               f_delta: Optional[torch.Tensor] = None, hk: Optional[torch.Tensor] = None, frame_len: Optional[int] = None,
+               scale: float = SOFT_LLR_SCALE) -> torch.Tensor:
+        """ofdm_rx_llr_batch: rx_demod with int8 max-log LLRs out -> [n_frames, syms_per_frame * data_carriers * bps], LLR j = bit j
+        of the stream rx_demod packs LSB-first (positive = bit 1; definition in include/ofdm_hip.h)."""
+        frames = self._cx(frames)
+        f2 = frames.view(-1, frames.shape[-1])
+        n, stride = f2.shape
+        nl = syms_per_frame * self.data_carriers * self.modulation
+        out = self.empty((n, nl), torch.int8)
+        hk_stride = 0
+        if hk is not None:
+            hk = self._cx(hk)
+            hk_stride = self.n_fft if hk.dim() == 2 else 0  # [n_frames, N] per frame, [N] shared
+            assert hk.shape[-1] == self.n_fft and (hk.dim() == 1 or hk.shape[0] == n)
+        self._ck(self.lib.ofdm_rx_llr_batch(self.h, _dev(f2), n, stride, stride if frame_len is None else frame_len, first_symbol,
+                                            syms_per_frame, _dev(offset), _dev(f_delta), _dev(hk), hk_stride, float(scale), _dev(out), nl),
+                 "rx_llr")
+        return out
 
     # ---------------------------------------------------------------- pipelines
     def encode_batch(self, payload: torch.Tensor, out: Optional[torch.Tensor] = None,

@@ -385,6 +385,98 @@ __device__ __forceinline__ void ham_decode_block(const uint8_t *src, uint8_t *ds
     }
 }
 
+// ---- soft decisions (OFDM_ECC_HAMMING74_SOFT, include/ofdm_hip.h; restated in tests/soft_ref.py)
+// Max-log LLR of axis bit b (b = 0: the Gray MSB) of a Gray-PAM axis with M = 2^m levels a_l = 2 l - (M - 1), at v = x (M - 1),
+// in closed form.  Bit b of level l is bit j = m - 1 - b of l ^ (l >> 1): constant over the levels [(2r - 1) h, (2r + 1) h),
+// h = 2^j, r = (l + h) >> (j + 1), where it equals r & 1.  So the nearest level of the other bit value is (2r - 1) h - 1 or
+// (2r + 1) h, whichever exists and lies nearer to v, and with a* the nearest level overall
+//     Lambda = +-((v - a_o)^2 - (v - a*)^2) / 4 = +-(a* - a_o)(2 v - a_o - a*) / 4,   + when bit b of l* is 1.
+// ls = l* (the hard decision's level index, clamped to [0, M)).
+__device__ __forceinline__ float llr_axis_bit(float v, int ls, int j, int M) {
+    const int h = 1 << j, r = (ls + h) >> (j + 1);
+    const int lo = (2 * r - 1) * h - 1, hi = (2 * r + 1) * h;
+    const float as = (float)(2 * ls - (M - 1)), alo = (float)(2 * lo - (M - 1)), ahi = (float)(2 * hi - (M - 1));
+    float ao;
+    if (lo < 0) ao = ahi;
+    else if (hi > M - 1) ao = alo;
+    else ao = (v - alo) <= (ahi - v) ? alo : ahi;
+    const float lam = 0.25f * (as - ao) * (2.0f * v - ao - as);
+    return (r & 1) ? lam : -lam;
+}
+// int8 L = clamp(rint(s Lambda), -127, 127); a non-finite product gives 0
+__device__ __forceinline__ int llr_q(float y) {
+    if (!__builtin_isfinite(y)) return 0;
+    return (int)__builtin_amdgcn_fmed3f(rintf(y), -127.0f, 127.0f);
+}
+// the bps LLRs of one point in demap_point's stream order (I-axis bits, then Q-axis bits; BPSK: the I bit), each scaled by s,
+// to dst[0 .. bps)
+__device__ __forceinline__ void llr_point(cf z, int bps, float s, int8_t *dst) {
+    if (bps == 1) { dst[0] = (int8_t)llr_q(s * z.x); return; }
+    const int m = bps >> 1, M = 1 << m;
+    const float vi = z.x * (float)(M - 1), vq = z.y * (float)(M - 1);
+    const int li = (int)clamp0(fmaf(z.x, 0.5f * (float)(M - 1), (float)(M / 2)), (float)(M - 1));
+    const int lq = (int)clamp0(fmaf(z.y, 0.5f * (float)(M - 1), (float)(M / 2)), (float)(M - 1));
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+        if (b < m) {
+            dst[b] = (int8_t)llr_q(s * llr_axis_bit(vi, li, m - 1 - b, M));
+            dst[m + b] = (int8_t)llr_q(s * llr_axis_bit(vq, lq, m - 1 - b, M));
+        }
+}
+
+// Soft Hamming(7,4): codeword c = ham_enc(d) as int8 weights 16 (2 c_i - 1), i < 7, and 0 for an eighth byte, packed four to a dword
+// (w0: bits 0..3, w1: bits 4..6)
+__host__ __device__ constexpr unsigned ham_soft_w(int d, int half) {
+    unsigned c = (unsigned)d | ((((d ^ (d >> 1) ^ (d >> 3)) & 1u)) << 4) | ((((d ^ (d >> 2) ^ (d >> 3)) & 1u)) << 5) |
+                 (((((d >> 1) ^ (d >> 2) ^ (d >> 3)) & 1u)) << 6);
+    unsigned w = 0;
+    for (int i = 0; i < 4; ++i) {
+        const int bit = 4 * half + i;
+        const int v = bit == 7 ? 0 : (((c >> bit) & 1u) ? 16 : -16);
+        w |= ((unsigned)v & 0xFFu) << (8 * i);
+    }
+    return w;
+}
+// ML decode of one codeword from its 7 LLRs (the low 7 bytes of q1:q0; byte 7 is ignored): the nibble d maximising
+// sum_i (2 c_i - 1) L_i, ties to the smallest d.  Exact integers: key = 16 corr + (15 - d) through two v_dot4 per candidate,
+// and the largest key carries both rules.
+__device__ __forceinline__ unsigned ham_soft_cw(unsigned q0, unsigned q1) {
+    int best = -0x7fffffff;
+#pragma unroll
+    for (int d = 0; d < 16; ++d) {
+        const int key = __builtin_amdgcn_sdot4((int)q1, (int)ham_soft_w(d, 1), __builtin_amdgcn_sdot4((int)q0, (int)ham_soft_w(d, 0), 15 - d, false), false);
+        best = max(best, key);
+    }
+    return 15u - ((unsigned)best & 15u);
+}
+// one block of 8 codewords (56 LLRs = 14 dwords, LSB-first stream order as ofdm_hamming74_encode lays it out) -> 4 data bytes
+// (a little-endian dword).  D[14] only feeds the ignored eighth byte of the last codeword.
+__device__ __forceinline__ unsigned ham_soft_block(const unsigned (&D)[15]) {
+    unsigned out = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int by = 7 * j, di = by >> 2, sh = by & 3;
+        const unsigned q0 = __builtin_amdgcn_alignbyte(D[di + 1], D[di], sh);
+        const unsigned q1 = __builtin_amdgcn_alignbyte(D[di + 2], D[di + 1], sh);
+        out |= ham_soft_cw(q0, q1) << (4 * j);
+    }
+    return out;
+}
+// the block's 14 dwords from src (ALIGN8: src is 8-byte aligned; otherwise byte loads)
+template <bool ALIGN8> __device__ __forceinline__ void ham_soft_load(const int8_t *src, unsigned (&D)[15]) {
+    if (ALIGN8) {
+        const uint2 *s2 = reinterpret_cast<const uint2 *>(src);
+#pragma unroll
+        for (int i = 0; i < 7; ++i) { const uint2 v = s2[i]; D[2 * i] = v.x; D[2 * i + 1] = v.y; }
+    } else {
+        const uint8_t *s = reinterpret_cast<const uint8_t *>(src);
+#pragma unroll
+        for (int i = 0; i < 14; ++i)
+            D[i] = (unsigned)s[4 * i] | ((unsigned)s[4 * i + 1] << 8) | ((unsigned)s[4 * i + 2] << 16) | ((unsigned)s[4 * i + 3] << 24);
+    }
+    D[14] = 0;
+}
+
 // One 8-byte load of a complex sample through a pointer that came out of a select: as a struct of two floats the compiler
 // splits such a load into two global_load_dword (it no longer sees that the halves are adjacent).
 __device__ __forceinline__ cf ld_cf(const cf *a) {

@@ -42,6 +42,7 @@ struct Tuning {
     int scb_two_segments = 0;      // k_scb_chunks: two-segment staging also for L <= 1280
     int scb_big_tiles = 0;         // k_scb_fine: 1280-lag tiles / 128 threads
     int debug_demod64 = 0, debug_sc = 0, debug_tx = 0; // profile build only (kProfile)
+    int soft_chunk_frames = 0;     // OFDM_ECC_HAMMING74_SOFT decode: frames per k_sym<llr> + k_rx_finish_soft step (0 = the LLR workspace's 256 MB bound)
 };
 inline const Tuning &tuning_or_default(const Tuning *t) { static const Tuning d; return t ? *t : d; }
 
@@ -105,6 +106,10 @@ struct SymParams {
     long long tx_raw_total = -1;   // >= 0: TX of a continuous symbol stream (modulate + encode_block + prefix_block only):
                                    // payload is tx_raw_total plain bytes, one symbol per "frame", no length header, no frame
                                    // header blocks, no normalise
+    // LLR demod (k_sym<llr>): int8 max-log LLRs, syms_per_frame * data_carriers * bps per frame (include/ofdm_hip.h)
+    int8_t *llr = nullptr;
+    float llr_scale = 0.f;
+    long long llr_stride = 0;    // bytes between per-frame LLR rows
 };
 
 // N = 64 RX-demod fast path (kernels_fast.hip)
@@ -157,6 +162,8 @@ hipError_t run_ifft_cp(int n, const SymParams &p, hipStream_t st, int num_cu);
 hipError_t run_demod(int n, const SymParams &p, hipStream_t st, int num_cu);
 hipError_t run_chest(int n, const SymParams &p, hipStream_t st, int num_cu);
 hipError_t run_tx_symbols(int n, const SymParams &p, hipStream_t st, int num_cu);
+// LLR demod: the RX demod chain with int8 max-log LLRs out (p.llr) and, when p.out_bytes is set, the hard bytes too
+hipError_t run_llr(int n, const SymParams &p, hipStream_t st, int num_cu);
 
 // ---- Schmidl-Cox (kernels_sync.hip)
 struct ScParams {
@@ -254,6 +261,13 @@ hipError_t run_rx_finish(const uint8_t *raw, long long raw_stride, long long n_f
                          const int32_t *nsym, int bytes_per_symbol, int ecc, uint8_t *out, long long out_stride,
                          int32_t *out_len, hipStream_t st, const int32_t *frame_list = nullptr,
                          const int32_t *frame_count = nullptr);
+// soft RX finish (OFDM_ECC_HAMMING74_SOFT): the header from the hard bytes as k_rx_finish, the body ML-decoded from the LLR rows
+// (llr row f holds the frame's LLRs from stream bit 0; the body starts at LLR 128)
+hipError_t run_rx_finish_soft(const uint8_t *raw, long long raw_stride, const int8_t *llr, long long llr_stride, long long n_frames,
+                              const int32_t *status, const int32_t *nsym, int bytes_per_symbol, uint8_t *out, long long out_stride,
+                              int32_t *out_len, hipStream_t st);
+// soft Hamming(7,4) decode of n_bits / 56 blocks of 8 codewords (ofdm_hamming74_decode_soft)
+hipError_t run_ham_decode_soft(const int8_t *llr, long long n_bits, uint8_t *out, hipStream_t st);
 
 // channel (src/channel.rs:33-74) on the GPU (kernels_bytes.hip)
 struct ChannelParams {

@@ -327,6 +327,73 @@ hipError_t run_rx_finish(const uint8_t *raw, long long raw_stride, long long n_f
     return hipGetLastError();
 }
 
+// soft decode of one 8-codeword block at src (56 LLRs) into 4 bytes at dst (a dword store when dst is 4-byte aligned)
+template <bool ALIGN8> __device__ __forceinline__ void ham_soft_decode_to(const int8_t *src, uint8_t *dst) {
+    unsigned D[15];
+    ham_soft_load<ALIGN8>(src, D);
+    const unsigned w = ham_soft_block(D);
+    if (((uintptr_t)dst & 3) == 0) *reinterpret_cast<unsigned *>(dst) = w;
+    else { for (int j = 0; j < 4; ++j) dst[j] = (uint8_t)(w >> (8 * j)); }
+}
+
+// OFDM_ECC_HAMMING74_SOFT finish: the length header from the hard bytes exactly as k_rx_finish reads it, then the floor(keep / 7)
+// blocks of the body ML-decoded from the LLR row (body = LLRs 128 ..).  One wavefront per frame, one block of 8 codewords per lane:
+// the 64 lanes of a step read 64 consecutive 56-byte blocks.
+template <bool ALIGN8>
+__global__ __launch_bounds__(256) void k_rx_finish_soft(const uint8_t *raw, long long raw_stride, const int8_t *llr, long long llr_stride,
+                                                        long long n_frames, const int32_t *status, const int32_t *nsym, int bytes_per_symbol,
+                                                        uint8_t *out, long long out_stride, int32_t *out_len) {
+    const int lane = threadIdx.x & 63;
+  for (long long f = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); f < n_frames; f += (long long)gridDim.x * 4) {
+    if (status[f] != 0) { if (lane == 0) out_len[f] = 0; continue; }
+    const uint8_t *src = raw + f * raw_stride;
+    const long long body = (long long)nsym[f] * bytes_per_symbol - 16;
+    unsigned long long lo = 0, hi = 0; // bincode fixint little-endian u128 (src/packets/mod.rs:20-32)
+    if (((uintptr_t)src & 3) == 0) {
+        const uint32_t *h4 = reinterpret_cast<const uint32_t *>(src);
+        lo = (unsigned long long)h4[0] | ((unsigned long long)h4[1] << 32);
+        hi = (unsigned long long)h4[2] | ((unsigned long long)h4[3] << 32);
+    } else {
+        for (int i = 0; i < 8; ++i) { lo |= (unsigned long long)src[i] << (8 * i); hi |= (unsigned long long)src[8 + i] << (8 * i); }
+    }
+    const long long keep = (hi == 0 && lo < (unsigned long long)body) ? (long long)lo : body; // Vec::truncate
+    const long long blocks = keep / 7;
+    const int8_t *l = llr + f * llr_stride + 128;
+    uint8_t *dst = out + f * out_stride;
+    for (long long b = lane; b < blocks; b += 64) ham_soft_decode_to<ALIGN8>(l + b * 56, dst + b * 4);
+    if (lane == 0) out_len[f] = (int32_t)(blocks * 4);
+  }
+}
+hipError_t run_rx_finish_soft(const uint8_t *raw, long long raw_stride, const int8_t *llr, long long llr_stride, long long n_frames,
+                              const int32_t *status, const int32_t *nsym, int bytes_per_symbol, uint8_t *out, long long out_stride,
+                              int32_t *out_len, hipStream_t st) {
+    if (n_frames <= 0) return hipSuccess;
+    const unsigned blocks = grid_for(n_frames, 4);
+    if (((reinterpret_cast<uintptr_t>(llr) | (uintptr_t)llr_stride) & 7) == 0)
+        hipLaunchKernelGGL(k_rx_finish_soft<true>, dim3(blocks), dim3(256), 0, st, raw, raw_stride, llr, llr_stride, n_frames, status, nsym,
+                           bytes_per_symbol, out, out_stride, out_len);
+    else
+        hipLaunchKernelGGL(k_rx_finish_soft<false>, dim3(blocks), dim3(256), 0, st, raw, raw_stride, llr, llr_stride, n_frames, status, nsym,
+                           bytes_per_symbol, out, out_stride, out_len);
+    return hipGetLastError();
+}
+
+// ofdm_hamming74_decode_soft: one thread per block of 8 codewords
+template <bool ALIGN8>
+__global__ __launch_bounds__(256) void k_ham_decode_soft(const int8_t *llr, long long n_blocks, uint8_t *out) {
+    for (long long b = (long long)blockIdx.x * 256 + threadIdx.x; b < n_blocks; b += (long long)gridDim.x * 256)
+        ham_soft_decode_to<ALIGN8>(llr + b * 56, out + b * 4);
+}
+hipError_t run_ham_decode_soft(const int8_t *llr, long long n_bits, uint8_t *out, hipStream_t st) {
+    const long long blocks = n_bits / 56;
+    if (blocks <= 0) return hipSuccess;
+    if ((reinterpret_cast<uintptr_t>(llr) & 7) == 0)
+        hipLaunchKernelGGL(k_ham_decode_soft<true>, dim3(grid_for(blocks, 256)), dim3(256), 0, st, llr, blocks, out);
+    else
+        hipLaunchKernelGGL(k_ham_decode_soft<false>, dim3(grid_for(blocks, 256)), dim3(256), 0, st, llr, blocks, out);
+    return hipGetLastError();
+}
+
 // ---- channel (src/channel.rs:33-74), the loop-back test bench: FIR CHANNEL, optional CFO, uniform "noise" scaled by the
 // complex pseudo-variance.  One 256-thread workgroup per frame, two sweeps: (1) y = convolve(tx, h) * exp(+j f (i + 1)),
 // written to its place in the slot, with sum(y) and sum(y^2) reduced over the workgroup in f64 (variance = sum((mean - y)^2) / n

@@ -16,7 +16,7 @@ extern "C" __device__ float __ocml_atan2pi_f32(float, float); // atan2(y, x) / p
 
 namespace ofdm {
 
-enum { M_FFT = 0, M_IFFT = 1, M_IFFT_CP = 2, M_DEMOD = 3, M_CHEST = 4, M_TX = 5 };
+enum { M_FFT = 0, M_IFFT = 1, M_IFFT_CP = 2, M_DEMOD = 3, M_CHEST = 4, M_TX = 5, M_LLR = 6 };
 
 template <int T> __device__ __forceinline__ float symbol_sum(float x, float *red, int slot, int t) {
     // sum over the T threads of one symbol
@@ -44,7 +44,9 @@ __global__ __launch_bounds__(Plan<N>::WG) void k_sym(SymParams p) {
     constexpr int K = N / 64; // carrier-map tiling factor (EXT-4)
 
     __shared__ cf lds[G * P::LDS_SYM];
-    __shared__ unsigned char idx_lds[(MODE == M_DEMOD) ? G * N : 4];
+    constexpr bool RX = (MODE == M_DEMOD || MODE == M_LLR); // the receive body; M_LLR adds the LLR epilogue
+    __shared__ unsigned char idx_lds[RX ? G * N : 4];
+    __shared__ __align__(16) int8_t llr_lds[(MODE == M_LLR) ? G * N * 8 : 16]; // M_LLR: a symbol's LLRs (<= N points x 8 bits)
     __shared__ float red[(T > 64) ? G * (T / 64) : 1];
     __shared__ __align__(4) unsigned char txb[(MODE == M_TX) ? G * (N + 8) : 4]; // TX: the symbol's slice of the byte stream
 
@@ -218,7 +220,7 @@ __global__ __launch_bounds__(Plan<N>::WG) void k_sym(SymParams p) {
 #pragma unroll
             for (int m = 0; m < 8; ++m) v[m] = pre[m];
             fetch(base + (long long)gridDim.x * G + slot, pre); // issue the next symbol's loads now
-            if (MODE == M_DEMOD && p.f_delta && valid) {
+            if (RX && p.f_delta && valid) {
                 const long long n0 = (long long)(p.first_symbol + k) * p.in_sym_stride + p.in_skip;
                 const double turns = p.f_delta[f] * 0.15915494309189533577; // 1/(2 pi)
                 cf ph = cfo_phasor(turns, n0 + t), st = cfo_phasor(turns, T);
@@ -226,7 +228,7 @@ __global__ __launch_bounds__(Plan<N>::WG) void k_sym(SymParams p) {
                 for (int m = 0; m < 8; ++m) { v[m] = cmul(v[m], ph); ph = cmul(ph, st); }
             }
         }
-        if (MODE == M_DEMOD && valid && p.nsym_frame && k >= p.nsym_frame[f]) {
+        if (RX && valid && p.nsym_frame && k >= p.nsym_frame[f]) {
             // this frame holds fewer symbols (short capture / failed sync): nothing is written for it
 #pragma unroll
             for (int m = 0; m < 8; ++m) v[m] = make_float2(0.f, 0.f);
@@ -266,18 +268,39 @@ __global__ __launch_bounds__(Plan<N>::WG) void k_sym(SymParams p) {
                     if ((t & (W - 1)) == 0) atomicMax(p.frame_max + f, __float_as_uint(mine));
                 }
             }
-        } else if (MODE == M_DEMOD) {
+        } else if (RX) {
             const bool live = valid && !(p.nsym_frame && k >= p.nsym_frame[f]);
             const int nd = p.guard ? 48 * K : N;
+            float hn[MODE == M_LLR ? 8 : 1]; // M_LLR: |H|^2 of the eight bins
             // equalise: Y[k] /= H[k] (src/receiver.rs:68-70)
             if (p.hk && live) {
                 const cf *h = p.hk + f * p.hk_stride;
 #pragma unroll
                 for (int m = 0; m < 8; ++m) {
                     cf hh = h[t + m * T];
-                    const float rn = __builtin_amdgcn_rcpf(hh.x * hh.x + hh.y * hh.y); // as k_rxframe64 (1 ulp)
+                    const float n2 = hh.x * hh.x + hh.y * hh.y;
+                    if (MODE == M_LLR) hn[m] = n2;
+                    const float rn = __builtin_amdgcn_rcpf(n2); // as k_rxframe64 (1 ulp)
                     cf q = cmulc(v[m], hh);
                     v[m] = make_float2(q.x * rn, q.y * rn);
+                }
+            }
+            // M_LLR: s_k = scale w_k, w_k = |H_k|^2 / mean over the data bins of |H|^2 (1 without H); one symbol_sum per symbol
+            float sk[MODE == M_LLR ? 8 : 1];
+            if (MODE == M_LLR) {
+                if (p.hk) {
+                    float acc = 0.f;
+#pragma unroll
+                    for (int m = 0; m < 8; ++m) {
+                        if (!live) hn[m] = 0.f;
+                        if (carrier_class64(c0 + 8 * m, p.guard) == 0) acc += hn[m];
+                    }
+                    const float wm = p.llr_scale * (float)nd / symbol_sum<T>(acc, red, slot, t);
+#pragma unroll
+                    for (int m = 0; m < 8; ++m) sk[m] = wm * hn[m];
+                } else {
+#pragma unroll
+                    for (int m = 0; m < 8; ++m) sk[m] = p.llr_scale;
                 }
             }
             // decode_block (src/receiver.rs:106-145): mean pilot angle, rotate the data points by -phase
@@ -295,6 +318,7 @@ __global__ __launch_bounds__(Plan<N>::WG) void k_sym(SymParams p) {
             }
             // demodulate (src/receiver.rs:147-190): hard decision per data bin -> LDS (ordinal order)
             unsigned char *ib = idx_lds + slot * N;
+            int8_t *lb = llr_lds + slot * N * 8;
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
                 int c = c0 + 8 * m;
@@ -302,11 +326,22 @@ __global__ __launch_bounds__(Plan<N>::WG) void k_sym(SymParams p) {
                     int q = p.guard ? data_classes_below64(c) * K + (t % K) : (t + m * T);
                     ib[q] = (unsigned char)demap_point(v[m], p.bps);
                     if (p.soft && live) p.soft[(f * p.syms_per_frame + k) * (long long)nd + q] = v[m];
+                    if (MODE == M_LLR) llr_point(v[m], p.bps, sk[m], lb + q * p.bps);
                 }
             }
             group_sync<T>();
+            if (MODE == M_LLR && live) {
+                // the symbol's nd * bps LLRs (a multiple of 16 bytes) leave in 16-byte stores when the rows allow it
+                const int nl = nd * p.bps;
+                int8_t *dst = p.llr + f * p.llr_stride + (long long)k * nl;
+                if (((reinterpret_cast<uintptr_t>(p.llr) | (uintptr_t)p.llr_stride) & 15) == 0) {
+                    for (int i = t; i < nl / 16; i += T) reinterpret_cast<uint4 *>(dst)[i] = reinterpret_cast<const uint4 *>(lb)[i];
+                } else {
+                    for (int i = t; i < nl; i += T) dst[i] = lb[i];
+                }
+            }
             // pack bps-bit indices LSB-first into bytes (src/utils.rs:30-36) and write whole dwords
-            if (live) {
+            if (live && (MODE == M_DEMOD || p.out_bytes)) {
                 const int nbytes = nd * p.bps / 8;
                 unsigned char *dst = p.out_bytes + f * p.out_stride + (long long)k * nbytes;
                 if ((nbytes & 3) == 0 && (p.out_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(p.out_bytes) & 3) == 0) {
@@ -348,7 +383,7 @@ template <int N, int MODE> static hipError_t launch_sym(const SymParams &p, hipS
     long long groups = (total + P::G - 1) / P::G;
     long long cap = (long long)num_cu * 8; // persistent: ~8 workgroups per CU, grid-stride over symbol groups
     int grid = (int)(groups < cap ? groups : cap);
-    static const char *const names[] = {"k_sym<fft>", "k_sym<ifft>", "k_sym<ifft_cp>", "k_sym<demod>", "k_sym<chest>", "k_sym<tx>"};
+    static const char *const names[] = {"k_sym<fft>", "k_sym<ifft>", "k_sym<ifft_cp>", "k_sym<demod>", "k_sym<chest>", "k_sym<tx>", "k_sym<llr>"};
     trace_add(p.trace, names[MODE]);
     hipLaunchKernelGGL((k_sym<N, MODE>), dim3(grid), dim3(P::WG), 0, st, p);
     return hipGetLastError();
@@ -374,5 +409,6 @@ hipError_t run_ifft_cp(int n, const SymParams &p, hipStream_t st, int cu) { retu
 hipError_t run_demod(int n, const SymParams &p, hipStream_t st, int cu) { return dispatch_n<M_DEMOD>(n, p, st, cu); }
 hipError_t run_chest(int n, const SymParams &p, hipStream_t st, int cu) { return dispatch_n<M_CHEST>(n, p, st, cu); }
 hipError_t run_tx_symbols(int n, const SymParams &p, hipStream_t st, int cu) { return dispatch_n<M_TX>(n, p, st, cu); }
+hipError_t run_llr(int n, const SymParams &p, hipStream_t st, int cu) { return dispatch_n<M_LLR>(n, p, st, cu); }
 
 } // namespace ofdm

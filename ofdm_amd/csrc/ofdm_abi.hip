@@ -244,7 +244,7 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
     default: return OFDM_ERR_INVALID;
     }
     if (p->guard_bands != 0 && p->guard_bands != 1) return OFDM_ERR_INVALID;
-    if (p->ecc != OFDM_ECC_NONE && p->ecc != OFDM_ECC_HAMMING74) return OFDM_ERR_INVALID;
+    if (p->ecc != OFDM_ECC_NONE && p->ecc != OFDM_ECC_HAMMING74 && p->ecc != OFDM_ECC_HAMMING74_SOFT) return OFDM_ERR_INVALID;
     if (p->sync_window_reps < 1 || p->sync_window_reps > 3) return OFDM_ERR_INVALID;
     if (p->sync_backoff < 0 || p->sync_backoff > p->cp_len) return OFDM_ERR_INVALID;
     if (p->cfo_mode < OFDM_CFO_OFF || p->cfo_mode > OFDM_CFO_ABS) return OFDM_ERR_INVALID;
@@ -435,7 +435,7 @@ int ofdm_data_carriers(const ofdm_ctx *c) { return c ? c->carriers() : OFDM_ERR_
 int ofdm_bytes_per_symbol(const ofdm_ctx *c) { return c ? c->bytes_per_symbol() : OFDM_ERR_INVALID; }
 int64_t ofdm_coded_len(const ofdm_ctx *c, int64_t payload_bytes) {
     if (!c || payload_bytes < 0) return OFDM_ERR_INVALID;
-    return c->prm.ecc == OFDM_ECC_HAMMING74 ? ((payload_bytes + 3) / 4) * 7 : payload_bytes;
+    return c->prm.ecc != OFDM_ECC_NONE ? ((payload_bytes + 3) / 4) * 7 : payload_bytes; // the soft decoder reads the same code
 }
 int64_t ofdm_data_symbols(const ofdm_ctx *c, int64_t payload_bytes) {
     if (!c || payload_bytes < 0) return OFDM_ERR_INVALID;
@@ -554,6 +554,14 @@ int ofdm_hamming74_decode(ofdm_ctx *c, const uint8_t *in, int64_t n_bytes, uint8
     DeviceGuard dev_guard(c->device);
     c->trace.reset();
     HIP_TRY(c, run_ham_decode(in, n_bytes, out, corrected, c->stream));
+    return OFDM_OK;
+}
+int ofdm_hamming74_decode_soft(ofdm_ctx *c, const int8_t *llr, int64_t n_bits, uint8_t *out) {
+    if (!c || n_bits < 0 || (n_bits >= 56 && (!llr || !out))) return OFDM_ERR_INVALID;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    c->trace.add("k_ham_decode_soft");
+    HIP_TRY(c, run_ham_decode_soft(llr, n_bits, out, c->stream));
     return OFDM_OK;
 }
 
@@ -749,6 +757,35 @@ int ofdm_rx_demod_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int6
                      out_stride, reinterpret_cast<float2 *>(soft));
 }
 
+// int8 max-log LLRs in place of the hard bytes of ofdm_rx_demod_batch: k_sym<llr> (no shape-specialised kernel has the epilogue yet)
+static int llr_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len, int first_symbol,
+                   int syms_per_frame, const int32_t *offset, const double *f_delta, const int32_t *nsym_frame, const float2 *hk,
+                   int64_t hk_stride, float llr_scale, int8_t *llr, int64_t llr_stride, uint8_t *hard, int64_t hard_stride, bool trace) {
+    SymParams p = base_params(c);
+    if (!trace) p.trace = nullptr;
+    p.in = in; p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
+    p.first_symbol = first_symbol; p.syms_per_frame = syms_per_frame; p.in_sym_stride = c->S(); p.in_skip = c->prm.cp_len;
+    p.offset = offset; p.f_delta = f_delta; p.nsym_frame = nsym_frame;
+    p.hk = hk; p.hk_stride = hk_stride; p.out_bytes = hard; p.out_stride = hard_stride;
+    p.llr = llr; p.llr_scale = llr_scale; p.llr_stride = llr_stride;
+    HIP_TRY(c, run_llr(c->prm.n_fft, p, c->stream, c->num_cu));
+    return OFDM_OK;
+}
+int ofdm_rx_llr_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                      int32_t first_symbol, int32_t syms_per_frame, const int32_t *offset, const double *f_delta,
+                      const ofdm_fc32 *hk, int64_t hk_stride, float llr_scale, int8_t *llr, int64_t llr_stride) {
+    if (!c || n_frames < 0 || syms_per_frame < 0 || first_symbol < 0 || frame_len <= 0) return OFDM_ERR_INVALID;
+    if (!(llr_scale > 0.f && llr_scale <= 3.402823466e38f)) return OFDM_ERR_INVALID; // finite and > 0 (NaN fails both)
+    if (n_frames && syms_per_frame && (!in || !llr)) return OFDM_ERR_INVALID;
+    if (llr_stride < (int64_t)syms_per_frame * c->carriers() * c->prm.modulation) return OFDM_ERR_INVALID;
+    if (hk && hk_stride != 0 && hk_stride != c->prm.n_fft) return OFDM_ERR_INVALID;
+    if (!n_frames || !syms_per_frame) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    return llr_run(c, reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, first_symbol, syms_per_frame, offset,
+                   f_delta, nullptr, reinterpret_cast<const float2 *>(hk), hk_stride, llr_scale, llr, llr_stride, nullptr, 0, true);
+}
+
 // ------------------------------------------------------------------ pipelines
 int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, int64_t payload_stride,
                          const int32_t *payload_len, int32_t payload_bytes, ofdm_fc32 *out, int64_t out_stride) {
@@ -763,7 +800,7 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
     const int S = c->S();
     const uint8_t *src = payload; int64_t src_stride = payload_stride; const int32_t *src_len = payload_len;
     int32_t src_bytes = payload_bytes;
-    if (c->prm.ecc == OFDM_ECC_HAMMING74) {
+    if (c->prm.ecc != OFDM_ECC_NONE) { // HAMMING74 and HAMMING74_SOFT transmit the same frames
         const int64_t coded = ofdm_coded_len(c, payload_bytes);
         void *cw, *cl;
         int rc = ws_get(c, 1, (size_t)(coded ? coded : 1) * (size_t)n_frames, &cw);
@@ -807,6 +844,8 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
 }
 
 namespace { struct KnownSync { int32_t d_hat; double f_delta; float metric; }; }
+// OFDM_ECC_HAMMING74_SOFT decode: the LLR workspace (one frame chunk of LLR rows) never exceeds this
+static const int64_t kSoftLlrBytes = 256ll << 20;
 static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
                           int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
                           int32_t *status, int32_t *offset, double *f_delta, float *metric, const KnownSync *known);
@@ -887,7 +926,8 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
     // 3+4. channel estimate from the 5 training blocks and per data symbol CP strip + FFT + equalise + pilot phase +
     //      demap (receiver.rs:44-83).  N = 64: one fused wave-centric kernel; otherwise the generic pair.
     bool fused = false, finished = false;
-    if (N == 1024) { // one workgroup per frame: channel estimate kept in registers, 16 x 64 FFT (kernels_fast.hip)
+    const bool soft = c->prm.ecc == OFDM_ECC_HAMMING74_SOFT; // the fused frame kernels have no LLR epilogue: the generic chain
+    if (N == 1024 && !soft) { // one workgroup per frame: channel estimate kept in registers, 16 x 64 FFT (kernels_fast.hip)
         const bool off = c->tune.no_rxframe1024 != 0; // A/B switch
         SymParams p = base_params(c);
         p.in = x; p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
@@ -900,7 +940,7 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
         if (e == hipSuccess) { fused = true; finished = fin; }
         else if (e != hipErrorNotSupported) { c->last_hip = (int)e; return OFDM_ERR_HIP; }
     }
-    if (N == 64) {
+    if (N == 64 && !soft) {
         SymParams p = base_params(c);
         p.in = x; p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
         p.offset = offs; p.f_delta = fd; p.nsym_frame = (const int32_t *)w_nsym;
@@ -921,6 +961,29 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
         p.in = x; p.out = (float2 *)w_hk; p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
         p.offset = offs; p.f_delta = fd;
         HIP_TRY(c, run_chest(N, p, c->stream, c->num_cu));
+        if (soft) {
+            // 4s + 5s. per frame chunk: hard bytes (for the header) and LLRs in one k_sym<llr>, then the header and the ML decode of
+            // the body (k_rx_finish_soft).  The LLR workspace holds one chunk: at most kSoftLlrBytes whatever n_frames is.
+            const int64_t llr_row = (int64_t)max_symbols * c->carriers() * c->prm.modulation;
+            const int64_t llr_stride = (llr_row + 15) & ~(int64_t)15;
+            int64_t chunk = c->tune.soft_chunk_frames > 0 ? c->tune.soft_chunk_frames : kSoftLlrBytes / llr_stride;
+            if (chunk < 1) chunk = 1;
+            if (chunk > n_frames) chunk = n_frames;
+            void *w_llr;
+            if ((rc = ws_get(c, 9, (size_t)(llr_stride * chunk), &w_llr))) return rc;
+            for (int64_t f0 = 0; f0 < n_frames; f0 += chunk) {
+                const int64_t nf = n_frames - f0 < chunk ? n_frames - f0 : chunk;
+                rc = llr_run(c, x + f0 * frame_stride, nf, frame_stride, frame_len, 10, max_symbols, offs + f0, fd + f0,
+                             (const int32_t *)w_nsym + f0, (const float2 *)w_hk + f0 * N, N, OFDM_SOFT_LLR_SCALE, (int8_t *)w_llr, llr_stride,
+                             (uint8_t *)w_raw + f0 * raw_stride, raw_stride, f0 == 0);
+                if (rc) return rc;
+                if (f0 == 0) c->trace.add("k_rx_finish_soft");
+                HIP_TRY(c, run_rx_finish_soft((const uint8_t *)w_raw + f0 * raw_stride, raw_stride, (const int8_t *)w_llr, llr_stride, nf,
+                                              status + f0, (const int32_t *)w_nsym + f0, bps_bytes, out + f0 * out_stride, out_stride,
+                                              out_len + f0, c->stream));
+            }
+            return OFDM_OK;
+        }
         rc = demod_run(c, x, n_frames, frame_stride, frame_len, 10, max_symbols, offs, fd, (const int32_t *)w_nsym,
                        (const float2 *)w_hk, N, (uint8_t *)w_raw, raw_stride, nullptr);
         if (rc) return rc;

@@ -19,6 +19,9 @@
 //     tx_waves, txframe_keep_steps, txframe_rewrite,                  k_txframe64 / k_txframe_mid / k_txframe4096
 //     no_txframe_optimistic
 //     scb_two_segments, scb_big_tiles                                 k_scb_chunks / k_scb_fine
+//   soft decode (OFDM_ECC_HAMMING74_SOFT)
+//     soft_chunk_frames   frames per k_sym<llr> + k_rx_finish_soft step of the decode chain (0 = as many as fit the 256 MB LLR workspace;
+//                         the tests force a few frames to walk many steps)
 //   profile build only (libofdm_hip_profile.so): ablation exits and s_memtime section timers
 //     debug_demod64, debug_sc, debug_tx
 #ifndef OFDM_TUNE_KEY
@@ -48,6 +51,7 @@ OFDM_TUNE_KEY("demod64_narrow_stores", demod64_narrow_stores, false)
 OFDM_TUNE_KEY("demod64_store_policy", demod64_store_policy, false)
 OFDM_TUNE_KEY("scb_two_segments", scb_two_segments, false)
 OFDM_TUNE_KEY("scb_big_tiles", scb_big_tiles, false)
+OFDM_TUNE_KEY("soft_chunk_frames", soft_chunk_frames, false)
 OFDM_TUNE_KEY("debug_demod64", debug_demod64, true)
 OFDM_TUNE_KEY("debug_sc", debug_sc, true)
 OFDM_TUNE_KEY("debug_tx", debug_tx, true)
