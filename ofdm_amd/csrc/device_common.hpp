@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+extern "C" __device__ float __ocml_atan2pi_f32(float, float); // atan2(y, x) / pi (ROCm device library)
+
 namespace ofdm {
 
 typedef float2 cf;
@@ -260,6 +262,14 @@ __device__ __forceinline__ unsigned demap_point_rot(cf z, cf rot, int bps) {
         return __brev(g) >> 24;
     }
     return axis_code((unsigned)fi, m) | (axis_code((unsigned)fq, m) << m);
+}
+// OR the BPS-bit field idx into a packed LSB-first image (LDS) at bit offset bo; a 6-bit field may straddle two dwords
+template <int BPS> __device__ __forceinline__ void or_field(unsigned *img, int bo, unsigned idx) {
+    const int wd = bo >> 5, sh = bo & 31;
+    atomicOr(&img[wd], idx << sh);
+    if (BPS > 1 && (32 % BPS) != 0) {
+        if (sh + BPS > 32) atomicOr(&img[wd + 1], idx >> (32 - sh));
+    }
 }
 // map a bps-bit index to a constellation point (src/transmitter.rs:108-140; levels in [-1,1])
 __device__ __forceinline__ float axis_level(unsigned bits, int m) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #ifndef OFDM_PROFILE_BUILD
 #define OFDM_PROFILE_BUILD 0 // 1 (ofdm_amd/build.py, profile=True): libofdm_hip_profile.so with the ablation / section-timing branches
@@ -59,6 +60,22 @@ struct Trace {
 };
 inline void trace_add(Trace *t, const char *name) { if (t) t->add(name); }
 
+// ---- launcher plumbing shared by the kernels_*.hip files
+// Run-time value -> template argument: calls f(std::integral_constant<int, V>{}) for the V of the list that equals v (the callee
+// reads it as decltype(V)::value); a value outside the list is hipErrorNotSupported, the launchers' "not this fast path".
+template <int... Vs, class F> hipError_t with_int(int v, F &&f) {
+    hipError_t e = hipErrorNotSupported;
+    (void)((v == Vs && ((e = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return e;
+}
+template <class F> hipError_t with_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F> hipError_t with_bps(int bps, F &&f) { return with_int<1, 2, 4, 6, 8>(bps, f); } // bits per constellation point
+// Persistent grid: one workgroup per unit of work, at most `resident` of them (workgroups per CU x CUs), at most Tuning::grid_cap
+inline long long persistent_grid(long long units, long long resident, const Tuning &tu) {
+    if (tu.grid_cap > 0 && tu.grid_cap < resident) resident = tu.grid_cap;
+    return units < resident ? units : resident;
+}
+
 // Counters of the last Schmidl-Cox search on a context (ofdm_get_tuning "stat_sc_slow_frames" / "stat_sc_redo_frames"): how many
 // frames went to the all-f64 kernel, and how many the first launch of the two-launch search left to the whole search.  `dev` is a
 // small device buffer OWNED BY THE CONTEXT ([0] slow, [1] redo): the search copies its counters there on its stream, so that the
@@ -112,7 +129,7 @@ struct SymParams {
     long long llr_stride = 0;    // bytes between per-frame LLR rows
 };
 
-// N = 64 RX-demod fast path (kernels_fast.hip)
+// N = 64 RX-demod fast path (kernels_n64.hip)
 struct Fast64Params {
     const float2 *in = nullptr;
     long long frame_stride = 0;

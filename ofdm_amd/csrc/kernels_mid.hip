@@ -1,6 +1,6 @@
 // kernels_mid.hip -- symbol-stream RX demod and TX for the transform lengths between the two headline shapes:
 // N = 64 R, R in {2, 4, 8, 16, 32} (EXT-4: N = 128 .. 2048), as an R x 64 two-stage transform, the layout k_demod4096 /
-// k_tx4096 (kernels_fast.hip) use for R = 64:
+// k_tx4096 (kernels_n4096.hip) use for R = 64:
 //     X[c + R d] = sum_b W64^(b d) * [ W_N^(b c) * sum_a x[64 a + b] W_R^(a c) ]          a, c < R;  b, d < 64
 //   stage A  the R-point transform over a for each of the 64 columns b, straight from HBM (64 consecutive columns = 512
 //            contiguous bytes per row a), eight points per lane:
@@ -21,16 +21,9 @@
 #include <stdlib.h>
 #include <type_traits>
 
-extern "C" __device__ float __ocml_atan2pi_f32(float, float); // atan2(y, x) / pi (ROCm device library)
-
 namespace ofdm {
 
 namespace {
-
-template <int CTRL> __device__ __forceinline__ float dppq(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
-}
-template <int CTRL> __device__ __forceinline__ cf dppq_cf(cf a) { return make_float2(dppq<CTRL>(a.x), dppq<CTRL>(a.y)); }
 
 template <int R> struct Mid {
     static constexpr int N = 64 * R, CP = N / 4, S = N + CP;
@@ -72,11 +65,6 @@ template <int R> struct Mid {
     }
 };
 
-template <int LPS> __device__ __forceinline__ void symbol_sync() {
-    if (LPS > 64) __syncthreads();
-    else __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
-
 // Stage A on the eight points of one lane.  In: R >= 8: v[m] = x[64 (u + Q m) + b];  R < 8: v[i R + a] = x[64 a + b_i].
 // Out: R >= 8: v[j] = Y_b[j + 8 u];  R < 8: v[i R + c] = Y_{b_i}[c]   (before the W_N^(b c) twiddle).
 template <int R, bool INV> __device__ __forceinline__ void stage_a(cf *v, const cf *tA, int u) {
@@ -102,7 +90,7 @@ template <int R, bool INV> __device__ __forceinline__ void stage_a(cf *v, const 
             const float sg = u ? -1.f : 1.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const cf o = dppq_cf<0xB1>(v[j]); // quad_perm [1,0,3,2]
+                const cf o = dpp_cf<0xB1>(v[j]); // quad_perm [1,0,3,2]
                 v[j] = make_float2(fmaf(sg, v[j].x, o.x), fmaf(sg, v[j].y, o.y));
             }
         } else if (Q == 4) { // radix-4 across the quad: Y_e = (Z_0 + (-1)^e Z_2) + W4^e (Z_1 + (-1)^e Z_3)
@@ -112,7 +100,7 @@ template <int R, bool INV> __device__ __forceinline__ void stage_a(cf *v, const 
             if (INV) ry = -ry;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const cf z0 = dppq_cf<0x00>(v[j]), z1 = dppq_cf<0x55>(v[j]), z2 = dppq_cf<0xAA>(v[j]), z3 = dppq_cf<0xFF>(v[j]);
+                const cf z0 = dpp_cf<0x00>(v[j]), z1 = dpp_cf<0x55>(v[j]), z2 = dpp_cf<0xAA>(v[j]), z3 = dpp_cf<0xFF>(v[j]);
                 const cf pe = make_float2(fmaf(s2, z2.x, z0.x), fmaf(s2, z2.y, z0.y));
                 const cf po = make_float2(fmaf(s2, z3.x, z1.x), fmaf(s2, z3.y, z1.y));
                 v[j] = make_float2(fmaf(-ry, po.y, fmaf(rx, po.x, pe.x)), fmaf(ry, po.x, fmaf(rx, po.y, pe.y)));
@@ -326,7 +314,7 @@ __global__ __launch_bounds__(256, Mid<R>::OCC_RX - (FRAME ? 1 : 0)) void k_demod
             const int col = R >= 8 ? colA : colA + LPS * (e / R);
             T[(g * R + slot) * TS + col] = (R < 8 && e % R == 0) ? v[e] : cmul(v[e], z[e]);
         }
-        symbol_sync<LPS>(); // T complete; the PREVIOUS step's image complete (two synchronisations per step, not three: as k_demod4096)
+        group_sync<LPS>(); // T complete; the PREVIOUS step's image complete (two synchronisations per step, not three: as k_demod4096)
         if (pending) flush(pending); // ... so it leaves for HBM here and is cleared for this step's fields, which are written behind the next one
         pending = mine;
         // ---- stage B: FFT64 over b for row cB
@@ -370,7 +358,7 @@ __global__ __launch_bounds__(256, Mid<R>::OCC_RX - (FRAME ? 1 : 0)) void k_demod
         // (no guard bands, or a symbol inside one wavefront) one stands here.  Nothing closes the step: the image is read only behind
         // the next step's first synchronisation, T is rewritten only by wavefronts that are past this one (every stage-B read of T
         // lies before it), the pilot sums only behind the next step's first.
-        if (!GUARD || LPS <= 64) symbol_sync<LPS>();
+        if (!GUARD || LPS <= 64) group_sync<LPS>();
         // demodulate (src/receiver.rs:147-190) and pack LSB-first (src/utils.rs:30-36): OR every field into the image
         // A dead symbol (past the batch, or k >= nsym_frame[f]) must leave the image untouched: nothing flushes (and clears) it
         // after such a step, and demap_point(0) is not 0 for BPS >= 2 -- stale bits would be OR-ed into the next live symbol.
@@ -378,52 +366,24 @@ __global__ __launch_bounds__(256, Mid<R>::OCC_RX - (FRAME ? 1 : 0)) void k_demod
         for (int q = 0; q < 8; ++q) {
             if (live && boff[q] >= 0) {
                 const unsigned idx = GUARD ? demap_point_rot(v[q], rot, BPS) : demap_point(v[q], BPS);
-                const int wd = boff[q] >> 5, sh = boff[q] & 31;
-                atomicOr(&myimg[wd], idx << sh);
-                if (BPS > 1 && (32 % BPS) != 0) { // a field may straddle two dwords (only for 6-bit fields)
-                    if (sh + BPS > 32) atomicOr(&myimg[wd + 1], idx >> (32 - sh));
-                }
+                or_field<BPS>(myimg, boff[q], idx);
             }
         }
     }
-    symbol_sync<LPS>(); // the last image is complete
+    group_sync<LPS>(); // the last image is complete
     if (pending) flush(pending);
 }
 
-// Persistent grid: OCC resident workgroups per CU (39 KB of LDS each).  Tuning::grid_cap caps it (test hook: a small
-// grid makes every workgroup run many steps of the prefetch / deferred-store pipeline on a small batch).
-static long long mid_grid(long long steps, int num_cu, int occ, long long cap) {
-    long long grid = (long long)num_cu * occ;
-    if (cap > 0 && cap < grid) grid = cap;
-    return grid > steps ? steps : grid;
-}
-
-template <int R, int BPS, bool GUARD> hipError_t launch_demod_mid(const MidRxParams &p0, bool frame, hipStream_t st, int num_cu, long long cap) {
-    MidRxParams p = p0;
+// Persistent grids: OCC resident workgroups per CU (39 KB of LDS each); Tuning::grid_cap (test hook) makes every workgroup run
+// many steps of the prefetch / deferred-store pipeline on a small batch.
+template <int R, int BPS, bool GUARD, bool FRAME> hipError_t launch_demod_mid(MidRxParams p, hipStream_t st, int num_cu, const Tuning &tu) {
     constexpr int G = Mid<R>::G;
-    const long long steps = (p.total + G - 1) / G;
-    const long long grid = mid_grid(steps, num_cu, Mid<R>::OCC_RX - (frame ? 1 : 0), cap);
+    const long long grid = persistent_grid((p.total + G - 1) / G, (long long)num_cu * (Mid<R>::OCC_RX - (FRAME ? 1 : 0)), tu);
     const long long adv = grid * G;
     p.step_f = adv / p.syms_per_frame;
     p.step_k = (int)(adv - p.step_f * p.syms_per_frame);
-    if (frame) hipLaunchKernelGGL((k_demod_mid<R, BPS, GUARD, true>), dim3((unsigned)grid), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((k_demod_mid<R, BPS, GUARD, false>), dim3((unsigned)grid), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((k_demod_mid<R, BPS, GUARD, FRAME>), dim3((unsigned)grid), dim3(256), 0, st, p);
     return hipGetLastError();
-}
-template <int R> hipError_t dispatch_demod_mid(const MidRxParams &p, int bps, bool guard, bool frame, hipStream_t st, int num_cu, long long cap) {
-    switch (bps * 2 + (guard ? 1 : 0)) {
-    case 2: return launch_demod_mid<R, 1, false>(p, frame, st, num_cu, cap);
-    case 3: return launch_demod_mid<R, 1, true>(p, frame, st, num_cu, cap);
-    case 4: return launch_demod_mid<R, 2, false>(p, frame, st, num_cu, cap);
-    case 5: return launch_demod_mid<R, 2, true>(p, frame, st, num_cu, cap);
-    case 8: return launch_demod_mid<R, 4, false>(p, frame, st, num_cu, cap);
-    case 9: return launch_demod_mid<R, 4, true>(p, frame, st, num_cu, cap);
-    case 12: return launch_demod_mid<R, 6, false>(p, frame, st, num_cu, cap);
-    case 13: return launch_demod_mid<R, 6, true>(p, frame, st, num_cu, cap);
-    case 16: return launch_demod_mid<R, 8, false>(p, frame, st, num_cu, cap);
-    case 17: return launch_demod_mid<R, 8, true>(p, frame, st, num_cu, cap);
-    }
-    return hipErrorNotSupported;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -540,7 +500,7 @@ __global__ __launch_bounds__(256, Mid<R>::OCC_TX) void k_tx_mid(MidTxParams p) {
             const int col = R >= 8 ? colA : colA + LPS * (e / R);
             Tsym[slot * TS + col] = (R < 8 && e % R == 0) ? v[e] : cmul(v[e], z[e]);
         }
-        symbol_sync<LPS>(); // T complete; every lane of the symbol is past the mapping stage
+        group_sync<LPS>(); // T complete; every lane of the symbol is past the mapping stage
         sbw[l] = d0;        // next symbol's bytes
         sbw[l + LPS] = d1;
         fetch(sg + 2 * stride, d0, d1);
@@ -549,13 +509,13 @@ __global__ __launch_bounds__(256, Mid<R>::OCC_TX) void k_tx_mid(MidTxParams p) {
         stage_b<true>(v, buf, t, wr, w);
         // v[q] = N x[cB + R (t + 8 q)]: through T once more in sample order ([n >> 6][n & 63]) so that every store is a
         // full 16 bytes per lane
-        symbol_sync<LPS>(); // every lane has read its stage-B inputs out of T
+        group_sync<LPS>(); // every lane has read its stage-B inputs out of T
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const int n = cB + R * (t + 8 * q);
             Tsym[M::t2_index(n)] = make_float2(v[q].x * (1.0f / N), v[q].y * (1.0f / N));
         }
-        symbol_sync<LPS>();
+        group_sync<LPS>();
         if (sg < p.n_sym) { // prefix_block: out = [x[N - CP .. N), x[0 .. N)]
             float4 *dst4 = reinterpret_cast<float4 *>(p.out + sg * S);
 #pragma unroll
@@ -566,16 +526,14 @@ __global__ __launch_bounds__(256, Mid<R>::OCC_TX) void k_tx_mid(MidTxParams p) {
                 if (j == 3) dst4[i - ((N - CP) >> 1)] = y;                   // n >= N - CP: the cyclic prefix
             }
         }
-        symbol_sync<LPS>(); // sbw / T are reused by the next step
+        group_sync<LPS>(); // sbw / T are reused by the next step
     }
 }
 
-template <int R> hipError_t launch_tx_mid(const MidTxParams &p, bool guard, hipStream_t st, int num_cu, long long cap) {
+template <int R, bool GUARD> hipError_t launch_tx_mid(const MidTxParams &p, hipStream_t st, int num_cu, const Tuning &tu) {
     constexpr int G = Mid<R>::G;
-    const long long steps = (p.n_sym + G - 1) / G;
-    const long long grid = mid_grid(steps, num_cu, Mid<R>::OCC_TX, cap);
-    if (guard) hipLaunchKernelGGL((k_tx_mid<R, true>), dim3((unsigned)grid), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((k_tx_mid<R, false>), dim3((unsigned)grid), dim3(256), 0, st, p);
+    const long long grid = persistent_grid((p.n_sym + G - 1) / G, (long long)num_cu * Mid<R>::OCC_TX, tu);
+    hipLaunchKernelGGL((k_tx_mid<R, GUARD>), dim3((unsigned)grid), dim3(256), 0, st, p);
     return hipGetLastError();
 }
 
@@ -689,7 +647,7 @@ __global__ __launch_bounds__(256, (R <= 8 && KEEP == 0) ? 4 : 3) void k_txframe_
             sbw[l] = word(pr.d0, sb0 + 4 * l, 4 * l < sym_bytes);
             sbw[l + LPS] = word(pr.d1, sb0 + 4 * (l + LPS), 4 * (l + LPS) < sym_bytes);
         }
-        symbol_sync<LPS>();
+        group_sync<LPS>();
         long long left = 16 + len - (long long)k * sym_bytes;   // stream bytes that belong to this symbol
         left = left < 0 ? 0 : (left < sym_bytes ? left : sym_bytes);
         const int live_bits = valid ? (int)(((unsigned)left * 8u + (unsigned)p.bps - 1u) / (unsigned)p.bps) * p.bps : 0; // left <= 2048
@@ -704,12 +662,12 @@ __global__ __launch_bounds__(256, (R <= 8 && KEEP == 0) ? 4 : 3) void k_txframe_
             const int col = R >= 8 ? colA : colA + LPS * (e / R);
             Tsym[slot * TS + col] = (R < 8 && e % R == 0) ? v[e] : cmul(v[e], z[e]);
         }
-        symbol_sync<LPS>();
+        group_sync<LPS>();
 #pragma unroll
         for (int m = 0; m < 8; ++m) v[m] = T[rs * TS + t + 8 * m];
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the row reads above precede stage B's in-place writes
         stage_b<true>(v, buf, t, wr, w);
-        symbol_sync<LPS>(); // T and the byte window are free again
+        group_sync<LPS>(); // T and the byte window are free again
     };
 
     // the samples of symbol (f0 + fl, k), divided by the frame's maximum, through T into sample order and out (prefix_block: out = [x[N - CP .. N), x[0 .. N)]).
@@ -725,7 +683,7 @@ __global__ __launch_bounds__(256, (R <= 8 && KEEP == 0) ? 4 : 3) void k_txframe_
             const int n = cB + R * (t + 8 * q);
             Tsym[M::t2_index(n)] = make_float2(v[q].x * sc, v[q].y * sc);
         }
-        symbol_sync<LPS>();
+        group_sync<LPS>();
         if (valid) {
             float4 *dst4 = reinterpret_cast<float4 *>(p.out + (f0 + fl) * p.out_stride + (long long)(10 + k) * S);
 #pragma unroll
@@ -736,7 +694,7 @@ __global__ __launch_bounds__(256, (R <= 8 && KEEP == 0) ? 4 : 3) void k_txframe_
                 if (!RAW && j == 3) dst4[i - ((N - CP) >> 1)] = y;
             }
         }
-        symbol_sync<LPS>();
+        group_sync<LPS>();
     };
     // Build-once scheme, second half: every lane takes back exactly the four sample pairs IT stored for symbol (f0 + fl, k) -- they
     // are minutes old in L2 / the memory-side cache --, divides them by the frame's maximum (the same two roundings as the
@@ -903,11 +861,7 @@ __global__ __launch_bounds__(256, (R <= 8 && KEEP == 0) ? 4 : 3) void k_txframe_
     }
 }
 
-template <int R, int KEEP> static void launch_txframe_mid_k(const MidTxFrameParams &p, bool guard, dim3 grid, hipStream_t st) {
-    if (guard) hipLaunchKernelGGL((k_txframe_mid<R, true, KEEP>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((k_txframe_mid<R, false, KEEP>), grid, dim3(256), 0, st, p);
-}
-template <int R> hipError_t launch_txframe_mid(MidTxFrameParams p, bool guard, hipStream_t st, int num_cu, long long cap, int keep_max, bool rewrite) {
+template <int R, bool GUARD> hipError_t launch_txframe_mid(MidTxFrameParams p, hipStream_t st, int num_cu, const Tuning &tu, bool rewrite) {
     constexpr int G = Mid<R>::G;
     // a frame whose symbols fit keep_max (<= 4) steps of the workgroup is built ONCE, its points kept in registers until the frame's
     // maximum is known; otherwise frames per round: the count (<= 8, <= 32 slots' worth) that wastes the fewest symbol slots of
@@ -915,7 +869,7 @@ template <int R> hipError_t launch_txframe_mid(MidTxFrameParams p, bool guard, h
     const int steps1 = (p.D + G - 1) / G;
     // (R <= 4: the optimistic two-pass form runs at four waves per SIMD and is as fast or faster -- tools/lab/enc_keep_ab.py: N = 128, D = 8:
     //  0.65 against 0.575 of the one-write roofline; N = 256, D = 8: 0.64 against 0.60; from R = 8 on the kept form is 0-3 % ahead)
-    const int keep = (steps1 <= keep_max && steps1 <= 1 && R >= 8) ? 1 : 0;   // KEEP = 2 / 4 instantiate the symbol builder 2 / 4 times: 18-170 spilled registers, not built
+    const int keep = (steps1 <= tu.txframe_keep_steps && steps1 <= 1 && R >= 8) ? 1 : 0;   // KEEP = 2 / 4 instantiate the symbol builder 2 / 4 times: 18-170 spilled registers, not built
     if (keep) p.fpw = 1;
     else {
         int best = 1; double waste = 2.0;
@@ -927,11 +881,10 @@ template <int R> hipError_t launch_txframe_mid(MidTxFrameParams p, bool guard, h
         p.fpw = best;
     }
     const long long rounds = (p.n_frames + p.fpw - 1) / p.fpw;
-    const dim3 grid((unsigned)mid_grid(rounds, num_cu, (R <= 8 && !keep && !rewrite) ? 4 : 3, cap)); // waves per SIMD the instantiation is built for
-    if (keep) launch_txframe_mid_k<R, 1>(p, guard, grid, st);
-    else if (rewrite) launch_txframe_mid_k<R, -1>(p, guard, grid, st);
-    else launch_txframe_mid_k<R, 0>(p, guard, grid, st);
-    return hipGetLastError();
+    const dim3 grid((unsigned)persistent_grid(rounds, (long long)num_cu * ((R <= 8 && !keep && !rewrite) ? 4 : 3), tu)); // waves per SIMD the instantiation is built for
+    return with_int<1, -1, 0>(keep ? 1 : rewrite ? -1 : 0, [&](auto KEEP) {
+        hipLaunchKernelGGL((k_txframe_mid<R, GUARD, decltype(KEEP)::value>), grid, dim3(256), 0, st, p);
+        return hipGetLastError(); });
 }
 
 } // namespace
@@ -953,16 +906,10 @@ hipError_t run_demod_mid(int n_fft, const SymParams &sp, hipStream_t st, int num
     p.tw = sp.tw; p.hk = sp.hk; p.hk_stride = sp.hk_stride; p.out = sp.out_bytes; p.out_stride = sp.out_stride;
     p.offset = sp.offset; p.f_delta = sp.f_delta; p.nsym_frame = sp.nsym_frame; p.frame_len = sp.frame_len;
     if (p.total <= 0) return hipSuccess;
-    const long long cap = tuning_or_default(sp.tune).grid_cap;
     trace_add(sp.trace, frame ? "k_demod_mid<frame>" : "k_demod_mid");
-    switch (R) {
-    case 2: return dispatch_demod_mid<2>(p, sp.bps, sp.guard != 0, frame, st, num_cu, cap);
-    case 4: return dispatch_demod_mid<4>(p, sp.bps, sp.guard != 0, frame, st, num_cu, cap);
-    case 8: return dispatch_demod_mid<8>(p, sp.bps, sp.guard != 0, frame, st, num_cu, cap);
-    case 16: return dispatch_demod_mid<16>(p, sp.bps, sp.guard != 0, frame, st, num_cu, cap);
-    case 32: return dispatch_demod_mid<32>(p, sp.bps, sp.guard != 0, frame, st, num_cu, cap);
-    }
-    return hipErrorNotSupported;
+    return with_int<2, 4, 8, 16, 32>(R, [&](auto RR) { return with_bps(sp.bps, [&](auto B) { return with_bool(sp.guard != 0, [&](auto G) {
+        return with_bool(frame, [&](auto F) {
+            return launch_demod_mid<decltype(RR)::value, decltype(B)::value, decltype(G)::value, decltype(F)::value>(p, st, num_cu, tuning_or_default(sp.tune)); }); }); }); });
 }
 
 // Continuous-stream TX for N in {64 .. 2048} (N = 64: R = 1, stage A is the identity and 32 symbols share a workgroup step).
@@ -978,17 +925,9 @@ hipError_t run_tx_mid(int n_fft, const SymParams &sp, hipStream_t st, int num_cu
     if (sp.n_frames <= 0) return hipSuccess;
     MidTxParams p;
     p.bytes = sp.payload; p.n_bytes = sp.tx_raw_total; p.n_sym = sp.n_frames; p.tw = sp.tw; p.out = sp.out; p.bps = sp.bps;
-    const long long cap = tuning_or_default(sp.tune).grid_cap;
     trace_add(sp.trace, "k_tx_mid");
-    switch (R) {
-    case 1: return launch_tx_mid<1>(p, sp.guard != 0, st, num_cu, cap);
-    case 2: return launch_tx_mid<2>(p, sp.guard != 0, st, num_cu, cap);
-    case 4: return launch_tx_mid<4>(p, sp.guard != 0, st, num_cu, cap);
-    case 8: return launch_tx_mid<8>(p, sp.guard != 0, st, num_cu, cap);
-    case 16: return launch_tx_mid<16>(p, sp.guard != 0, st, num_cu, cap);
-    case 32: return launch_tx_mid<32>(p, sp.guard != 0, st, num_cu, cap);
-    }
-    return hipErrorNotSupported;
+    return with_int<1, 2, 4, 8, 16, 32>(R, [&](auto RR) { return with_bool(sp.guard != 0, [&](auto G) {
+        return launch_tx_mid<decltype(RR)::value, decltype(G)::value>(p, st, num_cu, tuning_or_default(sp.tune)); }); });
 }
 
 // encode for N in {64 .. 2048}: one pass over HBM (N = 64: for the frames k_txframe64 does not take, more than 56 data
@@ -1005,21 +944,12 @@ hipError_t run_txframe_mid(int n_fft, const SymParams &sp, const float2 *header,
     p.out = sp.out; p.out_stride = sp.out_stride_s; p.bps = sp.bps;
     const Tuning &tu = tuning_or_default(sp.tune);
     p.optimistic = tu.no_txframe_optimistic ? 0 : 1;
-    const long long cap = tu.grid_cap;
-    const int keep_max = tu.txframe_keep_steps;   // 0 = always build twice (A/B)
     const int G = 32 / R, steps1 = (p.D + G - 1) / G;
-    const bool once = steps1 <= keep_max && steps1 <= 1 && R >= 8;   // (launch_txframe_mid's condition)
+    const bool once = steps1 <= tu.txframe_keep_steps && steps1 <= 1 && R >= 8;   // (launch_txframe_mid's condition; txframe_keep_steps = 0: always build twice, A/B)
     const bool rewrite = tu.txframe_rewrite != 0 && !once;
     trace_add(sp.trace, once ? "k_txframe_mid<once>" : rewrite ? "k_txframe_mid<rewrite>" : "k_txframe_mid");
-    switch (R) {
-    case 1: return launch_txframe_mid<1>(p, sp.guard != 0, st, num_cu, cap, keep_max, rewrite);
-    case 2: return launch_txframe_mid<2>(p, sp.guard != 0, st, num_cu, cap, keep_max, rewrite);
-    case 4: return launch_txframe_mid<4>(p, sp.guard != 0, st, num_cu, cap, keep_max, rewrite);
-    case 8: return launch_txframe_mid<8>(p, sp.guard != 0, st, num_cu, cap, keep_max, rewrite);
-    case 16: return launch_txframe_mid<16>(p, sp.guard != 0, st, num_cu, cap, keep_max, rewrite);
-    case 32: return launch_txframe_mid<32>(p, sp.guard != 0, st, num_cu, cap, keep_max, rewrite);
-    }
-    return hipErrorNotSupported;
+    return with_int<1, 2, 4, 8, 16, 32>(R, [&](auto RR) { return with_bool(sp.guard != 0, [&](auto G) {
+        return launch_txframe_mid<decltype(RR)::value, decltype(G)::value>(p, st, num_cu, tu, rewrite); }); });
 }
 
 } // namespace ofdm

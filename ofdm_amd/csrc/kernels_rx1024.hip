@@ -26,15 +26,9 @@
 #include "device_common.hpp"
 #include "kernels.hpp"
 
-extern "C" __device__ float __ocml_atan2pi_f32(float, float); // atan2(y, x) / pi (ROCm device library)
-
 namespace ofdm {
 
 namespace {
-
-template <int CTRL> __device__ __forceinline__ float dpp_x(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
-}
 
 struct RxFrame1024Params {
     const float2 *in;
@@ -237,7 +231,7 @@ __global__ __launch_bounds__(128, 3) void k_rxframe1024(RxFrame1024Params p) {
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             const cf e = cmul(v[c], w16tab[2 * c + u]);
-            const cf o = make_float2(dpp_x<0xB1>(e.x), dpp_x<0xB1>(e.y));   // the partner's value (lane ^ 1)
+            const cf o = make_float2(dpp8_f<0xB1>(e.x), dpp8_f<0xB1>(e.y));   // the partner's value (lane ^ 1)
             const cf y = u ? make_float2(o.x - e.x, o.y - e.y) : make_float2(e.x + o.x, e.y + o.y);
             T[(c + 8 * u) * TS + b] = cmul(y, z[c]);                          // Y_b[c' + 8 u] * W1024^(b c)
         }
@@ -291,11 +285,7 @@ __global__ __launch_bounds__(128, 3) void k_rxframe1024(RxFrame1024Params p) {
             const int bo = bo8[q];
             if (bo >= 0) {
                 const unsigned idx = GUARD ? demap_point_rot(v[q], rot, BPS) : demap_point(v[q], BPS);
-                const int wd = bo >> 5, shf = bo & 31;
-                atomicOr(&img[wd], idx << shf);
-                if (BPS > 1 && (32 % BPS) != 0) {
-                    if (shf + BPS > 32) atomicOr(&img[wd + 1], idx >> (32 - shf));
-                }
+                or_field<BPS>(img, bo, idx);
             }
         }
         if (!fused) {
@@ -367,20 +357,12 @@ hipError_t run_rxframe1024(const SymParams &sp, float2 *hk_out, hipStream_t st, 
                       sp.out_stride <= (long long)RX_RAW_DW * 4 && !tuning_or_default(sp.tune).no_rx1024_finish;
     if (fuse) { p.final_out = final_out; p.final_stride = final_stride; p.final_len = final_len; }
     if (fused_out) *fused_out = fuse;
-    long long grid = (long long)num_cu * 6;   // 22.6 KB of LDS and 167 VGPRs per 2-wavefront workgroup: six (three wavefronts per SIMD) per CU
-    { const long long cap = tuning_or_default(sp.tune).grid_cap; if (cap > 0 && cap < grid) grid = cap; }
-    if (grid > p.n_frames) grid = p.n_frames;
+    // 22.6 KB of LDS and 167 VGPRs per 2-wavefront workgroup: six (three wavefronts per SIMD) per CU
+    const long long grid = persistent_grid(p.n_frames, (long long)num_cu * 6, tuning_or_default(sp.tune));
     trace_add(sp.trace, fuse ? "k_rxframe1024<finish>" : "k_rxframe1024");
-#define OFDM_LAUNCH_RX1024(B, G) { hipLaunchKernelGGL((k_rxframe1024<B, G>), dim3((unsigned)grid), dim3(128), 0, st, p); return hipGetLastError(); }
-    switch (sp.bps * 2 + (sp.guard ? 1 : 0)) {
-    case 2: OFDM_LAUNCH_RX1024(1, false) case 3: OFDM_LAUNCH_RX1024(1, true)
-    case 4: OFDM_LAUNCH_RX1024(2, false) case 5: OFDM_LAUNCH_RX1024(2, true)
-    case 8: OFDM_LAUNCH_RX1024(4, false) case 9: OFDM_LAUNCH_RX1024(4, true)
-    case 12: OFDM_LAUNCH_RX1024(6, false) case 13: OFDM_LAUNCH_RX1024(6, true)
-    case 16: OFDM_LAUNCH_RX1024(8, false) case 17: OFDM_LAUNCH_RX1024(8, true)
-    }
-#undef OFDM_LAUNCH_RX1024
-    return hipErrorNotSupported;
+    return with_bps(sp.bps, [&](auto B) { return with_bool(sp.guard != 0, [&](auto G) {
+        hipLaunchKernelGGL((k_rxframe1024<decltype(B)::value, decltype(G)::value>), dim3((unsigned)grid), dim3(128), 0, st, p);
+        return hipGetLastError(); }); });
 }
 
 } // namespace ofdm

@@ -366,14 +366,12 @@ hipError_t launch_sc80(const ScParams &p, ScExact *exact, int32_t *slow_list, in
     q.n_lags = (int)p.n_lags; q.threshold = p.threshold;
     q.d_hat = p.d_hat; q.exact = exact; q.slow_list = slow_list; q.slow_count = slow_count;
     const Tuning &tu = tuning_or_default(p.tune);
-    long long grid = (long long)num_cu * 8;   // one wavefront per workgroup, two per SIMD; 15 KB of LDS each
-    if (tu.grid_cap > 0 && grid > tu.grid_cap) grid = tu.grid_cap;
-    const long long groups = (p.n_frames + 3) / 4;
-    if (grid > groups) grid = groups;
+    // one wavefront (four frames) per workgroup, two per SIMD; 15 KB of LDS each
+    const long long grid = persistent_grid((p.n_frames + 3) / 4, (long long)num_cu * 8, tu);
     trace_add(p.trace, "k_sc80");
-    if (tu.sc80_depth == 2) hipLaunchKernelGGL(k_sc80<2>, dim3((unsigned)grid), dim3(64), 0, st, q);
-    else hipLaunchKernelGGL(k_sc80<1>, dim3((unsigned)grid), dim3(64), 0, st, q);
-    return hipGetLastError();
+    return with_bool(tu.sc80_depth == 2, [&](auto DEEP) {
+        hipLaunchKernelGGL(k_sc80<decltype(DEEP)::value ? 2 : 1>, dim3((unsigned)grid), dim3(64), 0, st, q);
+        return hipGetLastError(); });
 }
 
 } // namespace ofdm

@@ -395,16 +395,16 @@ hipError_t run_sc_big(const ScParams &p, void *workspace, int num_cu, hipStream_
     q.d_hat = p.d_hat; q.f_delta = p.f_delta; q.metric = p.metric;
     const long long items = p.n_frames * (long long)q.tiles_per_frame;
     const size_t lds1 = contig ? (size_t)(2 * B_TILE + p.L) * sizeof(float2) : (size_t)2 * B_TILE * sizeof(float2);
-    long long g1 = (long long)num_cu * ((long long)(160 * 1024) / (long long)lds1);
-    if (tu.grid_cap > 0 && g1 > tu.grid_cap) g1 = tu.grid_cap;
-    if (g1 > items) g1 = items;
-    hipError_t e;
+    const long long g1 = persistent_grid(items, (long long)num_cu * ((long long)(160 * 1024) / (long long)lds1), tu);
     trace_add(p.trace, contig ? "k_scb_chunks<contig>" : "k_scb_chunks");
-    if (contig) {
-        if ((e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_scb_chunks<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_scb_chunks<true>, dim3((unsigned)g1), dim3(256), lds1, st, q);
-    } else hipLaunchKernelGGL(k_scb_chunks<false>, dim3((unsigned)g1), dim3(256), lds1, st, q);
-    e = hipGetLastError();
+    const hipError_t e = with_bool(contig, [&](auto CONTIG) {
+        const auto kernel = k_scb_chunks<decltype(CONTIG)::value>;
+        if (decltype(CONTIG)::value) {
+            const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
+            if (ea != hipSuccess) return ea;
+        }
+        hipLaunchKernelGGL(kernel, dim3((unsigned)g1), dim3(256), lds1, st, q);
+        return hipGetLastError(); });
     if (e != hipSuccess) return e;
     // Tiles start at chunk boundaries, so a tile is a whole number of chunks: 320-lag tiles (5 lags per thread) where C <= 320
     // (N <= 2048), 640-lag tiles for N = 4096.  The small tile halves the LDS and the registers of a frame (12 instead of 7
@@ -416,13 +416,11 @@ hipError_t run_sc_big(const ScParams &p, void *workspace, int num_cu, hipStream_
     long long per_cu = (long long)(160 * 1024) / (long long)lds;
     const long long cap = small ? 12 : 8; // 3 / 2 waves per SIMD (163 / 236 VGPRs; 4 waves spill 22 registers for +2 %)
     if (per_cu > cap) per_cu = cap;
-    long long g2 = (long long)num_cu * per_cu;
-    if (tu.grid_cap > 0 && g2 > tu.grid_cap) g2 = tu.grid_cap;
-    if (g2 > p.n_frames) g2 = p.n_frames;
+    const long long g2 = persistent_grid(p.n_frames, (long long)num_cu * per_cu, tu);
     trace_add(p.trace, small ? "k_scb_fine<5>" : "k_scb_fine<10>");
-    if (small) hipLaunchKernelGGL(k_scb_fine<5>, dim3((unsigned)g2), dim3(F_WG), lds, st, q);
-    else hipLaunchKernelGGL(k_scb_fine<10>, dim3((unsigned)g2), dim3(F_WG), lds, st, q);
-    return hipGetLastError();
+    return with_bool(small, [&](auto SMALL) {
+        hipLaunchKernelGGL(k_scb_fine<decltype(SMALL)::value ? 5 : 10>, dim3((unsigned)g2), dim3(F_WG), lds, st, q);
+        return hipGetLastError(); });
 }
 
 } // namespace ofdm

@@ -543,24 +543,19 @@ hipError_t run_sc_stream(const ScParams &p, int num_cu, hipStream_t st) {
     q.d_hat = p.d_hat; q.f_delta = p.f_delta; q.metric = p.metric;
     q.debug = kProfile ? tuning_or_default(p.tune).debug_sc : 0;
     const size_t lds = sc_stream_lds(p.L, p.W);
-    if (lds > 48 * 1024) { // > 64 KB of dynamic LDS needs the attribute; per device, so set on every such call
-        const void *fn = delay == 2 ? reinterpret_cast<const void *>(k_sc_stream<2>) : delay == 1 ? reinterpret_cast<const void *>(k_sc_stream<1>)
-                                                                                                  : reinterpret_cast<const void *>(k_sc_stream<0>);
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
     long long per_cu = (long long)(160 * 1024) / (long long)lds;
     if (per_cu > 6) per_cu = 6;   // two wavefronts per frame, built for three wavefronts per SIMD
     if (per_cu < 1) per_cu = 1;
-    long long grid = (long long)num_cu * per_cu;
-    const Tuning &tu = tuning_or_default(p.tune);
-    if (tu.grid_cap > 0 && grid > tu.grid_cap) grid = tu.grid_cap;
-    if (grid > p.n_frames) grid = p.n_frames;
-    trace_add(p.trace, delay ? "k_sc_stream<regs>" : "k_sc_stream");
-    if (delay == 2) hipLaunchKernelGGL(k_sc_stream<2>, dim3((unsigned)grid), dim3(128), lds, st, q);
-    else if (delay == 1) hipLaunchKernelGGL(k_sc_stream<1>, dim3((unsigned)grid), dim3(128), lds, st, q);
-    else hipLaunchKernelGGL(k_sc_stream<0>, dim3((unsigned)grid), dim3(128), lds, st, q);
-    return hipGetLastError();
+    const long long grid = persistent_grid(p.n_frames, (long long)num_cu * per_cu, tuning_or_default(p.tune));
+    return with_int<2, 1, 0>(delay, [&](auto DELAY) {
+        const auto kernel = k_sc_stream<decltype(DELAY)::value>;
+        if (lds > 48 * 1024) { // > 64 KB of dynamic LDS needs the attribute; per device, so set on every such call
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        trace_add(p.trace, delay ? "k_sc_stream<regs>" : "k_sc_stream");
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(128), lds, st, q);
+        return hipGetLastError(); });
 }
 
 } // namespace ofdm

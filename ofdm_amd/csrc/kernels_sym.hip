@@ -12,8 +12,6 @@
 #include "device_common.hpp"
 #include "kernels.hpp"
 
-extern "C" __device__ float __ocml_atan2pi_f32(float, float); // atan2(y, x) / pi (ROCm device library)
-
 namespace ofdm {
 
 enum { M_FFT = 0, M_IFFT = 1, M_IFFT_CP = 2, M_DEMOD = 3, M_CHEST = 4, M_TX = 5, M_LLR = 6 };
@@ -390,16 +388,8 @@ template <int N, int MODE> static hipError_t launch_sym(const SymParams &p, hipS
 }
 
 template <int MODE> static hipError_t dispatch_n(int n, const SymParams &p, hipStream_t st, int num_cu) {
-    switch (n) {
-    case 64: return launch_sym<64, MODE>(p, st, num_cu);
-    case 128: return launch_sym<128, MODE>(p, st, num_cu);
-    case 256: return launch_sym<256, MODE>(p, st, num_cu);
-    case 512: return launch_sym<512, MODE>(p, st, num_cu);
-    case 1024: return launch_sym<1024, MODE>(p, st, num_cu);
-    case 2048: return launch_sym<2048, MODE>(p, st, num_cu);
-    case 4096: return launch_sym<4096, MODE>(p, st, num_cu);
-    default: return hipErrorInvalidValue;
-    }
+    const hipError_t e = with_int<64, 128, 256, 512, 1024, 2048, 4096>(n, [&](auto N) { return launch_sym<decltype(N)::value, MODE>(p, st, num_cu); });
+    return e == hipErrorNotSupported ? hipErrorInvalidValue : e; // the generic kernel is the last resort: another length is the caller's mistake
 }
 
 hipError_t run_fft(int n, const SymParams &p, bool inverse, hipStream_t st, int cu) {

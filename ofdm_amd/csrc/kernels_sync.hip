@@ -798,13 +798,12 @@ hipError_t run_sc_fast(const ScParams &p, void *workspace, int num_cu, hipStream
     // persistent over the frames; workgroups per CU bounded by LDS (22.5 KB for a 2176-sample frame -> 7)
     const int per_cu_cap = tu.sc_wg_per_cu > 0 ? tu.sc_wg_per_cu : 7; // tuning knob
     const size_t lds = sc_cf_lds_bytes(p.L, nch ? nch : 128, stage);
-    long long per_cu = (long long)(160 * 1024) / (long long)lds;
-    if (per_cu > per_cu_cap) per_cu = per_cu_cap;
-    if (per_cu < 1) per_cu = 1;
-    long long grid = (long long)num_cu * per_cu;
-    const long long gcap = tu.grid_cap > 0 ? tu.grid_cap : (1LL << 40);
-    if (grid > gcap) grid = gcap;
-    if (grid > p.n_frames) grid = p.n_frames;
+    auto grid_of = [&](size_t lds_bytes, long long most) { // workgroups per CU: what the LDS holds, at most `most`
+        long long per_cu = (long long)(160 * 1024) / (long long)lds_bytes;
+        if (per_cu > most) per_cu = most;
+        if (per_cu < 1) per_cu = 1;
+        return persistent_grid(p.n_frames, (long long)num_cu * per_cu, tu);
+    };
     if (use80) {
         // N = 64 (L = 80, W = 240): every lag exactly, one streaming pass that stops when the peak window has closed (kernels_sc80.hip)
         if ((e = launch_sc80(p, exact, slow_list, slow_count, num_cu, st)) != hipSuccess) return e;
@@ -828,42 +827,19 @@ hipError_t run_sc_fast(const ScParams &p, void *workspace, int num_cu, hipStream
             if (stage1 > 1280) stage1 = 1280;
             q1.n16 = (int)(stage1 / 2);
             const size_t lds1 = sc_cf_lds_bytes(p.L, 128, stage1);
-            long long pc = (long long)(160 * 1024) / (long long)lds1;
-            if (pc > 10) pc = 10;
-            long long g1 = (long long)num_cu * pc;
-            if (g1 > gcap) g1 = gcap;
-            if (g1 > p.n_frames) g1 = p.n_frames;
             trace_add(p.trace, "k_sc_cf<128,first>");
-            if (tu.sc128_one_wave) { // one wavefront per frame (two chunks per lane): no idle second wavefront during the fine pass, LDS-bound 15 frames per CU
-                long long pc1 = (long long)(160 * 1024) / (long long)lds1;
-                if (pc1 > 16) pc1 = 16;
-                long long g1w = (long long)num_cu * pc1;
-                if (g1w > gcap) g1w = gcap;
-                if (g1w > p.n_frames) g1w = p.n_frames;
-                hipLaunchKernelGGL((k_sc_cf<128, 2, 4>), dim3((unsigned)g1w), dim3(64), lds1, st, q1);
-            } else
-            hipLaunchKernelGGL((k_sc_cf<128, 1, 5>), dim3((unsigned)g1), dim3(128), lds1, st, q1);
+            // one wavefront per frame (two chunks per lane): no idle second wavefront during the fine pass, LDS-bound 15 frames per CU
+            if (tu.sc128_one_wave) hipLaunchKernelGGL((k_sc_cf<128, 2, 4>), dim3((unsigned)grid_of(lds1, 16)), dim3(64), lds1, st, q1);
+            else hipLaunchKernelGGL((k_sc_cf<128, 1, 5>), dim3((unsigned)grid_of(lds1, 10)), dim3(128), lds1, st, q1);
             if ((e = hipGetLastError()) != hipSuccess) return e;
             q.frame_list = redo_list; q.frame_count = redo_count;
             trace_add(p.trace, "k_sc_cf<256,list>");
         } else trace_add(p.trace, "k_sc_cf<256>");
-        hipLaunchKernelGGL((k_sc_cf<256, 2, 4>), dim3((unsigned)grid), dim3(128), lds, st, q); // <= 7 x 2 waves per CU
+        hipLaunchKernelGGL((k_sc_cf<256, 2, 4>), dim3((unsigned)grid_of(lds, per_cu_cap)), dim3(128), lds, st, q); // <= 7 x 2 waves per CU
     } else { // 128-chunk tile (bounded searches): 128 threads, one chunk each, up to 10 workgroups per CU (measured best)
-        per_cu = (long long)(160 * 1024) / (long long)lds;
-        if (per_cu > 10) per_cu = 10;
-        grid = (long long)num_cu * per_cu;
-        if (grid > gcap) grid = gcap;
-        if (grid > p.n_frames) grid = p.n_frames;
         trace_add(p.trace, "k_sc_cf<128>");
-        if (tu.sc128_one_wave) {
-            per_cu = (long long)(160 * 1024) / (long long)lds;
-            if (per_cu > 16) per_cu = 16;
-            grid = (long long)num_cu * per_cu;
-            if (grid > gcap) grid = gcap;
-            if (grid > p.n_frames) grid = p.n_frames;
-            hipLaunchKernelGGL((k_sc_cf<128, 2, 4>), dim3((unsigned)grid), dim3(64), lds, st, q);
-        } else
-        hipLaunchKernelGGL((k_sc_cf<128, 1, 5>), dim3((unsigned)grid), dim3(128), lds, st, q);
+        if (tu.sc128_one_wave) hipLaunchKernelGGL((k_sc_cf<128, 2, 4>), dim3((unsigned)grid_of(lds, 16)), dim3(64), lds, st, q);
+        else hipLaunchKernelGGL((k_sc_cf<128, 1, 5>), dim3((unsigned)grid_of(lds, 10)), dim3(128), lds, st, q);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(k_sc_post, dim3((unsigned)((p.n_frames + 255) / 256)), dim3(256), 0, st, p.d_hat, exact, p.n_frames, p.L,

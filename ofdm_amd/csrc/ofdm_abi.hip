@@ -68,6 +68,31 @@ static SymParams base_params(ofdm_ctx *c) {
     p.guard = c->prm.guard_bands;
     return p;
 }
+// ... of a receive stream: n_frames captures of frame_len samples, frame_stride apart, each with its own (optional) trimmed start,
+// CFO and live-symbol count; out_bytes / out_stride: the per-frame rows of demodulated bytes (none for the channel estimate)
+static SymParams rx_params(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len, const int32_t *offset,
+                           const double *f_delta, const int32_t *nsym_frame = nullptr, uint8_t *out_bytes = nullptr, int64_t out_stride = 0) {
+    SymParams p = base_params(c);
+    p.in = in; p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
+    p.offset = offset; p.f_delta = f_delta; p.nsym_frame = nsym_frame;
+    p.out_bytes = out_bytes; p.out_stride = out_stride;
+    return p;
+}
+
+// What one shape-specialised path made of a call: OFDM_OK = it took it, OFDM_ERR_HIP = it failed (code in last_hip), kNextPath = it
+// declined (hipErrorNotSupported: outside its envelope, or switched off by its A/B tuning key) and the next path in line is tried.
+static const int kNextPath = 1;
+static int fast_path(ofdm_ctx *c, hipError_t e) {
+    if (e == hipSuccess) return OFDM_OK;
+    if (e == hipErrorNotSupported) return kNextPath;
+    c->last_hip = (int)e;
+    return OFDM_ERR_HIP;
+}
+#define FAST_PATH(ctx, off, call)                                                          \
+    do {                                                                                   \
+        const int _r = fast_path(ctx, (off) ? hipErrorNotSupported : (call));              \
+        if (_r != kNextPath) return _r;                                                    \
+    } while (0)
 
 extern "C" {
 
@@ -482,16 +507,10 @@ int ofdm_tx_symbols_batch(ofdm_ctx *c, const uint8_t *bytes, int64_t n_bytes, of
     p.payload = bytes; p.payload_stride = bps_bytes; p.payload_len = nullptr; p.payload_bytes = bps_bytes;
     p.tx_raw_total = n_bytes;
     p.out = reinterpret_cast<float2 *>(out); p.out_stride_s = c->S(); p.frame_max = nullptr;
-    if (c->prm.n_fft == 4096) { // 64 x 64 two-stage kernel (kernels_fast.hip)
-        hipError_t e = c->tune.no_demod4096 ? hipErrorNotSupported : run_tx4096(p, c->stream, c->num_cu); // A/B switch shared with the RX side
-        if (e == hipSuccess) return OFDM_OK;
-        if (e != hipErrorNotSupported) { c->last_hip = (int)e; return OFDM_ERR_HIP; }
-    }
-    if (c->prm.n_fft < 4096) { // R x 64 two-stage kernels (kernels_mid.hip; N = 64 is the one-row case)
-        hipError_t e = c->tune.no_mid_kernels ? hipErrorNotSupported : run_tx_mid(c->prm.n_fft, p, c->stream, c->num_cu);
-        if (e == hipSuccess) return OFDM_OK;
-        if (e != hipErrorNotSupported) { c->last_hip = (int)e; return OFDM_ERR_HIP; }
-    }
+    // 64 x 64 two-stage kernel (kernels_n4096.hip; the A/B switch is shared with the RX side)
+    if (c->prm.n_fft == 4096) FAST_PATH(c, c->tune.no_demod4096, run_tx4096(p, c->stream, c->num_cu));
+    // R x 64 two-stage kernels (kernels_mid.hip; N = 64 is the one-row case)
+    if (c->prm.n_fft < 4096) FAST_PATH(c, c->tune.no_mid_kernels, run_tx_mid(c->prm.n_fft, p, c->stream, c->num_cu));
     HIP_TRY(c, run_tx_symbols(c->prm.n_fft, p, c->stream, c->num_cu));
     return OFDM_OK;
 }
@@ -706,10 +725,8 @@ int ofdm_estimate_channel_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_fram
     if (!c || n_frames < 0 || frame_len <= 0 || (n_frames && (!in || !hk))) return OFDM_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
     c->trace.reset();
-    SymParams p = base_params(c);
-    p.in = reinterpret_cast<const float2 *>(in); p.out = reinterpret_cast<float2 *>(hk);
-    p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
-    p.offset = offset; p.f_delta = f_delta;
+    SymParams p = rx_params(c, reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, offset, f_delta);
+    p.out = reinterpret_cast<float2 *>(hk);
     HIP_TRY(c, run_chest(c->prm.n_fft, p, c->stream, c->num_cu));
     return OFDM_OK;
 }
@@ -718,26 +735,16 @@ static int demod_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t fr
                      int first_symbol, int syms_per_frame, const int32_t *offset, const double *f_delta,
                      const int32_t *nsym_frame, const float2 *hk, int64_t hk_stride, uint8_t *out, int64_t out_stride,
                      float2 *soft) {
-    SymParams p = base_params(c);
-    p.in = in; p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
+    SymParams p = rx_params(c, in, n_frames, frame_stride, frame_len, offset, f_delta, nsym_frame, out, out_stride);
     p.first_symbol = first_symbol; p.syms_per_frame = syms_per_frame; p.in_sym_stride = c->S(); p.in_skip = c->prm.cp_len;
-    p.offset = offset; p.f_delta = f_delta; p.nsym_frame = nsym_frame;
-    p.hk = hk; p.hk_stride = hk_stride; p.out_bytes = out; p.out_stride = out_stride; p.soft = soft;
-    if (c->prm.n_fft == 64) { // regular, aligned streams take the wave-centric fast path (kernels_fast.hip)
-        hipError_t e = c->tune.no_fast64 ? hipErrorNotSupported : run_demod64_fast(p, c->stream, c->num_cu);
-        if (e == hipSuccess) return OFDM_OK;
-        if (e != hipErrorNotSupported) { c->last_hip = (int)e; return OFDM_ERR_HIP; }
-    }
-    if (c->prm.n_fft == 4096) { // 64 x 64 two-stage kernel for regular streams (kernels_fast.hip)
-        hipError_t e = c->tune.no_demod4096 ? hipErrorNotSupported : run_demod4096(p, c->stream, c->num_cu); // A/B switch
-        if (e == hipSuccess) return OFDM_OK;
-        if (e != hipErrorNotSupported) { c->last_hip = (int)e; return OFDM_ERR_HIP; }
-    }
-    if (c->prm.n_fft > 64 && c->prm.n_fft < 4096) { // R x 64 two-stage kernels for regular streams (kernels_mid.hip)
-        hipError_t e = c->tune.no_mid_kernels ? hipErrorNotSupported : run_demod_mid(c->prm.n_fft, p, c->stream, c->num_cu); // A/B switch
-        if (e == hipSuccess) return OFDM_OK;
-        if (e != hipErrorNotSupported) { c->last_hip = (int)e; return OFDM_ERR_HIP; }
-    }
+    p.hk = hk; p.hk_stride = hk_stride; p.soft = soft;
+    const int N = c->prm.n_fft;
+    // regular, aligned streams take the wave-centric fast path (kernels_n64.hip)
+    if (N == 64) FAST_PATH(c, c->tune.no_fast64, run_demod64_fast(p, c->stream, c->num_cu));
+    // 64 x 64 two-stage kernel for regular streams (kernels_n4096.hip)
+    if (N == 4096) FAST_PATH(c, c->tune.no_demod4096, run_demod4096(p, c->stream, c->num_cu));
+    // R x 64 two-stage kernels for regular streams (kernels_mid.hip)
+    if (N > 64 && N < 4096) FAST_PATH(c, c->tune.no_mid_kernels, run_demod_mid(N, p, c->stream, c->num_cu));
     HIP_TRY(c, run_demod(c->prm.n_fft, p, c->stream, c->num_cu));
     return OFDM_OK;
 }
@@ -761,12 +768,10 @@ int ofdm_rx_demod_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int6
 static int llr_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len, int first_symbol,
                    int syms_per_frame, const int32_t *offset, const double *f_delta, const int32_t *nsym_frame, const float2 *hk,
                    int64_t hk_stride, float llr_scale, int8_t *llr, int64_t llr_stride, uint8_t *hard, int64_t hard_stride, bool trace) {
-    SymParams p = base_params(c);
+    SymParams p = rx_params(c, in, n_frames, frame_stride, frame_len, offset, f_delta, nsym_frame, hard, hard_stride);
     if (!trace) p.trace = nullptr;
-    p.in = in; p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
     p.first_symbol = first_symbol; p.syms_per_frame = syms_per_frame; p.in_sym_stride = c->S(); p.in_skip = c->prm.cp_len;
-    p.offset = offset; p.f_delta = f_delta; p.nsym_frame = nsym_frame;
-    p.hk = hk; p.hk_stride = hk_stride; p.out_bytes = hard; p.out_stride = hard_stride;
+    p.hk = hk; p.hk_stride = hk_stride;
     p.llr = llr; p.llr_scale = llr_scale; p.llr_stride = llr_stride;
     HIP_TRY(c, run_llr(c->prm.n_fft, p, c->stream, c->num_cu));
     return OFDM_OK;
@@ -816,21 +821,12 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
     p.n_frames = n_frames; p.syms_per_frame = (int)ofdm_data_symbols(c, payload_bytes);
     p.payload = src; p.payload_stride = src_stride; p.payload_len = src_len; p.payload_bytes = src_bytes;
     p.out = reinterpret_cast<float2 *>(out); p.out_stride_s = out_stride;
-    if (c->prm.n_fft == 64) { // one workgroup per frame, frame built in LDS, single pass over HBM
-        hipError_t fe = c->tune.no_txframe64 ? hipErrorNotSupported : run_txframe64(p, c->d_header, c->header_max, c->stream, c->num_cu);
-        if (fe == hipSuccess) return OFDM_OK;
-        if (fe != hipErrorNotSupported) { c->last_hip = (int)fe; return OFDM_ERR_HIP; }
-    }
-    if (c->prm.n_fft < 4096) { // R x 64 two-stage kernel, frames built twice: one pass over HBM (kernels_mid.hip)
-        hipError_t fe = c->tune.no_mid_kernels ? hipErrorNotSupported : run_txframe_mid(c->prm.n_fft, p, c->d_header, c->header_max, c->stream, c->num_cu);
-        if (fe == hipSuccess) return OFDM_OK;
-        if (fe != hipErrorNotSupported) { c->last_hip = (int)fe; return OFDM_ERR_HIP; }
-    }
-    if (c->prm.n_fft == 4096) { // 64 x 64 two-stage kernel, frames built twice: one pass over HBM (kernels_fast.hip)
-        hipError_t fe = c->tune.no_demod4096 ? hipErrorNotSupported : run_txframe4096(p, c->d_header, c->header_max, c->stream, c->num_cu);
-        if (fe == hipSuccess) return OFDM_OK;
-        if (fe != hipErrorNotSupported) { c->last_hip = (int)fe; return OFDM_ERR_HIP; }
-    }
+    // one workgroup per frame, frame built in LDS, single pass over HBM (kernels_n64.hip)
+    if (c->prm.n_fft == 64) FAST_PATH(c, c->tune.no_txframe64, run_txframe64(p, c->d_header, c->header_max, c->stream, c->num_cu));
+    // R x 64 two-stage kernel, frames built twice: one pass over HBM (kernels_mid.hip)
+    if (c->prm.n_fft < 4096) FAST_PATH(c, c->tune.no_mid_kernels, run_txframe_mid(c->prm.n_fft, p, c->d_header, c->header_max, c->stream, c->num_cu));
+    // 64 x 64 two-stage kernel, frames built twice: one pass over HBM (kernels_n4096.hip)
+    if (c->prm.n_fft == 4096) FAST_PATH(c, c->tune.no_demod4096, run_txframe4096(p, c->d_header, c->header_max, c->stream, c->num_cu));
     void *mx;
     int rc = ws_get(c, 0, sizeof(unsigned) * (size_t)n_frames, &mx);
     if (rc) return rc;
@@ -927,39 +923,32 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
     //      demap (receiver.rs:44-83).  N = 64: one fused wave-centric kernel; otherwise the generic pair.
     bool fused = false, finished = false;
     const bool soft = c->prm.ecc == OFDM_ECC_HAMMING74_SOFT; // the fused frame kernels have no LLR epilogue: the generic chain
-    if (N == 1024 && !soft) { // one workgroup per frame: channel estimate kept in registers, 16 x 64 FFT (kernels_fast.hip)
+    if (N == 1024 && !soft) { // one workgroup per frame: channel estimate kept in registers, 16 x 64 FFT (kernels_rx1024.hip)
         const bool off = c->tune.no_rxframe1024 != 0; // A/B switch
-        SymParams p = base_params(c);
-        p.in = x; p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
-        p.offset = offs; p.f_delta = fd; p.nsym_frame = (const int32_t *)w_nsym;
-        p.out_bytes = (uint8_t *)w_raw; p.out_stride = raw_stride;
+        const SymParams p = rx_params(c, x, n_frames, frame_stride, frame_len, offs, fd, (const int32_t *)w_nsym, (uint8_t *)w_raw, raw_stride);
         // the kernel also parses the length header, truncates and Hamming-decodes into the caller's rows when they are 4-byte aligned
         bool fin = false;
-        hipError_t e = off ? hipErrorNotSupported
-                           : run_rxframe1024(p, nullptr, c->stream, c->num_cu, out, out_stride, out_len, c->prm.ecc, &fin);
-        if (e == hipSuccess) { fused = true; finished = fin; }
-        else if (e != hipErrorNotSupported) { c->last_hip = (int)e; return OFDM_ERR_HIP; }
+        const int r = fast_path(c, off ? hipErrorNotSupported
+                                       : run_rxframe1024(p, nullptr, c->stream, c->num_cu, out, out_stride, out_len, c->prm.ecc, &fin));
+        if (r == OFDM_OK) { fused = true; finished = fin; }
+        else if (r != kNextPath) return r;
     }
     if (N == 64 && !soft) {
-        SymParams p = base_params(c);
-        p.in = x; p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
-        p.offset = offs; p.f_delta = fd; p.nsym_frame = (const int32_t *)w_nsym;
-        p.out_bytes = (uint8_t *)w_raw; p.out_stride = raw_stride;
+        SymParams p = rx_params(c, x, n_frames, frame_stride, frame_len, offs, fd, (const int32_t *)w_nsym, (uint8_t *)w_raw, raw_stride);
         p.syms_per_frame = max_symbols; // (the launcher's "is there room for a whole frame in the capture" test)
         // without an outer code the kernel also parses the length header and writes the payload to its final place
         const bool fin = c->prm.ecc == OFDM_ECC_NONE && (reinterpret_cast<uintptr_t>(out) & 3) == 0 && (out_stride & 3) == 0;
         void *w_cut;
         if ((rc = ws_get(c, 8, sizeof(int32_t) * (size_t)(n_frames + 4), &w_cut))) return rc;
-        hipError_t e = fin ? run_rxframe64(p, nullptr, c->stream, c->num_cu, out, out_stride, out_len, nullptr, nullptr, (int32_t *)w_cut)
-                           : run_rxframe64(p, nullptr, c->stream, c->num_cu, nullptr, 0, nullptr, nullptr, nullptr, (int32_t *)w_cut);
-        if (e == hipSuccess) { fused = true; finished = fin; }
-        else if (e != hipErrorNotSupported) { c->last_hip = (int)e; return OFDM_ERR_HIP; }
+        const int r = fast_path(c, fin ? run_rxframe64(p, nullptr, c->stream, c->num_cu, out, out_stride, out_len, nullptr, nullptr, (int32_t *)w_cut)
+                                       : run_rxframe64(p, nullptr, c->stream, c->num_cu, nullptr, 0, nullptr, nullptr, nullptr, (int32_t *)w_cut));
+        if (r == OFDM_OK) { fused = true; finished = fin; }
+        else if (r != kNextPath) return r;
     }
     if (!fused) {
         if ((rc = ws_get(c, 4, sizeof(float2) * (size_t)N * (size_t)n_frames, &w_hk))) return rc;
-        SymParams p = base_params(c);
-        p.in = x; p.out = (float2 *)w_hk; p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
-        p.offset = offs; p.f_delta = fd;
+        SymParams p = rx_params(c, x, n_frames, frame_stride, frame_len, offs, fd);
+        p.out = (float2 *)w_hk;
         HIP_TRY(c, run_chest(N, p, c->stream, c->num_cu));
         if (soft) {
             // 4s + 5s. per frame chunk: hard bytes (for the header) and LLRs in one k_sym<llr>, then the header and the ML decode of

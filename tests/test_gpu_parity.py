@@ -160,7 +160,7 @@ def test_rx_demod(api, orc, n, mod, guard, nsym):
 @pytest.mark.parametrize("guard", [True, False])
 @pytest.mark.parametrize("mod", [1, 2, 4, 6, 8])
 def test_rx_demod_fast64_every_instantiation(api, orc, mod, guard, hk_on):
-    """Every k_demod64<BPS, GUARD, HK> that launch_bps (kernels_fast.hip) can dispatch, reached the way the headline
+    """Every k_demod64<BPS, GUARD, HK> that run_demod64_fast (kernels_n64.hip) can dispatch, reached the way the headline
     does (no soft output, syms_per_frame % 8 == 0) and compared DIRECTLY with the oracle's bytes: 8, 16 and 24 symbols
     per frame (groups_per_frame 1, 2, 3: the blk_/step_ frame-advance arithmetic) over the same samples, many workgroups,
     and for three of the combinations enough groups (> 8192 = 256 CUs x 8 workgroups x 4 waves) that the persistent grid
@@ -259,7 +259,7 @@ def test_rx_demod_mid_every_instantiation(api, orc, n, guard):
 @pytest.mark.parametrize("guard", [True, False])
 @pytest.mark.parametrize("n", [64, 128, 256, 512, 1024, 2048, 4096])
 def test_tx_symbols_mid_every_instantiation(api, orc, n, guard):
-    """k_tx_mid<R, GUARD> (kernels_mid.hip) and k_tx4096<GUARD> (kernels_fast.hip) against the oracle's modulate + encode_block +
+    """k_tx_mid<R, GUARD> (kernels_mid.hip) and k_tx4096<GUARD> (kernels_n4096.hip) against the oracle's modulate + encode_block +
     prefix_block for every modulation: a stream that ends inside a symbol, pilot-only symbols behind it, a 2-workgroup grid
     (>= 4 steps of the byte-prefetch pipeline per workgroup).  src/transmitter.rs:40-53, 108-181."""
     import torch
