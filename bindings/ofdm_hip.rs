@@ -34,6 +34,9 @@ pub const OFDM_ECC_NONE: i32 = 0;
 pub const OFDM_ECC_HAMMING74: i32 = 1;
 // same frames on the wire as OFDM_ECC_HAMMING74; decode ML-decodes the code from int8 LLRs (include/ofdm_hip.h)
 pub const OFDM_ECC_HAMMING74_SOFT: i32 = 2;
+// K = 7 rate-1/2 convolutional code (133 / 171 octal), zero-terminated by one tail byte, Viterbi-decoded from int8 LLRs; 3 and 4 are
+// not modes (include/ofdm_hip.h)
+pub const OFDM_ECC_CONV_K7: i32 = 5;
 pub const OFDM_SOFT_LLR_SCALE: f32 = 32.0;
 
 /// The crate's own `ModulationScheme` (src/transmitter.rs:98-104) is what `encode` / `decode` keep taking.  Its `Qam` arm is
@@ -91,6 +94,10 @@ extern "C" {
     pub fn ofdm_hamming74_encode(ctx: *mut ofdm_ctx, in_dev: *const u8, n_bytes: i64, out_dev: *mut u8) -> c_int;
     pub fn ofdm_hamming74_decode(ctx: *mut ofdm_ctx, in_dev: *const u8, n_bytes: i64, out_dev: *mut u8, corrected_dev: *mut u32) -> c_int;
     pub fn ofdm_hamming74_decode_soft(ctx: *mut ofdm_ctx, llr_dev: *const i8, n_bits: i64, out_dev: *mut u8) -> c_int;
+    pub fn ofdm_conv_k7_encode(ctx: *mut ofdm_ctx, in_dev: *const u8, n_frames: i64, in_stride: i64, n_bytes: i64, out_dev: *mut u8,
+                               out_stride: i64) -> c_int;
+    pub fn ofdm_conv_k7_decode_soft(ctx: *mut ofdm_ctx, llr_dev: *const i8, n_frames: i64, llr_stride: i64, n_steps: i64,
+                                    terminated: i32, out_dev: *mut u8, out_stride: i64) -> c_int;
     pub fn ofdm_sc_correlate_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,
                                    n_lags: i64, d_hat_dev: *mut i32, f_delta_dev: *mut f64, metric_dev: *mut f32) -> c_int;
     pub fn ofdm_frequency_correction_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_pairs: i64, stride: i64,

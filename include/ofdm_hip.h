@@ -64,9 +64,12 @@ enum {
 enum { OFDM_MOD_BPSK = 1, OFDM_MOD_QPSK = 2, OFDM_MOD_QAM16 = 4, OFDM_MOD_QAM64 = 6, OFDM_MOD_QAM256 = 8 };
 /* ecc: OFDM_ECC_HAMMING74_SOFT transmits exactly what OFDM_ECC_HAMMING74 transmits (coded_len, data_symbols, frame_samples and the
  * samples of every encode entry point are the same); only decode differs: the 16-byte length header is still read from hard bits, the
- * coded body is decoded by maximum likelihood from int8 LLRs (see "soft decisions" below) instead of by syndrome.  ecc >= 3: invalid. */
-enum { OFDM_ECC_NONE = 0, OFDM_ECC_HAMMING74 = 1, OFDM_ECC_HAMMING74_SOFT = 2 };
-/* llr_scale of the OFDM_ECC_HAMMING74_SOFT decode chain (chosen from the measured BER curves) */
+ * coded body is decoded by maximum likelihood from int8 LLRs (see "soft decisions" below) instead of by syndrome.
+ * OFDM_ECC_CONV_K7: the constraint-length-7, rate-1/2 convolutional code with generators 133 / 171 (octal) of 802.11a, DVB-T and DAB,
+ * zero-terminated by one tail byte (coded_len(p) = 2 (p + 1)), decoded by the Viterbi algorithm from the same int8 LLRs (see
+ * "convolutional code" below).  The values 3 and 4 are REJECTED (OFDM_ERR_INVALID), as is every value not named here. */
+enum { OFDM_ECC_NONE = 0, OFDM_ECC_HAMMING74 = 1, OFDM_ECC_HAMMING74_SOFT = 2, OFDM_ECC_CONV_K7 = 5 };
+/* llr_scale of the OFDM_ECC_HAMMING74_SOFT and OFDM_ECC_CONV_K7 decode chains (chosen from the measured BER curves) */
 #define OFDM_SOFT_LLR_SCALE 32.0f
 enum { OFDM_CFO_OFF = 0, OFDM_CFO_SIGNED = 1, OFDM_CFO_ABS = 2 }; /* ABS = reference's abs() (receiver.rs:239) */
 /* timing / CFO detector of decode: the north star's Schmidl-Cox (default), or the reference's own pair -- cross-correlation
@@ -267,6 +270,28 @@ int ofdm_rx_llr_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, 
  * ties go to the smallest data nibble. */
 int ofdm_hamming74_decode_soft(ofdm_ctx *ctx, const int8_t *llr_dev, int64_t n_bits, uint8_t *out_dev);
 
+/* ------------------------------------------------------------------ convolutional code (north-star extension; DESIGN.md 3, EXT-2 convolutional code)
+ * K = 7, rate 1/2, generators 133 / 171 octal; the definition shared by the kernels and tests/conv_ref.py.
+ * Encoder: input bits u_t, t in [0, T): the payload bytes followed by ONE 0x00 tail byte, each byte LSB first, T = 8 (p + 1).
+ * Register r_t = (u_t << 6) | s_t, state s_t = the previous six inputs (u_{t-1} at bit 5 .. u_{t-6} at bit 0), s_0 = 0;
+ * A_t = parity(r_t & 0133), B_t = parity(r_t & 0171), s_{t+1} = r_t >> 1.  Coded stream c_{2t} = A_t, c_{2t+1} = B_t, packed LSB
+ * first: 2 (p + 1) bytes, no padding bits.  The tail byte returns the encoder to state 0.
+ * Decoder: int8 LLRs L_j, positive = bit 1, L_{2t} for A_t, L_{2t+1} for B_t.  Path metrics are maximised in exact int32 arithmetic:
+ * PM_0[0] = 0, every other state excluded at t = 0.  State s' at t + 1 has input u = s' >> 5 and predecessors p0 = (s' & 31) << 1,
+ * p1 = p0 | 1; a transition with outputs (a, b) adds (2a - 1) L_{2t} + (2b - 1) L_{2t+1}; the survivor is p1 iff its candidate is
+ * strictly larger (a tie keeps p0).  Traceback starts at state 0 when `terminated`, otherwise at the largest final metric (lowest
+ * state on a tie); u_t = s_{t+1} >> 5, output bytes packed LSB first.  That is maximum likelihood over all T-bit inputs (whose last
+ * six bits are zero when terminated).  No puncturing, no interleaver, no sliding window: the whole frame is traced back. */
+/* rows of n_bytes payload bytes -> rows of 2 * (n_bytes + 1) coded bytes (row f at in_dev + f * in_stride / out_dev + f * out_stride;
+ * in_stride >= n_bytes, out_stride >= 2 * (n_bytes + 1), OFDM_ERR_INVALID otherwise) */
+int ofdm_conv_k7_encode(ofdm_ctx *ctx, const uint8_t *in_dev, int64_t n_frames, int64_t in_stride, int64_t n_bytes,
+                        uint8_t *out_dev, int64_t out_stride);
+/* rows of 2 * n_steps LLRs -> rows of floor(n_steps / 8) bytes (a tail byte, if the caller coded one, included).  llr_stride >=
+ * 2 * n_steps, out_stride >= floor(n_steps / 8) (OFDM_ERR_INVALID otherwise); n_steps > 2^20: OFDM_ERR_UNSUPPORTED (the int32 path
+ * metrics are not renormalised).  n_steps = 0 and n_frames = 0 succeed and write nothing. */
+int ofdm_conv_k7_decode_soft(ofdm_ctx *ctx, const int8_t *llr_dev, int64_t n_frames, int64_t llr_stride, int64_t n_steps,
+                             int32_t terminated, uint8_t *out_dev, int64_t out_stride);
+
 /* ------------------------------------------------------------------ pipelines */
 
 /* encode (src/transmitter.rs:11-58) for a batch: frame f = [lock][preamble x4][training x5][data symbols],
@@ -275,7 +300,9 @@ int ofdm_hamming74_decode_soft(ofdm_ctx *ctx, const int8_t *llr_dev, int64_t n_b
  * kernels prefetch whole rows and mask afterwards): payload_stride >= payload_bytes (OFDM_ERR_INVALID otherwise when n_frames > 1),
  * and the buffer ends no earlier than the last row's payload_bytes.  Every frame is laid out for payload_bytes (D = ofdm_data_symbols(payload_bytes))
  * and written to out_dev[f*out_stride ..] (out_stride >= ofdm_frame_samples(payload_bytes)).
- * With ECC the payload is Hamming(7,4)-encoded first and the header carries the coded length (HAMMING74 and HAMMING74_SOFT alike). */
+ * With ECC the payload is Hamming(7,4)-encoded first and the header carries the coded length (HAMMING74 and HAMMING74_SOFT alike);
+ * with OFDM_ECC_CONV_K7 it is convolutionally encoded (a row of true length len_f codes to 2 (len_f + 1) bytes).  The 16-byte
+ * header itself is never coded. */
 int ofdm_tx_encode_batch(ofdm_ctx *ctx, const uint8_t *payload_dev, int64_t n_frames, int64_t payload_stride,
                          const int32_t *payload_len_dev, int32_t payload_bytes, ofdm_fc32 *out_dev,
                          int64_t out_stride);
@@ -288,7 +315,11 @@ int ofdm_tx_encode_batch(ofdm_ctx *ctx, const uint8_t *payload_dev, int64_t n_fr
  * status/offset/f_delta/metric are per-frame outputs; any of offset/f_delta/metric may be NULL.
  * ecc = OFDM_ECC_HAMMING74_SOFT (here and in every decode entry point that wraps this one: _host, _long, _long_host): the header is
  * read from hard bits as with HAMMING74, the body from LLR 128 on is ML-decoded from ofdm_rx_llr_batch's LLRs at
- * OFDM_SOFT_LLR_SCALE with the frame's channel estimate; out_len = floor(coded / 7) * 4 as with HAMMING74. */
+ * OFDM_SOFT_LLR_SCALE with the frame's channel estimate; out_len = floor(coded / 7) * 4 as with HAMMING74.
+ * ecc = OFDM_ECC_CONV_K7 (likewise in every wrapper): with keep = the header's value if it is below the demodulated body, else the
+ * body, the Viterbi decoder runs 4 * keep steps over LLRs 128 .. 128 + 8 keep of the same LLRs, terminated iff the frame was not cut
+ * short, and out_len = max(keep / 2 - 1, 0) -- the tail byte is not delivered; out_stride >= max((max_symbols * bytes_per_symbol -
+ * 16) / 2 - 1, 0).  A max_symbols whose body exceeds 2^18 bytes (2^20 trellis steps): OFDM_ERR_UNSUPPORTED. */
 int ofdm_rx_decode_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t frame_stride,
                          int64_t frame_len, int64_t n_lags, int32_t max_symbols, uint8_t *out_dev,
                          int64_t out_stride, int32_t *out_len_dev, int32_t *status_dev, int32_t *offset_dev,

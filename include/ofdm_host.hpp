@@ -154,6 +154,27 @@ class Context {
         if (!out.empty()) check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
         return out;
     }
+    // K = 7 rate-1/2 convolutional code (OFDM_ECC_CONV_K7 as the context's ecc applies it inside encode / decode; these are the bare
+    // stages): payload -> 2 (n + 1) coded bytes, and 2 n_steps int8 LLRs (positive = bit 1) -> n_steps / 8 bytes by Viterbi decoding
+    std::vector<uint8_t> conv_encode(const std::vector<uint8_t> &data) {
+        std::vector<uint8_t> out(2 * (data.size() + 1));
+        DevBuf din(ctx_, data.size()), dout(ctx_, out.size());
+        if (!data.empty()) check(ofdm_memcpy_h2d(ctx_, din.p, data.data(), data.size()), "h2d");
+        check(ofdm_conv_k7_encode(ctx_, (const uint8_t *)din.p, 1, (int64_t)data.size(), (int64_t)data.size(), (uint8_t *)dout.p,
+                                  (int64_t)out.size()), "ofdm_conv_k7_encode");
+        check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
+        return out;
+    }
+    std::vector<uint8_t> viterbi_decode_soft(const std::vector<int8_t> &llr, bool terminated = true) {
+        const int64_t n_steps = (int64_t)(llr.size() / 2);
+        std::vector<uint8_t> out((size_t)(n_steps / 8));
+        DevBuf din(ctx_, llr.size()), dout(ctx_, out.size());
+        if (!llr.empty()) check(ofdm_memcpy_h2d(ctx_, din.p, llr.data(), llr.size()), "h2d");
+        check(ofdm_conv_k7_decode_soft(ctx_, (const int8_t *)din.p, 1, 2 * n_steps, n_steps, terminated ? 1 : 0, (uint8_t *)dout.p,
+                                       (int64_t)out.size()), "ofdm_conv_k7_decode_soft");
+        if (!out.empty()) check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
+        return out;
+    }
 
   private:
     ofdm_ctx *ctx_ = nullptr;

@@ -43,7 +43,7 @@ struct Tuning {
     int scb_two_segments = 0;      // k_scb_chunks: two-segment staging also for L <= 1280
     int scb_big_tiles = 0;         // k_scb_fine: 1280-lag tiles / 128 threads
     int debug_demod64 = 0, debug_sc = 0, debug_tx = 0; // profile build only (kProfile)
-    int soft_chunk_frames = 0;     // OFDM_ECC_HAMMING74_SOFT decode: frames per k_sym<llr> + k_rx_finish_soft step (0 = the LLR workspace's 256 MB bound)
+    int soft_chunk_frames = 0;     // OFDM_ECC_HAMMING74_SOFT / OFDM_ECC_CONV_K7 decode: frames per k_sym<llr> + k_rx_finish_soft / k_viterbi_k7 step (0 = the LLR workspace's 256 MB bound)
 };
 inline const Tuning &tuning_or_default(const Tuning *t) { static const Tuning d; return t ? *t : d; }
 
@@ -285,6 +285,31 @@ hipError_t run_rx_finish_soft(const uint8_t *raw, long long raw_stride, const in
                               int32_t *out_len, hipStream_t st);
 // soft Hamming(7,4) decode of n_bits / 56 blocks of 8 codewords (ofdm_hamming74_decode_soft)
 hipError_t run_ham_decode_soft(const int8_t *llr, long long n_bits, uint8_t *out, hipStream_t st);
+
+// ---- K = 7 rate-1/2 convolutional code (OFDM_ECC_CONV_K7; kernels_conv.hip)
+// rows of n_bytes payload bytes (row f: in_len[f] of them when in_len is given) -> rows of 2 (n_bytes + 1) coded bytes; out_len
+// (optional) receives every row's own coded length 2 (len + 1)
+hipError_t run_conv_encode(const uint8_t *in, long long n_frames, long long in_stride, const int32_t *in_len, long long n_bytes,
+                           uint8_t *out, long long out_stride, int32_t *out_len, hipStream_t st);
+struct ViterbiParams {
+    const int8_t *llr = nullptr;   // row f at llr + f * llr_stride
+    long long llr_stride = 0, n_frames = 0;
+    uint8_t *out = nullptr;
+    long long out_stride = 0;
+    unsigned long long *surv = nullptr; // survivor workspace: slab_words 8-byte decision words per wavefront of the grid
+    long long slab_words = 0;
+    // stage mode (raw == nullptr): n_steps steps from LLR 0 of every row, n_steps / 8 bytes out
+    int n_steps = 0, terminated = 1;
+    // chain mode: steps, termination and out_len from the length header in the frame's hard bytes; the body starts at LLR 128
+    const uint8_t *raw = nullptr;
+    long long raw_stride = 0;
+    const int32_t *status = nullptr, *nsym = nullptr;
+    int bytes_per_symbol = 0;
+    int32_t *out_len = nullptr;
+};
+// grid (workgroups of four wavefronts) and slab size for frames of at most max_steps steps; the workspace is blocks * 4 * slab_words * 8 bytes
+void viterbi_k7_plan(long long n_frames, long long max_steps, int num_cu, const Tuning *tune, long long *blocks, long long *slab_words);
+hipError_t run_viterbi_k7(const ViterbiParams &p, long long blocks, hipStream_t st);
 
 // channel (src/channel.rs:33-74) on the GPU (kernels_bytes.hip)
 struct ChannelParams {

@@ -1,0 +1,182 @@
+// kernels_conv.hip -- the constraint-length-7, rate-1/2 convolutional code (generators 133 / 171 octal, the 802.11a / DVB-T / DAB
+// code; OFDM_ECC_CONV_K7, include/ofdm_hip.h, DESIGN.md section 3, EXT-2 convolutional code; restated in tests/conv_ref.py).
+//   k_conv_encode   one thread per coded byte: four trellis steps, ten input bits out of two payload bytes.
+//   k_viterbi_k7    one wavefront per frame, lane s = trellis state s.  Forward pass: int32 path metrics in one VGPR, the two
+//                   predecessor metrics by ds_bpermute, one survivor decision per lane and step, shifted into a dword that leaves
+//                   every 32 steps with one coalesced store into the wavefront's own survivor slab (workspace, sized by the
+//                   grid).  Traceback: one coalesced load per 32 steps, the wave-uniform state walked with v_readlane and
+//                   scalar bit tests.  Everything is exact integer arithmetic.
+#include "device_common.hpp"
+#include "kernels.hpp"
+
+namespace ofdm {
+
+constexpr unsigned kConvG0 = 0133, kConvG1 = 0171;
+
+// outputs of the encoder register r = (u_t << 6) | state: A in bit 0, B in bit 1
+__device__ __forceinline__ unsigned conv_outputs(unsigned r) {
+    return (__popc(r & kConvG0) & 1u) | ((__popc(r & kConvG1) & 1u) << 1);
+}
+
+// coded byte j of a row covers steps 4j .. 4j + 3 = input bits 4j - 6 .. 4j + 3: payload bytes j / 2 - 1 and j / 2.  Bytes at or past
+// the row's own length read 0 (the tail byte, and whatever follows it in the slot).
+__global__ __launch_bounds__(256) void k_conv_encode(const uint8_t *in, long long n_frames, long long in_stride, const int32_t *in_len,
+                                                     long long n_bytes, uint8_t *out, long long out_stride, int32_t *out_len) {
+    const long long row = 2 * (n_bytes + 1), total = n_frames * row;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long f = i / row, j = i - f * row, b = j >> 1;
+        const long long len = in_len ? row_len(in_len[f], (int)n_bytes) : n_bytes;
+        const uint8_t *src = in + f * in_stride;
+        const unsigned cur = b < len ? src[b] : 0u, prev = (b >= 1 && b - 1 < len) ? src[b - 1] : 0u;
+        const unsigned w = (cur << 8) | prev;          // bit k = input bit 8 (b - 1) + k
+        const int j0 = (int)(j & 1) * 4;
+        unsigned byte = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) byte |= conv_outputs((w >> (j0 + k + 2)) & 0x7Fu) << (2 * k);
+        out[f * out_stride + j] = (uint8_t)byte;
+        if (out_len && j == 0) out_len[f] = (int32_t)(2 * (len + 1));
+    }
+}
+hipError_t run_conv_encode(const uint8_t *in, long long n_frames, long long in_stride, const int32_t *in_len, long long n_bytes,
+                           uint8_t *out, long long out_stride, int32_t *out_len, hipStream_t st) {
+    if (n_frames <= 0) return hipSuccess;
+    const long long total = n_frames * 2 * (n_bytes + 1);
+    long long g = (total + 255) / 256;
+    if (g > 2048LL * 8) g = 2048LL * 8;
+    hipLaunchKernelGGL(k_conv_encode, dim3((unsigned)g), dim3(256), 0, st, in, n_frames, in_stride, in_len, n_bytes, out, out_stride,
+                       out_len);
+    return hipGetLastError();
+}
+
+// One frame on one wavefront (all 64 lanes active).  llr: 2 T LLRs, positive = bit 1; the first n_out <= T / 8 decoded bytes go to
+// out; surv: this wavefront's slab, 64 dwords per 32 steps.  T, terminated and n_out are wave-uniform.
+//
+// Branch metrics.  Lane = state s' at t + 1: input u = s' >> 5, predecessors p0 = (s' & 31) << 1 and p1 = p0 | 1.  Both generators
+// tap delay 0 and delay 6, so the branch from p1 carries the complement of the outputs of the branch from p0: bm(p1) = -bm(p0),
+// and bm(p0) is one of +-(La + Lb), +-(La - Lb).  The lane that fetched a step's LLR pair packs La + Lb and La - Lb into one
+// dword; a step broadcasts it with one v_readlane, every lane takes its field (v_bfe_i32 at a per-lane offset) and applies its
+// sign inside the two multiply-adds that form the candidates.
+// Survivors.  Every lane shifts its own decision bit into a dword; after 32 steps the 64 dwords leave with one 256-byte store
+// (8 bytes per step, as one 64-bit mask per step would take).  The traceback reads a block back with one load (lane = state) and
+// picks the word of the wave-uniform state with v_readlane; the block below is in flight meanwhile.
+__device__ __forceinline__ void viterbi_k7_frame(const int8_t *llr, int T, bool terminated, uint8_t *out, int n_out, unsigned *surv,
+                                                 int lane) {
+    const unsigned r0 = ((unsigned)(lane >> 5) << 6) | ((unsigned)(lane & 31) << 1);
+    const int pa = __popc(r0 & kConvG0) & 1, pb = __popc(r0 & kConvG1) & 1;   // outputs (a, b) of the branch p0 -> s'
+    const int sg = 2 * pa - 1, nsg = -sg;                 // bm(p0) = sg * (La + Lb) if a == b, sg * (La - Lb) otherwise
+    const unsigned field = pa == pb ? 16u : 0u;
+    const int a0 = (lane & 31) << 3, a1 = a0 | 4;         // ds_bpermute byte addresses of lanes p0, p1
+    int pm = lane == 0 ? 0 : -(1 << 30);                  // every state but 0 is excluded at t = 0 (T <= 2^20 steps of at most 256 each)
+    const long long last = T > 0 ? T - 1 : 0;
+    long long tl = lane < last ? lane : last;             // (clamped: the load needs no branch, steps past T are never read)
+    int la = T > 0 ? llr[2 * tl] : 0, lb = T > 0 ? llr[2 * tl + 1] : 0;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int pq = (int)(((unsigned)(la + lb) << 16) | ((unsigned)(la - lb) & 0xFFFFu));
+        tl = (long long)t0 + 64 + lane;                   // the next 64 steps' LLRs are in flight while these run
+        tl = tl < last ? tl : last;
+        la = llr[2 * tl]; lb = llr[2 * tl + 1];
+        const int pq_hi = __shfl_xor(pq, 32, 64);       // the second 32 steps, brought to lanes 0 .. 31
+        for (int h = 0; h < 64 && t0 + h < T; h += 32) {
+            const int n = __builtin_amdgcn_readfirstlane(T - t0 - h < 32 ? T - t0 - h : 32);
+            const int pqh = h ? pq_hi : pq;
+            unsigned dv = 0;
+            auto step = [&](int i) __attribute__((always_inline)) {
+                const int v = __builtin_amdgcn_sbfe(__builtin_amdgcn_readlane(pqh, i), field, 16u);
+                const int c0 = __mul24(v, sg) + __builtin_amdgcn_ds_bpermute(a0, pm);
+                const int c1 = __mul24(v, nsg) + __builtin_amdgcn_ds_bpermute(a1, pm);
+                const bool d = c1 > c0;                   // a tie keeps p0
+                pm = d ? c1 : c0;
+                dv = (dv << 1) | (d ? 1u : 0u);           // step i of an n-step block: bit n - 1 - i
+            };
+            if (n == 32) {                                // a whole block: constant trip count, unrolled (the cross-lane operations
+#pragma unroll                                            // rule out unrolling a loop of unknown length)
+                for (int i = 0; i < 32; ++i) step(i);
+            } else {
+                for (int i = 0; i < n; ++i) step(i);
+            }
+            surv[(size_t)((t0 + h) >> 5) * 64 + lane] = dv;
+        }
+    }
+    if (T <= 0) return;
+    int s = 0;
+    if (!terminated) {                                    // the largest final metric, lowest state on a tie
+        int mx = pm;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { const int v = __shfl_xor(mx, o, 64); mx = v > mx ? v : mx; }
+        s = __ffsll((long long)__ballot(pm == mx)) - 1;
+    }
+    // The state is the last six inputs (u_t = s_{t+1} >> 5), so stepping back shifts one decision in at the bottom: s_t =
+    // ((s_{t+1} & 31) << 1) | decision, i.e. the decision of step t IS u_{t-6}.  Kept in one shift register `hist` (its low six bits
+    // = the state), the walk leaves the decoded bits behind it in output order: after the block that starts at step t0, bit 6 + j
+    // of hist is u_{t0 + j}.
+    unsigned long long hist = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(s);
+    int blk = (T - 1) >> 5;
+    unsigned wv = surv[(size_t)blk * 64 + lane];
+    for (; blk >= 0; --blk) {
+        const int n = __builtin_amdgcn_readfirstlane(T - 32 * blk < 32 ? T - 32 * blk : 32);
+        const int cur = (int)wv;
+        if (blk > 0) wv = surv[(size_t)(blk - 1) * 64 + lane];
+        auto back = [&](int pos) __attribute__((always_inline)) {   // step 32 blk + n - 1 - pos: bit pos of the state's decision word
+            const unsigned word = (unsigned)__builtin_amdgcn_readlane(cur, (int)((unsigned)hist & 63u));
+            hist = (hist << 1) | ((word >> pos) & 1u);
+        };
+        if (n == 32) {
+#pragma unroll
+            for (int pos = 0; pos < 32; ++pos) back(pos);
+        } else {
+            for (int pos = 0; pos < n; ++pos) back(pos);
+        }
+        const unsigned bits = (unsigned)(hist >> 6);
+        const int b = blk * 4 + lane;
+        if (lane < 4 && b < n_out) out[b] = (uint8_t)(bits >> (8 * lane));
+    }
+}
+
+// Stage mode (raw == nullptr): every row decodes n_steps steps from its LLR 0, `terminated` as given, n_steps / 8 bytes out.
+// Chain mode: the length header is read from the frame's hard bytes exactly as k_rx_finish reads it (keep = the header's value if it
+// is below body, else body); T = 4 keep steps over LLRs 128 .. 128 + 8 keep, terminated iff the frame was not cut short, and
+// out_len = max(keep / 2 - 1, 0): the tail byte is not delivered.
+__global__ __launch_bounds__(256) void k_viterbi_k7(ViterbiParams p) {
+    const int lane = threadIdx.x & 63;
+    const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (long long)gridDim.x * 4;
+    unsigned *surv = reinterpret_cast<unsigned *>(p.surv + wave * p.slab_words);
+    for (long long f = wave; f < p.n_frames; f += n_waves) {
+        const int8_t *l = p.llr + f * p.llr_stride;
+        uint8_t *dst = p.out + f * p.out_stride;
+        if (!p.raw) {
+            viterbi_k7_frame(l, p.n_steps, p.terminated != 0, dst, p.n_steps >> 3, surv, lane);
+            continue;
+        }
+        if (p.status[f] != 0) { if (lane == 0) p.out_len[f] = 0; continue; }
+        const uint8_t *src = p.raw + f * p.raw_stride;
+        const long long body = (long long)p.nsym[f] * p.bytes_per_symbol - 16;
+        unsigned long long lo = 0, hi = 0; // bincode fixint little-endian u128 (src/packets/mod.rs:20-32)
+        for (int i = 0; i < 8; ++i) { lo |= (unsigned long long)src[i] << (8 * i); hi |= (unsigned long long)src[8 + i] << (8 * i); }
+        long long keep = (hi == 0 && lo < (unsigned long long)body) ? (long long)lo : body; // Vec::truncate
+        const bool whole = hi == 0 && lo <= (unsigned long long)body;
+        keep = __builtin_amdgcn_readfirstlane((int)keep);
+        const int n_out = keep / 2 >= 1 ? (int)(keep / 2) - 1 : 0;
+        viterbi_k7_frame(l + 128, (int)(4 * keep), __builtin_amdgcn_readfirstlane((int)whole) != 0, dst, n_out, surv, lane);
+        if (lane == 0) p.out_len[f] = n_out;
+    }
+}
+
+// Grid and slab for frames of at most max_steps steps: one survivor slab (8 bytes per step) per resident wavefront, the whole
+// survivor workspace kept under 1 GiB by running fewer wavefronts when the frames are long.
+void viterbi_k7_plan(long long n_frames, long long max_steps, int num_cu, const Tuning *tune, long long *blocks, long long *slab_words) {
+    const long long words = ((max_steps > 0 ? max_steps : 1) + 63) & ~63LL;
+    long long by_memory = (1LL << 30) / (words * 8 * 4);
+    if (by_memory < 1) by_memory = 1;
+    long long resident = 8LL * num_cu;               // 256 threads, 8 workgroups per CU: 8 wavefronts per SIMD
+    if (resident > by_memory) resident = by_memory;
+    *blocks = persistent_grid((n_frames + 3) / 4, resident, tuning_or_default(tune));
+    if (*blocks < 1) *blocks = 1;
+    *slab_words = words;
+}
+hipError_t run_viterbi_k7(const ViterbiParams &p, long long blocks, hipStream_t st) {
+    if (p.n_frames <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_viterbi_k7, dim3((unsigned)blocks), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+} // namespace ofdm

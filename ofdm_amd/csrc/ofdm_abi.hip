@@ -269,7 +269,8 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
     default: return OFDM_ERR_INVALID;
     }
     if (p->guard_bands != 0 && p->guard_bands != 1) return OFDM_ERR_INVALID;
-    if (p->ecc != OFDM_ECC_NONE && p->ecc != OFDM_ECC_HAMMING74 && p->ecc != OFDM_ECC_HAMMING74_SOFT) return OFDM_ERR_INVALID;
+    if (p->ecc != OFDM_ECC_NONE && p->ecc != OFDM_ECC_HAMMING74 && p->ecc != OFDM_ECC_HAMMING74_SOFT && p->ecc != OFDM_ECC_CONV_K7)
+        return OFDM_ERR_INVALID; // 3 and 4 are not modes
     if (p->sync_window_reps < 1 || p->sync_window_reps > 3) return OFDM_ERR_INVALID;
     if (p->sync_backoff < 0 || p->sync_backoff > p->cp_len) return OFDM_ERR_INVALID;
     if (p->cfo_mode < OFDM_CFO_OFF || p->cfo_mode > OFDM_CFO_ABS) return OFDM_ERR_INVALID;
@@ -460,6 +461,7 @@ int ofdm_data_carriers(const ofdm_ctx *c) { return c ? c->carriers() : OFDM_ERR_
 int ofdm_bytes_per_symbol(const ofdm_ctx *c) { return c ? c->bytes_per_symbol() : OFDM_ERR_INVALID; }
 int64_t ofdm_coded_len(const ofdm_ctx *c, int64_t payload_bytes) {
     if (!c || payload_bytes < 0) return OFDM_ERR_INVALID;
+    if (c->prm.ecc == OFDM_ECC_CONV_K7) return 2 * (payload_bytes + 1); // rate 1/2 over the payload and one tail byte
     return c->prm.ecc != OFDM_ECC_NONE ? ((payload_bytes + 3) / 4) * 7 : payload_bytes; // the soft decoder reads the same code
 }
 int64_t ofdm_data_symbols(const ofdm_ctx *c, int64_t payload_bytes) {
@@ -581,6 +583,40 @@ int ofdm_hamming74_decode_soft(ofdm_ctx *c, const int8_t *llr, int64_t n_bits, u
     c->trace.reset();
     c->trace.add("k_ham_decode_soft");
     HIP_TRY(c, run_ham_decode_soft(llr, n_bits, out, c->stream));
+    return OFDM_OK;
+}
+
+// int32 path metrics, not renormalised: 2^20 steps of at most 256 each stay clear of the floor of the excluded states (-2^30)
+static const int64_t kViterbiMaxSteps = 1ll << 20;
+int ofdm_conv_k7_encode(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_t in_stride, int64_t n_bytes, uint8_t *out,
+                        int64_t out_stride) {
+    if (!c || n_frames < 0 || n_bytes < 0 || in_stride < n_bytes || out_stride < 2 * (n_bytes + 1)) return OFDM_ERR_INVALID;
+    if (n_frames && (!out || (n_bytes && !in))) return OFDM_ERR_INVALID;
+    if (!n_frames) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    c->trace.add("k_conv_encode");
+    HIP_TRY(c, run_conv_encode(in, n_frames, in_stride, nullptr, n_bytes, out, out_stride, nullptr, c->stream));
+    return OFDM_OK;
+}
+int ofdm_conv_k7_decode_soft(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, int64_t llr_stride, int64_t n_steps, int32_t terminated,
+                             uint8_t *out, int64_t out_stride) {
+    if (!c || n_frames < 0 || n_steps < 0 || llr_stride < 2 * n_steps || out_stride < n_steps / 8) return OFDM_ERR_INVALID;
+    if (n_steps > kViterbiMaxSteps) return OFDM_ERR_UNSUPPORTED;
+    if (n_frames && n_steps && (!llr || (n_steps >= 8 && !out))) return OFDM_ERR_INVALID;
+    if (!n_frames || !n_steps) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    ViterbiParams p;
+    long long blocks;
+    viterbi_k7_plan(n_frames, n_steps, c->num_cu, &c->tune, &blocks, &p.slab_words);
+    void *w_surv;
+    int rc = ws_get(c, 10, (size_t)(blocks * 4 * p.slab_words) * sizeof(unsigned long long), &w_surv);
+    if (rc) return rc;
+    p.llr = llr; p.llr_stride = llr_stride; p.n_frames = n_frames; p.out = out; p.out_stride = out_stride;
+    p.surv = (unsigned long long *)w_surv; p.n_steps = (int)n_steps; p.terminated = terminated != 0;
+    c->trace.add("k_viterbi_k7");
+    HIP_TRY(c, run_viterbi_k7(p, blocks, c->stream));
     return OFDM_OK;
 }
 
@@ -805,15 +841,22 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
     const int S = c->S();
     const uint8_t *src = payload; int64_t src_stride = payload_stride; const int32_t *src_len = payload_len;
     int32_t src_bytes = payload_bytes;
-    if (c->prm.ecc != OFDM_ECC_NONE) { // HAMMING74 and HAMMING74_SOFT transmit the same frames
+    if (c->prm.ecc != OFDM_ECC_NONE) { // HAMMING74 and HAMMING74_SOFT transmit the same frames, CONV_K7 its own code
         const int64_t coded = ofdm_coded_len(c, payload_bytes);
+        if (c->prm.ecc == OFDM_ECC_CONV_K7 && coded > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED; // (payload_bytes = INT32_MAX)
         void *cw, *cl;
         int rc = ws_get(c, 1, (size_t)(coded ? coded : 1) * (size_t)n_frames, &cw);
         if (rc) return rc;
         rc = ws_get(c, 2, sizeof(int32_t) * (size_t)n_frames, &cl);
         if (rc) return rc;
-        HIP_TRY(c, run_ham_encode(payload, n_frames, payload_stride, payload_len, payload_bytes, (uint8_t *)cw, coded,
-                                  (int32_t *)cl, c->stream));
+        if (c->prm.ecc == OFDM_ECC_CONV_K7) {
+            c->trace.add("k_conv_encode");
+            HIP_TRY(c, run_conv_encode(payload, n_frames, payload_stride, payload_len, payload_bytes, (uint8_t *)cw, coded,
+                                       (int32_t *)cl, c->stream));
+        } else {
+            HIP_TRY(c, run_ham_encode(payload, n_frames, payload_stride, payload_len, payload_bytes, (uint8_t *)cw, coded,
+                                      (int32_t *)cl, c->stream));
+        }
         src = (const uint8_t *)cw; src_stride = coded; src_len = payload_len ? (const int32_t *)cl : nullptr;
         src_bytes = (int32_t)coded;
     }
@@ -869,9 +912,11 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
     const int64_t raw_bytes = (int64_t)max_symbols * bps_bytes;
     const int64_t raw_stride = (raw_bytes + 3) & ~(int64_t)3;   // rows of the raw-byte workspace start on dwords (6-byte BPSK symbols: odd counts)
     // rows must hold what k_rx_finish can write: the whole body without an outer code, floor(body / 7) * 4 bytes after
-    // Hamming(7,4) decoding (include/ofdm_hip.h)
+    // Hamming(7,4) decoding, body / 2 - 1 after Viterbi decoding (include/ofdm_hip.h)
     const int64_t body_max = raw_bytes > 16 ? raw_bytes - 16 : 0;
-    if (out_stride < (c->prm.ecc == OFDM_ECC_NONE ? body_max : (body_max / 7) * 4)) return OFDM_ERR_INVALID;
+    if (out_stride < decode_row_bytes(c, body_max)) return OFDM_ERR_INVALID;
+    const bool conv = c->prm.ecc == OFDM_ECC_CONV_K7;
+    if (conv && 4 * body_max > kViterbiMaxSteps) return OFDM_ERR_UNSUPPORTED;
     if (!n_frames) return OFDM_OK;
     DeviceGuard dev_guard(c->device);
     c->trace.reset();
@@ -922,7 +967,7 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
     // 3+4. channel estimate from the 5 training blocks and per data symbol CP strip + FFT + equalise + pilot phase +
     //      demap (receiver.rs:44-83).  N = 64: one fused wave-centric kernel; otherwise the generic pair.
     bool fused = false, finished = false;
-    const bool soft = c->prm.ecc == OFDM_ECC_HAMMING74_SOFT; // the fused frame kernels have no LLR epilogue: the generic chain
+    const bool soft = c->prm.ecc == OFDM_ECC_HAMMING74_SOFT || conv; // the fused frame kernels have no LLR epilogue: the generic chain
     if (N == 1024 && !soft) { // one workgroup per frame: channel estimate kept in registers, 16 x 64 FFT (kernels_rx1024.hip)
         const bool off = c->tune.no_rxframe1024 != 0; // A/B switch
         const SymParams p = rx_params(c, x, n_frames, frame_stride, frame_len, offs, fd, (const int32_t *)w_nsym, (uint8_t *)w_raw, raw_stride);
@@ -952,7 +997,8 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
         HIP_TRY(c, run_chest(N, p, c->stream, c->num_cu));
         if (soft) {
             // 4s + 5s. per frame chunk: hard bytes (for the header) and LLRs in one k_sym<llr>, then the header and the ML decode of
-            // the body (k_rx_finish_soft).  The LLR workspace holds one chunk: at most kSoftLlrBytes whatever n_frames is.
+            // the body (k_rx_finish_soft; OFDM_ECC_CONV_K7: k_viterbi_k7, which also needs a survivor slab per resident wavefront).
+            // The LLR workspace holds one chunk: at most kSoftLlrBytes whatever n_frames is.
             const int64_t llr_row = (int64_t)max_symbols * c->carriers() * c->prm.modulation;
             const int64_t llr_stride = (llr_row + 15) & ~(int64_t)15;
             int64_t chunk = c->tune.soft_chunk_frames > 0 ? c->tune.soft_chunk_frames : kSoftLlrBytes / llr_stride;
@@ -960,12 +1006,29 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
             if (chunk > n_frames) chunk = n_frames;
             void *w_llr;
             if ((rc = ws_get(c, 9, (size_t)(llr_stride * chunk), &w_llr))) return rc;
+            ViterbiParams vp;
+            long long v_blocks = 0;
+            if (conv) {
+                void *w_surv;
+                viterbi_k7_plan(chunk, 4 * body_max, c->num_cu, &c->tune, &v_blocks, &vp.slab_words);
+                if ((rc = ws_get(c, 10, (size_t)(v_blocks * 4 * vp.slab_words) * sizeof(unsigned long long), &w_surv))) return rc;
+                vp.surv = (unsigned long long *)w_surv;
+                vp.llr = (const int8_t *)w_llr; vp.llr_stride = llr_stride; vp.out_stride = out_stride;
+                vp.raw_stride = raw_stride; vp.bytes_per_symbol = bps_bytes;
+            }
             for (int64_t f0 = 0; f0 < n_frames; f0 += chunk) {
                 const int64_t nf = n_frames - f0 < chunk ? n_frames - f0 : chunk;
                 rc = llr_run(c, x + f0 * frame_stride, nf, frame_stride, frame_len, 10, max_symbols, offs + f0, fd + f0,
                              (const int32_t *)w_nsym + f0, (const float2 *)w_hk + f0 * N, N, OFDM_SOFT_LLR_SCALE, (int8_t *)w_llr, llr_stride,
                              (uint8_t *)w_raw + f0 * raw_stride, raw_stride, f0 == 0);
                 if (rc) return rc;
+                if (conv) {
+                    if (f0 == 0) c->trace.add("k_viterbi_k7");
+                    vp.n_frames = nf; vp.out = out + f0 * out_stride; vp.raw = (const uint8_t *)w_raw + f0 * raw_stride;
+                    vp.status = status + f0; vp.nsym = (const int32_t *)w_nsym + f0; vp.out_len = out_len + f0;
+                    HIP_TRY(c, run_viterbi_k7(vp, v_blocks, c->stream));
+                    continue;
+                }
                 if (f0 == 0) c->trace.add("k_rx_finish_soft");
                 HIP_TRY(c, run_rx_finish_soft((const uint8_t *)w_raw + f0 * raw_stride, raw_stride, (const int8_t *)w_llr, llr_stride, nf,
                                               status + f0, (const int32_t *)w_nsym + f0, bps_bytes, out + f0 * out_stride, out_stride,

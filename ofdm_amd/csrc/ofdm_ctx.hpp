@@ -30,7 +30,7 @@ struct ofdm_ctx {
     ofdm::ScStats sc_stats;             // list counters of the last Schmidl-Cox search (ofdm_get_tuning "stat_sc_*")
     int32_t *d_stats = nullptr;         // [2] their home on the device (owned by the context)
     // workspaces (grown on demand, never inside a captured region)
-    Workspace ws[10];
+    Workspace ws[11];
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     HostPipe *pipe = nullptr;     // created by the first host-buffer call, freed by ofdm_destroy
 
@@ -71,6 +71,13 @@ inline int ws_get(ofdm_ctx *c, int slot, size_t bytes, void **out) {
     return OFDM_OK;
 }
 
+// Largest out_len the decode chain can write for a frame whose body (the bytes behind the 16-byte length header) is `body` bytes:
+// the row size every decode entry point asks of its caller (include/ofdm_hip.h)
+inline int64_t decode_row_bytes(const ofdm_ctx *c, int64_t body) {
+    if (c->prm.ecc == OFDM_ECC_NONE) return body;
+    if (c->prm.ecc == OFDM_ECC_CONV_K7) return body / 2 >= 1 ? body / 2 - 1 : 0; // 4 body steps = body / 2 bytes, less the tail byte
+    return (body / 7) * 4;                                                       // Hamming(7,4), hard or soft
+}
 
 // internal cross-file helpers (C linkage only because their definitions sit inside the extern "C" blocks; not in ofdm_hip.h)
 extern "C" {

@@ -19,8 +19,8 @@
 //     tx_waves, txframe_keep_steps, txframe_rewrite,                  k_txframe64 / k_txframe_mid / k_txframe4096
 //     no_txframe_optimistic
 //     scb_two_segments, scb_big_tiles                                 k_scb_chunks / k_scb_fine
-//   soft decode (OFDM_ECC_HAMMING74_SOFT)
-//     soft_chunk_frames   frames per k_sym<llr> + k_rx_finish_soft step of the decode chain (0 = as many as fit the 256 MB LLR workspace;
+//   soft decode (OFDM_ECC_HAMMING74_SOFT, OFDM_ECC_CONV_K7)
+//     soft_chunk_frames   frames per k_sym<llr> + k_rx_finish_soft / k_viterbi_k7 step of the decode chain (0 = as many as fit the 256 MB LLR workspace;
 //                         the tests force a few frames to walk many steps)
 //   profile build only (libofdm_hip_profile.so): ablation exits and s_memtime section timers
 //     debug_demod64, debug_sc, debug_tx
