@@ -256,7 +256,8 @@ int ofdm_rx_demod_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames
  *     Lambda_b(v) = ( min_{l: bit = 0} (v - a_l)^2 - min_{l: bit = 1} (v - a_l)^2 ) / 4          POSITIVE MEANS BIT 1
  * (BPSK / QPSK: Lambda = v, the sign convention of the hard decisions; a noiseless point's weakest bit has |Lambda| = 1).
  * Channel weight w_k = |H_k|^2 / (mean of |H|^2 over the data carriers), per frame or over the shared H; w = 1 without H.
- * Stored: int8 L = clamp(rint(llr_scale * w_k * Lambda), -127, 127), 0 when the product is not finite.
+ * Stored: int8 L = clamp(rint(llr_scale * w_k * Lambda), -127, 127), 0 when the product is not finite.  The product is formed in
+ * f32: at an llr_scale near FLT_MAX it overflows and 0 is stored where exact arithmetic would clamp to +-127.
  * The true LLR is L / llr_scale * 4 mean|H|^2 / ((M - 1)^2 sigma^2), sigma^2 = the complex noise variance of a received bin; the
  * library does not estimate sigma^2. */
 /* ofdm_rx_demod_batch with int8 LLRs out instead of hard bytes: arguments as there; llr_dev[f*llr_stride ..] receives

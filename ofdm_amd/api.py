@@ -450,21 +450,28 @@ class Context:
 
     def rx_llr(self, frames: torch.Tensor, syms_per_frame: int, first_symbol: int = 0, offset: Optional[torch.Tensor] = None,
                f_delta: Optional[torch.Tensor] = None, hk: Optional[torch.Tensor] = None, frame_len: Optional[int] = None,
-               scale: float = SOFT_LLR_SCALE) -> torch.Tensor:
+               scale: float = SOFT_LLR_SCALE, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """ofdm_rx_llr_batch: rx_demod with int8 max-log LLRs out -> [n_frames, syms_per_frame * data_carriers * bps], LLR j = bit j
-        of the stream rx_demod packs LSB-first (positive = bit 1; definition in include/ofdm_hip.h)."""
+        of the stream rx_demod packs LSB-first (positive = bit 1; definition in include/ofdm_hip.h).
+        out (optional): an int8 [n_frames, that many] tensor or view whose rows are contiguous; its row stride (llr_stride) may exceed
+        the row, and neither it nor the base needs any alignment."""
         frames = self._cx(frames)
         f2 = frames.view(-1, frames.shape[-1])
         n, stride = f2.shape
         nl = syms_per_frame * self.data_carriers * self.modulation
-        out = self.empty((n, nl), torch.int8)
+        if out is None:
+            out = self.empty((n, nl), torch.int8)
+        elif out.dtype != torch.int8 or out.device != self.device or out.shape != (n, nl) or (nl > 1 and out.stride(1) != 1) or \
+                (n > 1 and out.stride(0) < nl):
+            raise OfdmError("rx_llr: out must be an int8 [n_frames, syms_per_frame * data_carriers * bps] tensor with contiguous rows on the context's device")
+        llr_stride = out.stride(0) if n > 1 else nl
         hk_stride = 0
         if hk is not None:
             hk = self._cx(hk)
             hk_stride = self.n_fft if hk.dim() == 2 else 0  # [n_frames, N] per frame, [N] shared
             assert hk.shape[-1] == self.n_fft and (hk.dim() == 1 or hk.shape[0] == n)
         self._ck(self.lib.ofdm_rx_llr_batch(self.h, _dev(f2), n, stride, stride if frame_len is None else frame_len, first_symbol,
-                                            syms_per_frame, _dev(offset), _dev(f_delta), _dev(hk), hk_stride, float(scale), _dev(out), nl),
+                                            syms_per_frame, _dev(offset), _dev(f_delta), _dev(hk), hk_stride, float(scale), _dev(out), llr_stride),
                  "rx_llr")
         return out
 

@@ -378,9 +378,8 @@ template <int N, int MODE> static hipError_t launch_sym(const SymParams &p, hipS
     typedef Plan<N> P;
     const long long total = (MODE == M_CHEST) ? p.n_frames : p.n_frames * (long long)p.syms_per_frame;
     if (total <= 0) return hipSuccess;
-    long long groups = (total + P::G - 1) / P::G;
-    long long cap = (long long)num_cu * 8; // persistent: ~8 workgroups per CU, grid-stride over symbol groups
-    int grid = (int)(groups < cap ? groups : cap);
+    // persistent: ~8 workgroups per CU, grid-stride over symbol groups
+    const int grid = (int)persistent_grid((total + P::G - 1) / P::G, (long long)num_cu * 8, tuning_or_default(p.tune));
     static const char *const names[] = {"k_sym<fft>", "k_sym<ifft>", "k_sym<ifft_cp>", "k_sym<demod>", "k_sym<chest>", "k_sym<tx>", "k_sym<llr>"};
     trace_add(p.trace, names[MODE]);
     hipLaunchKernelGGL((k_sym<N, MODE>), dim3(grid), dim3(P::WG), 0, st, p);

@@ -2041,3 +2041,64 @@ def test_cpp_host_loopback(ofdm):
         long_cap.tofile(lpath)
         r = subprocess.run([exe, "--receive", lpath], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0 and "received 400 bytes" in r.stdout, r.stdout
+
+
+# ------------------------------------------------------------------ the generic kernel's persistent loop, every mode
+@pytest.mark.parametrize("n", [64, 128, 256, 512, 1024, 2048, 4096])
+def test_k_sym_many_steps_per_workgroup_change_nothing(api, orc, n):
+    """k_sym<N, MODE> is a persistent kernel: a workgroup takes G = 256 / (N / 8) symbols (frames for the channel estimate) per step
+    and strides over the batch, with the next step's samples / payload dwords fetched a step ahead and its LDS staging reused.  The
+    device-sized grid gives every workgroup ONE step on any batch a test can afford, so every mode runs here on grids of 1 and 3
+    workgroups too (tuning key grid_cap), on batches of more than eight steps whose last step is partial: the same arithmetic per
+    symbol whatever the grid, so the results must be the same bits as the device-sized grid's, which the tests above hold against
+    the oracle.  The shape-specialised kernels are switched off by their tuning keys and every call asserts its dispatch."""
+    import torch
+    rng = np.random.default_rng(9000 + n)
+    S = n + n // 4
+    G = max(1, 256 // (n // 8))
+    total = 8 * G + max(1, G // 2)
+    assert total > 8 * G and (G == 1 or total % G)
+    mod, guard = 6, True
+    ctx = api.Context(n_fft=n, modulation=mod, guard_bands=guard, tuning={"no_fast64": 1, "no_mid_kernels": 1, "no_demod4096": 1, "no_txframe64": 1})
+
+    def cx(*shape):
+        return dev(ctx, fc32(rng.standard_normal(shape) + 1j * rng.standard_normal(shape)))
+
+    bins, blocks = cx(total, n), cx(total, S)
+    D = 3
+    F = next(f for f in range(-(-total // D), 4 * total) if G == 1 or (f * D) % G)
+    x, _ = make_symbols_np(orc, rng, F * D, n, guard, mod, snr_db=20.0)
+    xs, hks = dev(ctx, x.reshape(F, D * S)), cx(F, n)
+    caps = cx(total, 10 * S + 40)
+    offs = torch.from_numpy(rng.integers(0, 60, total).astype(np.int32)).to(ctx.device)
+    fds = torch.from_numpy((rng.random(total) * 1.6 - 0.8) * np.pi / S).to(ctx.device)
+    stream = torch.from_numpy(rng.integers(0, 256, total * ctx.bytes_per_symbol - 5, dtype=np.uint8)).to(ctx.device)
+    nbytes = 2 * ctx.bytes_per_symbol                                # 16-byte header + body: three data symbols per frame
+    assert ctx.data_symbols(nbytes) == D
+    pay = torch.from_numpy(rng.integers(0, 256, (F, nbytes), dtype=np.uint8)).to(ctx.device)
+    lens = torch.from_numpy(rng.integers(0, nbytes + 1, F).astype(np.int32))
+    calls = [
+        ("k_sym<fft>", lambda: ctx.fft(bins)),
+        ("k_sym<ifft>", lambda: ctx.fft(bins, inverse=True)),
+        ("k_sym<fft>", lambda: ctx.unprefix_block(blocks)),         # the same kernel reading past a cyclic prefix
+        ("k_sym<ifft_cp>", lambda: ctx.prefix_block(bins)),
+        ("k_sym<demod>", lambda: torch.cat([t.view(torch.uint8).reshape(-1) for t in ctx.rx_demod(xs, D, hk=hks, want_soft=True)])),
+        ("k_sym<demod>", lambda: ctx.rx_demod(xs, D - 1, first_symbol=1, frame_len=D * S - S // 2)),
+        ("k_sym<chest>", lambda: ctx.estimate_channel(caps, offs, fds, frame_len=10 * S + 20)),
+        ("k_sym<tx>", lambda: ctx.tx_symbols(stream, n_sym=total)),
+        ("k_sym<tx>+k_tx_finish", lambda: ctx.encode_batch(pay, out=_misaligned_c64(ctx, F, ctx.frame_samples(nbytes)), lens=lens)),
+    ]
+
+    def raw(t):                                                      # the bits: -0.0 is not 0.0 here
+        return torch.view_as_real(t).view(torch.int32) if t.is_complex() else t
+
+    for i, (name, call) in enumerate(calls):
+        outs = []
+        for cap in (0, 1, 3):
+            ctx.set_tuning("grid_cap", cap)
+            outs.append(raw(call()))
+            assert ctx.last_dispatch() == name, (i, cap, ctx.last_dispatch())
+        ctx.synchronize()
+        assert bool(outs[0].any()), (n, i, name)
+        for cap, o in zip((1, 3), outs[1:]):
+            assert torch.equal(o, outs[0]), (n, i, name, cap)

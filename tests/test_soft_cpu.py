@@ -1,6 +1,7 @@
 """CPU checks of the soft-decision extension (OFDM_ECC_HAMMING74_SOFT, ofdm_rx_llr_batch, ofdm_hamming74_decode_soft): the boundary
 accepts the new ecc value and declares the two entry points, and the numpy restatement tests/soft_ref.py agrees with hand-worked
-values and with the kernels' closed form.  No kernel is launched here."""
+values and with the kernels' closed form, and the rule that holds the GPU's LLRs to the f64 oracle (soft_ref.llr_compare) accepts the
+reference itself and rejects every listed way of getting an LLR wrong.  No kernel is launched here."""
 import ctypes as C
 import os
 import re
@@ -96,7 +97,9 @@ def test_noiseless_weakest_bit_has_unit_magnitude():
 
 
 def test_closed_form_is_the_brute_force_minimum():
-    v = np.concatenate([np.linspace(-20, 20, 40001), np.arange(-17, 18, 1.0)])   # every level and boundary, dense in between
+    # every level and boundary, dense in between; out to three times the outermost level of the widest axis (15), so that the
+    # lo < 0 / hi > M - 1 branches of llr_axis_bit are held far outside the constellation for every M
+    v = np.concatenate([np.linspace(-48, 48, 96001), np.arange(-48, 49, 1.0)])
     for m in (1, 2, 3, 4):
         np.testing.assert_allclose(sr.axis_llr_closed(v, m), sr.axis_llr(v, m), rtol=0, atol=1e-9)
 
@@ -119,3 +122,135 @@ def test_soft_hamming_restatement_by_hand():
     one[3] = 5   # only d3 carries weight: every nibble with bit 3 set ties at +5, the smallest of them is 8
     assert sr.ham_decode_soft(one)[0] == 8
     assert sr.ham_decode_soft(np.zeros(55)).size == 0
+
+
+# ---------------------------------------------------------------------------------------------------------- the comparison rule
+SNRS = (30.0, 14.0, 6.0)
+
+
+def _channels(orc, rng, n, n_frames):
+    """None, one response per frame (1 + 0.3 randn) and the shared FFT of the reference's CHANNEL taps (|H| 0.29 .. 1.26), as fc32"""
+    per_frame = (1.0 + 0.3 * (rng.standard_normal((n_frames, n)) + 1j * rng.standard_normal((n_frames, n)))).astype(np.complex64)
+    return {"none": None, "per frame": per_frame, "taps": np.fft.fft(orc.channel_taps(), n).astype(np.complex64)}
+
+
+def _case(orc, rng, n, guard, mod, snr, hk, n_frames=3, syms=None):
+    from util import make_symbols_np
+
+    syms = syms or (12 if n == 64 else 2)
+    x, _ = make_symbols_np(orc, rng, n_frames * syms, n, guard, mod, snr_db=snr)
+    x = x.reshape(n_frames, -1)
+    if hk is not None:
+        x = sr.through_h(x, n, hk.reshape(-1, n))
+    return x, sr.oracle_llr_reference(orc, x, n, guard, mod, 32.0, hk)
+
+
+@pytest.mark.parametrize("n,guard", [(64, True), (64, False), (1024, True)])
+def test_rule_accepts_the_reference_and_excuses_at_most_one_percent(orc, n, guard):
+    rng = np.random.default_rng(1000 + n + guard)
+    worst = (0.0, None)
+    for mod in (1, 2, 4, 6, 8):
+        for snr in SNRS:
+            for name, hk in _channels(orc, rng, n, 3).items():
+                _, ref = _case(orc, rng, n, guard, mod, snr, hk)
+                share = sr.llr_compare(sr.quantise(ref["y"]), ref["y"], ref["eps"], what=f"{n} {guard} {mod} {snr} {name}")
+                sr.assert_signs(sr.quantise(ref["y"]), ref)
+                print(f"reference alone: N {n} guard {guard} mod {mod} {snr} dB H {name}: excused {100 * share:.3f} % of {ref['y'].size}")
+                assert share <= 0.01, (n, guard, mod, snr, name, share)
+                worst = max(worst, (share, (mod, snr, name)))
+    print("largest excused share", worst)
+
+
+def _axis_llr_always_alo(v, m):
+    """soft_ref.axis_llr_closed with the far level taken below l* whenever there is one"""
+    v = np.asarray(v, np.float64)
+    M = 1 << m
+    ls = np.clip(np.floor(v / 2.0 + M / 2.0), 0, M - 1).astype(np.int64)
+    a_s = 2.0 * ls - (M - 1)
+    out = np.empty(v.shape + (m,))
+    for b in range(m):
+        h = 1 << (m - 1 - b)
+        r = (ls + h) >> (m - b)
+        lo, hi = (2 * r - 1) * h - 1, (2 * r + 1) * h
+        ao = np.where(lo < 0, 2.0 * hi - (M - 1), 2.0 * lo - (M - 1))
+        lam = 0.25 * (a_s - ao) * (2.0 * v - ao - a_s)
+        out[..., b] = np.where(r & 1, lam, -lam)
+    return out
+
+
+def _mutants(ref, mod, hk, bins, n):
+    """name -> a wrong LLR array for the case `ref` (int64, so that +-128 can be represented)"""
+    y, pts, w = ref["y"], ref["points"], ref["weights"]
+    q = sr.quantise(y).astype(np.int64)
+    shape = y.shape
+    out = {"off by one": q + 1, "off by minus one": q - 1, "sign flipped": -q,
+           "truncated": np.clip(np.trunc(y), -127, 127).astype(np.int64), "clamp at 128": np.clip(np.rint(y), -128, 128).astype(np.int64)}
+    m = mod // 2
+    wb = 1.0 if w is None else w[:, None, :, None]
+    if mod >= 2:
+        out["I and Q swapped"] = sr.quantise(32.0 * wb * sr.point_llr(pts.imag + 1j * pts.real, mod)).reshape(shape).astype(np.int64)
+    if mod >= 4:
+        M = 1 << m
+        lam = sr.point_llr(pts, mod)
+        rev = np.concatenate([lam[..., :m][..., ::-1], lam[..., m:][..., ::-1]], axis=-1)
+        out["Gray order reversed"] = sr.quantise(32.0 * wb * rev).reshape(shape).astype(np.int64)
+        alo = np.concatenate([_axis_llr_always_alo(pts.real * (M - 1), m), _axis_llr_always_alo(pts.imag * (M - 1), m)], axis=-1)
+        out["far level always alo"] = sr.quantise(32.0 * wb * alo).reshape(shape).astype(np.int64)
+    if hk is not None:
+        h2 = np.abs(hk.astype(np.complex128).reshape(-1, n)) ** 2
+        lam = sr.point_llr(pts, mod)
+        out["weights over all N bins"] = sr.quantise(32.0 * (h2[:, bins] / h2.mean(-1, keepdims=True))[:, None, :, None] * lam).reshape(shape).astype(np.int64)
+        h1 = np.sqrt(h2[:, bins])
+        out["w = |H|"] = sr.quantise(32.0 * (h1 / h1.mean(-1, keepdims=True))[:, None, :, None] * lam).reshape(shape).astype(np.int64)
+    return out
+
+
+@pytest.mark.parametrize("mod", [1, 2, 4, 6, 8])
+def test_rule_rejects_every_mutation(orc, mod):
+    n, guard = 64, True
+    rng = np.random.default_rng(2000 + mod)
+    bins = sr.data_bins(orc, n, guard)
+    seen = set()
+    for snr in SNRS:
+        for name, hk in _channels(orc, rng, n, 3).items():
+            _, ref = _case(orc, rng, n, guard, mod, snr, hk)
+            for what, bad in _mutants(ref, mod, hk, bins, n).items():
+                if what == "clamp at 128" and not (np.abs(ref["y"]) > 128.5 + ref["eps"]).any():
+                    continue                                     # nothing saturates in this case (BPSK / QPSK at scale 32): no such mutant
+                with pytest.raises(AssertionError):
+                    sr.llr_compare(bad, ref["y"], ref["eps"])
+                seen.add(what)
+    want = {"off by one", "off by minus one", "sign flipped", "truncated", "weights over all N bins", "w = |H|"}
+    want |= {"I and Q swapped"} if mod >= 2 else set()
+    want |= {"Gray order reversed", "far level always alo", "clamp at 128"} if mod >= 4 else set()
+    assert want <= seen, want - seen
+
+
+def test_rule_edges_by_hand():
+    y = np.array([0.2, 0.49, 0.51, 126.3, 127.3, 127.9, 500.0, -0.5, np.nan, np.inf])
+    q = sr.quantise(y)
+    np.testing.assert_array_equal(q, [0, 0, 1, 126, 127, 127, 127, 0, 0, 0])
+    assert sr.llr_compare(q, y, 0.02) == 0.3                       # 0.49, 0.51 and -0.5 are within 0.02 of a boundary, the rest decided
+    np.testing.assert_array_equal(sr.llr_decided(y, 0.02), [1, 0, 0, 1, 1, 1, 1, 0, 1, 1])
+    sr.llr_compare([0, 1, 0, 126, 127, 127, 127, -1, 0, 0], y, 0.02)   # the undecided ones on the other side of their boundary
+    for i, wrong in ((0, 1), (1, -1), (1, 2), (2, 2), (3, 127), (5, 126), (6, 126), (7, 1), (8, 1), (9, 127)):
+        bad = q.astype(np.int64).copy()
+        bad[i] = wrong
+        with pytest.raises(AssertionError):
+            sr.llr_compare(bad, y, 0.02)
+    assert sr.llr_compare([1, 0], np.array([0.2, 0.9]), 0.6) == 1.0   # eps > 1/2: nothing is decided, one step across is allowed ...
+    with pytest.raises(AssertionError):
+        sr.llr_compare([2], np.array([0.2]), 0.6)                     # ... two are not
+    with pytest.raises(AssertionError):
+        sr.llr_compare([-1], np.array([0.2]), 0.6)                    # ... and -0.5 is 0.7 away
+
+
+def test_slope_is_the_derivative_of_the_brute_force():
+    rng = np.random.default_rng(5)
+    for mod in (1, 2, 4, 6, 8):
+        z = (rng.uniform(-1.6, 1.6, 4000) + 1j * rng.uniform(-1.6, 1.6, 4000))
+        d = 1e-7
+        num = (sr.point_llr(z + d * (1 + 1j), mod) - sr.point_llr(z - d * (1 + 1j), mod)) / (2 * d)
+        sl = sr.llr_slope(z, mod)
+        smooth = np.abs(np.abs(num) - sl) < 1e-3 * sl               # all but the points within d of a kink of Lambda
+        assert smooth.mean() > 0.999 and sl.min() >= 1.0, (mod, smooth.mean())
