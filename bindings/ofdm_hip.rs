@@ -37,6 +37,14 @@ pub const OFDM_ECC_HAMMING74_SOFT: i32 = 2;
 // K = 7 rate-1/2 convolutional code (133 / 171 octal), zero-terminated by one tail byte, Viterbi-decoded from int8 LLRs; 3 and 4 are
 // not modes (include/ofdm_hip.h)
 pub const OFDM_ECC_CONV_K7: i32 = 5;
+// framed convolutional modes: a rate-1/2 coded length block that decode reads instead of the uncoded header, then the payload at rate
+// 1/2, 2/3 or 3/4 (punctured); parity unpinned by the reference, tests/framed_ref.py is the definition (include/ofdm_hip.h)
+pub const OFDM_ECC_CONV_K7F_R12: i32 = 10;
+pub const OFDM_ECC_CONV_K7F_R23: i32 = 11;
+pub const OFDM_ECC_CONV_K7F_R34: i32 = 12;
+pub const OFDM_CONV_RATE_1_2: i32 = 0;
+pub const OFDM_CONV_RATE_2_3: i32 = 1;
+pub const OFDM_CONV_RATE_3_4: i32 = 2;
 pub const OFDM_SOFT_LLR_SCALE: f32 = 32.0;
 
 /// The crate's own `ModulationScheme` (src/transmitter.rs:98-104) is what `encode` / `decode` keep taking.  Its `Qam` arm is
@@ -98,6 +106,11 @@ extern "C" {
                                out_stride: i64) -> c_int;
     pub fn ofdm_conv_k7_decode_soft(ctx: *mut ofdm_ctx, llr_dev: *const i8, n_frames: i64, llr_stride: i64, n_steps: i64,
                                     terminated: i32, out_dev: *mut u8, out_stride: i64) -> c_int;
+    pub fn ofdm_conv_k7_kept_bits(n_steps: i64, rate: i32) -> i64;
+    pub fn ofdm_conv_k7_encode_punctured(ctx: *mut ofdm_ctx, in_dev: *const u8, n_frames: i64, in_stride: i64, n_bytes: i64, rate: i32,
+                                         out_dev: *mut u8, out_stride: i64) -> c_int;
+    pub fn ofdm_conv_k7_decode_punctured(ctx: *mut ofdm_ctx, llr_dev: *const i8, n_frames: i64, llr_stride: i64, n_steps: i64, rate: i32,
+                                         terminated: i32, out_dev: *mut u8, out_stride: i64) -> c_int;
     pub fn ofdm_sc_correlate_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,
                                    n_lags: i64, d_hat_dev: *mut i32, f_delta_dev: *mut f64, metric_dev: *mut f32) -> c_int;
     pub fn ofdm_frequency_correction_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_pairs: i64, stride: i64,

@@ -67,9 +67,16 @@ enum { OFDM_MOD_BPSK = 1, OFDM_MOD_QPSK = 2, OFDM_MOD_QAM16 = 4, OFDM_MOD_QAM64 
  * coded body is decoded by maximum likelihood from int8 LLRs (see "soft decisions" below) instead of by syndrome.
  * OFDM_ECC_CONV_K7: the constraint-length-7, rate-1/2 convolutional code with generators 133 / 171 (octal) of 802.11a, DVB-T and DAB,
  * zero-terminated by one tail byte (coded_len(p) = 2 (p + 1)), decoded by the Viterbi algorithm from the same int8 LLRs (see
- * "convolutional code" below).  The values 3 and 4 are REJECTED (OFDM_ERR_INVALID), as is every value not named here. */
-enum { OFDM_ECC_NONE = 0, OFDM_ECC_HAMMING74 = 1, OFDM_ECC_HAMMING74_SOFT = 2, OFDM_ECC_CONV_K7 = 5 };
-/* llr_scale of the OFDM_ECC_HAMMING74_SOFT and OFDM_ECC_CONV_K7 decode chains (chosen from the measured BER curves) */
+ * "convolutional code" below).  The values 3 and 4 are REJECTED (OFDM_ERR_INVALID), as is every value not named here.
+ * OFDM_ECC_CONV_K7F_R12 / _R23 / _R34: the framed convolutional modes -- the same code over the payload at rate 1/2, 2/3 or 3/4
+ * (punctured), behind a rate-1/2 coded length block that decode reads INSTEAD of the uncoded 16-byte header: coded_len(p) = 18 +
+ * ceil(kept(8 (p + 1), rate) / 8) (see "punctured rates and framed modes" below). */
+enum { OFDM_ECC_NONE = 0, OFDM_ECC_HAMMING74 = 1, OFDM_ECC_HAMMING74_SOFT = 2, OFDM_ECC_CONV_K7 = 5,
+       OFDM_ECC_CONV_K7F_R12 = 10, OFDM_ECC_CONV_K7F_R23 = 11, OFDM_ECC_CONV_K7F_R34 = 12 };
+/* puncturing rate of ofdm_conv_k7_*_punctured (the framed modes' body rate is OFDM_ECC_CONV_K7F_Rxx - OFDM_ECC_CONV_K7F_R12) */
+enum { OFDM_CONV_RATE_1_2 = 0, OFDM_CONV_RATE_2_3 = 1, OFDM_CONV_RATE_3_4 = 2 };
+/* llr_scale of the OFDM_ECC_HAMMING74_SOFT and OFDM_ECC_CONV_K7 decode chains (chosen from the measured BER curves);
+ * the OFDM_ECC_CONV_K7F_* chains inherit it from OFDM_ECC_CONV_K7 */
 #define OFDM_SOFT_LLR_SCALE 32.0f
 enum { OFDM_CFO_OFF = 0, OFDM_CFO_SIGNED = 1, OFDM_CFO_ABS = 2 }; /* ABS = reference's abs() (receiver.rs:239) */
 /* timing / CFO detector of decode: the north star's Schmidl-Cox (default), or the reference's own pair -- cross-correlation
@@ -282,7 +289,8 @@ int ofdm_hamming74_decode_soft(ofdm_ctx *ctx, const int8_t *llr_dev, int64_t n_b
  * p1 = p0 | 1; a transition with outputs (a, b) adds (2a - 1) L_{2t} + (2b - 1) L_{2t+1}; the survivor is p1 iff its candidate is
  * strictly larger (a tie keeps p0).  Traceback starts at state 0 when `terminated`, otherwise at the largest final metric (lowest
  * state on a tie); u_t = s_{t+1} >> 5, output bytes packed LSB first.  That is maximum likelihood over all T-bit inputs (whose last
- * six bits are zero when terminated).  No puncturing, no interleaver, no sliding window: the whole frame is traced back. */
+ * six bits are zero when terminated).  Puncturing: see "punctured rates and framed modes" below.  No interleaver, no sliding window:
+ * the whole frame is traced back. */
 /* rows of n_bytes payload bytes -> rows of 2 * (n_bytes + 1) coded bytes (row f at in_dev + f * in_stride / out_dev + f * out_stride;
  * in_stride >= n_bytes, out_stride >= 2 * (n_bytes + 1), OFDM_ERR_INVALID otherwise) */
 int ofdm_conv_k7_encode(ofdm_ctx *ctx, const uint8_t *in_dev, int64_t n_frames, int64_t in_stride, int64_t n_bytes,
@@ -292,6 +300,37 @@ int ofdm_conv_k7_encode(ofdm_ctx *ctx, const uint8_t *in_dev, int64_t n_frames, 
  * metrics are not renormalised).  n_steps = 0 and n_frames = 0 succeed and write nothing. */
 int ofdm_conv_k7_decode_soft(ofdm_ctx *ctx, const int8_t *llr_dev, int64_t n_frames, int64_t llr_stride, int64_t n_steps,
                              int32_t terminated, uint8_t *out_dev, int64_t out_stride);
+
+/* ------------------------------------------------------------------ punctured rates and framed modes (DESIGN.md 3, EXT-2 framed modes)
+ * Parity unpinned by the reference: tests/framed_ref.py is the definition.
+ * Rates.  A keep mask, periodic in the step index t, lists (A_t, B_t): rate 1/2 (1,1); rate 2/3 (1,1),(1,0); rate 3/4
+ * (1,1),(1,0),(0,1) -- the 802.11a patterns.  kept(T, rate) = the ones of the mask over steps 0 .. T - 1.  The punctured stream is the
+ * kept bits of c_0, c_1, ... of the encoder above, in order, packed LSB first and zero-padded to a whole byte:
+ * ceil(kept(8 (p + 1), rate) / 8) bytes for p payload bytes and the tail byte.  The decoder puts LLR 0 at every dropped position and
+ * then runs exactly the Viterbi rule above (same tie rules, same `terminated`).
+ * Framed modes (ecc = OFDM_ECC_CONV_K7F_R12 / _R23 / _R34).  Behind its usual 16-byte header a frame carries
+ *   1. the length block, always rate 1/2: the code above over the 8 bytes [u32 LE p][u32 LE ~p] and the tail byte = 18 bytes, 72 steps;
+ *   2. the body: the payload's p bytes and the tail byte at the mode's rate.
+ * coded_len(p) = 18 + ceil(kept(8 (p + 1), rate) / 8); the 16-byte header carries coded_len of the row's true length as in every
+ * mode, and the frame is the OFDM_ECC_NONE frame of that byte stream.  With per-row lengths row f codes its own len_f into both blocks.
+ * Decode of a frame that reached the demodulator (status OFDM_FRAME_OK so far), body = the demodulated bytes behind the 16-byte header,
+ * which is NOT read: body < 18 -> status OFDM_FRAME_HEADER, out_len 0.  Otherwise 72 steps, terminated, are decoded from LLRs 128 ..
+ * 272; the block is valid iff bytes 4..7 are the complement of bytes 0..3 and byte 8 is 0, an invalid one gives OFDM_FRAME_HEADER and
+ * out_len 0 (a garbled length is reported, never guessed).  With a valid p and avail = body - 18: if ceil(kept(8 (p + 1)) / 8) <=
+ * avail, 8 (p + 1) steps are decoded, terminated, from LLR 272 on and p bytes delivered; otherwise the frame was cut short: the
+ * largest T' with kept(T') <= 8 avail steps are decoded unterminated, min(p, T' / 8) bytes delivered, status unchanged. */
+/* kept(n_steps, rate); host call, no context.  OFDM_ERR_INVALID (< 0) for a rate that is not OFDM_CONV_RATE_* or n_steps < 0 */
+int64_t ofdm_conv_k7_kept_bits(int64_t n_steps, int32_t rate);
+/* ofdm_conv_k7_encode at `rate`: rows of n_bytes payload bytes -> rows of ceil(kept(8 (n_bytes + 1), rate) / 8) bytes; in_stride >=
+ * n_bytes, out_stride >= that row (OFDM_ERR_INVALID otherwise, and for an unknown rate).  rate = OFDM_CONV_RATE_1_2: the bytes of
+ * ofdm_conv_k7_encode. */
+int ofdm_conv_k7_encode_punctured(ofdm_ctx *ctx, const uint8_t *in_dev, int64_t n_frames, int64_t in_stride, int64_t n_bytes,
+                                  int32_t rate, uint8_t *out_dev, int64_t out_stride);
+/* ofdm_conv_k7_decode_soft at `rate`: rows of kept(n_steps, rate) LLRs (the kept positions only) -> rows of floor(n_steps / 8) bytes.
+ * llr_stride >= kept(n_steps, rate), out_stride >= floor(n_steps / 8) (OFDM_ERR_INVALID otherwise); n_steps > 2^20:
+ * OFDM_ERR_UNSUPPORTED.  rate = OFDM_CONV_RATE_1_2: the bytes of ofdm_conv_k7_decode_soft. */
+int ofdm_conv_k7_decode_punctured(ofdm_ctx *ctx, const int8_t *llr_dev, int64_t n_frames, int64_t llr_stride, int64_t n_steps,
+                                  int32_t rate, int32_t terminated, uint8_t *out_dev, int64_t out_stride);
 
 /* ------------------------------------------------------------------ pipelines */
 
@@ -303,7 +342,7 @@ int ofdm_conv_k7_decode_soft(ofdm_ctx *ctx, const int8_t *llr_dev, int64_t n_fra
  * and written to out_dev[f*out_stride ..] (out_stride >= ofdm_frame_samples(payload_bytes)).
  * With ECC the payload is Hamming(7,4)-encoded first and the header carries the coded length (HAMMING74 and HAMMING74_SOFT alike);
  * with OFDM_ECC_CONV_K7 it is convolutionally encoded (a row of true length len_f codes to 2 (len_f + 1) bytes).  The 16-byte
- * header itself is never coded. */
+ * header itself is never coded.  OFDM_ECC_CONV_K7F_*: the framed stream (length block + punctured body) of the row's len_f. */
 int ofdm_tx_encode_batch(ofdm_ctx *ctx, const uint8_t *payload_dev, int64_t n_frames, int64_t payload_stride,
                          const int32_t *payload_len_dev, int32_t payload_bytes, ofdm_fc32 *out_dev,
                          int64_t out_stride);
@@ -320,7 +359,10 @@ int ofdm_tx_encode_batch(ofdm_ctx *ctx, const uint8_t *payload_dev, int64_t n_fr
  * ecc = OFDM_ECC_CONV_K7 (likewise in every wrapper): with keep = the header's value if it is below the demodulated body, else the
  * body, the Viterbi decoder runs 4 * keep steps over LLRs 128 .. 128 + 8 keep of the same LLRs, terminated iff the frame was not cut
  * short, and out_len = max(keep / 2 - 1, 0) -- the tail byte is not delivered; out_stride >= max((max_symbols * bytes_per_symbol -
- * 16) / 2 - 1, 0).  A max_symbols whose body exceeds 2^18 bytes (2^20 trellis steps): OFDM_ERR_UNSUPPORTED. */
+ * 16) / 2 - 1, 0).  A max_symbols whose body exceeds 2^18 bytes (2^20 trellis steps): OFDM_ERR_UNSUPPORTED.
+ * ecc = OFDM_ECC_CONV_K7F_* (likewise in every wrapper): the rule of "punctured rates and framed modes" above; status may become
+ * OFDM_FRAME_HEADER.  With avail = max(max_symbols * bytes_per_symbol - 16 - 18, 0), out_stride >= floor(T' / 8) for the largest T'
+ * with kept(T', rate) <= 8 avail (at most 3 avail / 4); a T' above 2^20: OFDM_ERR_UNSUPPORTED. */
 int ofdm_rx_decode_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t frame_stride,
                          int64_t frame_len, int64_t n_lags, int32_t max_symbols, uint8_t *out_dev,
                          int64_t out_stride, int32_t *out_len_dev, int32_t *status_dev, int32_t *offset_dev,

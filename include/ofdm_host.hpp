@@ -175,6 +175,29 @@ class Context {
         if (!out.empty()) check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
         return out;
     }
+    // the same pair at a punctured rate (OFDM_CONV_RATE_1_2 / _2_3 / _3_4; the framed modes OFDM_ECC_CONV_K7F_* apply it inside encode /
+    // decode): payload -> ceil(kept(8 (n + 1), rate) / 8) bytes, and the kept(n_steps, rate) LLRs of n_steps steps -> n_steps / 8 bytes
+    static int64_t conv_kept_bits(int64_t n_steps, int rate) { return ofdm_conv_k7_kept_bits(n_steps, rate); }
+    std::vector<uint8_t> conv_encode_punctured(const std::vector<uint8_t> &data, int rate) {
+        const int64_t kept = ofdm_conv_k7_kept_bits(8 * ((int64_t)data.size() + 1), rate);
+        check(kept < 0 ? (int)kept : 0, "ofdm_conv_k7_kept_bits");
+        std::vector<uint8_t> out((size_t)((kept + 7) / 8));
+        DevBuf din(ctx_, data.size()), dout(ctx_, out.size());
+        if (!data.empty()) check(ofdm_memcpy_h2d(ctx_, din.p, data.data(), data.size()), "h2d");
+        check(ofdm_conv_k7_encode_punctured(ctx_, (const uint8_t *)din.p, 1, (int64_t)data.size(), (int64_t)data.size(), rate,
+                                            (uint8_t *)dout.p, (int64_t)out.size()), "ofdm_conv_k7_encode_punctured");
+        check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
+        return out;
+    }
+    std::vector<uint8_t> viterbi_decode_punctured(const std::vector<int8_t> &llr, int64_t n_steps, int rate, bool terminated = true) {
+        std::vector<uint8_t> out((size_t)(n_steps > 0 ? n_steps / 8 : 0));
+        DevBuf din(ctx_, llr.size()), dout(ctx_, out.size());
+        if (!llr.empty()) check(ofdm_memcpy_h2d(ctx_, din.p, llr.data(), llr.size()), "h2d");
+        check(ofdm_conv_k7_decode_punctured(ctx_, (const int8_t *)din.p, 1, (int64_t)llr.size(), n_steps, rate, terminated ? 1 : 0,
+                                            (uint8_t *)dout.p, (int64_t)out.size()), "ofdm_conv_k7_decode_punctured");
+        if (!out.empty()) check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
+        return out;
+    }
 
   private:
     ofdm_ctx *ctx_ = nullptr;

@@ -11,7 +11,8 @@ def __getattr__(name):
     # api imports torch and touches the GPU lazily; keep `import ofdm_amd` cheap
     if name in ("api", "Context", "encode", "decode", "decode_long", "pinned_empty", "channel", "default_pilots", "locking_signal", "preamble",
                 "training_signals", "OfdmError", "DecodeError", "BPSK", "QPSK", "QAM16", "QAM64", "QAM256",
-                "ECC_NONE", "ECC_HAMMING74", "ECC_HAMMING74_SOFT", "ECC_CONV_K7", "SOFT_LLR_SCALE", "CFO_OFF", "CFO_SIGNED", "CFO_ABS", "SYNC_SCHMIDL_COX", "SYNC_REFERENCE"):
+                "ECC_NONE", "ECC_HAMMING74", "ECC_HAMMING74_SOFT", "ECC_CONV_K7", "ECC_CONV_K7F_R12", "ECC_CONV_K7F_R23", "ECC_CONV_K7F_R34",
+                "CONV_RATE_1_2", "CONV_RATE_2_3", "CONV_RATE_3_4", "SOFT_LLR_SCALE", "CFO_OFF", "CFO_SIGNED", "CFO_ABS", "SYNC_SCHMIDL_COX", "SYNC_REFERENCE"):
         import importlib
 
         api = importlib.import_module(".api", __name__)

@@ -20,6 +20,9 @@ from . import _lib
 BPSK, QPSK, QAM16, QAM64, QAM256 = 1, 2, 4, 6, 8  # ModulationScheme (src/transmitter.rs:98-104) as bits/point
 ECC_NONE, ECC_HAMMING74, ECC_HAMMING74_SOFT = 0, 1, 2
 ECC_CONV_K7 = 5  # K = 7 rate-1/2 convolutional code, Viterbi-decoded from LLRs (3 and 4 are not modes)
+# framed convolutional modes: a coded length block in front of the payload at rate 1/2, 2/3, 3/4 (tests/framed_ref.py is the definition)
+ECC_CONV_K7F_R12, ECC_CONV_K7F_R23, ECC_CONV_K7F_R34 = 10, 11, 12
+CONV_RATE_1_2, CONV_RATE_2_3, CONV_RATE_3_4 = 0, 1, 2
 SOFT_LLR_SCALE = 32.0  # OFDM_SOFT_LLR_SCALE (include/ofdm_hip.h): the llr_scale of the soft decode chain
 CFO_OFF, CFO_SIGNED, CFO_ABS = 0, 1, 2
 FRAME_OK, FRAME_SHORT, FRAME_NOSYNC, FRAME_BADTIMING, FRAME_HEADER = 0, -1, -2, -3, -4
@@ -344,24 +347,46 @@ class Context:
         self._ck(self.lib.ofdm_hamming74_decode_soft(self.h, _dev(llr), llr.numel(), _dev(out)), "hamming74_decode_soft")
         return out
 
-    def conv_encode(self, data: torch.Tensor) -> torch.Tensor:
+    def conv_encode(self, data: torch.Tensor, rate: Optional[int] = None) -> torch.Tensor:
         """ofdm_conv_k7_encode: rows of data [n_frames, n_bytes] (uint8; the rows may be strided) -> [n_frames, 2 (n_bytes + 1)] coded
-        bytes of the K = 7 rate-1/2 code (133 / 171 octal), one zero tail byte appended to every row."""
+        bytes of the K = 7 rate-1/2 code (133 / 171 octal), one zero tail byte appended to every row.
+        rate (CONV_RATE_*): ofdm_conv_k7_encode_punctured -> [n_frames, ceil(kept(8 (n_bytes + 1), rate) / 8)]."""
         if data.dtype != torch.uint8 or data.dim() != 2 or data.device != self.device or (data.shape[1] > 1 and data.stride(1) != 1):
             raise OfdmError("expected a uint8 tensor [n_frames, n_bytes] with contiguous rows on the context's device")
         n, nb = data.shape
-        out = self.empty((n, 2 * (nb + 1)), torch.uint8)
         stride = data.stride(0) if n > 1 else nb
+        if rate is not None:
+            kept = int(self.lib.ofdm_conv_k7_kept_bits(8 * (nb + 1), int(rate)))
+            self._ck(min(kept, 0), "conv_k7_kept_bits")
+            out = self.empty((n, (kept + 7) // 8), torch.uint8)
+            self._ck(self.lib.ofdm_conv_k7_encode_punctured(self.h, _dev(data), n, stride, nb, int(rate), _dev(out), out.shape[1]),
+                     "conv_k7_encode_punctured")
+            return out
+        out = self.empty((n, 2 * (nb + 1)), torch.uint8)
         self._ck(self.lib.ofdm_conv_k7_encode(self.h, _dev(data), n, stride, nb, _dev(out), out.shape[1]), "conv_k7_encode")
         return out
 
-    def viterbi_decode_soft(self, llr: torch.Tensor, n_steps: Optional[int] = None, terminated: bool = True) -> torch.Tensor:
+    def viterbi_decode_soft(self, llr: torch.Tensor, n_steps: Optional[int] = None, terminated: bool = True,
+                            rate: Optional[int] = None) -> torch.Tensor:
         """ofdm_conv_k7_decode_soft: rows of llr [n_frames, >= 2 n_steps] (int8, positive = bit 1; the rows may be strided) ->
         [n_frames, n_steps // 8] bytes, the exact Viterbi (maximum-likelihood) decode; n_steps defaults to the row length // 2.
-        terminated: the traceback starts at state 0, otherwise at the best final state."""
+        terminated: the traceback starts at state 0, otherwise at the best final state.
+        rate (CONV_RATE_*): ofdm_conv_k7_decode_punctured, rows of the kept(n_steps, rate) LLRs of a punctured stream; n_steps is
+        required then."""
         if llr.dtype != torch.int8 or llr.dim() != 2 or llr.device != self.device or (llr.shape[1] > 1 and llr.stride(1) != 1):
             raise OfdmError("expected an int8 tensor [n_frames, >= 2 n_steps] with contiguous rows on the context's device")
         n, width = llr.shape
+        if rate is not None:
+            if n_steps is None or n_steps < 0:
+                raise OfdmError("viterbi_decode_soft: a punctured row does not tell its n_steps")
+            kept = int(self.lib.ofdm_conv_k7_kept_bits(int(n_steps), int(rate)))
+            self._ck(min(kept, 0), "conv_k7_kept_bits")
+            if kept > width:
+                raise OfdmError("viterbi_decode_soft: rows must hold kept(n_steps, rate) LLRs")
+            out = self.empty((n, int(n_steps) // 8), torch.uint8)
+            self._ck(self.lib.ofdm_conv_k7_decode_punctured(self.h, _dev(llr), n, llr.stride(0) if n > 1 else width, int(n_steps), int(rate),
+                                                            int(bool(terminated)), _dev(out), out.shape[1]), "conv_k7_decode_punctured")
+            return out
         n_steps = width // 2 if n_steps is None else int(n_steps)
         if n_steps < 0 or 2 * n_steps > width:
             raise OfdmError("viterbi_decode_soft: rows must hold 2 * n_steps LLRs")

@@ -311,6 +311,36 @@ struct ViterbiParams {
 void viterbi_k7_plan(long long n_frames, long long max_steps, int num_cu, const Tuning *tune, long long *blocks, long long *slab_words);
 hipError_t run_viterbi_k7(const ViterbiParams &p, long long blocks, hipStream_t st);
 
+// ---- punctured rates and the framed modes (OFDM_ECC_CONV_K7F_*; kernels_conv.hip, tests/framed_ref.py)
+// rate: 0 = 1/2 (nothing dropped), 1 = 2/3 (keep mask (1,1),(1,0) over the steps), 2 = 3/4 ((1,1),(1,0),(0,1)): the 802.11a patterns
+constexpr int kConvRates = 3;
+constexpr int kConvLengthBlock = 18;     // the framed modes' length block: [u32 LE p][u32 LE ~p] + tail byte at rate 1/2 = 72 steps
+// coded bits kept of steps 0 .. T - 1
+__host__ __device__ inline long long conv_kept_bits(long long T, int rate) {
+    if (rate == 1) return 3 * (T >> 1) + 2 * (T & 1);
+    if (rate == 2) { const long long g = T / 3, r = T - 3 * g; return 4 * g + (r == 0 ? 0 : r + 1); }
+    return 2 * T;
+}
+// the largest T with conv_kept_bits(T, rate) <= bits
+__host__ __device__ inline long long conv_max_steps(long long bits, int rate) {
+    if (rate == 1) { const long long g = bits / 3, r = bits - 3 * g; return 2 * g + (r == 2 ? 1 : 0); }
+    if (rate == 2) { const long long g = bits >> 2, r = bits & 3; return 3 * g + (r == 3 ? 2 : r == 2 ? 1 : 0); }
+    return bits >> 1;
+}
+// bytes of the punctured code of p payload bytes and the tail byte, zero-padded to a whole byte
+__host__ __device__ inline long long conv_body_len(long long p, int rate) { return (conv_kept_bits(8 * (p + 1), rate) + 7) >> 3; }
+// k_conv_encode_p: rows of head + conv_body_len(n_bytes, rate) bytes; head = kConvLengthBlock puts the row's length block in front
+// (the framed stream), head = 0 is the bare punctured code.  out_len (optional): every row's own length.
+hipError_t run_conv_encode_p(const uint8_t *in, long long n_frames, long long in_stride, const int32_t *in_len, long long n_bytes, int rate,
+                             int head, uint8_t *out, long long out_stride, int32_t *out_len, hipStream_t st);
+// k_viterbi_k7f.  Stage mode: rows of conv_kept_bits(n_steps, rate) LLRs.  Chain mode: the legacy header is not read; the length block
+// is decoded from LLR 128 on, the body from LLR 128 + 144 on, and status becomes OFDM_FRAME_HEADER where there is no valid length.
+struct ViterbiFParams : ViterbiParams {
+    int rate = 0;
+    int32_t *status_rw = nullptr;  // chain mode: read and written (`status` stays unused)
+};
+hipError_t run_viterbi_k7f(const ViterbiFParams &p, long long blocks, hipStream_t st);
+
 // channel (src/channel.rs:33-74) on the GPU (kernels_bytes.hip)
 struct ChannelParams {
     const float2 *tx = nullptr;

@@ -3,6 +3,7 @@
 // the TX / RX pipelines.  No exceptions cross the boundary; every HIP failure is mapped to OFDM_ERR_HIP.
 #include "ofdm_ctx.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -269,7 +270,8 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
     default: return OFDM_ERR_INVALID;
     }
     if (p->guard_bands != 0 && p->guard_bands != 1) return OFDM_ERR_INVALID;
-    if (p->ecc != OFDM_ECC_NONE && p->ecc != OFDM_ECC_HAMMING74 && p->ecc != OFDM_ECC_HAMMING74_SOFT && p->ecc != OFDM_ECC_CONV_K7)
+    if (p->ecc != OFDM_ECC_NONE && p->ecc != OFDM_ECC_HAMMING74 && p->ecc != OFDM_ECC_HAMMING74_SOFT && p->ecc != OFDM_ECC_CONV_K7 &&
+        framed_rate(p->ecc) < 0)
         return OFDM_ERR_INVALID; // 3 and 4 are not modes
     if (p->sync_window_reps < 1 || p->sync_window_reps > 3) return OFDM_ERR_INVALID;
     if (p->sync_backoff < 0 || p->sync_backoff > p->cp_len) return OFDM_ERR_INVALID;
@@ -462,6 +464,7 @@ int ofdm_bytes_per_symbol(const ofdm_ctx *c) { return c ? c->bytes_per_symbol() 
 int64_t ofdm_coded_len(const ofdm_ctx *c, int64_t payload_bytes) {
     if (!c || payload_bytes < 0) return OFDM_ERR_INVALID;
     if (c->prm.ecc == OFDM_ECC_CONV_K7) return 2 * (payload_bytes + 1); // rate 1/2 over the payload and one tail byte
+    if (framed_rate(c->prm.ecc) >= 0) return kConvLengthBlock + conv_body_len(payload_bytes, framed_rate(c->prm.ecc));
     return c->prm.ecc != OFDM_ECC_NONE ? ((payload_bytes + 3) / 4) * 7 : payload_bytes; // the soft decoder reads the same code
 }
 int64_t ofdm_data_symbols(const ofdm_ctx *c, int64_t payload_bytes) {
@@ -617,6 +620,44 @@ int ofdm_conv_k7_decode_soft(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, i
     p.surv = (unsigned long long *)w_surv; p.n_steps = (int)n_steps; p.terminated = terminated != 0;
     c->trace.add("k_viterbi_k7");
     HIP_TRY(c, run_viterbi_k7(p, blocks, c->stream));
+    return OFDM_OK;
+}
+
+int64_t ofdm_conv_k7_kept_bits(int64_t n_steps, int32_t rate) {
+    if (n_steps < 0 || rate < 0 || rate >= kConvRates) return OFDM_ERR_INVALID;
+    return conv_kept_bits(n_steps, rate);
+}
+int ofdm_conv_k7_encode_punctured(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_t in_stride, int64_t n_bytes, int32_t rate,
+                                  uint8_t *out, int64_t out_stride) {
+    if (!c || n_frames < 0 || n_bytes < 0 || rate < 0 || rate >= kConvRates) return OFDM_ERR_INVALID;
+    if (in_stride < n_bytes || out_stride < conv_body_len(n_bytes, rate)) return OFDM_ERR_INVALID;
+    if (n_frames && (!out || (n_bytes && !in))) return OFDM_ERR_INVALID;
+    if (!n_frames) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    c->trace.add("k_conv_encode_p");
+    HIP_TRY(c, run_conv_encode_p(in, n_frames, in_stride, nullptr, n_bytes, rate, 0, out, out_stride, nullptr, c->stream));
+    return OFDM_OK;
+}
+int ofdm_conv_k7_decode_punctured(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, int64_t llr_stride, int64_t n_steps, int32_t rate,
+                                  int32_t terminated, uint8_t *out, int64_t out_stride) {
+    if (!c || n_frames < 0 || n_steps < 0 || rate < 0 || rate >= kConvRates) return OFDM_ERR_INVALID;
+    if (n_steps > kViterbiMaxSteps) return OFDM_ERR_UNSUPPORTED;
+    if (llr_stride < conv_kept_bits(n_steps, rate) || out_stride < n_steps / 8) return OFDM_ERR_INVALID;
+    if (n_frames && n_steps && (!llr || (n_steps >= 8 && !out))) return OFDM_ERR_INVALID;
+    if (!n_frames || !n_steps) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    ViterbiFParams p;
+    long long blocks;
+    viterbi_k7_plan(n_frames, n_steps, c->num_cu, &c->tune, &blocks, &p.slab_words);
+    void *w_surv;
+    int rc = ws_get(c, 10, (size_t)(blocks * 4 * p.slab_words) * sizeof(unsigned long long), &w_surv);
+    if (rc) return rc;
+    p.llr = llr; p.llr_stride = llr_stride; p.n_frames = n_frames; p.out = out; p.out_stride = out_stride;
+    p.surv = (unsigned long long *)w_surv; p.n_steps = (int)n_steps; p.terminated = terminated != 0; p.rate = rate;
+    c->trace.add("k_viterbi_k7f");
+    HIP_TRY(c, run_viterbi_k7f(p, blocks, c->stream));
     return OFDM_OK;
 }
 
@@ -843,7 +884,8 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
     int32_t src_bytes = payload_bytes;
     if (c->prm.ecc != OFDM_ECC_NONE) { // HAMMING74 and HAMMING74_SOFT transmit the same frames, CONV_K7 its own code
         const int64_t coded = ofdm_coded_len(c, payload_bytes);
-        if (c->prm.ecc == OFDM_ECC_CONV_K7 && coded > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED; // (payload_bytes = INT32_MAX)
+        const int f_rate = framed_rate(c->prm.ecc);
+        if ((c->prm.ecc == OFDM_ECC_CONV_K7 || f_rate >= 0) && coded > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED; // (payload_bytes = INT32_MAX)
         void *cw, *cl;
         int rc = ws_get(c, 1, (size_t)(coded ? coded : 1) * (size_t)n_frames, &cw);
         if (rc) return rc;
@@ -853,6 +895,10 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
             c->trace.add("k_conv_encode");
             HIP_TRY(c, run_conv_encode(payload, n_frames, payload_stride, payload_len, payload_bytes, (uint8_t *)cw, coded,
                                        (int32_t *)cl, c->stream));
+        } else if (f_rate >= 0) {
+            c->trace.add("k_conv_encode_p");
+            HIP_TRY(c, run_conv_encode_p(payload, n_frames, payload_stride, payload_len, payload_bytes, f_rate, kConvLengthBlock,
+                                         (uint8_t *)cw, coded, (int32_t *)cl, c->stream));
         } else {
             HIP_TRY(c, run_ham_encode(payload, n_frames, payload_stride, payload_len, payload_bytes, (uint8_t *)cw, coded,
                                       (int32_t *)cl, c->stream));
@@ -915,8 +961,12 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
     // Hamming(7,4) decoding, body / 2 - 1 after Viterbi decoding (include/ofdm_hip.h)
     const int64_t body_max = raw_bytes > 16 ? raw_bytes - 16 : 0;
     if (out_stride < decode_row_bytes(c, body_max)) return OFDM_ERR_INVALID;
-    const bool conv = c->prm.ecc == OFDM_ECC_CONV_K7;
-    if (conv && 4 * body_max > kViterbiMaxSteps) return OFDM_ERR_UNSUPPORTED;
+    const int f_rate = framed_rate(c->prm.ecc);
+    const bool conv = c->prm.ecc == OFDM_ECC_CONV_K7 || f_rate >= 0;
+    // the longest trellis a frame can ask for (framed: the 72-step length block, then a body cut at the end of the capture)
+    const int64_t body_steps = f_rate < 0 ? 4 * body_max
+                                          : std::max<int64_t>(4 * kConvLengthBlock, conv_max_steps(8 * std::max<int64_t>(body_max - kConvLengthBlock, 0), f_rate));
+    if (conv && body_steps > kViterbiMaxSteps) return OFDM_ERR_UNSUPPORTED;
     if (!n_frames) return OFDM_OK;
     DeviceGuard dev_guard(c->device);
     c->trace.reset();
@@ -997,7 +1047,8 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
         HIP_TRY(c, run_chest(N, p, c->stream, c->num_cu));
         if (soft) {
             // 4s + 5s. per frame chunk: hard bytes (for the header) and LLRs in one k_sym<llr>, then the header and the ML decode of
-            // the body (k_rx_finish_soft; OFDM_ECC_CONV_K7: k_viterbi_k7, which also needs a survivor slab per resident wavefront).
+            // the body (k_rx_finish_soft; OFDM_ECC_CONV_K7: k_viterbi_k7, which also needs a survivor slab per resident wavefront;
+            // OFDM_ECC_CONV_K7F_*: k_viterbi_k7f, which reads the length from its own coded block and may set status).
             // The LLR workspace holds one chunk: at most kSoftLlrBytes whatever n_frames is.
             const int64_t llr_row = (int64_t)max_symbols * c->carriers() * c->prm.modulation;
             const int64_t llr_stride = (llr_row + 15) & ~(int64_t)15;
@@ -1006,15 +1057,15 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
             if (chunk > n_frames) chunk = n_frames;
             void *w_llr;
             if ((rc = ws_get(c, 9, (size_t)(llr_stride * chunk), &w_llr))) return rc;
-            ViterbiParams vp;
+            ViterbiFParams vp;   // (k_viterbi_k7 takes its ViterbiParams part)
             long long v_blocks = 0;
             if (conv) {
                 void *w_surv;
-                viterbi_k7_plan(chunk, 4 * body_max, c->num_cu, &c->tune, &v_blocks, &vp.slab_words);
+                viterbi_k7_plan(chunk, body_steps, c->num_cu, &c->tune, &v_blocks, &vp.slab_words);
                 if ((rc = ws_get(c, 10, (size_t)(v_blocks * 4 * vp.slab_words) * sizeof(unsigned long long), &w_surv))) return rc;
                 vp.surv = (unsigned long long *)w_surv;
                 vp.llr = (const int8_t *)w_llr; vp.llr_stride = llr_stride; vp.out_stride = out_stride;
-                vp.raw_stride = raw_stride; vp.bytes_per_symbol = bps_bytes;
+                vp.raw_stride = raw_stride; vp.bytes_per_symbol = bps_bytes; vp.rate = f_rate < 0 ? 0 : f_rate;
             }
             for (int64_t f0 = 0; f0 < n_frames; f0 += chunk) {
                 const int64_t nf = n_frames - f0 < chunk ? n_frames - f0 : chunk;
@@ -1023,9 +1074,10 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
                              (uint8_t *)w_raw + f0 * raw_stride, raw_stride, f0 == 0);
                 if (rc) return rc;
                 if (conv) {
-                    if (f0 == 0) c->trace.add("k_viterbi_k7");
+                    if (f0 == 0) c->trace.add(f_rate < 0 ? "k_viterbi_k7" : "k_viterbi_k7f");
                     vp.n_frames = nf; vp.out = out + f0 * out_stride; vp.raw = (const uint8_t *)w_raw + f0 * raw_stride;
                     vp.status = status + f0; vp.nsym = (const int32_t *)w_nsym + f0; vp.out_len = out_len + f0;
+                    if (f_rate >= 0) { vp.status_rw = status + f0; HIP_TRY(c, run_viterbi_k7f(vp, v_blocks, c->stream)); continue; }
                     HIP_TRY(c, run_viterbi_k7(vp, v_blocks, c->stream));
                     continue;
                 }

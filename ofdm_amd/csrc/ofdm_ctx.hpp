@@ -71,11 +71,16 @@ inline int ws_get(ofdm_ctx *c, int slot, size_t bytes, void **out) {
     return OFDM_OK;
 }
 
+// rate (0 = 1/2, 1 = 2/3, 2 = 3/4) of a framed convolutional mode, -1 for every other ecc value
+inline int framed_rate(int ecc) { return ecc >= OFDM_ECC_CONV_K7F_R12 && ecc <= OFDM_ECC_CONV_K7F_R34 ? ecc - OFDM_ECC_CONV_K7F_R12 : -1; }
+
 // Largest out_len the decode chain can write for a frame whose body (the bytes behind the 16-byte length header) is `body` bytes:
 // the row size every decode entry point asks of its caller (include/ofdm_hip.h)
 inline int64_t decode_row_bytes(const ofdm_ctx *c, int64_t body) {
     if (c->prm.ecc == OFDM_ECC_NONE) return body;
     if (c->prm.ecc == OFDM_ECC_CONV_K7) return body / 2 >= 1 ? body / 2 - 1 : 0; // 4 body steps = body / 2 bytes, less the tail byte
+    if (framed_rate(c->prm.ecc) >= 0)                // the steps a body cut at the end of the capture still holds, behind the length block
+        return body >= ofdm::kConvLengthBlock ? ofdm::conv_max_steps(8 * (body - ofdm::kConvLengthBlock), framed_rate(c->prm.ecc)) / 8 : 0;
     return (body / 7) * 4;                                                       // Hamming(7,4), hard or soft
 }
 
