@@ -42,6 +42,13 @@ pub const OFDM_ECC_CONV_K7: i32 = 5;
 pub const OFDM_ECC_CONV_K7F_R12: i32 = 10;
 pub const OFDM_ECC_CONV_K7F_R23: i32 = 11;
 pub const OFDM_ECC_CONV_K7F_R34: i32 = 12;
+// outer Reed-Solomon(255,223) around the frames of an inner mode, 20 + inner (inner = OFDM_ECC_NONE or a framed mode): the reference's
+// create_transmission_bytes / decipher_transmission_bytes inside encode / decode, on the device (include/ofdm_hip.h)
+pub const OFDM_ECC_RS255: i32 = 20;
+pub const OFDM_ECC_RS255_K7F_R12: i32 = 30;
+pub const OFDM_ECC_RS255_K7F_R23: i32 = 31;
+pub const OFDM_ECC_RS255_K7F_R34: i32 = 32;
+pub const OFDM_FRAME_UNCORRECTABLE: i32 = -5; // OFDM_ECC_RS255*: an RS block with more than 16 byte errors (the reference returns None)
 pub const OFDM_CONV_RATE_1_2: i32 = 0;
 pub const OFDM_CONV_RATE_2_3: i32 = 1;
 pub const OFDM_CONV_RATE_3_4: i32 = 2;
@@ -111,6 +118,10 @@ extern "C" {
                                          out_dev: *mut u8, out_stride: i64) -> c_int;
     pub fn ofdm_conv_k7_decode_punctured(ctx: *mut ofdm_ctx, llr_dev: *const i8, n_frames: i64, llr_stride: i64, n_steps: i64, rate: i32,
                                          terminated: i32, out_dev: *mut u8, out_stride: i64) -> c_int;
+    pub fn ofdm_rs255_encode_batch(ctx: *mut ofdm_ctx, in_dev: *const u8, n_frames: i64, in_stride: i64, in_len_dev: *const i32, n_bytes: i64,
+                                   out_dev: *mut u8, out_stride: i64) -> c_int;
+    pub fn ofdm_rs255_decode_batch(ctx: *mut ofdm_ctx, code_dev: *const u8, n_frames: i64, code_stride: i64, code_len_dev: *const i32,
+                                   n_code: i64, out_dev: *mut u8, out_stride: i64, out_len_dev: *mut i32, corrected_dev: *mut i32) -> c_int;
     pub fn ofdm_sc_correlate_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,
                                    n_lags: i64, d_hat_dev: *mut i32, f_delta_dev: *mut f64, metric_dev: *mut f32) -> c_int;
     pub fn ofdm_frequency_correction_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_pairs: i64, stride: i64,

@@ -57,7 +57,8 @@ enum {
     OFDM_FRAME_SHORT = -1,  /* "Input not long enough, bailing early" (src/receiver.rs:27-29) */
     OFDM_FRAME_NOSYNC = -2, /* no lag reached the Schmidl-Cox threshold */
     OFDM_FRAME_BADTIMING = -3, /* OFDM_SYNC_REFERENCE: offset = lag - 1 outside the capture (the reference panics in split_off, receiver.rs:25) */
-    OFDM_FRAME_HEADER = -4  /* fewer than 16 decoded bytes (reference panics in drain, receiver.rs:88) */
+    OFDM_FRAME_HEADER = -4, /* fewer than 16 decoded bytes (reference panics in drain, receiver.rs:88) */
+    OFDM_FRAME_UNCORRECTABLE = -5 /* OFDM_ECC_RS255*: an outer RS block with more than 16 byte errors (the reference returns None) */
 };
 
 /* ModulationScheme (src/transmitter.rs:98-104) as bits per constellation point */
@@ -70,9 +71,13 @@ enum { OFDM_MOD_BPSK = 1, OFDM_MOD_QPSK = 2, OFDM_MOD_QAM16 = 4, OFDM_MOD_QAM64 
  * "convolutional code" below).  The values 3 and 4 are REJECTED (OFDM_ERR_INVALID), as is every value not named here.
  * OFDM_ECC_CONV_K7F_R12 / _R23 / _R34: the framed convolutional modes -- the same code over the payload at rate 1/2, 2/3 or 3/4
  * (punctured), behind a rate-1/2 coded length block that decode reads INSTEAD of the uncoded 16-byte header: coded_len(p) = 18 +
- * ceil(kept(8 (p + 1), rate) / 8) (see "punctured rates and framed modes" below). */
+ * ceil(kept(8 (p + 1), rate) / 8) (see "punctured rates and framed modes" below).
+ * OFDM_ECC_RS255 / OFDM_ECC_RS255_K7F_R12 / _R23 / _R34 = 20 + inner, inner = OFDM_ECC_NONE or OFDM_ECC_CONV_K7F_*: the reference's
+ * outer Reed-Solomon(255,223) framing (create_transmission_bytes / decipher_transmission_bytes) around the inner mode's frame (see
+ * "outer Reed-Solomon code on the device" below).  21 .. 29 and 33 upwards are rejected like every other value not named. */
 enum { OFDM_ECC_NONE = 0, OFDM_ECC_HAMMING74 = 1, OFDM_ECC_HAMMING74_SOFT = 2, OFDM_ECC_CONV_K7 = 5,
-       OFDM_ECC_CONV_K7F_R12 = 10, OFDM_ECC_CONV_K7F_R23 = 11, OFDM_ECC_CONV_K7F_R34 = 12 };
+       OFDM_ECC_CONV_K7F_R12 = 10, OFDM_ECC_CONV_K7F_R23 = 11, OFDM_ECC_CONV_K7F_R34 = 12,
+       OFDM_ECC_RS255 = 20, OFDM_ECC_RS255_K7F_R12 = 30, OFDM_ECC_RS255_K7F_R23 = 31, OFDM_ECC_RS255_K7F_R34 = 32 };
 /* puncturing rate of ofdm_conv_k7_*_punctured (the framed modes' body rate is OFDM_ECC_CONV_K7F_Rxx - OFDM_ECC_CONV_K7F_R12) */
 enum { OFDM_CONV_RATE_1_2 = 0, OFDM_CONV_RATE_2_3 = 1, OFDM_CONV_RATE_3_4 = 2 };
 /* llr_scale of the OFDM_ECC_HAMMING74_SOFT and OFDM_ECC_CONV_K7 decode chains (chosen from the measured BER curves);
@@ -331,6 +336,34 @@ int ofdm_conv_k7_encode_punctured(ofdm_ctx *ctx, const uint8_t *in_dev, int64_t 
  * OFDM_ERR_UNSUPPORTED.  rate = OFDM_CONV_RATE_1_2: the bytes of ofdm_conv_k7_decode_soft. */
 int ofdm_conv_k7_decode_punctured(ofdm_ctx *ctx, const int8_t *llr_dev, int64_t n_frames, int64_t llr_stride, int64_t n_steps,
                                   int32_t rate, int32_t terminated, uint8_t *out_dev, int64_t out_stride);
+
+/* ------------------------------------------------------------------ outer Reed-Solomon code on the device (DESIGN.md 3, EXT-2 RS outer code)
+ * The code of ofdm_rs255_encode / ofdm_rs255_decode above, batched on device buffers on the context's stream (k_rs255_encode /
+ * k_rs255_decode).  Definition of a block's decode: the unique code word within 16 byte errors of the received 255 bytes if there is
+ * one, failure otherwise -- a function of the received bytes alone, also beyond 16 errors (the decoder checks that what it corrected
+ * is a code word).  The host functions are the executable form, and the device agrees with them on every input.
+ * encode: row f = in_dev[f*in_stride .. + len_f), len_f = in_len_dev[f] clamped to [0, n_bytes], or n_bytes when NULL, is coded as
+ *   ofdm_rs255_encode codes it into out_dev[f*out_stride ..]: 255 (len_f / 223 + 1) bytes; the bytes behind them, up to
+ *   ofdm_rs255_encoded_len(n_bytes), are written as 0.  in_stride >= n_bytes, out_stride >= ofdm_rs255_encoded_len(n_bytes).
+ * decode: row f = code_dev[f*code_stride .. + len_f), len_f = code_len_dev[f] clamped to [0, n_code], or n_code when NULL, is cut
+ *   into 255-byte blocks, the zero-padded remainder included even if it is empty, and 223 (len_f / 255 + 1) bytes are written to
+ *   out_dev[f*out_stride ..]; out_len_dev[f] (optional) = that count.  corrected_dev[f] (optional) = corrected bytes of the row, or
+ *   -1 if a block of the row cannot be decoded: the row is still written in full, decodable blocks corrected, the 223 data bytes of an
+ *   undecodable block as received, and the call returns OFDM_OK (OFDM_ERR_UNCORRECTABLE stays the host function's code).
+ *   code_stride >= n_code, out_stride >= ofdm_rs255_decoded_len(n_code).
+ * A violated stride rule, a negative count or a NULL context: OFDM_ERR_INVALID.  n_frames == 0: OFDM_OK, nothing is written.
+ *
+ * Frame modes ecc = OFDM_ECC_RS255* = 20 + inner.  Transmit: the frame is the inner mode's frame of ofdm_rs255_encode(payload), so
+ * coded_len(p) = inner_coded_len(255 (p / 223 + 1)); with per-row lengths row f codes its own len_f.  Receive: the inner mode's chain
+ * runs unchanged; a frame whose status it leaves at OFDM_FRAME_OK with len bytes is decoded as ofdm_rs255_decode decodes those len
+ * bytes: out_len = 223 (len / 255 + 1) -- the payload, zero-padded to whole blocks, trailing zero block included, as
+ * decipher_transmission_bytes returns it -- or, if a block cannot be decoded, status OFDM_FRAME_UNCORRECTABLE and out_len 0 (the
+ * reference returns None).  A frame with any other inner status keeps it, with out_len 0.  Rows: out_stride >= 223 (Lmax / 255 + 1),
+ * Lmax = the row size the inner mode asks for the same max_symbols (OFDM_ERR_INVALID otherwise), in every decode entry point. */
+int ofdm_rs255_encode_batch(ofdm_ctx *ctx, const uint8_t *in_dev, int64_t n_frames, int64_t in_stride, const int32_t *in_len_dev,
+                            int64_t n_bytes, uint8_t *out_dev, int64_t out_stride);
+int ofdm_rs255_decode_batch(ofdm_ctx *ctx, const uint8_t *code_dev, int64_t n_frames, int64_t code_stride, const int32_t *code_len_dev,
+                            int64_t n_code, uint8_t *out_dev, int64_t out_stride, int32_t *out_len_dev, int32_t *corrected_dev);
 
 /* ------------------------------------------------------------------ pipelines */
 

@@ -49,6 +49,7 @@ class Context {
         ofdm_params p;
         check(ofdm_default_params(&p), "ofdm_default_params");
         p.n_fft = n_fft; p.cp_len = n_fft / 4; p.guard_bands = guard_bands; p.modulation = (int)m; p.ecc = ecc; p.cfo_mode = cfo_mode;
+        ecc_ = ecc;
         if (pilots == Pilots::StdRng) {
             std::vector<double> pre(2 * (size_t)(n_fft + n_fft / 4)), trn(2 * (size_t)n_fft);
             check(ofdm_stdrng_pilots(n_fft, n_fft / 4, pre.data(), trn.data()), "ofdm_stdrng_pilots");
@@ -96,7 +97,8 @@ class Context {
     Decoded decode_capture(const ofdm_fc32 *fc, int64_t n, int32_t max_symbols = 0) {
         const int S = symbol_len();
         if (max_symbols <= 0) max_symbols = (int32_t)std::max<int64_t>((n + S - 1) / S - 10, 1);
-        const int64_t ob = std::max<int64_t>((int64_t)max_symbols * ofdm_bytes_per_symbol(ctx_), 4);
+        int64_t ob = std::max<int64_t>((int64_t)max_symbols * ofdm_bytes_per_symbol(ctx_), 4);
+        if (rs_outer(ecc_)) ob = ofdm_rs255_decoded_len(ob); // whole 223-byte blocks of the longest body, the trailing zero block included
         Decoded r;
         r.bytes.resize((size_t)ob);
         int32_t len = 0;
@@ -109,6 +111,7 @@ class Context {
         const auto fc = to_fc32(samples);
         Decoded r = decode_capture(fc.data(), (int64_t)fc.size(), max_symbols);
         if (r.status == OFDM_FRAME_SHORT) throw Error("Input not long enough, bailing early"); // src/receiver.rs:27-29
+        if (r.status == OFDM_FRAME_UNCORRECTABLE) throw Error("uncorrectable Reed-Solomon block"); // the reference returns None
         if (r.status != OFDM_FRAME_OK) throw Error("decode failed, frame status " + std::to_string(r.status));
         return std::move(r.bytes);
     }
@@ -198,9 +201,37 @@ class Context {
         if (!out.empty()) check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
         return out;
     }
+    // outer Reed-Solomon(255,223) on the device (the OFDM_ECC_RS255* modes apply it inside encode / decode): one row ->
+    // 255 (n / 223 + 1) code bytes, and one row of code bytes -> 223 (n / 255 + 1) bytes; *corrected = corrected bytes, -1 if a
+    // block has more than 16 errors (its data bytes come back as received)
+    std::vector<uint8_t> rs255_encode(const std::vector<uint8_t> &data) {
+        std::vector<uint8_t> out((size_t)ofdm_rs255_encoded_len((int64_t)data.size()));
+        DevBuf din(ctx_, data.size()), dout(ctx_, out.size());
+        if (!data.empty()) check(ofdm_memcpy_h2d(ctx_, din.p, data.data(), data.size()), "h2d");
+        check(ofdm_rs255_encode_batch(ctx_, (const uint8_t *)din.p, 1, (int64_t)data.size(), nullptr, (int64_t)data.size(), (uint8_t *)dout.p,
+                                      (int64_t)out.size()), "ofdm_rs255_encode_batch");
+        check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
+        return out;
+    }
+    std::vector<uint8_t> rs255_decode(const std::vector<uint8_t> &code, int32_t *corrected = nullptr) {
+        std::vector<uint8_t> out((size_t)ofdm_rs255_decoded_len((int64_t)code.size()));
+        DevBuf din(ctx_, code.size()), dout(ctx_, out.size()), dfix(ctx_, sizeof(int32_t));
+        if (!code.empty()) check(ofdm_memcpy_h2d(ctx_, din.p, code.data(), code.size()), "h2d");
+        check(ofdm_rs255_decode_batch(ctx_, (const uint8_t *)din.p, 1, (int64_t)code.size(), nullptr, (int64_t)code.size(), (uint8_t *)dout.p,
+                                      (int64_t)out.size(), nullptr, (int32_t *)dfix.p), "ofdm_rs255_decode_batch");
+        check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
+        if (corrected) check(ofdm_memcpy_d2h(ctx_, corrected, dfix.p, sizeof(int32_t)), "d2h");
+        return out;
+    }
 
   private:
+    // is `ecc` one of the modes with the outer Reed-Solomon code around the inner mode's frame (20 + inner)?
+    static bool rs_outer(int ecc) {
+        return ecc == OFDM_ECC_RS255 || ecc == OFDM_ECC_RS255_K7F_R12 || ecc == OFDM_ECC_RS255_K7F_R23 ||
+               ecc == OFDM_ECC_RS255_K7F_R34;
+    }
     ofdm_ctx *ctx_ = nullptr;
+    int ecc_ = OFDM_ECC_NONE;
 };
 
 // One context per (thread, parameter set), created on first use and kept: the reference's free functions are called once per

@@ -80,6 +80,8 @@ SIGNATURES = {
     "ofdm_conv_k7_kept_bits": (i64, [i64, i32]),
     "ofdm_conv_k7_encode_punctured": (C.c_int, [vp, vp, i64, i64, i64, i32, vp, i64]),
     "ofdm_conv_k7_decode_punctured": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, i64]),
+    "ofdm_rs255_encode_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64]),
+    "ofdm_rs255_decode_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp]),
     "ofdm_rx_llr_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, i64, C.c_float, vp, i64]),
     "ofdm_sc_correlate_batch": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp, vp]),
     "ofdm_frequency_correction_batch": (C.c_int, [vp, vp, i64, i64, i64, vp]),

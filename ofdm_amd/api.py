@@ -22,10 +22,14 @@ ECC_NONE, ECC_HAMMING74, ECC_HAMMING74_SOFT = 0, 1, 2
 ECC_CONV_K7 = 5  # K = 7 rate-1/2 convolutional code, Viterbi-decoded from LLRs (3 and 4 are not modes)
 # framed convolutional modes: a coded length block in front of the payload at rate 1/2, 2/3, 3/4 (tests/framed_ref.py is the definition)
 ECC_CONV_K7F_R12, ECC_CONV_K7F_R23, ECC_CONV_K7F_R34 = 10, 11, 12
+# outer Reed-Solomon(255,223) around the frames of an inner mode, 20 + inner (inner = ECC_NONE or a framed mode): the reference's
+# create_transmission_bytes / decipher_transmission_bytes inside encode / decode, on the device
+ECC_RS255, ECC_RS255_K7F_R12, ECC_RS255_K7F_R23, ECC_RS255_K7F_R34 = 20, 30, 31, 32
 CONV_RATE_1_2, CONV_RATE_2_3, CONV_RATE_3_4 = 0, 1, 2
 SOFT_LLR_SCALE = 32.0  # OFDM_SOFT_LLR_SCALE (include/ofdm_hip.h): the llr_scale of the soft decode chain
 CFO_OFF, CFO_SIGNED, CFO_ABS = 0, 1, 2
 FRAME_OK, FRAME_SHORT, FRAME_NOSYNC, FRAME_BADTIMING, FRAME_HEADER = 0, -1, -2, -3, -4
+FRAME_UNCORRECTABLE = -5  # ECC_RS255*: an outer RS block with more than 16 byte errors (the reference returns None)
 SYNC_SCHMIDL_COX, SYNC_REFERENCE = 0, 1
 RX_AUTO, RX_STAGED = 0, 1
 DEFAULT_TUNING: dict = {}  # merged under every Context's `tuning=` (tools/tune_env.py fills it; empty in tests, bench and smoke)
@@ -138,6 +142,11 @@ def _host(a: Optional[np.ndarray]):
 
 def _dev(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def conv_max_steps(bits: int, rate: int) -> int:
+    """The largest T with ofdm_conv_k7_kept_bits(T, rate) <= bits (the library's conv_max_steps; tests/framed_ref.max_steps)."""
+    return (bits // 2, 2 * (bits // 3) + (bits % 3 == 2), 3 * (bits // 4) + (0, 0, 1, 2)[bits % 4])[rate]
 
 
 class Context:
@@ -396,6 +405,55 @@ class Context:
                  "conv_k7_decode_soft")
         return out
 
+    def _rows_u8(self, t: torch.Tensor, what: str):
+        if t.dtype != torch.uint8 or t.dim() != 2 or t.device != self.device or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise OfdmError(f"{what}: expected a uint8 tensor [n_frames, n_bytes] with contiguous rows on the context's device")
+        n, nb = t.shape
+        return n, nb, (t.stride(0) if n > 1 else nb)
+
+    def _lens_i32(self, lens, n: int, what: str):
+        if lens is None:
+            return None
+        lens = lens.to(device=self.device, dtype=torch.int32).contiguous()
+        if lens.numel() != n:
+            raise OfdmError(f"{what}: lens must hold one length per row")
+        return lens
+
+    def rs255_encode(self, data: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ofdm_rs255_encode_batch: rows of data [n_frames, n_bytes] (uint8; the rows may be strided) -> [n_frames, 255 (n_bytes // 223 + 1)]
+        RS(255,223) code bytes, every row what create_transmission_bytes makes of it.  lens (int32 [n_frames], optional): the rows' own
+        lengths (clamped to [0, n_bytes]); a row is zero behind its own 255 (len // 223 + 1) bytes."""
+        n, nb, stride = self._rows_u8(data, "rs255_encode")
+        lens = self._lens_i32(lens, n, "rs255_encode")
+        out = self.empty((n, int(self.lib.ofdm_rs255_encoded_len(nb))), torch.uint8)
+        self._ck(self.lib.ofdm_rs255_encode_batch(self.h, _dev(data), n, stride, _dev(lens), nb, _dev(out), out.shape[1]), "rs255_encode_batch")
+        return out
+
+    def rs255_decode(self, code: torch.Tensor, lens: Optional[torch.Tensor] = None):
+        """ofdm_rs255_decode_batch: rows of code [n_frames, n_code] (uint8; the rows may be strided) -> (bytes [n_frames, 223 (n_code // 255 + 1)],
+        out_len int32 [n_frames], corrected int32 [n_frames]), every row what decipher_transmission_bytes makes of its own len bytes.
+        corrected = the row's corrected bytes, or -1 if a block has more than 16 byte errors: that block's data bytes are delivered as
+        received, the other blocks corrected.  Bytes behind out_len are not written."""
+        n, nc, stride = self._rows_u8(code, "rs255_decode")
+        lens = self._lens_i32(lens, n, "rs255_decode")
+        out = self.empty((n, int(self.lib.ofdm_rs255_decoded_len(nc))), torch.uint8)
+        out_len, fixed = self.empty((n,), torch.int32), self.empty((n,), torch.int32)
+        self._ck(self.lib.ofdm_rs255_decode_batch(self.h, _dev(code), n, stride, _dev(lens), nc, _dev(out), out.shape[1], _dev(out_len),
+                                                  _dev(fixed)), "rs255_decode_batch")
+        return out, out_len, fixed
+
+    def decode_row_bytes(self, max_symbols: int) -> int:
+        """Bytes per output row that the decode entry points are given for max_symbols (at least 4).  Modes without an outer code: the
+        demodulated body, which bounds what each of them delivers.  ECC_RS255*: 223 (Lmax // 255 + 1), Lmax = the longest row the
+        inner mode can deliver -- the rule of include/ofdm_hip.h."""
+        body = max(max_symbols * self.bytes_per_symbol - 16, 0)
+        if self.ecc in (ECC_RS255, ECC_RS255_K7F_R12, ECC_RS255_K7F_R23, ECC_RS255_K7F_R34):
+            lmax = body
+            if self.ecc != ECC_RS255:  # a framed inner mode: the whole bytes of the steps a cut body still holds behind the length block
+                lmax = conv_max_steps(8 * max(body - 18, 0), self.ecc - ECC_RS255_K7F_R12) // 8
+            body = int(self.lib.ofdm_rs255_decoded_len(lmax))
+        return max(body, 4)
+
     def sc_correlate(self, frames: torch.Tensor, frame_len: Optional[int] = None, n_lags: int = 0):
         """Schmidl-Cox timing / CFO per row of `frames` [n_frames, stride] -> (d_hat i32, f_delta f64, metric f32)."""
         frames = self._cx(frames)
@@ -522,7 +580,7 @@ class Context:
         frames = self._cx(frames)
         f2 = frames.view(-1, frames.shape[-1])
         n, stride = f2.shape
-        ob = max(max_symbols * self.bytes_per_symbol - 16, 4)
+        ob = self.decode_row_bytes(max_symbols)
         out = self.empty((n, ob), torch.uint8)
         res = {
             "bytes": out, "len": self.empty((n,), torch.int32), "status": self.empty((n,), torch.int32),
@@ -571,7 +629,7 @@ class Context:
         """ofdm_rx_decode_long: decode (src/receiver.rs:9-96) of ONE long capture on the device -> dict(bytes, len, status, offset,
         f_delta, metric), the result of decode_batch on the whole capture as a single frame."""
         x = self._cx(capture).reshape(-1)
-        ob = max(max_symbols * self.bytes_per_symbol - 16, 4)
+        ob = self.decode_row_bytes(max_symbols)
         out = self.empty((ob,), torch.uint8)
         ln, st, off, fd, m = C.c_int32(), C.c_int32(), C.c_int64(), C.c_double(), C.c_float()
         self._ck(self.lib.ofdm_rx_decode_long(self.h, _dev(x), x.numel(), lag_lo, lag_hi, d_hat_known, max_symbols, _dev(out), ob,
@@ -582,7 +640,7 @@ class Context:
     def decode_long_host(self, capture: np.ndarray, max_symbols: int):
         """ofdm_rx_decode_long_host: the same from a host array of complex64 (pinned_empty() memory is DMA-ed in place)."""
         x = np.ascontiguousarray(capture, dtype=np.complex64).reshape(-1)
-        ob = max(max_symbols * self.bytes_per_symbol - 16, 4)
+        ob = self.decode_row_bytes(max_symbols)
         out = np.zeros(ob, np.uint8)
         ln, st, off, fd, m = C.c_int32(), C.c_int32(), C.c_int64(), C.c_double(), C.c_float()
         self._ck(self.lib.ofdm_rx_decode_long_host(self.h, _host(x), x.size, max_symbols, _host(out), ob, C.byref(ln), C.byref(st),
@@ -596,7 +654,7 @@ class Context:
         """ofdm_rx_decode_host: decode_batch for a host array [n_frames, stride] of complex64 -> dict of host arrays."""
         x = frames if frames.dtype == np.complex64 and frames.flags.c_contiguous else np.ascontiguousarray(frames, dtype=np.complex64)
         n, stride = x.shape
-        ob = max(max_symbols * self.bytes_per_symbol - 16, 4)
+        ob = self.decode_row_bytes(max_symbols)
         res = out or {"bytes": np.zeros((n, ob), np.uint8), "len": np.zeros(n, np.int32), "status": np.zeros(n, np.int32),
                       "offset": np.zeros(n, np.int32), "f_delta": np.zeros(n, np.float64), "metric": np.zeros(n, np.float32)}
         self._ck(self.lib.ofdm_rx_decode_host(self.h, _host(x), n, stride, stride if frame_len is None else frame_len, n_lags,
@@ -698,6 +756,7 @@ def decode(samples, guard_bands: Optional[bool] = None, modulation: Optional[int
         raise DecodeError("Input not long enough, bailing early")
     if status != FRAME_OK:
         raise DecodeError({FRAME_NOSYNC: "no preamble found", FRAME_HEADER: "no length header decoded",
+                           FRAME_UNCORRECTABLE: "uncorrectable Reed-Solomon block (the reference returns None)",
                            FRAME_BADTIMING: "timing offset outside the capture (the reference panics in split_off)"}.get(status, "decode failed"))
     n = int(res["len"][0])
     return bytes(res["bytes"][0, :n].cpu().numpy())

@@ -341,6 +341,32 @@ struct ViterbiFParams : ViterbiParams {
 };
 hipError_t run_viterbi_k7f(const ViterbiFParams &p, long long blocks, hipStream_t st);
 
+// ---- outer Reed-Solomon(255,223) (ofdm_rs255_*_batch and the OFDM_ECC_RS255* modes; kernels_rs.hip, definition: outer_code.hip)
+// rows of n_bytes data bytes (row f: in_len[f], clamped, when in_len is given) -> rows of 255 (n_bytes / 223 + 1) code bytes, zero
+// behind the row's own 255 (len_f / 223 + 1); out_len (optional) receives that length
+struct Rs255EncodeParams {
+    const uint8_t *in = nullptr;
+    long long n_frames = 0, in_stride = 0, n_bytes = 0;
+    const int32_t *in_len = nullptr;
+    uint8_t *out = nullptr;
+    long long out_stride = 0;
+    int32_t *out_len = nullptr;
+};
+hipError_t run_rs255_encode(const Rs255EncodeParams &p, int num_cu, const Tuning *tune, hipStream_t st);
+// rows of n_code code bytes (row f: code_len[f], clamped, when code_len is given) -> 223 (len_f / 255 + 1) bytes a row; corrected
+// (optional): corrected bytes of the row, -1 if a block could not be decoded (its data bytes leave as received).  Chain mode
+// (status_rw != nullptr; out_len required, it may be code_len itself): rows with status != 0 are skipped with out_len 0, a row with an
+// undecodable block gets status OFDM_FRAME_UNCORRECTABLE and out_len 0.
+struct Rs255DecodeParams {
+    const uint8_t *code = nullptr;
+    long long n_frames = 0, code_stride = 0, n_code = 0;
+    const int32_t *code_len = nullptr;
+    uint8_t *out = nullptr;
+    long long out_stride = 0;
+    int32_t *out_len = nullptr, *corrected = nullptr, *status_rw = nullptr;
+};
+hipError_t run_rs255_decode(const Rs255DecodeParams &p, int num_cu, const Tuning *tune, hipStream_t st);
+
 // channel (src/channel.rs:33-74) on the GPU (kernels_bytes.hip)
 struct ChannelParams {
     const float2 *tx = nullptr;

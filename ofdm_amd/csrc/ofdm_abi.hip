@@ -271,8 +271,8 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
     }
     if (p->guard_bands != 0 && p->guard_bands != 1) return OFDM_ERR_INVALID;
     if (p->ecc != OFDM_ECC_NONE && p->ecc != OFDM_ECC_HAMMING74 && p->ecc != OFDM_ECC_HAMMING74_SOFT && p->ecc != OFDM_ECC_CONV_K7 &&
-        framed_rate(p->ecc) < 0)
-        return OFDM_ERR_INVALID; // 3 and 4 are not modes
+        framed_rate(p->ecc) < 0 && !rs_outer(p->ecc))
+        return OFDM_ERR_INVALID; // 3 and 4 are not modes, nor are 21 .. 29
     if (p->sync_window_reps < 1 || p->sync_window_reps > 3) return OFDM_ERR_INVALID;
     if (p->sync_backoff < 0 || p->sync_backoff > p->cp_len) return OFDM_ERR_INVALID;
     if (p->cfo_mode < OFDM_CFO_OFF || p->cfo_mode > OFDM_CFO_ABS) return OFDM_ERR_INVALID;
@@ -461,11 +461,16 @@ int ofdm_memset(ofdm_ctx *c, void *dev, int value, size_t bytes) {
 int ofdm_symbol_len(const ofdm_ctx *c) { return c ? c->S() : OFDM_ERR_INVALID; }
 int ofdm_data_carriers(const ofdm_ctx *c) { return c ? c->carriers() : OFDM_ERR_INVALID; }
 int ofdm_bytes_per_symbol(const ofdm_ctx *c) { return c ? c->bytes_per_symbol() : OFDM_ERR_INVALID; }
+// coded bytes of n payload bytes in mode `ecc` (no RS mode)
+static int64_t inner_coded_len(int ecc, int64_t n) {
+    if (ecc == OFDM_ECC_CONV_K7) return 2 * (n + 1); // rate 1/2 over the payload and one tail byte
+    if (framed_rate(ecc) >= 0) return kConvLengthBlock + conv_body_len(n, framed_rate(ecc));
+    return ecc != OFDM_ECC_NONE ? ((n + 3) / 4) * 7 : n; // the soft decoder reads the same code
+}
 int64_t ofdm_coded_len(const ofdm_ctx *c, int64_t payload_bytes) {
     if (!c || payload_bytes < 0) return OFDM_ERR_INVALID;
-    if (c->prm.ecc == OFDM_ECC_CONV_K7) return 2 * (payload_bytes + 1); // rate 1/2 over the payload and one tail byte
-    if (framed_rate(c->prm.ecc) >= 0) return kConvLengthBlock + conv_body_len(payload_bytes, framed_rate(c->prm.ecc));
-    return c->prm.ecc != OFDM_ECC_NONE ? ((payload_bytes + 3) / 4) * 7 : payload_bytes; // the soft decoder reads the same code
+    // OFDM_ECC_RS255*: the inner mode codes the RS blocks
+    return inner_coded_len(inner_ecc(c->prm.ecc), rs_outer(c->prm.ecc) ? ofdm_rs255_encoded_len(payload_bytes) : payload_bytes);
 }
 int64_t ofdm_data_symbols(const ofdm_ctx *c, int64_t payload_bytes) {
     if (!c || payload_bytes < 0) return OFDM_ERR_INVALID;
@@ -658,6 +663,35 @@ int ofdm_conv_k7_decode_punctured(ofdm_ctx *c, const int8_t *llr, int64_t n_fram
     p.surv = (unsigned long long *)w_surv; p.n_steps = (int)n_steps; p.terminated = terminated != 0; p.rate = rate;
     c->trace.add("k_viterbi_k7f");
     HIP_TRY(c, run_viterbi_k7f(p, blocks, c->stream));
+    return OFDM_OK;
+}
+
+// outer Reed-Solomon(255,223) on device rows (kernels_rs.hip)
+int ofdm_rs255_encode_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_t in_stride, const int32_t *in_len, int64_t n_bytes,
+                            uint8_t *out, int64_t out_stride) {
+    if (!c || n_frames < 0 || n_bytes < 0 || in_stride < n_bytes || out_stride < ofdm_rs255_encoded_len(n_bytes)) return OFDM_ERR_INVALID;
+    if (n_frames && (!out || (n_bytes && !in))) return OFDM_ERR_INVALID;
+    if (!n_frames) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    Rs255EncodeParams p;
+    p.in = in; p.n_frames = n_frames; p.in_stride = in_stride; p.n_bytes = n_bytes; p.in_len = in_len; p.out = out; p.out_stride = out_stride;
+    c->trace.add("k_rs255_encode");
+    HIP_TRY(c, run_rs255_encode(p, c->num_cu, &c->tune, c->stream));
+    return OFDM_OK;
+}
+int ofdm_rs255_decode_batch(ofdm_ctx *c, const uint8_t *code, int64_t n_frames, int64_t code_stride, const int32_t *code_len, int64_t n_code,
+                            uint8_t *out, int64_t out_stride, int32_t *out_len, int32_t *corrected) {
+    if (!c || n_frames < 0 || n_code < 0 || code_stride < n_code || out_stride < ofdm_rs255_decoded_len(n_code)) return OFDM_ERR_INVALID;
+    if (n_frames && (!out || (n_code && !code))) return OFDM_ERR_INVALID;
+    if (!n_frames) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    Rs255DecodeParams p;
+    p.code = code; p.n_frames = n_frames; p.code_stride = code_stride; p.n_code = n_code; p.code_len = code_len; p.out = out;
+    p.out_stride = out_stride; p.out_len = out_len; p.corrected = corrected;
+    c->trace.add("k_rs255_decode");
+    HIP_TRY(c, run_rs255_decode(p, c->num_cu, &c->tune, c->stream));
     return OFDM_OK;
 }
 
@@ -882,28 +916,41 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
     const int S = c->S();
     const uint8_t *src = payload; int64_t src_stride = payload_stride; const int32_t *src_len = payload_len;
     int32_t src_bytes = payload_bytes;
-    if (c->prm.ecc != OFDM_ECC_NONE) { // HAMMING74 and HAMMING74_SOFT transmit the same frames, CONV_K7 its own code
-        const int64_t coded = ofdm_coded_len(c, payload_bytes);
-        const int f_rate = framed_rate(c->prm.ecc);
-        if ((c->prm.ecc == OFDM_ECC_CONV_K7 || f_rate >= 0) && coded > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED; // (payload_bytes = INT32_MAX)
+    const int ecc = inner_ecc(c->prm.ecc);
+    if (rs_outer(c->prm.ecc)) { // OFDM_ECC_RS255*: the inner mode's frame of the RS-coded rows
+        const int64_t rs_len = ofdm_rs255_encoded_len(payload_bytes);
+        if (rs_len > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED;
+        void *rw, *rl;
+        int rc = ws_get(c, 11, (size_t)rs_len * (size_t)n_frames, &rw);
+        if (rc) return rc;
+        if ((rc = ws_get(c, 12, sizeof(int32_t) * (size_t)n_frames, &rl))) return rc;
+        Rs255EncodeParams rp;
+        rp.in = payload; rp.n_frames = n_frames; rp.in_stride = payload_stride; rp.n_bytes = payload_bytes; rp.in_len = payload_len;
+        rp.out = (uint8_t *)rw; rp.out_stride = rs_len; rp.out_len = payload_len ? (int32_t *)rl : nullptr;
+        c->trace.add("k_rs255_encode");
+        HIP_TRY(c, run_rs255_encode(rp, c->num_cu, &c->tune, c->stream));
+        src = (const uint8_t *)rw; src_stride = rs_len; src_len = payload_len ? (const int32_t *)rl : nullptr; src_bytes = (int32_t)rs_len;
+    }
+    if (ecc != OFDM_ECC_NONE) { // HAMMING74 and HAMMING74_SOFT transmit the same frames, CONV_K7 its own code
+        const int64_t coded = inner_coded_len(ecc, src_bytes);
+        const int f_rate = framed_rate(ecc);
+        if ((ecc == OFDM_ECC_CONV_K7 || f_rate >= 0) && coded > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED; // (payload_bytes = INT32_MAX)
         void *cw, *cl;
         int rc = ws_get(c, 1, (size_t)(coded ? coded : 1) * (size_t)n_frames, &cw);
         if (rc) return rc;
         rc = ws_get(c, 2, sizeof(int32_t) * (size_t)n_frames, &cl);
         if (rc) return rc;
-        if (c->prm.ecc == OFDM_ECC_CONV_K7) {
+        if (ecc == OFDM_ECC_CONV_K7) {
             c->trace.add("k_conv_encode");
-            HIP_TRY(c, run_conv_encode(payload, n_frames, payload_stride, payload_len, payload_bytes, (uint8_t *)cw, coded,
-                                       (int32_t *)cl, c->stream));
+            HIP_TRY(c, run_conv_encode(src, n_frames, src_stride, src_len, src_bytes, (uint8_t *)cw, coded, (int32_t *)cl, c->stream));
         } else if (f_rate >= 0) {
             c->trace.add("k_conv_encode_p");
-            HIP_TRY(c, run_conv_encode_p(payload, n_frames, payload_stride, payload_len, payload_bytes, f_rate, kConvLengthBlock,
-                                         (uint8_t *)cw, coded, (int32_t *)cl, c->stream));
+            HIP_TRY(c, run_conv_encode_p(src, n_frames, src_stride, src_len, src_bytes, f_rate, kConvLengthBlock, (uint8_t *)cw, coded,
+                                         (int32_t *)cl, c->stream));
         } else {
-            HIP_TRY(c, run_ham_encode(payload, n_frames, payload_stride, payload_len, payload_bytes, (uint8_t *)cw, coded,
-                                      (int32_t *)cl, c->stream));
+            HIP_TRY(c, run_ham_encode(src, n_frames, src_stride, src_len, src_bytes, (uint8_t *)cw, coded, (int32_t *)cl, c->stream));
         }
-        src = (const uint8_t *)cw; src_stride = coded; src_len = payload_len ? (const int32_t *)cl : nullptr;
+        src = (const uint8_t *)cw; src_stride = coded; src_len = src_len ? (const int32_t *)cl : nullptr;
         src_bytes = (int32_t)coded;
     }
     SymParams p = base_params(c);
@@ -948,9 +995,45 @@ int ofdm_abi_rx_decode_known(ofdm_ctx *c, const ofdm_fc32 *in, int64_t frame_len
     return rx_decode_impl(c, in, 1, frame_len, frame_len, 0, max_symbols, out, out_stride, out_len, status, offset, f_delta_out, metric_out, &k);
 }
 
+// The decode chain of mode `ecc` (the context's own mode, or the inner mode of an RS mode) into rows out / out_stride
+static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                           int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
+                           int32_t *status, int32_t *offset, double *f_delta, float *metric, const KnownSync *known);
+
 static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
                           int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
                           int32_t *status, int32_t *offset, double *f_delta, float *metric, const KnownSync *known) {
+    if (!c) return OFDM_ERR_INVALID;
+    if (!rs_outer(c->prm.ecc))
+        return rx_decode_inner(c, c->prm.ecc, in, n_frames, frame_stride, frame_len, n_lags, max_symbols, out, out_stride, out_len, status,
+                               offset, f_delta, metric, known);
+    // OFDM_ECC_RS255*: the inner mode's chain into a workspace (dword rows: the fused frame kernels write their payload there
+    // directly), then k_rs255_decode over what every frame delivered; out_len serves both as the inner length and the final one
+    if (n_frames < 0 || frame_len <= 0 || max_symbols <= 0) return OFDM_ERR_INVALID;
+    if (n_frames && (!in || !out || !out_len || !status)) return OFDM_ERR_INVALID;
+    const int64_t raw_bytes = (int64_t)max_symbols * c->bytes_per_symbol();
+    const int64_t inner_max = inner_row_bytes(inner_ecc(c->prm.ecc), raw_bytes > 16 ? raw_bytes - 16 : 0);
+    if (out_stride < ofdm_rs255_decoded_len(inner_max)) return OFDM_ERR_INVALID;
+    if (!n_frames) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    const int64_t row = (std::max<int64_t>(inner_max, 4) + 3) & ~(int64_t)3;
+    void *w_rows;
+    int rc = ws_get(c, 11, (size_t)row * (size_t)n_frames, &w_rows);
+    if (rc) return rc;
+    rc = rx_decode_inner(c, inner_ecc(c->prm.ecc), in, n_frames, frame_stride, frame_len, n_lags, max_symbols, (uint8_t *)w_rows, row, out_len,
+                         status, offset, f_delta, metric, known);
+    if (rc) return rc;
+    Rs255DecodeParams rp;
+    rp.code = (const uint8_t *)w_rows; rp.n_frames = n_frames; rp.code_stride = row; rp.n_code = inner_max; rp.code_len = out_len;
+    rp.out = out; rp.out_stride = out_stride; rp.out_len = out_len; rp.status_rw = status;
+    c->trace.add("k_rs255_decode");
+    HIP_TRY(c, run_rs255_decode(rp, c->num_cu, &c->tune, c->stream));
+    return OFDM_OK;
+}
+
+static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                           int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
+                           int32_t *status, int32_t *offset, double *f_delta, float *metric, const KnownSync *known) {
     if (!c || n_frames < 0 || frame_len <= 0 || max_symbols <= 0) return OFDM_ERR_INVALID;
     if (n_frames && (!in || !out || !out_len || !status)) return OFDM_ERR_INVALID;
     if (n_frames > 1 && frame_stride <= 0) return OFDM_ERR_INVALID;
@@ -960,9 +1043,9 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
     // rows must hold what k_rx_finish can write: the whole body without an outer code, floor(body / 7) * 4 bytes after
     // Hamming(7,4) decoding, body / 2 - 1 after Viterbi decoding (include/ofdm_hip.h)
     const int64_t body_max = raw_bytes > 16 ? raw_bytes - 16 : 0;
-    if (out_stride < decode_row_bytes(c, body_max)) return OFDM_ERR_INVALID;
-    const int f_rate = framed_rate(c->prm.ecc);
-    const bool conv = c->prm.ecc == OFDM_ECC_CONV_K7 || f_rate >= 0;
+    if (out_stride < inner_row_bytes(ecc, body_max)) return OFDM_ERR_INVALID;
+    const int f_rate = framed_rate(ecc);
+    const bool conv = ecc == OFDM_ECC_CONV_K7 || f_rate >= 0;
     // the longest trellis a frame can ask for (framed: the 72-step length block, then a body cut at the end of the capture)
     const int64_t body_steps = f_rate < 0 ? 4 * body_max
                                           : std::max<int64_t>(4 * kConvLengthBlock, conv_max_steps(8 * std::max<int64_t>(body_max - kConvLengthBlock, 0), f_rate));
@@ -1017,14 +1100,14 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
     // 3+4. channel estimate from the 5 training blocks and per data symbol CP strip + FFT + equalise + pilot phase +
     //      demap (receiver.rs:44-83).  N = 64: one fused wave-centric kernel; otherwise the generic pair.
     bool fused = false, finished = false;
-    const bool soft = c->prm.ecc == OFDM_ECC_HAMMING74_SOFT || conv; // the fused frame kernels have no LLR epilogue: the generic chain
+    const bool soft = ecc == OFDM_ECC_HAMMING74_SOFT || conv; // the fused frame kernels have no LLR epilogue: the generic chain
     if (N == 1024 && !soft) { // one workgroup per frame: channel estimate kept in registers, 16 x 64 FFT (kernels_rx1024.hip)
         const bool off = c->tune.no_rxframe1024 != 0; // A/B switch
         const SymParams p = rx_params(c, x, n_frames, frame_stride, frame_len, offs, fd, (const int32_t *)w_nsym, (uint8_t *)w_raw, raw_stride);
         // the kernel also parses the length header, truncates and Hamming-decodes into the caller's rows when they are 4-byte aligned
         bool fin = false;
         const int r = fast_path(c, off ? hipErrorNotSupported
-                                       : run_rxframe1024(p, nullptr, c->stream, c->num_cu, out, out_stride, out_len, c->prm.ecc, &fin));
+                                       : run_rxframe1024(p, nullptr, c->stream, c->num_cu, out, out_stride, out_len, ecc, &fin));
         if (r == OFDM_OK) { fused = true; finished = fin; }
         else if (r != kNextPath) return r;
     }
@@ -1032,7 +1115,7 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
         SymParams p = rx_params(c, x, n_frames, frame_stride, frame_len, offs, fd, (const int32_t *)w_nsym, (uint8_t *)w_raw, raw_stride);
         p.syms_per_frame = max_symbols; // (the launcher's "is there room for a whole frame in the capture" test)
         // without an outer code the kernel also parses the length header and writes the payload to its final place
-        const bool fin = c->prm.ecc == OFDM_ECC_NONE && (reinterpret_cast<uintptr_t>(out) & 3) == 0 && (out_stride & 3) == 0;
+        const bool fin = ecc == OFDM_ECC_NONE && (reinterpret_cast<uintptr_t>(out) & 3) == 0 && (out_stride & 3) == 0;
         void *w_cut;
         if ((rc = ws_get(c, 8, sizeof(int32_t) * (size_t)(n_frames + 4), &w_cut))) return rc;
         const int r = fast_path(c, fin ? run_rxframe64(p, nullptr, c->stream, c->num_cu, out, out_stride, out_len, nullptr, nullptr, (int32_t *)w_cut)
@@ -1096,7 +1179,7 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
     if (!finished) {
         c->trace.add("k_rx_finish");
         HIP_TRY(c, run_rx_finish((const uint8_t *)w_raw, raw_stride, n_frames, status, (const int32_t *)w_nsym, bps_bytes,
-                                 c->prm.ecc, out, out_stride, out_len, c->stream));
+                                 ecc, out, out_stride, out_len, c->stream));
     }
     return OFDM_OK;
 }

@@ -30,7 +30,7 @@ struct ofdm_ctx {
     ofdm::ScStats sc_stats;             // list counters of the last Schmidl-Cox search (ofdm_get_tuning "stat_sc_*")
     int32_t *d_stats = nullptr;         // [2] their home on the device (owned by the context)
     // workspaces (grown on demand, never inside a captured region)
-    Workspace ws[11];
+    Workspace ws[13];
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     HostPipe *pipe = nullptr;     // created by the first host-buffer call, freed by ofdm_destroy
 
@@ -74,14 +74,25 @@ inline int ws_get(ofdm_ctx *c, int slot, size_t bytes, void **out) {
 // rate (0 = 1/2, 1 = 2/3, 2 = 3/4) of a framed convolutional mode, -1 for every other ecc value
 inline int framed_rate(int ecc) { return ecc >= OFDM_ECC_CONV_K7F_R12 && ecc <= OFDM_ECC_CONV_K7F_R34 ? ecc - OFDM_ECC_CONV_K7F_R12 : -1; }
 
-// Largest out_len the decode chain can write for a frame whose body (the bytes behind the 16-byte length header) is `body` bytes:
-// the row size every decode entry point asks of its caller (include/ofdm_hip.h)
-inline int64_t decode_row_bytes(const ofdm_ctx *c, int64_t body) {
-    if (c->prm.ecc == OFDM_ECC_NONE) return body;
-    if (c->prm.ecc == OFDM_ECC_CONV_K7) return body / 2 >= 1 ? body / 2 - 1 : 0; // 4 body steps = body / 2 bytes, less the tail byte
-    if (framed_rate(c->prm.ecc) >= 0)                // the steps a body cut at the end of the capture still holds, behind the length block
-        return body >= ofdm::kConvLengthBlock ? ofdm::conv_max_steps(8 * (body - ofdm::kConvLengthBlock), framed_rate(c->prm.ecc)) / 8 : 0;
+// OFDM_ECC_RS255* = 20 + inner: the outer Reed-Solomon code around the frames of the inner mode (OFDM_ECC_NONE or a framed mode)
+inline bool rs_outer(int ecc) { return ecc == OFDM_ECC_RS255 || (ecc >= OFDM_ECC_RS255_K7F_R12 && ecc <= OFDM_ECC_RS255_K7F_R34); }
+// the mode whose frames travel: ecc itself, or the inner mode of an RS mode
+inline int inner_ecc(int ecc) { return rs_outer(ecc) ? ecc - OFDM_ECC_RS255 : ecc; }
+
+// Largest out_len the decode chain of mode `ecc` (no RS mode) can write for a frame whose body (the bytes behind the 16-byte length
+// header) is `body` bytes
+inline int64_t inner_row_bytes(int ecc, int64_t body) {
+    if (ecc == OFDM_ECC_NONE) return body;
+    if (ecc == OFDM_ECC_CONV_K7) return body / 2 >= 1 ? body / 2 - 1 : 0; // 4 body steps = body / 2 bytes, less the tail byte
+    if (framed_rate(ecc) >= 0)                       // the steps a body cut at the end of the capture still holds, behind the length block
+        return body >= ofdm::kConvLengthBlock ? ofdm::conv_max_steps(8 * (body - ofdm::kConvLengthBlock), framed_rate(ecc)) / 8 : 0;
     return (body / 7) * 4;                                                       // Hamming(7,4), hard or soft
+}
+// ... of the context's mode: the row size every decode entry point asks of its caller (include/ofdm_hip.h).  RS modes: the decoded
+// blocks of the longest row the inner mode can deliver.
+inline int64_t decode_row_bytes(const ofdm_ctx *c, int64_t body) {
+    const int64_t inner = inner_row_bytes(inner_ecc(c->prm.ecc), body);
+    return rs_outer(c->prm.ecc) ? ofdm_rs255_decoded_len(inner) : inner;
 }
 
 // internal cross-file helpers (C linkage only because their definitions sit inside the extern "C" blocks; not in ofdm_hip.h)

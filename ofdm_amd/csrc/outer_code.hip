@@ -5,8 +5,10 @@
 // 0x11d, generator element 2, generator polynomial prod_{i<32} (x - 2^i) (first consecutive root 0), code word =
 // data followed by the 32 remainder bytes.  The encoder is pinned by that text's published vectors
 // (tests/test_abi_cpu.py); the decoder (syndromes, Berlekamp-Massey, Chien, Forney) corrects up to 16 bytes per block,
-// which is unique decoding: any correct decoder returns the same bytes.  Beyond 16 errors the crate's behaviour
-// (failure vs. miscorrection) is not reproduced: "parity unpinned".
+// which is unique decoding: any correct decoder returns the same bytes.  Beyond 16 errors correct_block checks that what it
+// corrected is a code word, so a block's outcome is "the code word within 16 byte errors of the input if there is one, failure
+// otherwise" -- a function of the input alone.  tests/test_rs_modes_cpu.py holds it to the oracle on such inputs too, and
+// k_rs255_decode (kernels_rs.hip) is held to this file.
 // This is off the roofline by design: tens of bytes per OFDM symbol, on the host.
 #include "../../include/ofdm_hip.h"
 #include <cstring>
