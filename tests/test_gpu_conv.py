@@ -10,6 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv_ref as cr  # noqa: E402
+from chain_refs import conv_reference_decode as _reference_decode  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -149,28 +150,6 @@ def _data_snr(n, snr):
     # ofdm_channel_batch scales its noise by the whole frame's pseudo-variance (see test_gpu_soft.py): the data symbols of a larger N
     # see ~10 log10(N / 64) dB less than the channel's snr_db
     return snr + 10.0 * np.log10(n / 64)
-
-
-def _reference_decode(c, rx, r, max_symbols):
-    """per frame with status 0: (out_len, bytes) by the rule of the header -- the length header from the hard bytes, then
-    conv_ref.viterbi over the LLRs rx_llr returns for the frame"""
-    hk = c.estimate_channel(rx, r["offset"], r["f_delta"])
-    L = c.rx_llr(rx, max_symbols, first_symbol=10, offset=r["offset"], f_delta=r["f_delta"], hk=hk)
-    hard = c.rx_demod(rx, max_symbols, first_symbol=10, offset=r["offset"], f_delta=r["f_delta"], hk=hk)
-    c.synchronize()
-    L, hard = L.cpu().numpy(), hard.cpu().numpy()
-    body = max_symbols * c.bytes_per_symbol - 16
-    want = {}
-    for f in range(rx.shape[0]):
-        if int(r["status"][f]) != 0:
-            continue
-        lo = int.from_bytes(bytes(hard[f, :8]), "little")
-        hi = int.from_bytes(bytes(hard[f, 8:16]), "little")
-        keep = lo if (hi == 0 and lo < body) else body
-        n_out = max(keep // 2 - 1, 0)
-        dec = cr.viterbi(L[f, 128:128 + 8 * keep], terminated=(hi == 0 and lo <= body))
-        want[f] = (n_out, bytes(dec[:n_out]))
-    return want
 
 
 def _assert_is_reference(r, want):

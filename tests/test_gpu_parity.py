@@ -135,6 +135,30 @@ def test_hamming74(api, orc):
         assert want[:n] == bytes(data)
 
 
+@pytest.mark.parametrize("grid_cap", [0, 1])
+def test_hamming74_decode_every_seven_bit_word(api, orc, grid_cap):
+    """All 128 seven-bit words -- the 16 code words, their 112 single-error neighbours, which are every other word: a double error
+    decodes to a wrong nibble, and only the oracle says which -- in each of the eight code-word slots of a 7-byte block, the other
+    seven slots holding valid code words: 1 024 blocks through k_ham_decode, bytes and `fixed` count against the oracle."""
+    rng = np.random.default_rng(74)
+    ctx = api.Context(tuning={"grid_cap": grid_cap} if grid_cap else None)
+    data = rng.integers(0, 256, 4 * 8 * 128, dtype=np.uint8)
+    words = np.unpackbits(np.frombuffer(orc.hamming74_encode(bytes(data)), np.uint8), bitorder="little").reshape(8 * 128, 8, 7).copy()
+    for slot in range(8):
+        for w in range(128):
+            words[slot * 128 + w, slot] = [(w >> b) & 1 for b in range(7)]
+    code = np.packbits(words.reshape(-1), bitorder="little")
+    assert code.size == 7 * 1024
+    dec, fixed = ctx.hamming74_decode(dev(ctx, code))
+    want, want_fixed = orc.hamming74_decode(bytes(code))
+    got = host(dec)
+    assert got.size == len(want) == 4 * 1024
+    bad = np.nonzero(got.reshape(1024, 4) != np.frombuffer(want, np.uint8).reshape(1024, 4))[0]
+    assert bad.size == 0, [(int(b) // 128, int(b) % 128) for b in bad[:8]]          # (slot, word)
+    assert int(host(fixed)[0]) == want_fixed
+    assert want_fixed == 8 * (128 - 16)                                               # every word that is no code word counts once
+
+
 # ------------------------------------------------------------------ config 2: RX demod (FFT + demap)
 @pytest.mark.parametrize("n,mod,guard,nsym", [(64, 6, True, 320), (64, 2, False, 64), (64, 1, True, 40),
                                               (128, 4, True, 33), (1024, 6, True, 12), (4096, 8, True, 5),

@@ -10,6 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import rs_vectors as rv  # noqa: E402
+from chain_refs import rs_composition as _composition  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -176,22 +177,6 @@ def _data_snr(n, snr):
     # ofdm_channel_batch scales its noise by the whole frame's pseudo-variance: the data symbols of a larger N see
     # ~10 log10(N / 64) dB less than the channel's snr_db (tests/test_gpu_conv.py)
     return snr + 10.0 * np.log10(n / 64)
-
-
-def _composition(c, rx, max_symbols):
-    """what the RS mode must deliver: the host RS decoder over what the inner mode's context delivers for the same capture"""
-    inner = _ctx(n_fft=c.n_fft, modulation=c.modulation, guard_bands=c.guard_bands, ecc=c.ecc - 20)
-    ri = inner.decode_batch(rx, max_symbols=max_symbols)
-    inner.synchronize()
-    status, ln, by = ri["status"].cpu().numpy(), ri["len"].cpu().numpy(), ri["bytes"].cpu().numpy()
-    want = []
-    for f in range(rx.shape[0]):
-        if status[f] != 0:
-            want.append((int(status[f]), 0, b""))
-            continue
-        data, out_len, fixed = rv.host_row(c.lib, by[f], int(ln[f]))
-        want.append((UNCORRECTABLE, 0, b"") if fixed < 0 else (0, out_len, data))
-    return ri, want
 
 
 def _assert_is_composition(r, ri, want):

@@ -9,6 +9,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import soft_ref as sr  # noqa: E402
+from chain_refs import soft_reference_decode  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -187,12 +188,15 @@ def test_chain_is_the_composition_of_the_stages(n, mod):
     L = s.rx_llr(rx, D, first_symbol=10, offset=r["offset"], f_delta=r["f_delta"], hk=hk)
     s.synchronize()
     assert int((r["status"] == 0).sum()) >= 5
+    ref = soft_reference_decode(s, rx, r, D)     # the length from the hard header bytes, the blocks from soft_ref over the same LLRs
+    assert len(ref) >= 5
     for f in range(rx.shape[0]):
         if int(r["status"][f]) != 0:
             continue
         n_out = int(r["len"][f])
         want = s.hamming74_decode_soft(L[f, 128:128 + n_out // 4 * 56].contiguous())
         assert torch.equal(r["bytes"][f, :n_out], want), f
+        assert (n_out, bytes(want.cpu().numpy())) == ref[f], f
     s.set_tuning("soft_chunk_frames", 3)           # many chunks of the LLR workspace
     r3 = s.decode_batch(rx, max_symbols=D)
     s.set_tuning("soft_chunk_frames", 0)

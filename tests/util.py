@@ -66,6 +66,70 @@ def make_symbols_np(orc, rng, n_sym, n_fft, guard, mod, snr_db=30.0):
     return fc32(x), data
 
 
+def _raw_data_symbols(orc, stream, n_fft, guard, mod):
+    """prefix_block(encode_block(modulate(stream))) of a whole byte stream, unscaled, as orc.encode builds its data symbols"""
+    pts = orc.modulate(bytes(stream), mod)
+    out, used = [], 0
+    while used < pts.size:
+        blk, c = orc.encode_block(pts[used:], n_fft, guard)
+        used += c
+        out.append(orc.prefix_block(blk))
+    return np.concatenate(out)
+
+
+def forge_frame(orc, stream: bytes, n_fft, guard, mod, allow_louder=False):
+    """A frame whose 16-byte length header is whatever `stream` starts with: `stream` is the WHOLE byte stream of the data symbols,
+    header included.  The ten header blocks and the frame's scale come from orc.encode of a seeded random payload of the same
+    length (an honest frame that is no louder than its header): scale = honest sample / raw sample at the largest raw sample of
+    the honest data symbols, which normalize (src/transmitter.rs:183-194) makes one real constant per frame.
+    Returns complex128 [(10 + D) S].
+    Only for streams that are no louder than the header blocks (the normalisation then does not depend on the data symbols): asserted.
+    allow_louder: a stream that is louder (a run of equal bits that fills a symbol with equal points: a header of ones in BPSK, a
+    code word of zeros in 64-QAM) is passed through the oracle's normalize instead, which divides the whole frame by the new
+    maximum as orc.encode would have."""
+    stream = bytes(stream)
+    assert len(stream) >= 16
+    S = n_fft + n_fft // 4
+    n_body = len(stream) - 16
+    peak = lambda x: max(x.real.max(), x.imag.max())          # normalize's maximum: signed, over re and im
+    for seed in range(8):                                     # the first filler whose frame is no louder than its header
+        filler = bytes(np.random.default_rng([n_body, seed]).integers(0, 256, n_body, dtype=np.uint8))
+        honest = orc.encode(filler, guard, mod, n_fft)
+        if peak(honest[:10 * S]) == 1.0:
+            break
+    assert peak(honest[:10 * S]) == peak(honest) == 1.0, "no honest frame of this length with full scale in its header"
+    raw_honest = _raw_data_symbols(orc, n_body.to_bytes(16, "little") + filler, n_fft, guard, mod)
+    raw = _raw_data_symbols(orc, stream, n_fft, guard, mod)
+    assert honest.size == 10 * S + raw_honest.size and raw.size == raw_honest.size
+    k = int(np.argmax(np.abs(raw_honest)))
+    ratio = honest[10 * S + k] / raw_honest[k]
+    assert abs(ratio.imag) <= 1e-12 * abs(ratio), ratio
+    frame = np.concatenate([honest[:10 * S], ratio.real * raw])
+    if allow_louder:
+        return orc.normalize(frame)
+    assert peak(frame[10 * S:]) <= 1.0, "a forged frame louder than its header is not handled"
+    return frame
+
+
+def header_values(B, extra_lo=()):
+    """The (lo, hi) halves of the forged u128 length headers, for a decoder that sees a body of B bytes: 26 pairs, then (lo, 0) for
+    every extra_lo.  Small lengths, lengths around B, lengths around the 32-bit and 64-bit edges, and a high half that is not 0."""
+    los = [0, 1, 2, 3, 4, 6, 7, 8, 13, 14, B - 8, B - 7, B - 1, B, B + 1,
+           2 ** 31 - 1, 2 ** 31, 2 ** 32 - 1, 2 ** 32, 2 ** 32 + 5, 2 ** 32 + B - 1, 2 ** 63, 2 ** 64 - 1]
+    pairs = [(lo, 0) for lo in los] + [(5, 1), (0, 2 ** 63), (2 ** 64 - 1, 2 ** 64 - 1)] + [(lo, 0) for lo in extra_lo]
+    assert all(0 <= lo < 2 ** 64 and 0 <= hi < 2 ** 64 for lo, hi in pairs)
+    return pairs
+
+
+def header_bytes(lo, hi):
+    return int(lo).to_bytes(8, "little") + int(hi).to_bytes(8, "little")
+
+
+def header_rule(lo, hi, body):
+    """src/receiver.rs:85-95 in plain integers: the bytes kept of a body of `body` bytes"""
+    return lo if (hi == 0 and lo < body) else body
+
+
 def through_channel(orc, rng, tx, span, delay, f_delta, snr_db=30.0, taps=True, data_start=None):
     """Config-3 style capture: `delay` leading zeros, FIR CHANNEL (src/channel.rs:26-31), CFO
     exp(+j f (i+1)) (channel.rs:58-62), AWGN, cut/padded to `span` samples.
