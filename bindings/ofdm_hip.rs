@@ -21,7 +21,8 @@ pub struct ofdm_params {
     pub sync_window_reps: i32, pub sync_backoff: i32, pub cfo_mode: i32, pub sync_threshold: f32,
     pub sync_mode: i32,
     pub rx_path: i32,
-    pub reserved: [i32; 5],
+    pub chest_mode: i32,
+    pub reserved: [i32; 4],
 }
 
 pub const OFDM_OK: c_int = 0;
@@ -53,6 +54,10 @@ pub const OFDM_CONV_RATE_1_2: i32 = 0;
 pub const OFDM_CONV_RATE_2_3: i32 = 1;
 pub const OFDM_CONV_RATE_3_4: i32 = 2;
 pub const OFDM_SOFT_LLR_SCALE: f32 = 32.0;
+// ofdm_params.chest_mode: the reference's bin-by-bin estimate (default), or that estimate denoised by a weighted least-squares fit of
+// cp_len taps -- opt-in, receive side only; parity unpinned by the reference, tests/chest_ref.py is the definition (include/ofdm_hip.h)
+pub const OFDM_CHEST_LS: i32 = 0;
+pub const OFDM_CHEST_WLS: i32 = 1;
 
 /// The crate's own `ModulationScheme` (src/transmitter.rs:98-104) is what `encode` / `decode` keep taking.  Its `Qam` arm is
 /// empty in the reference (transmitter.rs:135-136, receiver.rs:185: "Only 16 qam is implemented"); here it selects 16-QAM.
@@ -130,6 +135,9 @@ extern "C" {
                                  f_delta_dev: *const f64, first_index_dev: *const i32) -> c_int;
     pub fn ofdm_estimate_channel_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64,
                                        frame_len: i64, offset_dev: *const i32, f_delta_dev: *const f64, hk_dev: *mut ofdm_fc32) -> c_int;
+    pub fn ofdm_chest_matrix(n_fft: i32, cp_len: i32, training: *const f64, rinv: *mut f64) -> c_int;
+    pub fn ofdm_chest_smooth_batch(ctx: *mut ofdm_ctx, hk_in_dev: *const ofdm_fc32, n_frames: i64, hk_out_dev: *mut ofdm_fc32) -> c_int;
+    pub fn ofdm_chest_window(ctx: *const ofdm_ctx, first_tap: *mut i32, n_taps: *mut i32) -> c_int;
     pub fn ofdm_rx_demod_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,
                                first_symbol: i32, syms_per_frame: i32, offset_dev: *const i32, f_delta_dev: *const f64,
                                hk_dev: *const ofdm_fc32, hk_stride: i64, out_dev: *mut u8, out_stride: i64, soft_dev: *mut ofdm_fc32) -> c_int;

@@ -92,6 +92,10 @@ enum { OFDM_SYNC_SCHMIDL_COX = 0, OFDM_SYNC_REFERENCE = 1 };
  * from one LDS image).  It never beat the staged chain (7.4 against 4.5 ms per 1 M config-3 frames in round 5) and was removed;
  * the slot stays so that the struct layout does not change, and takes AUTO or STAGED (the same chain). */
 enum { OFDM_RX_AUTO = 0, OFDM_RX_STAGED = 1 };
+/* ofdm_params.chest_mode: the channel estimate decode works with.  LS = the reference's estimate_channel, bin by bin (default).
+ * WLS = that estimate denoised by a weighted least-squares fit of cp_len taps (see "channel-estimate denoising" below): opt-in,
+ * receive side only, transmit is untouched. */
+enum { OFDM_CHEST_LS = 0, OFDM_CHEST_WLS = 1 };
 
 typedef struct {
     int32_t n_fft;            /* sub-carriers: 64 (reference) .. 4096, power of two */
@@ -105,7 +109,8 @@ typedef struct {
     float sync_threshold;     /* packet-detect threshold on M(d), default 0.5 */
     int32_t sync_mode;        /* OFDM_SYNC_*, default SCHMIDL_COX (this slot was reserved[0] == 0: same layout, same default) */
     int32_t rx_path;          /* OFDM_RX_AUTO or OFDM_RX_STAGED: one chain exists (see above) */
-    int32_t reserved[5];      /* must be zero */
+    int32_t chest_mode;       /* OFDM_CHEST_*, default LS (this slot was reserved[0] == 0: same layout, same default) */
+    int32_t reserved[4];      /* must be zero */
 } ofdm_params;
 
 /* ------------------------------------------------------------------ library / context */
@@ -248,6 +253,35 @@ int ofdm_cfo_rotate_batch(ofdm_ctx *ctx, ofdm_fc32 *x_dev, int64_t n_frames, int
 int ofdm_estimate_channel_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t frame_stride,
                                 int64_t frame_len, const int32_t *offset_dev, const double *f_delta_dev,
                                 ofdm_fc32 *hk_dev);
+/* With ofdm_params.chest_mode = OFDM_CHEST_WLS hk_dev receives H' of "channel-estimate denoising" below instead: bit for bit
+ * ofdm_chest_smooth_batch of what OFDM_CHEST_LS writes. */
+
+/* ------------------------------------------------------------------ channel-estimate denoising (north-star extension)
+ * Parity unpinned by the reference: tests/chest_ref.py is the definition.  With t_k the context's training table, W_k = |t_k|^2 and
+ * H^_k the estimate above (so W_k H^_k = conj(t_k) mean_b Y_b[k]; W_k H^_k counts as 0 where t_k = 0):
+ *   tap window   L_h = cp_len taps at delays n in [-pre, L_h - pre) taken mod n_fft, pre = cp_len / 4 (a frame start trimmed a few
+ *                samples late moves the channel to negative delays; with the default back-off CHANNEL sits at delays 3 .. 13)
+ *   estimate     h^ = argmin_h sum_k W_k |H^_k - sum_n h_n e^{-2 pi i k n / N}|^2: maximum likelihood for white noise on the training blocks
+ *   closed form  g_n = sum_k W_k H^_k e^{+2 pi i k n / N} (= N IFFT(W o H^) read at the window's indices; the window's offset is only an
+ *                index rotation, no phase ramp), h^ = R^-1 g, R[n][m] = r[n - m], r[d] = sum_k W_k e^{+2 pi i k d / N}: Hermitian, Toeplitz,
+ *                positive definite, constant per context and independent of pre
+ *   output       H'_k = sum_n h^_n e^{-2 pi i k n / N} = FFT of h^ scattered to the window's indices of a zero vector
+ * Tables and arithmetic on the device are f32 (k_chest_weight, the generic FFT kernel, k_chest_solve, the generic FFT kernel).
+ * A non-finite sample in a training block spoils the frame's WHOLE estimate H', not one bin as with OFDM_CHEST_LS.
+ * With chest_mode = OFDM_CHEST_WLS ofdm_estimate_channel_batch returns H' and every decode entry point (ofdm_rx_decode_batch, _host,
+ * _long, _long_host, a merged detection included) equalises and forms its LLR weights with H', for every ecc; the fused frame kernels
+ * take no estimate from outside, so the generic chain runs (ofdm_last_dispatch shows k_chest_solve). */
+/* R^-1 as cp_len x cp_len interleaved (re, im) doubles, row-major, solved in f64 (Levinson recursion + Trench's fill of the Toeplitz
+ * inverse, O(cp_len^2)).  training: n_fft interleaved doubles, NULL = the default table.  OFDM_ERR_INVALID for a bad size, a NULL
+ * rinv, or a table with so many zero bins that R is singular.  Host call, no context: exported so that the solver can be pinned
+ * without a GPU. */
+int ofdm_chest_matrix(int32_t n_fft, int32_t cp_len, const double *training, double *rinv);
+/* The stage on its own: n_frames rows of n_fft bins H^ -> H'.  hk_in_dev == hk_out_dev allowed.  Works on any context whatever its
+ * chest_mode (the tables are built on first use; OFDM_ERR_INVALID if the context's training table makes R singular). */
+int ofdm_chest_smooth_batch(ofdm_ctx *ctx, const ofdm_fc32 *hk_in_dev, int64_t n_frames, ofdm_fc32 *hk_out_dev);
+/* *first_tap = -pre, *n_taps = L_h.  Host call. */
+int ofdm_chest_window(const ofdm_ctx *ctx, int32_t *first_tap, int32_t *n_taps);
+
 /* RX demod = unprefix_block + equalise + decode_block + demodulate (src/receiver.rs:64-83) over
  * syms_per_frame OFDM symbols per frame.  Symbol k of frame f starts (at its cyclic prefix) at sample
  * offset_dev[f] + first_symbol*L + k*L of the frame (offset_dev NULL: 0); samples at or beyond frame_len read
@@ -395,7 +429,8 @@ int ofdm_tx_encode_batch(ofdm_ctx *ctx, const uint8_t *payload_dev, int64_t n_fr
  * 16) / 2 - 1, 0).  A max_symbols whose body exceeds 2^18 bytes (2^20 trellis steps): OFDM_ERR_UNSUPPORTED.
  * ecc = OFDM_ECC_CONV_K7F_* (likewise in every wrapper): the rule of "punctured rates and framed modes" above; status may become
  * OFDM_FRAME_HEADER.  With avail = max(max_symbols * bytes_per_symbol - 16 - 18, 0), out_stride >= floor(T' / 8) for the largest T'
- * with kept(T', rate) <= 8 avail (at most 3 avail / 4); a T' above 2^20: OFDM_ERR_UNSUPPORTED. */
+ * with kept(T', rate) <= 8 avail (at most 3 avail / 4); a T' above 2^20: OFDM_ERR_UNSUPPORTED.
+ * chest_mode = OFDM_CHEST_WLS (likewise in every wrapper, every ecc): "channel estimate" above is H' of "channel-estimate denoising". */
 int ofdm_rx_decode_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t frame_stride,
                          int64_t frame_len, int64_t n_lags, int32_t max_symbols, uint8_t *out_dev,
                          int64_t out_stride, int32_t *out_len_dev, int32_t *status_dev, int32_t *offset_dev,

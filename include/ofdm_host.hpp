@@ -45,10 +45,12 @@ class Context {
   public:
     explicit Context(bool guard_bands = false, ModulationScheme m = ModulationScheme::Bpsk, int n_fft = 64,
                      int ecc = OFDM_ECC_NONE, int cfo_mode = OFDM_CFO_SIGNED, int device = 0,
-                     Pilots pilots = default_pilot_choice()) {
+                     Pilots pilots = default_pilot_choice(), int chest_mode = OFDM_CHEST_LS) {
         ofdm_params p;
         check(ofdm_default_params(&p), "ofdm_default_params");
         p.n_fft = n_fft; p.cp_len = n_fft / 4; p.guard_bands = guard_bands; p.modulation = (int)m; p.ecc = ecc; p.cfo_mode = cfo_mode;
+        p.chest_mode = chest_mode; // OFDM_CHEST_WLS: decode works with the denoised channel estimate (include/ofdm_hip.h, EXT-5)
+        n_fft_ = n_fft;
         ecc_ = ecc;
         if (pilots == Pilots::StdRng) {
             std::vector<double> pre(2 * (size_t)(n_fft + n_fft / 4)), trn(2 * (size_t)n_fft);
@@ -223,6 +225,31 @@ class Context {
         if (corrected) check(ofdm_memcpy_d2h(ctx_, corrected, dfix.p, sizeof(int32_t)), "d2h");
         return out;
     }
+    // channel-estimate denoising (EXT-5; OFDM_CHEST_WLS as the context's chest_mode applies it inside decode; this is the bare stage):
+    // rows of n_fft bins of an estimate -> the weighted least-squares fit of cp_len taps to every row, as n_fft bins again
+    std::vector<Complex64> chest_smooth(const std::vector<Complex64> &hk) {
+        const auto fc = to_fc32(hk);
+        std::vector<ofdm_fc32> host(fc.size());
+        DevBuf d(ctx_, fc.size() * sizeof(ofdm_fc32));
+        if (!fc.empty()) check(ofdm_memcpy_h2d(ctx_, d.p, fc.data(), fc.size() * sizeof(ofdm_fc32)), "h2d");
+        check(ofdm_chest_smooth_batch(ctx_, (const ofdm_fc32 *)d.p, (int64_t)fc.size() / n_fft_, (ofdm_fc32 *)d.p), "ofdm_chest_smooth_batch");
+        if (!fc.empty()) check(ofdm_memcpy_d2h(ctx_, host.data(), d.p, host.size() * sizeof(ofdm_fc32)), "d2h");
+        return from_fc32(host);
+    }
+    // (first_tap, n_taps) = (-cp_len / 4, cp_len): the delays the denoised estimate may occupy
+    std::pair<int32_t, int32_t> chest_window() const {
+        int32_t first = 0, n = 0;
+        check(ofdm_chest_window(ctx_, &first, &n), "ofdm_chest_window");
+        return {first, n};
+    }
+    // R^-1 of the stage's normal equations for the default training table, cp_len x cp_len, row-major (host call, f64)
+    static std::vector<Complex64> chest_matrix(int n_fft) {
+        std::vector<double> r(2 * (size_t)(n_fft / 4) * (size_t)(n_fft / 4));
+        check(ofdm_chest_matrix(n_fft, n_fft / 4, nullptr, r.data()), "ofdm_chest_matrix");
+        std::vector<Complex64> o(r.size() / 2);
+        for (size_t i = 0; i < o.size(); ++i) o[i] = Complex64(r[2 * i], r[2 * i + 1]);
+        return o;
+    }
 
   private:
     // is `ecc` one of the modes with the outer Reed-Solomon code around the inner mode's frame (20 + inner)?
@@ -232,6 +259,7 @@ class Context {
     }
     ofdm_ctx *ctx_ = nullptr;
     int ecc_ = OFDM_ECC_NONE;
+    int n_fft_ = 64;
 };
 
 // One context per (thread, parameter set), created on first use and kept: the reference's free functions are called once per

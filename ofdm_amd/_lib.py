@@ -27,7 +27,8 @@ class Params(C.Structure):
     _fields_ = [
         ("n_fft", C.c_int32), ("cp_len", C.c_int32), ("modulation", C.c_int32), ("guard_bands", C.c_int32),
         ("ecc", C.c_int32), ("sync_window_reps", C.c_int32), ("sync_backoff", C.c_int32), ("cfo_mode", C.c_int32),
-        ("sync_threshold", C.c_float), ("sync_mode", C.c_int32), ("rx_path", C.c_int32), ("reserved", C.c_int32 * 5),
+        ("sync_threshold", C.c_float), ("sync_mode", C.c_int32), ("rx_path", C.c_int32), ("chest_mode", C.c_int32),
+        ("reserved", C.c_int32 * 4),
     ]
 
 
@@ -87,6 +88,9 @@ SIGNATURES = {
     "ofdm_frequency_correction_batch": (C.c_int, [vp, vp, i64, i64, i64, vp]),
     "ofdm_cfo_rotate_batch": (C.c_int, [vp, vp, i64, i64, i64, vp, vp]),
     "ofdm_estimate_channel_batch": (C.c_int, [vp, vp, i64, i64, i64, vp, vp, vp]),
+    "ofdm_chest_matrix": (C.c_int, [i32, i32, vp, vp]),
+    "ofdm_chest_smooth_batch": (C.c_int, [vp, vp, i64, vp]),
+    "ofdm_chest_window": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32)]),
     "ofdm_rx_demod_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, i64, vp, i64, vp]),
     "ofdm_tx_encode_batch": (C.c_int, [vp, vp, i64, i64, vp, i32, vp, i64]),
     "ofdm_rx_decode_batch": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, vp, i64, vp, vp, vp, vp, vp]),

@@ -32,6 +32,9 @@ FRAME_OK, FRAME_SHORT, FRAME_NOSYNC, FRAME_BADTIMING, FRAME_HEADER = 0, -1, -2, 
 FRAME_UNCORRECTABLE = -5  # ECC_RS255*: an outer RS block with more than 16 byte errors (the reference returns None)
 SYNC_SCHMIDL_COX, SYNC_REFERENCE = 0, 1
 RX_AUTO, RX_STAGED = 0, 1
+# channel estimate of the receive chain: the reference's bin-by-bin one, or that one denoised by a weighted least-squares fit of cp_len
+# taps (EXT-5; tests/chest_ref.py is the definition)
+CHEST_LS, CHEST_WLS = 0, 1
 DEFAULT_TUNING: dict = {}  # merged under every Context's `tuning=` (tools/tune_env.py fills it; empty in tests, bench and smoke)
 
 
@@ -156,7 +159,8 @@ class Context:
                  device: int = 0, preamble: Optional[np.ndarray] = None, training: Optional[np.ndarray] = None,
                  sync_window_reps: int = 3, sync_backoff: int = 4, cfo_mode: int = CFO_SIGNED,
                  sync_threshold: float = 0.5, use_torch_stream: bool = True, pilots: str = "default",
-                 sync_mode: int = SYNC_SCHMIDL_COX, rx_path: int = RX_AUTO, tuning: Optional[dict] = None):
+                 sync_mode: int = SYNC_SCHMIDL_COX, rx_path: int = RX_AUTO, tuning: Optional[dict] = None,
+                 chest_mode: int = CHEST_LS):
         self.lib = _lib.load()
         if pilots == "stdrng":  # the reference's own tables (restated, unverified) unless explicit tables are given
             sp, st = stdrng_pilots(n_fft)
@@ -174,6 +178,7 @@ class Context:
                                                                             sync_threshold)
         p.sync_mode = sync_mode
         p.rx_path = rx_path
+        p.chest_mode = chest_mode
         self.params = p
         pre = None if preamble is None else np.ascontiguousarray(preamble, dtype=np.complex128)
         trn = None if training is None else np.ascontiguousarray(training, dtype=np.complex128)
@@ -509,6 +514,22 @@ class Context:
                                                       f2.shape[1] if frame_len is None else frame_len, _dev(offset),
                                                       _dev(f_delta), _dev(hk)), "estimate_channel")
         return hk
+
+    def chest_smooth(self, hk: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ofdm_chest_smooth_batch: rows of n_fft bins of a channel estimate -> the weighted least-squares fit of cp_len taps to every
+        row, as n_fft bins again (EXT-5).  out may be hk itself.  Works whatever the context's chest_mode."""
+        hk = self._cx(hk)
+        assert hk.shape[-1] == self.n_fft
+        out = torch.empty_like(hk) if out is None else self._cx(out)
+        assert out.shape == hk.shape
+        self._ck(self.lib.ofdm_chest_smooth_batch(self.h, _dev(hk), hk.numel() // self.n_fft, _dev(out)), "chest_smooth")
+        return out
+
+    def chest_window(self):
+        """ofdm_chest_window: (first_tap, n_taps) = (-cp_len // 4, cp_len), the delays the denoised estimate may occupy."""
+        first, n = C.c_int32(), C.c_int32()
+        self._ck(self.lib.ofdm_chest_window(self.h, C.byref(first), C.byref(n)), "chest_window")
+        return int(first.value), int(n.value)
 
     def rx_demod(self, frames: torch.Tensor, syms_per_frame: int, first_symbol: int = 0,
                  offset: Optional[torch.Tensor] = None, f_delta: Optional[torch.Tensor] = None,

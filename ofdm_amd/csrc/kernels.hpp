@@ -43,6 +43,7 @@ struct Tuning {
     int scb_two_segments = 0;      // k_scb_chunks: two-segment staging also for L <= 1280
     int scb_big_tiles = 0;         // k_scb_fine: 1280-lag tiles / 128 threads
     int debug_demod64 = 0, debug_sc = 0, debug_tx = 0; // profile build only (kProfile)
+    int chest_solve_only = 0;      // ofdm_chest_smooth_batch: 1 = launch k_chest_solve alone on the rows given (into the workspace; nothing is delivered): its time on its own
     int soft_chunk_frames = 0;     // OFDM_ECC_HAMMING74_SOFT / OFDM_ECC_CONV_K7 decode: frames per k_sym<llr> + k_rx_finish_soft / k_viterbi_k7 step (0 = the LLR workspace's 256 MB bound)
 };
 inline const Tuning &tuning_or_default(const Tuning *t) { static const Tuning d; return t ? *t : d; }
@@ -366,6 +367,21 @@ struct Rs255DecodeParams {
     int32_t *out_len = nullptr, *corrected = nullptr, *status_rw = nullptr;
 };
 hipError_t run_rs255_decode(const Rs255DecodeParams &p, int num_cu, const Tuning *tune, hipStream_t st);
+
+// ---- EXT-5 channel-estimate denoising (OFDM_CHEST_WLS, ofdm_chest_smooth_batch; kernels_chest.hip, definition: tests/chest_ref.py)
+// rows of n_fft bins times the per-bin weight w (a weight of exactly 0 gives 0 whatever the bin holds); in == out allowed
+hipError_t run_chest_weight(const float2 *in, const float *w, float2 *out, long long n_frames, int n_fft, int num_cu, const Tuning *tune,
+                            hipStream_t st);
+// out row f = n_fft taps: tap (m - pre) mod n_fft = sum_n mt[n][m] g[f][(n - pre) mod n_fft] for m in [0, n_taps), every other tap 0.
+// mt: the n_taps x n_taps matrix TRANSPOSED (row = contraction index).  n_fft = 4 n_taps, n_taps a multiple of 16; g != out.
+struct ChestSolveParams {
+    const float2 *g = nullptr;
+    float2 *out = nullptr;
+    const float2 *mt = nullptr;
+    long long n_frames = 0;
+    int n_fft = 0, n_taps = 0, pre = 0;
+};
+hipError_t run_chest_solve(const ChestSolveParams &p, int num_cu, const Tuning *tune, hipStream_t st);
 
 // channel (src/channel.rs:33-74) on the GPU (kernels_bytes.hip)
 struct ChannelParams {

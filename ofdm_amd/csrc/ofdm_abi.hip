@@ -95,6 +95,116 @@ static int fast_path(ofdm_ctx *c, hipError_t e) {
         if (_r != kNextPath) return _r;                                                    \
     } while (0)
 
+// ---- EXT-5 channel-estimate denoising: host side (include/ofdm_hip.h, tests/chest_ref.py)
+// R^-1 of the Hermitian Toeplitz R[n][m] = r[n - m], r[d] = sum_k |t_k|^2 e^{+2 pi i k d / N}, L = N / 4, in f64 by Trench's algorithm:
+// the Levinson recursion gives x = the first column of R^-1 in O(L^2), and the Gohberg-Semencul identity fills the rest,
+//   B[i + 1][j + 1] = B[i][j] + (x[i + 1] conj(x[j + 1]) - conj(x[L - 1 - i]) x[L - 1 - j]) / x[0].
+// The recursion runs along diagonals from the first row and column only as far as the anti-diagonal; the other half follows from
+// persymmetry, B[i][j] = B[L - 1 - j][L - 1 - i], so no entry is more than L / 2 additions away from x.
+// false when R is not positive definite (fewer than L non-zero training bins).
+static bool chest_rinv(int N, const double *trn, std::vector<cd> &B) {
+    const int L = N / 4;
+    std::vector<cd> r(N);
+    for (int k = 0; k < N; k++) r[k] = cd{trn[2 * k] * trn[2 * k] + trn[2 * k + 1] * trn[2 * k + 1], 0.0};
+    host_fft(r, true);
+    for (auto &v : r) { v.re *= (double)N; v.im *= (double)N; }
+    if (!(r[0].re > 0.0)) return false;
+    std::vector<cd> x(L, cd{0.0, 0.0}), nx(L);
+    x[0] = cd{1.0 / r[0].re, 0.0};
+    for (int m = 1; m < L; m++) { // x solves the leading m x m system R x = e_0; extend to m + 1
+        cd eps{0.0, 0.0};
+        for (int i = 0; i < m; i++) { const cd t = cd_mul(r[m - i], x[i]); eps.re += t.re; eps.im += t.im; }
+        const double den = 1.0 - (eps.re * eps.re + eps.im * eps.im);
+        if (!(den > 0.0)) return false;
+        for (int i = 0; i <= m; i++) {
+            const cd f = i < m ? x[i] : cd{0.0, 0.0};
+            const cd b = i > 0 ? cd{x[m - i].re, -x[m - i].im} : cd{0.0, 0.0};
+            const cd eb = cd_mul(eps, b);
+            nx[i] = cd{(f.re - eb.re) / den, (f.im - eb.im) / den};
+        }
+        for (int i = 0; i <= m; i++) x[i] = nx[i];
+    }
+    const double x0 = x[0].re;
+    if (!(x0 > 0.0)) return false;
+    B.assign((size_t)L * L, cd{0.0, 0.0});
+    for (int i = 0; i < L; i++)
+        for (int j = 0; i + j < L; j++) {
+            cd v;
+            if (j == 0) v = x[i];
+            else if (i == 0) v = cd{x[j].re, -x[j].im};
+            else {
+                const cd a = cd_mul(x[i], cd{x[j].re, -x[j].im});
+                const cd b = cd_mul(cd{x[L - i].re, -x[L - i].im}, x[L - j]);
+                const cd p = B[(size_t)(i - 1) * L + (j - 1)];
+                v = cd{p.re + (a.re - b.re) / x0, p.im + (a.im - b.im) / x0};
+            }
+            B[(size_t)i * L + j] = v;
+            B[(size_t)(L - 1 - j) * L + (L - 1 - i)] = v;
+        }
+    return true;
+}
+
+// the device tables of the stage, built once per context
+static int chest_tables(ofdm_ctx *c) {
+    if (c->d_chest_mt) return OFDM_OK;
+    const int N = c->prm.n_fft, L = N / 4;
+    std::vector<cd> B;
+    if (!chest_rinv(N, c->training.data(), B)) return OFDM_ERR_INVALID;
+    std::vector<float> w(N);
+    std::vector<float2> mt((size_t)L * L);
+    for (int k = 0; k < N; k++) { const double re = c->training[2 * k], im = c->training[2 * k + 1]; w[k] = (float)(re * re + im * im); }
+    for (int m = 0; m < L; m++) // the inverse FFT in front of the solve carries 1 / N: the table carries the N (a power of two: exact)
+        for (int n = 0; n < L; n++) mt[(size_t)n * L + m] = make_float2((float)(B[(size_t)m * L + n].re * N), (float)(B[(size_t)m * L + n].im * N));
+    float *dw = nullptr;
+    float2 *dm = nullptr;
+    if (hipMalloc(&dw, sizeof(float) * N) != hipSuccess) return OFDM_ERR_NOMEM;
+    if (hipMalloc(&dm, sizeof(float2) * mt.size()) != hipSuccess) { hipFree(dw); return OFDM_ERR_NOMEM; }
+    if (hipMemcpy(dw, w.data(), sizeof(float) * N, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dm, mt.data(), sizeof(float2) * mt.size(), hipMemcpyHostToDevice) != hipSuccess) { hipFree(dw); hipFree(dm); return OFDM_ERR_HIP; }
+    c->d_chest_w = dw;
+    c->d_chest_mt = dm;
+    return OFDM_OK;
+}
+
+// rows of N bins `in` -> `out` (in == out allowed), per frame chunk: weight -> inverse FFT -> k_chest_solve -> forward FFT.  The
+// one workspace (slot 13: the solve's zeroed rows) holds a chunk, at most kChestChunkBytes whatever n_frames is.
+static const int64_t kChestChunkBytes = 64ll << 20;
+static int chest_smooth_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, float2 *out, bool trace) {
+    int rc = chest_tables(c);
+    if (rc) return rc;
+    const int N = c->prm.n_fft;
+    int64_t chunk = std::max<int64_t>(kChestChunkBytes / ((int64_t)sizeof(float2) * N), 64);
+    if (chunk > n_frames) chunk = n_frames;
+    void *w_taps;
+    if ((rc = ws_get(c, 13, sizeof(float2) * (size_t)N * (size_t)chunk, &w_taps))) return rc;
+    for (int64_t f0 = 0; f0 < n_frames; f0 += chunk) {
+        const int64_t nf = n_frames - f0 < chunk ? n_frames - f0 : chunk;
+        const bool tr = trace && f0 == 0;
+        float2 *rows = out + f0 * N;
+        if (c->tune.chest_solve_only) { // laboratory key: the contraction alone, timed by tools/bench_chest.py
+            ChestSolveParams sp;
+            sp.g = in + f0 * N; sp.out = (float2 *)w_taps; sp.mt = c->d_chest_mt; sp.n_frames = nf; sp.n_fft = N; sp.n_taps = N / 4; sp.pre = N / 16;
+            if (tr) c->trace.add("k_chest_solve");
+            HIP_TRY(c, run_chest_solve(sp, c->num_cu, &c->tune, c->stream));
+            continue;
+        }
+        if (tr) c->trace.add("k_chest_weight");
+        HIP_TRY(c, run_chest_weight(in + f0 * N, c->d_chest_w, rows, nf, N, c->num_cu, &c->tune, c->stream));
+        SymParams p = base_params(c);
+        if (!tr) p.trace = nullptr;
+        p.n_frames = nf; p.frame_stride = N; p.frame_len = N; p.syms_per_frame = 1; p.in_sym_stride = N; p.in_skip = 0;
+        p.in = rows; p.out = rows;
+        HIP_TRY(c, run_fft(N, p, true, c->stream, c->num_cu));
+        ChestSolveParams sp;
+        sp.g = rows; sp.out = (float2 *)w_taps; sp.mt = c->d_chest_mt; sp.n_frames = nf; sp.n_fft = N; sp.n_taps = N / 4; sp.pre = N / 16;
+        if (tr) c->trace.add("k_chest_solve");
+        HIP_TRY(c, run_chest_solve(sp, c->num_cu, &c->tune, c->stream));
+        p.in = (const float2 *)w_taps; p.out = rows;
+        HIP_TRY(c, run_fft(N, p, false, c->stream, c->num_cu));
+    }
+    return OFDM_OK;
+}
+
 extern "C" {
 
 int ofdm_abi_version(void) { return OFDM_HIP_ABI_VERSION; }
@@ -251,6 +361,8 @@ int ofdm_destroy(ofdm_ctx *c) {
     if (c->d_tw) hipFree(c->d_tw);
     if (c->d_inv_trn) hipFree(c->d_inv_trn);
     if (c->d_header) hipFree(c->d_header);
+    if (c->d_chest_w) hipFree(c->d_chest_w);
+    if (c->d_chest_mt) hipFree(c->d_chest_mt);
     if (c->d_stats) hipFree(c->d_stats);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
@@ -279,6 +391,7 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
     if (!(p->sync_threshold > 0.f && p->sync_threshold <= 1.f)) return OFDM_ERR_INVALID;
     if (p->sync_mode != OFDM_SYNC_SCHMIDL_COX && p->sync_mode != OFDM_SYNC_REFERENCE) return OFDM_ERR_INVALID;
     if (p->rx_path != OFDM_RX_AUTO && p->rx_path != OFDM_RX_STAGED) return OFDM_ERR_INVALID; // (2 was the one-pass kernel of rounds 2-4: removed)
+    if (p->chest_mode != OFDM_CHEST_LS && p->chest_mode != OFDM_CHEST_WLS) return OFDM_ERR_INVALID;
     for (int r : p->reserved) if (r != 0) return OFDM_ERR_INVALID;
 
     int ndev = 0;
@@ -306,6 +419,7 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
         ofdm_default_pilots(N, CP, pre.data(), trn.data());
         if (preamble) std::memcpy(pre.data(), preamble, sizeof(double) * 2 * S);
         if (training) std::memcpy(trn.data(), training, sizeof(double) * 2 * N);
+        c->training = trn;
 
         std::vector<float2> tw(N), inv(N), hdr(10 * S);
         for (int m = 0; m < N; m++) {
@@ -339,6 +453,7 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
         if (hipMemcpy(c->d_tw, tw.data(), sizeof(float2) * N, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(c->d_inv_trn, inv.data(), sizeof(float2) * N, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(c->d_header, hdr.data(), sizeof(float2) * 10 * S, hipMemcpyHostToDevice) != hipSuccess) { rc = OFDM_ERR_HIP; break; }
+        if (p->chest_mode == OFDM_CHEST_WLS) rc = chest_tables(c); // the host solve (its time per N)
     } while (0);
     if (rc != OFDM_OK) { ofdm_destroy(c); return rc; }
     *out = c;
@@ -839,7 +954,32 @@ int ofdm_estimate_channel_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_fram
     SymParams p = rx_params(c, reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, offset, f_delta);
     p.out = reinterpret_cast<float2 *>(hk);
     HIP_TRY(c, run_chest(c->prm.n_fft, p, c->stream, c->num_cu));
+    if (c->prm.chest_mode == OFDM_CHEST_WLS && n_frames) return chest_smooth_run(c, p.out, n_frames, p.out, true);
     return OFDM_OK;
+}
+
+int ofdm_chest_matrix(int32_t n_fft, int32_t cp_len, const double *training, double *rinv) {
+    if (!valid_nfft(n_fft) || cp_len != n_fft / 4 || !rinv) return OFDM_ERR_INVALID;
+    std::vector<double> trn(2 * (size_t)n_fft);
+    if (training) std::memcpy(trn.data(), training, sizeof(double) * trn.size());
+    else ofdm_default_pilots(n_fft, cp_len, nullptr, trn.data());
+    std::vector<cd> B;
+    if (!chest_rinv(n_fft, trn.data(), B)) return OFDM_ERR_INVALID;
+    for (size_t i = 0; i < B.size(); i++) { rinv[2 * i] = B[i].re; rinv[2 * i + 1] = B[i].im; }
+    return OFDM_OK;
+}
+int ofdm_chest_window(const ofdm_ctx *c, int32_t *first_tap, int32_t *n_taps) {
+    if (!c || !first_tap || !n_taps) return OFDM_ERR_INVALID;
+    *first_tap = -(c->prm.cp_len / 4);
+    *n_taps = c->prm.cp_len;
+    return OFDM_OK;
+}
+int ofdm_chest_smooth_batch(ofdm_ctx *c, const ofdm_fc32 *hk_in, int64_t n_frames, ofdm_fc32 *hk_out) {
+    if (!c || n_frames < 0 || (n_frames && (!hk_in || !hk_out))) return OFDM_ERR_INVALID;
+    if (!n_frames) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    return chest_smooth_run(c, reinterpret_cast<const float2 *>(hk_in), n_frames, reinterpret_cast<float2 *>(hk_out), true);
 }
 
 static int demod_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
@@ -1101,7 +1241,8 @@ static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_
     //      demap (receiver.rs:44-83).  N = 64: one fused wave-centric kernel; otherwise the generic pair.
     bool fused = false, finished = false;
     const bool soft = ecc == OFDM_ECC_HAMMING74_SOFT || conv; // the fused frame kernels have no LLR epilogue: the generic chain
-    if (N == 1024 && !soft) { // one workgroup per frame: channel estimate kept in registers, 16 x 64 FFT (kernels_rx1024.hip)
+    const bool wls = c->prm.chest_mode == OFDM_CHEST_WLS;     // ... and take no channel estimate from outside: the generic chain
+    if (N == 1024 && !soft && !wls) { // one workgroup per frame: channel estimate kept in registers, 16 x 64 FFT (kernels_rx1024.hip)
         const bool off = c->tune.no_rxframe1024 != 0; // A/B switch
         const SymParams p = rx_params(c, x, n_frames, frame_stride, frame_len, offs, fd, (const int32_t *)w_nsym, (uint8_t *)w_raw, raw_stride);
         // the kernel also parses the length header, truncates and Hamming-decodes into the caller's rows when they are 4-byte aligned
@@ -1111,7 +1252,7 @@ static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_
         if (r == OFDM_OK) { fused = true; finished = fin; }
         else if (r != kNextPath) return r;
     }
-    if (N == 64 && !soft) {
+    if (N == 64 && !soft && !wls) {
         SymParams p = rx_params(c, x, n_frames, frame_stride, frame_len, offs, fd, (const int32_t *)w_nsym, (uint8_t *)w_raw, raw_stride);
         p.syms_per_frame = max_symbols; // (the launcher's "is there room for a whole frame in the capture" test)
         // without an outer code the kernel also parses the length header and writes the payload to its final place
@@ -1128,6 +1269,7 @@ static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_
         SymParams p = rx_params(c, x, n_frames, frame_stride, frame_len, offs, fd);
         p.out = (float2 *)w_hk;
         HIP_TRY(c, run_chest(N, p, c->stream, c->num_cu));
+        if (wls && (rc = chest_smooth_run(c, (const float2 *)w_hk, n_frames, (float2 *)w_hk, true))) return rc; // EXT-5: H' in place of H^
         if (soft) {
             // 4s + 5s. per frame chunk: hard bytes (for the header) and LLRs in one k_sym<llr>, then the header and the ML decode of
             // the body (k_rx_finish_soft; OFDM_ECC_CONV_K7: k_viterbi_k7, which also needs a survivor slab per resident wavefront;

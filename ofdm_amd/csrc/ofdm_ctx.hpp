@@ -5,6 +5,7 @@
 #include "kernels.hpp"
 
 #include <cstddef>
+#include <vector>
 
 struct Workspace {
     void *ptr = nullptr;
@@ -25,12 +26,16 @@ struct ofdm_ctx {
     float2 *d_inv_trn = nullptr;  // 1 / training[k]
     float2 *d_header = nullptr;   // 10 * S un-normalised header samples
     float header_max = 0.f;
+    // EXT-5 channel-estimate denoising: built by ofdm_create when chest_mode is on, else by the first ofdm_chest_smooth_batch
+    std::vector<double> training;       // the context's training table (interleaved re, im): what the tables below are made from
+    float *d_chest_w = nullptr;         // W_k = |t_k|^2
+    float2 *d_chest_mt = nullptr;       // N R^-1, transposed: [L_h][L_h]
     ofdm::Tuning tune;                  // ofdm_set_tuning: per-context A/B switches and grid shapes (no environment variable is read)
     ofdm::Trace trace;                  // ofdm_last_dispatch: the kernels the last entry point launched
     ofdm::ScStats sc_stats;             // list counters of the last Schmidl-Cox search (ofdm_get_tuning "stat_sc_*")
     int32_t *d_stats = nullptr;         // [2] their home on the device (owned by the context)
     // workspaces (grown on demand, never inside a captured region)
-    Workspace ws[13];
+    Workspace ws[14];
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     HostPipe *pipe = nullptr;     // created by the first host-buffer call, freed by ofdm_destroy
 

@@ -22,6 +22,9 @@
 //   soft decode (OFDM_ECC_HAMMING74_SOFT, OFDM_ECC_CONV_K7)
 //     soft_chunk_frames   frames per k_sym<llr> + k_rx_finish_soft / k_viterbi_k7 step of the decode chain (0 = as many as fit the 256 MB LLR workspace;
 //                         the tests force a few frames to walk many steps)
+//   channel-estimate denoising (EXT-5)
+//     chest_solve_only    ofdm_chest_smooth_batch launches k_chest_solve alone on the rows it is given, into its workspace, and delivers
+//                         nothing: the kernel's time on its own (tools/bench_chest.py)
 //   profile build only (libofdm_hip_profile.so): ablation exits and s_memtime section timers
 //     debug_demod64, debug_sc, debug_tx
 #ifndef OFDM_TUNE_KEY
@@ -52,6 +55,7 @@ OFDM_TUNE_KEY("demod64_store_policy", demod64_store_policy, false)
 OFDM_TUNE_KEY("scb_two_segments", scb_two_segments, false)
 OFDM_TUNE_KEY("scb_big_tiles", scb_big_tiles, false)
 OFDM_TUNE_KEY("soft_chunk_frames", soft_chunk_frames, false)
+OFDM_TUNE_KEY("chest_solve_only", chest_solve_only, false)
 OFDM_TUNE_KEY("debug_demod64", debug_demod64, true)
 OFDM_TUNE_KEY("debug_sc", debug_sc, true)
 OFDM_TUNE_KEY("debug_tx", debug_tx, true)
