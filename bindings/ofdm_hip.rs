@@ -50,6 +50,11 @@ pub const OFDM_ECC_RS255_K7F_R12: i32 = 30;
 pub const OFDM_ECC_RS255_K7F_R23: i32 = 31;
 pub const OFDM_ECC_RS255_K7F_R34: i32 = 32;
 pub const OFDM_FRAME_UNCORRECTABLE: i32 = -5; // OFDM_ECC_RS255*: an RS block with more than 16 byte errors (the reference returns None)
+// CRC-32 frame check around any of the eleven modes above, 64 + mode: decode delivers exactly the payload that was sent or reports
+// the frame with OFDM_FRAME_FCS; parity unpinned by the reference, tests/fcs_ref.py is the definition (include/ofdm_hip.h)
+pub const OFDM_ECC_FCS: i32 = 64;
+pub const OFDM_FCS_OVERHEAD: i64 = 8;
+pub const OFDM_FRAME_FCS: i32 = -6;
 pub const OFDM_CONV_RATE_1_2: i32 = 0;
 pub const OFDM_CONV_RATE_2_3: i32 = 1;
 pub const OFDM_CONV_RATE_3_4: i32 = 2;
@@ -83,6 +88,7 @@ extern "C" {
     pub fn ofdm_rs255_encode(data: *const u8, n_bytes: i64, out: *mut u8) -> c_int;
     pub fn ofdm_rs255_decode(code: *const u8, n_code: i64, out: *mut u8, corrected: *mut i32) -> c_int;
     pub fn ofdm_tx_symbols_batch(ctx: *mut ofdm_ctx, bytes_dev: *const u8, n_bytes: i64, out_dev: *mut ofdm_fc32, n_sym: i64) -> c_int;
+    pub fn ofdm_crc32(data: *const u8, n_bytes: i64) -> u32;
     pub fn ofdm_chacha_block(key8: *const u32, words12_15: *const u32, rounds: i32, out16: *mut u32) -> c_int;
     pub fn ofdm_create(p: *const ofdm_params, preamble: *const f64, training: *const f64, device: c_int,
                        stream: *mut c_void, out: *mut *mut ofdm_ctx) -> c_int;
@@ -127,6 +133,10 @@ extern "C" {
                                    out_dev: *mut u8, out_stride: i64) -> c_int;
     pub fn ofdm_rs255_decode_batch(ctx: *mut ofdm_ctx, code_dev: *const u8, n_frames: i64, code_stride: i64, code_len_dev: *const i32,
                                    n_code: i64, out_dev: *mut u8, out_stride: i64, out_len_dev: *mut i32, corrected_dev: *mut i32) -> c_int;
+    pub fn ofdm_fcs_wrap_batch(ctx: *mut ofdm_ctx, in_dev: *const u8, n_frames: i64, in_stride: i64, in_len_dev: *const i32, n_bytes: i64,
+                               out_dev: *mut u8, out_stride: i64, out_len_dev: *mut i32) -> c_int;
+    pub fn ofdm_fcs_check_batch(ctx: *mut ofdm_ctx, row_dev: *const u8, n_frames: i64, row_stride: i64, row_len_dev: *const i32,
+                                n_row: i64, out_dev: *mut u8, out_stride: i64, out_len_dev: *mut i32, ok_dev: *mut i32) -> c_int;
     pub fn ofdm_sc_correlate_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,
                                    n_lags: i64, d_hat_dev: *mut i32, f_delta_dev: *mut f64, metric_dev: *mut f32) -> c_int;
     pub fn ofdm_frequency_correction_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_pairs: i64, stride: i64,

@@ -58,7 +58,8 @@ enum {
     OFDM_FRAME_NOSYNC = -2, /* no lag reached the Schmidl-Cox threshold */
     OFDM_FRAME_BADTIMING = -3, /* OFDM_SYNC_REFERENCE: offset = lag - 1 outside the capture (the reference panics in split_off, receiver.rs:25) */
     OFDM_FRAME_HEADER = -4, /* fewer than 16 decoded bytes (reference panics in drain, receiver.rs:88) */
-    OFDM_FRAME_UNCORRECTABLE = -5 /* OFDM_ECC_RS255*: an outer RS block with more than 16 byte errors (the reference returns None) */
+    OFDM_FRAME_UNCORRECTABLE = -5, /* OFDM_ECC_RS255*: an outer RS block with more than 16 byte errors (the reference returns None) */
+    OFDM_FRAME_FCS = -6     /* OFDM_ECC_FCS + mode: the delivered row is not a valid envelope (length word or CRC-32 wrong); out_len 0 */
 };
 
 /* ModulationScheme (src/transmitter.rs:98-104) as bits per constellation point */
@@ -74,10 +75,16 @@ enum { OFDM_MOD_BPSK = 1, OFDM_MOD_QPSK = 2, OFDM_MOD_QAM16 = 4, OFDM_MOD_QAM64 
  * ceil(kept(8 (p + 1), rate) / 8) (see "punctured rates and framed modes" below).
  * OFDM_ECC_RS255 / OFDM_ECC_RS255_K7F_R12 / _R23 / _R34 = 20 + inner, inner = OFDM_ECC_NONE or OFDM_ECC_CONV_K7F_*: the reference's
  * outer Reed-Solomon(255,223) framing (create_transmission_bytes / decipher_transmission_bytes) around the inner mode's frame (see
- * "outer Reed-Solomon code on the device" below).  21 .. 29 and 33 upwards are rejected like every other value not named. */
+ * "outer Reed-Solomon code on the device" below).  21 .. 29 and 33 .. 63 are rejected like every other value not named.
+ * OFDM_ECC_FCS + mode = 64 + mode, mode any of the eleven values above (64, 65, 66, 69, 74, 75, 76, 84, 94, 95, 96): the CRC-32 frame
+ * check around the payload of that mode (see "frame check sequence" below) -- decode delivers exactly the bytes that were sent or
+ * reports the frame.  Every other value from 64 upwards is rejected. */
 enum { OFDM_ECC_NONE = 0, OFDM_ECC_HAMMING74 = 1, OFDM_ECC_HAMMING74_SOFT = 2, OFDM_ECC_CONV_K7 = 5,
        OFDM_ECC_CONV_K7F_R12 = 10, OFDM_ECC_CONV_K7F_R23 = 11, OFDM_ECC_CONV_K7F_R34 = 12,
-       OFDM_ECC_RS255 = 20, OFDM_ECC_RS255_K7F_R12 = 30, OFDM_ECC_RS255_K7F_R23 = 31, OFDM_ECC_RS255_K7F_R34 = 32 };
+       OFDM_ECC_RS255 = 20, OFDM_ECC_RS255_K7F_R12 = 30, OFDM_ECC_RS255_K7F_R23 = 31, OFDM_ECC_RS255_K7F_R34 = 32,
+       OFDM_ECC_FCS = 64 };
+/* bytes the envelope of an OFDM_ECC_FCS mode adds to a payload: the u32 length word in front, the u32 CRC-32 behind */
+#define OFDM_FCS_OVERHEAD 8
 /* puncturing rate of ofdm_conv_k7_*_punctured (the framed modes' body rate is OFDM_ECC_CONV_K7F_Rxx - OFDM_ECC_CONV_K7F_R12) */
 enum { OFDM_CONV_RATE_1_2 = 0, OFDM_CONV_RATE_2_3 = 1, OFDM_CONV_RATE_3_4 = 2 };
 /* llr_scale of the OFDM_ECC_HAMMING74_SOFT and OFDM_ECC_CONV_K7 decode chains (chosen from the measured BER curves);
@@ -130,6 +137,9 @@ int ofdm_stdrng_pilots(int32_t n_fft, int32_t cp_len, double *preamble, double *
 /* One ChaCha block (16 words out) from key[8] and state words 12..15, `rounds` = 8 / 12 / 20: exported so that the
  * published test vectors can pin the generator core. Host call. */
 int ofdm_chacha_block(const uint32_t *key8, const uint32_t *words12_15, int32_t rounds, uint32_t *out16);
+/* CRC-32 of IEEE 802.3 / zlib over n_bytes bytes (see "frame check sequence" below); 0 for a NULL pointer or a negative count.
+ * Host call, no context: exported so that the definition can be pinned without a GPU. */
+uint32_t ofdm_crc32(const uint8_t *data, int64_t n_bytes);
 /* preamble / training: host pointers (interleaved doubles) or NULL for the defaults.
  * device: HIP device ordinal.  stream: a hipStream_t (as void*); NULL = the device's default (null) stream,
  * which is what torch uses as its current stream unless told otherwise. */
@@ -399,6 +409,38 @@ int ofdm_rs255_encode_batch(ofdm_ctx *ctx, const uint8_t *in_dev, int64_t n_fram
 int ofdm_rs255_decode_batch(ofdm_ctx *ctx, const uint8_t *code_dev, int64_t n_frames, int64_t code_stride, const int32_t *code_len_dev,
                             int64_t n_code, uint8_t *out_dev, int64_t out_stride, int32_t *out_len_dev, int32_t *corrected_dev);
 
+/* ------------------------------------------------------------------ frame check sequence (north-star extension; DESIGN.md 3, EXT-2 frame check)
+ * Parity unpinned by the reference (it has no check of its own): tests/fcs_ref.py over zlib.crc32 is the definition.
+ * crc32 = the CRC of IEEE 802.3 / zlib: reflected polynomial 0xEDB88320, register initialised to 0xFFFFFFFF, result complemented;
+ * crc32("123456789") = 0xCBF43926.
+ * Envelope of a payload of p bytes, p + OFDM_FCS_OVERHEAD bytes long:
+ *     E(payload) = [u32 LE p] ++ payload ++ [u32 LE crc32([u32 LE p] ++ payload)]
+ * Check of a delivered row of L bytes: valid iff L >= 8, p = the u32 at byte 0 satisfies p <= L - 8 (compared in 64 bits: p may be
+ * 0xFFFFFFFF), and the u32 at byte 4 + p equals crc32(row[0 : 4 + p]).  Bytes behind 8 + p are not looked at (the padding of the
+ * Hamming and RS modes); a valid row delivers row[4 : 4 + p].  An all-zero row is invalid (crc32 of four zero bytes is 0x2144DF1C),
+ * every error burst of at most 32 bits inside row[0 : 8 + p] is caught, any other damage slips through with probability 2^-32.
+ * Stage entry points (k_fcs_wrap / k_fcs_check, any context whatever its ecc):
+ * wrap: row f = in_dev[f*in_stride .. + len_f), len_f = in_len_dev[f] clamped to [0, n_bytes], or n_bytes when NULL, becomes its
+ *   envelope at out_dev[f*out_stride ..]; the bytes behind it, up to n_bytes + 8, are written as 0; out_len_dev[f] (optional) =
+ *   len_f + 8.  in_stride >= n_bytes, out_stride >= n_bytes + 8; n_bytes + 8 > INT32_MAX: OFDM_ERR_UNSUPPORTED.
+ * check: row f = row_dev[f*row_stride .. + L_f), L_f = row_len_dev[f] clamped to [0, n_row], or n_row when NULL.  Valid: the payload
+ *   is written to out_dev[f*out_stride ..], out_len_dev[f] = p, ok_dev[f] = 1.  Invalid: out_len_dev[f] = 0, ok_dev[f] = 0, and the
+ *   output row may hold bytes of the rejected payload.  out_len_dev and ok_dev are optional.  row_stride >= n_row, out_stride >=
+ *   max(n_row - 8, 0); input and output rows must not overlap.  No byte outside [row, row + L_f) is read whatever the length word says.
+ * A violated stride rule, a negative count or a NULL context: OFDM_ERR_INVALID.  n_frames == 0: OFDM_OK, nothing is written.
+ *
+ * Frame modes ecc = OFDM_ECC_FCS + mode.  Transmit: the frame is mode's frame of E(payload), row by row (a ragged row codes its own
+ * len_f); ofdm_coded_len(p), ofdm_data_symbols(p) and ofdm_frame_samples(p) are mode's values at p + 8; payload_bytes + 8 > INT32_MAX:
+ * OFDM_ERR_UNSUPPORTED.  Receive: mode's chain runs unchanged; a frame it leaves at OFDM_FRAME_OK with L bytes is checked: valid ->
+ * out_len = p, the payload at the start of the output row; invalid -> status OFDM_FRAME_FCS, out_len 0.  A frame with any other status
+ * keeps it, with out_len 0.  A frame cut short by the end of the capture fails the check and is reported.  Rows: out_stride >=
+ * max(R - 8, 0), R = the row size mode asks for the same max_symbols (OFDM_ERR_INVALID otherwise), in every decode entry point
+ * (ofdm_rx_decode_batch, _host, _long, _long_host, a merged detection included). */
+int ofdm_fcs_wrap_batch(ofdm_ctx *ctx, const uint8_t *in_dev, int64_t n_frames, int64_t in_stride, const int32_t *in_len_dev,
+                        int64_t n_bytes, uint8_t *out_dev, int64_t out_stride, int32_t *out_len_dev);
+int ofdm_fcs_check_batch(ofdm_ctx *ctx, const uint8_t *row_dev, int64_t n_frames, int64_t row_stride, const int32_t *row_len_dev,
+                         int64_t n_row, uint8_t *out_dev, int64_t out_stride, int32_t *out_len_dev, int32_t *ok_dev);
+
 /* ------------------------------------------------------------------ pipelines */
 
 /* encode (src/transmitter.rs:11-58) for a batch: frame f = [lock][preamble x4][training x5][data symbols],
@@ -430,7 +472,9 @@ int ofdm_tx_encode_batch(ofdm_ctx *ctx, const uint8_t *payload_dev, int64_t n_fr
  * ecc = OFDM_ECC_CONV_K7F_* (likewise in every wrapper): the rule of "punctured rates and framed modes" above; status may become
  * OFDM_FRAME_HEADER.  With avail = max(max_symbols * bytes_per_symbol - 16 - 18, 0), out_stride >= floor(T' / 8) for the largest T'
  * with kept(T', rate) <= 8 avail (at most 3 avail / 4); a T' above 2^20: OFDM_ERR_UNSUPPORTED.
- * chest_mode = OFDM_CHEST_WLS (likewise in every wrapper, every ecc): "channel estimate" above is H' of "channel-estimate denoising". */
+ * chest_mode = OFDM_CHEST_WLS (likewise in every wrapper, every ecc): "channel estimate" above is H' of "channel-estimate denoising".
+ * ecc = OFDM_ECC_FCS + mode (likewise in every wrapper): mode's rule above, then the check of "frame check sequence": out_len = the
+ * p bytes that were sent, or status OFDM_FRAME_FCS and out_len 0; out_stride >= max(R - 8, 0) with R = mode's row for max_symbols. */
 int ofdm_rx_decode_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t frame_stride,
                          int64_t frame_len, int64_t n_lags, int32_t max_symbols, uint8_t *out_dev,
                          int64_t out_stride, int32_t *out_len_dev, int32_t *status_dev, int32_t *offset_dev,

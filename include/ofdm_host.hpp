@@ -100,7 +100,8 @@ class Context {
         const int S = symbol_len();
         if (max_symbols <= 0) max_symbols = (int32_t)std::max<int64_t>((n + S - 1) / S - 10, 1);
         int64_t ob = std::max<int64_t>((int64_t)max_symbols * ofdm_bytes_per_symbol(ctx_), 4);
-        if (rs_outer(ecc_)) ob = ofdm_rs255_decoded_len(ob); // whole 223-byte blocks of the longest body, the trailing zero block included
+        if (rs_outer(base_ecc(ecc_))) ob = ofdm_rs255_decoded_len(ob); // whole 223-byte blocks of the longest body, the trailing zero block included
+        // (OFDM_ECC_FCS + mode asks for 8 bytes less than mode: the row above is large enough)
         Decoded r;
         r.bytes.resize((size_t)ob);
         int32_t len = 0;
@@ -114,6 +115,7 @@ class Context {
         Decoded r = decode_capture(fc.data(), (int64_t)fc.size(), max_symbols);
         if (r.status == OFDM_FRAME_SHORT) throw Error("Input not long enough, bailing early"); // src/receiver.rs:27-29
         if (r.status == OFDM_FRAME_UNCORRECTABLE) throw Error("uncorrectable Reed-Solomon block"); // the reference returns None
+        if (r.status == OFDM_FRAME_FCS) throw Error("frame check failed: the payload is damaged"); // OFDM_ECC_FCS + mode
         if (r.status != OFDM_FRAME_OK) throw Error("decode failed, frame status " + std::to_string(r.status));
         return std::move(r.bytes);
     }
@@ -225,6 +227,31 @@ class Context {
         if (corrected) check(ofdm_memcpy_d2h(ctx_, corrected, dfix.p, sizeof(int32_t)), "d2h");
         return out;
     }
+    // CRC-32 frame check on the device (the OFDM_ECC_FCS + mode contexts apply it inside encode / decode; these are the bare stages):
+    // one row -> its envelope [u32 LE n][data][u32 LE crc32 of both], and one delivered row -> the payload of a valid envelope, or
+    // nullopt (bytes behind the envelope are ignored)
+    std::vector<uint8_t> fcs_wrap(const std::vector<uint8_t> &data) {
+        std::vector<uint8_t> out(data.size() + OFDM_FCS_OVERHEAD);
+        DevBuf din(ctx_, data.size()), dout(ctx_, out.size());
+        if (!data.empty()) check(ofdm_memcpy_h2d(ctx_, din.p, data.data(), data.size()), "h2d");
+        check(ofdm_fcs_wrap_batch(ctx_, (const uint8_t *)din.p, 1, (int64_t)data.size(), nullptr, (int64_t)data.size(), (uint8_t *)dout.p,
+                                  (int64_t)out.size(), nullptr), "ofdm_fcs_wrap_batch");
+        check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
+        return out;
+    }
+    std::optional<std::vector<uint8_t>> fcs_check(const std::vector<uint8_t> &row) {
+        std::vector<uint8_t> out(row.size() > OFDM_FCS_OVERHEAD ? row.size() - OFDM_FCS_OVERHEAD : 0);
+        DevBuf din(ctx_, row.size()), dout(ctx_, out.size()), dres(ctx_, 2 * sizeof(int32_t));
+        if (!row.empty()) check(ofdm_memcpy_h2d(ctx_, din.p, row.data(), row.size()), "h2d");
+        check(ofdm_fcs_check_batch(ctx_, (const uint8_t *)din.p, 1, (int64_t)row.size(), nullptr, (int64_t)row.size(), (uint8_t *)dout.p,
+                                   (int64_t)out.size(), (int32_t *)dres.p, (int32_t *)dres.p + 1), "ofdm_fcs_check_batch");
+        int32_t res[2] = {0, 0}; // out_len, ok
+        check(ofdm_memcpy_d2h(ctx_, res, dres.p, sizeof(res)), "d2h");
+        if (!res[1]) return std::nullopt;
+        if (!out.empty()) check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
+        out.resize((size_t)res[0]);
+        return out;
+    }
     // channel-estimate denoising (EXT-5; OFDM_CHEST_WLS as the context's chest_mode applies it inside decode; this is the bare stage):
     // rows of n_fft bins of an estimate -> the weighted least-squares fit of cp_len taps to every row, as n_fft bins again
     std::vector<Complex64> chest_smooth(const std::vector<Complex64> &hk) {
@@ -257,6 +284,8 @@ class Context {
         return ecc == OFDM_ECC_RS255 || ecc == OFDM_ECC_RS255_K7F_R12 || ecc == OFDM_ECC_RS255_K7F_R23 ||
                ecc == OFDM_ECC_RS255_K7F_R34;
     }
+    // the mode under the frame check of an OFDM_ECC_FCS + mode value, else ecc itself
+    static int base_ecc(int ecc) { return ecc >= OFDM_ECC_FCS ? ecc - OFDM_ECC_FCS : ecc; }
     ofdm_ctx *ctx_ = nullptr;
     int ecc_ = OFDM_ECC_NONE;
     int n_fft_ = 64;
@@ -286,13 +315,17 @@ inline Context &cached_context(bool guard_bands, ModulationScheme m, int n_fft =
 }
 
 // free functions with the reference's optional-argument defaults (src/transmitter.rs:16-17, src/receiver.rs:16,83)
+// fcs: the CRC-32 frame check around the payload (ecc = OFDM_ECC_FCS + OFDM_ECC_NONE): decode returns exactly the bytes that were
+// sent or throws
 inline std::vector<Complex64> encode(const std::vector<uint8_t> &data, std::optional<bool> guard_bands = std::nullopt,
-                                     std::optional<ModulationScheme> modulation = std::nullopt) {
-    return cached_context(guard_bands.value_or(false), modulation.value_or(ModulationScheme::Bpsk)).encode(data);
+                                     std::optional<ModulationScheme> modulation = std::nullopt, bool fcs = false) {
+    return cached_context(guard_bands.value_or(false), modulation.value_or(ModulationScheme::Bpsk), 64, fcs ? OFDM_ECC_FCS : OFDM_ECC_NONE)
+        .encode(data);
 }
 inline std::vector<uint8_t> decode(std::vector<Complex64> samples, std::optional<bool> guard_bands = std::nullopt,
-                                   std::optional<ModulationScheme> modulation = std::nullopt) {
-    return cached_context(guard_bands.value_or(false), modulation.value_or(ModulationScheme::Bpsk), 64, OFDM_ECC_NONE, OFDM_CFO_ABS)
+                                   std::optional<ModulationScheme> modulation = std::nullopt, bool fcs = false) {
+    return cached_context(guard_bands.value_or(false), modulation.value_or(ModulationScheme::Bpsk), 64, fcs ? OFDM_ECC_FCS : OFDM_ECC_NONE,
+                          OFDM_CFO_ABS)
         .decode(std::move(samples));
 }
 
@@ -377,6 +410,9 @@ inline std::optional<std::vector<uint8_t>> decipher_transmission_bytes(const std
     check(rc, "ofdm_rs255_decode");
     return out;
 }
+
+// CRC-32 of IEEE 802.3 / zlib, host side (the check word of the OFDM_ECC_FCS envelope)
+inline uint32_t crc32(const std::vector<uint8_t> &data) { return ofdm_crc32(data.data(), (int64_t)data.size()); }
 
 // utils::Analysis (src/utils.rs:38-69)
 struct Analysis {

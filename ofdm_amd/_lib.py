@@ -41,6 +41,7 @@ SIGNATURES = {
     "ofdm_default_pilots": (C.c_int, [i32, i32, vp, vp]),
     "ofdm_stdrng_pilots": (C.c_int, [i32, i32, vp, vp]),
     "ofdm_chacha_block": (C.c_int, [vp, vp, i32, vp]),
+    "ofdm_crc32": (C.c_uint32, [vp, i64]),
     "ofdm_tx_symbols_batch": (C.c_int, [vp, vp, i64, vp, i64]),
     "ofdm_rs255_encoded_len": (C.c_int64, [i64]),
     "ofdm_rs255_decoded_len": (C.c_int64, [i64]),
@@ -83,6 +84,8 @@ SIGNATURES = {
     "ofdm_conv_k7_decode_punctured": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, i64]),
     "ofdm_rs255_encode_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64]),
     "ofdm_rs255_decode_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp]),
+    "ofdm_fcs_wrap_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp]),
+    "ofdm_fcs_check_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp]),
     "ofdm_rx_llr_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, i64, C.c_float, vp, i64]),
     "ofdm_sc_correlate_batch": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp, vp]),
     "ofdm_frequency_correction_batch": (C.c_int, [vp, vp, i64, i64, i64, vp]),

@@ -25,11 +25,16 @@ ECC_CONV_K7F_R12, ECC_CONV_K7F_R23, ECC_CONV_K7F_R34 = 10, 11, 12
 # outer Reed-Solomon(255,223) around the frames of an inner mode, 20 + inner (inner = ECC_NONE or a framed mode): the reference's
 # create_transmission_bytes / decipher_transmission_bytes inside encode / decode, on the device
 ECC_RS255, ECC_RS255_K7F_R12, ECC_RS255_K7F_R23, ECC_RS255_K7F_R34 = 20, 30, 31, 32
+# CRC-32 frame check around any of the eleven modes above, 64 + mode: decode delivers exactly the payload that was sent or reports the
+# frame with FRAME_FCS (tests/fcs_ref.py is the definition)
+ECC_FCS = 64
+FCS_OVERHEAD = 8  # OFDM_FCS_OVERHEAD: the envelope's length word and check word
 CONV_RATE_1_2, CONV_RATE_2_3, CONV_RATE_3_4 = 0, 1, 2
 SOFT_LLR_SCALE = 32.0  # OFDM_SOFT_LLR_SCALE (include/ofdm_hip.h): the llr_scale of the soft decode chain
 CFO_OFF, CFO_SIGNED, CFO_ABS = 0, 1, 2
 FRAME_OK, FRAME_SHORT, FRAME_NOSYNC, FRAME_BADTIMING, FRAME_HEADER = 0, -1, -2, -3, -4
 FRAME_UNCORRECTABLE = -5  # ECC_RS255*: an outer RS block with more than 16 byte errors (the reference returns None)
+FRAME_FCS = -6  # ECC_FCS + mode: the delivered row is not a valid envelope (length word or CRC-32 wrong)
 SYNC_SCHMIDL_COX, SYNC_REFERENCE = 0, 1
 RX_AUTO, RX_STAGED = 0, 1
 # channel estimate of the receive chain: the reference's bin-by-bin one, or that one denoised by a weighted least-squares fit of cp_len
@@ -94,6 +99,13 @@ def decipher_transmission_bytes(code: bytes) -> Optional[bytes]:
         return None
     _check(lib, rc, "ofdm_rs255_decode")
     return bytes(out)
+
+
+def crc32(data: bytes) -> int:
+    """ofdm_crc32: the CRC-32 of IEEE 802.3 / zlib, as the library's host code computes it (no GPU needed)."""
+    lib = _lib.load()
+    src = np.frombuffer(bytes(data), np.uint8).copy()
+    return int(lib.ofdm_crc32(src.ctypes.data if src.size else None, src.size))  # (no bytes: NULL, 0 -> 0 = crc32(b""))
 
 
 def sig_to_bytes(sig) -> bytes:
@@ -447,16 +459,55 @@ class Context:
                                                   _dev(fixed)), "rs255_decode_batch")
         return out, out_len, fixed
 
+    def fcs_wrap(self, data: torch.Tensor, lens: Optional[torch.Tensor] = None, want_len: bool = False,
+                 out: Optional[torch.Tensor] = None):
+        """ofdm_fcs_wrap_batch: rows of data [n_frames, n_bytes] (uint8; the rows may be strided) -> [n_frames, n_bytes + 8] envelopes
+        [u32 LE len][payload][u32 LE crc32 of both].  lens (int32 [n_frames], optional): the rows' own lengths (clamped to [0, n_bytes]);
+        a row is zero behind its own len + 8 bytes.  want_len: also return the envelope lengths (int32 [n_frames]).  out (optional): a
+        uint8 [n_frames, n_bytes + 8] tensor or view with contiguous rows."""
+        n, nb, stride = self._rows_u8(data, "fcs_wrap")
+        lens = self._lens_i32(lens, n, "fcs_wrap")
+        if out is None:
+            out = self.empty((n, nb + FCS_OVERHEAD), torch.uint8)
+        on, onb, ostride = self._rows_u8(out, "fcs_wrap (out)")
+        if on != n or onb != nb + FCS_OVERHEAD:
+            raise OfdmError("fcs_wrap: out must hold n_frames rows of n_bytes + 8 bytes")
+        out_len = self.empty((n,), torch.int32) if want_len else None
+        self._ck(self.lib.ofdm_fcs_wrap_batch(self.h, _dev(data), n, stride, _dev(lens), nb, _dev(out), ostride, _dev(out_len)),
+                 "fcs_wrap_batch")
+        return (out, out_len) if want_len else out
+
+    def fcs_check(self, rows: torch.Tensor, lens: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+        """ofdm_fcs_check_batch: rows [n_frames, n_row] (uint8; the rows may be strided), row f checked over its own lens[f] bytes
+        (clamped to [0, n_row]; n_row without lens) -> (bytes [n_frames, max(n_row - 8, 0)], out_len int32 [n_frames], ok int32
+        [n_frames]).  A valid row's payload is at the start of its output row with out_len = its length and ok = 1; an invalid row has
+        out_len = 0 and ok = 0.  out (optional): a uint8 [n_frames, >= n_row - 8] tensor or view with contiguous rows."""
+        n, nr, stride = self._rows_u8(rows, "fcs_check")
+        lens = self._lens_i32(lens, n, "fcs_check")
+        if out is None:
+            out = self.empty((n, max(nr - FCS_OVERHEAD, 0)), torch.uint8)
+        on, onb, ostride = self._rows_u8(out, "fcs_check (out)")
+        if on != n or onb < nr - FCS_OVERHEAD:
+            raise OfdmError("fcs_check: out must hold n_frames rows of at least n_row - 8 bytes")
+        out_len, ok = self.empty((n,), torch.int32), self.empty((n,), torch.int32)
+        self._ck(self.lib.ofdm_fcs_check_batch(self.h, _dev(rows), n, stride, _dev(lens), nr, _dev(out), max(ostride, onb), _dev(out_len), _dev(ok)),
+                 "fcs_check_batch")
+        return out, out_len, ok
+
     def decode_row_bytes(self, max_symbols: int) -> int:
         """Bytes per output row that the decode entry points are given for max_symbols (at least 4).  Modes without an outer code: the
         demodulated body, which bounds what each of them delivers.  ECC_RS255*: 223 (Lmax // 255 + 1), Lmax = the longest row the
-        inner mode can deliver -- the rule of include/ofdm_hip.h."""
+        inner mode can deliver.  ECC_FCS + mode: mode's row less the envelope's 8 bytes -- the rules of include/ofdm_hip.h."""
         body = max(max_symbols * self.bytes_per_symbol - 16, 0)
-        if self.ecc in (ECC_RS255, ECC_RS255_K7F_R12, ECC_RS255_K7F_R23, ECC_RS255_K7F_R34):
+        fcs = self.ecc >= ECC_FCS
+        ecc = self.ecc - ECC_FCS if fcs else self.ecc
+        if ecc in (ECC_RS255, ECC_RS255_K7F_R12, ECC_RS255_K7F_R23, ECC_RS255_K7F_R34):
             lmax = body
-            if self.ecc != ECC_RS255:  # a framed inner mode: the whole bytes of the steps a cut body still holds behind the length block
-                lmax = conv_max_steps(8 * max(body - 18, 0), self.ecc - ECC_RS255_K7F_R12) // 8
+            if ecc != ECC_RS255:  # a framed inner mode: the whole bytes of the steps a cut body still holds behind the length block
+                lmax = conv_max_steps(8 * max(body - 18, 0), ecc - ECC_RS255_K7F_R12) // 8
             body = int(self.lib.ofdm_rs255_decoded_len(lmax))
+        if fcs:
+            body = max(body - FCS_OVERHEAD, 0)
         return max(body, 4)
 
     def sc_correlate(self, frames: torch.Tensor, frame_len: Optional[int] = None, n_lags: int = 0):
@@ -741,11 +792,21 @@ def _ctx(n_fft, modulation, guard_bands, ecc=ECC_NONE, _replica: int = 0, **kw) 
     return _CTX_CACHE[key]
 
 
+def _with_fcs(ecc: int, fcs: bool) -> int:
+    return ecc + ECC_FCS if fcs and ecc < ECC_FCS else ecc
+
+
+_FRAME_ERRORS = {FRAME_NOSYNC: "no preamble found", FRAME_HEADER: "no length header decoded",
+                 FRAME_UNCORRECTABLE: "uncorrectable Reed-Solomon block (the reference returns None)",
+                 FRAME_FCS: "frame check failed: the payload is damaged",
+                 FRAME_BADTIMING: "timing offset outside the capture (the reference panics in split_off)"}
+
+
 def encode(data: bytes, guard_bands: Optional[bool] = None, modulation: Optional[int] = None, n_fft: int = 64,
-           ecc: int = ECC_NONE, **kw) -> np.ndarray:
+           ecc: int = ECC_NONE, fcs: bool = False, **kw) -> np.ndarray:
     """`ofdm::encode!(data, guard_bands, modulation)` (src/transmitter.rs:10-58): bytes -> Vec<Complex64>.
-    Defaults as the reference: guard_bands=false, modulation=Bpsk."""
-    ctx = _ctx(n_fft, BPSK if modulation is None else modulation, bool(guard_bands), ecc, **kw)
+    Defaults as the reference: guard_bands=false, modulation=Bpsk.  fcs: the CRC-32 frame check around the payload (ecc + ECC_FCS)."""
+    ctx = _ctx(n_fft, BPSK if modulation is None else modulation, bool(guard_bands), _with_fcs(ecc, fcs), **kw)
     pay = torch.frombuffer(bytearray(data) if len(data) else bytearray(1), dtype=torch.uint8)[: len(data)]
     pay = pay.reshape(1, len(data)).to(ctx.device)
     frames = ctx.encode_batch(pay)
@@ -764,10 +825,11 @@ def channel(transmission, snr: Optional[float] = None, timing_error: Optional[bo
 
 
 def decode(samples, guard_bands: Optional[bool] = None, modulation: Optional[int] = None, n_fft: int = 64,
-           ecc: int = ECC_NONE, **sync) -> bytes:
+           ecc: int = ECC_NONE, fcs: bool = False, **sync) -> bytes:
     """`ofdm::decode!(samples, guard_bands, modulation)` (src/receiver.rs:8-96): Vec<Complex64> -> Result<Vec<u8>>.
-    Raises DecodeError("Input not long enough, bailing early") where the reference returns Err."""
-    ctx = _ctx(n_fft, BPSK if modulation is None else modulation, bool(guard_bands), ecc, **sync)
+    Raises DecodeError("Input not long enough, bailing early") where the reference returns Err.  fcs: the frame was sent with
+    encode(..., fcs=True): exactly the payload comes back, or DecodeError when the check fails."""
+    ctx = _ctx(n_fft, BPSK if modulation is None else modulation, bool(guard_bands), _with_fcs(ecc, fcs), **sync)
     x = ctx.to_device(np.asarray(samples)).reshape(1, -1)
     max_symbols = max((x.shape[1] + ctx.S - 1) // ctx.S - 10, 1)
     res = ctx.decode_batch(x, max_symbols=max_symbols)
@@ -776,23 +838,23 @@ def decode(samples, guard_bands: Optional[bool] = None, modulation: Optional[int
     if status == FRAME_SHORT:
         raise DecodeError("Input not long enough, bailing early")
     if status != FRAME_OK:
-        raise DecodeError({FRAME_NOSYNC: "no preamble found", FRAME_HEADER: "no length header decoded",
-                           FRAME_UNCORRECTABLE: "uncorrectable Reed-Solomon block (the reference returns None)",
-                           FRAME_BADTIMING: "timing offset outside the capture (the reference panics in split_off)"}.get(status, "decode failed"))
+        raise DecodeError(_FRAME_ERRORS.get(status, "decode failed"))
     n = int(res["len"][0])
     return bytes(res["bytes"][0, :n].cpu().numpy())
 
 
 def decode_long(samples, guard_bands: Optional[bool] = None, modulation: Optional[int] = None, n_fft: int = 64,
-                ecc: int = ECC_NONE, world: int = 1, max_symbols: Optional[int] = None, device: int = 0, **sync):
+                ecc: int = ECC_NONE, world: int = 1, max_symbols: Optional[int] = None, device: int = 0, fcs: bool = False, **sync):
     """`ofdm::decode!` of ONE long capture (the 2 M-sample buffers of examples/jetson_rx.rs:15-17,48-49,84-86) on the HIP path.
     world > 1 rehearses the multi-GPU halo split on one device: `world` contexts, context r searching the lags
     dist.lag_ranges(...)[r] of the shared capture (ofdm_sc_correlate_long), the lowest range with a detection wins
     (dist.merge_first_detection), and that context runs the receive chain (ofdm_rx_decode_long with the merged detection).
-    Returns dict(bytes, len, status, offset, f_delta, metric); raises DecodeError where the reference returns Err."""
+    Returns dict(bytes, len, status, offset, f_delta, metric); raises DecodeError where the reference returns Err, and, with fcs (the
+    frame was sent with encode(..., fcs=True)), when the frame check fails."""
     from . import dist
 
     mod = BPSK if modulation is None else modulation
+    ecc = _with_fcs(ecc, fcs)
     ctxs = [_ctx(n_fft, mod, bool(guard_bands), ecc, device=device, _replica=r, **sync) for r in range(max(world, 1))]
     c0 = ctxs[0]
     x = samples if isinstance(samples, torch.Tensor) else c0.to_device(np.asarray(samples))
@@ -813,4 +875,6 @@ def decode_long(samples, guard_bands: Optional[bool] = None, modulation: Optiona
             "bytes": c0.empty((4,), torch.uint8), "len": 0, "status": FRAME_NOSYNC, "offset": 0, "f_delta": 0.0, "metric": 0.0}
     if res["status"] == FRAME_SHORT:
         raise DecodeError("Input not long enough, bailing early")
+    if fcs and res["status"] == FRAME_FCS:
+        raise DecodeError(_FRAME_ERRORS[FRAME_FCS])
     return res

@@ -45,6 +45,7 @@ struct Tuning {
     int debug_demod64 = 0, debug_sc = 0, debug_tx = 0; // profile build only (kProfile)
     int chest_solve_only = 0;      // ofdm_chest_smooth_batch: 1 = launch k_chest_solve alone on the rows given (into the workspace; nothing is delivered): its time on its own
     int soft_chunk_frames = 0;     // OFDM_ECC_HAMMING74_SOFT / OFDM_ECC_CONV_K7 decode: frames per k_sym<llr> + k_rx_finish_soft / k_viterbi_k7 step (0 = the LLR workspace's 256 MB bound)
+    int fcs_bitserial = 0;         // k_fcs_wrap / k_fcs_check: every lane reduces its chunk bit by bit in registers instead of through the slice-by-4 tables in LDS (A/B)
 };
 inline const Tuning &tuning_or_default(const Tuning *t) { static const Tuning d; return t ? *t : d; }
 
@@ -367,6 +368,38 @@ struct Rs255DecodeParams {
     int32_t *out_len = nullptr, *corrected = nullptr, *status_rw = nullptr;
 };
 hipError_t run_rs255_decode(const Rs255DecodeParams &p, int num_cu, const Tuning *tune, hipStream_t st);
+
+// ---- CRC-32 frame check (OFDM_ECC_FCS + mode, ofdm_fcs_wrap_batch / ofdm_fcs_check_batch; kernels_fcs.hip, definition: tests/fcs_ref.py)
+// IEEE 802.3 CRC-32 of n bytes on the host (ofdm_crc32)
+uint32_t crc32_host(const uint8_t *data, long long n);
+// k_fcs_wrap: rows of n_bytes payload bytes (row f: in_len[f], clamped, when in_len is given) -> envelopes [u32 LE len][payload][u32 LE
+// crc32 of both], zeros behind them up to n_bytes + 8; out_len (optional): every row's len + 8.  chunk and K are the launcher's.
+struct FcsWrapParams {
+    const uint8_t *in = nullptr;
+    long long n_frames = 0, in_stride = 0, n_bytes = 0;
+    const int32_t *in_len = nullptr;
+    uint8_t *out = nullptr;
+    long long out_stride = 0;
+    int32_t *out_len = nullptr;
+    int chunk = 4;
+    unsigned K[6] = {};
+};
+hipError_t run_fcs_wrap(FcsWrapParams p, int num_cu, const Tuning *tune, hipStream_t st);
+// k_fcs_check: rows of n_row bytes (row f: row_len[f], clamped, when row_len is given) -> the payload of a valid envelope at the start
+// of the output row (out_stride >= n_row - 8), out_len = its length, ok = 1; out_len = 0, ok = 0 for an invalid row (both optional in
+// stage mode).  Chain mode (status_rw != nullptr; out_len required, it may be row_len itself): rows with status != 0 are skipped with
+// out_len 0, an invalid row gets status OFDM_FRAME_FCS.
+struct FcsCheckParams {
+    const uint8_t *row = nullptr;
+    long long n_frames = 0, row_stride = 0, n_row = 0;
+    const int32_t *row_len = nullptr;
+    uint8_t *out = nullptr;
+    long long out_stride = 0;
+    int32_t *out_len = nullptr, *ok = nullptr, *status_rw = nullptr;
+    int chunk = 4;
+    unsigned K[6] = {};
+};
+hipError_t run_fcs_check(FcsCheckParams p, int num_cu, const Tuning *tune, hipStream_t st);
 
 // ---- EXT-5 channel-estimate denoising (OFDM_CHEST_WLS, ofdm_chest_smooth_batch; kernels_chest.hip, definition: tests/chest_ref.py)
 // rows of n_fft bins times the per-bin weight w (a weight of exactly 0 gives 0 whatever the bin holds); in == out allowed

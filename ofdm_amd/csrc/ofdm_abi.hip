@@ -344,6 +344,8 @@ int ofdm_stdrng_pilots(int32_t n_fft, int32_t cp_len, double *preamble, double *
     return OFDM_OK;
 }
 
+uint32_t ofdm_crc32(const uint8_t *data, int64_t n_bytes) { return (!data || n_bytes < 0) ? 0u : crc32_host(data, n_bytes); }
+
 int ofdm_chacha_block(const uint32_t *key8, const uint32_t *words12_15, int32_t rounds, uint32_t *out16) {
     if (!key8 || !words12_15 || !out16 || rounds <= 0 || (rounds & 1)) return OFDM_ERR_INVALID;
     StdRng::block(key8, words12_15, rounds, out16);
@@ -382,9 +384,7 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
     default: return OFDM_ERR_INVALID;
     }
     if (p->guard_bands != 0 && p->guard_bands != 1) return OFDM_ERR_INVALID;
-    if (p->ecc != OFDM_ECC_NONE && p->ecc != OFDM_ECC_HAMMING74 && p->ecc != OFDM_ECC_HAMMING74_SOFT && p->ecc != OFDM_ECC_CONV_K7 &&
-        framed_rate(p->ecc) < 0 && !rs_outer(p->ecc))
-        return OFDM_ERR_INVALID; // 3 and 4 are not modes, nor are 21 .. 29
+    if (!base_mode(base_ecc(p->ecc))) return OFDM_ERR_INVALID; // 3 and 4 are not modes, nor are 21 .. 29; 64 + a base mode is
     if (p->sync_window_reps < 1 || p->sync_window_reps > 3) return OFDM_ERR_INVALID;
     if (p->sync_backoff < 0 || p->sync_backoff > p->cp_len) return OFDM_ERR_INVALID;
     if (p->cfo_mode < OFDM_CFO_OFF || p->cfo_mode > OFDM_CFO_ABS) return OFDM_ERR_INVALID;
@@ -584,8 +584,10 @@ static int64_t inner_coded_len(int ecc, int64_t n) {
 }
 int64_t ofdm_coded_len(const ofdm_ctx *c, int64_t payload_bytes) {
     if (!c || payload_bytes < 0) return OFDM_ERR_INVALID;
+    const int ecc = base_ecc(c->prm.ecc);
+    if (fcs_outer(c->prm.ecc)) payload_bytes += OFDM_FCS_OVERHEAD; // OFDM_ECC_FCS + mode: the mode codes the envelope
     // OFDM_ECC_RS255*: the inner mode codes the RS blocks
-    return inner_coded_len(inner_ecc(c->prm.ecc), rs_outer(c->prm.ecc) ? ofdm_rs255_encoded_len(payload_bytes) : payload_bytes);
+    return inner_coded_len(inner_ecc(ecc), rs_outer(ecc) ? ofdm_rs255_encoded_len(payload_bytes) : payload_bytes);
 }
 int64_t ofdm_data_symbols(const ofdm_ctx *c, int64_t payload_bytes) {
     if (!c || payload_bytes < 0) return OFDM_ERR_INVALID;
@@ -807,6 +809,38 @@ int ofdm_rs255_decode_batch(ofdm_ctx *c, const uint8_t *code, int64_t n_frames, 
     p.out_stride = out_stride; p.out_len = out_len; p.corrected = corrected;
     c->trace.add("k_rs255_decode");
     HIP_TRY(c, run_rs255_decode(p, c->num_cu, &c->tune, c->stream));
+    return OFDM_OK;
+}
+
+// CRC-32 frame check on device rows (kernels_fcs.hip)
+int ofdm_fcs_wrap_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_t in_stride, const int32_t *in_len, int64_t n_bytes,
+                        uint8_t *out, int64_t out_stride, int32_t *out_len) {
+    if (!c || n_frames < 0 || n_bytes < 0 || in_stride < n_bytes || out_stride - OFDM_FCS_OVERHEAD < n_bytes) return OFDM_ERR_INVALID;
+    if (n_bytes > 0x7fffffffll - OFDM_FCS_OVERHEAD) return OFDM_ERR_UNSUPPORTED; // the length word and out_len are 32 bits
+    if (n_frames && (!out || (n_bytes && !in))) return OFDM_ERR_INVALID;
+    if (!n_frames) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    FcsWrapParams p;
+    p.in = in; p.n_frames = n_frames; p.in_stride = in_stride; p.n_bytes = n_bytes; p.in_len = in_len; p.out = out; p.out_stride = out_stride;
+    p.out_len = out_len;
+    c->trace.add("k_fcs_wrap");
+    HIP_TRY(c, run_fcs_wrap(p, c->num_cu, &c->tune, c->stream));
+    return OFDM_OK;
+}
+int ofdm_fcs_check_batch(ofdm_ctx *c, const uint8_t *row, int64_t n_frames, int64_t row_stride, const int32_t *row_len, int64_t n_row,
+                         uint8_t *out, int64_t out_stride, int32_t *out_len, int32_t *ok) {
+    if (!c || n_frames < 0 || n_row < 0 || row_stride < n_row || out_stride < 0 || out_stride < n_row - OFDM_FCS_OVERHEAD) return OFDM_ERR_INVALID;
+    if (n_row > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED;
+    if (n_frames && ((n_row > OFDM_FCS_OVERHEAD && !out) || (n_row && !row))) return OFDM_ERR_INVALID;
+    if (!n_frames) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    FcsCheckParams p;
+    p.row = row; p.n_frames = n_frames; p.row_stride = row_stride; p.n_row = n_row; p.row_len = row_len; p.out = out; p.out_stride = out_stride;
+    p.out_len = out_len; p.ok = ok;
+    c->trace.add("k_fcs_check");
+    HIP_TRY(c, run_fcs_check(p, c->num_cu, &c->tune, c->stream));
     return OFDM_OK;
 }
 
@@ -1048,6 +1082,8 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
     if (!c || n_frames < 0 || payload_bytes < 0 || payload_stride < 0) return OFDM_ERR_INVALID;
     if (n_frames && (!out || (payload_bytes && !payload))) return OFDM_ERR_INVALID;
     if (n_frames > 1 && payload_stride < payload_bytes) return OFDM_ERR_INVALID; // rows are prefetched for payload_bytes (include/ofdm_hip.h)
+    const bool fcs = fcs_outer(c->prm.ecc);
+    if (fcs && payload_bytes > 0x7fffffff - OFDM_FCS_OVERHEAD) return OFDM_ERR_UNSUPPORTED;
     const int64_t frame = ofdm_frame_samples(c, payload_bytes);
     if (out_stride < frame) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
@@ -1056,20 +1092,33 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
     const int S = c->S();
     const uint8_t *src = payload; int64_t src_stride = payload_stride; const int32_t *src_len = payload_len;
     int32_t src_bytes = payload_bytes;
-    const int ecc = inner_ecc(c->prm.ecc);
-    if (rs_outer(c->prm.ecc)) { // OFDM_ECC_RS255*: the inner mode's frame of the RS-coded rows
-        const int64_t rs_len = ofdm_rs255_encoded_len(payload_bytes);
+    const int base = base_ecc(c->prm.ecc), ecc = inner_ecc(base);
+    if (fcs) { // OFDM_ECC_FCS + mode: the base mode's frame of the envelopes
+        const int64_t env = (int64_t)payload_bytes + OFDM_FCS_OVERHEAD;
+        void *fw, *fl;
+        int rc = ws_get(c, 14, (size_t)env * (size_t)n_frames, &fw);
+        if (rc) return rc;
+        if ((rc = ws_get(c, 15, sizeof(int32_t) * (size_t)n_frames, &fl))) return rc;
+        FcsWrapParams fp;
+        fp.in = payload; fp.n_frames = n_frames; fp.in_stride = payload_stride; fp.n_bytes = payload_bytes; fp.in_len = payload_len;
+        fp.out = (uint8_t *)fw; fp.out_stride = env; fp.out_len = payload_len ? (int32_t *)fl : nullptr;
+        c->trace.add("k_fcs_wrap");
+        HIP_TRY(c, run_fcs_wrap(fp, c->num_cu, &c->tune, c->stream));
+        src = (const uint8_t *)fw; src_stride = env; src_len = payload_len ? (const int32_t *)fl : nullptr; src_bytes = (int32_t)env;
+    }
+    if (rs_outer(base)) { // OFDM_ECC_RS255*: the inner mode's frame of the RS-coded rows
+        const int64_t rs_len = ofdm_rs255_encoded_len(src_bytes);
         if (rs_len > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED;
         void *rw, *rl;
         int rc = ws_get(c, 11, (size_t)rs_len * (size_t)n_frames, &rw);
         if (rc) return rc;
         if ((rc = ws_get(c, 12, sizeof(int32_t) * (size_t)n_frames, &rl))) return rc;
         Rs255EncodeParams rp;
-        rp.in = payload; rp.n_frames = n_frames; rp.in_stride = payload_stride; rp.n_bytes = payload_bytes; rp.in_len = payload_len;
-        rp.out = (uint8_t *)rw; rp.out_stride = rs_len; rp.out_len = payload_len ? (int32_t *)rl : nullptr;
+        rp.in = src; rp.n_frames = n_frames; rp.in_stride = src_stride; rp.n_bytes = src_bytes; rp.in_len = src_len;
+        rp.out = (uint8_t *)rw; rp.out_stride = rs_len; rp.out_len = src_len ? (int32_t *)rl : nullptr;
         c->trace.add("k_rs255_encode");
         HIP_TRY(c, run_rs255_encode(rp, c->num_cu, &c->tune, c->stream));
-        src = (const uint8_t *)rw; src_stride = rs_len; src_len = payload_len ? (const int32_t *)rl : nullptr; src_bytes = (int32_t)rs_len;
+        src = (const uint8_t *)rw; src_stride = rs_len; src_len = src_len ? (const int32_t *)rl : nullptr; src_bytes = (int32_t)rs_len;
     }
     if (ecc != OFDM_ECC_NONE) { // HAMMING74 and HAMMING74_SOFT transmit the same frames, CONV_K7 its own code
         const int64_t coded = inner_coded_len(ecc, src_bytes);
@@ -1140,19 +1189,19 @@ static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_
                            int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
                            int32_t *status, int32_t *offset, double *f_delta, float *metric, const KnownSync *known);
 
-static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+// The decode chain of base mode `ecc` (no FCS mode) into rows out / out_stride
+static int rx_decode_base(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
                           int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
                           int32_t *status, int32_t *offset, double *f_delta, float *metric, const KnownSync *known) {
-    if (!c) return OFDM_ERR_INVALID;
-    if (!rs_outer(c->prm.ecc))
-        return rx_decode_inner(c, c->prm.ecc, in, n_frames, frame_stride, frame_len, n_lags, max_symbols, out, out_stride, out_len, status,
+    if (!rs_outer(ecc))
+        return rx_decode_inner(c, ecc, in, n_frames, frame_stride, frame_len, n_lags, max_symbols, out, out_stride, out_len, status,
                                offset, f_delta, metric, known);
     // OFDM_ECC_RS255*: the inner mode's chain into a workspace (dword rows: the fused frame kernels write their payload there
     // directly), then k_rs255_decode over what every frame delivered; out_len serves both as the inner length and the final one
     if (n_frames < 0 || frame_len <= 0 || max_symbols <= 0) return OFDM_ERR_INVALID;
     if (n_frames && (!in || !out || !out_len || !status)) return OFDM_ERR_INVALID;
     const int64_t raw_bytes = (int64_t)max_symbols * c->bytes_per_symbol();
-    const int64_t inner_max = inner_row_bytes(inner_ecc(c->prm.ecc), raw_bytes > 16 ? raw_bytes - 16 : 0);
+    const int64_t inner_max = inner_row_bytes(inner_ecc(ecc), raw_bytes > 16 ? raw_bytes - 16 : 0);
     if (out_stride < ofdm_rs255_decoded_len(inner_max)) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
     DeviceGuard dev_guard(c->device);
@@ -1160,7 +1209,7 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
     void *w_rows;
     int rc = ws_get(c, 11, (size_t)row * (size_t)n_frames, &w_rows);
     if (rc) return rc;
-    rc = rx_decode_inner(c, inner_ecc(c->prm.ecc), in, n_frames, frame_stride, frame_len, n_lags, max_symbols, (uint8_t *)w_rows, row, out_len,
+    rc = rx_decode_inner(c, inner_ecc(ecc), in, n_frames, frame_stride, frame_len, n_lags, max_symbols, (uint8_t *)w_rows, row, out_len,
                          status, offset, f_delta, metric, known);
     if (rc) return rc;
     Rs255DecodeParams rp;
@@ -1168,6 +1217,39 @@ static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
     rp.out = out; rp.out_stride = out_stride; rp.out_len = out_len; rp.status_rw = status;
     c->trace.add("k_rs255_decode");
     HIP_TRY(c, run_rs255_decode(rp, c->num_cu, &c->tune, c->stream));
+    return OFDM_OK;
+}
+
+static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                          int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
+                          int32_t *status, int32_t *offset, double *f_delta, float *metric, const KnownSync *known) {
+    if (!c) return OFDM_ERR_INVALID;
+    if (!fcs_outer(c->prm.ecc))
+        return rx_decode_base(c, c->prm.ecc, in, n_frames, frame_stride, frame_len, n_lags, max_symbols, out, out_stride, out_len, status,
+                              offset, f_delta, metric, known);
+    // OFDM_ECC_FCS + mode: the base mode's chain into a workspace of dword rows (the fused frame kernels and k_rs255_decode write
+    // there as they write to a caller's rows), then k_fcs_check over what every frame delivered, in place on status / out_len
+    if (n_frames < 0 || frame_len <= 0 || max_symbols <= 0) return OFDM_ERR_INVALID;
+    if (n_frames && (!in || !out || !out_len || !status)) return OFDM_ERR_INVALID;
+    const int ecc = base_ecc(c->prm.ecc);
+    const int64_t raw_bytes = (int64_t)max_symbols * c->bytes_per_symbol();
+    const int64_t base_max = base_row_bytes(ecc, raw_bytes > 16 ? raw_bytes - 16 : 0);
+    if (base_max > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED;
+    if (out_stride < base_max - OFDM_FCS_OVERHEAD) return OFDM_ERR_INVALID;
+    if (!n_frames) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    const int64_t row = (std::max<int64_t>(base_max, 4) + 3) & ~(int64_t)3;
+    void *w_rows;
+    int rc = ws_get(c, 14, (size_t)row * (size_t)n_frames, &w_rows);
+    if (rc) return rc;
+    rc = rx_decode_base(c, ecc, in, n_frames, frame_stride, frame_len, n_lags, max_symbols, (uint8_t *)w_rows, row, out_len, status, offset,
+                        f_delta, metric, known);
+    if (rc) return rc;
+    FcsCheckParams fp;
+    fp.row = (const uint8_t *)w_rows; fp.n_frames = n_frames; fp.row_stride = row; fp.n_row = base_max; fp.row_len = out_len;
+    fp.out = out; fp.out_stride = out_stride; fp.out_len = out_len; fp.status_rw = status;
+    c->trace.add("k_fcs_check");
+    HIP_TRY(c, run_fcs_check(fp, c->num_cu, &c->tune, c->stream));
     return OFDM_OK;
 }
 

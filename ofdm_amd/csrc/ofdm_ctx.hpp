@@ -35,7 +35,7 @@ struct ofdm_ctx {
     ofdm::ScStats sc_stats;             // list counters of the last Schmidl-Cox search (ofdm_get_tuning "stat_sc_*")
     int32_t *d_stats = nullptr;         // [2] their home on the device (owned by the context)
     // workspaces (grown on demand, never inside a captured region)
-    Workspace ws[14];
+    Workspace ws[16];
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     HostPipe *pipe = nullptr;     // created by the first host-buffer call, freed by ofdm_destroy
 
@@ -84,6 +84,15 @@ inline bool rs_outer(int ecc) { return ecc == OFDM_ECC_RS255 || (ecc >= OFDM_ECC
 // the mode whose frames travel: ecc itself, or the inner mode of an RS mode
 inline int inner_ecc(int ecc) { return rs_outer(ecc) ? ecc - OFDM_ECC_RS255 : ecc; }
 
+// OFDM_ECC_FCS + mode = 64 + mode: the CRC-32 frame check around the frames of `mode`, any of the eleven base modes (an RS mode included)
+inline bool base_mode(int ecc) {
+    return ecc == OFDM_ECC_NONE || ecc == OFDM_ECC_HAMMING74 || ecc == OFDM_ECC_HAMMING74_SOFT || ecc == OFDM_ECC_CONV_K7 || framed_rate(ecc) >= 0 ||
+           rs_outer(ecc);
+}
+inline bool fcs_outer(int ecc) { return ecc >= OFDM_ECC_FCS && base_mode(ecc - OFDM_ECC_FCS); }
+// the mode whose frames carry the envelope: ecc itself, or the base mode of an FCS mode
+inline int base_ecc(int ecc) { return fcs_outer(ecc) ? ecc - OFDM_ECC_FCS : ecc; }
+
 // Largest out_len the decode chain of mode `ecc` (no RS mode) can write for a frame whose body (the bytes behind the 16-byte length
 // header) is `body` bytes
 inline int64_t inner_row_bytes(int ecc, int64_t body) {
@@ -93,11 +102,16 @@ inline int64_t inner_row_bytes(int ecc, int64_t body) {
         return body >= ofdm::kConvLengthBlock ? ofdm::conv_max_steps(8 * (body - ofdm::kConvLengthBlock), framed_rate(ecc)) / 8 : 0;
     return (body / 7) * 4;                                                       // Hamming(7,4), hard or soft
 }
-// ... of the context's mode: the row size every decode entry point asks of its caller (include/ofdm_hip.h).  RS modes: the decoded
-// blocks of the longest row the inner mode can deliver.
+// ... of base mode `ecc` (no FCS mode).  RS modes: the decoded blocks of the longest row the inner mode can deliver.
+inline int64_t base_row_bytes(int ecc, int64_t body) {
+    const int64_t inner = inner_row_bytes(inner_ecc(ecc), body);
+    return rs_outer(ecc) ? ofdm_rs255_decoded_len(inner) : inner;
+}
+// ... of the context's mode: the row size every decode entry point asks of its caller (include/ofdm_hip.h).  FCS modes: the base
+// mode's row less the envelope's 8 bytes.
 inline int64_t decode_row_bytes(const ofdm_ctx *c, int64_t body) {
-    const int64_t inner = inner_row_bytes(inner_ecc(c->prm.ecc), body);
-    return rs_outer(c->prm.ecc) ? ofdm_rs255_decoded_len(inner) : inner;
+    const int64_t base = base_row_bytes(base_ecc(c->prm.ecc), body);
+    return fcs_outer(c->prm.ecc) ? (base > OFDM_FCS_OVERHEAD ? base - OFDM_FCS_OVERHEAD : 0) : base;
 }
 
 // internal cross-file helpers (C linkage only because their definitions sit inside the extern "C" blocks; not in ofdm_hip.h)

@@ -25,6 +25,9 @@
 //   channel-estimate denoising (EXT-5)
 //     chest_solve_only    ofdm_chest_smooth_batch launches k_chest_solve alone on the rows it is given, into its workspace, and delivers
 //                         nothing: the kernel's time on its own (tools/bench_chest.py)
+//   frame check (OFDM_ECC_FCS + mode)
+//     fcs_bitserial       k_fcs_wrap / k_fcs_check reduce every lane's chunk bit by bit in registers instead of through the slice-by-4
+//                         tables in LDS (tools/bench_fcs.py times both)
 //   profile build only (libofdm_hip_profile.so): ablation exits and s_memtime section timers
 //     debug_demod64, debug_sc, debug_tx
 #ifndef OFDM_TUNE_KEY
@@ -56,6 +59,7 @@ OFDM_TUNE_KEY("scb_two_segments", scb_two_segments, false)
 OFDM_TUNE_KEY("scb_big_tiles", scb_big_tiles, false)
 OFDM_TUNE_KEY("soft_chunk_frames", soft_chunk_frames, false)
 OFDM_TUNE_KEY("chest_solve_only", chest_solve_only, false)
+OFDM_TUNE_KEY("fcs_bitserial", fcs_bitserial, false)
 OFDM_TUNE_KEY("debug_demod64", debug_demod64, true)
 OFDM_TUNE_KEY("debug_sc", debug_sc, true)
 OFDM_TUNE_KEY("debug_tx", debug_tx, true)

@@ -67,6 +67,7 @@ int main(int argc, char **argv) {
     const char *corpus = "I met a traveller from an antique land, Who said: Two vast and trunkless legs of stone Stand in the desert. ";
     size_t num_bytes = 400;
     bool guard_bands = false, timing_error = false, ecc = false; // ecc: lab3c's ecc_enabled (outer RS(255,223), utils.rs:97-180)
+    bool fcs = false; // --fcs: the CRC-32 frame check inside encode / decode (ecc = OFDM_ECC_FCS): exactly the payload back, or an error
     ModulationScheme modulation = ModulationScheme::Qpsk;
     const char *tx_file = nullptr, *rx_file = nullptr; // examples/lab3c.rs: --transmit f / --receive f [--start a --stop b]
     long start = 0, stop = -1;
@@ -75,6 +76,7 @@ int main(int argc, char **argv) {
         if (!std::strcmp(argv[i], "--timing-error")) timing_error = true;          // lab3b
         else if (!std::strcmp(argv[i], "--guard")) guard_bands = true;
         else if (!std::strcmp(argv[i], "--ecc")) ecc = true;
+        else if (!std::strcmp(argv[i], "--fcs")) fcs = true;
         else if (!std::strcmp(argv[i], "--bpsk")) modulation = ModulationScheme::Bpsk;
         else if (!std::strcmp(argv[i], "--qam64")) modulation = ModulationScheme::Qam64;
         else if (!std::strcmp(argv[i], "--bytes") && i + 1 < argc) num_bytes = (size_t)std::atol(argv[++i]);
@@ -143,12 +145,12 @@ int main(int argc, char **argv) {
         if (rx_file) { // decode a stored capture (or a slice of it)
             std::vector<Complex64> cap;
             if (!read_fc32(rx_file, cap, start, stop)) { std::printf("cannot read %s\n", rx_file); return 4; }
-            auto received = finish(decode(std::move(cap), guard_bands, modulation));
+            auto received = finish(decode(std::move(cap), guard_bands, modulation, fcs));
             std::printf("received %zu bytes\n%.*s\n", received.size(), (int)std::min<size_t>(received.size(), 100), (const char *)received.data());
             if (received.size() != text.size()) return 2;
             return Analysis(text, received).num_errs == 0 ? 0 : 1;
         }
-        auto tx = encode(source, guard_bands, modulation);                         // ofdm::encode!
+        auto tx = encode(source, guard_bands, modulation, fcs);                    // ofdm::encode!
         if (tx_file) { // write the frame for tx_samples_from_file
             if (!write_fc32(tx_file, tx)) { std::printf("cannot write %s\n", tx_file); return 4; }
             std::printf("wrote %zu samples (%zu bytes) to %s\n", tx.size(), tx.size() * 8, tx_file);
@@ -156,7 +158,7 @@ int main(int argc, char **argv) {
         }
         double fd = 0;
         auto rx = channel(tx, 30.0, timing_error, 2021, &fd);                      // ofdm::channel!(snr: 30.0[, timing_error])
-        auto received = finish(decode(std::move(rx), guard_bands, modulation));    // ofdm::decode!
+        auto received = finish(decode(std::move(rx), guard_bands, modulation, fcs)); // ofdm::decode!
         if (received.size() != text.size()) { std::printf("length mismatch: %zu vs %zu\n", received.size(), text.size()); return 2; }
         Analysis a(text, received);
         std::printf("Analysis { num_errs: %u, num_block_errs: %u, err_rate: %g }  samples: %zu  f_delta: %g\n", a.num_errs,
