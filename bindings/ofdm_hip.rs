@@ -49,8 +49,12 @@ pub const OFDM_ECC_RS255: i32 = 20;
 pub const OFDM_ECC_RS255_K7F_R12: i32 = 30;
 pub const OFDM_ECC_RS255_K7F_R23: i32 = 31;
 pub const OFDM_ECC_RS255_K7F_R34: i32 = 32;
-pub const OFDM_FRAME_UNCORRECTABLE: i32 = -5; // OFDM_ECC_RS255*: an RS block with more than 16 byte errors (the reference returns None)
-// CRC-32 frame check around any of the eleven modes above, 64 + mode: decode delivers exactly the payload that was sent or reports
+pub const OFDM_FRAME_UNCORRECTABLE: i32 = -5; // OFDM_ECC_RS255*: an RS block with more than 16 byte errors (the reference returns None); OFDM_ECC_LDPC648: an unconverged code word
+// LDPC(648,324), rate 1/2, layered normalised min-sum from LLRs; the length travels in the first code word; parity unpinned by the
+// reference, tests/ldpc_ref.py is the definition (include/ofdm_hip.h)
+pub const OFDM_ECC_LDPC648: i32 = 16;
+pub const OFDM_LDPC_MAX_ITER: i32 = 20;
+// CRC-32 frame check around any of the twelve modes above, 64 + mode: decode delivers exactly the payload that was sent or reports
 // the frame with OFDM_FRAME_FCS; parity unpinned by the reference, tests/fcs_ref.py is the definition (include/ofdm_hip.h)
 pub const OFDM_ECC_FCS: i32 = 64;
 pub const OFDM_FCS_OVERHEAD: i64 = 8;
@@ -133,6 +137,13 @@ extern "C" {
                                    out_dev: *mut u8, out_stride: i64) -> c_int;
     pub fn ofdm_rs255_decode_batch(ctx: *mut ofdm_ctx, code_dev: *const u8, n_frames: i64, code_stride: i64, code_len_dev: *const i32,
                                    n_code: i64, out_dev: *mut u8, out_stride: i64, out_len_dev: *mut i32, corrected_dev: *mut i32) -> c_int;
+    pub fn ofdm_ldpc648_coded_len(payload_bytes: i64) -> i64;
+    pub fn ofdm_ldpc648_encode(info: *const u8, n_cw: i64, code: *mut u8) -> c_int;
+    pub fn ofdm_ldpc648_decode(llr: *const i8, n_cw: i64, max_iter: i32, out: *mut u8, iters: *mut i32) -> c_int;
+    pub fn ofdm_ldpc648_encode_batch(ctx: *mut ofdm_ctx, in_dev: *const u8, n_frames: i64, in_stride: i64, n_cw: i64, out_dev: *mut u8,
+                                     out_stride: i64) -> c_int;
+    pub fn ofdm_ldpc648_decode_batch(ctx: *mut ofdm_ctx, llr_dev: *const i8, n_frames: i64, llr_stride: i64, n_cw: i64, max_iter: i32,
+                                     out_dev: *mut u8, out_stride: i64, iters_dev: *mut i32) -> c_int;
     pub fn ofdm_fcs_wrap_batch(ctx: *mut ofdm_ctx, in_dev: *const u8, n_frames: i64, in_stride: i64, in_len_dev: *const i32, n_bytes: i64,
                                out_dev: *mut u8, out_stride: i64, out_len_dev: *mut i32) -> c_int;
     pub fn ofdm_fcs_check_batch(ctx: *mut ofdm_ctx, row_dev: *const u8, n_frames: i64, row_stride: i64, row_len_dev: *const i32,

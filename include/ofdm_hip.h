@@ -58,7 +58,8 @@ enum {
     OFDM_FRAME_NOSYNC = -2, /* no lag reached the Schmidl-Cox threshold */
     OFDM_FRAME_BADTIMING = -3, /* OFDM_SYNC_REFERENCE: offset = lag - 1 outside the capture (the reference panics in split_off, receiver.rs:25) */
     OFDM_FRAME_HEADER = -4, /* fewer than 16 decoded bytes (reference panics in drain, receiver.rs:88) */
-    OFDM_FRAME_UNCORRECTABLE = -5, /* OFDM_ECC_RS255*: an outer RS block with more than 16 byte errors (the reference returns None) */
+    OFDM_FRAME_UNCORRECTABLE = -5, /* OFDM_ECC_RS255*: an outer RS block with more than 16 byte errors (the reference returns None);
+                                    * OFDM_ECC_LDPC648: a code word behind the first did not converge within OFDM_LDPC_MAX_ITER iterations */
     OFDM_FRAME_FCS = -6     /* OFDM_ECC_FCS + mode: the delivered row is not a valid envelope (length word or CRC-32 wrong); out_len 0 */
 };
 
@@ -76,13 +77,18 @@ enum { OFDM_MOD_BPSK = 1, OFDM_MOD_QPSK = 2, OFDM_MOD_QAM16 = 4, OFDM_MOD_QAM64 
  * OFDM_ECC_RS255 / OFDM_ECC_RS255_K7F_R12 / _R23 / _R34 = 20 + inner, inner = OFDM_ECC_NONE or OFDM_ECC_CONV_K7F_*: the reference's
  * outer Reed-Solomon(255,223) framing (create_transmission_bytes / decipher_transmission_bytes) around the inner mode's frame (see
  * "outer Reed-Solomon code on the device" below).  21 .. 29 and 33 .. 63 are rejected like every other value not named.
- * OFDM_ECC_FCS + mode = 64 + mode, mode any of the eleven values above (64, 65, 66, 69, 74, 75, 76, 84, 94, 95, 96): the CRC-32 frame
+ * OFDM_ECC_LDPC648: the quasi-cyclic LDPC(648,324) code, rate 1/2, 40 info bytes to 80 coded bytes, behind no other header than its
+ * own first code word, decoded by layered normalised min-sum from the same int8 LLRs: coded_len(p) = 80 ceil((p + 8) / 40) (see
+ * "LDPC(648,324)" below).  13 .. 15 and 17 .. 19 stay rejected, as does 36 (RS outside LDPC is not a mode).
+ * OFDM_ECC_FCS + mode = 64 + mode, mode any of the twelve values above (64, 65, 66, 69, 74, 75, 76, 80, 84, 94, 95, 96): the CRC-32 frame
  * check around the payload of that mode (see "frame check sequence" below) -- decode delivers exactly the bytes that were sent or
  * reports the frame.  Every other value from 64 upwards is rejected. */
 enum { OFDM_ECC_NONE = 0, OFDM_ECC_HAMMING74 = 1, OFDM_ECC_HAMMING74_SOFT = 2, OFDM_ECC_CONV_K7 = 5,
        OFDM_ECC_CONV_K7F_R12 = 10, OFDM_ECC_CONV_K7F_R23 = 11, OFDM_ECC_CONV_K7F_R34 = 12,
        OFDM_ECC_RS255 = 20, OFDM_ECC_RS255_K7F_R12 = 30, OFDM_ECC_RS255_K7F_R23 = 31, OFDM_ECC_RS255_K7F_R34 = 32,
-       OFDM_ECC_FCS = 64 };
+       OFDM_ECC_LDPC648 = 16, OFDM_ECC_FCS = 64 };
+/* iterations the OFDM_ECC_LDPC648 decode chain gives a code word: a definition, not a tuned number */
+#define OFDM_LDPC_MAX_ITER 20
 /* bytes the envelope of an OFDM_ECC_FCS mode adds to a payload: the u32 length word in front, the u32 CRC-32 behind */
 #define OFDM_FCS_OVERHEAD 8
 /* puncturing rate of ofdm_conv_k7_*_punctured (the framed modes' body rate is OFDM_ECC_CONV_K7F_Rxx - OFDM_ECC_CONV_K7F_R12) */
@@ -409,6 +415,62 @@ int ofdm_rs255_encode_batch(ofdm_ctx *ctx, const uint8_t *in_dev, int64_t n_fram
 int ofdm_rs255_decode_batch(ofdm_ctx *ctx, const uint8_t *code_dev, int64_t n_frames, int64_t code_stride, const int32_t *code_len_dev,
                             int64_t n_code, uint8_t *out_dev, int64_t out_stride, int32_t *out_len_dev, int32_t *corrected_dev);
 
+/* ------------------------------------------------------------------ LDPC(648,324) (north-star extension; DESIGN.md 3, EXT-2 LDPC)
+ * Parity unpinned by the reference (it has no LDPC code): tests/ldpc_ref.py (numpy, exact integers) is the definition;
+ * ofdm_ldpc648_encode / ofdm_ldpc648_decode are its executable form on the host, and the device agrees with both bit for bit.
+ * The code: quasi-cyclic, Z = 27, 12 x 24 blocks, 88 of them non-zero; entry s is the 27 x 27 identity shifted so that check z of block
+ * row l touches variable 27 c + (z + s) mod 27 of block column c, "-" a zero block:
+ *      0  -  -  -  0  0  -  -  0  -  -  0  1  0  -  -  -  -  -  -  -  -  -  -
+ *     22  0  -  - 17  -  0  0 12  -  -  -  -  0  0  -  -  -  -  -  -  -  -  -
+ *      6  -  0  - 10  -  -  - 24  -  0  -  -  -  0  0  -  -  -  -  -  -  -  -
+ *      2  -  -  0 20  -  -  - 25  0  -  -  -  -  -  0  0  -  -  -  -  -  -  -
+ *     23  -  -  -  3  -  -  -  0  -  9 11  -  -  -  -  0  0  -  -  -  -  -  -
+ *     24  - 23  1 17  -  3  - 10  -  -  -  -  -  -  -  -  0  0  -  -  -  -  -
+ *     25  -  -  -  8  -  -  -  7 18  -  -  0  -  -  -  -  -  0  0  -  -  -  -
+ *     13 24  -  -  0  -  8  -  6  -  -  -  -  -  -  -  -  -  -  0  0  -  -  -
+ *      7 20  - 16 22 10  -  - 23  -  -  -  -  -  -  -  -  -  -  -  0  0  -  -
+ *     11  -  -  - 19  -  -  - 13  -  3 17  -  -  -  -  -  -  -  -  -  0  0  -
+ *     25  -  8  - 23 18  - 14  9  -  -  -  -  -  -  -  -  -  -  -  -  -  0  0
+ *      3  -  -  - 16  -  -  2 25  5  -  -  1  -  -  -  -  -  -  -  -  -  -  0
+ * It is intended to be the n = 648, rate-1/2 matrix of 802.11n, written from memory and UNVERIFIED against the standard; this table
+ * is the definition (rank 324, invertible parity half, no 4-cycles: tests/test_ldpc_cpu.py).
+ * Code word: x[0 .. 319] = the 40 info bytes, each LSB first; x[320 .. 323] = 0 (shortened); x[324 .. 647] = the unique parity with
+ * H x = 0.  Sent: x[0 .. 319] ++ x[324 .. 643] packed LSB first, 80 bytes; the last four parity bits are punctured.
+ * Decoder: 640 int8 LLRs a code word, positive = bit 1.  Layered normalised min-sum, factor 3/4, exact integers; inside, positive =
+ * bit 0.  Q_v = -L_v (v < 320), +2047 (v = 320 .. 323), -L_{v-4} (v = 324 .. 643), 0 (v = 644 .. 647); all R = 0.  Iterations it =
+ * 1, 2, ...; in each the block rows l = 0 .. 11 in order; for check z of the row, with its edges e in table order and v_e their
+ * variables:  T_e = clamp(Q_{v_e} - R_e, +-2047);  m_e = min over e' != e of |T_e'|;  sign_e = product over e' != e of (T_e' < 0 ? -1
+ * : +1);  R_e = sign_e min((3 m_e) >> 2, 127);  Q_{v_e} = clamp(T_e + R_e, +-2047).  After each whole iteration x_v = (Q_v < 0): if
+ * all 324 checks hold the code word has CONVERGED at iteration it and stops; otherwise up to max_iter iterations run.  The output is
+ * always x[0 .. 319] of the last iteration run; iters = it when converged, 0 when not.
+ * ofdm_ldpc648_coded_len(p) = 80 ceil((p + 8) / 40) (OFDM_ERR_INVALID for p < 0): host call, no context.
+ * ofdm_ldpc648_encode: n_cw blocks of 40 info bytes -> n_cw blocks of 80 code bytes, on the host.
+ * ofdm_ldpc648_decode: n_cw blocks of 640 LLRs -> n_cw blocks of 40 bytes and iters[n_cw] (optional), on the host; max_iter in 1 .. 64.
+ * ofdm_ldpc648_encode_batch / _decode_batch (k_ldpc_encode / k_ldpc_decode): the same on device rows, row f holding n_cw plain code
+ *   words (no frame rule); every code word runs to convergence or max_iter; iters_dev (optional) holds n_frames * n_cw counts, row
+ *   after row.  in_stride >= 40 n_cw and out_stride >= 80 n_cw (encode), llr_stride >= 640 n_cw and out_stride >= 40 n_cw (decode),
+ *   max_iter in 1 .. 64, n_frames, n_cw >= 0: OFDM_ERR_INVALID otherwise.  A zero count succeeds and writes nothing.
+ *
+ * Frame mode ecc = OFDM_ECC_LDPC648.  Info stream of a payload of p bytes: [u32 LE p][u32 LE ~p] ++ payload, zero-padded to B =
+ * ceil((p + 8) / 40) code words; coded_len(p) = 80 B; the frame is the OFDM_ECC_NONE frame of the coded stream (its 16-byte header
+ * carries 80 B and decode does not read it).  With per-row lengths row f codes its own len_f, zeros behind.
+ * Receive, for a frame the chain leaves at OFDM_FRAME_OK, body = the demodulated bytes behind the 16-byte header, nb = body / 80:
+ *   nb = 0: status OFDM_FRAME_HEADER, out_len 0.  Code word 0 is decoded from LLRs 128 .. 767 (OFDM_SOFT_LLR_SCALE, OFDM_LDPC_MAX_ITER
+ *   iterations at most); unconverged, or its bytes 4 .. 7 not the complement of bytes 0 .. 3: OFDM_FRAME_HEADER, out_len 0.  With p =
+ *   bytes 0 .. 3 and B = ceil((p + 8) / 40), computed in 64 bits, code words 1 .. min(B, nb) - 1 are decoded; one unconverged:
+ *   OFDM_FRAME_UNCORRECTABLE, out_len 0.  Otherwise min(p, 40 nb - 8) bytes are delivered with the status unchanged: a frame cut by
+ *   the end of the capture delivers its prefix.  Bytes of a row beyond out_len are unspecified.
+ * Rows: out_stride >= max(40 floor(body_max / 80) - 8, 0), body_max = max(max_symbols * bytes_per_symbol - 16, 0) (OFDM_ERR_INVALID
+ * otherwise), in every decode entry point (ofdm_rx_decode_batch, _host, _long, _long_host); chest_mode is honoured.  OFDM_ECC_FCS +
+ * OFDM_ECC_LDPC648 wraps the mode like any other; 20 + 16 (RS outside LDPC) is rejected. */
+int64_t ofdm_ldpc648_coded_len(int64_t payload_bytes);
+int ofdm_ldpc648_encode(const uint8_t *info, int64_t n_cw, uint8_t *code);
+int ofdm_ldpc648_decode(const int8_t *llr, int64_t n_cw, int32_t max_iter, uint8_t *out, int32_t *iters);
+int ofdm_ldpc648_encode_batch(ofdm_ctx *ctx, const uint8_t *in_dev, int64_t n_frames, int64_t in_stride, int64_t n_cw, uint8_t *out_dev,
+                              int64_t out_stride);
+int ofdm_ldpc648_decode_batch(ofdm_ctx *ctx, const int8_t *llr_dev, int64_t n_frames, int64_t llr_stride, int64_t n_cw, int32_t max_iter,
+                              uint8_t *out_dev, int64_t out_stride, int32_t *iters_dev /* optional, n_frames * n_cw */);
+
 /* ------------------------------------------------------------------ frame check sequence (north-star extension; DESIGN.md 3, EXT-2 frame check)
  * Parity unpinned by the reference (it has no check of its own): tests/fcs_ref.py over zlib.crc32 is the definition.
  * crc32 = the CRC of IEEE 802.3 / zlib: reflected polynomial 0xEDB88320, register initialised to 0xFFFFFFFF, result complemented;
@@ -451,7 +513,8 @@ int ofdm_fcs_check_batch(ofdm_ctx *ctx, const uint8_t *row_dev, int64_t n_frames
  * and written to out_dev[f*out_stride ..] (out_stride >= ofdm_frame_samples(payload_bytes)).
  * With ECC the payload is Hamming(7,4)-encoded first and the header carries the coded length (HAMMING74 and HAMMING74_SOFT alike);
  * with OFDM_ECC_CONV_K7 it is convolutionally encoded (a row of true length len_f codes to 2 (len_f + 1) bytes).  The 16-byte
- * header itself is never coded.  OFDM_ECC_CONV_K7F_*: the framed stream (length block + punctured body) of the row's len_f. */
+ * header itself is never coded.  OFDM_ECC_CONV_K7F_*: the framed stream (length block + punctured body) of the row's len_f.
+ * OFDM_ECC_LDPC648: the coded info stream of the row's len_f ("LDPC(648,324)" above). */
 int ofdm_tx_encode_batch(ofdm_ctx *ctx, const uint8_t *payload_dev, int64_t n_frames, int64_t payload_stride,
                          const int32_t *payload_len_dev, int32_t payload_bytes, ofdm_fc32 *out_dev,
                          int64_t out_stride);
@@ -473,6 +536,8 @@ int ofdm_tx_encode_batch(ofdm_ctx *ctx, const uint8_t *payload_dev, int64_t n_fr
  * OFDM_FRAME_HEADER.  With avail = max(max_symbols * bytes_per_symbol - 16 - 18, 0), out_stride >= floor(T' / 8) for the largest T'
  * with kept(T', rate) <= 8 avail (at most 3 avail / 4); a T' above 2^20: OFDM_ERR_UNSUPPORTED.
  * chest_mode = OFDM_CHEST_WLS (likewise in every wrapper, every ecc): "channel estimate" above is H' of "channel-estimate denoising".
+ * ecc = OFDM_ECC_LDPC648 (likewise in every wrapper): the frame rule of "LDPC(648,324)" above; status may become OFDM_FRAME_HEADER or
+ * OFDM_FRAME_UNCORRECTABLE; out_stride >= max(40 floor(body_max / 80) - 8, 0).
  * ecc = OFDM_ECC_FCS + mode (likewise in every wrapper): mode's rule above, then the check of "frame check sequence": out_len = the
  * p bytes that were sent, or status OFDM_FRAME_FCS and out_len 0; out_stride >= max(R - 8, 0) with R = mode's row for max_symbols. */
 int ofdm_rx_decode_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t frame_stride,

@@ -114,7 +114,7 @@ class Context {
         const auto fc = to_fc32(samples);
         Decoded r = decode_capture(fc.data(), (int64_t)fc.size(), max_symbols);
         if (r.status == OFDM_FRAME_SHORT) throw Error("Input not long enough, bailing early"); // src/receiver.rs:27-29
-        if (r.status == OFDM_FRAME_UNCORRECTABLE) throw Error("uncorrectable Reed-Solomon block"); // the reference returns None
+        if (r.status == OFDM_FRAME_UNCORRECTABLE) throw Error("uncorrectable block"); // RS: the reference returns None; LDPC: a code word did not converge
         if (r.status == OFDM_FRAME_FCS) throw Error("frame check failed: the payload is damaged"); // OFDM_ECC_FCS + mode
         if (r.status != OFDM_FRAME_OK) throw Error("decode failed, frame status " + std::to_string(r.status));
         return std::move(r.bytes);
@@ -225,6 +225,31 @@ class Context {
                                       (int64_t)out.size(), nullptr, (int32_t *)dfix.p), "ofdm_rs255_decode_batch");
         check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
         if (corrected) check(ofdm_memcpy_d2h(ctx_, corrected, dfix.p, sizeof(int32_t)), "d2h");
+        return out;
+    }
+    // LDPC(648,324) on the device (OFDM_ECC_LDPC648 applies it inside encode / decode; these are the bare stages): whole 40-byte blocks ->
+    // 80 code bytes each, and whole code words of 640 LLRs (positive = bit 1) -> 40 bytes each; iters (optional): per code word the
+    // iteration it converged at, 0 if it did not within max_iter
+    std::vector<uint8_t> ldpc_encode(const std::vector<uint8_t> &info) {
+        if (info.size() % 40) throw Error("ldpc_encode: whole 40-byte blocks expected");
+        std::vector<uint8_t> out(2 * info.size());
+        DevBuf din(ctx_, info.size()), dout(ctx_, out.size());
+        if (!info.empty()) check(ofdm_memcpy_h2d(ctx_, din.p, info.data(), info.size()), "h2d");
+        check(ofdm_ldpc648_encode_batch(ctx_, (const uint8_t *)din.p, 1, (int64_t)info.size(), (int64_t)(info.size() / 40), (uint8_t *)dout.p,
+                                        (int64_t)out.size()), "ofdm_ldpc648_encode_batch");
+        if (!out.empty()) check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
+        return out;
+    }
+    std::vector<uint8_t> ldpc_decode(const std::vector<int8_t> &llr, int32_t max_iter = OFDM_LDPC_MAX_ITER, std::vector<int32_t> *iters = nullptr) {
+        if (llr.size() % 640) throw Error("ldpc_decode: whole code words of 640 LLRs expected");
+        const size_t n_cw = llr.size() / 640;
+        std::vector<uint8_t> out(40 * n_cw);
+        DevBuf din(ctx_, llr.size()), dout(ctx_, out.size()), dit(ctx_, sizeof(int32_t) * n_cw);
+        if (!llr.empty()) check(ofdm_memcpy_h2d(ctx_, din.p, llr.data(), llr.size()), "h2d");
+        check(ofdm_ldpc648_decode_batch(ctx_, (const int8_t *)din.p, 1, (int64_t)llr.size(), (int64_t)n_cw, max_iter, (uint8_t *)dout.p,
+                                        (int64_t)out.size(), (int32_t *)dit.p), "ofdm_ldpc648_decode_batch");
+        if (!out.empty()) check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
+        if (iters) { iters->resize(n_cw); if (n_cw) check(ofdm_memcpy_d2h(ctx_, iters->data(), dit.p, sizeof(int32_t) * n_cw), "d2h"); }
         return out;
     }
     // CRC-32 frame check on the device (the OFDM_ECC_FCS + mode contexts apply it inside encode / decode; these are the bare stages):
@@ -413,6 +438,23 @@ inline std::optional<std::vector<uint8_t>> decipher_transmission_bytes(const std
 
 // CRC-32 of IEEE 802.3 / zlib, host side (the check word of the OFDM_ECC_FCS envelope)
 inline uint32_t crc32(const std::vector<uint8_t> &data) { return ofdm_crc32(data.data(), (int64_t)data.size()); }
+
+// LDPC(648,324) on the host (the code of OFDM_ECC_LDPC648; include/ofdm_hip.h): bytes a frame of p payload bytes carries, whole
+// 40-byte blocks -> 80 code bytes each, whole code words of 640 LLRs (positive = bit 1) -> 40 bytes each
+inline int64_t ldpc648_coded_len(int64_t payload_bytes) { return ofdm_ldpc648_coded_len(payload_bytes); }
+inline std::vector<uint8_t> ldpc648_encode(const std::vector<uint8_t> &info) {
+    if (info.size() % 40) throw Error("ldpc648_encode: whole 40-byte blocks expected");
+    std::vector<uint8_t> out(2 * info.size());
+    check(ofdm_ldpc648_encode(info.data(), (int64_t)(info.size() / 40), out.data()), "ofdm_ldpc648_encode");
+    return out;
+}
+inline std::vector<uint8_t> ldpc648_decode(const std::vector<int8_t> &llr, int32_t max_iter = OFDM_LDPC_MAX_ITER, std::vector<int32_t> *iters = nullptr) {
+    if (llr.size() % 640) throw Error("ldpc648_decode: whole code words of 640 LLRs expected");
+    std::vector<uint8_t> out(llr.size() / 16);
+    if (iters) iters->resize(llr.size() / 640);
+    check(ofdm_ldpc648_decode(llr.data(), (int64_t)(llr.size() / 640), max_iter, out.data(), iters ? iters->data() : nullptr), "ofdm_ldpc648_decode");
+    return out;
+}
 
 // utils::Analysis (src/utils.rs:38-69)
 struct Analysis {

@@ -84,6 +84,11 @@ SIGNATURES = {
     "ofdm_conv_k7_decode_punctured": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, i64]),
     "ofdm_rs255_encode_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64]),
     "ofdm_rs255_decode_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp]),
+    "ofdm_ldpc648_coded_len": (i64, [i64]),
+    "ofdm_ldpc648_encode": (C.c_int, [vp, i64, vp]),
+    "ofdm_ldpc648_decode": (C.c_int, [vp, i64, i32, vp, vp]),
+    "ofdm_ldpc648_encode_batch": (C.c_int, [vp, vp, i64, i64, i64, vp, i64]),
+    "ofdm_ldpc648_decode_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, vp, i64, vp]),
     "ofdm_fcs_wrap_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp]),
     "ofdm_fcs_check_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp]),
     "ofdm_rx_llr_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, i64, C.c_float, vp, i64]),

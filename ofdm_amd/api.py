@@ -28,12 +28,15 @@ ECC_RS255, ECC_RS255_K7F_R12, ECC_RS255_K7F_R23, ECC_RS255_K7F_R34 = 20, 30, 31,
 # CRC-32 frame check around any of the eleven modes above, 64 + mode: decode delivers exactly the payload that was sent or reports the
 # frame with FRAME_FCS (tests/fcs_ref.py is the definition)
 ECC_FCS = 64
+# LDPC(648,324), rate 1/2, layered min-sum from LLRs; the length travels in the first code word (tests/ldpc_ref.py is the definition)
+ECC_LDPC648 = 16
+LDPC_MAX_ITER = 20  # OFDM_LDPC_MAX_ITER: iterations the decode chain gives a code word
 FCS_OVERHEAD = 8  # OFDM_FCS_OVERHEAD: the envelope's length word and check word
 CONV_RATE_1_2, CONV_RATE_2_3, CONV_RATE_3_4 = 0, 1, 2
 SOFT_LLR_SCALE = 32.0  # OFDM_SOFT_LLR_SCALE (include/ofdm_hip.h): the llr_scale of the soft decode chain
 CFO_OFF, CFO_SIGNED, CFO_ABS = 0, 1, 2
 FRAME_OK, FRAME_SHORT, FRAME_NOSYNC, FRAME_BADTIMING, FRAME_HEADER = 0, -1, -2, -3, -4
-FRAME_UNCORRECTABLE = -5  # ECC_RS255*: an outer RS block with more than 16 byte errors (the reference returns None)
+FRAME_UNCORRECTABLE = -5  # ECC_RS255*: an outer RS block with more than 16 byte errors (the reference returns None); ECC_LDPC648: a code word did not converge
 FRAME_FCS = -6  # ECC_FCS + mode: the delivered row is not a valid envelope (length word or CRC-32 wrong)
 SYNC_SCHMIDL_COX, SYNC_REFERENCE = 0, 1
 RX_AUTO, RX_STAGED = 0, 1
@@ -459,6 +462,31 @@ class Context:
                                                   _dev(fixed)), "rs255_decode_batch")
         return out, out_len, fixed
 
+    def ldpc_encode(self, info: torch.Tensor) -> torch.Tensor:
+        """ofdm_ldpc648_encode_batch: rows of info [n_frames, 40 n_cw] (uint8; the rows may be strided) -> [n_frames, 80 n_cw] code bytes,
+        every 40-byte block coded on its own (LDPC(648,324): the info bytes, then 40 parity bytes)."""
+        n, nb, stride = self._rows_u8(info, "ldpc_encode")
+        if nb % 40:
+            raise OfdmError("ldpc_encode: rows must hold whole 40-byte blocks")
+        out = self.empty((n, 2 * nb), torch.uint8)
+        self._ck(self.lib.ofdm_ldpc648_encode_batch(self.h, _dev(info), n, max(stride, nb), nb // 40, _dev(out), 2 * nb), "ldpc648_encode_batch")
+        return out
+
+    def ldpc_decode(self, llr: torch.Tensor, max_iter: int = LDPC_MAX_ITER):
+        """ofdm_ldpc648_decode_batch: rows of llr [n_frames, 640 n_cw] (int8, positive = bit 1; the rows may be strided) -> (bytes
+        [n_frames, 40 n_cw], iters int32 [n_frames, n_cw]): layered normalised min-sum, every code word to convergence or max_iter (1 ..
+        64) iterations; iters = the iteration a code word converged at, 0 if it did not."""
+        if llr.dtype != torch.int8 or llr.dim() != 2 or llr.device != self.device or (llr.shape[1] > 1 and llr.stride(1) != 1):
+            raise OfdmError("ldpc_decode: expected an int8 tensor [n_frames, 640 n_cw] with contiguous rows on the context's device")
+        n, width = llr.shape
+        if width % 640:
+            raise OfdmError("ldpc_decode: rows must hold whole code words of 640 LLRs")
+        n_cw = width // 640
+        out, iters = self.empty((n, 40 * n_cw), torch.uint8), self.empty((n, n_cw), torch.int32)
+        self._ck(self.lib.ofdm_ldpc648_decode_batch(self.h, _dev(llr), n, max(llr.stride(0), width) if n > 1 else width, n_cw, int(max_iter),
+                                                    _dev(out), 40 * n_cw, _dev(iters)), "ldpc648_decode_batch")
+        return out, iters
+
     def fcs_wrap(self, data: torch.Tensor, lens: Optional[torch.Tensor] = None, want_len: bool = False,
                  out: Optional[torch.Tensor] = None):
         """ofdm_fcs_wrap_batch: rows of data [n_frames, n_bytes] (uint8; the rows may be strided) -> [n_frames, n_bytes + 8] envelopes
@@ -497,7 +525,8 @@ class Context:
     def decode_row_bytes(self, max_symbols: int) -> int:
         """Bytes per output row that the decode entry points are given for max_symbols (at least 4).  Modes without an outer code: the
         demodulated body, which bounds what each of them delivers.  ECC_RS255*: 223 (Lmax // 255 + 1), Lmax = the longest row the
-        inner mode can deliver.  ECC_FCS + mode: mode's row less the envelope's 8 bytes -- the rules of include/ofdm_hip.h."""
+        inner mode can deliver.  ECC_LDPC648: the info bytes of the whole code words less the two length words.  ECC_FCS + mode: mode's
+        row less the envelope's 8 bytes -- the rules of include/ofdm_hip.h."""
         body = max(max_symbols * self.bytes_per_symbol - 16, 0)
         fcs = self.ecc >= ECC_FCS
         ecc = self.ecc - ECC_FCS if fcs else self.ecc
@@ -506,6 +535,8 @@ class Context:
             if ecc != ECC_RS255:  # a framed inner mode: the whole bytes of the steps a cut body still holds behind the length block
                 lmax = conv_max_steps(8 * max(body - 18, 0), ecc - ECC_RS255_K7F_R12) // 8
             body = int(self.lib.ofdm_rs255_decoded_len(lmax))
+        if ecc == ECC_LDPC648:
+            body = max(40 * (body // 80) - 8, 0)
         if fcs:
             body = max(body - FCS_OVERHEAD, 0)
         return max(body, 4)
@@ -797,7 +828,7 @@ def _with_fcs(ecc: int, fcs: bool) -> int:
 
 
 _FRAME_ERRORS = {FRAME_NOSYNC: "no preamble found", FRAME_HEADER: "no length header decoded",
-                 FRAME_UNCORRECTABLE: "uncorrectable Reed-Solomon block (the reference returns None)",
+                 FRAME_UNCORRECTABLE: "uncorrectable block (Reed-Solomon: the reference returns None; LDPC: a code word did not converge)",
                  FRAME_FCS: "frame check failed: the payload is damaged",
                  FRAME_BADTIMING: "timing offset outside the capture (the reference panics in split_off)"}
 

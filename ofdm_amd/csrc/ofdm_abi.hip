@@ -2,6 +2,7 @@
 // Context, parameter validation, host-side constant tables (f64 -> f32), workspace and the orchestration of
 // the TX / RX pipelines.  No exceptions cross the boundary; every HIP failure is mapped to OFDM_ERR_HIP.
 #include "ofdm_ctx.hpp"
+#include "ldpc_table.h"
 
 #include <algorithm>
 #include <cmath>
@@ -384,7 +385,7 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
     default: return OFDM_ERR_INVALID;
     }
     if (p->guard_bands != 0 && p->guard_bands != 1) return OFDM_ERR_INVALID;
-    if (!base_mode(base_ecc(p->ecc))) return OFDM_ERR_INVALID; // 3 and 4 are not modes, nor are 21 .. 29; 64 + a base mode is
+    if (!base_mode(base_ecc(p->ecc))) return OFDM_ERR_INVALID; // 3 and 4 are not modes, nor are 21 .. 29 or 36; 64 + a base mode is
     if (p->sync_window_reps < 1 || p->sync_window_reps > 3) return OFDM_ERR_INVALID;
     if (p->sync_backoff < 0 || p->sync_backoff > p->cp_len) return OFDM_ERR_INVALID;
     if (p->cfo_mode < OFDM_CFO_OFF || p->cfo_mode > OFDM_CFO_ABS) return OFDM_ERR_INVALID;
@@ -580,6 +581,7 @@ int ofdm_bytes_per_symbol(const ofdm_ctx *c) { return c ? c->bytes_per_symbol() 
 static int64_t inner_coded_len(int ecc, int64_t n) {
     if (ecc == OFDM_ECC_CONV_K7) return 2 * (n + 1); // rate 1/2 over the payload and one tail byte
     if (framed_rate(ecc) >= 0) return kConvLengthBlock + conv_body_len(n, framed_rate(ecc));
+    if (ecc == OFDM_ECC_LDPC648) return ofdm_ldpc648_coded_len(n);
     return ecc != OFDM_ECC_NONE ? ((n + 3) / 4) * 7 : n; // the soft decoder reads the same code
 }
 int64_t ofdm_coded_len(const ofdm_ctx *c, int64_t payload_bytes) {
@@ -809,6 +811,36 @@ int ofdm_rs255_decode_batch(ofdm_ctx *c, const uint8_t *code, int64_t n_frames, 
     p.out_stride = out_stride; p.out_len = out_len; p.corrected = corrected;
     c->trace.add("k_rs255_decode");
     HIP_TRY(c, run_rs255_decode(p, c->num_cu, &c->tune, c->stream));
+    return OFDM_OK;
+}
+
+// LDPC(648,324) on device rows (kernels_ldpc.hip): rows of n_cw plain code words, no frame rule
+int ofdm_ldpc648_encode_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_t in_stride, int64_t n_cw, uint8_t *out, int64_t out_stride) {
+    if (!c || n_frames < 0 || n_cw < 0 || n_cw > (int64_t)1 << 40) return OFDM_ERR_INVALID;
+    if (in_stride < kLdpcInfoBytes * n_cw || out_stride < kLdpcCodeBytes * n_cw) return OFDM_ERR_INVALID;
+    if (n_frames && n_cw && (!in || !out)) return OFDM_ERR_INVALID;
+    if (!n_frames || !n_cw) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    LdpcEncodeParams p;
+    p.in = in; p.n_frames = n_frames; p.in_stride = in_stride; p.n_cw = n_cw; p.out = out; p.out_stride = out_stride;
+    c->trace.add("k_ldpc_encode");
+    HIP_TRY(c, run_ldpc_encode(p, c->num_cu, &c->tune, c->stream));
+    return OFDM_OK;
+}
+int ofdm_ldpc648_decode_batch(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, int64_t llr_stride, int64_t n_cw, int32_t max_iter,
+                              uint8_t *out, int64_t out_stride, int32_t *iters) {
+    if (!c || n_frames < 0 || n_cw < 0 || n_cw > (int64_t)1 << 40 || max_iter < 1 || max_iter > kLdpcMaxIterLimit) return OFDM_ERR_INVALID;
+    if (llr_stride < kLdpcSentBits * n_cw || out_stride < kLdpcInfoBytes * n_cw) return OFDM_ERR_INVALID;
+    if (n_frames && n_cw && (!llr || !out)) return OFDM_ERR_INVALID;
+    if (!n_frames || !n_cw) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    LdpcDecodeParams p;
+    p.llr = llr; p.n_frames = n_frames; p.llr_stride = llr_stride; p.n_cw = n_cw; p.max_iter = max_iter; p.out = out; p.out_stride = out_stride;
+    p.iters = iters;
+    c->trace.add("k_ldpc_decode");
+    HIP_TRY(c, run_ldpc_decode(p, c->num_cu, &c->tune, c->stream));
     return OFDM_OK;
 }
 
@@ -1123,7 +1155,7 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
     if (ecc != OFDM_ECC_NONE) { // HAMMING74 and HAMMING74_SOFT transmit the same frames, CONV_K7 its own code
         const int64_t coded = inner_coded_len(ecc, src_bytes);
         const int f_rate = framed_rate(ecc);
-        if ((ecc == OFDM_ECC_CONV_K7 || f_rate >= 0) && coded > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED; // (payload_bytes = INT32_MAX)
+        if ((ecc == OFDM_ECC_CONV_K7 || f_rate >= 0 || ecc == OFDM_ECC_LDPC648) && coded > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED; // (payload_bytes = INT32_MAX)
         void *cw, *cl;
         int rc = ws_get(c, 1, (size_t)(coded ? coded : 1) * (size_t)n_frames, &cw);
         if (rc) return rc;
@@ -1136,6 +1168,12 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
             c->trace.add("k_conv_encode_p");
             HIP_TRY(c, run_conv_encode_p(src, n_frames, src_stride, src_len, src_bytes, f_rate, kConvLengthBlock, (uint8_t *)cw, coded,
                                          (int32_t *)cl, c->stream));
+        } else if (ecc == OFDM_ECC_LDPC648) { // the code of [u32 LE p][u32 LE ~p] ++ payload, row by row
+            LdpcEncodeParams lp;
+            lp.in = src; lp.n_frames = n_frames; lp.in_stride = src_stride; lp.n_bytes = src_bytes; lp.in_len = src_len; lp.framed = 1;
+            lp.n_cw = coded / kLdpcCodeBytes; lp.out = (uint8_t *)cw; lp.out_stride = coded; lp.out_len = (int32_t *)cl;
+            c->trace.add("k_ldpc_encode");
+            HIP_TRY(c, run_ldpc_encode(lp, c->num_cu, &c->tune, c->stream));
         } else {
             HIP_TRY(c, run_ham_encode(src, n_frames, src_stride, src_len, src_bytes, (uint8_t *)cw, coded, (int32_t *)cl, c->stream));
         }
@@ -1322,7 +1360,8 @@ static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_
     // 3+4. channel estimate from the 5 training blocks and per data symbol CP strip + FFT + equalise + pilot phase +
     //      demap (receiver.rs:44-83).  N = 64: one fused wave-centric kernel; otherwise the generic pair.
     bool fused = false, finished = false;
-    const bool soft = ecc == OFDM_ECC_HAMMING74_SOFT || conv; // the fused frame kernels have no LLR epilogue: the generic chain
+    const bool ldpc = ecc == OFDM_ECC_LDPC648;
+    const bool soft = ecc == OFDM_ECC_HAMMING74_SOFT || conv || ldpc; // the fused frame kernels have no LLR epilogue: the generic chain
     const bool wls = c->prm.chest_mode == OFDM_CHEST_WLS;     // ... and take no channel estimate from outside: the generic chain
     if (N == 1024 && !soft && !wls) { // one workgroup per frame: channel estimate kept in registers, 16 x 64 FFT (kernels_rx1024.hip)
         const bool off = c->tune.no_rxframe1024 != 0; // A/B switch
@@ -1355,7 +1394,8 @@ static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_
         if (soft) {
             // 4s + 5s. per frame chunk: hard bytes (for the header) and LLRs in one k_sym<llr>, then the header and the ML decode of
             // the body (k_rx_finish_soft; OFDM_ECC_CONV_K7: k_viterbi_k7, which also needs a survivor slab per resident wavefront;
-            // OFDM_ECC_CONV_K7F_*: k_viterbi_k7f, which reads the length from its own coded block and may set status).
+            // OFDM_ECC_CONV_K7F_*: k_viterbi_k7f, which reads the length from its own coded block and may set status;
+            // OFDM_ECC_LDPC648: k_ldpc_decode, which reads the length from its first code word and may set status).
             // The LLR workspace holds one chunk: at most kSoftLlrBytes whatever n_frames is.
             const int64_t llr_row = (int64_t)max_symbols * c->carriers() * c->prm.modulation;
             const int64_t llr_stride = (llr_row + 15) & ~(int64_t)15;
@@ -1380,6 +1420,15 @@ static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_
                              (const int32_t *)w_nsym + f0, (const float2 *)w_hk + f0 * N, N, OFDM_SOFT_LLR_SCALE, (int8_t *)w_llr, llr_stride,
                              (uint8_t *)w_raw + f0 * raw_stride, raw_stride, f0 == 0);
                 if (rc) return rc;
+                if (ldpc) {
+                    LdpcDecodeParams lp;
+                    lp.llr = (const int8_t *)w_llr; lp.n_frames = nf; lp.llr_stride = llr_stride; lp.max_iter = OFDM_LDPC_MAX_ITER;
+                    lp.out = out + f0 * out_stride; lp.out_stride = out_stride; lp.status_rw = status + f0; lp.out_len = out_len + f0;
+                    lp.nsym = (const int32_t *)w_nsym + f0; lp.bytes_per_symbol = bps_bytes;
+                    if (f0 == 0) c->trace.add("k_ldpc_decode");
+                    HIP_TRY(c, run_ldpc_decode(lp, c->num_cu, &c->tune, c->stream));
+                    continue;
+                }
                 if (conv) {
                     if (f0 == 0) c->trace.add(f_rate < 0 ? "k_viterbi_k7" : "k_viterbi_k7f");
                     vp.n_frames = nf; vp.out = out + f0 * out_stride; vp.raw = (const uint8_t *)w_raw + f0 * raw_stride;

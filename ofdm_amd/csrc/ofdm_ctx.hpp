@@ -84,10 +84,10 @@ inline bool rs_outer(int ecc) { return ecc == OFDM_ECC_RS255 || (ecc >= OFDM_ECC
 // the mode whose frames travel: ecc itself, or the inner mode of an RS mode
 inline int inner_ecc(int ecc) { return rs_outer(ecc) ? ecc - OFDM_ECC_RS255 : ecc; }
 
-// OFDM_ECC_FCS + mode = 64 + mode: the CRC-32 frame check around the frames of `mode`, any of the eleven base modes (an RS mode included)
+// OFDM_ECC_FCS + mode = 64 + mode: the CRC-32 frame check around the frames of `mode`, any of the twelve base modes (an RS mode included)
 inline bool base_mode(int ecc) {
     return ecc == OFDM_ECC_NONE || ecc == OFDM_ECC_HAMMING74 || ecc == OFDM_ECC_HAMMING74_SOFT || ecc == OFDM_ECC_CONV_K7 || framed_rate(ecc) >= 0 ||
-           rs_outer(ecc);
+           rs_outer(ecc) || ecc == OFDM_ECC_LDPC648;
 }
 inline bool fcs_outer(int ecc) { return ecc >= OFDM_ECC_FCS && base_mode(ecc - OFDM_ECC_FCS); }
 // the mode whose frames carry the envelope: ecc itself, or the base mode of an FCS mode
@@ -97,6 +97,7 @@ inline int base_ecc(int ecc) { return fcs_outer(ecc) ? ecc - OFDM_ECC_FCS : ecc;
 // header) is `body` bytes
 inline int64_t inner_row_bytes(int ecc, int64_t body) {
     if (ecc == OFDM_ECC_NONE) return body;
+    if (ecc == OFDM_ECC_LDPC648) return body >= 80 ? 40 * (body / 80) - 8 : 0; // the whole code words' info bytes less the two length words
     if (ecc == OFDM_ECC_CONV_K7) return body / 2 >= 1 ? body / 2 - 1 : 0; // 4 body steps = body / 2 bytes, less the tail byte
     if (framed_rate(ecc) >= 0)                       // the steps a body cut at the end of the capture still holds, behind the length block
         return body >= ofdm::kConvLengthBlock ? ofdm::conv_max_steps(8 * (body - ofdm::kConvLengthBlock), framed_rate(ecc)) / 8 : 0;

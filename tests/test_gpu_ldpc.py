@@ -1,0 +1,401 @@
+"""GPU checks of the LDPC(648,324) mode (OFDM_ECC_LDPC648: k_ldpc_encode, k_ldpc_decode and the decode chain around them) against
+the numpy restatement tests/ldpc_ref.py, which is their definition (parity unpinned by the reference).  Everything compared with it
+is compared bit for bit, iteration counts included: once the LLRs exist nothing here is floating point."""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ldpc_ref as lr  # noqa: E402
+import ldpc_vectors as lv  # noqa: E402
+from test_gpu_conv import _data_snr  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 1), (3, 2), (5, 3), (70, 15), (9, 33)]   # (n_frames, n_cw): odd n_cw leaves the last code word without a partner
+
+
+def _api():
+    from ofdm_amd import api
+
+    return api
+
+
+def _ctx(**kw):
+    api = _api()
+    kw.setdefault("n_fft", 64)
+    kw.setdefault("modulation", api.QAM64)
+    kw.setdefault("guard_bands", True)
+    kw.setdefault("ecc", api.ECC_LDPC648)
+    return api.Context(**kw)
+
+
+def _odd_rows(c, host, dtype):
+    """host [n, w] -> a device view [n, w] with an odd row stride on an odd base address"""
+    n, w = host.shape
+    stride = w + 3 if (w + 3) & 1 else w + 4
+    buf = torch.full((n * stride + 1,), 99, dtype=dtype, device=c.device)
+    view = buf[1:].view(n, stride)[:, :w]
+    view.copy_(torch.from_numpy(host).to(c.device))
+    assert view.data_ptr() & 1 and (n == 1 or view.stride(0) & 1)
+    return view
+
+
+# ---------------------------------------------------------------------------------------------------------- 1. the stages
+@pytest.mark.parametrize("n_frames,n_cw", SHAPES)
+def test_decoder_stage_is_the_reference(n_frames, n_cw):
+    c = _ctx()
+    llr, want, want_it = lv.mixed(n_frames * n_cw)
+    assert (want_it == 0).any() or n_frames * n_cw < 8
+    dev = _odd_rows(c, llr.reshape(n_frames, n_cw * lr.SENT_BITS), torch.int8)
+    first = None
+    for cap in (0, 1, 3):                                  # the device-sized grid, then one and three workgroups for every frame
+        c.set_tuning("grid_cap", cap)
+        got, its = c.ldpc_decode(dev)
+        c.synchronize()
+        assert c.last_dispatch() == "k_ldpc_decode"
+        assert got.shape == (n_frames, 40 * n_cw) and its.shape == (n_frames, n_cw)
+        np.testing.assert_array_equal(its.cpu().numpy().reshape(-1), want_it, err_msg=str(cap))
+        np.testing.assert_array_equal(got.cpu().numpy().reshape(-1, 40), want, err_msg=str(cap))
+        first = got if first is None else first
+        assert torch.equal(first, got)
+    c.set_tuning("grid_cap", 0)
+
+
+@pytest.mark.parametrize("max_iter", [1, 5, 64])
+def test_decoder_stage_at_other_iteration_limits(max_iter):
+    c = _ctx()
+    llr, want, want_it = lv.mixed(66, max_iter)
+    dev = _odd_rows(c, llr.reshape(6, 11 * lr.SENT_BITS), torch.int8)
+    got, its = c.ldpc_decode(dev, max_iter=max_iter)
+    c.synchronize()
+    np.testing.assert_array_equal(its.cpu().numpy().reshape(-1), want_it)
+    np.testing.assert_array_equal(got.cpu().numpy().reshape(-1, 40), want)
+
+
+@pytest.mark.parametrize("n_frames,n_cw", SHAPES)
+def test_encoder_stage_is_the_reference(n_frames, n_cw):
+    c = _ctx()
+    info = np.random.default_rng(n_frames * 100 + n_cw).integers(0, 256, (n_frames, 40 * n_cw), dtype=np.uint8)
+    info[0, :40] = np.arange(40)                            # a known answer of tests/test_ldpc_cpu.py among them
+    for cap in (0, 1):
+        c.set_tuning("grid_cap", cap)
+        got = c.ldpc_encode(_odd_rows(c, info, torch.uint8))
+        c.synchronize()
+        assert c.last_dispatch() == "k_ldpc_encode" and got.shape == (n_frames, 80 * n_cw)
+        np.testing.assert_array_equal(got.cpu().numpy().reshape(-1, 80), lr.encode(info.reshape(-1, 40)))
+    c.set_tuning("grid_cap", 0)
+    assert got[0, 40:80].cpu().numpy().tobytes().hex() == "08e71a7c4a39f145219fcb02d9c773209884af579f8dcbf7b55f6baaa04a9df0d8e5c0cd24c9a196"
+
+
+def test_stage_argument_checks():
+    c = _ctx()
+    llr = torch.zeros((2, 1280), dtype=torch.int8, device=c.device)
+    out = torch.full((2, 160), 7, dtype=torch.uint8, device=c.device)
+    it = torch.full((4,), -9, dtype=torch.int32, device=c.device)
+    d = c.lib.ofdm_ldpc648_decode_batch
+    assert d(c.h, llr.data_ptr(), 2, 1280, 2, 20, out.data_ptr(), 80, it.data_ptr()) == 0
+    assert d(c.h, llr.data_ptr(), 2, 1280, 2, 20, out.data_ptr(), 80, None) == 0          # iters is optional
+    assert d(c.h, llr.data_ptr(), 2, 1279, 2, 20, out.data_ptr(), 80, None) == -1         # llr_stride below 640 n_cw
+    assert d(c.h, llr.data_ptr(), 2, 1280, 2, 20, out.data_ptr(), 79, None) == -1         # out_stride below 40 n_cw
+    for bad in (0, -1, 65):
+        assert d(c.h, llr.data_ptr(), 2, 1280, 2, bad, out.data_ptr(), 80, None) == -1
+    assert d(c.h, llr.data_ptr(), 2, 1280, 2, 64, out.data_ptr(), 80, None) == 0
+    assert d(c.h, llr.data_ptr(), -1, 1280, 2, 20, out.data_ptr(), 80, None) == -1
+    assert d(c.h, llr.data_ptr(), 2, 1280, -1, 20, out.data_ptr(), 80, None) == -1
+    assert d(c.h, None, 2, 1280, 2, 20, out.data_ptr(), 80, None) == -1
+    assert d(None, llr.data_ptr(), 2, 1280, 2, 20, out.data_ptr(), 80, None) == -1
+    c.synchronize()
+    assert it.tolist() == [1, 1, 1, 1]                      # all-zero LLRs converge at once
+    out.fill_(7); it.fill_(-9)
+    assert d(c.h, None, 0, 1280, 2, 20, None, 80, None) == 0 and d(c.h, llr.data_ptr(), 2, 0, 0, 20, out.data_ptr(), 0, it.data_ptr()) == 0
+    e = c.lib.ofdm_ldpc648_encode_batch
+    info = torch.zeros((2, 80), dtype=torch.uint8, device=c.device)
+    code = torch.full((2, 160), 7, dtype=torch.uint8, device=c.device)
+    assert e(c.h, info.data_ptr(), 2, 79, 2, code.data_ptr(), 160) == -1
+    assert e(c.h, info.data_ptr(), 2, 80, 2, code.data_ptr(), 159) == -1
+    assert e(c.h, info.data_ptr(), -1, 80, 2, code.data_ptr(), 160) == -1
+    assert e(c.h, info.data_ptr(), 2, 80, -1, code.data_ptr(), 160) == -1
+    assert e(c.h, None, 2, 80, 2, code.data_ptr(), 160) == -1 and e(None, info.data_ptr(), 2, 80, 2, code.data_ptr(), 160) == -1
+    assert e(c.h, None, 0, 80, 2, None, 160) == 0 and e(c.h, info.data_ptr(), 2, 0, 0, code.data_ptr(), 0) == 0
+    c.synchronize()
+    assert (out == 7).all() and (it == -9).all() and (code == 7).all()   # zero counts write nothing
+    assert e(c.h, info.data_ptr(), 2, 80, 2, code.data_ptr(), 160) == 0
+    c.synchronize()
+    assert not code.any()
+
+
+# ---------------------------------------------------------------------------------------------------------- 2. transmit
+def _streams(pay, lens, width):
+    out = np.zeros((pay.shape[0], width), np.uint8)
+    for f, ln in enumerate(lens):
+        s = lr.stream(pay[f, :ln].tobytes())
+        out[f, : s.size] = s
+    return out
+
+
+@pytest.mark.parametrize("n,mod", [(64, 6), (1024, 4), (256, 1)])
+def test_transmit_is_the_uncoded_frame_of_the_ldpc_stream(n, mod):
+    api = _api()
+    u = _ctx(n_fft=n, modulation=mod, ecc=api.ECC_NONE)
+    c = _ctx(n_fft=n, modulation=mod)
+    for p in (0, 31, 32, 33, 560, 1304):
+        assert c.coded_len(p) == lr.coded_len(p)
+        assert (c.data_symbols(p), c.frame_samples(p)) == (u.data_symbols(lr.coded_len(p)), u.frame_samples(lr.coded_len(p)))
+    g = torch.Generator(device="cuda"); g.manual_seed(n + mod)
+    pay = torch.randint(0, 256, (5, 777), dtype=torch.uint8, device=c.device, generator=g)
+    host = pay.cpu().numpy()
+    width = lr.coded_len(777)
+    tx = c.encode_batch(pay)
+    assert "k_ldpc_encode" in c.last_dispatch().split("+")
+    coded = torch.from_numpy(_streams(host, [777] * 5, width)).to(c.device)
+    assert torch.equal(tx, u.encode_batch(coded))
+    lens = [777, 0, 13, 500, 776]                            # ragged rows: every row codes its own length, zeros behind
+    coded = torch.from_numpy(_streams(host, lens, width)).to(c.device)
+    clen = torch.tensor([lr.coded_len(ln) for ln in lens], dtype=torch.int32)
+    assert torch.equal(c.encode_batch(pay, lens=torch.tensor(lens, dtype=torch.int32)), u.encode_batch(coded, lens=clen))
+
+
+# ---------------------------------------------------------------------------------------------------------- helpers of 3 - 7
+def _link(ecc, n, mod, n_frames, payload, snr, seed, guard=True, **kw):
+    """the link of test_gpu_conv.py: seeded payloads, delays 1 .. 32, CFO within +-1 / S, one channel seed"""
+    api = _api()
+    c = api.Context(n_fft=n, modulation=mod, guard_bands=guard, ecc=ecc, **kw)
+    g = torch.Generator(device="cuda"); g.manual_seed(seed)
+    pay = torch.randint(0, 256, (n_frames, max(payload, 1)), dtype=torch.uint8, device=c.device, generator=g)[:, :payload].contiguous()
+    tx = c.encode_batch(pay)
+    d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
+    fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
+    rx = c.channel_batch(tx, snr_db=snr, seed=seed, delay=d, f_delta=fd, span=tx.shape[1] + 160)
+    return c, pay, rx, c.data_symbols(payload)
+
+
+def _reference_decode(c, rx, r, max_symbols, frame_len=None):
+    """per frame that reached the demodulator: (status, out_len, bytes) by the rule of the header -- ldpc_ref.receive over the LLRs
+    rx_llr returns for the frame at OFDM_SOFT_LLR_SCALE with the context's channel estimate, from LLR 128 on"""
+    frame_len = rx.shape[1] if frame_len is None else frame_len
+    hk = c.estimate_channel(rx, r["offset"], r["f_delta"], frame_len=frame_len)
+    L = c.rx_llr(rx, max_symbols, first_symbol=10, offset=r["offset"], f_delta=r["f_delta"], hk=hk, frame_len=frame_len)
+    c.synchronize()
+    L = L.cpu().numpy()
+    want = {}
+    for f in range(rx.shape[0]):
+        if int(r["status"][f]) not in (0, lr.HEADER_STATUS, lr.UNCORRECTABLE_STATUS):
+            continue
+        nsym = min(-(-(frame_len - int(r["offset"][f])) // c.S) - 10, max_symbols)      # k_rx_prepare's live symbols
+        body = nsym * c.bytes_per_symbol - 16
+        st, data = lr.receive(L[f, 128:], body)
+        want[f] = (st, len(data), data)
+    return want
+
+
+def _assert_is_reference(r, want):
+    for f, (st, n_out, data) in want.items():
+        assert int(r["status"][f]) == st, f
+        assert int(r["len"][f]) == n_out, f
+        assert bytes(r["bytes"][f, :n_out].cpu().numpy()) == data, f
+
+
+# ---------------------------------------------------------------------------------------------------------- 3. chain = stages
+@pytest.mark.parametrize("chest", [0, 1])
+@pytest.mark.parametrize("n,mod", [(64, 6), (256, 4), (1024, 6), (4096, 2)])
+def test_chain_is_the_composition_of_the_stages(n, mod, chest):
+    api = _api()
+    for snr, least in ((30.0, 7), (13.0, 0)):                # a clean channel, then one that leaves code words unconverged
+        c, pay, rx, D = _link(api.ECC_LDPC648, n, mod, 7, 400, _data_snr(n, snr), 5 + n, chest_mode=chest)
+        r = c.decode_batch(rx, max_symbols=D)
+        c.synchronize()
+        assert "k_ldpc_decode" in c.last_dispatch().split("+") and ("k_chest_solve" in c.last_dispatch()) == bool(chest)
+        want = _reference_decode(c, rx, r, D)
+        good = [f for f, (st, n_out, data) in want.items() if st == 0 and data == bytes(pay[f].cpu().numpy())]
+        print(f"N = {n}, {mod} bits, chest {chest}, {snr} dB: statuses {r['status'].tolist()}, {len(good)} of 7 whole")
+        assert len(want) == 7 and len(good) >= least
+        _assert_is_reference(r, want)
+        c.set_tuning("soft_chunk_frames", 3)                 # many chunks of the LLR workspace
+        r3 = c.decode_batch(rx, max_symbols=D)
+        c.set_tuning("soft_chunk_frames", 0)
+        for k in ("status", "len", "offset", "f_delta", "metric"):
+            assert torch.equal(r[k], r3[k]), k
+        _assert_is_reference(r3, want)
+
+
+# ---------------------------------------------------------------------------------------------------------- 4. every status branch
+def _forged_rows():
+    rng = np.random.default_rng(70)
+    pay = rng.integers(0, 256, 100, dtype=np.uint8).tobytes()            # 3 code words
+    info = lr.info_stream(pay).reshape(-1, 40)
+    good = lr.encode(info).reshape(-1)
+
+    def with_len(p, inv=None):
+        i = info.copy()
+        i[0, :4] = np.frombuffer((p & 0xFFFFFFFF).to_bytes(4, "little"), np.uint8)
+        i[0, 4:8] = np.frombuffer(((p ^ 0xFFFFFFFF) if inv is None else inv).to_bytes(4, "little"), np.uint8)
+        return lr.encode(i).reshape(-1)
+
+    junk = rng.integers(0, 256, 80, dtype=np.uint8)
+    rows = {"valid": good,
+            "cw0 random": np.concatenate([junk, good[80:]]),
+            "not complementary": with_len(100, 100 ^ 0xFFFFFFEF),
+            "later cw random": np.concatenate([good[:160], junk]),
+            "p beyond the frame": with_len(1000),
+            "p = 2^32 - 1": with_len(0xFFFFFFFF),
+            "short p": np.concatenate([with_len(20)[:80], junk, junk])}
+    return pay, rows
+
+
+def test_every_status_branch_deterministically():
+    api = _api()
+    u = _ctx(ecc=api.ECC_NONE)
+    c = _ctx()
+    pay, rows = _forged_rows()
+    names = list(rows)
+    tx = u.encode_batch(torch.from_numpy(np.stack([rows[k] for k in names])).to(u.device))
+    rx = u.channel_batch(tx, snr_db=40.0, seed=7, span=tx.shape[1] + 160)
+    D = c.data_symbols(100)
+    assert D == u.data_symbols(240) and D * c.bytes_per_symbol - 16 >= 240
+    seen = set()
+    S = c.S
+    cases = [("whole", D, rx.shape[1]), ("capture cut mid-frame", D, 8 + 15 * S + S // 2), ("max_symbols cut", 5, rx.shape[1]),
+             ("body < 80", 2, rx.shape[1])]
+    for what, syms, frame_len in cases:
+        cap = rx[:, :frame_len].contiguous()
+        for _ in range(2):                                   # deterministically
+            r = c.decode_batch(cap, max_symbols=syms)
+            c.synchronize()
+            want = _reference_decode(c, cap, r, syms)
+            assert len(want) == len(names), what
+            _assert_is_reference(r, want)
+        st = dict(zip(names, r["status"].tolist()))
+        ln = dict(zip(names, r["len"].tolist()))
+        seen |= set(st.values())
+        if what == "whole":
+            assert st == {"valid": 0, "cw0 random": api.FRAME_HEADER, "not complementary": api.FRAME_HEADER,
+                          "later cw random": api.FRAME_UNCORRECTABLE, "p beyond the frame": 0, "p = 2^32 - 1": 0, "short p": 0}, st
+            assert (ln["valid"], ln["p beyond the frame"], ln["p = 2^32 - 1"], ln["short p"]) == (100, 112, 112, 20)
+            assert bytes(r["bytes"][0, :100].cpu().numpy()) == pay and bytes(r["bytes"][6, :20].cpu().numpy()) == pay[:20]
+        elif what == "body < 80":
+            assert set(st.values()) == {api.FRAME_HEADER} and not any(ln.values())
+        else:                                                # two whole code words are left: the prefix, and the junk behind the cut unseen
+            assert st["valid"] == 0 and ln["valid"] == 72 and bytes(r["bytes"][0, :72].cpu().numpy()) == pay[:72], (what, st, ln)
+            assert st["later cw random"] == 0 and ln["later cw random"] == 72
+    assert seen == {0, api.FRAME_HEADER, api.FRAME_UNCORRECTABLE}, seen
+
+
+# ---------------------------------------------------------------------------------------------------------- 5. entry points
+@pytest.mark.parametrize("fcs", [False, True])
+def test_every_decode_entry_point(fcs):
+    api = _api()
+    ecc = api.ECC_LDPC648 + (api.ECC_FCS if fcs else 0)
+    c, pay, rx, D = _link(ecc, 64, 6, 6, 560, 30.0, 77)
+    assert c.coded_len(560) == lr.coded_len(560 + (8 if fcs else 0))
+    r = c.decode_batch(rx, max_symbols=D)
+    c.synchronize()
+    assert (r["status"] == 0).all() and (r["len"] == 560).all() and torch.equal(r["bytes"][:, :560], pay)
+    if fcs:
+        assert "k_ldpc_decode" in c.last_dispatch() and c.last_dispatch().endswith("k_fcs_check")
+    host = c.decode_host(rx.cpu().numpy(), max_symbols=D, chunk_frames=2)
+    for k in ("status", "len", "offset", "f_delta", "metric"):
+        np.testing.assert_array_equal(host[k], r[k].cpu().numpy(), err_msg=k)
+    assert (host["bytes"][:, :560] == pay.cpu().numpy()).all()
+    for f in (0, 5):
+        cap = rx[f].contiguous()
+        for res in (c.decode_long(cap, D), c.decode_long_host(cap.cpu().numpy(), D)):
+            assert (res["status"], res["len"], res["offset"]) == (0, 560, int(r["offset"][f]))
+            assert bytes(np.asarray(res["bytes"].cpu() if torch.is_tensor(res["bytes"]) else res["bytes"])[:560]) == bytes(pay[f].cpu().numpy())
+        assert api.decode(cap.cpu().numpy(), True, api.QAM64, ecc=api.ECC_LDPC648, fcs=fcs) == bytes(pay[f].cpu().numpy())
+        assert api.decode_long(cap.cpu().numpy(), True, api.QAM64, ecc=api.ECC_LDPC648, fcs=fcs)["len"] == 560
+    msg = b"a graph that is its own interleaver"
+    assert api.decode(api.encode(msg, True, api.QAM16, ecc=api.ECC_LDPC648, fcs=fcs), True, api.QAM16, ecc=api.ECC_LDPC648, fcs=fcs) == msg
+    # a row too short for what the chain can write is refused; decode_batch's own rows are long enough
+    need = lr.row_bytes(D * c.bytes_per_symbol - 16) - (8 if fcs else 0)
+    assert c.decode_row_bytes(D) == need
+    out = torch.zeros((1, need), dtype=torch.uint8, device=c.device)
+    i32 = torch.zeros((2,), dtype=torch.int32, device=c.device)
+    args = (c.h, rx.data_ptr(), 1, rx.shape[1], rx.shape[1], 0, D, out.data_ptr())
+    assert c.lib.ofdm_rx_decode_batch(*args, need - 1, i32.data_ptr(), i32[1:].data_ptr(), None, None, None) == -1
+    assert c.lib.ofdm_rx_decode_batch(*args, need, i32.data_ptr(), i32[1:].data_ptr(), None, None, None) == 0
+    c.synchronize()
+    assert i32.tolist() == [560, 0]
+
+
+def test_damaged_frame_with_the_frame_check_is_reported_never_delivered():
+    """A damaged info stream inside VALID code words: the LDPC decoder converges on it, and only the CRC-32 of the frame-check mode can
+    tell.  The stream is forged through an OFDM_ECC_NONE context."""
+    api = _api()
+    u = _ctx(ecc=api.ECC_NONE)
+    c = _ctx(ecc=api.ECC_LDPC648 + api.ECC_FCS)
+    plain = _ctx()
+    rng = np.random.default_rng(8)
+    pay = rng.integers(0, 256, 150, dtype=np.uint8)
+    env = c.fcs_wrap(torch.from_numpy(pay[None]).to(c.device))[0].cpu().numpy()
+    rows = []
+    for flip in (None, 60):
+        e = env.copy()
+        if flip is not None:
+            e[flip] ^= 0x04
+        rows.append(lr.stream(e.tobytes()))
+    tx = u.encode_batch(torch.from_numpy(np.stack(rows)).to(u.device))
+    rx = u.channel_batch(tx, snr_db=40.0, seed=3, span=tx.shape[1] + 160)
+    D = c.data_symbols(150)
+    r = c.decode_batch(rx, max_symbols=D)
+    c.synchronize()
+    assert r["status"].tolist() == [0, api.FRAME_FCS] and r["len"].tolist() == [150, 0]
+    assert bytes(r["bytes"][0, :150].cpu().numpy()) == pay.tobytes()
+    p = plain.decode_batch(rx, max_symbols=D)                # without the check the damaged envelope is delivered as it was sent
+    plain.synchronize()
+    assert p["status"].tolist() == [0, 0] and p["len"].tolist() == [158, 158]
+    with pytest.raises(api.DecodeError):
+        api.decode(rx[1].cpu().numpy(), True, api.QAM64, ecc=api.ECC_LDPC648, fcs=True)
+
+
+# ---------------------------------------------------------------------------------------------------------- 6. dispatch
+@pytest.mark.parametrize("n", [64, 1024])
+def test_dispatch_names_the_ldpc_kernels(n):
+    api = _api()
+    c, pay, rx, D = _link(api.ECC_LDPC648, n, 6, 2, 300, 30.0, 3)
+    c.decode_batch(rx, max_symbols=D)
+    dc = c.last_dispatch()
+    assert "k_sym<llr>" in dc and "k_ldpc_decode" in dc.split("+") and "k_rx_finish" not in dc and "k_viterbi" not in dc, dc
+    c.encode_batch(pay)
+    assert "k_ldpc_encode" in c.last_dispatch().split("+")
+    v, _, rxv, Dv = _link(api.ECC_CONV_K7F_R12, n, 6, 2, 300, 30.0, 3)   # the other modes keep their kernels
+    v.decode_batch(rxv, max_symbols=Dv)
+    assert "k_ldpc" not in v.last_dispatch()
+    v.encode_batch(pay)
+    assert "k_ldpc" not in v.last_dispatch()
+
+
+# ---------------------------------------------------------------------------------------------------------- 7. the point of the feature
+POINT_SNR_DB = 6.0   # the highest point of the sweep of tools/bench_ldpc.py at which CONV_K7F_R12 delivers fewer than 90 % of its frames whole
+
+
+def test_ldpc_against_the_framed_viterbi_mode_on_one_link():
+    """N = 64, 64-QAM, guard bands, 1 024 frames of 560 bytes at POINT_SNR_DB = 6 dB, the same payloads, delays, CFO and channel seed
+    for OFDM_ECC_CONV_K7F_R12 and OFDM_ECC_LDPC648.  6 dB is the highest point of the sweep in profiles/ldpc_ber_and_speed.json at
+    which CONV_K7F_R12 delivers fewer than 90 % of 4 096 frames whole (3 423, and 662 more with status 0 and damaged bytes; LDPC648:
+    4 039 whole, 57 reported, none wrong; at 7 dB CONV_K7F_R12 is at 3 876).  Asserted: no LDPC frame is delivered (status 0) with a
+    wrong length or wrong bytes, and LDPC delivers at least as many frames whole -- the sweep shows that with room to spare at every
+    point from 4 to 10 dB.  Both counts of this link are printed (the counts of these 1 024 frames are NOT YET MEASURED: the record's "point"
+    block of tools/bench_ldpc.py; the sweep's 4 096 frames at 6 dB are the figures above)."""
+    api = _api()
+    res = {}
+    for ecc in (api.ECC_CONV_K7F_R12, api.ECC_LDPC648):
+        c, pay, rx, D = _link(ecc, 64, 6, 1024, 560, POINT_SNR_DB, 9012)
+        r = c.decode_batch(rx, max_symbols=D)
+        c.synchronize()
+        good = (r["status"] == 0) & (r["len"] == 560)
+        good &= (r["bytes"][:, :560] == pay).all(dim=1)
+        res[ecc] = (r, pay, good)
+    assert torch.equal(res[api.ECC_CONV_K7F_R12][1], res[api.ECC_LDPC648][1])          # the same payloads
+    r, pay, good = res[api.ECC_LDPC648]
+    n_k7f, n_ldpc = int(res[api.ECC_CONV_K7F_R12][2].sum()), int(good.sum())
+    delivered = r["status"] == 0
+    wrong = int((delivered & ~good).sum())
+    print(f"{POINT_SNR_DB} dB, 1024 frames delivered whole: CONV_K7F_R12 {n_k7f}, LDPC648 {n_ldpc}; LDPC status 0 with a wrong length or "
+          f"wrong bytes: {wrong}; LDPC reported: header {int((r['status'] == api.FRAME_HEADER).sum())}, uncorrectable "
+          f"{int((r['status'] == api.FRAME_UNCORRECTABLE).sum())}")
+    assert wrong == 0
+    assert n_ldpc >= n_k7f, (n_ldpc, n_k7f)
