@@ -395,6 +395,25 @@ __device__ __forceinline__ void ham_decode_block(const uint8_t *src, uint8_t *ds
     }
 }
 
+// ---- the length header (src/receiver.rs:85-95): the bincode fixint little-endian u128 (src/packets/mod.rs:20-32) a frame's bytes start
+// with, as lo / hi, and what it makes of a demodulated body of `body` bytes.  Every finish kernel, fused or not, takes the rule from
+// here.  Macros, not functions: a function is simplified on its own before it is inlined -- the rule to a select that wants `lo`
+// before `hi == 0` is known -- and every kernel that uses one comes out different.
+// lo, hi (unsigned long long, 0 on entry) from global memory, byte by byte / as four dwords where the row allows it
+#define OFDM_HEADER_READ_BYTES(src, lo, hi) \
+    for (int i = 0; i < 8; ++i) { lo |= (unsigned long long)(src)[i] << (8 * i); hi |= (unsigned long long)(src)[8 + i] << (8 * i); }
+#define OFDM_HEADER_READ(src, lo, hi)                                                                                            \
+    {                                                                                                                            \
+        if (((uintptr_t)(src) & 3) == 0) {                                                                                       \
+            const uint32_t *h4 = reinterpret_cast<const uint32_t *>(src);                                                        \
+            lo = (unsigned long long)h4[0] | ((unsigned long long)h4[1] << 32); hi = (unsigned long long)h4[2] | ((unsigned long long)h4[3] << 32); \
+        } else { OFDM_HEADER_READ_BYTES(src, lo, hi) }                                                                           \
+    }
+// Vec::truncate: the header's value if it is below the body, else the whole body (T: the caller's own integer type), and whether the
+// body holds all the header announces (the frame was not cut short)
+#define OFDM_HEADER_KEEP(T, lo, hi, body) (((hi) == 0 && (lo) < (unsigned long long)(body)) ? (T)(lo) : (body))
+#define OFDM_HEADER_WHOLE(lo, hi, body) ((hi) == 0 && (lo) <= (unsigned long long)(body))
+
 // ---- soft decisions (OFDM_ECC_HAMMING74_SOFT, include/ofdm_hip.h; restated in tests/soft_ref.py)
 // Max-log LLR of axis bit b (b = 0: the Gray MSB) of a Gray-PAM axis with M = 2^m levels a_l = 2 l - (M - 1), at v = x (M - 1),
 // in closed form.  Bit b of level l is bit j = m - 1 - b of l ^ (l >> 1): constant over the levels [(2r - 1) h, (2r + 1) h),

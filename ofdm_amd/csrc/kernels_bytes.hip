@@ -287,15 +287,9 @@ __global__ __launch_bounds__(256) void k_rx_finish(const uint8_t *raw, long long
     if (status[f] != 0) { if (lane == 0) out_len[f] = 0; continue; }
     const uint8_t *src = raw + f * raw_stride;
     const long long body = (long long)nsym[f] * bytes_per_symbol - 16;
-    unsigned long long lo = 0, hi = 0; // bincode fixint little-endian u128 (src/packets/mod.rs:20-32)
-    if (((uintptr_t)src & 3) == 0) {
-        const uint32_t *h4 = reinterpret_cast<const uint32_t *>(src);
-        lo = (unsigned long long)h4[0] | ((unsigned long long)h4[1] << 32);
-        hi = (unsigned long long)h4[2] | ((unsigned long long)h4[3] << 32);
-    } else {
-        for (int i = 0; i < 8; ++i) { lo |= (unsigned long long)src[i] << (8 * i); hi |= (unsigned long long)src[8 + i] << (8 * i); }
-    }
-    const long long keep = (hi == 0 && lo < (unsigned long long)body) ? (long long)lo : body; // Vec::truncate
+    unsigned long long lo = 0, hi = 0;
+    OFDM_HEADER_READ(src, lo, hi)
+    const long long keep = OFDM_HEADER_KEEP(long long, lo, hi, body);
     uint8_t *dst = out + f * out_stride;
     if (!ecc) {
         if ((((uintptr_t)src | (uintptr_t)dst) & 3) == 0) { // dword copy (the library's own buffers are 4-byte aligned)
@@ -348,15 +342,9 @@ __global__ __launch_bounds__(256) void k_rx_finish_soft(const uint8_t *raw, long
     if (status[f] != 0) { if (lane == 0) out_len[f] = 0; continue; }
     const uint8_t *src = raw + f * raw_stride;
     const long long body = (long long)nsym[f] * bytes_per_symbol - 16;
-    unsigned long long lo = 0, hi = 0; // bincode fixint little-endian u128 (src/packets/mod.rs:20-32)
-    if (((uintptr_t)src & 3) == 0) {
-        const uint32_t *h4 = reinterpret_cast<const uint32_t *>(src);
-        lo = (unsigned long long)h4[0] | ((unsigned long long)h4[1] << 32);
-        hi = (unsigned long long)h4[2] | ((unsigned long long)h4[3] << 32);
-    } else {
-        for (int i = 0; i < 8; ++i) { lo |= (unsigned long long)src[i] << (8 * i); hi |= (unsigned long long)src[8 + i] << (8 * i); }
-    }
-    const long long keep = (hi == 0 && lo < (unsigned long long)body) ? (long long)lo : body; // Vec::truncate
+    unsigned long long lo = 0, hi = 0;
+    OFDM_HEADER_READ(src, lo, hi)
+    const long long keep = OFDM_HEADER_KEEP(long long, lo, hi, body);
     const long long blocks = keep / 7;
     const int8_t *l = llr + f * llr_stride + 128;
     uint8_t *dst = out + f * out_stride;

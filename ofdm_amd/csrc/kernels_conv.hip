@@ -229,10 +229,10 @@ __global__ __launch_bounds__(256) void k_viterbi_k7(ViterbiParams p) {
         if (p.status[f] != 0) { if (lane == 0) p.out_len[f] = 0; continue; }
         const uint8_t *src = p.raw + f * p.raw_stride;
         const long long body = (long long)p.nsym[f] * p.bytes_per_symbol - 16;
-        unsigned long long lo = 0, hi = 0; // bincode fixint little-endian u128 (src/packets/mod.rs:20-32)
-        for (int i = 0; i < 8; ++i) { lo |= (unsigned long long)src[i] << (8 * i); hi |= (unsigned long long)src[8 + i] << (8 * i); }
-        long long keep = (hi == 0 && lo < (unsigned long long)body) ? (long long)lo : body; // Vec::truncate
-        const bool whole = hi == 0 && lo <= (unsigned long long)body;
+        unsigned long long lo = 0, hi = 0;
+        OFDM_HEADER_READ_BYTES(src, lo, hi) // (byte by byte whatever the row's alignment)
+        long long keep = OFDM_HEADER_KEEP(long long, lo, hi, body);
+        const bool whole = OFDM_HEADER_WHOLE(lo, hi, body);
         keep = __builtin_amdgcn_readfirstlane((int)keep);
         const int n_out = keep / 2 >= 1 ? (int)(keep / 2) - 1 : 0;
         viterbi_k7_frame(l + 128, (int)(4 * keep), __builtin_amdgcn_readfirstlane((int)whole) != 0, dst, n_out, surv, lane);

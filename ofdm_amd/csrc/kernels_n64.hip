@@ -445,7 +445,7 @@ __global__ __launch_bounds__(256, (MODE == 0 && GUARD) ? 4 : 3) void k_rxframe64
                     const unsigned long long lo = (unsigned long long)img[0] | ((unsigned long long)img[1] << 32);
                     const unsigned long long hi = (unsigned long long)img[2] | ((unsigned long long)img[3] << 32);
                     const int body = ns * SYM_BYTES - 16;
-                    keep = (hi == 0 && lo < (unsigned long long)body) ? (int)lo : body;
+                    keep = OFDM_HEADER_KEEP(int, lo, hi, body);
                     if (lane == 0) p.final_len[f] = keep;
                 }
                 unsigned char *fo = p.final_out + f * p.final_stride;

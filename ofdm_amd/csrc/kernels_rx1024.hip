@@ -307,7 +307,7 @@ __global__ __launch_bounds__(128, 3) void k_rxframe1024(RxFrame1024Params p) {
             const unsigned long long lo = (unsigned long long)raw[0] | ((unsigned long long)raw[1] << 32);
             const unsigned long long hi = (unsigned long long)raw[2] | ((unsigned long long)raw[3] << 32);
             const int body = ns * nbytes - 16;
-            const int keep = (hi == 0 && lo < (unsigned long long)body) ? (int)lo : body;
+            const int keep = OFDM_HEADER_KEEP(int, lo, hi, body);
             const unsigned char *srcb = reinterpret_cast<const unsigned char *>(raw) + 16;
             unsigned char *dstb = p.final_out + f * p.final_stride;
             if (!p.ecc) {

@@ -168,7 +168,7 @@ static int chest_tables(ofdm_ctx *c) {
 }
 
 // rows of N bins `in` -> `out` (in == out allowed), per frame chunk: weight -> inverse FFT -> k_chest_solve -> forward FFT.  The
-// one workspace (slot 13: the solve's zeroed rows) holds a chunk, at most kChestChunkBytes whatever n_frames is.
+// one workspace (the solve's zeroed rows) holds a chunk, at most kChestChunkBytes whatever n_frames is.
 static const int64_t kChestChunkBytes = 64ll << 20;
 static int chest_smooth_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, float2 *out, bool trace) {
     int rc = chest_tables(c);
@@ -177,7 +177,7 @@ static int chest_smooth_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, flo
     int64_t chunk = std::max<int64_t>(kChestChunkBytes / ((int64_t)sizeof(float2) * N), 64);
     if (chunk > n_frames) chunk = n_frames;
     void *w_taps;
-    if ((rc = ws_get(c, 13, sizeof(float2) * (size_t)N * (size_t)chunk, &w_taps))) return rc;
+    if ((rc = ws_get(c, kWsChestTaps, sizeof(float2) * (size_t)N * (size_t)chunk, &w_taps))) return rc;
     for (int64_t f0 = 0; f0 < n_frames; f0 += chunk) {
         const int64_t nf = n_frames - f0 < chunk ? n_frames - f0 : chunk;
         const bool tr = trace && f0 == 0;
@@ -385,7 +385,8 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
     default: return OFDM_ERR_INVALID;
     }
     if (p->guard_bands != 0 && p->guard_bands != 1) return OFDM_ERR_INVALID;
-    if (!base_mode(base_ecc(p->ecc))) return OFDM_ERR_INVALID; // 3 and 4 are not modes, nor are 21 .. 29 or 36; 64 + a base mode is
+    ModePlan mode;
+    if (!mode_plan(p->ecc, &mode)) return OFDM_ERR_INVALID;
     if (p->sync_window_reps < 1 || p->sync_window_reps > 3) return OFDM_ERR_INVALID;
     if (p->sync_backoff < 0 || p->sync_backoff > p->cp_len) return OFDM_ERR_INVALID;
     if (p->cfo_mode < OFDM_CFO_OFF || p->cfo_mode > OFDM_CFO_ABS) return OFDM_ERR_INVALID;
@@ -406,6 +407,7 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
     ofdm_ctx *c = new (std::nothrow) ofdm_ctx();
     if (!c) return OFDM_ERR_NOMEM;
     c->prm = *p;
+    c->mode = mode;
     c->device = device;
     c->trace.reset();
     c->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
@@ -577,19 +579,9 @@ int ofdm_memset(ofdm_ctx *c, void *dev, int value, size_t bytes) {
 int ofdm_symbol_len(const ofdm_ctx *c) { return c ? c->S() : OFDM_ERR_INVALID; }
 int ofdm_data_carriers(const ofdm_ctx *c) { return c ? c->carriers() : OFDM_ERR_INVALID; }
 int ofdm_bytes_per_symbol(const ofdm_ctx *c) { return c ? c->bytes_per_symbol() : OFDM_ERR_INVALID; }
-// coded bytes of n payload bytes in mode `ecc` (no RS mode)
-static int64_t inner_coded_len(int ecc, int64_t n) {
-    if (ecc == OFDM_ECC_CONV_K7) return 2 * (n + 1); // rate 1/2 over the payload and one tail byte
-    if (framed_rate(ecc) >= 0) return kConvLengthBlock + conv_body_len(n, framed_rate(ecc));
-    if (ecc == OFDM_ECC_LDPC648) return ofdm_ldpc648_coded_len(n);
-    return ecc != OFDM_ECC_NONE ? ((n + 3) / 4) * 7 : n; // the soft decoder reads the same code
-}
 int64_t ofdm_coded_len(const ofdm_ctx *c, int64_t payload_bytes) {
     if (!c || payload_bytes < 0) return OFDM_ERR_INVALID;
-    const int ecc = base_ecc(c->prm.ecc);
-    if (fcs_outer(c->prm.ecc)) payload_bytes += OFDM_FCS_OVERHEAD; // OFDM_ECC_FCS + mode: the mode codes the envelope
-    // OFDM_ECC_RS255*: the inner mode codes the RS blocks
-    return inner_coded_len(inner_ecc(ecc), rs_outer(ecc) ? ofdm_rs255_encoded_len(payload_bytes) : payload_bytes);
+    return coded_len(c->mode, payload_bytes);
 }
 int64_t ofdm_data_symbols(const ofdm_ctx *c, int64_t payload_bytes) {
     if (!c || payload_bytes < 0) return OFDM_ERR_INVALID;
@@ -683,7 +675,7 @@ int ofdm_normalize_batch(ofdm_ctx *c, ofdm_fc32 *x, int64_t n_frames, int64_t fr
     c->trace.reset();
     if (!n_frames) return OFDM_OK;
     void *mx;
-    int rc = ws_get(c, 0, sizeof(unsigned) * (size_t)n_frames, &mx);
+    int rc = ws_get(c, kWsFrameMax, sizeof(unsigned) * (size_t)n_frames, &mx);
     if (rc) return rc;
     HIP_TRY(c, hipMemsetAsync(mx, 0, sizeof(unsigned) * (size_t)n_frames, c->stream));
     HIP_TRY(c, run_frame_max(reinterpret_cast<float2 *>(x), n_frames, frame_stride, frame_len, (unsigned *)mx, c->stream));
@@ -713,6 +705,14 @@ int ofdm_hamming74_decode_soft(ofdm_ctx *c, const int8_t *llr, int64_t n_bits, u
     return OFDM_OK;
 }
 
+// The survivor slabs of a Viterbi launch over n_frames frames of at most max_steps steps: the grid, and p's slab size and workspace
+static int viterbi_survivors(ofdm_ctx *c, int64_t n_frames, int64_t max_steps, ViterbiParams &p, long long *blocks) {
+    viterbi_k7_plan(n_frames, max_steps, c->num_cu, &c->tune, blocks, &p.slab_words);
+    void *w_surv = nullptr;
+    const int rc = ws_get(c, kWsSurvivors, (size_t)(*blocks * 4 * p.slab_words) * sizeof(unsigned long long), &w_surv);
+    p.surv = (unsigned long long *)w_surv;
+    return rc;
+}
 // int32 path metrics, not renormalised: 2^20 steps of at most 256 each stay clear of the floor of the excluded states (-2^30)
 static const int64_t kViterbiMaxSteps = 1ll << 20;
 int ofdm_conv_k7_encode(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_t in_stride, int64_t n_bytes, uint8_t *out,
@@ -736,12 +736,10 @@ int ofdm_conv_k7_decode_soft(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, i
     c->trace.reset();
     ViterbiParams p;
     long long blocks;
-    viterbi_k7_plan(n_frames, n_steps, c->num_cu, &c->tune, &blocks, &p.slab_words);
-    void *w_surv;
-    int rc = ws_get(c, 10, (size_t)(blocks * 4 * p.slab_words) * sizeof(unsigned long long), &w_surv);
+    int rc = viterbi_survivors(c, n_frames, n_steps, p, &blocks);
     if (rc) return rc;
     p.llr = llr; p.llr_stride = llr_stride; p.n_frames = n_frames; p.out = out; p.out_stride = out_stride;
-    p.surv = (unsigned long long *)w_surv; p.n_steps = (int)n_steps; p.terminated = terminated != 0;
+    p.n_steps = (int)n_steps; p.terminated = terminated != 0;
     c->trace.add("k_viterbi_k7");
     HIP_TRY(c, run_viterbi_k7(p, blocks, c->stream));
     return OFDM_OK;
@@ -774,16 +772,59 @@ int ofdm_conv_k7_decode_punctured(ofdm_ctx *c, const int8_t *llr, int64_t n_fram
     c->trace.reset();
     ViterbiFParams p;
     long long blocks;
-    viterbi_k7_plan(n_frames, n_steps, c->num_cu, &c->tune, &blocks, &p.slab_words);
-    void *w_surv;
-    int rc = ws_get(c, 10, (size_t)(blocks * 4 * p.slab_words) * sizeof(unsigned long long), &w_surv);
+    int rc = viterbi_survivors(c, n_frames, n_steps, p, &blocks);
     if (rc) return rc;
     p.llr = llr; p.llr_stride = llr_stride; p.n_frames = n_frames; p.out = out; p.out_stride = out_stride;
-    p.surv = (unsigned long long *)w_surv; p.n_steps = (int)n_steps; p.terminated = terminated != 0; p.rate = rate;
+    p.n_steps = (int)n_steps; p.terminated = terminated != 0; p.rate = rate;
     c->trace.add("k_viterbi_k7f");
     HIP_TRY(c, run_viterbi_k7f(p, blocks, c->stream));
     return OFDM_OK;
 }
+
+// ---- the outer layers of a mode (ModePlan::outer; the length maps are outer_coded_bytes / outer_row_limit in ofdm_ctx.hpp).  One kernel
+// each way: on transmit rows + optional lengths -> longer rows + optional lengths, on receive rows -> the rows of the layer outside.
+// The stage entry points below and the chains of the frame modes launch them through the same four functions.
+namespace {
+struct LayerCall {
+    const uint8_t *in; int64_t n_frames, in_stride, n_in; const int32_t *in_len;  // rows of n_in bytes (row f: in_len[f] when given)
+    uint8_t *out; int64_t out_stride; int32_t *out_len;
+    int32_t *aux, *status_rw; // receive: ok / corrected per row (stage mode), the frames' status (chain mode)
+};
+hipError_t fcs_wrap(ofdm_ctx *c, const LayerCall &r) {
+    FcsWrapParams p;
+    p.in = r.in; p.n_frames = r.n_frames; p.in_stride = r.in_stride; p.n_bytes = r.n_in; p.in_len = r.in_len; p.out = r.out; p.out_stride = r.out_stride;
+    p.out_len = r.out_len;
+    return run_fcs_wrap(p, c->num_cu, &c->tune, c->stream);
+}
+hipError_t fcs_check(ofdm_ctx *c, const LayerCall &r) {
+    FcsCheckParams p;
+    p.row = r.in; p.n_frames = r.n_frames; p.row_stride = r.in_stride; p.n_row = r.n_in; p.row_len = r.in_len; p.out = r.out; p.out_stride = r.out_stride;
+    p.out_len = r.out_len; p.ok = r.aux; p.status_rw = r.status_rw;
+    return run_fcs_check(p, c->num_cu, &c->tune, c->stream);
+}
+hipError_t rs_encode(ofdm_ctx *c, const LayerCall &r) {
+    Rs255EncodeParams p;
+    p.in = r.in; p.n_frames = r.n_frames; p.in_stride = r.in_stride; p.n_bytes = r.n_in; p.in_len = r.in_len; p.out = r.out; p.out_stride = r.out_stride;
+    p.out_len = r.out_len;
+    return run_rs255_encode(p, c->num_cu, &c->tune, c->stream);
+}
+hipError_t rs_decode(ofdm_ctx *c, const LayerCall &r) {
+    Rs255DecodeParams p;
+    p.code = r.in; p.n_frames = r.n_frames; p.code_stride = r.in_stride; p.n_code = r.n_in; p.code_len = r.in_len; p.out = r.out; p.out_stride = r.out_stride;
+    p.out_len = r.out_len; p.corrected = r.aux; p.status_rw = r.status_rw;
+    return run_rs255_decode(p, c->num_cu, &c->tune, c->stream);
+}
+struct OuterStage {
+    WsRole tx_rows, tx_len, rx_rows;
+    const char *tx_name, *rx_name;
+    hipError_t (*encode)(ofdm_ctx *, const LayerCall &), (*decode)(ofdm_ctx *, const LayerCall &);
+    int64_t rx_max_row; // the longest row the receive kernel takes
+};
+const OuterStage kOuter[] = { // indexed by OuterLayer
+    {kWsTxFcsRows, kWsTxFcsLen, kWsRxFcsRows, "k_fcs_wrap", "k_fcs_check", fcs_wrap, fcs_check, 0x7fffffffll}, // its length word is 32 bits
+    {kWsTxRsRows, kWsTxRsLen, kWsRxRsRows, "k_rs255_encode", "k_rs255_decode", rs_encode, rs_decode, INT64_MAX},
+};
+} // namespace
 
 // outer Reed-Solomon(255,223) on device rows (kernels_rs.hip)
 int ofdm_rs255_encode_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_t in_stride, const int32_t *in_len, int64_t n_bytes,
@@ -793,10 +834,8 @@ int ofdm_rs255_encode_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, in
     if (!n_frames) return OFDM_OK;
     DeviceGuard dev_guard(c->device);
     c->trace.reset();
-    Rs255EncodeParams p;
-    p.in = in; p.n_frames = n_frames; p.in_stride = in_stride; p.n_bytes = n_bytes; p.in_len = in_len; p.out = out; p.out_stride = out_stride;
     c->trace.add("k_rs255_encode");
-    HIP_TRY(c, run_rs255_encode(p, c->num_cu, &c->tune, c->stream));
+    HIP_TRY(c, rs_encode(c, LayerCall{in, n_frames, in_stride, n_bytes, in_len, out, out_stride, nullptr, nullptr, nullptr}));
     return OFDM_OK;
 }
 int ofdm_rs255_decode_batch(ofdm_ctx *c, const uint8_t *code, int64_t n_frames, int64_t code_stride, const int32_t *code_len, int64_t n_code,
@@ -806,11 +845,8 @@ int ofdm_rs255_decode_batch(ofdm_ctx *c, const uint8_t *code, int64_t n_frames, 
     if (!n_frames) return OFDM_OK;
     DeviceGuard dev_guard(c->device);
     c->trace.reset();
-    Rs255DecodeParams p;
-    p.code = code; p.n_frames = n_frames; p.code_stride = code_stride; p.n_code = n_code; p.code_len = code_len; p.out = out;
-    p.out_stride = out_stride; p.out_len = out_len; p.corrected = corrected;
     c->trace.add("k_rs255_decode");
-    HIP_TRY(c, run_rs255_decode(p, c->num_cu, &c->tune, c->stream));
+    HIP_TRY(c, rs_decode(c, LayerCall{code, n_frames, code_stride, n_code, code_len, out, out_stride, out_len, corrected, nullptr}));
     return OFDM_OK;
 }
 
@@ -853,11 +889,8 @@ int ofdm_fcs_wrap_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_
     if (!n_frames) return OFDM_OK;
     DeviceGuard dev_guard(c->device);
     c->trace.reset();
-    FcsWrapParams p;
-    p.in = in; p.n_frames = n_frames; p.in_stride = in_stride; p.n_bytes = n_bytes; p.in_len = in_len; p.out = out; p.out_stride = out_stride;
-    p.out_len = out_len;
     c->trace.add("k_fcs_wrap");
-    HIP_TRY(c, run_fcs_wrap(p, c->num_cu, &c->tune, c->stream));
+    HIP_TRY(c, fcs_wrap(c, LayerCall{in, n_frames, in_stride, n_bytes, in_len, out, out_stride, out_len, nullptr, nullptr}));
     return OFDM_OK;
 }
 int ofdm_fcs_check_batch(ofdm_ctx *c, const uint8_t *row, int64_t n_frames, int64_t row_stride, const int32_t *row_len, int64_t n_row,
@@ -868,11 +901,8 @@ int ofdm_fcs_check_batch(ofdm_ctx *c, const uint8_t *row, int64_t n_frames, int6
     if (!n_frames) return OFDM_OK;
     DeviceGuard dev_guard(c->device);
     c->trace.reset();
-    FcsCheckParams p;
-    p.row = row; p.n_frames = n_frames; p.row_stride = row_stride; p.n_row = n_row; p.row_len = row_len; p.out = out; p.out_stride = out_stride;
-    p.out_len = out_len; p.ok = ok;
     c->trace.add("k_fcs_check");
-    HIP_TRY(c, run_fcs_check(p, c->num_cu, &c->tune, c->stream));
+    HIP_TRY(c, fcs_check(c, LayerCall{row, n_frames, row_stride, n_row, row_len, out, out_stride, out_len, ok, nullptr}));
     return OFDM_OK;
 }
 
@@ -909,7 +939,7 @@ static int sc_run_impl(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t 
     // of unaligned batches): one-tile frames through the coarse-then-fine f32 filter + exact f64 decisions (k_sc_cf)
     if (sc_fast_ok(p) || (!c->tune.no_sc80 && sc80_wanted(p))) {
         void *wsp;
-        int rc = ws_get(c, 6, sc_fast_workspace_bytes(n_frames, p.n_lags), &wsp);
+        int rc = ws_get(c, kWsSearch, sc_fast_workspace_bytes(n_frames, p.n_lags), &wsp);
         if (rc) return rc;
         HIP_TRY(c, run_sc_fast(p, wsp, c->num_cu, c->stream));
         return OFDM_OK;
@@ -925,7 +955,7 @@ static int sc_run_impl(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t 
     const bool one_small_tile = n_lags <= sc_tile_lags() && sc_lds_bytes(p) <= 64 * 1024; // bounded search, window in LDS: k_sc_tile reads less
     if (sc_big_ok(p) && !one_small_tile && !c->tune.no_sc_big) {
         void *wsp;
-        int rc = ws_get(c, 6, sc_big_workspace_bytes(p), &wsp);
+        int rc = ws_get(c, kWsSearch, sc_big_workspace_bytes(p), &wsp);
         if (rc) return rc;
         HIP_TRY(c, run_sc_big(p, wsp, c->num_cu, c->stream));
         return OFDM_OK;
@@ -940,9 +970,9 @@ static int sc_run_impl(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t 
     }
     // long captures: first threshold crossing per tile -> per frame -> peak search from there (one tile)
     void *cross, *d1;
-    int rc = ws_get(c, 6, sizeof(long long) * (size_t)(n_frames * tiles), &cross);
+    int rc = ws_get(c, kWsSearch, sizeof(long long) * (size_t)(n_frames * tiles), &cross);
     if (rc) return rc;
-    rc = ws_get(c, 7, sizeof(int32_t) * (size_t)n_frames, &d1);
+    rc = ws_get(c, kWsSearchD1, sizeof(int32_t) * (size_t)n_frames, &d1);
     if (rc) return rc;
     p.tiles_per_frame = (int)tiles; p.mode = 1; p.cross = (long long *)cross;
     HIP_TRY(c, run_sc(p, c->stream));
@@ -989,7 +1019,7 @@ int ofdm_xcorr_batch(ofdm_ctx *c, const ofdm_fc32 *a, int64_t n_frames, int64_t 
     DeviceGuard dev_guard(c->device);
     c->trace.reset();
     void *w;
-    int rc = ws_get(c, 6, xcorr_workspace_bytes(n_frames, a_len, nb), &w);
+    int rc = ws_get(c, kWsSearch, xcorr_workspace_bytes(n_frames, a_len, nb), &w);
     if (rc) return rc;
     HIP_TRY(c, run_xcorr(reinterpret_cast<const float2 *>(a), n_frames, a_stride, a_len, reinterpret_cast<const float2 *>(b), nb, w,
                          idx_max, peak, reinterpret_cast<float2 *>(out), out_stride, c->num_cu, c->stream));
@@ -1114,8 +1144,8 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
     if (!c || n_frames < 0 || payload_bytes < 0 || payload_stride < 0) return OFDM_ERR_INVALID;
     if (n_frames && (!out || (payload_bytes && !payload))) return OFDM_ERR_INVALID;
     if (n_frames > 1 && payload_stride < payload_bytes) return OFDM_ERR_INVALID; // rows are prefetched for payload_bytes (include/ofdm_hip.h)
-    const bool fcs = fcs_outer(c->prm.ecc);
-    if (fcs && payload_bytes > 0x7fffffff - OFDM_FCS_OVERHEAD) return OFDM_ERR_UNSUPPORTED;
+    const ModePlan &m = c->mode;
+    if (m.has(kLayerFcs) && payload_bytes > 0x7fffffff - OFDM_FCS_OVERHEAD) return OFDM_ERR_UNSUPPORTED;
     const int64_t frame = ofdm_frame_samples(c, payload_bytes);
     if (out_stride < frame) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
@@ -1124,51 +1154,33 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
     const int S = c->S();
     const uint8_t *src = payload; int64_t src_stride = payload_stride; const int32_t *src_len = payload_len;
     int32_t src_bytes = payload_bytes;
-    const int base = base_ecc(c->prm.ecc), ecc = inner_ecc(base);
-    if (fcs) { // OFDM_ECC_FCS + mode: the base mode's frame of the envelopes
-        const int64_t env = (int64_t)payload_bytes + OFDM_FCS_OVERHEAD;
-        void *fw, *fl;
-        int rc = ws_get(c, 14, (size_t)env * (size_t)n_frames, &fw);
-        if (rc) return rc;
-        if ((rc = ws_get(c, 15, sizeof(int32_t) * (size_t)n_frames, &fl))) return rc;
-        FcsWrapParams fp;
-        fp.in = payload; fp.n_frames = n_frames; fp.in_stride = payload_stride; fp.n_bytes = payload_bytes; fp.in_len = payload_len;
-        fp.out = (uint8_t *)fw; fp.out_stride = env; fp.out_len = payload_len ? (int32_t *)fl : nullptr;
-        c->trace.add("k_fcs_wrap");
-        HIP_TRY(c, run_fcs_wrap(fp, c->num_cu, &c->tune, c->stream));
-        src = (const uint8_t *)fw; src_stride = env; src_len = payload_len ? (const int32_t *)fl : nullptr; src_bytes = (int32_t)env;
+    int rc;
+    for (int i = 0; i < m.n_outer; i++) { // outside-in: the next layer's frame of this layer's rows
+        const OuterStage &s = kOuter[m.outer[i]];
+        const int64_t coded = outer_coded_bytes(m.outer[i], src_bytes);
+        if (coded > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED;
+        void *rows, *len;
+        if ((rc = ws_get(c, s.tx_rows, (size_t)coded * (size_t)n_frames, &rows))) return rc;
+        if ((rc = ws_get(c, s.tx_len, sizeof(int32_t) * (size_t)n_frames, &len))) return rc;
+        if (!src_len) len = nullptr; // only ragged rows carry lengths on
+        c->trace.add(s.tx_name);
+        HIP_TRY(c, s.encode(c, LayerCall{src, n_frames, src_stride, src_bytes, src_len, (uint8_t *)rows, coded, (int32_t *)len, nullptr, nullptr}));
+        src = (const uint8_t *)rows; src_stride = coded; src_len = (const int32_t *)len; src_bytes = (int32_t)coded;
     }
-    if (rs_outer(base)) { // OFDM_ECC_RS255*: the inner mode's frame of the RS-coded rows
-        const int64_t rs_len = ofdm_rs255_encoded_len(src_bytes);
-        if (rs_len > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED;
-        void *rw, *rl;
-        int rc = ws_get(c, 11, (size_t)rs_len * (size_t)n_frames, &rw);
-        if (rc) return rc;
-        if ((rc = ws_get(c, 12, sizeof(int32_t) * (size_t)n_frames, &rl))) return rc;
-        Rs255EncodeParams rp;
-        rp.in = src; rp.n_frames = n_frames; rp.in_stride = src_stride; rp.n_bytes = src_bytes; rp.in_len = src_len;
-        rp.out = (uint8_t *)rw; rp.out_stride = rs_len; rp.out_len = src_len ? (int32_t *)rl : nullptr;
-        c->trace.add("k_rs255_encode");
-        HIP_TRY(c, run_rs255_encode(rp, c->num_cu, &c->tune, c->stream));
-        src = (const uint8_t *)rw; src_stride = rs_len; src_len = src_len ? (const int32_t *)rl : nullptr; src_bytes = (int32_t)rs_len;
-    }
-    if (ecc != OFDM_ECC_NONE) { // HAMMING74 and HAMMING74_SOFT transmit the same frames, CONV_K7 its own code
-        const int64_t coded = inner_coded_len(ecc, src_bytes);
-        const int f_rate = framed_rate(ecc);
-        if ((ecc == OFDM_ECC_CONV_K7 || f_rate >= 0 || ecc == OFDM_ECC_LDPC648) && coded > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED; // (payload_bytes = INT32_MAX)
+    if (m.inner != OFDM_ECC_NONE) { // HAMMING74 and HAMMING74_SOFT transmit the same frames
+        const int64_t coded = inner_coded_bytes(m, src_bytes);
+        if ((m.conv() || m.ldpc()) && coded > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED; // (payload_bytes = INT32_MAX)
         void *cw, *cl;
-        int rc = ws_get(c, 1, (size_t)(coded ? coded : 1) * (size_t)n_frames, &cw);
-        if (rc) return rc;
-        rc = ws_get(c, 2, sizeof(int32_t) * (size_t)n_frames, &cl);
-        if (rc) return rc;
-        if (ecc == OFDM_ECC_CONV_K7) {
+        if ((rc = ws_get(c, kWsTxCoded, (size_t)(coded ? coded : 1) * (size_t)n_frames, &cw))) return rc;
+        if ((rc = ws_get(c, kWsTxCodedLen, sizeof(int32_t) * (size_t)n_frames, &cl))) return rc;
+        if (m.inner == OFDM_ECC_CONV_K7) {
             c->trace.add("k_conv_encode");
             HIP_TRY(c, run_conv_encode(src, n_frames, src_stride, src_len, src_bytes, (uint8_t *)cw, coded, (int32_t *)cl, c->stream));
-        } else if (f_rate >= 0) {
+        } else if (m.rate() >= 0) {
             c->trace.add("k_conv_encode_p");
-            HIP_TRY(c, run_conv_encode_p(src, n_frames, src_stride, src_len, src_bytes, f_rate, kConvLengthBlock, (uint8_t *)cw, coded,
+            HIP_TRY(c, run_conv_encode_p(src, n_frames, src_stride, src_len, src_bytes, m.rate(), kConvLengthBlock, (uint8_t *)cw, coded,
                                          (int32_t *)cl, c->stream));
-        } else if (ecc == OFDM_ECC_LDPC648) { // the code of [u32 LE p][u32 LE ~p] ++ payload, row by row
+        } else if (m.ldpc()) { // the code of [u32 LE p][u32 LE ~p] ++ payload, row by row
             LdpcEncodeParams lp;
             lp.in = src; lp.n_frames = n_frames; lp.in_stride = src_stride; lp.n_bytes = src_bytes; lp.in_len = src_len; lp.framed = 1;
             lp.n_cw = coded / kLdpcCodeBytes; lp.out = (uint8_t *)cw; lp.out_stride = coded; lp.out_len = (int32_t *)cl;
@@ -1191,8 +1203,7 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
     // 64 x 64 two-stage kernel, frames built twice: one pass over HBM (kernels_n4096.hip)
     if (c->prm.n_fft == 4096) FAST_PATH(c, c->tune.no_demod4096, run_txframe4096(p, c->d_header, c->header_max, c->stream, c->num_cu));
     void *mx;
-    int rc = ws_get(c, 0, sizeof(unsigned) * (size_t)n_frames, &mx);
-    if (rc) return rc;
+    if ((rc = ws_get(c, kWsFrameMax, sizeof(unsigned) * (size_t)n_frames, &mx))) return rc;
     HIP_TRY(c, hipMemsetAsync(mx, 0, sizeof(unsigned) * (size_t)n_frames, c->stream));
     p.frame_max = (unsigned *)mx;
     HIP_TRY(c, run_tx_symbols(c->prm.n_fft, p, c->stream, c->num_cu));
@@ -1202,100 +1213,85 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
     return OFDM_OK;
 }
 
-namespace { struct KnownSync { int32_t d_hat; double f_delta; float metric; }; }
+namespace {
+struct KnownSync { int32_t d_hat; double f_delta; float metric; };
+// The arguments of a decode call: ofdm_rx_decode_batch's own, or one capture with its timing (ofdm_abi_rx_decode_known)
+struct DecodeCall {
+    const float2 *in; int64_t n_frames, frame_stride, frame_len, n_lags; int32_t max_symbols;
+    uint8_t *out; int64_t out_stride;                          // rows of out_stride bytes
+    int32_t *out_len, *status, *offset; double *f_delta; float *metric; // per frame (offset, f_delta, metric: optional)
+    const KnownSync *known;
+};
+// What steps 1 - 4 of the chain leave to the soft finishing kernels (raw: the hard bytes, for the length header)
+struct SoftInput { int32_t *offs; double *fd; const int32_t *nsym; const float2 *hk; uint8_t *raw; int64_t raw_stride, body_steps; };
+} // namespace
 // OFDM_ECC_HAMMING74_SOFT decode: the LLR workspace (one frame chunk of LLR rows) never exceeds this
 static const int64_t kSoftLlrBytes = 256ll << 20;
-static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
-                          int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
-                          int32_t *status, int32_t *offset, double *f_delta, float *metric, const KnownSync *known);
 
-int ofdm_rx_decode_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
-                         int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
-                         int32_t *status, int32_t *offset, double *f_delta, float *metric) {
-    return rx_decode_impl(c, in, n_frames, frame_stride, frame_len, n_lags, max_symbols, out, out_stride, out_len, status, offset, f_delta,
-                          metric, nullptr);
-}
-int ofdm_abi_rx_decode_known(ofdm_ctx *c, const ofdm_fc32 *in, int64_t frame_len, int32_t d_hat, double f_delta, float metric,
-                             int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len, int32_t *status, int32_t *offset,
-                             double *f_delta_out, float *metric_out) {
-    const KnownSync k{d_hat, f_delta, metric};
-    return rx_decode_impl(c, in, 1, frame_len, frame_len, 0, max_symbols, out, out_stride, out_len, status, offset, f_delta_out, metric_out, &k);
-}
-
-// The decode chain of mode `ecc` (the context's own mode, or the inner mode of an RS mode) into rows out / out_stride
-static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
-                           int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
-                           int32_t *status, int32_t *offset, double *f_delta, float *metric, const KnownSync *known);
-
-// The decode chain of base mode `ecc` (no FCS mode) into rows out / out_stride
-static int rx_decode_base(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
-                          int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
-                          int32_t *status, int32_t *offset, double *f_delta, float *metric, const KnownSync *known) {
-    if (!rs_outer(ecc))
-        return rx_decode_inner(c, ecc, in, n_frames, frame_stride, frame_len, n_lags, max_symbols, out, out_stride, out_len, status,
-                               offset, f_delta, metric, known);
-    // OFDM_ECC_RS255*: the inner mode's chain into a workspace (dword rows: the fused frame kernels write their payload there
-    // directly), then k_rs255_decode over what every frame delivered; out_len serves both as the inner length and the final one
-    if (n_frames < 0 || frame_len <= 0 || max_symbols <= 0) return OFDM_ERR_INVALID;
-    if (n_frames && (!in || !out || !out_len || !status)) return OFDM_ERR_INVALID;
-    const int64_t raw_bytes = (int64_t)max_symbols * c->bytes_per_symbol();
-    const int64_t inner_max = inner_row_bytes(inner_ecc(ecc), raw_bytes > 16 ? raw_bytes - 16 : 0);
-    if (out_stride < ofdm_rs255_decoded_len(inner_max)) return OFDM_ERR_INVALID;
-    if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    const int64_t row = (std::max<int64_t>(inner_max, 4) + 3) & ~(int64_t)3;
-    void *w_rows;
-    int rc = ws_get(c, 11, (size_t)row * (size_t)n_frames, &w_rows);
-    if (rc) return rc;
-    rc = rx_decode_inner(c, inner_ecc(ecc), in, n_frames, frame_stride, frame_len, n_lags, max_symbols, (uint8_t *)w_rows, row, out_len,
-                         status, offset, f_delta, metric, known);
-    if (rc) return rc;
-    Rs255DecodeParams rp;
-    rp.code = (const uint8_t *)w_rows; rp.n_frames = n_frames; rp.code_stride = row; rp.n_code = inner_max; rp.code_len = out_len;
-    rp.out = out; rp.out_stride = out_stride; rp.out_len = out_len; rp.status_rw = status;
-    c->trace.add("k_rs255_decode");
-    HIP_TRY(c, run_rs255_decode(rp, c->num_cu, &c->tune, c->stream));
+// 4s + 5s of the chain, per frame chunk: hard bytes (for the header) and LLRs in one k_sym<llr>, then ONE finishing kernel -- the header
+// and the ML decode of the body (k_rx_finish_soft); OFDM_ECC_CONV_K7: k_viterbi_k7, which also needs a survivor slab per resident
+// wavefront; OFDM_ECC_CONV_K7F_*: k_viterbi_k7f, which reads the length from its own coded block and may set status;
+// OFDM_ECC_LDPC648: k_ldpc_decode, which reads the length from its first code word and may set status.
+// The LLR workspace holds one chunk: at most kSoftLlrBytes whatever n_frames is.
+static int rx_finish_soft(ofdm_ctx *c, const DecodeCall &d, const SoftInput &s) {
+    const ModePlan &m = c->mode;
+    const int N = c->prm.n_fft, bps_bytes = c->bytes_per_symbol();
+    const int64_t llr_row = (int64_t)d.max_symbols * c->carriers() * c->prm.modulation;
+    const int64_t llr_stride = (llr_row + 15) & ~(int64_t)15;
+    int64_t chunk = c->tune.soft_chunk_frames > 0 ? c->tune.soft_chunk_frames : kSoftLlrBytes / llr_stride;
+    if (chunk < 1) chunk = 1;
+    if (chunk > d.n_frames) chunk = d.n_frames;
+    void *w_llr;
+    int rc;
+    if ((rc = ws_get(c, kWsLlr, (size_t)(llr_stride * chunk), &w_llr))) return rc;
+    const int8_t *llr = (const int8_t *)w_llr;
+    ViterbiParams vp;
+    long long v_blocks = 0;
+    if (m.conv()) {
+        if ((rc = viterbi_survivors(c, chunk, s.body_steps, vp, &v_blocks))) return rc;
+        vp.llr = llr; vp.llr_stride = llr_stride; vp.out_stride = d.out_stride;
+        vp.raw_stride = s.raw_stride; vp.bytes_per_symbol = bps_bytes;
+    }
+    const char *name = m.ldpc() ? "k_ldpc_decode" : !m.conv() ? "k_rx_finish_soft" : m.rate() < 0 ? "k_viterbi_k7" : "k_viterbi_k7f";
+    for (int64_t f0 = 0; f0 < d.n_frames; f0 += chunk) {
+        const int64_t nf = d.n_frames - f0 < chunk ? d.n_frames - f0 : chunk;
+        const int32_t *nsym = s.nsym + f0;
+        const uint8_t *raw = s.raw + f0 * s.raw_stride;
+        uint8_t *out = d.out + f0 * d.out_stride;
+        rc = llr_run(c, d.in + f0 * d.frame_stride, nf, d.frame_stride, d.frame_len, 10, d.max_symbols, s.offs + f0, s.fd + f0, nsym,
+                     s.hk + f0 * N, N, OFDM_SOFT_LLR_SCALE, (int8_t *)w_llr, llr_stride, s.raw + f0 * s.raw_stride, s.raw_stride, f0 == 0);
+        if (rc) return rc;
+        if (f0 == 0) c->trace.add(name);
+        if (m.ldpc()) {
+            LdpcDecodeParams lp;
+            lp.llr = llr; lp.n_frames = nf; lp.llr_stride = llr_stride; lp.max_iter = OFDM_LDPC_MAX_ITER;
+            lp.out = out; lp.out_stride = d.out_stride; lp.status_rw = d.status + f0; lp.out_len = d.out_len + f0;
+            lp.nsym = nsym; lp.bytes_per_symbol = bps_bytes;
+            HIP_TRY(c, run_ldpc_decode(lp, c->num_cu, &c->tune, c->stream));
+        } else if (m.conv()) {
+            vp.n_frames = nf; vp.out = out; vp.raw = raw; vp.status = d.status + f0; vp.nsym = nsym; vp.out_len = d.out_len + f0;
+            if (m.rate() < 0) {
+                HIP_TRY(c, run_viterbi_k7(vp, v_blocks, c->stream));
+            } else {
+                const ViterbiFParams vf{vp, m.rate(), d.status + f0}; // (it may set status)
+                HIP_TRY(c, run_viterbi_k7f(vf, v_blocks, c->stream));
+            }
+        } else {
+            HIP_TRY(c, run_rx_finish_soft(raw, s.raw_stride, llr, llr_stride, nf, d.status + f0, nsym, bps_bytes, out, d.out_stride,
+                                          d.out_len + f0, c->stream));
+        }
+    }
     return OFDM_OK;
 }
 
-static int rx_decode_impl(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
-                          int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
-                          int32_t *status, int32_t *offset, double *f_delta, float *metric, const KnownSync *known) {
-    if (!c) return OFDM_ERR_INVALID;
-    if (!fcs_outer(c->prm.ecc))
-        return rx_decode_base(c, c->prm.ecc, in, n_frames, frame_stride, frame_len, n_lags, max_symbols, out, out_stride, out_len, status,
-                              offset, f_delta, metric, known);
-    // OFDM_ECC_FCS + mode: the base mode's chain into a workspace of dword rows (the fused frame kernels and k_rs255_decode write
-    // there as they write to a caller's rows), then k_fcs_check over what every frame delivered, in place on status / out_len
-    if (n_frames < 0 || frame_len <= 0 || max_symbols <= 0) return OFDM_ERR_INVALID;
-    if (n_frames && (!in || !out || !out_len || !status)) return OFDM_ERR_INVALID;
-    const int ecc = base_ecc(c->prm.ecc);
-    const int64_t raw_bytes = (int64_t)max_symbols * c->bytes_per_symbol();
-    const int64_t base_max = base_row_bytes(ecc, raw_bytes > 16 ? raw_bytes - 16 : 0);
-    if (base_max > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED;
-    if (out_stride < base_max - OFDM_FCS_OVERHEAD) return OFDM_ERR_INVALID;
-    if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    const int64_t row = (std::max<int64_t>(base_max, 4) + 3) & ~(int64_t)3;
-    void *w_rows;
-    int rc = ws_get(c, 14, (size_t)row * (size_t)n_frames, &w_rows);
-    if (rc) return rc;
-    rc = rx_decode_base(c, ecc, in, n_frames, frame_stride, frame_len, n_lags, max_symbols, (uint8_t *)w_rows, row, out_len, status, offset,
-                        f_delta, metric, known);
-    if (rc) return rc;
-    FcsCheckParams fp;
-    fp.row = (const uint8_t *)w_rows; fp.n_frames = n_frames; fp.row_stride = row; fp.n_row = base_max; fp.row_len = out_len;
-    fp.out = out; fp.out_stride = out_stride; fp.out_len = out_len; fp.status_rw = status;
-    c->trace.add("k_fcs_check");
-    HIP_TRY(c, run_fcs_check(fp, c->num_cu, &c->tune, c->stream));
-    return OFDM_OK;
-}
-
-static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
-                           int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
-                           int32_t *status, int32_t *offset, double *f_delta, float *metric, const KnownSync *known) {
-    if (!c || n_frames < 0 || frame_len <= 0 || max_symbols <= 0) return OFDM_ERR_INVALID;
-    if (n_frames && (!in || !out || !out_len || !status)) return OFDM_ERR_INVALID;
+// The chain of the plan's inner mode into the rows d.out / d.out_stride: the caller's, or the innermost outer layer's workspace
+static int rx_decode_inner(ofdm_ctx *c, const DecodeCall &d) {
+    const ModePlan &m = c->mode;
+    const int64_t n_frames = d.n_frames, frame_stride = d.frame_stride, frame_len = d.frame_len, out_stride = d.out_stride;
+    const int32_t max_symbols = d.max_symbols;
+    uint8_t *const out = d.out;
+    int32_t *const out_len = d.out_len, *const status = d.status, *const offset = d.offset;
+    float *const metric = d.metric;
     if (n_frames > 1 && frame_stride <= 0) return OFDM_ERR_INVALID;
     const int bps_bytes = c->bytes_per_symbol();
     const int64_t raw_bytes = (int64_t)max_symbols * bps_bytes;
@@ -1303,28 +1299,26 @@ static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_
     // rows must hold what k_rx_finish can write: the whole body without an outer code, floor(body / 7) * 4 bytes after
     // Hamming(7,4) decoding, body / 2 - 1 after Viterbi decoding (include/ofdm_hip.h)
     const int64_t body_max = raw_bytes > 16 ? raw_bytes - 16 : 0;
-    if (out_stride < inner_row_bytes(ecc, body_max)) return OFDM_ERR_INVALID;
-    const int f_rate = framed_rate(ecc);
-    const bool conv = ecc == OFDM_ECC_CONV_K7 || f_rate >= 0;
+    if (out_stride < inner_row_limit(m, body_max)) return OFDM_ERR_INVALID;
+    const int ecc = m.inner, f_rate = m.rate();
     // the longest trellis a frame can ask for (framed: the 72-step length block, then a body cut at the end of the capture)
     const int64_t body_steps = f_rate < 0 ? 4 * body_max
                                           : std::max<int64_t>(4 * kConvLengthBlock, conv_max_steps(8 * std::max<int64_t>(body_max - kConvLengthBlock, 0), f_rate));
-    if (conv && body_steps > kViterbiMaxSteps) return OFDM_ERR_UNSUPPORTED;
+    if (m.conv() && body_steps > kViterbiMaxSteps) return OFDM_ERR_UNSUPPORTED;
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
     c->trace.reset();
     const int N = c->prm.n_fft;
     void *w_dhat, *w_fd, *w_off, *w_nsym, *w_hk = nullptr, *w_raw = nullptr;
     int rc;
-    if ((rc = ws_get(c, 0, sizeof(int32_t) * (size_t)n_frames, &w_dhat))) return rc;
-    if ((rc = ws_get(c, 1, sizeof(double) * (size_t)n_frames, &w_fd))) return rc;
-    if ((rc = ws_get(c, 2, sizeof(int32_t) * (size_t)n_frames, &w_off))) return rc;
-    if ((rc = ws_get(c, 3, sizeof(int32_t) * (size_t)n_frames, &w_nsym))) return rc;
+    if ((rc = ws_get(c, kWsDhat, sizeof(int32_t) * (size_t)n_frames, &w_dhat))) return rc;
+    if ((rc = ws_get(c, kWsFdelta, sizeof(double) * (size_t)n_frames, &w_fd))) return rc;
+    if ((rc = ws_get(c, kWsOffset, sizeof(int32_t) * (size_t)n_frames, &w_off))) return rc;
+    if ((rc = ws_get(c, kWsNsym, sizeof(int32_t) * (size_t)n_frames, &w_nsym))) return rc;
     int32_t *offs = offset ? offset : (int32_t *)w_off;
-    double *fd = f_delta ? f_delta : (double *)w_fd;
-    const float2 *x = reinterpret_cast<const float2 *>(in);
-    if ((rc = ws_get(c, 5, (size_t)raw_stride * (size_t)n_frames, &w_raw))) return rc;
-    if (known) {
+    double *fd = d.f_delta ? d.f_delta : (double *)w_fd;
+    const float2 *x = d.in;
+    if ((rc = ws_get(c, kWsRaw, (size_t)raw_stride * (size_t)n_frames, &w_raw))) return rc;
+    if (const KnownSync *known = d.known) {
         // 1k. the caller brings the timing of the one capture (ofdm_rx_decode_long with lag_lo > 0)
         if (n_frames != 1 || c->prm.sync_mode != OFDM_SYNC_SCHMIDL_COX) return OFDM_ERR_INVALID;
         c->trace.add("k_set_sync+k_rx_prepare");
@@ -1336,7 +1330,7 @@ static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_
         //     idx_max - N (= lag - 1), then frequency_correction on chunks 3 and 4 (receiver.rs:39; always |.|)
         if (frame_len > 0x3fffffff) return OFDM_ERR_UNSUPPORTED;
         void *w_x;
-        if ((rc = ws_get(c, 6, xcorr_workspace_bytes(n_frames, frame_len, c->S()), &w_x))) return rc;
+        if ((rc = ws_get(c, kWsSearch, xcorr_workspace_bytes(n_frames, frame_len, c->S()), &w_x))) return rc;
         c->trace.add("k_xcorr+k_rx_prepare_ref");
         HIP_TRY(c, run_xcorr(x, n_frames, frame_stride, frame_len, c->d_header, c->S(), w_x, (int32_t *)w_dhat, metric, nullptr, 0,
                              c->num_cu, c->stream));
@@ -1350,7 +1344,7 @@ static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_
         else { c->trace.add("k_freq_corr"); HIP_TRY(c, run_freq_correction(x + 3 * c->S(), n_frames, frame_stride, c->S(), c->S(), fd, c->stream, offs, status)); }
     } else {
     // 1. timing + CFO: Schmidl-Cox over the repeated preamble (replaces xcorr_fft, src/receiver.rs:20-25,39)
-    rc = ofdm_abi_sc_run(c, x, n_frames, frame_stride, frame_len, n_lags, (int32_t *)w_dhat, fd, metric);
+    rc = ofdm_abi_sc_run(c, x, n_frames, frame_stride, frame_len, d.n_lags, (int32_t *)w_dhat, fd, metric);
     if (rc) return rc;
     // 2. trimmed start, length check, live symbols (receiver.rs:21-36)
     c->trace.add("k_rx_prepare");
@@ -1360,8 +1354,7 @@ static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_
     // 3+4. channel estimate from the 5 training blocks and per data symbol CP strip + FFT + equalise + pilot phase +
     //      demap (receiver.rs:44-83).  N = 64: one fused wave-centric kernel; otherwise the generic pair.
     bool fused = false, finished = false;
-    const bool ldpc = ecc == OFDM_ECC_LDPC648;
-    const bool soft = ecc == OFDM_ECC_HAMMING74_SOFT || conv || ldpc; // the fused frame kernels have no LLR epilogue: the generic chain
+    const bool soft = m.soft();                               // the fused frame kernels have no LLR epilogue: the generic chain
     const bool wls = c->prm.chest_mode == OFDM_CHEST_WLS;     // ... and take no channel estimate from outside: the generic chain
     if (N == 1024 && !soft && !wls) { // one workgroup per frame: channel estimate kept in registers, 16 x 64 FFT (kernels_rx1024.hip)
         const bool off = c->tune.no_rxframe1024 != 0; // A/B switch
@@ -1379,70 +1372,21 @@ static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_
         // without an outer code the kernel also parses the length header and writes the payload to its final place
         const bool fin = ecc == OFDM_ECC_NONE && (reinterpret_cast<uintptr_t>(out) & 3) == 0 && (out_stride & 3) == 0;
         void *w_cut;
-        if ((rc = ws_get(c, 8, sizeof(int32_t) * (size_t)(n_frames + 4), &w_cut))) return rc;
+        if ((rc = ws_get(c, kWsCut, sizeof(int32_t) * (size_t)(n_frames + 4), &w_cut))) return rc;
         const int r = fast_path(c, fin ? run_rxframe64(p, nullptr, c->stream, c->num_cu, out, out_stride, out_len, nullptr, nullptr, (int32_t *)w_cut)
                                        : run_rxframe64(p, nullptr, c->stream, c->num_cu, nullptr, 0, nullptr, nullptr, nullptr, (int32_t *)w_cut));
         if (r == OFDM_OK) { fused = true; finished = fin; }
         else if (r != kNextPath) return r;
     }
     if (!fused) {
-        if ((rc = ws_get(c, 4, sizeof(float2) * (size_t)N * (size_t)n_frames, &w_hk))) return rc;
+        if ((rc = ws_get(c, kWsHk, sizeof(float2) * (size_t)N * (size_t)n_frames, &w_hk))) return rc;
         SymParams p = rx_params(c, x, n_frames, frame_stride, frame_len, offs, fd);
         p.out = (float2 *)w_hk;
         HIP_TRY(c, run_chest(N, p, c->stream, c->num_cu));
         if (wls && (rc = chest_smooth_run(c, (const float2 *)w_hk, n_frames, (float2 *)w_hk, true))) return rc; // EXT-5: H' in place of H^
         if (soft) {
-            // 4s + 5s. per frame chunk: hard bytes (for the header) and LLRs in one k_sym<llr>, then the header and the ML decode of
-            // the body (k_rx_finish_soft; OFDM_ECC_CONV_K7: k_viterbi_k7, which also needs a survivor slab per resident wavefront;
-            // OFDM_ECC_CONV_K7F_*: k_viterbi_k7f, which reads the length from its own coded block and may set status;
-            // OFDM_ECC_LDPC648: k_ldpc_decode, which reads the length from its first code word and may set status).
-            // The LLR workspace holds one chunk: at most kSoftLlrBytes whatever n_frames is.
-            const int64_t llr_row = (int64_t)max_symbols * c->carriers() * c->prm.modulation;
-            const int64_t llr_stride = (llr_row + 15) & ~(int64_t)15;
-            int64_t chunk = c->tune.soft_chunk_frames > 0 ? c->tune.soft_chunk_frames : kSoftLlrBytes / llr_stride;
-            if (chunk < 1) chunk = 1;
-            if (chunk > n_frames) chunk = n_frames;
-            void *w_llr;
-            if ((rc = ws_get(c, 9, (size_t)(llr_stride * chunk), &w_llr))) return rc;
-            ViterbiFParams vp;   // (k_viterbi_k7 takes its ViterbiParams part)
-            long long v_blocks = 0;
-            if (conv) {
-                void *w_surv;
-                viterbi_k7_plan(chunk, body_steps, c->num_cu, &c->tune, &v_blocks, &vp.slab_words);
-                if ((rc = ws_get(c, 10, (size_t)(v_blocks * 4 * vp.slab_words) * sizeof(unsigned long long), &w_surv))) return rc;
-                vp.surv = (unsigned long long *)w_surv;
-                vp.llr = (const int8_t *)w_llr; vp.llr_stride = llr_stride; vp.out_stride = out_stride;
-                vp.raw_stride = raw_stride; vp.bytes_per_symbol = bps_bytes; vp.rate = f_rate < 0 ? 0 : f_rate;
-            }
-            for (int64_t f0 = 0; f0 < n_frames; f0 += chunk) {
-                const int64_t nf = n_frames - f0 < chunk ? n_frames - f0 : chunk;
-                rc = llr_run(c, x + f0 * frame_stride, nf, frame_stride, frame_len, 10, max_symbols, offs + f0, fd + f0,
-                             (const int32_t *)w_nsym + f0, (const float2 *)w_hk + f0 * N, N, OFDM_SOFT_LLR_SCALE, (int8_t *)w_llr, llr_stride,
-                             (uint8_t *)w_raw + f0 * raw_stride, raw_stride, f0 == 0);
-                if (rc) return rc;
-                if (ldpc) {
-                    LdpcDecodeParams lp;
-                    lp.llr = (const int8_t *)w_llr; lp.n_frames = nf; lp.llr_stride = llr_stride; lp.max_iter = OFDM_LDPC_MAX_ITER;
-                    lp.out = out + f0 * out_stride; lp.out_stride = out_stride; lp.status_rw = status + f0; lp.out_len = out_len + f0;
-                    lp.nsym = (const int32_t *)w_nsym + f0; lp.bytes_per_symbol = bps_bytes;
-                    if (f0 == 0) c->trace.add("k_ldpc_decode");
-                    HIP_TRY(c, run_ldpc_decode(lp, c->num_cu, &c->tune, c->stream));
-                    continue;
-                }
-                if (conv) {
-                    if (f0 == 0) c->trace.add(f_rate < 0 ? "k_viterbi_k7" : "k_viterbi_k7f");
-                    vp.n_frames = nf; vp.out = out + f0 * out_stride; vp.raw = (const uint8_t *)w_raw + f0 * raw_stride;
-                    vp.status = status + f0; vp.nsym = (const int32_t *)w_nsym + f0; vp.out_len = out_len + f0;
-                    if (f_rate >= 0) { vp.status_rw = status + f0; HIP_TRY(c, run_viterbi_k7f(vp, v_blocks, c->stream)); continue; }
-                    HIP_TRY(c, run_viterbi_k7(vp, v_blocks, c->stream));
-                    continue;
-                }
-                if (f0 == 0) c->trace.add("k_rx_finish_soft");
-                HIP_TRY(c, run_rx_finish_soft((const uint8_t *)w_raw + f0 * raw_stride, raw_stride, (const int8_t *)w_llr, llr_stride, nf,
-                                              status + f0, (const int32_t *)w_nsym + f0, bps_bytes, out + f0 * out_stride, out_stride,
-                                              out_len + f0, c->stream));
-            }
-            return OFDM_OK;
+            const SoftInput si{offs, fd, (const int32_t *)w_nsym, (const float2 *)w_hk, (uint8_t *)w_raw, raw_stride, body_steps};
+            return rx_finish_soft(c, d, si);
         }
         rc = demod_run(c, x, n_frames, frame_stride, frame_len, 10, max_symbols, offs, fd, (const int32_t *)w_nsym,
                        (const float2 *)w_hk, N, (uint8_t *)w_raw, raw_stride, nullptr);
@@ -1455,6 +1399,56 @@ static int rx_decode_inner(ofdm_ctx *c, int ecc, const ofdm_fc32 *in, int64_t n_
                                  ecc, out, out_stride, out_len, c->stream));
     }
     return OFDM_OK;
+}
+
+// The decode chain of the context's mode: the inner chain into the innermost outer layer's workspace (dword rows: the fused frame
+// kernels and the layer inside write there as they write to a caller's rows), then every outer layer's kernel inside-out over what
+// every frame delivered, in place on out_len / status
+static int rx_decode(ofdm_ctx *c, const DecodeCall &d) {
+    if (!c || d.n_frames < 0 || d.frame_len <= 0 || d.max_symbols <= 0) return OFDM_ERR_INVALID;
+    if (d.n_frames && (!d.in || !d.out || !d.out_len || !d.status)) return OFDM_ERR_INVALID;
+    const ModePlan &m = c->mode;
+    const int64_t raw_bytes = (int64_t)d.max_symbols * c->bytes_per_symbol();
+    int64_t n_row[2], row = inner_row_limit(m, raw_bytes > 16 ? raw_bytes - 16 : 0); // n_row[i]: the longest row layer i can be given
+    for (int i = m.n_outer - 1; i >= 0; i--) { n_row[i] = row; row = outer_row_limit(m.outer[i], row); }
+    DeviceGuard dev_guard(c->device);
+    struct { uint8_t *rows; int64_t stride; } to[3] = {{d.out, d.out_stride}}; // to[i]: where layer i writes; to[n_outer]: the inner chain
+    int rc;
+    for (int i = 0; i < m.n_outer; i++) {
+        const OuterStage &s = kOuter[m.outer[i]];
+        if (n_row[i] > s.rx_max_row) return OFDM_ERR_UNSUPPORTED;
+        if (to[i].stride < outer_row_limit(m.outer[i], n_row[i])) return OFDM_ERR_INVALID;
+        if (!d.n_frames) return OFDM_OK;
+        void *w_rows;
+        to[i + 1].stride = (std::max<int64_t>(n_row[i], 4) + 3) & ~(int64_t)3;
+        if ((rc = ws_get(c, s.rx_rows, (size_t)to[i + 1].stride * (size_t)d.n_frames, &w_rows))) return rc;
+        to[i + 1].rows = (uint8_t *)w_rows;
+    }
+    DecodeCall inner = d;
+    inner.out = to[m.n_outer].rows; inner.out_stride = to[m.n_outer].stride;
+    if ((rc = rx_decode_inner(c, inner))) return rc;
+    for (int i = m.n_outer - 1; i >= 0; i--) {
+        const OuterStage &s = kOuter[m.outer[i]];
+        c->trace.add(s.rx_name);
+        HIP_TRY(c, s.decode(c, LayerCall{to[i + 1].rows, d.n_frames, to[i + 1].stride, n_row[i], d.out_len, to[i].rows, to[i].stride, d.out_len, nullptr, d.status}));
+    }
+    return OFDM_OK;
+}
+
+int ofdm_rx_decode_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                         int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
+                         int32_t *status, int32_t *offset, double *f_delta, float *metric) {
+    const DecodeCall d{reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, n_lags, max_symbols, out, out_stride, out_len,
+                       status, offset, f_delta, metric, nullptr};
+    return rx_decode(c, d);
+}
+int ofdm_abi_rx_decode_known(ofdm_ctx *c, const ofdm_fc32 *in, int64_t frame_len, int32_t d_hat, double f_delta, float metric,
+                             int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len, int32_t *status, int32_t *offset,
+                             double *f_delta_out, float *metric_out) {
+    const KnownSync k{d_hat, f_delta, metric};
+    const DecodeCall d{reinterpret_cast<const float2 *>(in), 1, frame_len, frame_len, 0, max_symbols, out, out_stride, out_len, status, offset,
+                       f_delta_out, metric_out, &k};
+    return rx_decode(c, d);
 }
 
 // CHANNEL (src/channel.rs:26-31): 64 taps, the non-zero ones are 8..16 and 18
@@ -1494,7 +1488,7 @@ int ofdm_hbm_read_probe(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_symbols, int
     DeviceGuard dev_guard(c->device);
     c->trace.reset();
     void *sink;
-    int rc = ws_get(c, 7, 64, &sink);
+    int rc = ws_get(c, kWsProbeSink, 64, &sink);
     if (rc) return rc;
     HIP_TRY(c, run_read_probe(reinterpret_cast<const float2 *>(in), n_symbols, pattern, (unsigned *)sink, c->num_cu, c->stream));
     return OFDM_OK;

@@ -7,15 +7,83 @@
 #include <cstddef>
 #include <vector>
 
+// ---- what a mode is.  ecc = [OFDM_ECC_FCS +] [OFDM_ECC_RS255 +] inner (include/ofdm_hip.h): the inner code makes the frames that travel,
+// every outer layer turns rows (+ optional per-row lengths) into longer rows on transmit and back on receive.
+enum OuterLayer { kLayerFcs, kLayerRs };
+struct ModePlan {
+    int n_outer = 0;
+    OuterLayer outer[2] = {};   // outside-in
+    int inner = OFDM_ECC_NONE;  // NONE, HAMMING74, HAMMING74_SOFT, CONV_K7, CONV_K7F_R12 / _R23 / _R34 or LDPC648
+    bool has(OuterLayer l) const { return (n_outer > 0 && outer[0] == l) || (n_outer > 1 && outer[1] == l); }
+    // rate (0 = 1/2, 1 = 2/3, 2 = 3/4) of a framed convolutional inner mode, -1 for every other
+    int rate() const { return inner >= OFDM_ECC_CONV_K7F_R12 && inner <= OFDM_ECC_CONV_K7F_R34 ? inner - OFDM_ECC_CONV_K7F_R12 : -1; }
+    bool conv() const { return inner == OFDM_ECC_CONV_K7 || rate() >= 0; }
+    bool ldpc() const { return inner == OFDM_ECC_LDPC648; }
+    bool soft() const { return inner == OFDM_ECC_HAMMING74_SOFT || conv() || ldpc(); } // decoded from LLRs
+};
+// The plan of `ecc`; false when ecc is no mode (3 and 4 are none, nor are 21 .. 29 or 36 = RS around LDPC; 64 + a base mode is one).
+// RS goes around OFDM_ECC_NONE and the framed modes only, the frame check around all twelve.
+inline bool mode_plan(int ecc, ModePlan *m) {
+    *m = ModePlan();
+    if (ecc >= OFDM_ECC_FCS) { m->outer[m->n_outer++] = kLayerFcs; ecc -= OFDM_ECC_FCS; }
+    const int in = ecc - OFDM_ECC_RS255;
+    if (in == OFDM_ECC_NONE || (in >= OFDM_ECC_CONV_K7F_R12 && in <= OFDM_ECC_CONV_K7F_R34)) { m->outer[m->n_outer++] = kLayerRs; ecc = in; }
+    m->inner = ecc;
+    return ecc == OFDM_ECC_NONE || ecc == OFDM_ECC_HAMMING74 || ecc == OFDM_ECC_HAMMING74_SOFT || m->conv() || m->ldpc();
+}
+
+// The two length maps of every layer.  *_coded_bytes: payload bytes -> the bytes the layer makes of them.  *_row_limit: the largest row
+// the layer can deliver for `body` bytes in front of it (inner: the bytes behind the 16-byte length header; outer: the row below).
+inline int64_t inner_coded_bytes(const ModePlan &m, int64_t n) {
+    if (m.inner == OFDM_ECC_CONV_K7) return 2 * (n + 1); // rate 1/2 over the payload and one tail byte
+    if (m.rate() >= 0) return ofdm::kConvLengthBlock + ofdm::conv_body_len(n, m.rate());
+    if (m.ldpc()) return ofdm_ldpc648_coded_len(n);
+    return m.inner != OFDM_ECC_NONE ? ((n + 3) / 4) * 7 : n; // the soft decoder reads the same code
+}
+inline int64_t inner_row_limit(const ModePlan &m, int64_t body) {
+    if (m.inner == OFDM_ECC_NONE) return body;
+    if (m.ldpc()) return body >= 80 ? 40 * (body / 80) - 8 : 0;                  // the whole code words' info bytes less the two length words
+    if (m.inner == OFDM_ECC_CONV_K7) return body / 2 >= 1 ? body / 2 - 1 : 0;    // 4 body steps = body / 2 bytes, less the tail byte
+    if (m.rate() >= 0)                               // the steps a body cut at the end of the capture still holds, behind the length block
+        return body >= ofdm::kConvLengthBlock ? ofdm::conv_max_steps(8 * (body - ofdm::kConvLengthBlock), m.rate()) / 8 : 0;
+    return (body / 7) * 4;                                                       // Hamming(7,4), hard or soft
+}
+inline int64_t outer_coded_bytes(OuterLayer l, int64_t n) { return l == kLayerFcs ? n + OFDM_FCS_OVERHEAD : ofdm_rs255_encoded_len(n); }
+// (kLayerFcs: below 0 for a row shorter than the envelope, which delivers nothing)
+inline int64_t outer_row_limit(OuterLayer l, int64_t row) { return l == kLayerFcs ? row - OFDM_FCS_OVERHEAD : ofdm_rs255_decoded_len(row); }
+
+// ... composed over the plan: what ofdm_coded_len returns, and the row size every decode entry point asks of its caller
+inline int64_t coded_len(const ModePlan &m, int64_t n) {
+    for (int i = 0; i < m.n_outer; i++) n = outer_coded_bytes(m.outer[i], n);
+    return inner_coded_bytes(m, n);
+}
+inline int64_t row_bytes(const ModePlan &m, int64_t body) {
+    int64_t row = inner_row_limit(m, body);
+    for (int i = m.n_outer - 1; i >= 0; i--) row = outer_row_limit(m.outer[i], row);
+    return row > 0 ? row : 0;
+}
+
 struct Workspace {
     void *ptr = nullptr;
     size_t cap = 0;
+};
+// One slot per buffer role.  The rule: two roles that can be live in the same entry point never share a slot.
+enum WsRole {
+    kWsDhat, kWsFdelta, kWsOffset, kWsNsym, kWsHk, kWsRaw, kWsCut, kWsLlr, kWsSurvivors, // the decode chain, search to finish
+    kWsSearch, kWsSearchD1,      // the timing search's scratch (k_sc_*, k_scb_*, k_xcorr: one at a time) and the tiled search's first crossings
+    kWsChestTaps,                // EXT-5: the solve's zeroed rows
+    kWsRxFcsRows, kWsRxRsRows,   // decode: the dword rows an outer layer reads
+    kWsTxFcsRows, kWsTxFcsLen, kWsTxRsRows, kWsTxRsLen, kWsTxCoded, kWsTxCodedLen, // encode: rows and ragged lengths out of every layer
+    kWsFrameMax,                 // per-frame maxima (ofdm_tx_encode_batch, ofdm_normalize_batch)
+    kWsProbeSink,                // ofdm_hbm_read_probe
+    kWsRoles
 };
 
 struct HostPipe; // pinned staging, copy streams and slot buffers of the host-buffer entry points (ofdm_host_path.hip)
 
 struct ofdm_ctx {
     ofdm_params prm;
+    ModePlan mode;                // the layers of prm.ecc (ofdm_create)
     int device = 0;
     int num_cu = 256;
     hipStream_t stream = nullptr;
@@ -35,7 +103,7 @@ struct ofdm_ctx {
     ofdm::ScStats sc_stats;             // list counters of the last Schmidl-Cox search (ofdm_get_tuning "stat_sc_*")
     int32_t *d_stats = nullptr;         // [2] their home on the device (owned by the context)
     // workspaces (grown on demand, never inside a captured region)
-    Workspace ws[16];
+    Workspace ws[kWsRoles];
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     HostPipe *pipe = nullptr;     // created by the first host-buffer call, freed by ofdm_destroy
 
@@ -63,8 +131,8 @@ struct DeviceGuard {
         if (_e != hipSuccess) { (ctx)->last_hip = (int)_e; return OFDM_ERR_HIP; } \
     } while (0)
 
-inline int ws_get(ofdm_ctx *c, int slot, size_t bytes, void **out) {
-    Workspace &w = c->ws[slot];
+inline int ws_get(ofdm_ctx *c, WsRole role, size_t bytes, void **out) {
+    Workspace &w = c->ws[role];
     if (bytes > w.cap) {
         if (w.ptr) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, hipFree(w.ptr)); w.ptr = nullptr; w.cap = 0; }
         size_t want = bytes + bytes / 8 + 256;
@@ -74,45 +142,6 @@ inline int ws_get(ofdm_ctx *c, int slot, size_t bytes, void **out) {
     }
     *out = w.ptr;
     return OFDM_OK;
-}
-
-// rate (0 = 1/2, 1 = 2/3, 2 = 3/4) of a framed convolutional mode, -1 for every other ecc value
-inline int framed_rate(int ecc) { return ecc >= OFDM_ECC_CONV_K7F_R12 && ecc <= OFDM_ECC_CONV_K7F_R34 ? ecc - OFDM_ECC_CONV_K7F_R12 : -1; }
-
-// OFDM_ECC_RS255* = 20 + inner: the outer Reed-Solomon code around the frames of the inner mode (OFDM_ECC_NONE or a framed mode)
-inline bool rs_outer(int ecc) { return ecc == OFDM_ECC_RS255 || (ecc >= OFDM_ECC_RS255_K7F_R12 && ecc <= OFDM_ECC_RS255_K7F_R34); }
-// the mode whose frames travel: ecc itself, or the inner mode of an RS mode
-inline int inner_ecc(int ecc) { return rs_outer(ecc) ? ecc - OFDM_ECC_RS255 : ecc; }
-
-// OFDM_ECC_FCS + mode = 64 + mode: the CRC-32 frame check around the frames of `mode`, any of the twelve base modes (an RS mode included)
-inline bool base_mode(int ecc) {
-    return ecc == OFDM_ECC_NONE || ecc == OFDM_ECC_HAMMING74 || ecc == OFDM_ECC_HAMMING74_SOFT || ecc == OFDM_ECC_CONV_K7 || framed_rate(ecc) >= 0 ||
-           rs_outer(ecc) || ecc == OFDM_ECC_LDPC648;
-}
-inline bool fcs_outer(int ecc) { return ecc >= OFDM_ECC_FCS && base_mode(ecc - OFDM_ECC_FCS); }
-// the mode whose frames carry the envelope: ecc itself, or the base mode of an FCS mode
-inline int base_ecc(int ecc) { return fcs_outer(ecc) ? ecc - OFDM_ECC_FCS : ecc; }
-
-// Largest out_len the decode chain of mode `ecc` (no RS mode) can write for a frame whose body (the bytes behind the 16-byte length
-// header) is `body` bytes
-inline int64_t inner_row_bytes(int ecc, int64_t body) {
-    if (ecc == OFDM_ECC_NONE) return body;
-    if (ecc == OFDM_ECC_LDPC648) return body >= 80 ? 40 * (body / 80) - 8 : 0; // the whole code words' info bytes less the two length words
-    if (ecc == OFDM_ECC_CONV_K7) return body / 2 >= 1 ? body / 2 - 1 : 0; // 4 body steps = body / 2 bytes, less the tail byte
-    if (framed_rate(ecc) >= 0)                       // the steps a body cut at the end of the capture still holds, behind the length block
-        return body >= ofdm::kConvLengthBlock ? ofdm::conv_max_steps(8 * (body - ofdm::kConvLengthBlock), framed_rate(ecc)) / 8 : 0;
-    return (body / 7) * 4;                                                       // Hamming(7,4), hard or soft
-}
-// ... of base mode `ecc` (no FCS mode).  RS modes: the decoded blocks of the longest row the inner mode can deliver.
-inline int64_t base_row_bytes(int ecc, int64_t body) {
-    const int64_t inner = inner_row_bytes(inner_ecc(ecc), body);
-    return rs_outer(ecc) ? ofdm_rs255_decoded_len(inner) : inner;
-}
-// ... of the context's mode: the row size every decode entry point asks of its caller (include/ofdm_hip.h).  FCS modes: the base
-// mode's row less the envelope's 8 bytes.
-inline int64_t decode_row_bytes(const ofdm_ctx *c, int64_t body) {
-    const int64_t base = base_row_bytes(base_ecc(c->prm.ecc), body);
-    return fcs_outer(c->prm.ecc) ? (base > OFDM_FCS_OVERHEAD ? base - OFDM_FCS_OVERHEAD : 0) : base;
 }
 
 // internal cross-file helpers (C linkage only because their definitions sit inside the extern "C" blocks; not in ofdm_hip.h)

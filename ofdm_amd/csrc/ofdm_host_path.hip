@@ -522,7 +522,7 @@ int ofdm_rx_decode_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_frames,
     if (n_frames > 1 && frame_stride < frame_len) return OFDM_ERR_INVALID; // rows of a host batch do not overlap
     const int64_t raw = (int64_t)max_symbols * c->bytes_per_symbol();
     const int64_t body = raw > 16 ? raw - 16 : 0;
-    const int64_t need = decode_row_bytes(c, body);
+    const int64_t need = row_bytes(c->mode, body);
     if (out_stride < need) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
     DeviceGuard dev_guard(c->device);

@@ -1,5 +1,5 @@
 """What the decode chains must deliver, composed from the stage entry points and the CPU restatements -- shared by the tests of the
-modes (tests/test_gpu_soft.py, test_gpu_conv.py, test_gpu_rs.py) and by tests/test_gpu_forged_header.py.  Every helper reads the
+modes (tests/test_gpu_soft.py, test_gpu_conv.py, test_gpu_rs.py) and by tests/test_gpu_forged_header.py.  Every decode helper reads the
 16-byte length header from the hard bytes rx_demod returns for the chain's own offset / f_delta / channel estimate and applies the
 rule of src/receiver.rs:85-95 in plain integers."""
 import os
@@ -9,6 +9,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv_ref as cr  # noqa: E402
+import fcs_ref  # noqa: E402
+import framed_ref as fr  # noqa: E402
+import ldpc_ref as lr  # noqa: E402
 import rs_vectors as rv  # noqa: E402
 import soft_ref as sr  # noqa: E402
 
@@ -80,3 +83,50 @@ def rs_composition(c, rx, max_symbols):
         data, out_len, fixed = rv.host_row(c.lib, by[f], int(ln[f]))
         want.append((UNCORRECTABLE, 0, b"") if fixed < 0 else (0, out_len, data))
     return ri, want
+
+
+# ---- a mode as a whole (tests/test_gpu_modes.py): ecc = [64 +] [20 +] inner, the lengths composed layer by layer from the references
+BASE_MODES = (0, 1, 2, 5, 10, 11, 12, 16, 20, 30, 31, 32)
+ALL_MODES = BASE_MODES + tuple(fcs_ref.ECC_FCS + m for m in BASE_MODES)
+
+
+def mode_layers(ecc):
+    """(frame check?, RS outer code?, inner mode)"""
+    fcs = ecc >= fcs_ref.ECC_FCS
+    base = ecc - fcs_ref.ECC_FCS if fcs else ecc
+    rs = base in (20, 30, 31, 32)
+    return fcs, rs, base - 20 if rs else base
+
+
+def mode_coded_len(ecc, p):
+    """bytes a frame of mode ecc carries behind its 16-byte header for a payload of p bytes"""
+    fcs, rs, inner = mode_layers(ecc)
+    if fcs:
+        p += fcs_ref.OVERHEAD
+    if rs:
+        p = 255 * (p // 223 + 1)                 # whole blocks and the trailing zero block
+    if inner == 0:
+        return p
+    if inner in (1, 2):
+        return 7 * -(-p // 4)
+    if inner == 5:
+        return 2 * (p + 1)
+    return lr.coded_len(p) if inner == 16 else fr.coded_len(p, inner - 10)
+
+
+def mode_row_bytes(ecc, body):
+    """the largest row the decode chain of mode ecc can deliver for a demodulated body of `body` bytes: the out_stride it asks for"""
+    fcs, rs, inner = mode_layers(ecc)
+    if inner == 0:
+        row = body
+    elif inner in (1, 2):
+        row = 4 * (body // 7)
+    elif inner == 5:
+        row = max(body // 2 - 1, 0)
+    elif inner == 16:
+        row = lr.row_bytes(body)
+    else:
+        row = fr.max_steps(8 * (body - fr.LENGTH_BLOCK), inner - 10) // 8 if body >= fr.LENGTH_BLOCK else 0
+    if rs:
+        row = 223 * (row // 255 + 1)
+    return max(row - fcs_ref.OVERHEAD, 0) if fcs else row
