@@ -1,5 +1,6 @@
 """What the decode chains must deliver, composed from the stage entry points and the CPU restatements -- shared by the tests of the
-modes (tests/test_gpu_soft.py, test_gpu_conv.py, test_gpu_rs.py) and by tests/test_gpu_forged_header.py.  Every decode helper reads the
+modes (tests/test_gpu_soft.py, test_gpu_conv.py, test_gpu_rs.py) and by tests/test_gpu_forged_header.py; the assertions those tests
+share are tests/chain_checks.py, the seeded link they run over is tools/link.py.  Every decode helper reads the
 16-byte length header from the hard bytes rx_demod returns for the chain's own offset / f_delta / channel estimate and applies the
 rule of src/receiver.rs:85-95 in plain integers."""
 import os
@@ -64,6 +65,20 @@ def conv_reference_decode(c, rx, r, max_symbols):
         dec = cr.viterbi(L[f, 128:128 + 8 * keep], terminated=(hi == 0 and lo <= body))
         want[f] = (n_out, bytes(dec[:n_out]))
     return want
+
+
+def decoder_rows(rng, n_steps, per_kind):
+    """LLR rows [4 * per_kind, 2 n_steps]: noisy codewords, uniform int8, all zero, +-127 along one codeword; and the bytes behind
+    the last kind"""
+    u = rng.integers(0, 2, (2 * per_kind, n_steps))
+    u[:, max(n_steps - 8, 0):] = 0                               # (a zero tail where there is room for one; not required)
+    code = np.stack([cr.encode_bits(r) for r in u]).astype(np.int64).reshape(2 * per_kind, 2 * n_steps)
+    noisy = np.clip(np.rint((2 * code[:per_kind] - 1) * 20 + rng.normal(0, 22, (per_kind, 2 * n_steps))), -127, 127)
+    uniform = rng.integers(-128, 128, (per_kind, 2 * n_steps))
+    zero = np.zeros((per_kind, 2 * n_steps), np.int64)
+    hard = (2 * code[per_kind:] - 1) * 127                        # the largest metrics a frame can produce
+    sent = np.packbits(u[per_kind:, : n_steps // 8 * 8], axis=1, bitorder="little") if n_steps >= 8 else np.zeros((per_kind, 0), np.uint8)
+    return np.concatenate([noisy, uniform, zero, hard]).astype(np.int8), sent
 
 
 def rs_composition(c, rx, max_symbols):

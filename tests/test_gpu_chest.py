@@ -16,17 +16,13 @@ import chest_cases as cc  # noqa: E402
 import chest_ref as cr  # noqa: E402
 import framed_ref as fr  # noqa: E402
 import rs_vectors as rv  # noqa: E402
+from chain_checks import assert_entry_points_agree, assert_rows_are, ofdm_api as _api  # noqa: E402
+from tools.link import link  # noqa: E402
 from util import assert_bytes_match, header_rule, rel_err, wide  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 ROWS = 67
-
-
-def _api():
-    from ofdm_amd import api
-
-    return api
 
 
 # ---------------------------------------------------------------------------------------------------------- 1. the stage
@@ -99,16 +95,8 @@ def test_stage_argument_checks():
 
 # ---------------------------------------------------------------------------------------------------------- 2. the mode's wiring
 def _link(ecc, n, n_frames, payload, seed, chest_mode, mod=4, snr=30.0):
-    """seeded payloads, delays 1 .. 32, CFO within +-1 / S, one channel seed (the link of tests/test_gpu_framed.py)"""
-    api = _api()
-    c = api.Context(n_fft=n, modulation=mod, guard_bands=True, ecc=ecc, chest_mode=chest_mode)
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    pay = torch.randint(0, 256, (n_frames, payload), dtype=torch.uint8, device=c.device, generator=g)
-    tx = c.encode_batch(pay)
-    d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
-    fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
-    rx = c.channel_batch(tx, snr_db=snr, seed=seed, delay=d, f_delta=fd, span=tx.shape[1] + 160)
-    return c, pay, rx, c.data_symbols(payload)
+    """the seeded link of tools/link.py with guard bands and the context's chest_mode set"""
+    return link(ecc, n, mod, n_frames, payload, snr, seed, chest_mode=chest_mode)
 
 
 @pytest.mark.parametrize("n", [64, 1024])
@@ -163,7 +151,7 @@ def test_chain_with_the_mode_is_the_composition_of_the_stages(orc, n, ecc_name):
     r = c.decode_batch(rx, max_symbols=D)
     c.synchronize()
     assert "k_chest_solve" in c.last_dispatch() and "k_rxframe" not in c.last_dispatch()
-    status, ln, by = r["status"].cpu().numpy(), r["len"].cpu().numpy(), r["bytes"].cpu().numpy()
+    status = r["status"].cpu().numpy()
     # the timing the chain reports is the search's own
     d, fd, _ = c.sc_correlate(rx)
     assert torch.equal(r["offset"], torch.clamp(d - c.S - 4, min=0).to(torch.int32)) and torch.equal(r["f_delta"], fd)
@@ -182,9 +170,7 @@ def test_chain_with_the_mode_is_the_composition_of_the_stages(orc, n, ecc_name):
     else:
         want = _staged_reference(c, rx, r, D, ecc, orc)
     assert sum(1 for st, _, _ in want.values() if st == 0) >= 3
-    for f, (st, n_out, data) in want.items():
-        assert (int(status[f]), int(ln[f])) == (st, n_out), f
-        assert bytes(by[f, :n_out]) == bytes(data), f
+    assert_rows_are(r, want)
     good = [f for f, (st, n_out, data) in want.items() if st == 0 and bytes(data[:300]) == bytes(pay[f].cpu().numpy())]
     if ecc != api.ECC_NONE and ecc != api.ECC_HAMMING74:
         assert len(good) >= 3                              # (30 dB: the coded modes deliver the payload)
@@ -207,26 +193,17 @@ def test_chain_with_the_mode_is_the_composition_of_the_stages(orc, n, ecc_name):
 def test_every_decode_entry_point_with_the_mode():
     api = _api()
     c, pay, rx, D = _link(api.ECC_CONV_K7F_R34, 64, 5, 300, 91, api.CHEST_WLS)
-    r = c.decode_batch(rx, max_symbols=D)
-    c.synchronize()
+    r, ones = assert_entry_points_agree(api, c, rx, D)      # (api.decode builds its own context: it has no chest_mode to pass on)
     assert int((r["status"] == 0).sum()) >= 3
-    host = c.decode_host(rx.cpu().numpy(), max_symbols=D, chunk_frames=2)
-    for k in ("status", "len", "offset", "f_delta", "metric"):
-        np.testing.assert_array_equal(host[k], r[k].cpu().numpy(), err_msg=k)
-    for f, n_out in enumerate(r["len"].cpu().numpy()):
-        assert bytes(host["bytes"][f, :n_out]) == bytes(r["bytes"][f, :n_out].cpu().numpy()), f
     cap = rx[1].contiguous()
-    one = c.decode_batch(cap.reshape(1, -1), max_symbols=D)
-    n_out = int(one["len"][0])
+    st, n_out, off, data = ones[1]
     d_hat = int(c.sc_correlate(cap.reshape(1, -1))[0][0])
     assert d_hat > 1      # (lag_lo = 1 leaves the detection where it is and takes the route of a known timing)
-    for res in (c.decode_long(cap, D), c.decode_long_host(cap.cpu().numpy(), D), c.decode_long(cap, D, d_hat_known=d_hat),
-                c.decode_long(cap, D, lag_lo=1)):
-        assert (res["status"], res["len"], res["offset"]) == (int(one["status"][0]), n_out, int(one["offset"][0]))
-        assert bytes(np.asarray(res["bytes"].cpu() if torch.is_tensor(res["bytes"]) else res["bytes"])[:n_out]) == \
-            bytes(one["bytes"][0, :n_out].cpu().numpy())
+    for res in (c.decode_long(cap, D, d_hat_known=d_hat), c.decode_long(cap, D, lag_lo=1)):
+        assert (res["status"], res["len"], res["offset"]) == (st, n_out, off)
+        assert bytes(res["bytes"].cpu().numpy()[:n_out]) == data
     assert "k_chest_solve" in c.last_dispatch()
-    assert n_out == 300 and bytes(one["bytes"][0, :300].cpu().numpy()) == bytes(pay[1].cpu().numpy())
+    assert n_out == 300 and data == bytes(pay[1].cpu().numpy())
 
 
 @pytest.mark.parametrize("n", [64, 1024])

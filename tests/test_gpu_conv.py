@@ -10,18 +10,15 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv_ref as cr  # noqa: E402
-from chain_refs import conv_reference_decode as _reference_decode  # noqa: E402
+from chain_checks import (assert_chunking_changes_nothing, assert_entry_points_agree, assert_refuses_short_rows, assert_rows_are,  # noqa: E402
+                          ofdm_api as _api)
+from chain_refs import conv_reference_decode, decoder_rows as _decoder_rows  # noqa: E402
+from tools.link import bit_errors, data_snr as _data_snr, link as _link  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 MODS = (1, 2, 4, 6, 8)
 KNOWN = (("", "0000"), ("61", "fb689c03"), ("616263", "fb68708c8bb89c03"), ("0001020304050607", "0000fb34ecd317e7b04f487b5f9ca4a80300"))
-
-
-def _api():
-    from ofdm_amd import api
-
-    return api
 
 
 def _ctx(**kw):
@@ -61,20 +58,6 @@ def test_encoder_matches_the_restatement(n_bytes):
 
 
 # ---------------------------------------------------------------------------------------------------------- 6. the decoder stage
-def _decoder_rows(rng, n_steps, per_kind):
-    """LLR rows [4 * per_kind, 2 n_steps]: noisy codewords, uniform int8, all zero, +-127 along one codeword; and the bytes behind
-    the last kind"""
-    u = rng.integers(0, 2, (2 * per_kind, n_steps))
-    u[:, max(n_steps - 8, 0):] = 0                               # (a zero tail where there is room for one; not required)
-    code = np.stack([cr.encode_bits(r) for r in u]).astype(np.int64).reshape(2 * per_kind, 2 * n_steps)
-    noisy = np.clip(np.rint((2 * code[:per_kind] - 1) * 20 + rng.normal(0, 22, (per_kind, 2 * n_steps))), -127, 127)
-    uniform = rng.integers(-128, 128, (per_kind, 2 * n_steps))
-    zero = np.zeros((per_kind, 2 * n_steps), np.int64)
-    hard = (2 * code[per_kind:] - 1) * 127                        # the largest metrics a frame can produce
-    sent = np.packbits(u[per_kind:, : n_steps // 8 * 8], axis=1, bitorder="little") if n_steps >= 8 else np.zeros((per_kind, 0), np.uint8)
-    return np.concatenate([noisy, uniform, zero, hard]).astype(np.int8), sent
-
-
 @pytest.mark.parametrize("n_steps", [0, 8, 13, 48, 64, 65, 1000, 4488, 10440])
 def test_decoder_matches_the_restatement(n_steps):
     c = _ctx()
@@ -133,29 +116,9 @@ def test_transmit_is_the_uncoded_frame_of_the_coded_bytes(n, mod):
 
 
 # ---------------------------------------------------------------------------------------------------------- helpers of 8-13
-def _link(ecc, n, mod, n_frames, payload, snr, seed, guard=True):
-    """the link of test_gpu_soft.py: seeded payloads, delays 1 .. 32, CFO within +-1 / S, one channel seed"""
-    api = _api()
-    c = api.Context(n_fft=n, modulation=mod, guard_bands=guard, ecc=ecc)
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    pay = torch.randint(0, 256, (n_frames, max(payload, 1)), dtype=torch.uint8, device=c.device, generator=g)[:, :payload].contiguous()
-    tx = c.encode_batch(pay)
-    d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
-    fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
-    rx = c.channel_batch(tx, snr_db=snr, seed=seed, delay=d, f_delta=fd, span=tx.shape[1] + 160)
-    return c, pay, rx, c.data_symbols(payload)
-
-
-def _data_snr(n, snr):
-    # ofdm_channel_batch scales its noise by the whole frame's pseudo-variance (see test_gpu_soft.py): the data symbols of a larger N
-    # see ~10 log10(N / 64) dB less than the channel's snr_db
-    return snr + 10.0 * np.log10(n / 64)
-
-
-def _assert_is_reference(r, want):
-    for f, (n_out, data) in want.items():
-        assert int(r["len"][f]) == n_out, f
-        assert bytes(r["bytes"][f, :n_out].cpu().numpy()) == data, f
+def _reference_decode(c, rx, r, max_symbols):
+    """chain_refs.conv_reference_decode as {frame: (status 0, out_len, bytes)}"""
+    return {f: (0, n_out, data) for f, (n_out, data) in conv_reference_decode(c, rx, r, max_symbols).items()}
 
 
 # ---------------------------------------------------------------------------------------------------------- 8. chain = stages
@@ -167,13 +130,8 @@ def test_chain_is_the_composition_of_the_stages(n, mod):
     c.synchronize()
     want = _reference_decode(c, rx, r, D)
     assert len(want) >= 5
-    _assert_is_reference(r, want)
-    c.set_tuning("soft_chunk_frames", 3)           # many chunks of the LLR workspace
-    r3 = c.decode_batch(rx, max_symbols=D)
-    c.set_tuning("soft_chunk_frames", 0)
-    for k in ("status", "len", "offset", "f_delta", "metric"):
-        assert torch.equal(r[k], r3[k]), k
-    _assert_is_reference(r3, want)
+    assert_rows_are(r, want)
+    assert_rows_are(assert_chunking_changes_nothing(c, rx, D, r), want)   # many chunks of the LLR workspace
 
 
 # ---------------------------------------------------------------------------------------------------------- 9. a frame cut short
@@ -189,13 +147,13 @@ def test_cut_frame_is_decoded_unterminated(n, mod):
     assert (r["status"] == 0).all()
     assert (r["len"] == body // 2 - 1).all()
     want = _reference_decode(c, rx, r, short)
-    _assert_is_reference(r, want)
+    assert_rows_are(r, want)
     hk = c.estimate_channel(rx, r["offset"], r["f_delta"])
     L = c.rx_llr(rx, short, first_symbol=10, offset=r["offset"], f_delta=r["f_delta"], hk=hk).cpu().numpy()
     for f in range(4):   # spelled out: the unterminated reference over the whole cut body
-        assert want[f][1] == bytes(cr.viterbi(L[f, 128:128 + 8 * body], terminated=False)[: body // 2 - 1])
+        assert want[f][2] == bytes(cr.viterbi(L[f, 128:128 + 8 * body], terminated=False)[: body // 2 - 1])
         # a clean channel: what was received of the payload is right, except possibly the last bytes next to the open end
-        assert want[f][1][: body // 2 - 8] == bytes(pay[f, : body // 2 - 8].cpu().numpy())
+        assert want[f][2][: body // 2 - 8] == bytes(pay[f, : body // 2 - 8].cpu().numpy())
 
 
 # ---------------------------------------------------------------------------------------------------------- 10. clean channel
@@ -224,35 +182,11 @@ def test_clean_channel_returns_the_payload(n):
 def test_every_decode_entry_point_in_conv_mode():
     api = _api()
     c, pay, rx, D = _link(api.ECC_CONV_K7, 64, 6, 6, 560, 16.0, 77)
-    r = c.decode_batch(rx, max_symbols=D)
-    c.synchronize()
-    host = c.decode_host(rx.cpu().numpy(), max_symbols=D, chunk_frames=2)
-    for k in ("status", "len", "offset", "f_delta", "metric"):
-        np.testing.assert_array_equal(host[k], r[k].cpu().numpy(), err_msg=k)
-    for f, n_out in enumerate(r["len"].cpu().numpy()):
-        assert bytes(host["bytes"][f, :n_out]) == bytes(r["bytes"][f, :n_out].cpu().numpy()), f
-    for f in range(rx.shape[0]):
-        cap = rx[f].contiguous()
-        one = c.decode_batch(cap.reshape(1, -1), max_symbols=D)
-        lg = c.decode_long(cap, D)
-        lh = c.decode_long_host(cap.cpu().numpy(), D)
-        n_out = int(one["len"][0])
-        for res in (lg, lh):
-            assert (res["status"], res["len"], res["offset"]) == (int(one["status"][0]), n_out, int(one["offset"][0]))
-            assert bytes(np.asarray(res["bytes"].cpu() if torch.is_tensor(res["bytes"]) else res["bytes"])[:n_out]) == \
-                bytes(one["bytes"][0, :n_out].cpu().numpy())
-        if int(one["status"][0]) == 0:
-            got = api.decode(cap.cpu().numpy(), True, api.QAM64, ecc=api.ECC_CONV_K7)
-            assert got == bytes(one["bytes"][0, :n_out].cpu().numpy())
+    assert_entry_points_agree(api, c, rx, D, dict(ecc=api.ECC_CONV_K7))
     rt = api.decode(api.encode(b"a trellis of 64 states", True, api.QAM16, ecc=api.ECC_CONV_K7), True, api.QAM16, ecc=api.ECC_CONV_K7)
     assert rt == b"a trellis of 64 states"
     # a row too short for what the chain can write is refused
-    out = torch.zeros((1, 8), dtype=torch.uint8, device=c.device)
-    i32 = torch.zeros((2,), dtype=torch.int32, device=c.device)
-    need = (D * c.bytes_per_symbol - 16) // 2 - 1
-    f = c.lib.ofdm_rx_decode_batch
-    args = (c.h, rx.data_ptr(), 1, rx.shape[1], rx.shape[1], 0, D, out.data_ptr())
-    assert f(*args, need - 1, i32.data_ptr(), i32[1:].data_ptr(), None, None, None) == -1
+    assert_refuses_short_rows(c, rx, D, (D * c.bytes_per_symbol - 16) // 2 - 1)
 
 
 # ---------------------------------------------------------------------------------------------------------- 12. dispatch
@@ -280,8 +214,7 @@ CONV_POINTS = ((12.0, 9012), (14.0, 9014))
 
 
 def _payload_bit_errors(r, pay, ok):
-    diff = torch.bitwise_xor(r["bytes"][:, :pay.shape[1]], pay)[ok]
-    return int(sum(int(((diff >> b) & 1).sum()) for b in range(8)))
+    return bit_errors(torch.bitwise_xor(r["bytes"][:, :pay.shape[1]], pay)[ok])
 
 
 def test_conv_beats_soft_hamming_at_low_snr():

@@ -13,18 +13,14 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fcs_ref  # noqa: E402
+from chain_checks import assert_entry_points_agree, assert_refuses_short_rows, ofdm_api as _api  # noqa: E402
+from tools.link import delivered, generator, link_on, seeded_channel  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 FCS = fcs_ref.ECC_FCS
 FRAME_FCS, NOSYNC, UNCORRECTABLE = -6, -2, -5
 SENTINEL = 0xEE
-
-
-def _api():
-    from ofdm_amd import api
-
-    return api
 
 
 @functools.lru_cache(maxsize=None)
@@ -270,12 +266,9 @@ def test_transmit_is_the_base_frame_of_the_envelope(n_fft, mode):
     assert torch.equal(got, want), (n_fft, mode, "lens = None")
 
 
-def _channel(c, tx, snr, seed, span_extra=160):
-    n_frames = tx.shape[0]
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
-    fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
-    return c.channel_batch(tx, snr_db=snr, seed=seed, delay=d, f_delta=fd, span=tx.shape[1] + span_extra)
+def _channel(c, tx, snr, seed):
+    """frames this file built itself through the channel of tools/link.py, the delays and CFOs from a fresh generator"""
+    return seeded_channel(c, tx, snr, seed, generator(c, seed))
 
 
 @pytest.mark.parametrize("n_fft,mode", MODE_CASES)
@@ -392,32 +385,19 @@ def test_every_entry_point_in_an_fcs_mode():
     rx = _channel(c, tx, 40.0, 75)
     rx[4, 1000:1100] = 0                                         # one frame loses a data symbol behind its length block: reported by every entry point
     D = c.data_symbols(p)
-    r = c.decode_batch(rx, max_symbols=D)
-    c.synchronize()
+    r, ones = assert_entry_points_agree(api, c, rx, D, dict(ecc=api.ECC_CONV_K7F_R23, fcs=True), chunk_frames=4)
     assert r["status"].tolist() == [0, 0, 0, 0, FRAME_FCS, 0] and r["len"].tolist() == [p, 0, 7, p, 0, p]
-    host = c.decode_host(rx.cpu().numpy(), max_symbols=D, chunk_frames=4)
-    for k in ("status", "len", "offset", "f_delta", "metric"):
-        np.testing.assert_array_equal(host[k], r[k].cpu().numpy(), err_msg=k)
-    for f, n_out in enumerate(r["len"].tolist()):
-        assert bytes(host["bytes"][f, :n_out]) == bytes(r["bytes"][f, :n_out].cpu().numpy()) == bytes(pay[f, :n_out]), f
-    for f in range(6):
-        cap = rx[f].contiguous()
-        one = c.decode_batch(cap.reshape(1, -1), max_symbols=D)
-        lg = c.decode_long(cap, D)
-        assert c.last_dispatch().split("+")[-1] == "k_fcs_check", c.last_dispatch()
-        lh = c.decode_long_host(cap.cpu().numpy(), D)
-        n_out = int(one["len"][0])
-        assert (int(one["status"][0]), n_out) == (int(r["status"][f]), int(r["len"][f])), f
-        for res in (lg, lh):
-            assert (res["status"], res["len"], res["offset"]) == (int(one["status"][0]), n_out, int(one["offset"][0])), f
-            assert bytes(np.asarray(res["bytes"].cpu() if torch.is_tensor(res["bytes"]) else res["bytes"])[:n_out]) == bytes(pay[f, :n_out]), f
-        if f == 4:
-            with pytest.raises(api.DecodeError):
-                api.decode(cap.cpu().numpy(), True, api.QAM64, ecc=api.ECC_CONV_K7F_R23, fcs=True)
-            with pytest.raises(api.DecodeError):
-                api.decode_long(cap, True, api.QAM64, ecc=api.ECC_CONV_K7F_R23, max_symbols=D, fcs=True)
-        else:
-            assert api.decode(cap.cpu().numpy(), True, api.QAM64, ecc=api.ECC_CONV_K7F_R23, fcs=True) == bytes(pay[f, :n_out])
+    for f, (st, n_out, _, data) in enumerate(ones):         # every entry point agreed with the one-row decode: that is the batch's row
+        assert (st, n_out) == (int(r["status"][f]), int(r["len"][f])), f
+        assert data == bytes(r["bytes"][f, :n_out].cpu().numpy()) == bytes(pay[f, :n_out]), f
+    for f in range(6):                                           # whatever the frame holds, the check is the chain's last kernel
+        c.decode_long(rx[f].contiguous(), D)
+        assert c.last_dispatch().split("+")[-1] == "k_fcs_check", (f, c.last_dispatch())
+    cap = rx[4].contiguous()
+    with pytest.raises(api.DecodeError):                         # the damaged frame is an error, not bytes
+        api.decode(cap.cpu().numpy(), True, api.QAM64, ecc=api.ECC_CONV_K7F_R23, fcs=True)
+    with pytest.raises(api.DecodeError):
+        api.decode_long(cap, True, api.QAM64, ecc=api.ECC_CONV_K7F_R23, max_symbols=D, fcs=True)
     # a detection merged from two contexts (each searches its own lag range of one longer capture)
     g = torch.Generator(device="cuda"); g.manual_seed(11)
     long_cap = 0.002 * torch.view_as_complex(torch.randn((40000, 2), dtype=torch.float32, device=c.device, generator=g))
@@ -440,18 +420,11 @@ def test_every_entry_point_in_an_fcs_mode():
     for mode, row in ((0, body), (20, 223 * (body // 255 + 1))):
         assert _ctx(FCS + mode).decode_row_bytes(D) == row - 8 and _ctx(mode).decode_row_bytes(D) == row, mode
     assert _ctx(FCS).decode_row_bytes(1) == max(max(_ctx(FCS).bytes_per_symbol - 16, 0) - 8, 4)
-    out = torch.zeros((1, 4096), dtype=torch.uint8, device=c.device)
-    i32 = torch.zeros((2,), dtype=torch.int32, device=c.device)
-    args = (c.h, rx.data_ptr(), 1, rx.shape[1], rx.shape[1], 0, D, out.data_ptr())
-    f = c.lib.ofdm_rx_decode_batch
-    assert f(*args, need - 1, i32.data_ptr(), i32[1:].data_ptr(), None, None, None) == -1
-    assert f(*args, need, i32.data_ptr(), i32[1:].data_ptr(), None, None, None) == 0
-    c.synchronize()
-    assert i32.tolist() == [p, 0]
+    assert assert_refuses_short_rows(c, rx, D, need, accepts=True) == [p, 0]
 
 
 # ---------------------------------------------------------------------------------------------------------- 8. it earns its keep
-# The link of test_rs_outer_code_earns_its_keep (tests/test_gpu_rs.py): N = 64, 64-QAM, guard bands, payload 560, 12 dB, seed 9012.
+# The link test_rs_outer_code_earns_its_keep (tests/test_gpu_rs.py) runs, tools/link.py at N = 64, 64-QAM, guard bands, payload 560, 12 dB, seed 9012.
 # Conditions set before the run: rate 3/4 alone hands out at least 8 of 256 frames with status 0 and wrong bytes (that test's
 # commentary records 42 failed frames on this link); with the frame check no frame with status 0 differs from what was sent, and at
 # least one is reported with OFDM_FRAME_FCS.  Without any code, 64 frames: every frame is wrong with status 0; with the frame check
@@ -461,16 +434,10 @@ KEEP_SNR, KEEP_SEED = 12.0, 9012
 
 def _keep(ecc, n_frames):
     c = _ctx(ecc)
-    g = torch.Generator(device="cuda"); g.manual_seed(KEEP_SEED)
-    pay = torch.randint(0, 256, (n_frames, 560), dtype=torch.uint8, device=c.device, generator=g)
-    tx = c.encode_batch(pay)
-    d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
-    fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
-    rx = c.channel_batch(tx, snr_db=KEEP_SNR, seed=KEEP_SEED, delay=d, f_delta=fd, span=tx.shape[1] + 160)
+    pay, rx = link_on(c, n_frames, 560, KEEP_SNR, KEEP_SEED)
     r = c.decode_batch(rx, max_symbols=c.data_symbols(560))
     c.synchronize()
-    ok = r["status"] == 0
-    right = ok & (r["len"] == 560) & (r["bytes"][:, :560] == pay).all(dim=1)
+    right, ok = delivered(r, pay, 560)
     return int(right.sum()), int((ok & ~right).sum()), int((r["status"] == FRAME_FCS).sum()), int((~ok).sum())
 
 

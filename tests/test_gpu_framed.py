@@ -11,17 +11,14 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv_ref as cr  # noqa: E402
 import framed_ref as fr  # noqa: E402
-from test_gpu_conv import _data_snr, _decoder_rows  # noqa: E402
+from chain_checks import (assert_chunking_changes_nothing, assert_entry_points_agree, assert_refuses_short_rows, assert_rows_are,  # noqa: E402
+                          ofdm_api as _api)
+from chain_refs import decoder_rows as _decoder_rows  # noqa: E402
+from tools.link import data_snr as _data_snr, delivered, link as _link  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 RATES = (0, 1, 2)
-
-
-def _api():
-    from ofdm_amd import api
-
-    return api
 
 
 def _framed(rate):
@@ -141,19 +138,6 @@ def test_transmit_is_the_uncoded_frame_of_the_framed_stream(n, mod):
 
 
 # ---------------------------------------------------------------------------------------------------------- helpers of 4-12
-def _link(ecc, n, mod, n_frames, payload, snr, seed, guard=True):
-    """the link of test_gpu_conv.py: seeded payloads, delays 1 .. 32, CFO within +-1 / S, one channel seed"""
-    api = _api()
-    c = api.Context(n_fft=n, modulation=mod, guard_bands=guard, ecc=ecc)
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    pay = torch.randint(0, 256, (n_frames, max(payload, 1)), dtype=torch.uint8, device=c.device, generator=g)[:, :payload].contiguous()
-    tx = c.encode_batch(pay)
-    d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
-    fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
-    rx = c.channel_batch(tx, snr_db=snr, seed=seed, delay=d, f_delta=fd, span=tx.shape[1] + 160)
-    return c, pay, rx, c.data_symbols(payload)
-
-
 def _reference_decode(c, rx, r, max_symbols, rate):
     """per frame that reached the demodulator (status 0, or OFDM_FRAME_HEADER set behind it): (status, out_len, bytes) by the rule of
     the header -- framed_ref.decode_stream over the LLRs rx_llr returns for the frame, from LLR 128 on"""
@@ -171,13 +155,6 @@ def _reference_decode(c, rx, r, max_symbols, rate):
     return want
 
 
-def _assert_is_reference(r, want):
-    for f, (st, n_out, data) in want.items():
-        assert int(r["status"][f]) == st, f
-        assert int(r["len"][f]) == n_out, f
-        assert bytes(r["bytes"][f, :n_out].cpu().numpy()) == data, f
-
-
 # ---------------------------------------------------------------------------------------------------------- 4. chain = stages
 @pytest.mark.parametrize("n,mod", [(64, 6), (256, 4), (1024, 6), (4096, 2)])
 def test_chain_is_the_composition_of_the_stages(n, mod):
@@ -187,13 +164,8 @@ def test_chain_is_the_composition_of_the_stages(n, mod):
         c.synchronize()
         want = _reference_decode(c, rx, r, D, rate)
         assert sum(1 for st, _, _ in want.values() if st == 0) >= 5
-        _assert_is_reference(r, want)
-        c.set_tuning("soft_chunk_frames", 3)           # many chunks of the LLR workspace
-        r3 = c.decode_batch(rx, max_symbols=D)
-        c.set_tuning("soft_chunk_frames", 0)
-        for k in ("status", "len", "offset", "f_delta", "metric"):
-            assert torch.equal(r[k], r3[k]), k
-        _assert_is_reference(r3, want)
+        assert_rows_are(r, want)
+        assert_rows_are(assert_chunking_changes_nothing(c, rx, D, r), want)   # many chunks of the LLR workspace
 
 
 # ---------------------------------------------------------------------------------------------------------- 5. clean channel
@@ -230,7 +202,7 @@ def test_cut_frame_delivers_the_unterminated_prefix(n, mod):
         assert (r["status"] == 0).all() and (r["len"] == n_out).all()
         want = _reference_decode(c, rx, r, short, rate)
         assert len(want) == 4
-        _assert_is_reference(r, want)
+        assert_rows_are(r, want)
         hk = c.estimate_channel(rx, r["offset"], r["f_delta"])
         L = c.rx_llr(rx, short, first_symbol=10, offset=r["offset"], f_delta=r["f_delta"], hk=hk).cpu().numpy()
         for f in range(4):   # spelled out: the unterminated reference over what is there of the body
@@ -283,38 +255,19 @@ def test_every_decode_entry_point_in_a_framed_mode():
     api = _api()
     ecc = api.ECC_CONV_K7F_R23
     c, pay, rx, D = _link(ecc, 64, 6, 6, 560, 16.0, 77)
-    r = c.decode_batch(rx, max_symbols=D)
-    c.synchronize()
-    host = c.decode_host(rx.cpu().numpy(), max_symbols=D, chunk_frames=2)
-    for k in ("status", "len", "offset", "f_delta", "metric"):
-        np.testing.assert_array_equal(host[k], r[k].cpu().numpy(), err_msg=k)
-    for f, n_out in enumerate(r["len"].cpu().numpy()):
-        assert bytes(host["bytes"][f, :n_out]) == bytes(r["bytes"][f, :n_out].cpu().numpy()), f
+    r, ones = assert_entry_points_agree(api, c, rx, D, dict(ecc=ecc))
     assert int((r["status"] == 0).sum()) >= 4
-    for f in range(rx.shape[0]):
-        cap = rx[f].contiguous()
-        one = c.decode_batch(cap.reshape(1, -1), max_symbols=D)
-        lg = c.decode_long(cap, D)
-        lh = c.decode_long_host(cap.cpu().numpy(), D)
-        n_out = int(one["len"][0])
-        for res in (lg, lh):
-            assert (res["status"], res["len"], res["offset"]) == (int(one["status"][0]), n_out, int(one["offset"][0]))
-            assert bytes(np.asarray(res["bytes"].cpu() if torch.is_tensor(res["bytes"]) else res["bytes"])[:n_out]) == \
-                bytes(one["bytes"][0, :n_out].cpu().numpy())
-        if int(one["status"][0]) == 0:
-            got = api.decode(cap.cpu().numpy(), True, api.QAM64, ecc=ecc)
-            assert got == bytes(one["bytes"][0, :n_out].cpu().numpy())
-            assert api.decode_long(cap.cpu().numpy(), True, api.QAM64, ecc=ecc)["len"] == n_out
+    for f, (st, n_out, _, _) in enumerate(ones):
+        if st == 0:
+            assert api.decode_long(rx[f].cpu().numpy(), True, api.QAM64, ecc=ecc)["len"] == n_out
     for e in (api.ECC_CONV_K7F_R12, api.ECC_CONV_K7F_R23, api.ECC_CONV_K7F_R34):
         assert api.decode(api.encode(b"a trellis of 64 states", True, api.QAM16, ecc=e), True, api.QAM16, ecc=e) == b"a trellis of 64 states"
     # a row too short for what the chain can write is refused; decode_batch's own rows are long enough
-    out = torch.zeros((1, 8), dtype=torch.uint8, device=c.device)
-    i32 = torch.zeros((2,), dtype=torch.int32, device=c.device)
     need = fr.max_steps(8 * (D * c.bytes_per_symbol - 16 - 18), 1) // 8
     assert need <= D * c.bytes_per_symbol - 16
-    f = c.lib.ofdm_rx_decode_batch
-    args = (c.h, rx.data_ptr(), 1, rx.shape[1], rx.shape[1], 0, D, out.data_ptr())
-    assert f(*args, need - 1, i32.data_ptr(), i32[1:].data_ptr(), None, None, None) == -1
+    assert_refuses_short_rows(c, rx, D, need)
+    out = torch.zeros((1, 8), dtype=torch.uint8, device=c.device)
+    i32 = torch.zeros((2,), dtype=torch.int32, device=c.device)
     # a max_symbols whose body could exceed 2^20 steps (rate 3/4: 6 steps per body byte) is refused before anything runs
     c34 = _ctx(ecc=api.ECC_CONV_K7F_R34)
     big = (1 << 20) // 6 // c34.bytes_per_symbol + 8
@@ -352,9 +305,7 @@ def test_coded_length_block_delivers_more_frames_than_the_uncoded_header():
         c, pay, rx, D = _link(ecc, 64, 6, 1024, 560, 12.0, 9012)
         r = c.decode_batch(rx, max_symbols=D)
         c.synchronize()
-        good = (r["status"] == 0) & (r["len"] == 560)
-        good &= (r["bytes"][:, :560] == pay).all(dim=1)
-        res[ecc] = (r, pay, good)
+        res[ecc] = (r, pay, delivered(r, pay, 560)[0])
     assert torch.equal(res[api.ECC_CONV_K7][1], res[api.ECC_CONV_K7F_R12][1])          # the same payloads
     r = res[api.ECC_CONV_K7F_R12][0]
     n_old, n_new = int(res[api.ECC_CONV_K7][2].sum()), int(res[api.ECC_CONV_K7F_R12][2].sum())

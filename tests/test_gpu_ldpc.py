@@ -11,17 +11,13 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ldpc_ref as lr  # noqa: E402
 import ldpc_vectors as lv  # noqa: E402
-from test_gpu_conv import _data_snr  # noqa: E402
+from chain_checks import (assert_chunking_changes_nothing, assert_entry_points_agree, assert_refuses_short_rows, assert_rows_are,  # noqa: E402
+                          ofdm_api as _api)
+from tools.link import data_snr as _data_snr, delivered, link as _link  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1), (3, 2), (5, 3), (70, 15), (9, 33)]   # (n_frames, n_cw): odd n_cw leaves the last code word without a partner
-
-
-def _api():
-    from ofdm_amd import api
-
-    return api
 
 
 def _ctx(**kw):
@@ -160,19 +156,6 @@ def test_transmit_is_the_uncoded_frame_of_the_ldpc_stream(n, mod):
 
 
 # ---------------------------------------------------------------------------------------------------------- helpers of 3 - 7
-def _link(ecc, n, mod, n_frames, payload, snr, seed, guard=True, **kw):
-    """the link of test_gpu_conv.py: seeded payloads, delays 1 .. 32, CFO within +-1 / S, one channel seed"""
-    api = _api()
-    c = api.Context(n_fft=n, modulation=mod, guard_bands=guard, ecc=ecc, **kw)
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    pay = torch.randint(0, 256, (n_frames, max(payload, 1)), dtype=torch.uint8, device=c.device, generator=g)[:, :payload].contiguous()
-    tx = c.encode_batch(pay)
-    d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
-    fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
-    rx = c.channel_batch(tx, snr_db=snr, seed=seed, delay=d, f_delta=fd, span=tx.shape[1] + 160)
-    return c, pay, rx, c.data_symbols(payload)
-
-
 def _reference_decode(c, rx, r, max_symbols, frame_len=None):
     """per frame that reached the demodulator: (status, out_len, bytes) by the rule of the header -- ldpc_ref.receive over the LLRs
     rx_llr returns for the frame at OFDM_SOFT_LLR_SCALE with the context's channel estimate, from LLR 128 on"""
@@ -192,13 +175,6 @@ def _reference_decode(c, rx, r, max_symbols, frame_len=None):
     return want
 
 
-def _assert_is_reference(r, want):
-    for f, (st, n_out, data) in want.items():
-        assert int(r["status"][f]) == st, f
-        assert int(r["len"][f]) == n_out, f
-        assert bytes(r["bytes"][f, :n_out].cpu().numpy()) == data, f
-
-
 # ---------------------------------------------------------------------------------------------------------- 3. chain = stages
 @pytest.mark.parametrize("chest", [0, 1])
 @pytest.mark.parametrize("n,mod", [(64, 6), (256, 4), (1024, 6), (4096, 2)])
@@ -213,13 +189,8 @@ def test_chain_is_the_composition_of_the_stages(n, mod, chest):
         good = [f for f, (st, n_out, data) in want.items() if st == 0 and data == bytes(pay[f].cpu().numpy())]
         print(f"N = {n}, {mod} bits, chest {chest}, {snr} dB: statuses {r['status'].tolist()}, {len(good)} of 7 whole")
         assert len(want) == 7 and len(good) >= least
-        _assert_is_reference(r, want)
-        c.set_tuning("soft_chunk_frames", 3)                 # many chunks of the LLR workspace
-        r3 = c.decode_batch(rx, max_symbols=D)
-        c.set_tuning("soft_chunk_frames", 0)
-        for k in ("status", "len", "offset", "f_delta", "metric"):
-            assert torch.equal(r[k], r3[k]), k
-        _assert_is_reference(r3, want)
+        assert_rows_are(r, want)
+        assert_rows_are(assert_chunking_changes_nothing(c, rx, D, r), want)   # many chunks of the LLR workspace
 
 
 # ---------------------------------------------------------------------------------------------------------- 4. every status branch
@@ -267,7 +238,7 @@ def test_every_status_branch_deterministically():
             c.synchronize()
             want = _reference_decode(c, cap, r, syms)
             assert len(want) == len(names), what
-            _assert_is_reference(r, want)
+            assert_rows_are(r, want)
         st = dict(zip(names, r["status"].tolist()))
         ln = dict(zip(names, r["len"].tolist()))
         seen |= set(st.values())
@@ -291,34 +262,21 @@ def test_every_decode_entry_point(fcs):
     ecc = api.ECC_LDPC648 + (api.ECC_FCS if fcs else 0)
     c, pay, rx, D = _link(ecc, 64, 6, 6, 560, 30.0, 77)
     assert c.coded_len(560) == lr.coded_len(560 + (8 if fcs else 0))
-    r = c.decode_batch(rx, max_symbols=D)
-    c.synchronize()
+    r, ones = assert_entry_points_agree(api, c, rx, D, dict(ecc=api.ECC_LDPC648, fcs=fcs))
     assert (r["status"] == 0).all() and (r["len"] == 560).all() and torch.equal(r["bytes"][:, :560], pay)
+    for f, one in enumerate(ones):                           # every entry point agreed with the one-row decode: that is the payload
+        assert one == (0, 560, int(r["offset"][f]), bytes(pay[f].cpu().numpy())), f
+    c.decode_batch(rx, max_symbols=D)                        # (the entry points above ran since: last_dispatch is this call's again)
     if fcs:
         assert "k_ldpc_decode" in c.last_dispatch() and c.last_dispatch().endswith("k_fcs_check")
-    host = c.decode_host(rx.cpu().numpy(), max_symbols=D, chunk_frames=2)
-    for k in ("status", "len", "offset", "f_delta", "metric"):
-        np.testing.assert_array_equal(host[k], r[k].cpu().numpy(), err_msg=k)
-    assert (host["bytes"][:, :560] == pay.cpu().numpy()).all()
     for f in (0, 5):
-        cap = rx[f].contiguous()
-        for res in (c.decode_long(cap, D), c.decode_long_host(cap.cpu().numpy(), D)):
-            assert (res["status"], res["len"], res["offset"]) == (0, 560, int(r["offset"][f]))
-            assert bytes(np.asarray(res["bytes"].cpu() if torch.is_tensor(res["bytes"]) else res["bytes"])[:560]) == bytes(pay[f].cpu().numpy())
-        assert api.decode(cap.cpu().numpy(), True, api.QAM64, ecc=api.ECC_LDPC648, fcs=fcs) == bytes(pay[f].cpu().numpy())
-        assert api.decode_long(cap.cpu().numpy(), True, api.QAM64, ecc=api.ECC_LDPC648, fcs=fcs)["len"] == 560
+        assert api.decode_long(rx[f].cpu().numpy(), True, api.QAM64, ecc=api.ECC_LDPC648, fcs=fcs)["len"] == 560
     msg = b"a graph that is its own interleaver"
     assert api.decode(api.encode(msg, True, api.QAM16, ecc=api.ECC_LDPC648, fcs=fcs), True, api.QAM16, ecc=api.ECC_LDPC648, fcs=fcs) == msg
     # a row too short for what the chain can write is refused; decode_batch's own rows are long enough
     need = lr.row_bytes(D * c.bytes_per_symbol - 16) - (8 if fcs else 0)
     assert c.decode_row_bytes(D) == need
-    out = torch.zeros((1, need), dtype=torch.uint8, device=c.device)
-    i32 = torch.zeros((2,), dtype=torch.int32, device=c.device)
-    args = (c.h, rx.data_ptr(), 1, rx.shape[1], rx.shape[1], 0, D, out.data_ptr())
-    assert c.lib.ofdm_rx_decode_batch(*args, need - 1, i32.data_ptr(), i32[1:].data_ptr(), None, None, None) == -1
-    assert c.lib.ofdm_rx_decode_batch(*args, need, i32.data_ptr(), i32[1:].data_ptr(), None, None, None) == 0
-    c.synchronize()
-    assert i32.tolist() == [560, 0]
+    assert assert_refuses_short_rows(c, rx, D, need, accepts=True) == [560, 0]
 
 
 def test_damaged_frame_with_the_frame_check_is_reported_never_delivered():
@@ -386,14 +344,12 @@ def test_ldpc_against_the_framed_viterbi_mode_on_one_link():
         c, pay, rx, D = _link(ecc, 64, 6, 1024, 560, POINT_SNR_DB, 9012)
         r = c.decode_batch(rx, max_symbols=D)
         c.synchronize()
-        good = (r["status"] == 0) & (r["len"] == 560)
-        good &= (r["bytes"][:, :560] == pay).all(dim=1)
-        res[ecc] = (r, pay, good)
+        res[ecc] = (r, pay, delivered(r, pay, 560)[0])
     assert torch.equal(res[api.ECC_CONV_K7F_R12][1], res[api.ECC_LDPC648][1])          # the same payloads
     r, pay, good = res[api.ECC_LDPC648]
     n_k7f, n_ldpc = int(res[api.ECC_CONV_K7F_R12][2].sum()), int(good.sum())
-    delivered = r["status"] == 0
-    wrong = int((delivered & ~good).sum())
+    status_0 = r["status"] == 0
+    wrong = int((status_0 & ~good).sum())
     print(f"{POINT_SNR_DB} dB, 1024 frames delivered whole: CONV_K7F_R12 {n_k7f}, LDPC648 {n_ldpc}; LDPC status 0 with a wrong length or "
           f"wrong bytes: {wrong}; LDPC reported: header {int((r['status'] == api.FRAME_HEADER).sum())}, uncorrectable "
           f"{int((r['status'] == api.FRAME_UNCORRECTABLE).sum())}")

@@ -10,19 +10,16 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import rs_vectors as rv  # noqa: E402
+from chain_checks import (assert_chunking_changes_nothing, assert_entry_points_agree, assert_refuses_short_rows, assert_rows_are,  # noqa: E402
+                          ofdm_api as _api)
 from chain_refs import rs_composition as _composition  # noqa: E402
+from tools.link import data_snr as _data_snr, delivered, link as _link  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 RS_MODES = (20, 30, 31, 32)
 OLD_MODES = (0, 1, 2, 5, 10, 11, 12)
 UNCORRECTABLE = -5
-
-
-def _api():
-    from ofdm_amd import api
-
-    return api
 
 
 def _ctx(**kw):
@@ -160,30 +157,8 @@ def test_transmit_is_the_inner_frame_of_the_rs_coded_payload(n, mod):
 
 
 # ---------------------------------------------------------------------------------------------------------- 5. chain = composition
-def _link(ecc, n, mod, n_frames, payload, snr, seed, guard=True):
-    """the link of test_gpu_conv.py: seeded payloads, delays 1 .. 32, CFO within +-1 / S, one channel seed"""
-    api = _api()
-    c = api.Context(n_fft=n, modulation=mod, guard_bands=guard, ecc=ecc)
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    pay = torch.randint(0, 256, (n_frames, max(payload, 1)), dtype=torch.uint8, device=c.device, generator=g)[:, :payload].contiguous()
-    tx = c.encode_batch(pay)
-    d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
-    fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
-    rx = c.channel_batch(tx, snr_db=snr, seed=seed, delay=d, f_delta=fd, span=tx.shape[1] + 160)
-    return c, pay, rx, c.data_symbols(payload)
-
-
-def _data_snr(n, snr):
-    # ofdm_channel_batch scales its noise by the whole frame's pseudo-variance: the data symbols of a larger N see
-    # ~10 log10(N / 64) dB less than the channel's snr_db (tests/test_gpu_conv.py)
-    return snr + 10.0 * np.log10(n / 64)
-
-
 def _assert_is_composition(r, ri, want):
-    status, ln, by = r["status"].cpu().numpy(), r["len"].cpu().numpy(), r["bytes"].cpu().numpy()
-    for f, (st, n_out, data) in enumerate(want):
-        assert (int(status[f]), int(ln[f])) == (st, n_out), (f, status[f], ln[f], st, n_out)
-        assert bytes(by[f, :n_out]) == data, f
+    assert_rows_are(r, dict(enumerate(want)))
     for k in ("offset", "f_delta", "metric"):
         assert torch.equal(r[k], ri[k]), k
 
@@ -196,13 +171,7 @@ def test_chain_is_the_composition(n, ecc):
     c.synchronize()
     ri, want = _composition(c, rx, D)
     _assert_is_composition(r, ri, want)
-    c.set_tuning("soft_chunk_frames", 3)
-    try:
-        r3 = c.decode_batch(rx, max_symbols=D)
-        c.synchronize()
-    finally:
-        c.set_tuning("soft_chunk_frames", 0)
-    _assert_is_composition(r3, ri, want)
+    _assert_is_composition(assert_chunking_changes_nothing(c, rx, D, r), ri, want)
 
 
 # ---------------------------------------------------------------------------------------------------------- 6. clean channel
@@ -237,43 +206,17 @@ def test_every_decode_entry_point_in_rs_mode():
     api = _api()
     ecc = api.ECC_RS255_K7F_R34
     c, pay, rx, D = _link(ecc, 64, 6, 6, 560, 16.0, 77)
-    r = c.decode_batch(rx, max_symbols=D)
-    c.synchronize()
-    host = c.decode_host(rx.cpu().numpy(), max_symbols=D, chunk_frames=2)
-    for k in ("status", "len", "offset", "f_delta", "metric"):
-        np.testing.assert_array_equal(host[k], r[k].cpu().numpy(), err_msg=k)
-    for f, n_out in enumerate(r["len"].cpu().numpy()):
-        assert bytes(host["bytes"][f, :n_out]) == bytes(r["bytes"][f, :n_out].cpu().numpy()), f
-    for f in range(rx.shape[0]):
-        cap = rx[f].contiguous()
-        one = c.decode_batch(cap.reshape(1, -1), max_symbols=D)
-        lg = c.decode_long(cap, D)
-        lh = c.decode_long_host(cap.cpu().numpy(), D)
-        n_out = int(one["len"][0])
-        for res in (lg, lh):
-            assert (res["status"], res["len"], res["offset"]) == (int(one["status"][0]), n_out, int(one["offset"][0]))
-            assert bytes(np.asarray(res["bytes"].cpu() if torch.is_tensor(res["bytes"]) else res["bytes"])[:n_out]) == \
-                bytes(one["bytes"][0, :n_out].cpu().numpy())
-        if int(one["status"][0]) == 0:
-            got = api.decode(cap.cpu().numpy(), True, api.QAM64, ecc=ecc)
-            assert got == bytes(one["bytes"][0, :n_out].cpu().numpy())
+    assert_entry_points_agree(api, c, rx, D, dict(ecc=ecc))
     msg = b"sixteen bytes a block, and the block knows"
     rt = api.decode(api.encode(msg, True, api.QAM16, ecc=ecc), True, api.QAM16, ecc=ecc)
     assert rt == msg + bytes(2 * 223 - len(msg))               # decipher_transmission_bytes: whole blocks, the trailing zero block too
     # a row one byte too short for what the chain can write is refused
-    out = torch.zeros((1, 4096), dtype=torch.uint8, device=c.device)
-    i32 = torch.zeros((2,), dtype=torch.int32, device=c.device)
     body = D * c.bytes_per_symbol - 16
     bits = 8 * (body - 18)                                     # rate 3/4: the largest T with kept(T) <= bits (framed_ref.max_steps)
     T = 3 * (bits >> 2) + {0: 0, 1: 0, 2: 1, 3: 2}[bits & 3]
     assert c.lib.ofdm_conv_k7_kept_bits(T, 2) <= bits < c.lib.ofdm_conv_k7_kept_bits(T + 1, 2)
     need = 223 * ((T // 8) // 255 + 1)
-    assert need <= 4096
-    f = c.lib.ofdm_rx_decode_batch
-    args = (c.h, rx.data_ptr(), 1, rx.shape[1], rx.shape[1], 0, D, out.data_ptr())
-    assert f(*args, need - 1, i32.data_ptr(), i32[1:].data_ptr(), None, None, None) == -1
-    assert f(*args, need, i32.data_ptr(), i32[1:].data_ptr(), None, None, None) == 0
-    c.synchronize()
+    assert_refuses_short_rows(c, rx, D, need, accepts=True)     # ... and one of `need` bytes is taken
 
 
 # ---------------------------------------------------------------------------------------------------------- 9. dispatch
@@ -309,9 +252,8 @@ def _not_delivered(api, ecc, snr):
     c, pay, rx, D = _link(ecc, 64, 6, 256, 560, snr, KEEP_SEED)
     r = c.decode_batch(rx, max_symbols=D)
     c.synchronize()
-    want_len = 560 if ecc < 20 else 223 * 4
-    right = (r["status"] == 0) & (r["len"] == want_len) & (r["bytes"][:, :560] == pay).all(dim=1)
-    return pay, int((~right).sum()), int(((r["status"] == 0) & ~right).sum())
+    right, ok = delivered(r, pay, 560 if ecc < 20 else 223 * 4)
+    return pay, int((~right).sum()), int((ok & ~right).sum())
 
 
 def test_rs_outer_code_earns_its_keep():

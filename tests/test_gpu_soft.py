@@ -9,17 +9,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import soft_ref as sr  # noqa: E402
+from chain_checks import assert_chunking_changes_nothing, assert_entry_points_agree, ofdm_api as _api  # noqa: E402
 from chain_refs import soft_reference_decode  # noqa: E402
+from tools.link import bit_errors, data_snr as _data_snr, link_on  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 MODS = (1, 2, 4, 6, 8)
-
-
-def _api():
-    from ofdm_amd import api
-
-    return api
 
 
 def _data_bins(orc, n, guard):
@@ -127,32 +123,12 @@ def test_transmit_is_unchanged():
 
 # ---------------------------------------------------------------------------------------------------------- helpers of 4-8
 def _link(n, mod, n_frames, payload, snr, seed, guard=True):
+    """a hard and a soft Hamming context over ONE capture (the frames on the wire are the same): the seeded link of tools/link.py"""
     api = _api()
     h = api.Context(n_fft=n, modulation=mod, guard_bands=guard, ecc=api.ECC_HAMMING74)
     s = api.Context(n_fft=n, modulation=mod, guard_bands=guard, ecc=api.ECC_HAMMING74_SOFT)
-    g = torch.Generator(device="cuda"); g.manual_seed(seed)
-    pay = torch.randint(0, 256, (n_frames, payload), dtype=torch.uint8, device=h.device, generator=g)
-    tx = h.encode_batch(pay)
-    d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=h.device, generator=g)
-    fd = (torch.rand((n_frames,), dtype=torch.float64, device=h.device, generator=g) - 0.5) * (2.0 / h.S)
-    rx = h.channel_batch(tx, snr_db=snr, seed=seed, delay=d, f_delta=fd, span=tx.shape[1] + 160)
+    pay, rx = link_on(h, n_frames, payload, snr, seed)
     return h, s, pay, rx, h.data_symbols(payload)
-
-
-def _data_snr(n, snr):
-    # ofdm_channel_batch scales its noise by the whole frame's pseudo-variance, which the real-valued locking block dominates more the
-    # larger N is (data samples ~ 1/sqrt(N)): the data symbols see ~10 log10(N / 64) dB less than the channel's snr_db
-    return snr + 10.0 * np.log10(n / 64)
-
-
-def _same_bytes(a, b):
-    # bytes past out_len are not written: compare each frame's out_len bytes
-    la, lb = a["len"].cpu().numpy(), np.asarray(b["len"].cpu() if torch.is_tensor(b["len"]) else b["len"])
-    np.testing.assert_array_equal(la, lb)
-    ba = a["bytes"].cpu().numpy()
-    bb = b["bytes"].cpu().numpy() if torch.is_tensor(b["bytes"]) else b["bytes"]
-    for f, n in enumerate(la):
-        assert bytes(ba[f, :n]) == bytes(bb[f, :n]), f
 
 
 def _same(a, b, keys=("status", "len", "offset", "f_delta", "metric")):
@@ -197,11 +173,7 @@ def test_chain_is_the_composition_of_the_stages(n, mod):
         want = s.hamming74_decode_soft(L[f, 128:128 + n_out // 4 * 56].contiguous())
         assert torch.equal(r["bytes"][f, :n_out], want), f
         assert (n_out, bytes(want.cpu().numpy())) == ref[f], f
-    s.set_tuning("soft_chunk_frames", 3)           # many chunks of the LLR workspace
-    r3 = s.decode_batch(rx, max_symbols=D)
-    s.set_tuning("soft_chunk_frames", 0)
-    _same(r, r3)
-    _same_bytes(r, r3)
+    assert_chunking_changes_nothing(s, rx, D, r)   # many chunks of the LLR workspace: the same rows, byte for byte
 
 
 # ---------------------------------------------------------------------------------------------------------- 6. soft beats hard
@@ -213,8 +185,7 @@ SOFT_POINTS = ((12.0, 64), (14.0, 64), (16.0, 64))
 
 def _payload_bit_errors(r, pay):
     ok = (r["status"] == 0) & (r["len"] == (pay.shape[1] + 3) // 4 * 4)
-    diff = torch.bitwise_xor(r["bytes"][:, :pay.shape[1]], pay)[ok]
-    return int(sum(int(((diff >> b) & 1).sum()) for b in range(8))), ok
+    return bit_errors(torch.bitwise_xor(r["bytes"][:, :pay.shape[1]], pay)[ok]), ok
 
 
 def test_soft_beats_hard_at_low_snr():
@@ -235,24 +206,8 @@ def test_soft_beats_hard_at_low_snr():
 def test_every_decode_entry_point_in_soft_mode():
     api = _api()
     h, s, pay, rx, D = _link(64, 6, 6, 560, 16.0, 77)
-    r = s.decode_batch(rx, max_symbols=D)
-    s.synchronize()
-    host = s.decode_host(rx.cpu().numpy(), max_symbols=D, chunk_frames=2)
-    for k in ("status", "len", "offset", "f_delta", "metric"):
-        np.testing.assert_array_equal(host[k], r[k].cpu().numpy(), err_msg=k)
-    _same_bytes(r, host)
-    for f in range(rx.shape[0]):
-        cap = rx[f].contiguous()
-        one = s.decode_batch(cap.reshape(1, -1), max_symbols=D)
-        lg = s.decode_long(cap, D)
-        lh = s.decode_long_host(cap.cpu().numpy(), D)
-        n_out = int(one["len"][0])
-        for res in (lg, lh):
-            assert (res["status"], res["len"], res["offset"]) == (int(one["status"][0]), n_out, int(one["offset"][0]))
-            assert bytes(np.asarray(res["bytes"].cpu() if torch.is_tensor(res["bytes"]) else res["bytes"])[:n_out]) == \
-                bytes(one["bytes"][0, :n_out].cpu().numpy())
-        got = api.decode(cap.cpu().numpy(), True, api.QAM64, ecc=api.ECC_HAMMING74_SOFT)
-        assert got == bytes(one["bytes"][0, :n_out].cpu().numpy())
+    r, ones = assert_entry_points_agree(api, s, rx, D, dict(ecc=api.ECC_HAMMING74_SOFT))
+    assert [st for st, _, _, _ in ones] == [0] * 6                # api.decode was asked for every frame
     rt = api.decode(api.encode(b"soft decisions", True, api.QAM16, ecc=api.ECC_HAMMING74_SOFT), True, api.QAM16,
                     ecc=api.ECC_HAMMING74_SOFT)
     assert rt[:14] == b"soft decisions"

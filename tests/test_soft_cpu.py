@@ -108,6 +108,15 @@ def test_quantise_and_weights():
     np.testing.assert_array_equal(sr.quantise([0.5, 1.5, -2.5, 200.0, -1e9, np.nan, np.inf, -np.inf]), [0, 2, -2, 127, -127, 0, 0, 0])
     hk = np.array([[1.0, 2.0, 0.0, 1j]])
     np.testing.assert_allclose(sr.channel_weights(hk, np.array([0, 1, 3])), [[0.5, 2.0, 0.5]])
+    # what the seeded link of tools/link.py rests on (the GPU tests of this mode drew (n, p) directly before it): payloads drawn
+    # max(p, 1) wide and cut to p are the payloads drawn p wide, and the generator stands where it stood, for p >= 1
+    import torch
+
+    for n, p in ((7, 400), (3, 1), (64, 560)):
+        a, b = torch.Generator().manual_seed(77), torch.Generator().manual_seed(77)
+        assert torch.equal(torch.randint(0, 256, (n, p), generator=a), torch.randint(0, 256, (n, max(p, 1)), generator=b)[:, :p])
+        assert torch.equal(torch.randint(1, 33, (n,), generator=a), torch.randint(1, 33, (n,), generator=b))
+        assert torch.equal(torch.rand((n,), dtype=torch.float64, generator=a), torch.rand((n,), dtype=torch.float64, generator=b))
 
 
 def test_soft_hamming_restatement_by_hand():

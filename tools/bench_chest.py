@@ -17,7 +17,6 @@ reference: tests/chest_ref.py is the definition.
 import argparse
 import ctypes as C
 import json
-import math
 import os
 import sys
 import time
@@ -28,6 +27,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from ofdm_amd import api  # noqa: E402
+from tools.link import alternated_ms, bit_errors, capture, link_on, median, save_record  # noqa: E402
 
 BER_MODES = (("none", api.ECC_NONE), ("hamming74_soft", api.ECC_HAMMING74_SOFT), ("k7f_r12", api.ECC_CONV_K7F_R12),
              ("k7f_r23", api.ECC_CONV_K7F_R23), ("k7f_r34", api.ECC_CONV_K7F_R34), ("rs255_k7f_r34", api.ECC_RS255_K7F_R34))
@@ -40,10 +40,6 @@ def _ctx(n, ecc, chest):
     return api.Context(n_fft=n, modulation=api.QAM64, guard_bands=True, ecc=ecc, chest_mode=chest)
 
 
-def _bit_errors(diff):
-    return int(sum(int(((diff >> b) & 1).sum()) for b in range(8)))
-
-
 def ber(n, payload, snrs, n_frames, seed):
     rows = []
     for snr in snrs:
@@ -51,13 +47,7 @@ def ber(n, payload, snrs, n_frames, seed):
         for name, ecc in BER_MODES:
             ctxs = {k: _ctx(n, ecc, v) for k, v in CHEST}
             c = ctxs["ls"]
-            g = torch.Generator(device=c.device); g.manual_seed(seed + int(10 * snr))
-            pay = torch.randint(0, 256, (n_frames, payload), dtype=torch.uint8, device=c.device, generator=g)
-            tx = c.encode_batch(pay)
-            d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
-            fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
-            rx = c.channel_batch(tx, snr_db=snr, seed=seed + int(10 * snr), delay=d, f_delta=fd, span=tx.shape[1] + 160)
-            del tx
+            pay, rx = link_on(c, n_frames, payload, snr, seed + int(10 * snr))
             true_len = 223 * (payload // 223 + 1) if ecc == api.ECC_RS255_K7F_R34 else payload
             res = {k: cx.decode_batch(rx, max_symbols=c.data_symbols(payload)) for k, cx in ctxs.items()}
             torch.cuda.synchronize()
@@ -68,7 +58,7 @@ def ber(n, payload, snrs, n_frames, seed):
             for k, r in res.items():
                 diff = torch.bitwise_xor(r["bytes"][:, :payload], pay)
                 right = oks[k] & (diff == 0).all(dim=1)
-                bits = _bit_errors(diff[both])
+                bits = bit_errors(diff[both])
                 row[name][k] = {"frames_right": int(right.sum()), "frames_wrong": int(((r["status"] == 0) & ~right).sum()),
                                 "frames_reported": int((r["status"] != 0).sum()), "payload_bit_errors": bits,
                                 "ber": bits / max(1, int(both.sum()) * payload * 8)}
@@ -80,20 +70,6 @@ def ber(n, payload, snrs, n_frames, seed):
             "channel": "ofdm_channel_batch: FIR CHANNEL, delay 1..32, CFO uniform in +-1/S rad/sample", "points": rows}
 
 
-def _capture(c, g, n_frames, pay, span, seed):
-    x = torch.empty((n_frames, span), dtype=torch.complex64, device=c.device)
-    chunk = 8192
-    for lo in range(0, n_frames, chunk):
-        hi = min(lo + chunk, n_frames)
-        tx = c.encode_batch(pay[lo:hi].contiguous())
-        d = torch.randint(1, 65, (hi - lo,), device=c.device, generator=g, dtype=torch.int32)
-        fd = (torch.rand((hi - lo,), device=c.device, generator=g, dtype=torch.float64) * 1.9 - 0.95) * math.pi / c.S
-        c.channel_batch(tx, snr_db=40.0, seed=seed + lo, delay=d, f_delta=fd, out=x[lo:hi])
-        del tx
-    torch.cuda.synchronize()
-    return x
-
-
 def speed(n, n_frames, payload, reps):
     res = {"n_fft": n, "frames": n_frames, "payload": payload}
     for name, ecc in SPEED_MODES:
@@ -102,20 +78,15 @@ def speed(n, n_frames, payload, reps):
         g = torch.Generator(device=c.device); g.manual_seed(4)
         pay = torch.randint(0, 256, (n_frames, payload), dtype=torch.uint8, device=c.device, generator=g)
         D = c.data_symbols(payload)
-        x = _capture(c, g, n_frames, pay, c.frame_samples(payload) + 256, 4_000_003)
-        for cx in ctxs.values():
-            cx.decode_batch(x, max_symbols=D)   # warm-up: tables, workspaces, code objects
-        torch.cuda.synchronize()
-        times = {k: [] for k in ctxs}
-        for _ in range(reps):                   # alternated: ls, wls, ls, ...
-            for k, cx in ctxs.items():
-                cx.timer_start(); cx.decode_batch(x, max_symbols=D); times[k].append(cx.timer_stop_ms())
+        x = capture(c, g, n_frames, pay, c.frame_samples(payload) + 256, 4_000_003)
+        # warm-up of both (tables, workspaces, code objects), then alternated: ls, wls, ls, ...
+        times = alternated_ms({k: (cx, lambda cx=cx, x=x: cx.decode_batch(x, max_symbols=D)) for k, cx in ctxs.items()}, reps)
         out = {}
         for k, cx in ctxs.items():
             r = cx.decode_batch(x, max_symbols=D)
             torch.cuda.synchronize()
             ok = (r["status"] == 0) & (r["len"] == payload)
-            out[k] = {"ms_per_pass": sorted(times[k])[len(times[k]) // 2], "ms_all": times[k], "dispatch": cx.last_dispatch(),
+            out[k] = {"ms_per_pass": median(times[k]), "ms_all": times[k], "dispatch": cx.last_dispatch(),
                       "frames_exact": int(((r["bytes"][:, :payload] == pay).all(dim=1) & ok).sum())}
             del r
         out["wls_minus_ls_ms"] = out["wls"]["ms_per_pass"] - out["ls"]["ms_per_pass"]
@@ -131,12 +102,8 @@ def speed(n, n_frames, payload, reps):
     stage = {}
     for key, solve_only in (("stage_ms", 0), ("k_chest_solve_ms", 1)):
         c.set_tuning("chest_solve_only", solve_only)
-        c.chest_smooth(hk, out=out)
-        torch.cuda.synchronize()
-        t = []
-        for _ in range(reps):
-            c.timer_start(); c.chest_smooth(hk, out=out); t.append(c.timer_stop_ms())
-        stage[key] = sorted(t)[len(t) // 2]
+        t = alternated_ms({key: (c, lambda: c.chest_smooth(hk, out=out))}, reps)[key]
+        stage[key] = median(t)
         stage[key + "_all"] = t
         stage[key.replace("_ms", "_dispatch")] = c.last_dispatch()
     c.set_tuning("chest_solve_only", 0)
@@ -188,10 +155,7 @@ def main():
         rec["ber"] = [ber(64, 560, [float(v) for v in a.snrs.split(",")], a.ber_frames, 11),
                       ber(1024, 1304, [float(v) for v in a.snrs_1024.split(",")], a.ber_frames, 12)]
     print(json.dumps(rec))
-    if a.out:
-        with open(a.out + ".tmp", "w") as f:
-            json.dump(rec, f, indent=1)
-        os.replace(a.out + ".tmp", a.out)
+    save_record(rec, a.out)
 
 
 if __name__ == "__main__":

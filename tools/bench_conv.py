@@ -14,7 +14,6 @@ to profiles/conv_ber_and_speed.json (--out).
 import argparse
 import csv
 import json
-import math
 import os
 import sys
 
@@ -23,16 +22,13 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from ofdm_amd import api  # noqa: E402
+from tools.link import alternated_ms, bit_errors, capture, link_on, median, save_record  # noqa: E402
 
 MODES = (("hamming74", api.ECC_HAMMING74), ("hamming74_soft", api.ECC_HAMMING74_SOFT), ("conv_k7", api.ECC_CONV_K7))
 
 
 def _ctx(n, ecc):
     return api.Context(n_fft=n, modulation=api.QAM64, guard_bands=True, ecc=ecc)
-
-
-def _bit_errors(diff):
-    return int(sum(int(((diff >> b) & 1).sum()) for b in range(8)))
 
 
 def ber(n, payload, snrs, n_frames, seed):
@@ -44,13 +40,7 @@ def ber(n, payload, snrs, n_frames, seed):
             if name == "hamming74_soft":   # the frames on the wire are those of hamming74: the same capture
                 rx = res["hamming74"][1]
             else:
-                g = torch.Generator(device=c.device); g.manual_seed(seed + int(10 * snr))
-                pay = torch.randint(0, 256, (n_frames, payload), dtype=torch.uint8, device=c.device, generator=g)
-                tx = c.encode_batch(pay)
-                d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
-                fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
-                rx = c.channel_batch(tx, snr_db=snr, seed=seed + int(10 * snr), delay=d, f_delta=fd, span=tx.shape[1] + 160)
-                del tx
+                pay, rx = link_on(c, n_frames, payload, snr, seed + int(10 * snr))
             r = c.decode_batch(rx, max_symbols=c.data_symbols(payload))
             want = payload if name == "conv_k7" else (payload + 3) // 4 * 4
             oks[name] = (r["status"] == 0) & (r["len"] == want)
@@ -63,7 +53,7 @@ def ber(n, payload, snrs, n_frames, seed):
         for name in ctxs:
             r, _, pay = res[name]
             diff = torch.bitwise_xor(r["bytes"][:, :payload], pay)[every]
-            bits = _bit_errors(diff)
+            bits = bit_errors(diff)
             row[name] = {"payload_bit_errors": bits, "ber": bits / max(1, row["frames_compared"] * payload * 8),
                          "frames_with_errors": int((diff != 0).any(dim=1).sum())}
         rows.append(row)
@@ -71,20 +61,6 @@ def ber(n, payload, snrs, n_frames, seed):
         torch.cuda.empty_cache()
     return {"n_fft": n, "modulation": "64-QAM", "guard_bands": True, "payload": payload, "frames_per_point": n_frames, "seed": seed,
             "channel": "ofdm_channel_batch: FIR CHANNEL, delay 1..32, CFO uniform in +-1/S rad/sample", "points": rows}
-
-
-def _capture(c, g, n_frames, payload, pay, span, seed):
-    x = torch.empty((n_frames, span), dtype=torch.complex64, device=c.device)
-    chunk = 8192
-    for lo in range(0, n_frames, chunk):
-        hi = min(lo + chunk, n_frames)
-        tx = c.encode_batch(pay[lo:hi].contiguous())
-        d = torch.randint(1, 65, (hi - lo,), device=c.device, generator=g, dtype=torch.int32)
-        fd = (torch.rand((hi - lo,), device=c.device, generator=g, dtype=torch.float64) * 1.9 - 0.95) * math.pi / c.S
-        c.channel_batch(tx, snr_db=40.0, seed=seed + lo, delay=d, f_delta=fd, out=x[lo:hi])
-        del tx
-    torch.cuda.synchronize()
-    return x
 
 
 def speed(n, n_frames, payload, reps):
@@ -95,16 +71,13 @@ def speed(n, n_frames, payload, reps):
     caps = {}
     for name, c in (("hamming74_soft", s), ("conv_k7", v)):
         D = c.data_symbols(payload)
-        caps[name] = (c, _capture(c, g, n_frames, payload, pay, c.frame_samples(payload) + 256, 4_000_003), D)
-        c.decode_batch(caps[name][1], max_symbols=D)   # warm-up: workspaces grown, code objects loaded
-    times = {name: [] for name in caps}
-    for _ in range(reps):   # alternated: soft Hamming, conv, soft Hamming, conv ...
-        for name, (c, x, D) in caps.items():
-            c.timer_start(); c.decode_batch(x, max_symbols=D); times[name].append(c.timer_stop_ms())
+        caps[name] = (c, capture(c, g, n_frames, pay, c.frame_samples(payload) + 256, 4_000_003), D)
+    # warm-up of both, then alternated: soft Hamming, conv, soft Hamming, conv ...
+    times = alternated_ms({name: (c, lambda c=c, x=x, D=D: c.decode_batch(x, max_symbols=D)) for name, (c, x, D) in caps.items()}, reps)
     for name, (c, x, D) in caps.items():
         r = c.decode_batch(x, max_symbols=D)
         torch.cuda.synchronize()
-        m = sorted(times[name])[len(times[name]) // 2]
+        m = median(times[name])
         ok = (r["status"] == 0) & (r["len"] >= payload)
         res[name] = {"ms_per_pass": m, "ms_all": times[name], "data_symbols": D, "coded_len": c.coded_len(payload),
                      "slot_bytes": n_frames * x.shape[1] * 8, "dispatch": c.last_dispatch(),
@@ -168,10 +141,8 @@ def main():
         rec["ber"] = [ber(64, 560, [float(v) for v in a.snrs.split(",")], a.ber_frames, 11),
                       ber(1024, 1304, [float(v) for v in a.snrs_1024.split(",")], a.ber_frames, 12)]
     print(json.dumps(rec))
-    if not a.speed_only and a.out:
-        with open(a.out + ".tmp", "w") as f:
-            json.dump(rec, f, indent=1)
-        os.replace(a.out + ".tmp", a.out)
+    if not a.speed_only:
+        save_record(rec, a.out)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """The frame-check modes (OFDM_ECC_FCS + mode = 64 + mode) against their base modes: frames right / wrong / reported, and speed.  Prints
 one JSON record and writes it to profiles/fcs_ber_and_speed.json (--out).
 
-  link      the link of tools/bench_rs.py: N = 64, payload 560, 64-QAM, guard bands, through ofdm_channel_batch (FIR CHANNEL, delay
+  link      the seeded link of tools/link.py: N = 64, payload 560, 64-QAM, guard bands, through ofdm_channel_batch (FIR CHANNEL, delay
             1..32, CFO), the same payloads, delays, CFO and channel seed for every mode, every mode encoded by its own context.  Per
             point and mode: frames right (status 0, the true length and every byte; a base mode that pads -- Hamming -- is right when
             its first 560 bytes are), frames WRONG with status 0, frames reported (any other status; those of the check separately).
@@ -17,7 +17,6 @@ one JSON record and writes it to profiles/fcs_ber_and_speed.json (--out).
 import argparse
 import ctypes as C
 import json
-import math
 import os
 import sys
 import time
@@ -29,6 +28,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from ofdm_amd import api  # noqa: E402
+from tools.link import alternated_ms, capture, delivered, link_on, median, open_record  # noqa: E402
 
 BASE = (("none", api.ECC_NONE), ("hamming74_soft", api.ECC_HAMMING74_SOFT), ("conv_k7", api.ECC_CONV_K7), ("k7f_r12", api.ECC_CONV_K7F_R12),
         ("k7f_r23", api.ECC_CONV_K7F_R23), ("k7f_r34", api.ECC_CONV_K7F_R34))
@@ -45,20 +45,13 @@ def link(n, payload, snrs, n_frames, seed):
     for snr in snrs:
         row = {"snr_db": snr}
         for name, c in ctxs.items():
-            g = torch.Generator(device=c.device); g.manual_seed(seed + int(10 * snr))
-            pay = torch.randint(0, 256, (n_frames, payload), dtype=torch.uint8, device=c.device, generator=g)
-            tx = c.encode_batch(pay)
-            d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
-            fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
-            rx = c.channel_batch(tx, snr_db=snr, seed=seed + int(10 * snr), delay=d, f_delta=fd, span=tx.shape[1] + 160)
-            del tx
+            pay, rx = link_on(c, n_frames, payload, snr, seed + int(10 * snr))
             r = c.decode_batch(rx, max_symbols=c.data_symbols(payload))
             torch.cuda.synchronize()
             del rx
             exact = name.startswith("fcs_") or "hamming" not in name      # Hamming alone delivers floor(coded / 7) * 4 >= payload bytes
-            length_ok = (r["len"] == payload) if exact else (r["len"] >= payload)
-            right = (r["status"] == 0) & length_ok & (r["bytes"][:, :payload] == pay).all(dim=1)
-            row[name] = {"right": int(right.sum()), "wrong": int(((r["status"] == 0) & ~right).sum()), "reported": int((r["status"] != 0).sum()),
+            right, ok = delivered(r, pay, payload, exact)
+            row[name] = {"right": int(right.sum()), "wrong": int((ok & ~right).sum()), "reported": int((~ok).sum()),
                          "reported_by_the_check": int((r["status"] == api.FRAME_FCS).sum()), "frame_samples": c.frame_samples(payload)}
         rows.append(row)
         torch.cuda.empty_cache()
@@ -67,24 +60,6 @@ def link(n, payload, snrs, n_frames, seed):
             "caveat": "frames of different length see slightly different noise at equal snr_db (the noise is scaled by the whole frame's "
                       "pseudo-variance)",
             "fcs_modes_wrong_total": sum(v["wrong"] for row in rows for k, v in row.items() if k.startswith("fcs_")), "points": rows}
-
-
-def _capture(c, g, n_frames, pay, span, seed):
-    x = torch.empty((n_frames, span), dtype=torch.complex64, device=c.device)
-    chunk = 8192
-    for lo in range(0, n_frames, chunk):
-        hi = min(lo + chunk, n_frames)
-        tx = c.encode_batch(pay[lo:hi].contiguous())
-        d = torch.randint(1, 65, (hi - lo,), device=c.device, generator=g, dtype=torch.int32)
-        fd = (torch.rand((hi - lo,), device=c.device, generator=g, dtype=torch.float64) * 1.9 - 0.95) * math.pi / c.S
-        c.channel_batch(tx, snr_db=40.0, seed=seed + lo, delay=d, f_delta=fd, out=x[lo:hi])
-        del tx
-    torch.cuda.synchronize()
-    return x
-
-
-def _median(v):
-    return sorted(v)[len(v) // 2]
 
 
 def _host_crc(lib, rows, width, threads):
@@ -113,15 +88,13 @@ def kernel_alone(c, n_rows, payload, reps, threads):
         env = c.fcs_wrap(pay)
         out, out_len, ok = c.fcs_check(env)
         torch.cuda.synchronize()
-        wrap_ms, check_ms = [], []
-        for _ in range(reps):
-            c.timer_start(); c.fcs_wrap(pay); wrap_ms.append(c.timer_stop_ms())
-            c.timer_start(); out, out_len, ok = c.fcs_check(env); check_ms.append(c.timer_stop_ms())
+        ms = alternated_ms({"wrap": (c, lambda: c.fcs_wrap(pay)), "check": (c, lambda: c.fcs_check(env))}, reps)
+        wrap_ms, check_ms = ms["wrap"], ms["check"]
         dirty = env.clone()
         dirty[::2, 100] ^= 0x40
         _, dlen, dok = c.fcs_check(dirty)
         torch.cuda.synchronize()
-        res[variant] = {"k_fcs_wrap_ms": _median(wrap_ms), "k_fcs_check_ms": _median(check_ms), "wrap_ms_all": wrap_ms, "check_ms_all": check_ms,
+        res[variant] = {"k_fcs_wrap_ms": median(wrap_ms), "k_fcs_check_ms": median(check_ms), "wrap_ms_all": wrap_ms, "check_ms_all": check_ms,
                         "every_clean_row_accepted": bool((ok == 1).all()) and bool((out_len == payload).all()) and bool((out == pay).all()),
                         "every_damaged_row_rejected": bool((dok[::2] == 0).all()) and bool((dok[1::2] == 1).all()) and bool((dlen[::2] == 0).all())}
         del dirty
@@ -146,23 +119,20 @@ def speed(n, n_frames, payload, reps, threads, names):
         pay = torch.randint(0, 256, (n_frames, payload), dtype=torch.uint8, device=c.device, generator=g)
         D = c.data_symbols(payload)
         assert D == cb.data_symbols(payload + api.FCS_OVERHEAD)
-        x = _capture(c, g, n_frames, pay, c.frame_samples(payload) + 256, 4_000_003)
-        c.decode_batch(x, max_symbols=D); cb.decode_batch(x, max_symbols=D)   # warm-up: workspaces grown, code objects loaded
-        torch.cuda.synchronize()
-        t_fcs, t_base = [], []
-        for _ in range(reps):   # alternated: fcs, base, fcs, base, ...
-            c.timer_start(); c.decode_batch(x, max_symbols=D); t_fcs.append(c.timer_stop_ms())
-            cb.timer_start(); cb.decode_batch(x, max_symbols=D); t_base.append(cb.timer_stop_ms())
+        x = capture(c, g, n_frames, pay, c.frame_samples(payload) + 256, 4_000_003)
+        # warm-up of both, then alternated: fcs, base, fcs, base, ...
+        ms = alternated_ms({"fcs": (c, lambda: c.decode_batch(x, max_symbols=D)), "base": (cb, lambda: cb.decode_batch(x, max_symbols=D))}, reps)
+        t_fcs, t_base = ms["fcs"], ms["base"]
         r = c.decode_batch(x, max_symbols=D)
         torch.cuda.synchronize()
-        exact = int(((r["status"] == 0) & (r["len"] == payload) & (r["bytes"][:, :payload] == pay).all(dim=1)).sum())
-        wrong = int(((r["status"] == 0) & ~((r["len"] == payload) & (r["bytes"][:, :payload] == pay).all(dim=1))).sum())
-        res["fcs_" + name] = {"ms_per_pass": _median(t_fcs), "ms_all": t_fcs, "spread_ms": max(t_fcs) - min(t_fcs), "data_symbols": D,
+        right, ok = delivered(r, pay, payload)
+        exact, wrong = int(right.sum()), int((ok & ~right).sum())
+        res["fcs_" + name] = {"ms_per_pass": median(t_fcs), "ms_all": t_fcs, "spread_ms": max(t_fcs) - min(t_fcs), "data_symbols": D,
                               "frames_exact": exact, "frames_wrong_status_0": wrong, "dispatch": c.last_dispatch(),
-                              "minus_base_ms": _median(t_fcs) - _median(t_base), "over_base": _median(t_fcs) / _median(t_base)}
+                              "minus_base_ms": median(t_fcs) - median(t_base), "over_base": median(t_fcs) / median(t_base)}
         rb = cb.decode_batch(x, max_symbols=D)
         torch.cuda.synchronize()
-        res[name] = {"ms_per_pass": _median(t_base), "ms_all": t_base, "spread_ms": max(t_base) - min(t_base),
+        res[name] = {"ms_per_pass": median(t_base), "ms_all": t_base, "spread_ms": max(t_base) - min(t_base),
                      "frames_status_0": int((rb["status"] == 0).sum()), "dispatch": cb.last_dispatch()}
         c0 = c0 or c
         del x, r, rb, pay
@@ -188,13 +158,7 @@ def main():
     a = ap.parse_args()
     rec = {"tool": "tools/bench_fcs.py", "llr_scale": api.SOFT_LLR_SCALE, "device": torch.cuda.get_device_name(0),
            "definition": "tests/fcs_ref.py over zlib.crc32: E(payload) = [u32 LE p] ++ payload ++ [u32 LE crc32 of both]"}
-
-    def save():   # after every block: a long run that is cut short keeps what it has
-        if a.out:
-            with open(a.out + ".tmp", "w") as f:
-                json.dump(rec, f, indent=1)
-            os.replace(a.out + ".tmp", a.out)
-
+    rec, save = open_record(rec, a.out)   # saved after every block: a long run that is cut short keeps what it has
     if not a.speed_only:
         rec["link"] = link(64, 560, [float(v) for v in a.snrs.split(",")], a.frames, 11)
         save()

@@ -16,7 +16,6 @@ reference: tests/framed_ref.py is the definition.
 """
 import argparse
 import json
-import math
 import os
 import sys
 
@@ -25,6 +24,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from ofdm_amd import api  # noqa: E402
+from tools.link import alternated_ms, bit_errors, capture, link_on, median, save_record  # noqa: E402
 
 MODES = (("conv_k7", api.ECC_CONV_K7), ("k7f_r12", api.ECC_CONV_K7F_R12), ("k7f_r23", api.ECC_CONV_K7F_R23),
          ("k7f_r34", api.ECC_CONV_K7F_R34))
@@ -32,10 +32,6 @@ MODES = (("conv_k7", api.ECC_CONV_K7), ("k7f_r12", api.ECC_CONV_K7F_R12), ("k7f_
 
 def _ctx(n, ecc):
     return api.Context(n_fft=n, modulation=api.QAM64, guard_bands=True, ecc=ecc)
-
-
-def _bit_errors(diff):
-    return int(sum(int(((diff >> b) & 1).sum()) for b in range(8)))
 
 
 def air_time(n, payload):
@@ -52,13 +48,7 @@ def ber(n, payload, snrs, n_frames, seed):
     for snr in snrs:
         row, res, oks = {"snr_db": snr}, {}, {}
         for name, c in ctxs.items():
-            g = torch.Generator(device=c.device); g.manual_seed(seed + int(10 * snr))
-            pay = torch.randint(0, 256, (n_frames, payload), dtype=torch.uint8, device=c.device, generator=g)
-            tx = c.encode_batch(pay)
-            d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
-            fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
-            rx = c.channel_batch(tx, snr_db=snr, seed=seed + int(10 * snr), delay=d, f_delta=fd, span=tx.shape[1] + 160)
-            del tx
+            pay, rx = link_on(c, n_frames, payload, snr, seed + int(10 * snr))
             r = c.decode_batch(rx, max_symbols=c.data_symbols(payload))
             torch.cuda.synchronize()
             del rx
@@ -69,7 +59,7 @@ def ber(n, payload, snrs, n_frames, seed):
         for name in ctxs:
             r, pay = res[name]
             diff = torch.bitwise_xor(r["bytes"][:, :payload], pay)
-            bits = _bit_errors(diff[every])
+            bits = bit_errors(diff[every])
             whole = oks[name] & (diff == 0).all(dim=1)
             row[name] = {"frames_ok": int(oks[name].sum()), "frames_delivered_whole": int(whole.sum()),
                          "invalid_length_blocks": int((r["status"] == api.FRAME_HEADER).sum()),
@@ -85,20 +75,6 @@ def ber(n, payload, snrs, n_frames, seed):
                       "pseudo-variance)", "air_time": air_time(n, payload), "points": rows}
 
 
-def _capture(c, g, n_frames, pay, span, seed):
-    x = torch.empty((n_frames, span), dtype=torch.complex64, device=c.device)
-    chunk = 8192
-    for lo in range(0, n_frames, chunk):
-        hi = min(lo + chunk, n_frames)
-        tx = c.encode_batch(pay[lo:hi].contiguous())
-        d = torch.randint(1, 65, (hi - lo,), device=c.device, generator=g, dtype=torch.int32)
-        fd = (torch.rand((hi - lo,), device=c.device, generator=g, dtype=torch.float64) * 1.9 - 0.95) * math.pi / c.S
-        c.channel_batch(tx, snr_db=40.0, seed=seed + lo, delay=d, f_delta=fd, out=x[lo:hi])
-        del tx
-    torch.cuda.synchronize()
-    return x
-
-
 def speed(n, n_frames, payload, reps):
     res = {"n_fft": n, "frames": n_frames, "payload": payload}
     caps = {}
@@ -107,17 +83,13 @@ def speed(n, n_frames, payload, reps):
         g = torch.Generator(device=c.device); g.manual_seed(4)
         pay = torch.randint(0, 256, (n_frames, payload), dtype=torch.uint8, device=c.device, generator=g)
         D = c.data_symbols(payload)
-        caps[name] = (c, _capture(c, g, n_frames, pay, c.frame_samples(payload) + 256, 4_000_003), D, pay)
-        c.decode_batch(caps[name][1], max_symbols=D)   # warm-up: workspaces grown, code objects loaded
-    torch.cuda.synchronize()
-    times = {name: [] for name in caps}
-    for _ in range(reps):   # alternated: conv_k7, k7f_r12, k7f_r23, k7f_r34, conv_k7 ...
-        for name, (c, x, D, _) in caps.items():
-            c.timer_start(); c.decode_batch(x, max_symbols=D); times[name].append(c.timer_stop_ms())
+        caps[name] = (c, capture(c, g, n_frames, pay, c.frame_samples(payload) + 256, 4_000_003), D, pay)
+    # warm-up of all, then alternated: conv_k7, k7f_r12, k7f_r23, k7f_r34, conv_k7 ...
+    times = alternated_ms({name: (c, lambda c=c, x=x, D=D: c.decode_batch(x, max_symbols=D)) for name, (c, x, D, _) in caps.items()}, reps)
     for name, (c, x, D, pay) in caps.items():
         r = c.decode_batch(x, max_symbols=D)
         torch.cuda.synchronize()
-        m = sorted(times[name])[len(times[name]) // 2]
+        m = median(times[name])
         ok = (r["status"] == 0) & (r["len"] == payload)
         res[name] = {"ms_per_pass": m, "ms_all": times[name], "data_symbols": D, "coded_len": c.coded_len(payload),
                      "frame_samples": c.frame_samples(payload), "dispatch": c.last_dispatch(),
@@ -154,10 +126,7 @@ def main():
         rec["ber"] = [ber(64, 560, [float(v) for v in a.snrs.split(",")], a.ber_frames, 11),
                       ber(1024, 1304, [float(v) for v in a.snrs_1024.split(",")], a.ber_frames, 12)]
     print(json.dumps(rec))
-    if a.out:
-        with open(a.out + ".tmp", "w") as f:
-            json.dump(rec, f, indent=1)
-        os.replace(a.out + ".tmp", a.out)
+    save_record(rec, a.out)
 
 
 if __name__ == "__main__":

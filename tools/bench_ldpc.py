@@ -11,7 +11,7 @@ tests/ldpc_ref.py is the definition.
   kernel   k_ldpc_decode alone (Context.ldpc_decode) on rows of 15 code words, clean LLRs (+-32) and the LLRs of the N = 64 link at the
            middle of its sweep, max_iter 5, 10, 20 and 40: ms, average iterations of the converged code words, share unconverged, edge
            updates per second (88 x 27 edges per code word and iteration run).
-  point    the link of tests/test_gpu_ldpc.py (1 024 frames, seed 9012) at the highest point of the N = 64 sweep at which K7F_R12
+  point    the link tests/test_gpu_ldpc.py runs (tools/link.py; 1 024 frames, seed 9012) at the highest point of the N = 64 sweep at which K7F_R12
            delivers fewer than 90 % of its frames whole: right / wrong / reported of K7F_R12 and LDPC648.
   host     ofdm_ldpc648_decode on 16 threads over the same noisy rows at max_iter 20, outputs compared with the device's.
 """
@@ -29,6 +29,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from ofdm_amd import api  # noqa: E402
+from tools.link import alternated_ms, delivered, link, link_on, median, open_record  # noqa: E402
 
 MODES = (("k7f_r12", api.ECC_CONV_K7F_R12), ("rs255_k7f_r34", api.ECC_RS255_K7F_R34), ("ldpc648", api.ECC_LDPC648))
 EDGES = 88 * 27
@@ -38,31 +39,18 @@ def _ctx(n, ecc):
     return api.Context(n_fft=n, modulation=api.QAM64, guard_bands=True, ecc=ecc)
 
 
-def _link(c, n_frames, payload, snr, seed):
-    g = torch.Generator(device=c.device); g.manual_seed(seed)
-    pay = torch.randint(0, 256, (n_frames, payload), dtype=torch.uint8, device=c.device, generator=g)
-    tx = c.encode_batch(pay)
-    d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
-    fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
-    rx = c.channel_batch(tx, snr_db=snr, seed=seed, delay=d, f_delta=fd, span=tx.shape[1] + 160)
-    return pay, rx
-
-
 def ber(n, payload, snrs, n_frames, seed):
     ctxs = {name: _ctx(n, ecc) for name, ecc in MODES}
     rows = []
     for snr in snrs:
         row = {"snr_db": snr}
         for name, c in ctxs.items():
-            pay, rx = _link(c, n_frames, payload, snr, seed + int(10 * snr))
+            pay, rx = link_on(c, n_frames, payload, snr, seed + int(10 * snr))
             r = c.decode_batch(rx, max_symbols=c.data_symbols(payload))
             torch.cuda.synchronize()
             del rx
-            ok = r["status"] == 0
             # RS modes deliver whole 223-byte blocks: the payload is their prefix
-            right = ok & (r["len"] >= payload) & (r["bytes"][:, :payload] == pay).all(dim=1)
-            if name == "ldpc648" or name == "k7f_r12":
-                right &= r["len"] == payload
+            right, ok = delivered(r, pay, payload, exact=name != "rs255_k7f_r34")
             row[name] = {"right": int(right.sum()), "wrong": int((ok & ~right).sum()), "reported": int((~ok).sum()),
                          "status_counts": {str(int(s)): int((r["status"] == s).sum()) for s in torch.unique(r["status"]).tolist()}}
         rows.append(row)
@@ -85,23 +73,19 @@ def speed(n, n_frames, payload, reps):
         pays = []
         for lo in range(0, n_frames, 8192):
             hi = min(lo + 8192, n_frames)
-            pay, rx = _link(c, hi - lo, payload, 40.0, 4_000_003 + lo)
+            pay, rx = link_on(c, hi - lo, payload, 40.0, 4_000_003 + lo)
             x[lo:hi] = rx
             pays.append(pay)
             del rx
         D = c.data_symbols(payload)
         caps[name] = (c, x, D, torch.cat(pays))
-        c.decode_batch(x, max_symbols=D)   # warm-up: workspaces grown, code objects loaded
-    torch.cuda.synchronize()
-    times = {name: [] for name in caps}
-    for _ in range(reps):   # alternated
-        for name, (c, x, D, _) in caps.items():
-            c.timer_start(); c.decode_batch(x, max_symbols=D); times[name].append(c.timer_stop_ms())
+    # warm-up of all, then alternated
+    times = alternated_ms({name: (c, lambda c=c, x=x, D=D: c.decode_batch(x, max_symbols=D)) for name, (c, x, D, _) in caps.items()}, reps)
     for name, (c, x, D, pay) in caps.items():
         r = c.decode_batch(x, max_symbols=D)
         torch.cuda.synchronize()
         ok = (r["status"] == 0) & (r["len"] >= payload)
-        res[name] = {"ms_per_pass": sorted(times[name])[len(times[name]) // 2], "ms_all": times[name],
+        res[name] = {"ms_per_pass": median(times[name]), "ms_all": times[name],
                      "spread_ms": max(times[name]) - min(times[name]), "data_symbols": D, "coded_len": c.coded_len(payload),
                      "frame_samples": c.frame_samples(payload), "dispatch": c.last_dispatch(),
                      "frames_exact": int(((r["bytes"][:, :payload] == pay).all(dim=1) & ok).sum())}
@@ -115,7 +99,7 @@ def _noisy_llrs(n_frames, n_cw, snr):
     """the LLRs the N = 64 link hands k_ldpc_decode at `snr`, rows of n_cw code words"""
     c = _ctx(64, api.ECC_LDPC648)
     payload = 40 * n_cw - 8
-    pay, rx = _link(c, n_frames, payload, snr, 77)
+    pay, rx = link_on(c, n_frames, payload, snr, 77)
     D = c.data_symbols(payload)
     r = c.decode_batch(rx, max_symbols=D)
     hk = c.estimate_channel(rx, r["offset"], r["f_delta"])
@@ -134,11 +118,9 @@ def kernel_alone(n_frames, n_cw, snr, reps):
     out = {"frames": int(noisy.shape[0]), "codewords_per_frame": n_cw, "noisy_snr_db": snr, "runs": []}
     for name, llr in (("clean", clean), ("noisy", noisy)):
         for max_iter in (5, 10, 20, 40):
-            c.ldpc_decode(llr, max_iter=max_iter)
-            ts = []
-            for _ in range(reps):
-                c.timer_start(); by, it = c.ldpc_decode(llr, max_iter=max_iter); ts.append(c.timer_stop_ms())
-            ms = sorted(ts)[len(ts) // 2]
+            ts = alternated_ms({"decode": (c, lambda: c.ldpc_decode(llr, max_iter=max_iter))}, reps)["decode"]
+            by, it = c.ldpc_decode(llr, max_iter=max_iter)
+            ms = median(ts)
             run = torch.where(it > 0, it, torch.full_like(it, max_iter)).sum().item()
             conv = it > 0
             out["runs"].append({"llrs": name, "max_iter": max_iter, "ms": ms, "ms_all": ts, "codewords": int(it.numel()),
@@ -170,19 +152,17 @@ def kernel_alone(n_frames, n_cw, snr, reps):
 
 
 def point(rec, n_frames=1024, payload=560, seed=9012):
-    """the link of tests/test_gpu_ldpc.py::test_ldpc_against_the_framed_viterbi_mode_on_one_link at the highest point of the N = 64
-    sweep at which K7F_R12 delivers fewer than 90 % of its frames whole"""
+    """the counts of tests/test_gpu_ldpc.py::test_ldpc_against_the_framed_viterbi_mode_on_one_link over the link that test runs
+    (tools/link.py), at the highest point of the N = 64 sweep at which K7F_R12 delivers fewer than 90 % of its frames whole"""
     sweep = rec["ber"][0]
     below = [p["snr_db"] for p in sweep["points"] if p["k7f_r12"]["right"] < 0.9 * sweep["frames_per_point"]]
     snr = max(below)
     out = {"snr_db": snr, "frames": n_frames, "payload": payload, "seed": seed}
     for name, ecc in (("k7f_r12", api.ECC_CONV_K7F_R12), ("ldpc648", api.ECC_LDPC648)):
-        c = _ctx(64, ecc)
-        pay, rx = _link(c, n_frames, payload, snr, seed)
-        r = c.decode_batch(rx, max_symbols=c.data_symbols(payload))
+        c, pay, rx, D = link(ecc, 64, api.QAM64, n_frames, payload, snr, seed)
+        r = c.decode_batch(rx, max_symbols=D)
         torch.cuda.synchronize()
-        ok = r["status"] == 0
-        right = ok & (r["len"] == payload) & (r["bytes"][:, :payload] == pay).all(dim=1)
+        right, ok = delivered(r, pay, payload)
         out[name] = {"right": int(right.sum()), "wrong": int((ok & ~right).sum()), "reported": int((~ok).sum())}
     return out
 
@@ -202,14 +182,8 @@ def main():
     blocks = a.blocks.split(",")
     rec = {"tool": "tools/bench_ldpc.py", "llr_scale": api.SOFT_LLR_SCALE, "ldpc_max_iter": api.LDPC_MAX_ITER,
            "device": torch.cuda.get_device_name(0), "definition": "parity unpinned by the reference: tests/ldpc_ref.py is the definition"}
-    if a.out and os.path.exists(a.out):   # blocks measured by an earlier call stay
-        with open(a.out) as f:
-            rec = {**json.load(f), **rec}
-    def save():   # after every block: a later block that fails does not take the earlier ones with it
-        if a.out:
-            with open(a.out + ".tmp", "w") as f:
-                json.dump(rec, f, indent=1)
-            os.replace(a.out + ".tmp", a.out)
+    # blocks measured by an earlier call stay; saved after every block: a later block that fails does not take the earlier ones with it
+    rec, save = open_record(rec, a.out, keep_earlier=True)
 
     if "ber" in blocks:
         rec["ber"] = [ber(64, 560, [float(v) for v in a.snrs.split(",")], a.ber_frames, 11),

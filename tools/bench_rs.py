@@ -1,7 +1,7 @@
 """The RS-outer frame modes (OFDM_ECC_RS255 = 20 + inner) against their inner modes: frames delivered, air time and speed.  Prints one
 JSON record and writes it to profiles/rs_ber_and_speed.json (--out).
 
-  delivery  the link of tools/bench_framed.py: N = 64, payload 560, 64-QAM, guard bands, through ofdm_channel_batch (FIR CHANNEL, delay
+  delivery  the seeded link of tools/link.py: N = 64, payload 560, 64-QAM, guard bands, through ofdm_channel_batch (FIR CHANNEL, delay
             1..32, CFO), the same payloads, delays, CFO and channel seed for every mode, every mode encoded by its own context.  Per
             point and mode: frames delivered right (status 0, the true length -- for an RS mode the payload zero-padded to whole
             blocks, trailing zero block included -- and every byte), frames delivered WRONG with status 0, frames reported
@@ -16,7 +16,6 @@ JSON record and writes it to profiles/rs_ber_and_speed.json (--out).
 import argparse
 import ctypes as C
 import json
-import math
 import os
 import sys
 import time
@@ -28,6 +27,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from ofdm_amd import api  # noqa: E402
+from tools.link import alternated_ms, capture, delivered, link, link_on, median, open_record  # noqa: E402
 
 INNER = (("none", api.ECC_NONE), ("k7f_r12", api.ECC_CONV_K7F_R12), ("k7f_r23", api.ECC_CONV_K7F_R23), ("k7f_r34", api.ECC_CONV_K7F_R34))
 
@@ -44,23 +44,16 @@ def delivery(n, payload, snrs, n_frames, seed):
     for snr in snrs:
         row = {"snr_db": snr}
         for name, c in ctxs.items():
-            g = torch.Generator(device=c.device); g.manual_seed(seed + int(10 * snr))
-            pay = torch.randint(0, 256, (n_frames, payload), dtype=torch.uint8, device=c.device, generator=g)
-            tx = c.encode_batch(pay)
-            d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
-            fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
-            rx = c.channel_batch(tx, snr_db=snr, seed=seed + int(10 * snr), delay=d, f_delta=fd, span=tx.shape[1] + 160)
-            del tx
+            pay, rx = link_on(c, n_frames, payload, snr, seed + int(10 * snr))
             r = c.decode_batch(rx, max_symbols=c.data_symbols(payload))
             torch.cuda.synchronize()
             del rx
             rs = name.startswith("rs_")
-            want_len = padded if rs else payload
-            right = (r["status"] == 0) & (r["len"] == want_len) & (r["bytes"][:, :payload] == pay).all(dim=1)
+            right, ok = delivered(r, pay, padded if rs else payload)
             if rs:
                 right &= ~(r["bytes"][:, payload:padded] != 0).any(dim=1)
             reported = (r["status"] == api.FRAME_HEADER) | (r["status"] == api.FRAME_UNCORRECTABLE)
-            row[name] = {"delivered_right": int(right.sum()), "delivered_wrong_status_0": int(((r["status"] == 0) & ~right).sum()),
+            row[name] = {"delivered_right": int(right.sum()), "delivered_wrong_status_0": int((ok & ~right).sum()),
                          "reported": int(reported.sum()), "uncorrectable": int((r["status"] == api.FRAME_UNCORRECTABLE).sum()),
                          "other_status": int(((r["status"] != 0) & ~reported).sum()), "frame_samples": c.frame_samples(payload)}
         rows.append(row)
@@ -72,44 +65,20 @@ def delivery(n, payload, snrs, n_frames, seed):
 
 
 def test_point(snrs, n_frames=256, payload=560, seed=9012):
-    """the link and the counts of tests/test_gpu_rs.py::test_rs_outer_code_earns_its_keep (N = 64, 64-QAM, guard bands): frames not
-    delivered right by rate 3/4 alone and with RS around it, and RS-mode frames delivered wrong with status 0"""
+    """the counts of tests/test_gpu_rs.py::test_rs_outer_code_earns_its_keep over the link that test runs (tools/link.py: N = 64,
+    64-QAM, guard bands): frames not delivered right by rate 3/4 alone and with RS around it, and RS-mode frames delivered wrong
+    with status 0"""
     rows = []
     for snr in snrs:
         row = {"snr_db": snr, "frames": n_frames, "payload": payload, "seed": seed}
         for name, ecc in (("k7f_r34", api.ECC_CONV_K7F_R34), ("rs_k7f_r34", api.ECC_RS255_K7F_R34)):
-            c = _ctx(64, ecc)
-            g = torch.Generator(device="cuda"); g.manual_seed(seed)
-            pay = torch.randint(0, 256, (n_frames, payload), dtype=torch.uint8, device=c.device, generator=g)
-            tx = c.encode_batch(pay)
-            d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
-            fd = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) - 0.5) * (2.0 / c.S)
-            rx = c.channel_batch(tx, snr_db=snr, seed=seed, delay=d, f_delta=fd, span=tx.shape[1] + 160)
-            r = c.decode_batch(rx, max_symbols=c.data_symbols(payload))
+            c, pay, rx, D = link(ecc, 64, api.QAM64, n_frames, payload, snr, seed)
+            r = c.decode_batch(rx, max_symbols=D)
             torch.cuda.synchronize()
-            want_len = payload if ecc < 20 else 223 * (255 * (payload // 223 + 1) // 255 + 1)
-            right = (r["status"] == 0) & (r["len"] == want_len) & (r["bytes"][:, :payload] == pay).all(dim=1)
-            row[name] = {"not_delivered_right": int((~right).sum()), "wrong_with_status_0": int(((r["status"] == 0) & ~right).sum())}
+            right, ok = delivered(r, pay, payload if ecc < 20 else 223 * (255 * (payload // 223 + 1) // 255 + 1))
+            row[name] = {"not_delivered_right": int((~right).sum()), "wrong_with_status_0": int((ok & ~right).sum())}
         rows.append(row)
     return rows
-
-
-def _capture(c, g, n_frames, pay, span, seed):
-    x = torch.empty((n_frames, span), dtype=torch.complex64, device=c.device)
-    chunk = 8192
-    for lo in range(0, n_frames, chunk):
-        hi = min(lo + chunk, n_frames)
-        tx = c.encode_batch(pay[lo:hi].contiguous())
-        d = torch.randint(1, 65, (hi - lo,), device=c.device, generator=g, dtype=torch.int32)
-        fd = (torch.rand((hi - lo,), device=c.device, generator=g, dtype=torch.float64) * 1.9 - 0.95) * math.pi / c.S
-        c.channel_batch(tx, snr_db=40.0, seed=seed + lo, delay=d, f_delta=fd, out=x[lo:hi])
-        del tx
-    torch.cuda.synchronize()
-    return x
-
-
-def _median(v):
-    return sorted(v)[len(v) // 2]
 
 
 def _host_decode(lib, rows, threads):
@@ -145,20 +114,13 @@ def kernel_alone(c, n_rows, payload, reps, threads):
     dirty.scatter_(1, idx, torch.bitwise_xor(torch.gather(dirty, 1, idx), val))
     res = {"rows": n_rows, "row_bytes": width, "blocks_per_row": blocks + 1, "host_threads": threads}
     for name, code in (("clean", clean), ("errors_8_per_block", dirty)):
-        c.rs255_decode(code)
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(reps):
-            c.timer_start(); out, out_len, fixed = c.rs255_decode(code); ms.append(c.timer_stop_ms())
+        ms = alternated_ms({"decode": (c, lambda: c.rs255_decode(code))}, reps)["decode"]
+        out, out_len, fixed = c.rs255_decode(code)
         ok = bool((out[:, :payload] == pay).all()) and bool((fixed == (0 if name == "clean" else 8 * blocks)).all())
         host_s, host_bad = _host_decode(c.lib, code.cpu().numpy(), threads)
-        res[name] = {"k_rs255_decode_ms": _median(ms), "ms_all": ms, "device_output_right": ok, "host_ms": 1e3 * host_s,
-                     "host_rows_failed": host_bad, "host_over_device": 1e3 * host_s / _median(ms)}
-    c.rs255_encode(pay)
-    ms = []
-    for _ in range(reps):
-        c.timer_start(); c.rs255_encode(pay); ms.append(c.timer_stop_ms())
-    res["k_rs255_encode_ms"] = _median(ms)
+        res[name] = {"k_rs255_decode_ms": median(ms), "ms_all": ms, "device_output_right": ok, "host_ms": 1e3 * host_s,
+                     "host_rows_failed": host_bad, "host_over_device": 1e3 * host_s / median(ms)}
+    res["k_rs255_encode_ms"] = median(alternated_ms({"encode": (c, lambda: c.rs255_encode(pay))}, reps)["encode"])
     return res
 
 
@@ -171,19 +133,15 @@ def speed(n, n_frames, payload, reps, threads):
         pay = torch.randint(0, 256, (n_frames, payload), dtype=torch.uint8, device=c.device, generator=g)
         D = c.data_symbols(payload)
         assert D == ci.data_symbols(res["inner_bytes"])
-        x = _capture(c, g, n_frames, pay, c.frame_samples(payload) + 256, 4_000_003)
+        x = capture(c, g, n_frames, pay, c.frame_samples(payload) + 256, 4_000_003)
         runs["rs_" + name], runs[name] = (c, x, D, pay), (ci, x, D, None)
-        c.decode_batch(x, max_symbols=D); ci.decode_batch(x, max_symbols=D)   # warm-up: workspaces grown, code objects loaded
-    torch.cuda.synchronize()
-    times = {name: [] for name in runs}
-    for _ in range(reps):   # alternated: rs_none, none, rs_k7f_r12, k7f_r12, ...
-        for name, (c, x, D, _) in runs.items():
-            c.timer_start(); c.decode_batch(x, max_symbols=D); times[name].append(c.timer_stop_ms())
+    # warm-up of all, then alternated: rs_none, none, rs_k7f_r12, k7f_r12, ...
+    times = alternated_ms({name: (c, lambda c=c, x=x, D=D: c.decode_batch(x, max_symbols=D)) for name, (c, x, D, _) in runs.items()}, reps)
     padded = 223 * (res["inner_bytes"] // 255 + 1)
     for name, (c, x, D, pay) in runs.items():
         r = c.decode_batch(x, max_symbols=D)
         torch.cuda.synchronize()
-        res[name] = {"ms_per_pass": _median(times[name]), "ms_all": times[name], "spread_ms": max(times[name]) - min(times[name]),
+        res[name] = {"ms_per_pass": median(times[name]), "ms_all": times[name], "spread_ms": max(times[name]) - min(times[name]),
                      "data_symbols": D, "frame_samples": c.frame_samples(payload if pay is not None else res["inner_bytes"]),
                      "dispatch": c.last_dispatch()}
         if pay is not None:
@@ -216,12 +174,7 @@ def main():
     a = ap.parse_args()
     rec = {"tool": "tools/bench_rs.py", "llr_scale": api.SOFT_LLR_SCALE, "device": torch.cuda.get_device_name(0),
            "definition": "ofdm_rs255_decode (ofdm_amd/csrc/outer_code.hip), pinned to the oracle's decipher_transmission_bytes"}
-    def save():   # after every block: a long run that is cut short keeps what it has
-        if a.out:
-            with open(a.out + ".tmp", "w") as f:
-                json.dump(rec, f, indent=1)
-            os.replace(a.out + ".tmp", a.out)
-
+    rec, save = open_record(rec, a.out)   # saved after every block: a long run that is cut short keeps what it has
     if not a.speed_only:
         rec["test_rs_outer_code_earns_its_keep"] = test_point([12.0, 11.0, 13.0])
         rec["delivery"] = delivery(64, 560, [float(v) for v in a.snrs.split(",")], a.frames, 11)

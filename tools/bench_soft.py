@@ -20,6 +20,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from ofdm_amd import api  # noqa: E402
+from tools.link import alternated_ms, bit_errors, link_on, median, save_record  # noqa: E402
 
 HBM_PEAK = 8.0e12
 
@@ -46,16 +47,11 @@ def speed(n, n_frames, payload, reps):
         del tx
     slot = n_frames * span * 8
     res = {"n_fft": n, "frames": n_frames, "payload": payload, "data_symbols": D, "slot_bytes": slot}
-    hard, soft = [], []
-    h.decode_batch(x, max_symbols=D)   # warm-up: workspaces grown, code objects loaded
-    s.decode_batch(x, max_symbols=D)
-    for _ in range(reps):   # alternated: hard, soft, hard, soft ...
-        h.timer_start(); h.decode_batch(x, max_symbols=D); hard.append(h.timer_stop_ms())
-        s.timer_start(); s.decode_batch(x, max_symbols=D); soft.append(s.timer_stop_ms())
+    times = alternated_ms({"hard": (h, lambda: h.decode_batch(x, max_symbols=D)), "soft": (s, lambda: s.decode_batch(x, max_symbols=D))}, reps)
     rh, rs = h.decode_batch(x, max_symbols=D), s.decode_batch(x, max_symbols=D)
     torch.cuda.synchronize()
-    for name, ms, r, c in (("hard", hard, rh, h), ("soft", soft, rs, s)):
-        m = sorted(ms)[len(ms) // 2]
+    for name, ms, r, c in (("hard", times["hard"], rh, h), ("soft", times["soft"], rs, s)):
+        m = median(ms)
         ok = (r["status"] == 0) & (r["len"] >= payload)
         res[name] = {"ms_per_pass": m, "ms_all": ms, "of_8tbs_on_slot_bytes": slot / (m / 1e3) / HBM_PEAK, "dispatch": c.last_dispatch(),
                      "frames_exact": int(((r["bytes"][:, :payload] == pay).all(dim=1) & ok).sum())}
@@ -76,13 +72,7 @@ def ber(n, payload, snrs, n_frames, seed, scales=()):
     D = h.data_symbols(payload)
     rows = []
     for snr in snrs:
-        g = torch.Generator(device=h.device); g.manual_seed(seed + int(10 * snr))
-        pay = torch.randint(0, 256, (n_frames, payload), dtype=torch.uint8, device=h.device, generator=g)
-        tx = h.encode_batch(pay)
-        d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=h.device, generator=g)
-        fd = (torch.rand((n_frames,), dtype=torch.float64, device=h.device, generator=g) - 0.5) * (2.0 / h.S)
-        rx = h.channel_batch(tx, snr_db=snr, seed=seed + int(10 * snr), delay=d, f_delta=fd, span=tx.shape[1] + 160)
-        del tx
+        pay, rx = link_on(h, n_frames, payload, snr, seed + int(10 * snr))
         want = (payload + 3) // 4 * 4
         row = {"snr_db": snr}
         oks = []
@@ -96,7 +86,7 @@ def ber(n, payload, snrs, n_frames, seed, scales=()):
         row["header_mismatches"] = int((oks[0] ^ oks[1]).sum())
         for name in ("hard", "soft"):
             diff = torch.bitwise_xor(row[name]["bytes"][:, :payload], pay)[both]
-            bits = int(sum(int(((diff >> b) & 1).sum()) for b in range(8)))
+            bits = bit_errors(diff)
             row[name] = {"payload_bit_errors": bits, "ber": bits / max(1, row["frames_compared"] * payload * 8),
                          "frames_with_errors": int((diff != 0).any(dim=1).sum())}
         if scales:   # the same decode through the stages (rx_llr + hamming74_decode_soft) at other LLR scales
@@ -108,7 +98,7 @@ def ber(n, payload, snrs, n_frames, seed, scales=()):
                 L = s.rx_llr(rx, D, first_symbol=10, offset=r["offset"], f_delta=r["f_delta"], hk=hk, scale=sc)
                 dec = s.hamming74_decode_soft(L[:, 128:128 + nb * 56].contiguous()).view(n_frames, -1)[:, :payload]
                 diff = torch.bitwise_xor(dec, pay)[both]
-                row["payload_bit_errors_by_scale"][str(sc)] = int(sum(int(((diff >> b) & 1).sum()) for b in range(8)))
+                row["payload_bit_errors_by_scale"][str(sc)] = bit_errors(diff)
         row.pop("_soft_raw", None)
         rows.append(row)
         del rx
@@ -167,12 +157,9 @@ def main():
         snrs = [float(v) for v in a.snrs.split(",")]
         scales = [float(v) for v in a.scales.split(",") if v]
         rec["ber"] = [ber(64, 560, snrs, a.ber_frames, 11, scales), ber(1024, 1304, [float(v) for v in a.snrs_1024.split(",")], a.ber_frames, 12)]
-    line = json.dumps(rec)
-    print(line)
-    if not a.speed_only and a.out:
-        with open(a.out + ".tmp", "w") as f:
-            json.dump(rec, f, indent=1)
-        os.replace(a.out + ".tmp", a.out)
+    print(json.dumps(rec))
+    if not a.speed_only:
+        save_record(rec, a.out)
 
 
 if __name__ == "__main__":
