@@ -195,6 +195,11 @@ __global__ __launch_bounds__(F_WG, LPT == 10 ? 2 : 3) void k_scb_fine(ScBigParam
         }
         __threadfence_block();
         __syncthreads();
+        // A window energy slid along a tile is exact to a few hundred roundings of the sums it was slid from: where the window holds
+        // nothing but zeros (behind a capture that ends inside its frame) it comes out as a residue of ~1e-15 of those sums, not as
+        // 0, and residue / residue is a "metric" of any size that once beat the true peak.  An energy below 2^-40 of the frame's
+        // total (120 dB down, a thousand times the worst residue) therefore counts as the zero it stands for: no metric defined there.
+        const double zfloor = Ep[nch] * 9.094947017729282e-13;
         // exact sums at chunk boundary c (lag c C)
         auto boundary = [&](int c) -> BSums {
             return BSums{Qr[c + cW] - Qr[c], Qi[c + cW] - Qi[c], Ep[c + cW] - Ep[c], Ep[c + cW + cL] - Ep[c + cL]};
@@ -275,7 +280,7 @@ __global__ __launch_bounds__(F_WG, LPT == 10 ? 2 : 3) void k_scb_fine(ScBigParam
                     const BSums x = j ? bs_add(base, pre[j - 1]) : base;
                     const double num = x.pr * x.pr + x.pi * x.pi, den = x.e * x.r;
                     const long long lag = d0 + a0 + j;
-                    if (lag >= lo && lag <= hi && den > 0.0 && num >= thr * den) mine = a0 + j;
+                    if (lag >= lo && lag <= hi && x.e > zfloor && x.r > zfloor && num >= thr * den) mine = a0 + j;
                 }
 #pragma unroll
                 for (int sft = 32; sft >= 1; sft >>= 1) { const int o = __shfl_xor(mine, sft, 64); mine = o < mine ? o : mine; }
@@ -293,7 +298,7 @@ __global__ __launch_bounds__(F_WG, LPT == 10 ? 2 : 3) void k_scb_fine(ScBigParam
                 const BSums x = j ? bs_add(base, pre[j - 1]) : base;
                 const double num = x.pr * x.pr + x.pi * x.pi, den = x.e * x.r;
                 const long long lag = d0 + a0 + j;
-                if (lag >= lo && lag <= hi && den > 0.0) mineb = bc_pick(mineb, BCand{num, den, x.pr, x.pi, (int)lag});
+                if (lag >= lo && lag <= hi && x.e > zfloor && x.r > zfloor) mineb = bc_pick(mineb, BCand{num, den, x.pr, x.pi, (int)lag});
             }
 #pragma unroll
             for (int sft = 32; sft >= 1; sft >>= 1) mineb = bc_pick(mineb, bc_shfl_xor(mineb, sft));
@@ -338,7 +343,7 @@ __global__ __launch_bounds__(F_WG, LPT == 10 ? 2 : 3) void k_scb_fine(ScBigParam
             for (int cb = (int)((d1 + C - 1) / C) + tid; (long long)cb * C <= dend; cb += F_WG) {
                 const BSums x = boundary(cb);
                 const double num = x.pr * x.pr + x.pi * x.pi, den = x.e * x.r;
-                if (den > 0.0) bb = bc_pick(bb, BCand{num, den, x.pr, x.pi, cb * C});
+                if (x.e > zfloor && x.r > zfloor) bb = bc_pick(bb, BCand{num, den, x.pr, x.pi, cb * C});
             }
 #pragma unroll
             for (int sft = 32; sft >= 1; sft >>= 1) bb = bc_pick(bb, bc_shfl_xor(bb, sft));

@@ -34,6 +34,16 @@ def stage():
     return _ctx(0)                                               # the stage entry points work on any context, whatever its ecc
 
 
+@pytest.fixture(scope="module")
+def bitserial():
+    """a context of its own whose k_fcs_wrap / k_fcs_check reduce every lane's chunk bit by bit in registers (laboratory key
+    fcs_bitserial) instead of through the slice-by-4 tables in LDS"""
+    api = _api()
+    c = api.Context(n_fft=64, modulation=api.QAM64, guard_bands=True, tuning={"fcs_bitserial": 1})
+    assert c.get_tuning("fcs_bitserial") == 1
+    return c
+
+
 def _embed(c, rows: np.ndarray, slack: int = 9):
     """the rows on the device at an ODD base address, the row stride `slack` bytes larger than the row, 0xEE everywhere else:
     (view [n, nb], the whole allocation)"""
@@ -76,7 +86,10 @@ def _wrap_case(c, data: np.ndarray, lens):
     return host
 
 
-@pytest.mark.parametrize("n_bytes", [0, 1, 2, 3, 4, 5, 7, 8, 59, 60, 61, 63, 64, 65, 251, 252, 253, 255, 256, 257, 560, 1304, 4099])
+WRAP_SIZES = [0, 1, 2, 3, 4, 5, 7, 8, 59, 60, 61, 63, 64, 65, 251, 252, 253, 255, 256, 257, 560, 1304, 4099]
+
+
+@pytest.mark.parametrize("n_bytes", WRAP_SIZES)
 def test_wrap_is_zlib(stage, n_bytes):
     rng = np.random.default_rng(1000 + n_bytes)
     data = rng.integers(0, 256, (7, n_bytes), dtype=np.uint8)
@@ -225,6 +238,19 @@ def test_stage_argument_checks(stage):
     assert check(c.h, p, 0, 308, None, 308, mark.data_ptr(), 300, None, None) == 0
     c.synchronize()
     assert bool((mark == 0xC3).all())
+
+
+# ---------------------------------------------------------------------------------------------------------- 3b. the other reduction
+# the same tests, unchanged, on the bit-serial kernels k_fcs_wrap<true> / k_fcs_check<true>: zlib.crc32 is the reference of both
+@pytest.mark.parametrize("n_bytes", WRAP_SIZES)
+def test_wrap_is_zlib_bitserial(bitserial, n_bytes):
+    test_wrap_is_zlib(bitserial, n_bytes)
+
+
+@pytest.mark.parametrize("test", [test_wrap_long_rows, test_wrap_many_rows_per_wavefront, test_check_is_the_rule, test_stage_argument_checks],
+                         ids=lambda t: t.__name__[5:])
+def test_stage_bitserial(bitserial, test):
+    test(bitserial)
 
 
 # ---------------------------------------------------------------------------------------------------------- 4 + 5. the frame modes

@@ -5,7 +5,8 @@ indices; <= 1e-5 norm-relative on complex FFT / correlation / channel samples (f
 import numpy as np
 import pytest
 
-from util import assert_bytes_match, fc32, make_symbols, make_symbols_np, rel_err, through_channel, wide
+from util import (SC80_SEARCHES, assert_bytes_match, fc32, long_period_captures, loud_payload, make_capture, make_symbols,
+                  make_symbols_np, rel_err, sc80_corner_captures, through_channel, wide)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5  # north_star tolerance for complex samples
@@ -386,11 +387,6 @@ def test_rx_demod_equalised_fast_kernels(api, orc, n, mod, guard):
 
 
 # ------------------------------------------------------------------ EXT-3: Schmidl-Cox, a14, a15, a16
-def make_capture(orc, rng, mod, guard, payload, span, delay, fd, snr_db=30.0, n_fft=64):
-    tx = orc.encode(payload, guard, mod, n_fft)
-    return through_channel(orc, rng, tx, span, delay, fd, snr_db), tx
-
-
 # N = 64 searches with W = 3 L go through k_sc80 (every lag on f64 prefix differences, kernels_sc80.hip); the round-4 f32 filter pair
 # (k_sc_cf) stays in the library for other windows, for the one-pass receive kernel and as the A/B: both are held to the oracle
 SC_DETECTORS = [pytest.param({}, id="k_sc80"), pytest.param({"no_sc80": 1}, id="k_sc_cf")]
@@ -512,15 +508,11 @@ def test_sc80_streaming_detector_corner_cases(api, orc):
     last sample a lag reads), thresholds that are not a power of two (the crossing filter's fused compare), all-zero lead-ins
     (exact prefix differences: no slow list), and captures whose dynamic range defeats prefix differences -- an exact-zero gap
     behind a burst, a packet 75 dB below a burst -- which must come back from the slow list with the oracle's answer."""
-    rng = np.random.default_rng(80)
-    span = 2176
-    tx = orc.encode(bytes(rng.integers(0, 256, 560, dtype=np.uint8)), True, orc.QAM64)
-    ordinary = [through_channel(orc, rng, tx, span, int(d), float(fd), 30.0) for d, fd in
-                zip(rng.integers(1, 80, 13), (rng.random(13) * 1.9 - 0.95) * np.pi / 80)]
+    ordinary, dynamic = sc80_corner_captures(orc)
     # (a) ragged batches, capped grid, bounded and short searches, other thresholds
     for nfr in (1, 2, 3, 5, 13):
         caps = np.stack(ordinary[:nfr])
-        for thr, n_lags, flen in ((0.5, 0, span), (0.37, 0, span), (0.81, 300, span), (0.5, 0, 400), (0.5, 0, 322), (0.5, 45, 2000)):
+        for thr, n_lags, flen in SC80_SEARCHES:
             ctx = api.Context(modulation=api.QAM64, guard_bands=True, sync_threshold=thr, tuning={"grid_cap": 2})
             d_hat, f_delta, metric = (host(t) for t in ctx.sc_correlate(dev(ctx, caps), frame_len=flen, n_lags=n_lags))
             assert ctx.last_dispatch().startswith("k_sc80"), ctx.last_dispatch()
@@ -530,12 +522,7 @@ def test_sc80_streaming_detector_corner_cases(api, orc):
                 if wd >= 0:
                     assert abs(f_delta[f] - wfd) <= 1e-9 and abs(metric[f] - wm) <= 1e-6, (nfr, thr, n_lags, flen, f)
     # (b) dynamic range
-    clean = np.zeros(span, complex); clean[500:500 + 1600] = tx[:1600]            # zeros, then a noiseless frame: exact, stays on the fast path
-    lead = fc32(clean)
-    gap = clean.copy(); gap[3:40] += 30.0 * (rng.standard_normal(37) + 1j * rng.standard_normal(37))      # burst, EXACT zeros, frame
-    quiet = 1e-3 * wide(ordinary[0]); quiet[5:25] += 3.0 * (rng.standard_normal(20) + 1j * rng.standard_normal(20))     # burst, then a packet 75 dB down
-    hot = wide(ordinary[1]).copy(); hot[2:14] += 40.0 * (rng.standard_normal(12) + 1j * rng.standard_normal(12))       # burst 50 dB up: trusted
-    caps = np.stack([lead, fc32(gap), fc32(quiet), fc32(hot), ordinary[2]])
+    caps, lead = dynamic, dynamic[0]
     ctx = api.Context(modulation=api.QAM64, guard_bands=True)
     d_hat, f_delta, metric = (host(t) for t in ctx.sc_correlate(dev(ctx, caps[:1])))
     assert ctx.get_tuning("stat_sc_slow_frames") == 0 and d_hat[0] == orc.sc_sync(wide(lead), 80, 3, 0, 0.5)[0] >= 0
@@ -866,34 +853,6 @@ def test_tx_encode_mid_frames(api, orc, n, mod, guard, nbytes):
         tail = frames[f, want.size:]
         assert tail.size % S == 0 and (tail.size == 0 or np.abs(tail).max() <= np.abs(frames[f, :want.size]).max())
         assert abs(max(frames[f].real.max(), frames[f].imag.max()) - 1.0) < 1e-6
-
-def loud_payload(orc, n, mod, nbytes, sym=1, seed=0):
-    """A payload whose data symbol `sym` has a time sample far above the header blocks' full scale (without guard bands every bin is a
-    data carrier: each carrier gets the constellation point whose contribution to sample 1 of the symbol is largest)."""
-    rng = np.random.default_rng(seed)
-    sym_bytes = n * mod // 8
-    pts = []
-    for pat in range(1 << mod):                       # the point of every bit pattern (LSB-first stream bits)
-        bits = np.array([(pat >> b) & 1 for b in range(8)], np.uint8)
-        pts.append(orc.modulate(bytes(np.packbits(bits, bitorder="little")), mod)[0])
-    pts = np.array(pts)
-    freq, used = orc.encode_block(np.arange(1, n + 1, dtype=np.float64) + 0j, n, False)
-    assert used == n
-    pos_of = {int(round(freq[p].real)) - 1: p for p in range(n)}     # where stream point i lands in the frequency vector
-    resp = np.empty(n, np.complex128)
-    for p in range(n):                                # what a unit at bin position p contributes to time sample 1
-        e = np.zeros(n, np.complex128)
-        e[p] = 1.0
-        resp[p] = orc.prefix_block(e)[n // 4 + 1]
-    pat = np.array([int(np.argmax((pts * resp[pos_of[i]]).real)) for i in range(n)])
-    bits = ((pat[:, None] >> np.arange(mod)[None, :]) & 1).astype(np.uint8).reshape(-1)
-    loud = np.packbits(bits, bitorder="little")
-    pay = rng.integers(0, 256, nbytes, dtype=np.uint8)
-    lo = sym * sym_bytes - 16
-    assert loud.size == sym_bytes and lo >= 0 and lo + sym_bytes <= nbytes
-    pay[lo: lo + sym_bytes] = loud
-    return pay
-
 
 @pytest.mark.parametrize("n,mod,nsym", [(64, 2, 60), (128, 2, 20), (256, 6, 16), (1024, 4, 5), (4096, 2, 3)])
 def test_tx_encode_frames_louder_than_their_header(api, orc, n, mod, nsym):
@@ -1237,6 +1196,8 @@ def test_sc_stream_detector_against_the_oracle(api, orc, n, reps):
         fast = disp.startswith("k_sc_cf<")
         assert fast or disp.startswith("k_sc_stream") == aligned, (disp, span)
         assert not fast or W + 20 <= 320, (disp, W)
+        # a period of one or two 640-sample tiles (N = 512, 1024) keeps the partner micro-chunk in the producer's registers: another instantiation
+        assert fast or disp == ("k_sc_stream<regs>" if n in (512, 1024) else "k_sc_stream"), (disp, n)
         for f in range(caps.shape[0]):
             wd, wp, wm, wfd = orc.sc_sync(wide(caps[f]), L=S, window_reps=reps, n_lags=lags, threshold=0.5)
             assert d_hat[f] == wd, (n, reps, lags, f, int(d_hat[f]), wd)
@@ -1270,16 +1231,7 @@ def test_sc_correlate_and_decode_long_periods(api, orc, n, mod, nbytes, two_pass
     flen = ctx.frame_samples(nbytes)
     span = (flen + 3 * S // 2) // 2 * 2
     nf = 5 if n <= 1024 else 3
-    caps = []
-    for f in range(nf):
-        tx = orc.encode(bytes(rng.integers(0, 256, nbytes, dtype=np.uint8)), True, mod, n)
-        d = int(rng.integers(1, S))
-        fd = (rng.random() * 1.8 - 0.9) * np.pi / S
-        caps.append(through_channel(orc, rng, tx, span, d, fd, 32.0, data_start=10 * S))
-    caps.append(fc32(0.05 * (rng.standard_normal(span) + 1j * rng.standard_normal(span))))     # noise only
-    cut = caps[0].copy(); cut[int(3.5 * S):] = 0                                               # ends inside the preamble
-    caps.append(cut)
-    caps = np.stack(caps)
+    caps = long_period_captures(orc, rng, n, mod, nbytes, nf, span)
     for lags in (0, 2 * S):
         xd = dev(ctx, caps)
         d_hat, f_delta, metric = (host(v) for v in ctx.sc_correlate(xd, n_lags=lags))

@@ -175,3 +175,75 @@ def assert_bytes_match(got: bytes, want: bytes, soft, mod, nd_per_byte_group=Non
     margin = decision_margin(np.asarray(soft)[bad_pts], mod)
     assert np.all(margin < tol), f"{what}: {np.sum(margin >= tol)} decisions differ away from any boundary"
     return int(bad_pts.size)
+
+
+def make_capture(orc, rng, mod, guard, payload, span, delay, fd, snr_db=30.0, n_fft=64):
+    tx = orc.encode(payload, guard, mod, n_fft)
+    return through_channel(orc, rng, tx, span, delay, fd, snr_db), tx
+
+
+# the (threshold, n_lags, frame_len) searches k_sc80's corner-case captures are put through: other thresholds, bounded searches,
+# captures barely longer than one window
+SC80_SPAN = 2176
+SC80_SEARCHES = ((0.5, 0, SC80_SPAN), (0.37, 0, SC80_SPAN), (0.81, 300, SC80_SPAN), (0.5, 0, 400), (0.5, 0, 322), (0.5, 45, 2000))
+
+
+def sc80_corner_captures(orc):
+    """The N = 64 captures k_sc80 is tested on (seeded): -> (13 ordinary captures of SC80_SPAN samples, packets at delays 1 .. 79 through
+    the FIR channel with CFO at 30 dB; the five dynamic-range captures [zeros then a noiseless frame, a burst then EXACT zeros then
+    the frame, a burst then a packet 75 dB down, a burst 50 dB up in front of a packet, an ordinary capture])."""
+    rng = np.random.default_rng(80)
+    span = SC80_SPAN
+    tx = orc.encode(bytes(rng.integers(0, 256, 560, dtype=np.uint8)), True, orc.QAM64)
+    ordinary = [through_channel(orc, rng, tx, span, int(d), float(fd), 30.0) for d, fd in
+                zip(rng.integers(1, 80, 13), (rng.random(13) * 1.9 - 0.95) * np.pi / 80)]
+    clean = np.zeros(span, complex); clean[500:500 + 1600] = tx[:1600]            # zeros, then a noiseless frame: exact, stays on the fast path
+    lead = fc32(clean)
+    gap = clean.copy(); gap[3:40] += 30.0 * (rng.standard_normal(37) + 1j * rng.standard_normal(37))      # burst, EXACT zeros, frame
+    quiet = 1e-3 * wide(ordinary[0]); quiet[5:25] += 3.0 * (rng.standard_normal(20) + 1j * rng.standard_normal(20))     # burst, then a packet 75 dB down
+    hot = wide(ordinary[1]).copy(); hot[2:14] += 40.0 * (rng.standard_normal(12) + 1j * rng.standard_normal(12))       # burst 50 dB up: trusted
+    return ordinary, np.stack([lead, fc32(gap), fc32(quiet), fc32(hot), ordinary[2]])
+
+
+def long_period_captures(orc, rng, n, mod, nbytes, nf, span):
+    """nf frames of nbytes through the FIR channel (delay below one period, CFO, 32 dB), a noise-only capture and the first capture cut
+    inside its preamble: [nf + 2, span] complex64"""
+    S = n + n // 4
+    caps = []
+    for f in range(nf):
+        tx = orc.encode(bytes(rng.integers(0, 256, nbytes, dtype=np.uint8)), True, mod, n)
+        d = int(rng.integers(1, S))
+        fd = (rng.random() * 1.8 - 0.9) * np.pi / S
+        caps.append(through_channel(orc, rng, tx, span, d, fd, 32.0, data_start=10 * S))
+    caps.append(fc32(0.05 * (rng.standard_normal(span) + 1j * rng.standard_normal(span))))     # noise only
+    cut = caps[0].copy(); cut[int(3.5 * S):] = 0                                               # ends inside the preamble
+    caps.append(cut)
+    return np.stack(caps)
+
+
+def loud_payload(orc, n, mod, nbytes, sym=1, seed=0):
+    """A payload whose data symbol `sym` has a time sample far above the header blocks' full scale (without guard bands every bin is a
+    data carrier: each carrier gets the constellation point whose contribution to sample 1 of the symbol is largest)."""
+    rng = np.random.default_rng(seed)
+    sym_bytes = n * mod // 8
+    pts = []
+    for pat in range(1 << mod):                       # the point of every bit pattern (LSB-first stream bits)
+        bits = np.array([(pat >> b) & 1 for b in range(8)], np.uint8)
+        pts.append(orc.modulate(bytes(np.packbits(bits, bitorder="little")), mod)[0])
+    pts = np.array(pts)
+    freq, used = orc.encode_block(np.arange(1, n + 1, dtype=np.float64) + 0j, n, False)
+    assert used == n
+    pos_of = {int(round(freq[p].real)) - 1: p for p in range(n)}     # where stream point i lands in the frequency vector
+    resp = np.empty(n, np.complex128)
+    for p in range(n):                                # what a unit at bin position p contributes to time sample 1
+        e = np.zeros(n, np.complex128)
+        e[p] = 1.0
+        resp[p] = orc.prefix_block(e)[n // 4 + 1]
+    pat = np.array([int(np.argmax((pts * resp[pos_of[i]]).real)) for i in range(n)])
+    bits = ((pat[:, None] >> np.arange(mod)[None, :]) & 1).astype(np.uint8).reshape(-1)
+    loud = np.packbits(bits, bitorder="little")
+    pay = rng.integers(0, 256, nbytes, dtype=np.uint8)
+    lo = sym * sym_bytes - 16
+    assert loud.size == sym_bytes and lo >= 0 and lo + sym_bytes <= nbytes
+    pay[lo: lo + sym_bytes] = loud
+    return pay
