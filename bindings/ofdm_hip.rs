@@ -67,6 +67,16 @@ pub const OFDM_SOFT_LLR_SCALE: f32 = 32.0;
 // cp_len taps -- opt-in, receive side only; parity unpinned by the reference, tests/chest_ref.py is the definition (include/ofdm_hip.h)
 pub const OFDM_CHEST_LS: i32 = 0;
 pub const OFDM_CHEST_WLS: i32 = 1;
+// ofdm_rx_quality_batch: indices into a frame's row of OFDM_QUALITY_FIELDS floats (noise variance, gain, linear SNR, LLR unit, linear
+// EVM^2, counted points); parity unpinned by the reference, tests/quality_ref.py is the definition (include/ofdm_hip.h)
+pub const OFDM_Q_VALID: usize = 0;
+pub const OFDM_Q_NOISE_VAR: usize = 1;
+pub const OFDM_Q_GAIN: usize = 2;
+pub const OFDM_Q_SNR: usize = 3;
+pub const OFDM_Q_LLR_UNIT: usize = 4;
+pub const OFDM_Q_EVM2: usize = 5;
+pub const OFDM_Q_POINTS: usize = 6;
+pub const OFDM_QUALITY_FIELDS: usize = 8;
 
 /// The crate's own `ModulationScheme` (src/transmitter.rs:98-104) is what `encode` / `decode` keep taking.  Its `Qam` arm is
 /// empty in the reference (transmitter.rs:135-136, receiver.rs:185: "Only 16 qam is implemented"); here it selects 16-QAM.
@@ -165,6 +175,10 @@ extern "C" {
     pub fn ofdm_rx_llr_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,
                              first_symbol: i32, syms_per_frame: i32, offset_dev: *const i32, f_delta_dev: *const f64,
                              hk_dev: *const ofdm_fc32, hk_stride: i64, llr_scale: f32, llr_dev: *mut i8, llr_stride: i64) -> c_int;
+    pub fn ofdm_rx_quality_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,
+                                 first_symbol: i32, syms_per_frame: i32, n_points_dev: *const i32, offset_dev: *const i32,
+                                 f_delta_dev: *const f64, hk_dev: *const ofdm_fc32, hk_stride: i64, status_dev: *const i32,
+                                 quality_dev: *mut f32) -> c_int;
     pub fn ofdm_tx_encode_batch(ctx: *mut ofdm_ctx, payload_dev: *const u8, n_frames: i64, payload_stride: i64,
                                 payload_len_dev: *const i32, payload_bytes: i32, out_dev: *mut ofdm_fc32, out_stride: i64) -> c_int;
     pub fn ofdm_rx_decode_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,

@@ -320,8 +320,9 @@ int ofdm_rx_demod_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames
  * Channel weight w_k = |H_k|^2 / (mean of |H|^2 over the data carriers), per frame or over the shared H; w = 1 without H.
  * Stored: int8 L = clamp(rint(llr_scale * w_k * Lambda), -127, 127), 0 when the product is not finite.  The product is formed in
  * f32: at an llr_scale near FLT_MAX it overflows and 0 is stored where exact arithmetic would clamp to +-127.
- * The true LLR is L / llr_scale * 4 mean|H|^2 / ((M - 1)^2 sigma^2), sigma^2 = the complex noise variance of a received bin; the
- * library does not estimate sigma^2. */
+ * The true LLR is L / llr_scale * 4 mean|H|^2 / ((M - 1)^2 sigma^2), sigma^2 = the complex noise variance of a received bin:
+ * ofdm_rx_quality_batch ("link quality" below) estimates sigma^2 and returns that factor as OFDM_Q_LLR_UNIT.  No decoder scales
+ * its LLRs by it. */
 /* ofdm_rx_demod_batch with int8 LLRs out instead of hard bytes: arguments as there; llr_dev[f*llr_stride ..] receives
  * syms_per_frame * data_carriers * bps LLRs, LLR j = bit j of the stream rx_demod packs LSB-first.  llr_scale must be finite and
  * > 0, llr_stride >= syms_per_frame * data_carriers * bps (OFDM_ERR_INVALID otherwise). */
@@ -332,6 +333,50 @@ int ofdm_rx_llr_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, 
  * first) -> 4 bytes per block.  Per codeword the c of the 16 that maximises sum_i (2 c_i - 1) L_i, in exact integer arithmetic;
  * ties go to the smallest data nibble. */
 int ofdm_hamming74_decode_soft(ofdm_ctx *ctx, const int8_t *llr_dev, int64_t n_bits, uint8_t *out_dev);
+
+/* ------------------------------------------------------------------ link quality (north-star extension)
+ * Parity unpinned by the reference, which measures nothing of the kind: tests/quality_ref.py is the definition.  Per frame f, with
+ * o = offset_dev[f], S = n_fft + cp_len, samples at or beyond frame_len reading as zero and the derotation of
+ * ofdm_estimate_channel_batch (sample id counted from o):
+ *   training part, counted only if o >= 0 and o + 10 S <= frame_len (all five training blocks inside the capture):
+ *     y_b[n]     the derotated sample o + (5 + b) S + cp_len + n, b < 5, n < n_fft;  ybar = mean_b y_b;  Ybar = FFT(ybar), unnormalised:
+ *                the quantity ofdm_estimate_channel_batch divides by the training table
+ *     noise_var  (1/4) sum_b sum_n |y_b[n] - ybar[n]|^2  =  (1 / (4 N)) sum_k sum_b |Y_b[k] - Ybar[k]|^2: the unbiased estimate of the
+ *                complex noise variance of one received bin, the sigma^2 of "soft decisions" above (formed from the deviations)
+ *     gain       sum_{k in D} (|Ybar[k]|^2 - noise_var / 5) / sum_{k in D} |t_k|^2, D = the data carriers, t = the training table:
+ *                the |t_k|^2-weighted mean of |H_k|^2 with the noise bias of Ybar removed
+ *     snr        max(gain, 0) Es / noise_var, LINEAR (+inf if noise_var is 0); Es = the constellation's mean |point|^2: 1 (BPSK),
+ *                2 (QPSK), 2 (M + 1) / (3 (M - 1)) for M levels per axis (10/9, 6/7, 34/45 for 16-, 64-, 256-QAM)
+ *     llr_unit   4 mean_{k in D} |hk[f][k]|^2 / ((M - 1)^2 noise_var), M = 2 for BPSK and QPSK, the mean 1 without hk_dev
+ *   data part (decision-directed EVM), over the frame's first n_points_dev[f] constellation points in rx_demod's stream order from data
+ *   symbol first_symbol (point j lies in symbol j / data_carriers).  Point j is counted iff j < n_points_dev[f], j / data_carriers <
+ *   syms_per_frame and its symbol lies wholly inside the capture, o + (first_symbol + j / data_carriers + 1) S <= frame_len:
+ *     x          the equalised, pilot-phase-corrected point, what ofdm_rx_demod_batch writes to soft_dev
+ *     evm2       sum |x - xh|^2 / sum |xh|^2 over the counted points, xh = the constellation point nearest x (the hard decision mapped
+ *                back), LINEAR; 0 when nothing is counted
+ *     points     the number counted, as a float
+ *   The caller supplies the count because transmit pads the last symbol with zero points, which must not be counted.
+ * A frame whose training part is not counted has OFDM_Q_VALID = 0 and every field 0.  A non-finite sample makes the fields it
+ * reaches non-finite (one in a training block: noise_var, gain, snr, llr_unit; one in a counted data symbol: evm2); nothing is clamped. */
+enum {
+    OFDM_Q_VALID = 0,     /* 1 if the training part was counted, else 0 (and the row is 0) */
+    OFDM_Q_NOISE_VAR = 1,
+    OFDM_Q_GAIN = 2,
+    OFDM_Q_SNR = 3,       /* linear */
+    OFDM_Q_LLR_UNIT = 4,
+    OFDM_Q_EVM2 = 5,      /* linear */
+    OFDM_Q_POINTS = 6,
+    OFDM_QUALITY_FIELDS = 8 /* floats per row; index 7 is reserved and 0 */
+};
+/* Arguments as ofdm_rx_demod_batch; quality_dev receives n_frames rows of OFDM_QUALITY_FIELDS floats.  n_points_dev (optional): NULL
+ * or a count <= 0 = no EVM.  status_dev (optional): a frame whose status is not OFDM_FRAME_OK gets an all-zero row and is not read.
+ * OFDM_ERR_INVALID: NULL in_dev or quality_dev (with n_frames > 0), a negative size, hk_stride not in {0, n_fft}, or syms_per_frame *
+ * data_carriers above 2^24 (points is a float: no frame may count more; a larger n_points_dev[f] counts what syms_per_frame holds).
+ * n_frames == 0: OFDM_OK.  One launch (k_linkq), no workspace. */
+int ofdm_rx_quality_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                          int32_t first_symbol, int32_t syms_per_frame, const int32_t *n_points_dev,
+                          const int32_t *offset_dev, const double *f_delta_dev, const ofdm_fc32 *hk_dev, int64_t hk_stride,
+                          const int32_t *status_dev, float *quality_dev);
 
 /* ------------------------------------------------------------------ convolutional code (north-star extension; DESIGN.md 3, EXT-2 convolutional code)
  * K = 7, rate 1/2, generators 133 / 171 octal; the definition shared by the kernels and tests/conv_ref.py.

@@ -10,6 +10,7 @@
 #include "ofdm_hip.h"
 
 #include <algorithm>
+#include <cmath>
 #include <complex>
 #include <cstdint>
 #include <cstring>
@@ -118,6 +119,38 @@ class Context {
         if (r.status == OFDM_FRAME_FCS) throw Error("frame check failed: the payload is damaged"); // OFDM_ECC_FCS + mode
         if (r.status != OFDM_FRAME_OK) throw Error("decode failed, frame status " + std::to_string(r.status));
         return std::move(r.bytes);
+    }
+    // link quality (EXT-6, include/ofdm_hip.h) of the capture decode_capture just decoded: noise variance, gain, SNR and LLR unit from the
+    // frame's five training blocks, and -- when payload_bytes (the size of the payload that was sent) is given -- the decision-directed
+    // EVM over the points that carry it.  One channel estimate (the context's chest_mode) and one ofdm_rx_quality_batch over the frame at
+    // r.offset with r.f_delta; decode itself is untouched.  A capture that was not decoded (r.status != OFDM_FRAME_OK) gives valid = false.
+    struct LinkQuality { bool valid = false; float noise_var = 0.f, gain = 0.f, snr_db = NAN, llr_unit = 0.f, evm_db = NAN, points = 0.f; };
+    LinkQuality link_quality(const ofdm_fc32 *fc, int64_t n, const Decoded &r, int64_t payload_bytes = -1) {
+        LinkQuality q;
+        if (r.status != OFDM_FRAME_OK || r.offset < 0 || r.offset >= n) return q;
+        const int S = symbol_len(), nd = ofdm_data_carriers(ctx_), bps = 8 * ofdm_bytes_per_symbol(ctx_) / nd;
+        int32_t points = 0, syms = 0;
+        if (payload_bytes >= 0) {
+            points = (int32_t)((8 * (16 + ofdm_coded_len(ctx_, payload_bytes)) + bps - 1) / bps); // the 16-byte length header included
+            syms = (points + nd - 1) / nd;
+        }
+        const int64_t len = std::min<int64_t>(n - r.offset, (int64_t)(10 + syms) * S); // the frame alone: sample ids count from its start
+        DevBuf din(ctx_, (size_t)len * sizeof(ofdm_fc32)), dhk(ctx_, (size_t)n_fft_ * sizeof(ofdm_fc32)), dfd(ctx_, sizeof(double)),
+            dpts(ctx_, sizeof(int32_t)), dq(ctx_, OFDM_QUALITY_FIELDS * sizeof(float));
+        check(ofdm_memcpy_h2d(ctx_, din.p, fc + r.offset, (size_t)len * sizeof(ofdm_fc32)), "h2d");
+        check(ofdm_memcpy_h2d(ctx_, dfd.p, &r.f_delta, sizeof(double)), "h2d");
+        check(ofdm_memcpy_h2d(ctx_, dpts.p, &points, sizeof(int32_t)), "h2d");
+        check(ofdm_estimate_channel_batch(ctx_, (const ofdm_fc32 *)din.p, 1, len, len, nullptr, (const double *)dfd.p, (ofdm_fc32 *)dhk.p),
+              "ofdm_estimate_channel_batch");
+        check(ofdm_rx_quality_batch(ctx_, (const ofdm_fc32 *)din.p, 1, len, len, 10, syms, (const int32_t *)dpts.p, nullptr, (const double *)dfd.p,
+                                    (const ofdm_fc32 *)dhk.p, n_fft_, nullptr, (float *)dq.p), "ofdm_rx_quality_batch");
+        float row[OFDM_QUALITY_FIELDS];
+        check(ofdm_memcpy_d2h(ctx_, row, dq.p, sizeof(row)), "d2h");
+        q.valid = row[OFDM_Q_VALID] != 0.f;
+        q.noise_var = row[OFDM_Q_NOISE_VAR]; q.gain = row[OFDM_Q_GAIN]; q.llr_unit = row[OFDM_Q_LLR_UNIT]; q.points = row[OFDM_Q_POINTS];
+        if (q.valid) q.snr_db = 10.0f * std::log10(row[OFDM_Q_SNR]);
+        if (q.points > 0.f) q.evm_db = 10.0f * std::log10(row[OFDM_Q_EVM2]);
+        return q;
     }
     // batches on host memory: H2D / kernels / D2H pipelined inside the library (ofdm_rx_decode_host, ofdm_tx_encode_host)
     struct BatchResult { std::vector<uint8_t> bytes; int64_t row = 0; std::vector<int32_t> len, status, offset; std::vector<double> f_delta; };

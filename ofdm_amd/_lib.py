@@ -92,6 +92,7 @@ SIGNATURES = {
     "ofdm_fcs_wrap_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp]),
     "ofdm_fcs_check_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp]),
     "ofdm_rx_llr_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, i64, C.c_float, vp, i64]),
+    "ofdm_rx_quality_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, vp, i64, vp, vp]),
     "ofdm_sc_correlate_batch": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp, vp]),
     "ofdm_frequency_correction_batch": (C.c_int, [vp, vp, i64, i64, i64, vp]),
     "ofdm_cfo_rotate_batch": (C.c_int, [vp, vp, i64, i64, i64, vp, vp]),

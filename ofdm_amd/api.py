@@ -43,6 +43,9 @@ RX_AUTO, RX_STAGED = 0, 1
 # channel estimate of the receive chain: the reference's bin-by-bin one, or that one denoised by a weighted least-squares fit of cp_len
 # taps (EXT-5; tests/chest_ref.py is the definition)
 CHEST_LS, CHEST_WLS = 0, 1
+# ofdm_rx_quality_batch: indices into a frame's row of QUALITY_FIELDS floats (EXT-6; tests/quality_ref.py is the definition)
+Q_VALID, Q_NOISE_VAR, Q_GAIN, Q_SNR, Q_LLR_UNIT, Q_EVM2, Q_POINTS = 0, 1, 2, 3, 4, 5, 6
+QUALITY_FIELDS = 8
 DEFAULT_TUNING: dict = {}  # merged under every Context's `tuning=` (tools/tune_env.py fills it; empty in tests, bench and smoke)
 
 
@@ -660,6 +663,69 @@ class Context:
                                             syms_per_frame, _dev(offset), _dev(f_delta), _dev(hk), hk_stride, float(scale), _dev(out), llr_stride),
                  "rx_llr")
         return out
+
+    def frame_points(self, payload_bytes: int) -> int:
+        """Occupied constellation points of a frame of payload_bytes: ceil(8 (16 + coded_len(payload_bytes)) / bps), the 16-byte length
+        header included.  Transmit pads the last data symbol with zero points behind them."""
+        return -(-8 * (16 + self.coded_len(payload_bytes)) // self.modulation)
+
+    def rx_quality(self, frames: torch.Tensor, syms_per_frame: int, first_symbol: int = 10, n_points=None,
+                   offset: Optional[torch.Tensor] = None, f_delta: Optional[torch.Tensor] = None, hk: Optional[torch.Tensor] = None,
+                   status: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, frame_len: Optional[int] = None) -> torch.Tensor:
+        """ofdm_rx_quality_batch -> float32 [n_frames, QUALITY_FIELDS] (columns Q_*): noise variance, gain, linear SNR and LLR unit from
+        the five training blocks, and the decision-directed EVM^2 over the first n_points points of every frame (an int for all frames,
+        an int32 tensor per frame, None = no EVM) from data symbol first_symbol on.  status (optional): rows of frames with status != 0
+        are 0 and the frames are not read.  Definition: include/ofdm_hip.h, tests/quality_ref.py."""
+        frames = self._cx(frames)
+        f2 = frames.view(-1, frames.shape[-1])
+        n, stride = f2.shape
+        if n_points is not None and not isinstance(n_points, torch.Tensor):
+            n_points = torch.full((n,), int(n_points), dtype=torch.int32, device=self.device)
+        for name, t, dt in (("n_points", n_points, torch.int32), ("offset", offset, torch.int32), ("f_delta", f_delta, torch.float64),
+                            ("status", status, torch.int32)):
+            if t is not None and (t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.numel() != n):
+                raise OfdmError(f"rx_quality: {name} must be a contiguous {dt} tensor of n_frames elements on the context's device")
+        if out is None:
+            out = self.empty((n, QUALITY_FIELDS), torch.float32)
+        elif out.dtype != torch.float32 or out.device != self.device or out.shape != (n, QUALITY_FIELDS) or not out.is_contiguous():
+            raise OfdmError("rx_quality: out must be a contiguous float32 [n_frames, QUALITY_FIELDS] tensor on the context's device")
+        hk_stride = 0
+        if hk is not None:
+            hk = self._cx(hk)
+            hk_stride = self.n_fft if hk.dim() == 2 else 0  # [n_frames, N] per frame, [N] shared
+            assert hk.shape[-1] == self.n_fft and (hk.dim() == 1 or hk.shape[0] == n)
+        self._ck(self.lib.ofdm_rx_quality_batch(self.h, _dev(f2), n, stride, stride if frame_len is None else frame_len, first_symbol,
+                                                syms_per_frame, _dev(n_points), _dev(offset), _dev(f_delta), _dev(hk), hk_stride,
+                                                _dev(status), _dev(out)), "rx_quality")
+        return out
+
+    def link_quality(self, frames: torch.Tensor, decoded: dict, payload_bytes: Optional[int] = None, n_points=None) -> dict:
+        """What the link was like for the frames decode_batch just decoded: `decoded` is the dict it returned for `frames`.  Runs
+        estimate_channel with the decode's offset and f_delta (so chest_mode is honoured: under CHEST_WLS the denoised H' equalises and
+        weighs) and rx_quality with the decode's status -> tensors over the frames: valid, noise_var, gain, snr_db, llr_unit, evm_db,
+        points.  payload_bytes (the frames' payload size; the points are frame_points of it) or n_points (an int or a tensor per frame)
+        say which points carry data; without either only the training fields are measured.  snr_db is NaN where valid is 0, evm_db
+        where no point was counted.  decode_batch itself is untouched: this is one channel estimate and one more pass over the frames."""
+        frames = self._cx(frames)
+        f2 = frames.view(-1, frames.shape[-1])
+        status = decoded["status"]
+        offset = torch.where(status == 0, decoded["offset"], torch.zeros_like(decoded["offset"]))  # (a frame without timing is not read)
+        hk = self.estimate_channel(f2, offset, decoded["f_delta"])
+        if n_points is None and payload_bytes is not None:
+            n_points = self.frame_points(payload_bytes)
+        if n_points is None:
+            syms = 0
+        elif isinstance(n_points, torch.Tensor):
+            syms = max(f2.shape[1] // self.S - 10, 0)  # every data symbol a row can hold; only those that hold counted points are walked
+        else:
+            syms = -(-int(n_points) // self.data_carriers)
+        q = self.rx_quality(f2, syms, 10, n_points, offset, decoded["f_delta"], hk, status)
+        nan = torch.full_like(q[:, 0], float("nan"))
+        return {
+            "valid": q[:, Q_VALID] != 0, "noise_var": q[:, Q_NOISE_VAR], "gain": q[:, Q_GAIN],
+            "snr_db": torch.where(q[:, Q_VALID] != 0, 10.0 * torch.log10(q[:, Q_SNR]), nan), "llr_unit": q[:, Q_LLR_UNIT],
+            "evm_db": torch.where(q[:, Q_POINTS] > 0, 10.0 * torch.log10(q[:, Q_EVM2]), nan), "points": q[:, Q_POINTS],
+        }
 
     # ---------------------------------------------------------------- pipelines
     def encode_batch(self, payload: torch.Tensor, out: Optional[torch.Tensor] = None,

@@ -27,7 +27,7 @@ template <bool INV> __device__ __forceinline__ cf twid(cf w) { return INV ? make
 
 // ---- carrier map (reference: src/transmitter.rs:150-161, src/receiver.rs:122-133), tiled k = N/64
 // class of reference bin c (0..63): 0 data, 1 null, 2 pilot
-__device__ __forceinline__ int carrier_class64(int c, int guard) {
+__host__ __device__ __forceinline__ int carrier_class64(int c, int guard) {
     if (!guard) return 0;
     if (c >= 59 || c <= 5 || c == 32) return 1;
     if (c == 6 || c == 25 || c == 39 || c == 58) return 2;
@@ -94,6 +94,26 @@ __device__ __forceinline__ int swz(int i) { return i ^ ((i >> 3) & 7); }
 template <int T> __device__ __forceinline__ void group_sync() {
     if (T > 64) __syncthreads();
     else __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+// Sum over the T threads of one symbol (slot `slot` of the workgroup, thread t of the symbol).  red: G * (T / 64) floats of LDS for T > 64,
+// where every thread of the workgroup must arrive (two barriers); the order of the additions is fixed.
+template <int T> __device__ __forceinline__ float symbol_sum(float x, float *red, int slot, int t) {
+    // sum over the T threads of one symbol
+    constexpr int W = T < 64 ? T : 64;
+#pragma unroll
+    for (int m = W / 2; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
+    if (T > 64) {
+        constexpr int NW = T / 64;
+        __syncthreads();
+        if ((t & 63) == 0) red[slot * NW + (t >> 6)] = x;
+        __syncthreads();
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NW; ++i) s += red[slot * NW + i];
+        x = s;
+    }
+    return x;
 }
 
 // Load the per-thread twiddles for all passes after the first (loop invariant for a persistent thread).

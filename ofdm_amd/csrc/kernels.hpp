@@ -184,6 +184,34 @@ hipError_t run_tx_symbols(int n, const SymParams &p, hipStream_t st, int num_cu)
 // LLR demod: the RX demod chain with int8 max-log LLRs out (p.llr) and, when p.out_bytes is set, the hard bytes too
 hipError_t run_llr(int n, const SymParams &p, hipStream_t st, int num_cu);
 
+// ---- EXT-6 link quality (ofdm_rx_quality_batch; kernels_quality.hip, definition: tests/quality_ref.py)
+// k_linkq: one row of kQualityFields floats per frame from the five training blocks (noise variance, gain, SNR, LLR unit) and the
+// decision-directed EVM of the frame's first n_points[f] data points.  A frame with status[f] != 0 is not read and gets a zero row.
+constexpr int kQualityFields = 8;
+struct LinkqParams {
+    const Tuning *tune = nullptr;
+    Trace *trace = nullptr;
+    const float2 *in = nullptr;
+    long long n_frames = 0, frame_stride = 0, frame_len = 0;
+    int first_symbol = 0, syms_per_frame = 0;
+    int sym_len = 0;                     // S = N + CP
+    const int32_t *n_points = nullptr;   // optional: occupied constellation points per frame (nullptr: no EVM)
+    const int32_t *offset = nullptr;
+    const double *f_delta = nullptr;
+    const int32_t *status = nullptr;     // optional
+    const float2 *hk = nullptr;
+    long long hk_stride = 0;
+    const float2 *tw = nullptr;
+    int bps = 1, guard = 0;
+    float inv_t2 = 0.f;                  // 1 / sum over the data carriers of |t_k|^2
+    float es = 1.f;                      // mean |point|^2 of the constellation
+    float *quality = nullptr;            // [n_frames][kQualityFields]
+};
+hipError_t run_linkq(int n, const LinkqParams &p, hipStream_t st, int num_cu);
+// the two constants of a context: training = n interleaved (re, im) doubles; bps = bits per constellation point
+float linkq_inv_t2(const double *training, int n, int guard);
+float linkq_es(int bps);
+
 // ---- Schmidl-Cox (kernels_sync.hip)
 struct ScParams {
     const Tuning *tune = nullptr;

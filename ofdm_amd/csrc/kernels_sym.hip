@@ -16,24 +16,6 @@ namespace ofdm {
 
 enum { M_FFT = 0, M_IFFT = 1, M_IFFT_CP = 2, M_DEMOD = 3, M_CHEST = 4, M_TX = 5, M_LLR = 6 };
 
-template <int T> __device__ __forceinline__ float symbol_sum(float x, float *red, int slot, int t) {
-    // sum over the T threads of one symbol
-    constexpr int W = T < 64 ? T : 64;
-#pragma unroll
-    for (int m = W / 2; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-    if (T > 64) {
-        constexpr int NW = T / 64;
-        __syncthreads();
-        if ((t & 63) == 0) red[slot * NW + (t >> 6)] = x;
-        __syncthreads();
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < NW; ++i) s += red[slot * NW + i];
-        x = s;
-    }
-    return x;
-}
-
 template <int N, int MODE>
 __global__ __launch_bounds__(Plan<N>::WG) void k_sym(SymParams p) {
     typedef Plan<N> P;

@@ -1138,6 +1138,32 @@ int ofdm_rx_llr_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_
                    f_delta, nullptr, reinterpret_cast<const float2 *>(hk), hk_stride, llr_scale, llr, llr_stride, nullptr, 0, true);
 }
 
+// EXT-6 link quality: one launch of k_linkq, a row per frame (include/ofdm_hip.h, tests/quality_ref.py)
+int ofdm_rx_quality_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                          int32_t first_symbol, int32_t syms_per_frame, const int32_t *n_points, const int32_t *offset,
+                          const double *f_delta, const ofdm_fc32 *hk, int64_t hk_stride, const int32_t *status, float *quality) {
+    if (!c || n_frames < 0 || syms_per_frame < 0 || first_symbol < 0 || frame_len <= 0 || frame_stride < 0) return OFDM_ERR_INVALID;
+    if (n_frames && (!in || !quality)) return OFDM_ERR_INVALID;
+    if (hk && hk_stride != 0 && hk_stride != c->prm.n_fft) return OFDM_ERR_INVALID;
+    if ((int64_t)syms_per_frame * c->carriers() > (1ll << 24)) return OFDM_ERR_INVALID; // OFDM_Q_POINTS is a float
+    if (!n_frames) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    LinkqParams p;
+    p.tune = &c->tune; p.trace = &c->trace;
+    p.in = reinterpret_cast<const float2 *>(in); p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
+    p.first_symbol = first_symbol; p.syms_per_frame = syms_per_frame; p.sym_len = c->S();
+    p.n_points = n_points; p.offset = offset; p.f_delta = f_delta; p.status = status;
+    p.hk = reinterpret_cast<const float2 *>(hk); p.hk_stride = hk_stride; p.tw = c->d_tw;
+    p.bps = c->prm.modulation; p.guard = c->prm.guard_bands;
+    const int N = c->prm.n_fft;
+    p.inv_t2 = linkq_inv_t2(c->training.data(), N, p.guard);
+    p.es = linkq_es(p.bps);
+    p.quality = quality;
+    HIP_TRY(c, run_linkq(N, p, c->stream, c->num_cu));
+    return OFDM_OK;
+}
+
 // ------------------------------------------------------------------ pipelines
 int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, int64_t payload_stride,
                          const int32_t *payload_len, int32_t payload_bytes, ofdm_fc32 *out, int64_t out_stride) {
