@@ -53,8 +53,13 @@ pub const OFDM_FRAME_UNCORRECTABLE: i32 = -5; // OFDM_ECC_RS255*: an RS block wi
 // LDPC(648,324), rate 1/2, layered normalised min-sum from LLRs; the length travels in the first code word; parity unpinned by the
 // reference, tests/ldpc_ref.py is the definition (include/ofdm_hip.h)
 pub const OFDM_ECC_LDPC648: i32 = 16;
+// the project's own LDPC(648) codes of rates 2/3, 3/4 and 5/6 under the same frame rule (K = 53 / 60 / 67 info bytes a code word);
+// `rate` of the ofdm_ldpc648_*_rate functions: 0 = 1/2, 1 = 2/3, 2 = 3/4, 3 = 5/6
+pub const OFDM_ECC_LDPC648_R23: i32 = 41;
+pub const OFDM_ECC_LDPC648_R34: i32 = 42;
+pub const OFDM_ECC_LDPC648_R56: i32 = 43;
 pub const OFDM_LDPC_MAX_ITER: i32 = 20;
-// CRC-32 frame check around any of the twelve modes above, 64 + mode: decode delivers exactly the payload that was sent or reports
+// CRC-32 frame check around any of the fifteen modes above, 64 + mode: decode delivers exactly the payload that was sent or reports
 // the frame with OFDM_FRAME_FCS; parity unpinned by the reference, tests/fcs_ref.py is the definition (include/ofdm_hip.h)
 pub const OFDM_ECC_FCS: i32 = 64;
 pub const OFDM_FCS_OVERHEAD: i64 = 8;
@@ -154,6 +159,14 @@ extern "C" {
                                      out_stride: i64) -> c_int;
     pub fn ofdm_ldpc648_decode_batch(ctx: *mut ofdm_ctx, llr_dev: *const i8, n_frames: i64, llr_stride: i64, n_cw: i64, max_iter: i32,
                                      out_dev: *mut u8, out_stride: i64, iters_dev: *mut i32) -> c_int;
+    pub fn ofdm_ldpc648_info_bytes(rate: i32) -> i32;
+    pub fn ofdm_ldpc648_coded_len_rate(payload_bytes: i64, rate: i32) -> i64;
+    pub fn ofdm_ldpc648_encode_rate(info: *const u8, n_cw: i64, rate: i32, code: *mut u8) -> c_int;
+    pub fn ofdm_ldpc648_decode_rate(llr: *const i8, n_cw: i64, max_iter: i32, rate: i32, out: *mut u8, iters: *mut i32) -> c_int;
+    pub fn ofdm_ldpc648_encode_rate_batch(ctx: *mut ofdm_ctx, in_dev: *const u8, n_frames: i64, in_stride: i64, n_cw: i64, rate: i32,
+                                          out_dev: *mut u8, out_stride: i64) -> c_int;
+    pub fn ofdm_ldpc648_decode_rate_batch(ctx: *mut ofdm_ctx, llr_dev: *const i8, n_frames: i64, llr_stride: i64, n_cw: i64, max_iter: i32,
+                                          rate: i32, out_dev: *mut u8, out_stride: i64, iters_dev: *mut i32) -> c_int;
     pub fn ofdm_fcs_wrap_batch(ctx: *mut ofdm_ctx, in_dev: *const u8, n_frames: i64, in_stride: i64, in_len_dev: *const i32, n_bytes: i64,
                                out_dev: *mut u8, out_stride: i64, out_len_dev: *mut i32) -> c_int;
     pub fn ofdm_fcs_check_batch(ctx: *mut ofdm_ctx, row_dev: *const u8, n_frames: i64, row_stride: i64, row_len_dev: *const i32,

@@ -76,18 +76,21 @@ enum { OFDM_MOD_BPSK = 1, OFDM_MOD_QPSK = 2, OFDM_MOD_QAM16 = 4, OFDM_MOD_QAM64 
  * ceil(kept(8 (p + 1), rate) / 8) (see "punctured rates and framed modes" below).
  * OFDM_ECC_RS255 / OFDM_ECC_RS255_K7F_R12 / _R23 / _R34 = 20 + inner, inner = OFDM_ECC_NONE or OFDM_ECC_CONV_K7F_*: the reference's
  * outer Reed-Solomon(255,223) framing (create_transmission_bytes / decipher_transmission_bytes) around the inner mode's frame (see
- * "outer Reed-Solomon code on the device" below).  21 .. 29 and 33 .. 63 are rejected like every other value not named.
+ * "outer Reed-Solomon code on the device" below).  21 .. 29 and 33 .. 40 are rejected like every other value not named.
  * OFDM_ECC_LDPC648: the quasi-cyclic LDPC(648,324) code, rate 1/2, 40 info bytes to 80 coded bytes, behind no other header than its
  * own first code word, decoded by layered normalised min-sum from the same int8 LLRs: coded_len(p) = 80 ceil((p + 8) / 40) (see
  * "LDPC(648,324)" below).  13 .. 15 and 17 .. 19 stay rejected, as does 36 (RS outside LDPC is not a mode).
- * OFDM_ECC_FCS + mode = 64 + mode, mode any of the twelve values above (64, 65, 66, 69, 74, 75, 76, 80, 84, 94, 95, 96): the CRC-32 frame
- * check around the payload of that mode (see "frame check sequence" below) -- decode delivers exactly the bytes that were sent or
- * reports the frame.  Every other value from 64 upwards is rejected. */
+ * OFDM_ECC_LDPC648_R23 / _R34 / _R56 = 41 / 42 / 43: the same frame rule over the project's own LDPC(648) codes of rates 2/3, 3/4 and 5/6,
+ * K = 53 / 60 / 67 info bytes to 80 coded bytes: coded_len(p) = 80 ceil((p + 8) / K) (see "LDPC(648), rates 2/3, 3/4 and 5/6" below).
+ * 37 .. 40 and 44 .. 63 stay rejected, 61 .. 63 (RS outside them) among them.
+ * OFDM_ECC_FCS + mode = 64 + mode, mode any of the fifteen values above (64, 65, 66, 69, 74, 75, 76, 80, 84, 94, 95, 96, 105, 106, 107): the
+ * CRC-32 frame check around the payload of that mode (see "frame check sequence" below) -- decode delivers exactly the bytes that were
+ * sent or reports the frame.  Every other value from 64 upwards is rejected. */
 enum { OFDM_ECC_NONE = 0, OFDM_ECC_HAMMING74 = 1, OFDM_ECC_HAMMING74_SOFT = 2, OFDM_ECC_CONV_K7 = 5,
        OFDM_ECC_CONV_K7F_R12 = 10, OFDM_ECC_CONV_K7F_R23 = 11, OFDM_ECC_CONV_K7F_R34 = 12,
        OFDM_ECC_RS255 = 20, OFDM_ECC_RS255_K7F_R12 = 30, OFDM_ECC_RS255_K7F_R23 = 31, OFDM_ECC_RS255_K7F_R34 = 32,
-       OFDM_ECC_LDPC648 = 16, OFDM_ECC_FCS = 64 };
-/* iterations the OFDM_ECC_LDPC648 decode chain gives a code word: a definition, not a tuned number */
+       OFDM_ECC_LDPC648 = 16, OFDM_ECC_LDPC648_R23 = 41, OFDM_ECC_LDPC648_R34 = 42, OFDM_ECC_LDPC648_R56 = 43, OFDM_ECC_FCS = 64 };
+/* iterations the OFDM_ECC_LDPC648* decode chains give a code word: a definition, not a tuned number */
 #define OFDM_LDPC_MAX_ITER 20
 /* bytes the envelope of an OFDM_ECC_FCS mode adds to a payload: the u32 length word in front, the u32 CRC-32 behind */
 #define OFDM_FCS_OVERHEAD 8
@@ -507,7 +510,51 @@ int ofdm_rs255_decode_batch(ofdm_ctx *ctx, const uint8_t *code_dev, int64_t n_fr
  *   the end of the capture delivers its prefix.  Bytes of a row beyond out_len are unspecified.
  * Rows: out_stride >= max(40 floor(body_max / 80) - 8, 0), body_max = max(max_symbols * bytes_per_symbol - 16, 0) (OFDM_ERR_INVALID
  * otherwise), in every decode entry point (ofdm_rx_decode_batch, _host, _long, _long_host); chest_mode is honoured.  OFDM_ECC_FCS +
- * OFDM_ECC_LDPC648 wraps the mode like any other; 20 + 16 (RS outside LDPC) is rejected. */
+ * OFDM_ECC_LDPC648 wraps the mode like any other; 20 + 16 (RS outside LDPC) is rejected.
+ *
+ * LDPC(648), rates 2/3, 3/4 and 5/6 (OFDM_ECC_LDPC648_R23 / _R34 / _R56; tests/ldpc_rates_ref.py is the definition, for rate 1/2 it is
+ * ldpc_ref.py again).  `rate`: 0 = 1/2 (the code above), 1 = 2/3, 2 = 3/4, 3 = 5/6; every other value OFDM_ERR_INVALID.  All four are
+ * quasi-cyclic with Z = 27 and 24 block columns, 12 / 8 / 6 / 4 block rows, and the entry convention and the parity structure of the
+ * table above: the first parity column carries shifts 1 / 0 / 1 in the first, the middle (rows / 2) and the last block row, then the
+ * dual diagonal.  The three tables below are THE PROJECT'S OWN, found by a seeded greedy search (row degrees balanced, no 4-cycles, the
+ * fewest 6-cycles of 30 draws); they are NOT the matrices of 802.11n.  The tables are the definition (full rank 216 / 162 / 108,
+ * invertible parity halves, no 4-cycles: tests/test_ldpc_rates_cpu.py).
+ *   rate 2/3, 8 x 24, 87 blocks:
+ *     15  5 24  -  3 14  -  -  8 23  -  4  -  - 13  -  1  0  -  -  -  -  -  -
+ *      5  2 12  9  - 17  -  1  -  - 10  - 26  -  -  -  -  0  0  -  -  -  -  -
+ *     21 24 22  2  -  2 25  -  4  -  -  5  -  -  -  -  -  -  0  0  -  -  -  -
+ *     26 13  7 22  -  - 15  - 11  - 18  - 17  -  -  4  -  -  -  0  0  -  -  -
+ *      0  5  - 15  0 24  - 11  - 10  -  -  -  0  1  -  0  -  -  -  0  0  -  -
+ *      3 21 18 12 22  - 25  -  - 22  -  - 16  -  -  5  -  -  -  -  -  0  0  -
+ *      5 14 22  8  -  - 13 14  -  - 18  -  -  2  - 11  -  -  -  -  -  -  0  0
+ *      4 17  7  5 26  -  -  3  -  -  -  5  -  8 16  -  1  -  -  -  -  -  -  0
+ *   rate 3/4, 6 x 24, 85 blocks:
+ *     11 13 17 14 16  - 14 20  - 26  -  2 26  -  - 26 23  -  1  0  -  -  -  -
+ *     21  3 11 15 13 26  5  -  - 15  -  8  - 13  - 21  - 18  -  0  0  -  -  -
+ *     22  1 21  6 21  8  - 20 25  - 16  -  9  -  - 17  - 25  -  -  0  0  -  -
+ *     18 22 11 25 18 13  - 13 26  - 22  - 21  - 16  -  4  -  0  -  -  0  0  -
+ *     13 18  5 12 20  -  3 21  0  -  - 11  - 25  8  - 19  -  -  -  -  -  0  0
+ *     25 22 21  3 13 24 10  -  - 24 12  -  -  3 10  -  -  3  1  -  -  -  -  0
+ *   rate 5/6, 4 x 24, 81 blocks:
+ *     10 13 21 20 13 19 12 15  6 26 10 20  9  - 11 18  - 10 19 23  1  0  -  -
+ *      5 21 26 18 17 12 15 14  2 18  0  9  - 23 20 20 21  -  4  7  -  0  0  -
+ *     19 20  4 22 11  7 13 11 14 20 16 17 22 15  0  - 14 10  - 13  0  -  0  0
+ *     22 15 22 11 21  3 21 25 12 19  8 23  8 22  - 23 19  4  6  -  1  -  -  0
+ * Every rate sends 640 bits = 80 bytes a code word.  With M = 27 rows checks and K = ofdm_ldpc648_info_bytes(rate) = 40 / 53 / 60 / 67:
+ * x[0 .. 8 K - 1] = the K info bytes, LSB first; x[8 K .. 647 - M] = 0 (shortened: 4 / 8 / 6 / 4 bits, not sent); x[648 - M .. 647] =
+ * the unique parity with H x = 0.  Sent: x[0 .. 8 K - 1] ++ x[648 - M .. 648 - M + (640 - 8 K) - 1], packed LSB first: 320 of 324 /
+ * all 216 / 160 of 162 / 104 of 108 parity bits, the last 4 / 0 / 2 / 4 are punctured.  The decoder is the one above over the code's
+ * table: shortened positions start at +2047, punctured ones at 0, sent ones at -L; output x[0 .. 8 K - 1].
+ * ofdm_ldpc648_info_bytes(rate) = K.  ofdm_ldpc648_coded_len_rate(p, rate) = 80 ceil((p + 8) / K).
+ * ofdm_ldpc648_encode_rate / _decode_rate: n_cw blocks of K info bytes -> n_cw blocks of 80 code bytes, and n_cw blocks of 640 LLRs ->
+ *   n_cw blocks of K bytes and iters[n_cw] (optional), on the host.  ofdm_ldpc648_encode_rate_batch / _decode_rate_batch
+ *   (k_ldpc_encode<r23|r34|r56> / k_ldpc_decode<r23|r34|r56>; rate 0: k_ldpc_encode / k_ldpc_decode): the same on device rows, with
+ *   in_stride >= K n_cw and out_stride >= 80 n_cw (encode), llr_stride >= 640 n_cw and out_stride >= K n_cw (decode).  Rate 0 through
+ *   any of them gives what the functions without `rate` give, byte for byte.
+ * Frame modes ecc = OFDM_ECC_LDPC648_R23 / _R34 / _R56: the frame rule of OFDM_ECC_LDPC648 above with K in place of 40 -- info stream
+ * [u32 LE p][u32 LE ~p] ++ payload, zero-padded to B = ceil((p + 8) / K) code words, coded_len(p) = 80 B; receive with nb = body / 80:
+ * the same OFDM_FRAME_HEADER / OFDM_FRAME_UNCORRECTABLE verdicts, min(p, K nb - 8) bytes delivered; rows: out_stride >= max(K
+ * floor(body_max / 80) - 8, 0).  OFDM_ECC_FCS + each wraps it like any other mode; 20 + each (61 .. 63) is rejected. */
 int64_t ofdm_ldpc648_coded_len(int64_t payload_bytes);
 int ofdm_ldpc648_encode(const uint8_t *info, int64_t n_cw, uint8_t *code);
 int ofdm_ldpc648_decode(const int8_t *llr, int64_t n_cw, int32_t max_iter, uint8_t *out, int32_t *iters);
@@ -515,6 +562,14 @@ int ofdm_ldpc648_encode_batch(ofdm_ctx *ctx, const uint8_t *in_dev, int64_t n_fr
                               int64_t out_stride);
 int ofdm_ldpc648_decode_batch(ofdm_ctx *ctx, const int8_t *llr_dev, int64_t n_frames, int64_t llr_stride, int64_t n_cw, int32_t max_iter,
                               uint8_t *out_dev, int64_t out_stride, int32_t *iters_dev /* optional, n_frames * n_cw */);
+int32_t ofdm_ldpc648_info_bytes(int32_t rate);
+int64_t ofdm_ldpc648_coded_len_rate(int64_t payload_bytes, int32_t rate);
+int ofdm_ldpc648_encode_rate(const uint8_t *info, int64_t n_cw, int32_t rate, uint8_t *code);
+int ofdm_ldpc648_decode_rate(const int8_t *llr, int64_t n_cw, int32_t max_iter, int32_t rate, uint8_t *out, int32_t *iters);
+int ofdm_ldpc648_encode_rate_batch(ofdm_ctx *ctx, const uint8_t *in_dev, int64_t n_frames, int64_t in_stride, int64_t n_cw, int32_t rate,
+                                   uint8_t *out_dev, int64_t out_stride);
+int ofdm_ldpc648_decode_rate_batch(ofdm_ctx *ctx, const int8_t *llr_dev, int64_t n_frames, int64_t llr_stride, int64_t n_cw, int32_t max_iter,
+                                   int32_t rate, uint8_t *out_dev, int64_t out_stride, int32_t *iters_dev /* optional, n_frames * n_cw */);
 
 /* ------------------------------------------------------------------ frame check sequence (north-star extension; DESIGN.md 3, EXT-2 frame check)
  * Parity unpinned by the reference (it has no check of its own): tests/fcs_ref.py over zlib.crc32 is the definition.

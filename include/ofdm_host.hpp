@@ -285,6 +285,34 @@ class Context {
         if (iters) { iters->resize(n_cw); if (n_cw) check(ofdm_memcpy_d2h(ctx_, iters->data(), dit.p, sizeof(int32_t) * n_cw), "d2h"); }
         return out;
     }
+    // ... and over the family: rate 0 = 1/2 (the two above), 1 = 2/3, 2 = 3/4, 3 = 5/6; K = ofdm_ldpc648_info_bytes(rate) info bytes a code word
+    std::vector<uint8_t> ldpc_encode(const std::vector<uint8_t> &info, int32_t rate) {
+        const int32_t k = ofdm_ldpc648_info_bytes(rate);
+        if (k <= 0) throw Error("ldpc_encode: rate must be 0 .. 3");
+        if (info.size() % (size_t)k) throw Error("ldpc_encode: whole blocks of K info bytes expected");
+        const size_t n_cw = info.size() / (size_t)k;
+        std::vector<uint8_t> out(80 * n_cw);
+        DevBuf din(ctx_, info.size()), dout(ctx_, out.size());
+        if (!info.empty()) check(ofdm_memcpy_h2d(ctx_, din.p, info.data(), info.size()), "h2d");
+        check(ofdm_ldpc648_encode_rate_batch(ctx_, (const uint8_t *)din.p, 1, (int64_t)info.size(), (int64_t)n_cw, rate, (uint8_t *)dout.p,
+                                             (int64_t)out.size()), "ofdm_ldpc648_encode_rate_batch");
+        if (!out.empty()) check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
+        return out;
+    }
+    std::vector<uint8_t> ldpc_decode(const std::vector<int8_t> &llr, int32_t max_iter, int32_t rate, std::vector<int32_t> *iters = nullptr) {
+        const int32_t k = ofdm_ldpc648_info_bytes(rate);
+        if (k <= 0) throw Error("ldpc_decode: rate must be 0 .. 3");
+        if (llr.size() % 640) throw Error("ldpc_decode: whole code words of 640 LLRs expected");
+        const size_t n_cw = llr.size() / 640;
+        std::vector<uint8_t> out((size_t)k * n_cw);
+        DevBuf din(ctx_, llr.size()), dout(ctx_, out.size()), dit(ctx_, sizeof(int32_t) * n_cw);
+        if (!llr.empty()) check(ofdm_memcpy_h2d(ctx_, din.p, llr.data(), llr.size()), "h2d");
+        check(ofdm_ldpc648_decode_rate_batch(ctx_, (const int8_t *)din.p, 1, (int64_t)llr.size(), (int64_t)n_cw, max_iter, rate, (uint8_t *)dout.p,
+                                             (int64_t)out.size(), (int32_t *)dit.p), "ofdm_ldpc648_decode_rate_batch");
+        if (!out.empty()) check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
+        if (iters) { iters->resize(n_cw); if (n_cw) check(ofdm_memcpy_d2h(ctx_, iters->data(), dit.p, sizeof(int32_t) * n_cw), "d2h"); }
+        return out;
+    }
     // CRC-32 frame check on the device (the OFDM_ECC_FCS + mode contexts apply it inside encode / decode; these are the bare stages):
     // one row -> its envelope [u32 LE n][data][u32 LE crc32 of both], and one delivered row -> the payload of a valid envelope, or
     // nullopt (bytes behind the envelope are ignored)
@@ -486,6 +514,30 @@ inline std::vector<uint8_t> ldpc648_decode(const std::vector<int8_t> &llr, int32
     std::vector<uint8_t> out(llr.size() / 16);
     if (iters) iters->resize(llr.size() / 640);
     check(ofdm_ldpc648_decode(llr.data(), (int64_t)(llr.size() / 640), max_iter, out.data(), iters ? iters->data() : nullptr), "ofdm_ldpc648_decode");
+    return out;
+}
+
+// ... and over the family (rate 0 = 1/2, 1 = 2/3, 2 = 3/4, 3 = 5/6: the codes of OFDM_ECC_LDPC648 / _R23 / _R34 / _R56), K = ldpc648_info_bytes(rate)
+inline int32_t ldpc648_info_bytes(int32_t rate) {
+    const int32_t k = ofdm_ldpc648_info_bytes(rate);
+    if (k <= 0) throw Error("ldpc648_info_bytes: rate must be 0 .. 3");
+    return k;
+}
+inline int64_t ldpc648_coded_len(int64_t payload_bytes, int32_t rate) { return ofdm_ldpc648_coded_len_rate(payload_bytes, rate); }
+inline std::vector<uint8_t> ldpc648_encode(const std::vector<uint8_t> &info, int32_t rate) {
+    const size_t k = (size_t)ldpc648_info_bytes(rate);
+    if (info.size() % k) throw Error("ldpc648_encode: whole blocks of K info bytes expected");
+    std::vector<uint8_t> out(80 * (info.size() / k));
+    check(ofdm_ldpc648_encode_rate(info.data(), (int64_t)(info.size() / k), rate, out.data()), "ofdm_ldpc648_encode_rate");
+    return out;
+}
+inline std::vector<uint8_t> ldpc648_decode(const std::vector<int8_t> &llr, int32_t max_iter, int32_t rate, std::vector<int32_t> *iters = nullptr) {
+    const size_t k = (size_t)ldpc648_info_bytes(rate);
+    if (llr.size() % 640) throw Error("ldpc648_decode: whole code words of 640 LLRs expected");
+    std::vector<uint8_t> out(k * (llr.size() / 640));
+    if (iters) iters->resize(llr.size() / 640);
+    check(ofdm_ldpc648_decode_rate(llr.data(), (int64_t)(llr.size() / 640), max_iter, rate, out.data(), iters ? iters->data() : nullptr),
+          "ofdm_ldpc648_decode_rate");
     return out;
 }
 

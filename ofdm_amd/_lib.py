@@ -89,6 +89,12 @@ SIGNATURES = {
     "ofdm_ldpc648_decode": (C.c_int, [vp, i64, i32, vp, vp]),
     "ofdm_ldpc648_encode_batch": (C.c_int, [vp, vp, i64, i64, i64, vp, i64]),
     "ofdm_ldpc648_decode_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, vp, i64, vp]),
+    "ofdm_ldpc648_info_bytes": (i32, [i32]),
+    "ofdm_ldpc648_coded_len_rate": (i64, [i64, i32]),
+    "ofdm_ldpc648_encode_rate": (C.c_int, [vp, i64, i32, vp]),
+    "ofdm_ldpc648_decode_rate": (C.c_int, [vp, i64, i32, i32, vp, vp]),
+    "ofdm_ldpc648_encode_rate_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, vp, i64]),
+    "ofdm_ldpc648_decode_rate_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, i64, vp]),
     "ofdm_fcs_wrap_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp]),
     "ofdm_fcs_check_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp]),
     "ofdm_rx_llr_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, i64, C.c_float, vp, i64]),

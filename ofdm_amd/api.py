@@ -25,11 +25,16 @@ ECC_CONV_K7F_R12, ECC_CONV_K7F_R23, ECC_CONV_K7F_R34 = 10, 11, 12
 # outer Reed-Solomon(255,223) around the frames of an inner mode, 20 + inner (inner = ECC_NONE or a framed mode): the reference's
 # create_transmission_bytes / decipher_transmission_bytes inside encode / decode, on the device
 ECC_RS255, ECC_RS255_K7F_R12, ECC_RS255_K7F_R23, ECC_RS255_K7F_R34 = 20, 30, 31, 32
-# CRC-32 frame check around any of the eleven modes above, 64 + mode: decode delivers exactly the payload that was sent or reports the
+# CRC-32 frame check around any mode (the LDPC modes below included), 64 + mode: decode delivers exactly the payload that was sent or reports the
 # frame with FRAME_FCS (tests/fcs_ref.py is the definition)
 ECC_FCS = 64
 # LDPC(648,324), rate 1/2, layered min-sum from LLRs; the length travels in the first code word (tests/ldpc_ref.py is the definition)
 ECC_LDPC648 = 16
+# the project's own LDPC(648) codes of rates 2/3, 3/4 and 5/6 under the same frame rule, K = 53 / 60 / 67 info bytes to 80 coded bytes
+# (tests/ldpc_rates_ref.py is the definition); `rate=` of Context.ldpc_encode / ldpc_decode: 0 = 1/2, 1 = 2/3, 2 = 3/4, 3 = 5/6
+ECC_LDPC648_R23, ECC_LDPC648_R34, ECC_LDPC648_R56 = 41, 42, 43
+LDPC_RATE_1_2, LDPC_RATE_2_3, LDPC_RATE_3_4, LDPC_RATE_5_6 = 0, 1, 2, 3
+LDPC_INFO_BYTES = (40, 53, 60, 67)  # ofdm_ldpc648_info_bytes(rate)
 LDPC_MAX_ITER = 20  # OFDM_LDPC_MAX_ITER: iterations the decode chain gives a code word
 FCS_OVERHEAD = 8  # OFDM_FCS_OVERHEAD: the envelope's length word and check word
 CONV_RATE_1_2, CONV_RATE_2_3, CONV_RATE_3_4 = 0, 1, 2
@@ -465,27 +470,45 @@ class Context:
                                                   _dev(fixed)), "rs255_decode_batch")
         return out, out_len, fixed
 
-    def ldpc_encode(self, info: torch.Tensor) -> torch.Tensor:
-        """ofdm_ldpc648_encode_batch: rows of info [n_frames, 40 n_cw] (uint8; the rows may be strided) -> [n_frames, 80 n_cw] code bytes,
-        every 40-byte block coded on its own (LDPC(648,324): the info bytes, then 40 parity bytes)."""
+    @staticmethod
+    def _ldpc_k(rate: int, what: str) -> int:
+        if rate not in (0, 1, 2, 3):
+            raise OfdmError(f"{what}: rate must be 0 (1/2), 1 (2/3), 2 (3/4) or 3 (5/6)")
+        return LDPC_INFO_BYTES[rate]
+
+    def ldpc_encode(self, info: torch.Tensor, rate: int = 0) -> torch.Tensor:
+        """ofdm_ldpc648_encode_batch / _encode_rate_batch: rows of info [n_frames, K n_cw] (uint8; the rows may be strided; K = 40 / 53 /
+        60 / 67 for rate 0 .. 3) -> [n_frames, 80 n_cw] code bytes, every K-byte block coded on its own (the info bytes, then 80 - K
+        parity bytes)."""
+        k = self._ldpc_k(rate, "ldpc_encode")
         n, nb, stride = self._rows_u8(info, "ldpc_encode")
-        if nb % 40:
-            raise OfdmError("ldpc_encode: rows must hold whole 40-byte blocks")
-        out = self.empty((n, 2 * nb), torch.uint8)
+        if nb % k:
+            raise OfdmError(f"ldpc_encode: rows must hold whole {k}-byte blocks")
+        out = self.empty((n, 80 * (nb // k)), torch.uint8)
+        if rate:
+            self._ck(self.lib.ofdm_ldpc648_encode_rate_batch(self.h, _dev(info), n, max(stride, nb), nb // k, rate, _dev(out), out.shape[1]),
+                     "ldpc648_encode_rate_batch")
+            return out
         self._ck(self.lib.ofdm_ldpc648_encode_batch(self.h, _dev(info), n, max(stride, nb), nb // 40, _dev(out), 2 * nb), "ldpc648_encode_batch")
         return out
 
-    def ldpc_decode(self, llr: torch.Tensor, max_iter: int = LDPC_MAX_ITER):
-        """ofdm_ldpc648_decode_batch: rows of llr [n_frames, 640 n_cw] (int8, positive = bit 1; the rows may be strided) -> (bytes
-        [n_frames, 40 n_cw], iters int32 [n_frames, n_cw]): layered normalised min-sum, every code word to convergence or max_iter (1 ..
-        64) iterations; iters = the iteration a code word converged at, 0 if it did not."""
+    def ldpc_decode(self, llr: torch.Tensor, max_iter: int = LDPC_MAX_ITER, rate: int = 0):
+        """ofdm_ldpc648_decode_batch / _decode_rate_batch: rows of llr [n_frames, 640 n_cw] (int8, positive = bit 1; the rows may be
+        strided) -> (bytes [n_frames, K n_cw], iters int32 [n_frames, n_cw]), K = 40 / 53 / 60 / 67 for rate 0 .. 3: layered normalised
+        min-sum, every code word to convergence or max_iter (1 .. 64) iterations; iters = the iteration a code word converged at, 0 if
+        it did not."""
+        k = self._ldpc_k(rate, "ldpc_decode")
         if llr.dtype != torch.int8 or llr.dim() != 2 or llr.device != self.device or (llr.shape[1] > 1 and llr.stride(1) != 1):
             raise OfdmError("ldpc_decode: expected an int8 tensor [n_frames, 640 n_cw] with contiguous rows on the context's device")
         n, width = llr.shape
         if width % 640:
             raise OfdmError("ldpc_decode: rows must hold whole code words of 640 LLRs")
         n_cw = width // 640
-        out, iters = self.empty((n, 40 * n_cw), torch.uint8), self.empty((n, n_cw), torch.int32)
+        out, iters = self.empty((n, k * n_cw), torch.uint8), self.empty((n, n_cw), torch.int32)
+        if rate:
+            self._ck(self.lib.ofdm_ldpc648_decode_rate_batch(self.h, _dev(llr), n, max(llr.stride(0), width) if n > 1 else width, n_cw,
+                                                             int(max_iter), rate, _dev(out), k * n_cw, _dev(iters)), "ldpc648_decode_rate_batch")
+            return out, iters
         self._ck(self.lib.ofdm_ldpc648_decode_batch(self.h, _dev(llr), n, max(llr.stride(0), width) if n > 1 else width, n_cw, int(max_iter),
                                                     _dev(out), 40 * n_cw, _dev(iters)), "ldpc648_decode_batch")
         return out, iters
@@ -528,7 +551,7 @@ class Context:
     def decode_row_bytes(self, max_symbols: int) -> int:
         """Bytes per output row that the decode entry points are given for max_symbols (at least 4).  Modes without an outer code: the
         demodulated body, which bounds what each of them delivers.  ECC_RS255*: 223 (Lmax // 255 + 1), Lmax = the longest row the
-        inner mode can deliver.  ECC_LDPC648: the info bytes of the whole code words less the two length words.  ECC_FCS + mode: mode's
+        inner mode can deliver.  ECC_LDPC648*: the info bytes of the whole code words less the two length words.  ECC_FCS + mode: mode's
         row less the envelope's 8 bytes -- the rules of include/ofdm_hip.h."""
         body = max(max_symbols * self.bytes_per_symbol - 16, 0)
         fcs = self.ecc >= ECC_FCS
@@ -538,8 +561,8 @@ class Context:
             if ecc != ECC_RS255:  # a framed inner mode: the whole bytes of the steps a cut body still holds behind the length block
                 lmax = conv_max_steps(8 * max(body - 18, 0), ecc - ECC_RS255_K7F_R12) // 8
             body = int(self.lib.ofdm_rs255_decoded_len(lmax))
-        if ecc == ECC_LDPC648:
-            body = max(40 * (body // 80) - 8, 0)
+        if ecc in (ECC_LDPC648, ECC_LDPC648_R23, ECC_LDPC648_R34, ECC_LDPC648_R56):
+            body = max(LDPC_INFO_BYTES[0 if ecc == ECC_LDPC648 else ecc - ECC_LDPC648_R23 + 1] * (body // 80) - 8, 0)
         if fcs:
             body = max(body - FCS_OVERHEAD, 0)
         return max(body, 4)

@@ -460,6 +460,12 @@ struct LdpcDecodeParams {
     int bytes_per_symbol = 0;
 };
 hipError_t run_ldpc_decode(const LdpcDecodeParams &p, int num_cu, const Tuning *tune, hipStream_t st);
+// The family (kernels_ldpc_rates.hip): rate 0 = the two kernels above, 1 / 2 / 3 = k_ldpc_encode<r23|r34|r56> and k_ldpc_decode<r23|r34|r56>,
+// the same parameters with K = 53 / 60 / 67 info bytes a code word in place of 40; any other rate: hipErrorInvalidValue.
+hipError_t run_ldpc_rate_encode(const LdpcEncodeParams &p, int rate, int num_cu, const Tuning *tune, hipStream_t st);
+hipError_t run_ldpc_rate_decode(const LdpcDecodeParams &p, int rate, int num_cu, const Tuning *tune, hipStream_t st);
+const char *ldpc_rate_encode_name(int rate); // the dispatch name of the kernel a rate launches
+const char *ldpc_rate_decode_name(int rate);
 
 // ---- EXT-5 channel-estimate denoising (OFDM_CHEST_WLS, ofdm_chest_smooth_batch; kernels_chest.hip, definition: tests/chest_ref.py)
 // rows of n_fft bins times the per-bin weight w (a weight of exactly 0 gives 0 whatever the bin holds); in == out allowed

@@ -13,6 +13,10 @@
 //     R_e = sign_e min((3 m_e) >> 2, 127);  Q_{v_e} = clamp(T_e + R_e, +-2047).
 // After each whole iteration x_v = (Q_v < 0); if all 324 checks hold the code word has CONVERGED at iteration it and stops, otherwise
 // up to max_iter iterations run.  Output: x[0 .. 319] of the last iteration run; iters = it when converged, 0 when not.
+//
+// The family (ofdm_ldpc648_*_rate, rate 0 = 1/2, 1 = 2/3, 2 = 3/4, 3 = 5/6; definition: tests/ldpc_rates_ref.py): the same rule over
+// the table, the K info bytes and the sent map of ldpc_table.h's LdpcCode.  Rate 0 is the code above, and through the _rate functions
+// it gives what the functions above give, byte for byte.
 #include "../../include/ofdm_hip.h"
 #include "ldpc_table.h"
 
@@ -96,6 +100,75 @@ int decode_codeword(const int8_t *llr, int max_iter, uint8_t *out) {
     return iters;
 }
 
+// ---- the family, over one LdpcCode
+void encode_codeword(const LdpcCode &C, const uint8_t *info, uint8_t *code) {
+    const int k = C.info_cols();
+    uint32_t u[kLdpcCols] = {0}, par[kLdpcRows] = {0}, lam[kLdpcRows], p0 = 0;
+    for (int v = 0; v < C.info_bits(); v++)
+        if ((info[v >> 3] >> (v & 7)) & 1) u[v / kLdpcZ] |= 1u << (v % kLdpcZ);
+    for (int l = 0; l < C.rows; l++) {
+        lam[l] = 0;
+        for (int c = 0; c < k; c++)
+            if (C.shift[l][c] >= 0) lam[l] ^= ldpc_rot(u[c], C.shift[l][c]);
+        p0 ^= lam[l];
+    }
+    par[0] = p0;
+    for (int l = 0; l + 1 < C.rows; l++)
+        par[l + 1] = lam[l] ^ (l ? par[l] : 0u) ^ (C.shift[l][k] >= 0 ? ldpc_rot(p0, C.shift[l][k]) : 0u);
+    std::memcpy(code, info, C.info_bytes);
+    std::memset(code + C.info_bytes, 0, kLdpcCodeBytes - C.info_bytes);
+    for (int t = 0; t < C.parity_sent(); t++) // parity bit t = x[648 - M + t]; those behind the 640 sent bits are punctured
+        if ((par[t / kLdpcZ] >> (t % kLdpcZ)) & 1) code[C.info_bytes + (t >> 3)] |= (uint8_t)(1u << (t & 7));
+}
+
+int decode_codeword(const LdpcCode &C, const int8_t *llr, int max_iter, uint8_t *out) {
+    int16_t Q[kLdpcN];
+    int8_t R[kLdpcEdges][kLdpcZ];
+    for (int v = 0; v < kLdpcN; v++) {
+        const int i = C.llr_index(v);
+        Q[v] = (int16_t)(i >= 0 ? -(int)llr[i] : (i == -1 ? kLdpcQMax : 0));
+    }
+    std::memset(R, 0, sizeof(R));
+    int iters = 0;
+    for (int it = 1; it <= max_iter && !iters; it++) {
+        for (int l = 0; l < C.rows; l++) {
+            const int e0 = C.first[l], deg = C.first[l + 1] - e0;
+            for (int z = 0; z < kLdpcZ; z++) {
+                int T[kLdpcCols], var[kLdpcCols];
+                for (int i = 0; i < deg; i++) {
+                    var[i] = kLdpcZ * C.col[e0 + i] + (z + C.sh[e0 + i]) % kLdpcZ;
+                    T[i] = clampi(Q[var[i]] - R[e0 + i][z], kLdpcQMax);
+                }
+                for (int i = 0; i < deg; i++) {
+                    int m = 1 << 30, sign = 1;
+                    for (int j = 0; j < deg; j++) {
+                        if (j == i) continue;
+                        const int a = T[j] < 0 ? -T[j] : T[j];
+                        if (a < m) m = a;
+                        if (T[j] < 0) sign = -sign;
+                    }
+                    int r = (3 * m) >> 2;
+                    if (r > kLdpcRMax) r = kLdpcRMax;
+                    R[e0 + i][z] = (int8_t)(sign * r);
+                    Q[var[i]] = (int16_t)clampi(T[i] + sign * r, kLdpcQMax);
+                }
+            }
+        }
+        bool ok = true;
+        for (int l = 0; l < C.rows && ok; l++)
+            for (int z = 0; z < kLdpcZ && ok; z++) {
+                int par = 0;
+                for (int e = C.first[l]; e < C.first[l + 1]; e++) par ^= Q[kLdpcZ * C.col[e] + (z + C.sh[e]) % kLdpcZ] < 0;
+                ok = !par;
+            }
+        if (ok) iters = it;
+    }
+    std::memset(out, 0, C.info_bytes);
+    for (int v = 0; v < C.info_bits(); v++)
+        if (Q[v] < 0) out[v >> 3] |= (uint8_t)(1u << (v & 7));
+    return iters;
+}
+
 } // namespace
 
 extern "C" {
@@ -115,6 +188,34 @@ int ofdm_ldpc648_decode(const int8_t *llr, int64_t n_cw, int32_t max_iter, uint8
     if (n_cw < 0 || max_iter < 1 || max_iter > kLdpcMaxIterLimit || (n_cw > 0 && (!llr || !out))) return OFDM_ERR_INVALID;
     for (int64_t k = 0; k < n_cw; k++) {
         const int it = decode_codeword(llr + k * kLdpcSentBits, max_iter, out + k * kLdpcInfoBytes);
+        if (iters) iters[k] = it;
+    }
+    return OFDM_OK;
+}
+
+int32_t ofdm_ldpc648_info_bytes(int32_t rate) {
+    if (rate < 0 || rate >= kLdpcRates) return OFDM_ERR_INVALID;
+    return kLdpcCodes[rate].info_bytes;
+}
+
+int64_t ofdm_ldpc648_coded_len_rate(int64_t payload_bytes, int32_t rate) {
+    if (payload_bytes < 0 || rate < 0 || rate >= kLdpcRates) return OFDM_ERR_INVALID;
+    return kLdpcCodeBytes * ldpc_stream_codewords_k(payload_bytes, kLdpcCodes[rate].info_bytes);
+}
+
+int ofdm_ldpc648_encode_rate(const uint8_t *info, int64_t n_cw, int32_t rate, uint8_t *code) {
+    if (rate < 0 || rate >= kLdpcRates || n_cw < 0 || (n_cw > 0 && (!info || !code))) return OFDM_ERR_INVALID;
+    const LdpcCode &C = kLdpcCodes[rate];
+    for (int64_t k = 0; k < n_cw; k++) encode_codeword(C, info + k * C.info_bytes, code + k * kLdpcCodeBytes);
+    return OFDM_OK;
+}
+
+int ofdm_ldpc648_decode_rate(const int8_t *llr, int64_t n_cw, int32_t max_iter, int32_t rate, uint8_t *out, int32_t *iters) {
+    if (rate < 0 || rate >= kLdpcRates || n_cw < 0 || max_iter < 1 || max_iter > kLdpcMaxIterLimit || (n_cw > 0 && (!llr || !out)))
+        return OFDM_ERR_INVALID;
+    const LdpcCode &C = kLdpcCodes[rate];
+    for (int64_t k = 0; k < n_cw; k++) {
+        const int it = decode_codeword(C, llr + k * kLdpcSentBits, max_iter, out + k * C.info_bytes);
         if (iters) iters[k] = it;
     }
     return OFDM_OK;

@@ -879,6 +879,37 @@ int ofdm_ldpc648_decode_batch(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, 
     HIP_TRY(c, run_ldpc_decode(p, c->num_cu, &c->tune, c->stream));
     return OFDM_OK;
 }
+// ... and the family (kernels_ldpc_rates.hip): K = ofdm_ldpc648_info_bytes(rate) info bytes a code word; rate 0 launches the kernels above
+int ofdm_ldpc648_encode_rate_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_t in_stride, int64_t n_cw, int32_t rate, uint8_t *out,
+                                   int64_t out_stride) {
+    if (!c || rate < 0 || rate >= kLdpcRates || n_frames < 0 || n_cw < 0 || n_cw > (int64_t)1 << 40) return OFDM_ERR_INVALID;
+    if (in_stride < kLdpcCodes[rate].info_bytes * n_cw || out_stride < kLdpcCodeBytes * n_cw) return OFDM_ERR_INVALID;
+    if (n_frames && n_cw && (!in || !out)) return OFDM_ERR_INVALID;
+    if (!n_frames || !n_cw) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    LdpcEncodeParams p;
+    p.in = in; p.n_frames = n_frames; p.in_stride = in_stride; p.n_cw = n_cw; p.out = out; p.out_stride = out_stride;
+    c->trace.add(ldpc_rate_encode_name(rate));
+    HIP_TRY(c, run_ldpc_rate_encode(p, rate, c->num_cu, &c->tune, c->stream));
+    return OFDM_OK;
+}
+int ofdm_ldpc648_decode_rate_batch(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, int64_t llr_stride, int64_t n_cw, int32_t max_iter,
+                                   int32_t rate, uint8_t *out, int64_t out_stride, int32_t *iters) {
+    if (!c || rate < 0 || rate >= kLdpcRates || n_frames < 0 || n_cw < 0 || n_cw > (int64_t)1 << 40 || max_iter < 1 || max_iter > kLdpcMaxIterLimit)
+        return OFDM_ERR_INVALID;
+    if (llr_stride < kLdpcSentBits * n_cw || out_stride < kLdpcCodes[rate].info_bytes * n_cw) return OFDM_ERR_INVALID;
+    if (n_frames && n_cw && (!llr || !out)) return OFDM_ERR_INVALID;
+    if (!n_frames || !n_cw) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    LdpcDecodeParams p;
+    p.llr = llr; p.n_frames = n_frames; p.llr_stride = llr_stride; p.n_cw = n_cw; p.max_iter = max_iter; p.out = out; p.out_stride = out_stride;
+    p.iters = iters;
+    c->trace.add(ldpc_rate_decode_name(rate));
+    HIP_TRY(c, run_ldpc_rate_decode(p, rate, c->num_cu, &c->tune, c->stream));
+    return OFDM_OK;
+}
 
 // CRC-32 frame check on device rows (kernels_fcs.hip)
 int ofdm_fcs_wrap_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_t in_stride, const int32_t *in_len, int64_t n_bytes,
@@ -1210,8 +1241,8 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
             LdpcEncodeParams lp;
             lp.in = src; lp.n_frames = n_frames; lp.in_stride = src_stride; lp.n_bytes = src_bytes; lp.in_len = src_len; lp.framed = 1;
             lp.n_cw = coded / kLdpcCodeBytes; lp.out = (uint8_t *)cw; lp.out_stride = coded; lp.out_len = (int32_t *)cl;
-            c->trace.add("k_ldpc_encode");
-            HIP_TRY(c, run_ldpc_encode(lp, c->num_cu, &c->tune, c->stream));
+            c->trace.add(ldpc_rate_encode_name(m.ldpc_rate()));
+            HIP_TRY(c, run_ldpc_rate_encode(lp, m.ldpc_rate(), c->num_cu, &c->tune, c->stream));
         } else {
             HIP_TRY(c, run_ham_encode(src, n_frames, src_stride, src_len, src_bytes, (uint8_t *)cw, coded, (int32_t *)cl, c->stream));
         }
@@ -1257,7 +1288,8 @@ static const int64_t kSoftLlrBytes = 256ll << 20;
 // 4s + 5s of the chain, per frame chunk: hard bytes (for the header) and LLRs in one k_sym<llr>, then ONE finishing kernel -- the header
 // and the ML decode of the body (k_rx_finish_soft); OFDM_ECC_CONV_K7: k_viterbi_k7, which also needs a survivor slab per resident
 // wavefront; OFDM_ECC_CONV_K7F_*: k_viterbi_k7f, which reads the length from its own coded block and may set status;
-// OFDM_ECC_LDPC648: k_ldpc_decode, which reads the length from its first code word and may set status.
+// OFDM_ECC_LDPC648 / _R23 / _R34 / _R56: k_ldpc_decode / k_ldpc_decode<r23|r34|r56>, which reads the length from its first code word and
+// may set status.
 // The LLR workspace holds one chunk: at most kSoftLlrBytes whatever n_frames is.
 static int rx_finish_soft(ofdm_ctx *c, const DecodeCall &d, const SoftInput &s) {
     const ModePlan &m = c->mode;
@@ -1278,7 +1310,7 @@ static int rx_finish_soft(ofdm_ctx *c, const DecodeCall &d, const SoftInput &s) 
         vp.llr = llr; vp.llr_stride = llr_stride; vp.out_stride = d.out_stride;
         vp.raw_stride = s.raw_stride; vp.bytes_per_symbol = bps_bytes;
     }
-    const char *name = m.ldpc() ? "k_ldpc_decode" : !m.conv() ? "k_rx_finish_soft" : m.rate() < 0 ? "k_viterbi_k7" : "k_viterbi_k7f";
+    const char *name = m.ldpc() ? ldpc_rate_decode_name(m.ldpc_rate()) : !m.conv() ? "k_rx_finish_soft" : m.rate() < 0 ? "k_viterbi_k7" : "k_viterbi_k7f";
     for (int64_t f0 = 0; f0 < d.n_frames; f0 += chunk) {
         const int64_t nf = d.n_frames - f0 < chunk ? d.n_frames - f0 : chunk;
         const int32_t *nsym = s.nsym + f0;
@@ -1293,7 +1325,7 @@ static int rx_finish_soft(ofdm_ctx *c, const DecodeCall &d, const SoftInput &s) 
             lp.llr = llr; lp.n_frames = nf; lp.llr_stride = llr_stride; lp.max_iter = OFDM_LDPC_MAX_ITER;
             lp.out = out; lp.out_stride = d.out_stride; lp.status_rw = d.status + f0; lp.out_len = d.out_len + f0;
             lp.nsym = nsym; lp.bytes_per_symbol = bps_bytes;
-            HIP_TRY(c, run_ldpc_decode(lp, c->num_cu, &c->tune, c->stream));
+            HIP_TRY(c, run_ldpc_rate_decode(lp, m.ldpc_rate(), c->num_cu, &c->tune, c->stream));
         } else if (m.conv()) {
             vp.n_frames = nf; vp.out = out; vp.raw = raw; vp.status = d.status + f0; vp.nsym = nsym; vp.out_len = d.out_len + f0;
             if (m.rate() < 0) {

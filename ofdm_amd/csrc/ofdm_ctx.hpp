@@ -13,16 +13,21 @@ enum OuterLayer { kLayerFcs, kLayerRs };
 struct ModePlan {
     int n_outer = 0;
     OuterLayer outer[2] = {};   // outside-in
-    int inner = OFDM_ECC_NONE;  // NONE, HAMMING74, HAMMING74_SOFT, CONV_K7, CONV_K7F_R12 / _R23 / _R34 or LDPC648
+    int inner = OFDM_ECC_NONE;  // NONE, HAMMING74, HAMMING74_SOFT, CONV_K7, CONV_K7F_R12 / _R23 / _R34, LDPC648 or LDPC648_R23 / _R34 / _R56
     bool has(OuterLayer l) const { return (n_outer > 0 && outer[0] == l) || (n_outer > 1 && outer[1] == l); }
     // rate (0 = 1/2, 1 = 2/3, 2 = 3/4) of a framed convolutional inner mode, -1 for every other
     int rate() const { return inner >= OFDM_ECC_CONV_K7F_R12 && inner <= OFDM_ECC_CONV_K7F_R34 ? inner - OFDM_ECC_CONV_K7F_R12 : -1; }
     bool conv() const { return inner == OFDM_ECC_CONV_K7 || rate() >= 0; }
-    bool ldpc() const { return inner == OFDM_ECC_LDPC648; }
+    // rate (0 = 1/2, 1 = 2/3, 2 = 3/4, 3 = 5/6) of an LDPC(648) inner mode, -1 for every other
+    int ldpc_rate() const {
+        if (inner == OFDM_ECC_LDPC648) return 0;
+        return inner >= OFDM_ECC_LDPC648_R23 && inner <= OFDM_ECC_LDPC648_R56 ? inner - OFDM_ECC_LDPC648_R23 + 1 : -1;
+    }
+    bool ldpc() const { return ldpc_rate() >= 0; }
     bool soft() const { return inner == OFDM_ECC_HAMMING74_SOFT || conv() || ldpc(); } // decoded from LLRs
 };
-// The plan of `ecc`; false when ecc is no mode (3 and 4 are none, nor are 21 .. 29 or 36 = RS around LDPC; 64 + a base mode is one).
-// RS goes around OFDM_ECC_NONE and the framed modes only, the frame check around all twelve.
+// The plan of `ecc`; false when ecc is no mode (3 and 4 are none, nor are 21 .. 29 or 36 and 61 .. 63 = RS around LDPC; 64 + a base mode
+// is one).  RS goes around OFDM_ECC_NONE and the framed modes only, the frame check around all fifteen.
 inline bool mode_plan(int ecc, ModePlan *m) {
     *m = ModePlan();
     if (ecc >= OFDM_ECC_FCS) { m->outer[m->n_outer++] = kLayerFcs; ecc -= OFDM_ECC_FCS; }
@@ -37,12 +42,12 @@ inline bool mode_plan(int ecc, ModePlan *m) {
 inline int64_t inner_coded_bytes(const ModePlan &m, int64_t n) {
     if (m.inner == OFDM_ECC_CONV_K7) return 2 * (n + 1); // rate 1/2 over the payload and one tail byte
     if (m.rate() >= 0) return ofdm::kConvLengthBlock + ofdm::conv_body_len(n, m.rate());
-    if (m.ldpc()) return ofdm_ldpc648_coded_len(n);
+    if (m.ldpc()) return ofdm_ldpc648_coded_len_rate(n, m.ldpc_rate());
     return m.inner != OFDM_ECC_NONE ? ((n + 3) / 4) * 7 : n; // the soft decoder reads the same code
 }
 inline int64_t inner_row_limit(const ModePlan &m, int64_t body) {
     if (m.inner == OFDM_ECC_NONE) return body;
-    if (m.ldpc()) return body >= 80 ? 40 * (body / 80) - 8 : 0;                  // the whole code words' info bytes less the two length words
+    if (m.ldpc()) return body >= 80 ? ofdm_ldpc648_info_bytes(m.ldpc_rate()) * (body / 80) - 8 : 0; // the whole code words' info bytes less the two length words
     if (m.inner == OFDM_ECC_CONV_K7) return body / 2 >= 1 ? body / 2 - 1 : 0;    // 4 body steps = body / 2 bytes, less the tail byte
     if (m.rate() >= 0)                               // the steps a body cut at the end of the capture still holds, behind the length block
         return body >= ofdm::kConvLengthBlock ? ofdm::conv_max_steps(8 * (body - ofdm::kConvLengthBlock), m.rate()) / 8 : 0;
