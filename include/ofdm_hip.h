@@ -246,7 +246,16 @@ int ofdm_rs255_decode(const uint8_t *code, int64_t n_code, uint8_t *out, int32_t
  * n_lags bounds the peak window too: it is [d1, min(d1 + W, n_lags - 1)], so a bounded search returns an earlier lag than the
  * full one whenever the true peak lies beyond n_lags - 1 (same rule in the oracle; tests: test_bounded_search_clips_the_peak_window).
  * Any n_fft is served: L = 80 by the one-tile f32-filter / f64-decision kernel, L >= 160 by streaming chunk sums and a bounded
- * exact search whose LDS footprint does not depend on L (N = 4096 included). */
+ * exact search whose LDS footprint does not depend on L (N = 4096 included).
+ * How close to the oracle (orc_sc_sync, direct f64 sums per lag): for N = 64 with W = 3 L (k_sc80) and wherever k_sc_tile decides, no
+ * decision is taken inside the rounding-error bound of the sums it rests on -- such a lag is summed again as the oracle sums it --, so
+ * d_hat is the oracle's at any dynamic range.  The detectors of N >= 128 -- the streaming k_sc_stream and the two-pass k_scb_chunks +
+ * k_scb_fine behind it -- decide on slid prefix differences without such a bound: d_hat is the oracle's unless M lies within 1e-12
+ * of the threshold (or of the maximum) AND a burst earlier in the capture holds more than 2^9 times the window's energy.  Measured:
+ * no difference at a margin of 1e-9 with windows down to 2^-17 of the capture's energy, none at 1e-12 with windows of 2^-9; at 1e-12
+ * k_sc_stream differs in 2 of 8 decisions with windows of 2^-15 and in 2 of 8 with 2^-17, k_scb_fine in none of 4 with 2^-15 and in
+ * 2 of 4 with 2^-17 (tests/test_gpu_sc_margins.py).  ofdm_params.sync_threshold is a float; the tests set thresholds a float cannot
+ * hold through a laboratory key (ofdm_amd/csrc/ofdm_hip_tuning.h). */
 int ofdm_sc_correlate_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t frame_stride,
                             int64_t frame_len, int64_t n_lags, int32_t *d_hat_dev, double *f_delta_dev,
                             float *metric_dev);

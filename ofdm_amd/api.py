@@ -222,6 +222,9 @@ class Context:
         self.bytes_per_symbol = self.lib.ofdm_bytes_per_symbol(h)
         for k, v in {**DEFAULT_TUNING, **(tuning or {})}.items():
             self.set_tuning(k, v)
+        if float(np.float32(sync_threshold)) != float(sync_threshold):
+            # ofdm_params carries the threshold as a float; a double that a float cannot hold goes through the laboratory key
+            self.set_tuning("sync_threshold_bits", int(np.float64(sync_threshold).view(np.int64)))
 
     def close(self):
         if getattr(self, "h", None):

@@ -24,14 +24,25 @@
 // Unit u of a 256-byte piece lands at unit u ^ 8 in the odd rows: the two rows that share a ds_read_b64 pass then hit
 // disjoint banks (5 l' mod 32 and 5 l' + 16 mod 32 are complementary).
 //
-// Exactness.  Decisions are taken on prefix DIFFERENCES, whose absolute error is ~1e-15 of the prefix magnitude.  A window
-// whose energy is below 2^-20 of the energy seen so far is therefore not trusted (unless nothing but zeros came before it,
-// where the difference is exact): if such a lag could matter, the frame goes to the slow list and k_sc_tile redoes it with
-// direct f64 sums.  Never seen on captures with less than 60 dB of dynamic range; all-zero lead-ins stay on this path.
+// Exactness.  Decisions are taken on prefix DIFFERENCES, whose absolute error is at most dl = base_e (t + 32) 2^-52 (base_e: the energy
+// seen so far, t: the period-step).  So no decision is taken inside that bound:
+//   * the crossing: a lag crosses only if it does so with dl against it on every sum; a lag that neither does that nor stays below the
+//     threshold with dl in its favour, in front of the first sure crossing, sends the frame to the slow list;
+//   * the maximum: the row's best must beat every other lag of the window by more than a trusted lane's metric can be wrong (tie(t) =
+//     2 filter_slack (t + 36), about 3e-7 relative at thr = 0.5: a bound on dl / E that needs nothing but the step); a lag that comes that close to the best of its time is kept
+//     as its lane's runner-up, and a runner-up inside the bound sends the frame to the slow list;
+//   * a window whose energy is below 2^-20 of the energy seen so far (other than an exact zero behind nothing but zeros) is not
+//     trusted at all: if such a lag could matter under the same bound, the frame goes to the slow list.
+// k_sc_tile redoes the slow list: sliding f64 sums under an error bound of their own, and the oracle's own per-lag sums in the
+// oracle's order wherever that bound could turn a decision (kernels_sync.hip).  tests/test_gpu_sc_margins.py puts the threshold within
+// 1e-12 of a lag's metric behind bursts that leave the windows 2^-17 of the capture's energy: every such case is the oracle's.
+// Ordinary captures do not reach the list: the metric of a lag in front of the crossing would have to lie within ~1e-13 of the
+// threshold, or the window's two best metrics within ~3e-7 of each other (none of 1 M config-3 slots does); all-zero lead-ins stay here.
 // Roofline: HBM, 8 B per sample actually needed (the slot up to d1 + 2 W + L, rounded up to pieces).
 #include "device_common.hpp"
 #include "kernels.hpp"
 #include <limits.h>
+#include <cmath>
 
 namespace ofdm {
 
@@ -44,6 +55,7 @@ struct S80Params {
     long long n_frames, frame_stride, frame_len;
     int n_lags;
     double threshold;
+    double filter_slack;   // per (period-step + 32): how far below the threshold the crossing filter reaches (launch_sc80)
     int32_t *d_hat;
     ScExact *exact;
     int32_t *slow_list, *slow_count;
@@ -86,6 +98,19 @@ __device__ __forceinline__ S8Cand s8_row_best(S8Cand c) {
     c = s8_pick(c, s8_cand_dpp<0x140>(c));   // row_mirror
     return c;
 }
+// the runner-up of a peak window needs no lag and no P: only how close it came
+struct S8Sec { double num, den; };
+template <int CTRL> __device__ __forceinline__ S8Sec s8_sec_max(S8Sec a) {
+    const S8Sec b = S8Sec{s8_dpp<CTRL>(a.num), s8_dpp<CTRL>(a.den)};
+    return b.num * a.den > a.num * b.den ? b : a;
+}
+__device__ __forceinline__ S8Sec s8_row_sec(S8Sec c) {
+    c = s8_sec_max<0xB1>(c);
+    c = s8_sec_max<0x4E>(c);
+    c = s8_sec_max<0x141>(c);
+    c = s8_sec_max<0x140>(c);
+    return c;
+}
 __device__ __forceinline__ int s8_row_min(int x) {
     x = min(x, s8_dpp_i<0xB1>(x));
     x = min(x, s8_dpp_i<0x4E>(x));
@@ -106,7 +131,7 @@ struct S8State {
     int d1, hi;                   // first crossing (-1: none yet), last lag of the peak window
     bool done, amb;
     S8Cand best;                  // this lane's first maximum among its own lags of the window
-    unsigned limit;               // the last 16-byte unit of the slot this row still needs (byte offset)
+    S8Sec second;                 // ... and the best of its other lags that came close to the best of their time
 };
 
 } // namespace
@@ -131,6 +156,7 @@ __global__ __launch_bounds__(64, 2) void k_sc80(S80Params p) {
     const int n = p.n_lags;
     const double thr = p.threshold;
     const double thr_f = thr * (1.0 - 8.8817841970012523e-16);   // the filter's threshold: a hair lower, so that the rounding of thr * den can never hide a crossing from it
+    const double slack = p.filter_slack;
     const long long groups = (p.n_frames + 3) >> 2;
 
     // ring pieces whose last byte is read by step 0 .. 5 of the six-step body (first piece, count), and the pieces issued before a
@@ -170,7 +196,7 @@ __global__ __launch_bounds__(64, 2) void k_sc80(S80Params p) {
         s.d1 = -1; s.hi = n - 1;
         s.done = !live; s.amb = false;
         s.best = S8Cand{-1.0, 1.0, 0.0, 0.0, INT_MAX};
-        s.limit = limit0;
+        s.second = S8Sec{-1.0, 1.0};
 
         unsigned round_byte = 0;   // stream byte of ring slot 0 in this round
         int t0 = 0;                // period of the body's first step
@@ -193,8 +219,9 @@ __global__ __launch_bounds__(64, 2) void k_sc80(S80Params p) {
             {
                 constexpr int SF = (S - D + 6) % 6;
                 const unsigned base = round_byte + (S >= D ? 3840u : 0u);
+                const unsigned limit = ((unsigned)(s.hi + 319) * 8u) & ~15u;   // the last 16-byte unit lag hi's window reads: nothing beyond it is needed (limit0 until the crossing is known)
 #pragma unroll
-                for (int k = F0[SF]; k < F0[SF] + FN[SF]; ++k) issue_at(sb, rowoff, s.limit, k, base + 256u * k);
+                for (int k = F0[SF]; k < F0[SF] + FN[SF]; ++k) issue_at(sb, rowoff, limit, k, base + 256u * k);
             }
 
             // e of period t, q of period t - 1, their in-lane exclusive partial sums
@@ -228,8 +255,13 @@ __global__ __launch_bounds__(64, 2) void k_sc80(S80Params p) {
             }
             // (smallest difference by its high word: doubles of either sign order like their high words as signed integers
             // down to 2^-20 relative, which is all a trust threshold needs)
-            const int ehi = min(min(min(__double2hiint(En[0]), __double2hiint(En[1])), min(__double2hiint(En[2]), __double2hiint(En[3]))), __double2hiint(En[4]));
-            const bool okn = zero_before || ehi >= __double2hiint(s.base_e * 9.5367431640625e-7);
+            // Behind nothing but zeros a difference that is zero is an exact zero (no metric at that lag) and passes; the others are
+            // held to the bound there too, so that every trusted sum is either 0 or at least 2^-20 of the energy seen so far.
+            int eh[5];
+#pragma unroll
+            for (int j = 0; j < 5; ++j) { eh[j] = __double2hiint(En[j]); eh[j] = (zero_before && eh[j] == 0) ? INT_MAX : eh[j]; }
+            const int ehi = min(min(min(eh[0], eh[1]), min(eh[2], eh[3])), eh[4]);
+            const bool okn = ehi >= __double2hiint(s.base_e * 9.5367431640625e-7);
 
             if (t >= 4) {   // (wave-uniform) the lags of period t - 4: E = last step's differences, R = this step's
                 const int d0 = 80 * (t - 4) + 5 * lp;
@@ -253,24 +285,38 @@ __global__ __launch_bounds__(64, 2) void k_sc80(S80Params p) {
                     }
                 }
                 if (__builtin_amdgcn_ballot_w64(cnt > 0 && s.d1 < 0)) {   // some row is still looking for its crossing
-                    // filter: num - thr den >= 0 at any of the five lags (sign bits of five fused multiply-adds); the block below decides
-                    // exactly, also about lags beyond cnt and all-zero windows (0 >= 0), which the filter lets through
+                    // filter: num - thr den >= 0 at any of the five lags (sign bits of five fused multiply-adds), with the threshold lowered
+                    // by more than the sums of a trusted lane can be wrong at this step (every trusted sum is 0 or >= 2^-20 base_e, so dl
+                    // is at most 2^20 (t + 32) 2^-52 of it: launch_sc80 turns that into filter_slack).  The block below decides, also
+                    // about lags beyond cnt and all-zero windows (0 >= 0), which the filter lets through.
+                    const double thr_w = thr_f * fmax(0.0, 1.0 - slack * (double)(t + 32));
                     int sg = -1;
 #pragma unroll
-                    for (int j = 0; j < 5; ++j) sg &= __double2hiint(fma(-thr_f, den[j], num[j]));
+                    for (int j = 0; j < 5; ++j) sg &= __double2hiint(fma(-thr_w, den[j], num[j]));
                     const bool any = sg >= 0 && ok && s.d1 < 0 && cnt > 0;
                     if (__builtin_amdgcn_ballot_w64(any)) {   // (about once per frame) a row's first crossing may be in this step
-                        int mine = INT_MAX;
+                        // A lag crosses for sure when it does so with the worst-case rounding error dl of the prefixes against it on
+                        // every sum, and surely does not when it fails with dl in its favour; a lag in between is the oracle's to
+                        // decide, and if it lies in front of the first sure crossing the frame goes to the slow list.
+                        const double dl = s.base_e * (double)(t + 32) * 2.220446049250313e-16;
+                        int mine = INT_MAX, doubt = INT_MAX;
 #pragma unroll
                         for (int j = 4; j >= 0; --j) {
-                            const double td = thr * den[j];
-                            if (j < cnt && num[j] >= td && td > 0.0) mine = d0 + j;
+                            const double pa = fabs(Pr[j]) + fabs(Pi[j]);
+                            const double el = s.Ep[j] - dl, rl = En[j] - dl;
+                            const bool pos = el > 0.0 && rl > 0.0;
+                            const bool zero = s.Ep[j] == 0.0 || En[j] == 0.0;   // a trusted lane's zero is exact: no metric at this lag
+                            const bool sure = pos && num[j] - 4.0 * dl * pa >= thr * ((s.Ep[j] + dl) * (En[j] + dl));
+                            const bool never = zero || (pos && num[j] + 4.0 * dl * (pa + dl) < thr * (el * rl));
+                            if (j < cnt && sure) mine = d0 + j;
+                            if (j < cnt && !sure && !never) doubt = d0 + j;
                         }
-                        const int c = s8_row_min(any ? mine : INT_MAX);
+                        const int cs = s8_row_min(any ? mine : INT_MAX), cd = s8_row_min(any ? doubt : INT_MAX);
+                        if (s.d1 < 0 && cd < cs) s.amb = true;
+                        const int c = min(cs, cd);   // (a doubtful lag ends the search as a crossing would: the verdict is k_sc_tile's then)
                         if (s.d1 < 0 && c != INT_MAX) {
                             s.d1 = c;
                             s.hi = c + 240 < n - 1 ? c + 240 : n - 1;
-                            s.limit = ((unsigned)(s.hi + 319) * 8u) & ~15u;   // nothing beyond lag hi's window is needed any more
                         }
                     }
                 }
@@ -279,10 +325,33 @@ __global__ __launch_bounds__(64, 2) void k_sc80(S80Params p) {
                     int lo = s.d1 - d0;
                     lo = lo < 0 ? 0 : lo;
                     const bool live_lane = ok && s.d1 >= 0;
+                    // A maximum must not be picked inside the sums' error.  A trusted lane's metric is wrong by at most
+                    // (2 + 5.7 / sqrt(M)) 2^20 (t + 32) 2^-52 relative, and M >= thr near a maximum: two metrics closer than
+                    // tie(t) = 2 filter_slack (t + 36) -- room for a rival judged up to four steps later -- are the oracle's to rank.
+                    // The loser of such a comparison is kept as the lane's runner-up (rare: the block below is skipped otherwise);
+                    // a lag that never comes that close to the best of its time cannot come that close to the final best.
+                    const double tie = fmin(0.5, 2.0 * slack * (double)(t + 36));
+                    const S8Sec start = S8Sec{s.best.num, s.best.den};
+                    bool any_near = false;
 #pragma unroll
                     for (int j = 0; j < 5; ++j) {
-                        const bool beats = num[j] * s.best.den > s.best.num * den[j];
-                        if (live_lane && j < cnt && j >= lo && beats) s.best = S8Cand{num[j], den[j], Pr[j], Pi[j], d0 + j};
+                        const bool in = live_lane && j < cnt && j >= lo;
+                        const double lhs = num[j] * s.best.den, rhs = s.best.num * den[j];
+                        any_near |= in && s.best.num >= 0.0 && fabs(lhs - rhs) <= tie * fabs(rhs);
+                        if (in && lhs > rhs) s.best = S8Cand{num[j], den[j], Pr[j], Pi[j], d0 + j};
+                    }
+                    if (__builtin_amdgcn_ballot_w64(any_near)) {   // (rare) the same walk again from the step's first best, keeping the losers
+                        S8Sec b0 = start;
+#pragma unroll
+                        for (int j = 0; j < 5; ++j) {
+                            const bool in = live_lane && j < cnt && j >= lo;
+                            const double lhs = num[j] * b0.den, rhs = b0.num * den[j];
+                            const bool beats = lhs > rhs;
+                            const bool close = in && fabs(lhs - rhs) <= tie * fabs(rhs) && b0.num >= 0.0;
+                            const S8Sec loser = beats ? b0 : S8Sec{num[j], den[j]};
+                            if (close && loser.num * s.second.den > s.second.num * loser.den) s.second = loser;
+                            if (in && beats) b0 = S8Sec{num[j], den[j]};
+                        }
                     }
                 }
                 const int last = 80 * (t - 4) + 79;   // every lag up to here has been judged
@@ -319,6 +388,15 @@ __global__ __launch_bounds__(64, 2) void k_sc80(S80Params p) {
         }
         // ---- the row's verdict: first maximum over its lanes; a row that met an untrusted lag goes to the slow list
         const S8Cand b = s8_row_best(s.best);
+        // ... which must beat the best of all other lags of the window (the other lanes' bests, the winner lane's runner-up) by more
+        // than the metrics of trusted lanes can be wrong: a maximum inside that bound is the oracle's to pick
+        S8Sec mine2 = S8Sec{s.best.num, s.best.den};
+        if (s.best.lag == b.lag) mine2 = s.second;
+        const S8Sec b2 = s8_row_sec(mine2);
+        if (b.lag != INT_MAX && b2.num >= 0.0) {
+            const double tie = fmin(0.5, 2.0 * slack * (double)(s.hi / 80 + 4 + 36));   // (hi / 80 + 4: the step that judged lag hi)
+            if (b2.num * b.den >= b.num * b2.den * (1.0 - tie)) s.amb = true;
+        }
         const unsigned long long ambm = __builtin_amdgcn_ballot_w64(s.amb);
         const bool row_amb = ((ambm >> (16 * row)) & 0xFFFFull) != 0ull;
         if (lp == 0 && live) {
@@ -364,6 +442,9 @@ hipError_t launch_sc80(const ScParams &p, ScExact *exact, int32_t *slow_list, in
     S80Params q;
     q.in = p.in; q.n_frames = p.n_frames; q.frame_stride = p.n_frames > 1 ? p.frame_stride : 0; q.frame_len = p.frame_len + (p.frame_len & 1);
     q.n_lags = (int)p.n_lags; q.threshold = p.threshold;
+    // With a = dl / min(E, R), a lag that is not surely below the threshold has num >= thr E R (1 - 2 a - 5.7 a / sqrt(thr)); trusted
+    // sums have a <= 2^20 (t + 32) 2^-52 (1 + 2^-20).  Half as much again on top.
+    q.filter_slack = 1.5 * (2.0 + 6.0 / std::sqrt(p.threshold)) * 1048576.0 * 2.220446049250313e-16;
     q.d_hat = p.d_hat; q.exact = exact; q.slow_list = slow_list; q.slow_count = slow_count;
     const Tuning &tu = tuning_or_default(p.tune);
     // one wavefront (four frames) per workgroup, two per SIMD; 15 KB of LDS each

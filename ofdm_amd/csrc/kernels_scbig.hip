@@ -19,8 +19,12 @@
 //                  d0+L, d0+W, d0+W+L) are staged into LDS, each thread slides the three sums over its 5 / 10 lags in f64 from the
 //                  tile's boundary sums
 //                  (prefix differences), a workgroup scan chains the threads.
-// Every decision is taken on f64 sums, as k_sc_tile does: timing indices equal the f64 oracle's except on ties below f64
-// resolution.  Works for any N in 128..4096 (the LDS footprint does not depend on L) and any capture of up to 2047 chunks.
+// Every decision is taken on f64 sums, but on prefix differences of chunk totals slid lag by lag, WITHOUT an error bound (k_sc80 and
+// k_sc_tile have one): timing indices equal the f64 oracle's while a decision is not closer than the prefixes' rounding, about 2^-52
+// of the capture's energy over the window's.  Measured (MI355X, tests/test_gpu_sc_margins.py, N = 2048, searches that end at the lag
+// in question): with the threshold within 1e-9 of a lag's metric every case is the oracle's, also behind a burst that leaves the
+// windows 2^-17 of the capture's energy; within 1e-12 every case is down to windows of 2^-15, and 2 of 4 decisions differ behind the
+// burst that leaves 2^-17.  Ties below f64 resolution aside.  Works for any N in 128..4096 (the LDS footprint does not depend on L) and any capture of up to 2047 chunks.
 #include "device_common.hpp"
 #include "kernels.hpp"
 #include <limits.h>

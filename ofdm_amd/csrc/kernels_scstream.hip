@@ -20,8 +20,13 @@
 //     (their 36 samples come back from L2); inside the peak window an interval stays on a short live list only while its bound
 //     reaches the best exact value seen so far, and the list is evaluated exactly when the window closes (or the list is full);
 //   * then the wavefront writes d_hat, CFO = arg P / L, M and moves on: the rest of the frame is never fetched.
-// Every decision is taken on f64 sums, as in k_sc_tile / k_scb_fine: timing indices equal the f64 oracle's except on ties below
-// f64 resolution.  Roofline: HBM, 8 B per sample actually needed; the bench reports achieved rates against the WHOLE capture.
+// Every decision is taken on f64 sums, but on prefix differences slid lag by lag, WITHOUT an error bound (k_sc80 and k_sc_tile have
+// one): timing indices equal the f64 oracle's while a decision is not closer than the prefixes' rounding, about 2^-52 of the energy
+// streamed so far over the window's.  Measured (MI355X, tests/test_gpu_sc_margins.py, N = 256 / 1024 / 2048): with the threshold
+// within 1e-9 of a lag's metric every case is the oracle's, also behind a burst that leaves the windows 2^-17 of the capture's
+// energy; within 1e-12 every case is while the windows hold 2^-9 of the energy or more, and 2 of 8 decisions differ behind each of the
+// bursts that leave 2^-15 and 2^-17.  Ties below f64 resolution aside.
+// Roofline: HBM, 8 B per sample actually needed; the bench reports achieved rates against the WHOLE capture.
 #include "device_common.hpp"
 #include "kernels.hpp"
 #include <limits.h>

@@ -5,8 +5,14 @@
 // thread then owns C = 10 consecutive lags and advances the three sliding sums by the exact update
 //     P(d+1) = P(d) + conj(r[d+W]) r[d+W+L] - conj(r[d]) r[d+L]     (same for E, R)
 // A wavefront-shuffle scan over the per-thread totals (plus a 4-entry LDS step across the waves) turns the
-// local prefixes into the sums at every lag.  All sums are f64: products of f32 samples are exact in f64, so
-// the integer outputs (first threshold crossing, argmax) agree bit-for-bit with the f64 CPU oracle.
+// local prefixes into the sums at every lag.  All sums are f64 and products of f32 samples are exact in f64, but a slid sum
+// still carries the roundings of everything that slid through it: at most dl = 2^-45 of the energy of the staged samples, on
+// every sum of the tile.  A crossing decision that dl could turn, and every lag that could be the maximum within dl when there
+// is more than one, is therefore summed again by one thread as the oracle sums it (sc_direct: the W products in order, bit for
+// bit the oracle's P, E, R) and decided on that.  So the integer outputs (first threshold crossing, argmax) are the f64 CPU
+// oracle's whatever the dynamic range (tests/test_gpu_sc_margins.py).  A window in front of the first or behind the last staged
+// sample that is not zero is an exact zero and takes neither look; ordinary captures take the second one only at the few lags whose
+// windows just begin to fill (64 captures with a 20 000-sample zero lead-in, N = 64: 0.038 ms with plain slid sums, 0.061 ms now).
 //
 // Roofline: HBM.  Algorithmic traffic is 8 B per input sample + 16 B per frame of results; the halo of W + L
 // samples per tile is re-read from L2.  ~45 f64-rate VALU ops per lag (MI355X: f64 vector = 1/2 f32 rate).
@@ -38,6 +44,23 @@ __device__ __forceinline__ Cand c_shfl_down(Cand a, int d) {
                 __shfl_down(a.pi, d, 64), __shfl_down(a.lag, d, 64)};
 }
 
+// The oracle's own sums at one lag (orc_sc_sync's sc_at): one thread, the W products in order.  Products of f32 samples are exact in
+// f64, so every step rounds as the oracle's does (fused or not): P, E, R come out bit for bit.
+__device__ __forceinline__ Sums sc_direct(const cf *raw, int lag, int L, int W) {
+    Sums y = Sums{0, 0, 0, 0};
+    for (int m = 0; m < W; ++m) {
+        const cf a = raw[lag + m], b = raw[lag + m + L];
+        const double ar = a.x, ai = a.y, br = b.x, bi = b.y;
+        y.pr += ar * br + ai * bi;
+        y.pi += ar * bi - ai * br;
+        y.e += ar * ar + ai * ai;
+        y.r += br * br + bi * bi;
+    }
+    return y;
+}
+// ... and its num and den (no fused multiply-add: the oracle is compiled without contraction)
+__device__ __forceinline__ double sc_num(Sums y) { return __dadd_rn(__dmul_rn(y.pr, y.pr), __dmul_rn(y.pi, y.pi)); }
+
 __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int span = SC_CH + p.W + p.L;
@@ -45,6 +68,8 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
     Sums *wsum = reinterpret_cast<Sums *>(smem + (size_t)span * sizeof(cf)); // [4] wave totals
     Cand *wcand = reinterpret_cast<Cand *>(wsum + 4);                          // [4]
     int *wmin = reinterpret_cast<int *>(wcand + 4);                            // [4]
+    double *wtot = reinterpret_cast<double *>(wmin + 4);                       // [4] wave totals of the staged energy, then [2] the peak's bounds
+    int *wnz = reinterpret_cast<int *>(wtot + 4);                              // [8] per wave: first and last staged sample that is not zero
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int L = p.L, W = p.W;
@@ -91,6 +116,25 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
     }
     __syncthreads();
 
+    // ---- the energy of everything staged bounds every intermediate value of the sliding sums below: about a hundred roundings lie
+    //      between the samples and a lag's sums, each at most 2^-53 of twice that energy -> dl = 2^-45 of it bounds the error of every
+    //      sum at every lag of the tile.  A decision that dl could turn is taken again on the oracle's own sums (sc_direct).
+    //      A window in front of the first or behind the last staged sample that is not zero (lead-ins, padding, the zeros staged beyond
+    //      the frame) is an exact zero: the oracle gives such a lag no metric, and neither look is needed.
+    double tot = 0.0;
+    int nz0 = INT_MAX, nz1 = -1;
+    for (int i = tid; i < span; i += SC_WG) {
+        const cf a = raw[i];
+        tot += (double)a.x * a.x + (double)a.y * a.y;
+        if (a.x != 0.f || a.y != 0.f) { nz0 = nz0 < i ? nz0 : i; nz1 = i; }
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        tot += __shfl_xor(tot, s, 64);
+        const int o0 = __shfl_xor(nz0, s, 64), o1 = __shfl_xor(nz1, s, 64);
+        nz0 = o0 < nz0 ? o0 : nz0; nz1 = o1 > nz1 ? o1 : nz1;
+    }
+    if (lane == 0) { wtot[wave] = tot; wnz[wave] = nz0; wnz[4 + wave] = nz1; }
     // ---- sums at the tile's first lag: WG reduction over the W products
     Sums x0 = Sums{0, 0, 0, 0};
     for (int m = tid; m < W; m += SC_WG) {
@@ -106,6 +150,10 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
     if (lane == 0) wsum[wave] = x0;
     __syncthreads();
     x0 = s_add(s_add(wsum[0], wsum[1]), s_add(wsum[2], wsum[3]));
+    const double dl = ((wtot[0] + wtot[1]) + (wtot[2] + wtot[3])) * 2.8421709430404007e-14;
+    const int nz_first = min(min(wnz[0], wnz[1]), min(wnz[2], wnz[3])), nz_last = max(max(wnz[4], wnz[5]), max(wnz[6], wnz[7]));
+    // E or R of lag d (relative to the tile) is a sum of zeros
+    auto zero_window = [&](int d) { return d + W <= nz_first || d > nz_last || d + L + W <= nz_first || d + L > nz_last; };
     __syncthreads();
 
     // ---- per-thread updates for its C lags, local inclusive prefix
@@ -151,8 +199,18 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
 #pragma unroll
         for (int j = SC_C - 1; j >= 0; --j) {
             Sums x = j ? s_add(base, pre[j - 1]) : base;
-            double num = x.pr * x.pr + x.pi * x.pi, den = x.e * x.r;
-            if (a0 + j < n && den > 0.0 && num >= thr * den) mine = a0 + j;
+            double num = x.pr * x.pr + x.pi * x.pi;
+            const double pa = fabs(x.pr) + fabs(x.pi), el = x.e - dl, rl = x.r - dl;
+            const bool pos = el > 0.0 && rl > 0.0;
+            bool cross = pos && num - 4.0 * dl * pa >= thr * ((x.e + dl) * (x.r + dl));
+            const bool never = pos && num + 4.0 * dl * (pa + dl) < thr * (el * rl);
+            // (rare) inside the bound: the oracle's sums decide
+            if (a0 + j < n && !cross && !never && !zero_window(a0 + j)) {
+                const Sums y = sc_direct(raw, a0 + j, L, W);
+                const double den = __dmul_rn(y.e, y.r);
+                cross = den > 0.0 && sc_num(y) >= __dmul_rn(thr, den);
+            }
+            if (a0 + j < n && cross) mine = a0 + j;
         }
 #pragma unroll
         for (int s = 32; s >= 1; s >>= 1) { int o = __shfl_xor(mine, s, 64); mine = o < mine ? o : mine; }
@@ -169,24 +227,65 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
             continue;
         }
     }
-    // ---- (B) first maximum of M over [d1, d1 + W]
+    // ---- (B) first maximum of M over [d1, d1 + W]: on the sliding sums first.  Then every lag whose metric, with dl in its favour on
+    //      every sum, still reaches that maximum's with dl against it is a contender; where there is one besides the maximum itself
+    //      (rare), the contenders are summed again as the oracle sums them and the first maximum among those is the answer.
     Cand best = Cand{-1.0, 1.0, 0.0, 0.0, -1};
 #pragma unroll
     for (int j = 0; j < SC_C; ++j) {
         const int lag = a0 + j;
         Sums x = j ? s_add(base, pre[j - 1]) : base;
         double num = x.pr * x.pr + x.pi * x.pi, den = x.e * x.r;
-        if (lag < n && lag >= d1 && lag <= d1 + W && den > 0.0) best = c_pick(best, Cand{num, den, x.pr, x.pi, lag});
+        if (lag < n && lag >= d1 && lag <= d1 + W && den > 0.0 && !zero_window(lag)) best = c_pick(best, Cand{num, den, x.pr, x.pi, lag});
     }
+    auto wg_best = [&](Cand c) {   // first maximum over the workgroup, in every thread
 #pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        Cand o = c_shfl_down(best, s);
-        if (lane + s < 64) best = c_pick(best, o);
+        for (int s = 1; s < 64; s <<= 1) {
+            Cand o = c_shfl_down(c, s);
+            if (lane + s < 64) c = c_pick(c, o);
+        }
+        __syncthreads();
+        if (lane == 0) wcand[wave] = c;
+        __syncthreads();
+        return c_pick(c_pick(wcand[0], wcand[1]), c_pick(wcand[2], wcand[3]));
+    };
+    Cand b = wg_best(best);
+    {
+        // the maximum's owner publishes its bounds: num from below, den from above
+#pragma unroll
+        for (int j = 0; j < SC_C; ++j) {
+            Sums x = j ? s_add(base, pre[j - 1]) : base;
+            if (a0 + j == b.lag) {
+                wtot[0] = b.num - 4.0 * dl * (fabs(x.pr) + fabs(x.pi));
+                wtot[1] = (x.e + dl) * (x.r + dl);
+            }
+        }
+        __syncthreads();
+        const double ref_nlo = b.lag >= 0 ? wtot[0] : 0.0, ref_dhi = b.lag >= 0 ? wtot[1] : 1.0;   // (no maximum yet: every lag contends)
+        unsigned contend = 0;   // bit j: lag a0 + j could be the oracle's maximum
+#pragma unroll
+        for (int j = 0; j < SC_C; ++j) {
+            const int lag = a0 + j;
+            Sums x = j ? s_add(base, pre[j - 1]) : base;
+            const double num = x.pr * x.pr + x.pi * x.pi, el = x.e - dl, rl = x.r - dl;
+            const bool pos = el > 0.0 && rl > 0.0;
+            const bool out = pos && (num + 4.0 * dl * (fabs(x.pr) + fabs(x.pi) + dl)) * ref_dhi < ref_nlo * (el * rl);
+            if (lag < n && lag >= d1 && lag <= d1 + W && !out && !zero_window(lag)) contend |= 1u << j;
+        }
+        const unsigned others = b.lag >= a0 && b.lag < a0 + SC_C ? contend & ~(1u << (b.lag - a0)) : contend;
+        if (__syncthreads_or(others != 0u)) {
+            Cand exact = Cand{-1.0, 1.0, 0.0, 0.0, -1};
+#pragma unroll
+            for (int j = 0; j < SC_C; ++j)
+                if (contend >> j & 1u) {
+                    const Sums y = sc_direct(raw, a0 + j, L, W);
+                    const double den = __dmul_rn(y.e, y.r);
+                    if (den > 0.0) exact = c_pick(exact, Cand{sc_num(y), den, y.pr, y.pi, a0 + j});
+                }
+            b = wg_best(exact);
+        }
     }
-    if (lane == 0) wcand[wave] = best;
-    __syncthreads();
     if (tid == 0) {
-        Cand b = c_pick(c_pick(wcand[0], wcand[1]), c_pick(wcand[2], wcand[3]));
         if (b.lag < 0) { p.d_hat[f] = -1; if (p.f_delta) p.f_delta[f] = 0.0; if (p.metric) p.metric[f] = 0.f; }
         else {
             p.d_hat[f] = (int32_t)(d0 + b.lag);
@@ -198,7 +297,8 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
 }
 
 size_t sc_lds_bytes(const ScParams &p) {
-    return (size_t)(SC_CH + p.W + p.L) * sizeof(float2) + 4 * sizeof(Sums) + 4 * sizeof(Cand) + 4 * sizeof(int) + 64;
+    // samples, wsum[4], wcand[4], wmin[4], wtot[4], wnz[8]
+    return (size_t)(SC_CH + p.W + p.L) * sizeof(float2) + 4 * sizeof(Sums) + 4 * sizeof(Cand) + 4 * sizeof(int) + 4 * sizeof(double) + 8 * sizeof(int);
 }
 
 hipError_t run_sc(const ScParams &p, hipStream_t st) {

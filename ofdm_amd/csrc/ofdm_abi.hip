@@ -501,6 +501,13 @@ const TuneKey kTuneKeys[] = { // the laboratory keys: ofdm_hip_tuning.h (private
 int ofdm_set_tuning(ofdm_ctx *c, const char *key, int64_t value) {
     if (!c || !key) return OFDM_ERR_INVALID;
     if (std::strcmp(key, "grid_cap") == 0) { if (value < 0) return OFDM_ERR_INVALID; c->tune.grid_cap = value; return OFDM_OK; }
+    if (std::strcmp(key, "sync_threshold_bits") == 0) { // the threshold as the bit pattern of a double (ofdm_hip_tuning.h); 0 = the params' float again
+        double thr;
+        std::memcpy(&thr, &value, sizeof(thr));
+        if (value != 0 && !(thr > 0.0 && thr <= 1.0)) return OFDM_ERR_INVALID;
+        c->sync_threshold_f64 = thr;
+        return OFDM_OK;
+    }
     for (const TuneKey &k : kTuneKeys)
         if (std::strcmp(key, k.name) == 0) {
             if (k.profile_only && !kProfile) return OFDM_ERR_UNSUPPORTED; // the ablation branches are not in this build
@@ -519,6 +526,7 @@ int ofdm_get_tuning(const ofdm_ctx *c, const char *key, int64_t *value) {
     if (!c || !key || !value) return OFDM_ERR_INVALID;
     if (std::strcmp(key, "grid_cap") == 0) { *value = c->tune.grid_cap; return OFDM_OK; }
     if (std::strcmp(key, "profile_build") == 0) { *value = kProfile ? 1 : 0; return OFDM_OK; }
+    if (std::strcmp(key, "sync_threshold_bits") == 0) { std::memcpy(value, &c->sync_threshold_f64, sizeof(*value)); return OFDM_OK; }
     if (std::strcmp(key, "stat_sc_slow_frames") == 0 || std::strcmp(key, "stat_sc_redo_frames") == 0) {
         // counters of the LAST Schmidl-Cox search of this context (synchronises its stream); -1 when that search kept no such list
         const bool slow = key[8] == 's';
@@ -945,7 +953,7 @@ static bool sc_make_params(ofdm_ctx *c, const float2 *in, int64_t n_frames, int6
     if (valid <= 0) return false;
     if (n_lags <= 0 || n_lags > valid) n_lags = valid;
     p.in = in; p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len; p.n_lags = n_lags;
-    p.L = L; p.W = W; p.threshold = (double)c->prm.sync_threshold;
+    p.L = L; p.W = W; p.threshold = c->sync_threshold_f64 > 0.0 ? c->sync_threshold_f64 : (double)c->prm.sync_threshold;
     p.d_hat = d_hat; p.f_delta = f_delta; p.metric = metric;
     p.tiles_per_frame = 1; p.mode = 0;
     p.tune = &c->tune; p.trace = &c->trace;

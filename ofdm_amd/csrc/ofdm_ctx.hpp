@@ -104,6 +104,7 @@ struct ofdm_ctx {
     float *d_chest_w = nullptr;         // W_k = |t_k|^2
     float2 *d_chest_mt = nullptr;       // N R^-1, transposed: [L_h][L_h]
     ofdm::Tuning tune;                  // ofdm_set_tuning: per-context A/B switches and grid shapes (no environment variable is read)
+    double sync_threshold_f64 = 0.0;    // ofdm_set_tuning "sync_threshold_bits": the packet-detect threshold as a double (0 = prm.sync_threshold, a float)
     ofdm::Trace trace;                  // ofdm_last_dispatch: the kernels the last entry point launched
     ofdm::ScStats sc_stats;             // list counters of the last Schmidl-Cox search (ofdm_get_tuning "stat_sc_*")
     int32_t *d_stats = nullptr;         // [2] their home on the device (owned by the context)

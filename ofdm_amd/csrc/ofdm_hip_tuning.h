@@ -28,6 +28,9 @@
 //   frame check (OFDM_ECC_FCS + mode)
 //     fcs_bitserial       k_fcs_wrap / k_fcs_check reduce every lane's chunk bit by bit in registers instead of through the slice-by-4
 //                         tables in LDS (tools/bench_fcs.py times both)
+//   Schmidl-Cox threshold in full precision (handled by name in ofdm_abi.hip, 64 bits: not in the table below)
+//     sync_threshold_bits the bit pattern of a double in (0, 1] that replaces ofdm_params.sync_threshold (a float: 6e-8 apart) in every
+//                         search of the context; 0 = the float again.  The margin tests set the threshold within 1e-12 of a lag's own metric
 //   profile build only (libofdm_hip_profile.so): ablation exits and s_memtime section timers
 //     debug_demod64, debug_sc, debug_tx
 #ifndef OFDM_TUNE_KEY
