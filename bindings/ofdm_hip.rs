@@ -82,6 +82,10 @@ pub const OFDM_Q_LLR_UNIT: usize = 4;
 pub const OFDM_Q_EVM2: usize = 5;
 pub const OFDM_Q_POINTS: usize = 6;
 pub const OFDM_QUALITY_FIELDS: usize = 8;
+// ofdm_llr_combine_batch / ofdm_rx_decode_combine_batch (EXT-7 soft combining): at most this many captures of one frame, and the weight
+// of the best live one; parity unpinned by the reference, tests/combine_ref.py is the definition (include/ofdm_hip.h)
+pub const OFDM_COMBINE_MAX_BRANCHES: i32 = 8;
+pub const OFDM_COMBINE_WEIGHT_ONE: i32 = 64;
 
 /// The crate's own `ModulationScheme` (src/transmitter.rs:98-104) is what `encode` / `decode` keep taking.  Its `Qam` arm is
 /// empty in the reference (transmitter.rs:135-136, receiver.rs:185: "Only 16 qam is implemented"); here it selects 16-QAM.
@@ -192,6 +196,13 @@ extern "C" {
                                  first_symbol: i32, syms_per_frame: i32, n_points_dev: *const i32, offset_dev: *const i32,
                                  f_delta_dev: *const f64, hk_dev: *const ofdm_fc32, hk_stride: i64, status_dev: *const i32,
                                  quality_dev: *mut f32) -> c_int;
+    pub fn ofdm_llr_combine_batch(ctx: *mut ofdm_ctx, llr_dev: *const i8, n_frames: i64, n_branches: i32, llr_stride: i64, n_llr: i64,
+                                  quality_dev: *const f32, status_dev: *const i32, n_live_dev: *const i32, out_dev: *mut i8,
+                                  out_stride: i64, weight_dev: *mut i32) -> c_int;
+    pub fn ofdm_rx_decode_combine_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, n_branches: i32, frame_stride: i64,
+                                        frame_len: i64, n_lags: i64, max_symbols: i32, out_dev: *mut u8, out_stride: i64,
+                                        out_len_dev: *mut i32, status_dev: *mut i32, branch_status_dev: *mut i32, offset_dev: *mut i32,
+                                        f_delta_dev: *mut f64, metric_dev: *mut f32, weight_dev: *mut i32, quality_dev: *mut f32) -> c_int;
     pub fn ofdm_tx_encode_batch(ctx: *mut ofdm_ctx, payload_dev: *const u8, n_frames: i64, payload_stride: i64,
                                 payload_len_dev: *const i32, payload_bytes: i32, out_dev: *mut ofdm_fc32, out_stride: i64) -> c_int;
     pub fn ofdm_rx_decode_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,

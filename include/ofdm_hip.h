@@ -334,7 +334,7 @@ int ofdm_rx_demod_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames
  * f32: at an llr_scale near FLT_MAX it overflows and 0 is stored where exact arithmetic would clamp to +-127.
  * The true LLR is L / llr_scale * 4 mean|H|^2 / ((M - 1)^2 sigma^2), sigma^2 = the complex noise variance of a received bin:
  * ofdm_rx_quality_batch ("link quality" below) estimates sigma^2 and returns that factor as OFDM_Q_LLR_UNIT.  No decoder scales
- * its LLRs by it. */
+ * its LLRs by it; soft combining ("soft combining" below, EXT-7) weighs the captures of one frame by it. */
 /* ofdm_rx_demod_batch with int8 LLRs out instead of hard bytes: arguments as there; llr_dev[f*llr_stride ..] receives
  * syms_per_frame * data_carriers * bps LLRs, LLR j = bit j of the stream rx_demod packs LSB-first.  llr_scale must be finite and
  * > 0, llr_stride >= syms_per_frame * data_carriers * bps (OFDM_ERR_INVALID otherwise). */
@@ -653,6 +653,53 @@ int ofdm_rx_decode_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frame
                          int64_t frame_len, int64_t n_lags, int32_t max_symbols, uint8_t *out_dev,
                          int64_t out_stride, int32_t *out_len_dev, int32_t *status_dev, int32_t *offset_dev,
                          double *f_delta_dev, float *metric_dev);
+
+/* ------------------------------------------------------------------ soft combining (north-star extension)
+ * LLR-level (Chase) combining of R = n_branches captures of ONE frame -- two antennas, or a frame received twice.  Parity unpinned by
+ * the reference, which has nothing of the kind: tests/combine_ref.py is the definition.  Layout: branch r of frame f is row f * R + r
+ * of every per-branch array, so captures [n_frames][R][frame_len] are an ordinary batch of n_frames * R rows.  Per frame:
+ *   live       branch r is live iff its status is 0 (or status_dev is NULL), its quality row has OFDM_Q_VALID == 1 and u_r =
+ *              OFDM_Q_LLR_UNIT is finite and > 0; without quality rows every branch with status 0 is live and u_r = 1
+ *   weights    u_max = the largest u_r over the live branches; q_r = rint(64 (double)u_r / (double)u_max), the IEEE f64 quotient, ties
+ *              to even: an integer in [0, OFDM_COMBINE_WEIGHT_ONE].  A dead branch has q_r = 0, and a live one more than about 21 dB
+ *              below the best rounds to 0: it is left out (and not read), as intended
+ *   counted    branch r counts at positions j < n_r, n_r = n_live_dev[f * R + r] clamped to [0, n_llr], or n_llr without the array (a
+ *              branch cut short by the end of its capture)
+ *   combined   out[j] = clamp((sum_r q_r L_r[j] + 32) >> 6, -127, 127) over the branches that count at j, the shift arithmetic (floor),
+ *              the sum in int32 (at most 8 * 64 * 128 in magnitude); a position at which no branch counts is 0.  With R = 1 this is L
+ *              itself, except that -128 becomes -127.  Bytes of the output row behind n_llr are not written.
+ * The weights come from link quality because an unweighted sum of a good and a poor capture is worse than the good one alone
+ * (profiles/combine_ber_and_speed.json). */
+#define OFDM_COMBINE_MAX_BRANCHES 8
+#define OFDM_COMBINE_WEIGHT_ONE 64
+/* The stage, on any context whatever its ecc: llr_dev rows f * R + r of n_llr int8 LLRs, llr_stride apart -> out_dev rows f, out_stride
+ * apart; quality_dev: n_frames * R rows of OFDM_QUALITY_FIELDS floats, or NULL; status_dev, n_live_dev: optional int32 per branch row;
+ * weight_dev: optional int32 per branch row, receives q_r.  Rows may start at any address and have any stride >= n_llr (16-byte
+ * aligned bases and strides take the 16-byte path).  OFDM_ERR_INVALID: a NULL llr_dev or out_dev with n_frames > 0, a negative size,
+ * llr_stride or out_stride < n_llr, n_branches outside 1 .. OFDM_COMBINE_MAX_BRANCHES; n_llr > 2^31 - 2^13: OFDM_ERR_UNSUPPORTED.
+ * n_frames == 0: OFDM_OK, nothing is written.  One launch (k_llr_combine), no workspace. */
+int ofdm_llr_combine_batch(ofdm_ctx *ctx, const int8_t *llr_dev, int64_t n_frames, int32_t n_branches, int64_t llr_stride, int64_t n_llr,
+                           const float *quality_dev, const int32_t *status_dev, const int32_t *n_live_dev, int8_t *out_dev,
+                           int64_t out_stride, int32_t *weight_dev);
+/* ofdm_rx_decode_batch for frames of R captures each: capture r of frame f = in_dev[(f * R + r) * frame_stride .. + frame_len).
+ * Defined as the composition of the stages:
+ *   1. per branch row, the front end of ofdm_rx_decode_batch: the context's sync mode, the trimmed start and live symbols, the channel
+ *      estimate (chest_mode honoured) -> status_r, offset_r, f_delta_r, nsym_r, H_r
+ *   2. the training part of ofdm_rx_quality_batch over the same rows (syms_per_frame = 0, no points, status_r, H_r)
+ *   3. ofdm_rx_llr_batch's LLRs at OFDM_SOFT_LLR_SCALE over max_symbols symbols from symbol 10
+ *   4. the rule above with n_r = nsym_r * data_carriers * bps; nsym_f = the largest nsym_r over the live branches; status_f = 0 if a
+ *      branch is live, otherwise the first non-zero status_r in branch order, or OFDM_FRAME_HEADER if every status_r is 0
+ *   5. the mode's finishing step on the combined row with status_f and nsym_f, then its outer layers, as ofdm_rx_decode_batch runs them
+ * out_dev / out_stride / out_len_dev / status_dev: per FRAME, out_stride by the mode's rule for ofdm_rx_decode_batch; out_len is 0 for
+ * a frame without a live branch.  branch_status_dev, offset_dev, f_delta_dev, metric_dev (the search's), weight_dev (q_r), quality_dev
+ * (rows of OFDM_QUALITY_FIELDS): per BRANCH ROW, each optional.  With R = 1 every output equals ofdm_rx_decode_batch's bit for bit.
+ * Supported: the modes whose inner code reads nothing from one capture's hard bytes -- OFDM_ECC_CONV_K7F_* and OFDM_ECC_LDPC648 / _R23 /
+ * _R34 / _R56, alone or under OFDM_ECC_RS255 and / or OFDM_ECC_FCS; every other mode: OFDM_ERR_UNSUPPORTED.  OFDM_ERR_INVALID as
+ * ofdm_rx_decode_batch, and for n_branches outside 1 .. OFDM_COMBINE_MAX_BRANCHES.  The LLR workspace holds R + 1 rows a frame. */
+int ofdm_rx_decode_combine_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int32_t n_branches, int64_t frame_stride,
+                                 int64_t frame_len, int64_t n_lags, int32_t max_symbols, uint8_t *out_dev, int64_t out_stride,
+                                 int32_t *out_len_dev, int32_t *status_dev, int32_t *branch_status_dev, int32_t *offset_dev,
+                                 double *f_delta_dev, float *metric_dev, int32_t *weight_dev, float *quality_dev);
 
 /* ------------------------------------------------------------------ host buffers
  * The reference's encode returns a host Vec<Complex64> and decode consumes one (src/transmitter.rs:11-15, src/receiver.rs:9-13).

@@ -164,6 +164,51 @@ class Context {
                                   r.status.data(), r.offset.data(), r.f_delta.data(), nullptr, chunk_frames), "ofdm_rx_decode_host");
         return r;
     }
+    // soft combining (EXT-7, include/ofdm_hip.h): frames of n_branches captures each, capture r of frame f at frames[(f * n_branches + r) *
+    // frame_stride ..] -- two antennas, or a frame received twice -- decoded once per frame from the captures' LLRs weighted by link quality.
+    // The captures are copied to the device and the results back by this call (the chain itself works on device buffers).  Modes: the
+    // framed convolutional and the LDPC modes, alone or under RS / the frame check; every other mode throws (OFDM_ERR_UNSUPPORTED).
+    struct CombineResult { std::vector<uint8_t> bytes; int64_t row = 0; std::vector<int32_t> len, status, branch_status, weight; };
+    CombineResult decode_combine(const ofdm_fc32 *frames, int64_t n_frames, int32_t n_branches, int64_t frame_stride, int64_t frame_len,
+                                 int32_t max_symbols, int64_t n_lags = 0) {
+        CombineResult r;
+        const size_t nf = (size_t)n_frames, rows = nf * (size_t)n_branches;
+        r.row = std::max<int64_t>((int64_t)max_symbols * ofdm_bytes_per_symbol(ctx_) - 16, 4);
+        if (rs_outer(base_ecc(ecc_))) r.row = ofdm_rs255_decoded_len(r.row); // whole 223-byte blocks, the trailing zero block included
+        r.bytes.resize(nf * (size_t)r.row);
+        r.len.resize(nf); r.status.resize(nf); r.branch_status.resize(rows); r.weight.resize(rows);
+        if (!n_frames) return r;
+        const size_t samples = (rows - 1) * (size_t)frame_stride + (size_t)frame_len;
+        DevBuf din(ctx_, samples * sizeof(ofdm_fc32)), dout(ctx_, r.bytes.size()), dlen(ctx_, nf * 4), dst(ctx_, nf * 4), dbs(ctx_, rows * 4), dw(ctx_, rows * 4);
+        check(ofdm_memcpy_h2d(ctx_, din.p, frames, samples * sizeof(ofdm_fc32)), "h2d");
+        check(ofdm_rx_decode_combine_batch(ctx_, (const ofdm_fc32 *)din.p, n_frames, n_branches, frame_stride, frame_len, n_lags, max_symbols,
+                                           (uint8_t *)dout.p, r.row, (int32_t *)dlen.p, (int32_t *)dst.p, (int32_t *)dbs.p, nullptr, nullptr, nullptr,
+                                           (int32_t *)dw.p, nullptr), "ofdm_rx_decode_combine_batch");
+        check(ofdm_memcpy_d2h(ctx_, r.bytes.data(), dout.p, r.bytes.size()), "d2h");
+        check(ofdm_memcpy_d2h(ctx_, r.len.data(), dlen.p, nf * 4), "d2h");
+        check(ofdm_memcpy_d2h(ctx_, r.status.data(), dst.p, nf * 4), "d2h");
+        check(ofdm_memcpy_d2h(ctx_, r.branch_status.data(), dbs.p, rows * 4), "d2h");
+        check(ofdm_memcpy_d2h(ctx_, r.weight.data(), dw.p, rows * 4), "d2h");
+        return r;
+    }
+    // the stage alone on host rows: n_frames * n_branches rows of n_llr int8 LLRs -> n_frames combined rows; quality (rows of
+    // OFDM_QUALITY_FIELDS floats), status and n_live (int32 per branch row) are optional
+    std::vector<int8_t> llr_combine(const int8_t *llr, int64_t n_frames, int32_t n_branches, int64_t n_llr, const float *quality = nullptr,
+                                    const int32_t *status = nullptr, const int32_t *n_live = nullptr) {
+        const size_t rows = (size_t)n_frames * (size_t)n_branches, nl = (size_t)n_llr;
+        std::vector<int8_t> out((size_t)n_frames * nl);
+        if (!n_frames) return out;
+        DevBuf din(ctx_, rows * nl), dout(ctx_, out.size()), dq(ctx_, rows * OFDM_QUALITY_FIELDS * sizeof(float)), dst(ctx_, rows * 4), dnl(ctx_, rows * 4);
+        check(ofdm_memcpy_h2d(ctx_, din.p, llr, rows * nl), "h2d");
+        if (quality) check(ofdm_memcpy_h2d(ctx_, dq.p, quality, rows * OFDM_QUALITY_FIELDS * sizeof(float)), "h2d");
+        if (status) check(ofdm_memcpy_h2d(ctx_, dst.p, status, rows * 4), "h2d");
+        if (n_live) check(ofdm_memcpy_h2d(ctx_, dnl.p, n_live, rows * 4), "h2d");
+        check(ofdm_llr_combine_batch(ctx_, (const int8_t *)din.p, n_frames, n_branches, n_llr, n_llr, quality ? (const float *)dq.p : nullptr,
+                                     status ? (const int32_t *)dst.p : nullptr, n_live ? (const int32_t *)dnl.p : nullptr, (int8_t *)dout.p, n_llr,
+                                     nullptr), "ofdm_llr_combine_batch");
+        check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size()), "d2h");
+        return out;
+    }
     std::vector<ofdm_fc32> encode_batch(const uint8_t *payload, int64_t n_frames, int32_t payload_bytes, int64_t chunk_frames = 0) {
         const int64_t frame = ofdm_frame_samples(ctx_, payload_bytes);
         std::vector<ofdm_fc32> out((size_t)(n_frames * frame));

@@ -788,6 +788,62 @@ class Context:
                                                _dev(res["metric"])), "rx_decode")
         return res
 
+    def llr_combine(self, llr: torch.Tensor, n_branches: int, quality: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
+                    n_live: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, want_weight: bool = False):
+        """ofdm_llr_combine_batch (EXT-7): int8 LLR rows [n_frames * n_branches, n_llr], branch r of frame f being row f * n_branches +
+        r (or [n_frames, n_branches, n_llr]) -> the combined rows [n_frames, n_llr]: out[j] = clamp((sum_r q_r L_r[j] + 32) >> 6, +-127)
+        with q_r = rint(64 u_r / u_max) from the LLR units of `quality` (float32 rows of QUALITY_FIELDS per branch row; None: every
+        branch with status 0 weighs 64).  status, n_live: optional int32 per branch row (a branch with status != 0 is left out; branch
+        r counts below n_live only).  llr and out may be views with contiguous rows of any stride and base.  want_weight: also the
+        int32 weights per branch row.  Definition: include/ofdm_hip.h, tests/combine_ref.py."""
+        if llr.dim() == 3:
+            if llr.shape[1] != n_branches or (llr.shape[0] > 1 and llr.stride(0) != n_branches * llr.stride(1)):
+                raise OfdmError("llr_combine: a [n_frames, n_branches, n_llr] tensor must have one row stride")
+            llr = llr.as_strided((llr.shape[0] * n_branches, llr.shape[2]), (llr.stride(1), llr.stride(2)), llr.storage_offset())
+        if llr.dtype != torch.int8 or llr.device != self.device or llr.dim() != 2 or llr.shape[0] % max(n_branches, 1) or \
+                (llr.shape[1] > 1 and llr.stride(1) != 1) or (llr.shape[0] > 1 and llr.stride(0) < llr.shape[1]):
+            raise OfdmError("llr_combine: llr must be an int8 [n_frames * n_branches, n_llr] tensor with contiguous rows on the context's device")
+        rows, nl = llr.shape
+        n = rows // max(n_branches, 1)
+        for name, t, dt, cnt in (("quality", quality, torch.float32, rows * QUALITY_FIELDS), ("status", status, torch.int32, rows),
+                                 ("n_live", n_live, torch.int32, rows)):
+            if t is not None and (t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.numel() != cnt):
+                raise OfdmError(f"llr_combine: {name} must be a contiguous {dt} tensor of one entry per branch row on the context's device")
+        if out is None:
+            out = self.empty((n, nl), torch.int8)
+        elif out.dtype != torch.int8 or out.device != self.device or out.shape != (n, nl) or (nl > 1 and out.stride(1) != 1) or \
+                (n > 1 and out.stride(0) < nl):
+            raise OfdmError("llr_combine: out must be an int8 [n_frames, n_llr] tensor with contiguous rows on the context's device")
+        weight = self.empty((rows,), torch.int32) if want_weight else None
+        self._ck(self.lib.ofdm_llr_combine_batch(self.h, _dev(llr), n, n_branches, llr.stride(0) if rows > 1 else nl, nl, _dev(quality),
+                                                 _dev(status), _dev(n_live), _dev(out), out.stride(0) if n > 1 else nl, _dev(weight)),
+                 "llr_combine")
+        return (out, weight) if want_weight else out
+
+    def decode_combine(self, frames: torch.Tensor, max_symbols: int, n_lags: int = 0, frame_len: Optional[int] = None):
+        """ofdm_rx_decode_combine_batch (EXT-7): frames [n_frames, R, stride], R captures of every frame (two antennas, a frame received
+        twice) -> one decode per frame from the captures' LLRs combined by link quality.  bytes / len / status: per frame, as
+        decode_batch; branch_status, offset, f_delta, metric, weight [n_frames, R] and quality [n_frames, R, QUALITY_FIELDS]: per
+        capture.  Modes: ECC_CONV_K7F_* and ECC_LDPC648*, alone or under ECC_RS255 / ECC_FCS."""
+        frames = self._cx(frames)
+        if frames.dim() != 3:
+            raise OfdmError("decode_combine: frames must be [n_frames, n_branches, samples]")
+        n, R, stride = frames.shape
+        f2 = frames.view(n * R, stride)
+        ob = self.decode_row_bytes(max_symbols)
+        out = self.empty((n, ob), torch.uint8)
+        res = {
+            "bytes": out, "len": self.empty((n,), torch.int32), "status": self.empty((n,), torch.int32),
+            "branch_status": self.empty((n, R), torch.int32), "offset": self.empty((n, R), torch.int32),
+            "f_delta": self.empty((n, R), torch.float64), "metric": self.empty((n, R), torch.float32),
+            "weight": self.empty((n, R), torch.int32), "quality": self.empty((n, R, QUALITY_FIELDS), torch.float32),
+        }
+        self._ck(self.lib.ofdm_rx_decode_combine_batch(self.h, _dev(f2), n, R, stride, stride if frame_len is None else frame_len, n_lags,
+                                                       max_symbols, _dev(out), ob, _dev(res["len"]), _dev(res["status"]),
+                                                       _dev(res["branch_status"]), _dev(res["offset"]), _dev(res["f_delta"]),
+                                                       _dev(res["metric"]), _dev(res["weight"]), _dev(res["quality"])), "rx_decode_combine")
+        return res
+
     def channel_batch(self, tx: torch.Tensor, snr_db: float = 30.0, timing_error: bool = False, seed: int = 1,
                       delay: Optional[torch.Tensor] = None, f_delta: Optional[torch.Tensor] = None,
                       out: Optional[torch.Tensor] = None, span: Optional[int] = None, want_f_delta: bool = False):

@@ -212,6 +212,29 @@ hipError_t run_linkq(int n, const LinkqParams &p, hipStream_t st, int num_cu);
 float linkq_inv_t2(const double *training, int n, int guard);
 float linkq_es(int bps);
 
+// ---- EXT-7 soft combining (ofdm_llr_combine_batch and the combine step of ofdm_rx_decode_combine_batch; kernels_combine.hip,
+// definition: tests/combine_ref.py)
+// k_llr_combine: branch r of frame f is row f * n_branches + r of llr, quality, status, n_live and weight; one combined row a frame.
+constexpr int kCombineMaxBranches = 8;
+struct CombineParams {
+    const Tuning *tune = nullptr;
+    Trace *trace = nullptr;
+    const int8_t *llr = nullptr;
+    long long n_frames = 0, llr_stride = 0;
+    int n_branches = 1;
+    int n_llr = 0;
+    const float *quality = nullptr;      // optional rows of kQualityFields floats (nullptr: every branch with status 0 is live, u = 1)
+    const int32_t *status = nullptr;     // optional
+    const int32_t *n_live = nullptr;     // optional: branch row counts for j < clamp(n_live * live_unit, 0, n_llr)
+    int live_unit = 1;                   // stage: 1; chain: n_live holds live SYMBOLS, live_unit = data_carriers * bps
+    int8_t *out = nullptr;
+    long long out_stride = 0;
+    int32_t *weight = nullptr;           // optional: q_r per branch row
+    // chain only (both or neither): the merged status and the largest n_live entry over the live branches, per frame
+    int32_t *status_out = nullptr, *nsym_out = nullptr;
+};
+hipError_t run_llr_combine(const CombineParams &p, int num_cu, hipStream_t st);
+
 // ---- Schmidl-Cox (kernels_sync.hip)
 struct ScParams {
     const Tuning *tune = nullptr;

@@ -1178,6 +1178,23 @@ int ofdm_rx_llr_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_
 }
 
 // EXT-6 link quality: one launch of k_linkq, a row per frame (include/ofdm_hip.h, tests/quality_ref.py)
+static int linkq_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len, int32_t first_symbol,
+                     int32_t syms_per_frame, const int32_t *n_points, const int32_t *offset, const double *f_delta, const float2 *hk,
+                     int64_t hk_stride, const int32_t *status, float *quality) {
+    LinkqParams p;
+    p.tune = &c->tune; p.trace = &c->trace;
+    p.in = in; p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
+    p.first_symbol = first_symbol; p.syms_per_frame = syms_per_frame; p.sym_len = c->S();
+    p.n_points = n_points; p.offset = offset; p.f_delta = f_delta; p.status = status;
+    p.hk = hk; p.hk_stride = hk_stride; p.tw = c->d_tw;
+    p.bps = c->prm.modulation; p.guard = c->prm.guard_bands;
+    const int N = c->prm.n_fft;
+    p.inv_t2 = linkq_inv_t2(c->training.data(), N, p.guard);
+    p.es = linkq_es(p.bps);
+    p.quality = quality;
+    HIP_TRY(c, run_linkq(N, p, c->stream, c->num_cu));
+    return OFDM_OK;
+}
 int ofdm_rx_quality_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
                           int32_t first_symbol, int32_t syms_per_frame, const int32_t *n_points, const int32_t *offset,
                           const double *f_delta, const ofdm_fc32 *hk, int64_t hk_stride, const int32_t *status, float *quality) {
@@ -1188,18 +1205,26 @@ int ofdm_rx_quality_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
     if (!n_frames) return OFDM_OK;
     DeviceGuard dev_guard(c->device);
     c->trace.reset();
-    LinkqParams p;
+    return linkq_run(c, reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, first_symbol, syms_per_frame, n_points, offset,
+                     f_delta, reinterpret_cast<const float2 *>(hk), hk_stride, status, quality);
+}
+
+// EXT-7 soft combining, the stage: one launch of k_llr_combine (include/ofdm_hip.h, tests/combine_ref.py)
+int ofdm_llr_combine_batch(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, int32_t n_branches, int64_t llr_stride, int64_t n_llr,
+                           const float *quality, const int32_t *status, const int32_t *n_live, int8_t *out, int64_t out_stride,
+                           int32_t *weight) {
+    if (!c || n_frames < 0 || n_llr < 0 || n_branches < 1 || n_branches > OFDM_COMBINE_MAX_BRANCHES) return OFDM_ERR_INVALID;
+    if (llr_stride < n_llr || out_stride < n_llr || (n_frames && (!llr || !out))) return OFDM_ERR_INVALID;
+    if (n_llr > 0x7fffffffll - (1 << 13)) return OFDM_ERR_UNSUPPORTED; // the kernel's column indices are ints
+    if (!n_frames) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    CombineParams p;
     p.tune = &c->tune; p.trace = &c->trace;
-    p.in = reinterpret_cast<const float2 *>(in); p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
-    p.first_symbol = first_symbol; p.syms_per_frame = syms_per_frame; p.sym_len = c->S();
-    p.n_points = n_points; p.offset = offset; p.f_delta = f_delta; p.status = status;
-    p.hk = reinterpret_cast<const float2 *>(hk); p.hk_stride = hk_stride; p.tw = c->d_tw;
-    p.bps = c->prm.modulation; p.guard = c->prm.guard_bands;
-    const int N = c->prm.n_fft;
-    p.inv_t2 = linkq_inv_t2(c->training.data(), N, p.guard);
-    p.es = linkq_es(p.bps);
-    p.quality = quality;
-    HIP_TRY(c, run_linkq(N, p, c->stream, c->num_cu));
+    p.llr = llr; p.n_frames = n_frames; p.llr_stride = llr_stride; p.n_branches = n_branches; p.n_llr = (int)n_llr;
+    p.quality = quality; p.status = status; p.n_live = n_live;
+    p.out = out; p.out_stride = out_stride; p.weight = weight;
+    HIP_TRY(c, run_llr_combine(p, c->num_cu, c->stream));
     return OFDM_OK;
 }
 
@@ -1298,6 +1323,36 @@ static const int64_t kSoftLlrBytes = 256ll << 20;
 // wavefront; OFDM_ECC_CONV_K7F_*: k_viterbi_k7f, which reads the length from its own coded block and may set status;
 // OFDM_ECC_LDPC648 / _R23 / _R34 / _R56: k_ldpc_decode / k_ldpc_decode<r23|r34|r56>, which reads the length from its first code word and
 // may set status.
+// The finishing kernel of frames f0 .. f0 + nf of d over the LLR rows of one chunk (row 0 = frame f0); vp: the Viterbi launch as planned
+// for the chunk size (conv modes)
+static int soft_finish_chunk(ofdm_ctx *c, const DecodeCall &d, int64_t f0, int64_t nf, const int8_t *llr, int64_t llr_stride,
+                             const int32_t *nsym, const uint8_t *raw, int64_t raw_stride, ViterbiParams &vp, long long v_blocks) {
+    const ModePlan &m = c->mode;
+    const int bps_bytes = c->bytes_per_symbol();
+    uint8_t *out = d.out + f0 * d.out_stride;
+    if (m.ldpc()) {
+        LdpcDecodeParams lp;
+        lp.llr = llr; lp.n_frames = nf; lp.llr_stride = llr_stride; lp.max_iter = OFDM_LDPC_MAX_ITER;
+        lp.out = out; lp.out_stride = d.out_stride; lp.status_rw = d.status + f0; lp.out_len = d.out_len + f0;
+        lp.nsym = nsym; lp.bytes_per_symbol = bps_bytes;
+        HIP_TRY(c, run_ldpc_rate_decode(lp, m.ldpc_rate(), c->num_cu, &c->tune, c->stream));
+    } else if (m.conv()) {
+        vp.n_frames = nf; vp.out = out; vp.raw = raw; vp.status = d.status + f0; vp.nsym = nsym; vp.out_len = d.out_len + f0;
+        if (m.rate() < 0) {
+            HIP_TRY(c, run_viterbi_k7(vp, v_blocks, c->stream));
+        } else {
+            const ViterbiFParams vf{vp, m.rate(), d.status + f0}; // (it may set status)
+            HIP_TRY(c, run_viterbi_k7f(vf, v_blocks, c->stream));
+        }
+    } else {
+        HIP_TRY(c, run_rx_finish_soft(raw, raw_stride, llr, llr_stride, nf, d.status + f0, nsym, bps_bytes, out, d.out_stride,
+                                      d.out_len + f0, c->stream));
+    }
+    return OFDM_OK;
+}
+static const char *soft_finish_name(const ModePlan &m) {
+    return m.ldpc() ? ldpc_rate_decode_name(m.ldpc_rate()) : !m.conv() ? "k_rx_finish_soft" : m.rate() < 0 ? "k_viterbi_k7" : "k_viterbi_k7f";
+}
 // The LLR workspace holds one chunk: at most kSoftLlrBytes whatever n_frames is.
 static int rx_finish_soft(ofdm_ctx *c, const DecodeCall &d, const SoftInput &s) {
     const ModePlan &m = c->mode;
@@ -1318,63 +1373,50 @@ static int rx_finish_soft(ofdm_ctx *c, const DecodeCall &d, const SoftInput &s) 
         vp.llr = llr; vp.llr_stride = llr_stride; vp.out_stride = d.out_stride;
         vp.raw_stride = s.raw_stride; vp.bytes_per_symbol = bps_bytes;
     }
-    const char *name = m.ldpc() ? ldpc_rate_decode_name(m.ldpc_rate()) : !m.conv() ? "k_rx_finish_soft" : m.rate() < 0 ? "k_viterbi_k7" : "k_viterbi_k7f";
+    const char *name = soft_finish_name(m);
     for (int64_t f0 = 0; f0 < d.n_frames; f0 += chunk) {
         const int64_t nf = d.n_frames - f0 < chunk ? d.n_frames - f0 : chunk;
         const int32_t *nsym = s.nsym + f0;
         const uint8_t *raw = s.raw + f0 * s.raw_stride;
-        uint8_t *out = d.out + f0 * d.out_stride;
         rc = llr_run(c, d.in + f0 * d.frame_stride, nf, d.frame_stride, d.frame_len, 10, d.max_symbols, s.offs + f0, s.fd + f0, nsym,
                      s.hk + f0 * N, N, OFDM_SOFT_LLR_SCALE, (int8_t *)w_llr, llr_stride, s.raw + f0 * s.raw_stride, s.raw_stride, f0 == 0);
         if (rc) return rc;
         if (f0 == 0) c->trace.add(name);
-        if (m.ldpc()) {
-            LdpcDecodeParams lp;
-            lp.llr = llr; lp.n_frames = nf; lp.llr_stride = llr_stride; lp.max_iter = OFDM_LDPC_MAX_ITER;
-            lp.out = out; lp.out_stride = d.out_stride; lp.status_rw = d.status + f0; lp.out_len = d.out_len + f0;
-            lp.nsym = nsym; lp.bytes_per_symbol = bps_bytes;
-            HIP_TRY(c, run_ldpc_rate_decode(lp, m.ldpc_rate(), c->num_cu, &c->tune, c->stream));
-        } else if (m.conv()) {
-            vp.n_frames = nf; vp.out = out; vp.raw = raw; vp.status = d.status + f0; vp.nsym = nsym; vp.out_len = d.out_len + f0;
-            if (m.rate() < 0) {
-                HIP_TRY(c, run_viterbi_k7(vp, v_blocks, c->stream));
-            } else {
-                const ViterbiFParams vf{vp, m.rate(), d.status + f0}; // (it may set status)
-                HIP_TRY(c, run_viterbi_k7f(vf, v_blocks, c->stream));
-            }
-        } else {
-            HIP_TRY(c, run_rx_finish_soft(raw, s.raw_stride, llr, llr_stride, nf, d.status + f0, nsym, bps_bytes, out, d.out_stride,
-                                          d.out_len + f0, c->stream));
-        }
+        if ((rc = soft_finish_chunk(c, d, f0, nf, llr, llr_stride, nsym, raw, s.raw_stride, vp, v_blocks))) return rc;
     }
     return OFDM_OK;
 }
 
-// The chain of the plan's inner mode into the rows d.out / d.out_stride: the caller's, or the innermost outer layer's workspace
-static int rx_decode_inner(ofdm_ctx *c, const DecodeCall &d) {
+// The sizes the inner chain derives from max_symbols, and its two argument checks: the output rows hold what the finishing kernel can
+// write, and the longest trellis a frame can ask for is one the Viterbi kernels take
+struct InnerPlan { int bps_bytes; int64_t raw_bytes, raw_stride, body_max, body_steps; };
+static int inner_plan(ofdm_ctx *c, const DecodeCall &d, InnerPlan &ip) {
     const ModePlan &m = c->mode;
-    const int64_t n_frames = d.n_frames, frame_stride = d.frame_stride, frame_len = d.frame_len, out_stride = d.out_stride;
-    const int32_t max_symbols = d.max_symbols;
-    uint8_t *const out = d.out;
-    int32_t *const out_len = d.out_len, *const status = d.status, *const offset = d.offset;
-    float *const metric = d.metric;
-    if (n_frames > 1 && frame_stride <= 0) return OFDM_ERR_INVALID;
-    const int bps_bytes = c->bytes_per_symbol();
-    const int64_t raw_bytes = (int64_t)max_symbols * bps_bytes;
-    const int64_t raw_stride = (raw_bytes + 3) & ~(int64_t)3;   // rows of the raw-byte workspace start on dwords (6-byte BPSK symbols: odd counts)
+    ip.bps_bytes = c->bytes_per_symbol();
+    ip.raw_bytes = (int64_t)d.max_symbols * ip.bps_bytes;
+    ip.raw_stride = (ip.raw_bytes + 3) & ~(int64_t)3;   // rows of the raw-byte workspace start on dwords (6-byte BPSK symbols: odd counts)
     // rows must hold what k_rx_finish can write: the whole body without an outer code, floor(body / 7) * 4 bytes after
     // Hamming(7,4) decoding, body / 2 - 1 after Viterbi decoding (include/ofdm_hip.h)
-    const int64_t body_max = raw_bytes > 16 ? raw_bytes - 16 : 0;
-    if (out_stride < inner_row_limit(m, body_max)) return OFDM_ERR_INVALID;
-    const int ecc = m.inner, f_rate = m.rate();
+    ip.body_max = ip.raw_bytes > 16 ? ip.raw_bytes - 16 : 0;
+    if (d.out_stride < inner_row_limit(m, ip.body_max)) return OFDM_ERR_INVALID;
+    const int f_rate = m.rate();
     // the longest trellis a frame can ask for (framed: the 72-step length block, then a body cut at the end of the capture)
-    const int64_t body_steps = f_rate < 0 ? 4 * body_max
-                                          : std::max<int64_t>(4 * kConvLengthBlock, conv_max_steps(8 * std::max<int64_t>(body_max - kConvLengthBlock, 0), f_rate));
-    if (m.conv() && body_steps > kViterbiMaxSteps) return OFDM_ERR_UNSUPPORTED;
-    if (!n_frames) return OFDM_OK;
-    c->trace.reset();
-    const int N = c->prm.n_fft;
-    void *w_dhat, *w_fd, *w_off, *w_nsym, *w_hk = nullptr, *w_raw = nullptr;
+    ip.body_steps = f_rate < 0 ? 4 * ip.body_max
+                               : std::max<int64_t>(4 * kConvLengthBlock, conv_max_steps(8 * std::max<int64_t>(ip.body_max - kConvLengthBlock, 0), f_rate));
+    if (m.conv() && ip.body_steps > kViterbiMaxSteps) return OFDM_ERR_UNSUPPORTED;
+    return OFDM_OK;
+}
+
+// Steps 1 + 2 of the chain over the rows of d (ofdm_rx_decode_batch: the frames; ofdm_rx_decode_combine_batch: the branch rows): timing
+// and CFO by the context's sync mode, then the trimmed start, the length check and the live symbols.  Leaves d.status, d.metric and,
+// in fe, the arrays the kernels behind it index with: the caller's offset / f_delta arrays or the workspace's.
+struct FrontEnd { int32_t *offs; double *fd; int32_t *nsym; };
+static int rx_front_end(ofdm_ctx *c, const DecodeCall &d, int bps_bytes, FrontEnd &fe) {
+    const int64_t n_frames = d.n_frames, frame_stride = d.frame_stride, frame_len = d.frame_len;
+    const int32_t max_symbols = d.max_symbols;
+    int32_t *const status = d.status, *const offset = d.offset;
+    float *const metric = d.metric;
+    void *w_dhat, *w_fd, *w_off, *w_nsym;
     int rc;
     if ((rc = ws_get(c, kWsDhat, sizeof(int32_t) * (size_t)n_frames, &w_dhat))) return rc;
     if ((rc = ws_get(c, kWsFdelta, sizeof(double) * (size_t)n_frames, &w_fd))) return rc;
@@ -1383,7 +1425,6 @@ static int rx_decode_inner(ofdm_ctx *c, const DecodeCall &d) {
     int32_t *offs = offset ? offset : (int32_t *)w_off;
     double *fd = d.f_delta ? d.f_delta : (double *)w_fd;
     const float2 *x = d.in;
-    if ((rc = ws_get(c, kWsRaw, (size_t)raw_stride * (size_t)n_frames, &w_raw))) return rc;
     if (const KnownSync *known = d.known) {
         // 1k. the caller brings the timing of the one capture (ofdm_rx_decode_long with lag_lo > 0)
         if (n_frames != 1 || c->prm.sync_mode != OFDM_SYNC_SCHMIDL_COX) return OFDM_ERR_INVALID;
@@ -1409,14 +1450,57 @@ static int rx_decode_inner(ofdm_ctx *c, const DecodeCall &d) {
         if (c->prm.cfo_mode == OFDM_CFO_OFF) HIP_TRY(c, hipMemsetAsync(fd, 0, sizeof(double) * (size_t)n_frames, c->stream));
         else { c->trace.add("k_freq_corr"); HIP_TRY(c, run_freq_correction(x + 3 * c->S(), n_frames, frame_stride, c->S(), c->S(), fd, c->stream, offs, status)); }
     } else {
-    // 1. timing + CFO: Schmidl-Cox over the repeated preamble (replaces xcorr_fft, src/receiver.rs:20-25,39)
-    rc = ofdm_abi_sc_run(c, x, n_frames, frame_stride, frame_len, d.n_lags, (int32_t *)w_dhat, fd, metric);
-    if (rc) return rc;
-    // 2. trimmed start, length check, live symbols (receiver.rs:21-36)
-    c->trace.add("k_rx_prepare");
-    HIP_TRY(c, run_rx_prepare(n_frames, (const int32_t *)w_dhat, fd, frame_len, c->S(), c->prm.sync_backoff,
-                              c->prm.cfo_mode, max_symbols, bps_bytes, status, offs, (int32_t *)w_nsym, c->stream));
+        // 1. timing + CFO: Schmidl-Cox over the repeated preamble (replaces xcorr_fft, src/receiver.rs:20-25,39)
+        rc = ofdm_abi_sc_run(c, x, n_frames, frame_stride, frame_len, d.n_lags, (int32_t *)w_dhat, fd, metric);
+        if (rc) return rc;
+        // 2. trimmed start, length check, live symbols (receiver.rs:21-36)
+        c->trace.add("k_rx_prepare");
+        HIP_TRY(c, run_rx_prepare(n_frames, (const int32_t *)w_dhat, fd, frame_len, c->S(), c->prm.sync_backoff,
+                                  c->prm.cfo_mode, max_symbols, bps_bytes, status, offs, (int32_t *)w_nsym, c->stream));
     }
+    fe.offs = offs; fe.fd = fd; fe.nsym = (int32_t *)w_nsym;
+    return OFDM_OK;
+}
+// Step 3 of the generic chain over the same rows: the channel estimate from the 5 training blocks into the workspace, denoised under
+// OFDM_CHEST_WLS (EXT-5: H' in place of H^)
+static int rx_channel_estimate(ofdm_ctx *c, const DecodeCall &d, const FrontEnd &fe, const float2 **hk) {
+    const int N = c->prm.n_fft;
+    void *w_hk = nullptr;
+    int rc;
+    if ((rc = ws_get(c, kWsHk, sizeof(float2) * (size_t)N * (size_t)d.n_frames, &w_hk))) return rc;
+    SymParams p = rx_params(c, d.in, d.n_frames, d.frame_stride, d.frame_len, fe.offs, fe.fd);
+    p.out = (float2 *)w_hk;
+    HIP_TRY(c, run_chest(N, p, c->stream, c->num_cu));
+    if (c->prm.chest_mode == OFDM_CHEST_WLS && (rc = chest_smooth_run(c, (const float2 *)w_hk, d.n_frames, (float2 *)w_hk, true))) return rc;
+    *hk = (const float2 *)w_hk;
+    return OFDM_OK;
+}
+
+// The chain of the plan's inner mode into the rows d.out / d.out_stride: the caller's, or the innermost outer layer's workspace
+static int rx_decode_inner(ofdm_ctx *c, const DecodeCall &d) {
+    const ModePlan &m = c->mode;
+    const int64_t n_frames = d.n_frames, frame_stride = d.frame_stride, frame_len = d.frame_len, out_stride = d.out_stride;
+    const int32_t max_symbols = d.max_symbols;
+    uint8_t *const out = d.out;
+    int32_t *const out_len = d.out_len, *const status = d.status;
+    if (n_frames > 1 && frame_stride <= 0) return OFDM_ERR_INVALID;
+    InnerPlan ip;
+    int rc;
+    if ((rc = inner_plan(c, d, ip))) return rc;
+    const int bps_bytes = ip.bps_bytes;
+    const int64_t raw_stride = ip.raw_stride, body_steps = ip.body_steps;
+    const int ecc = m.inner;
+    if (!n_frames) return OFDM_OK;
+    c->trace.reset();
+    const int N = c->prm.n_fft;
+    void *w_raw = nullptr;
+    const float2 *x = d.in;
+    if ((rc = ws_get(c, kWsRaw, (size_t)raw_stride * (size_t)n_frames, &w_raw))) return rc;
+    FrontEnd fe;
+    if ((rc = rx_front_end(c, d, bps_bytes, fe))) return rc;
+    int32_t *const offs = fe.offs;
+    double *const fd = fe.fd;
+    void *const w_nsym = fe.nsym;
     // 3+4. channel estimate from the 5 training blocks and per data symbol CP strip + FFT + equalise + pilot phase +
     //      demap (receiver.rs:44-83).  N = 64: one fused wave-centric kernel; otherwise the generic pair.
     bool fused = false, finished = false;
@@ -1445,17 +1529,14 @@ static int rx_decode_inner(ofdm_ctx *c, const DecodeCall &d) {
         else if (r != kNextPath) return r;
     }
     if (!fused) {
-        if ((rc = ws_get(c, kWsHk, sizeof(float2) * (size_t)N * (size_t)n_frames, &w_hk))) return rc;
-        SymParams p = rx_params(c, x, n_frames, frame_stride, frame_len, offs, fd);
-        p.out = (float2 *)w_hk;
-        HIP_TRY(c, run_chest(N, p, c->stream, c->num_cu));
-        if (wls && (rc = chest_smooth_run(c, (const float2 *)w_hk, n_frames, (float2 *)w_hk, true))) return rc; // EXT-5: H' in place of H^
+        const float2 *hk = nullptr;
+        if ((rc = rx_channel_estimate(c, d, fe, &hk))) return rc;
         if (soft) {
-            const SoftInput si{offs, fd, (const int32_t *)w_nsym, (const float2 *)w_hk, (uint8_t *)w_raw, raw_stride, body_steps};
+            const SoftInput si{offs, fd, (const int32_t *)w_nsym, hk, (uint8_t *)w_raw, raw_stride, body_steps};
             return rx_finish_soft(c, d, si);
         }
         rc = demod_run(c, x, n_frames, frame_stride, frame_len, 10, max_symbols, offs, fd, (const int32_t *)w_nsym,
-                       (const float2 *)w_hk, N, (uint8_t *)w_raw, raw_stride, nullptr);
+                       hk, N, (uint8_t *)w_raw, raw_stride, nullptr);
         if (rc) return rc;
     }
     // 5. length header, truncate [, Hamming decode] (receiver.rs:85-95)
@@ -1470,7 +1551,10 @@ static int rx_decode_inner(ofdm_ctx *c, const DecodeCall &d) {
 // The decode chain of the context's mode: the inner chain into the innermost outer layer's workspace (dword rows: the fused frame
 // kernels and the layer inside write there as they write to a caller's rows), then every outer layer's kernel inside-out over what
 // every frame delivered, in place on out_len / status
-static int rx_decode(ofdm_ctx *c, const DecodeCall &d) {
+struct CombineCall { int32_t n_branches; int32_t *branch_status, *weight; float *quality; };
+static int rx_decode_combine_inner(ofdm_ctx *c, const DecodeCall &d, const CombineCall &cc);
+// (combine: the inner chain of ofdm_rx_decode_combine_batch in place of rx_decode_inner)
+static int rx_decode(ofdm_ctx *c, const DecodeCall &d, const CombineCall *combine = nullptr) {
     if (!c || d.n_frames < 0 || d.frame_len <= 0 || d.max_symbols <= 0) return OFDM_ERR_INVALID;
     if (d.n_frames && (!d.in || !d.out || !d.out_len || !d.status)) return OFDM_ERR_INVALID;
     const ModePlan &m = c->mode;
@@ -1492,7 +1576,7 @@ static int rx_decode(ofdm_ctx *c, const DecodeCall &d) {
     }
     DecodeCall inner = d;
     inner.out = to[m.n_outer].rows; inner.out_stride = to[m.n_outer].stride;
-    if ((rc = rx_decode_inner(c, inner))) return rc;
+    if ((rc = combine ? rx_decode_combine_inner(c, inner, *combine) : rx_decode_inner(c, inner))) return rc;
     for (int i = m.n_outer - 1; i >= 0; i--) {
         const OuterStage &s = kOuter[m.outer[i]];
         c->trace.add(s.rx_name);
@@ -1507,6 +1591,81 @@ int ofdm_rx_decode_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int
     const DecodeCall d{reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, n_lags, max_symbols, out, out_stride, out_len,
                        status, offset, f_delta, metric, nullptr};
     return rx_decode(c, d);
+}
+// EXT-7: the inner chain over frames of R captures.  d: the call per FRAME (out, out_len, status), its offset / f_delta / metric per BRANCH
+// ROW.  Front end, link quality and LLRs per branch row, k_llr_combine, then the mode's finishing kernel on the combined rows.
+// The LLR workspace holds one chunk of frames: R branch rows and the combined row each.
+static int rx_decode_combine_inner(ofdm_ctx *c, const DecodeCall &d, const CombineCall &cc) {
+    const ModePlan &m = c->mode;
+    const int R = cc.n_branches, N = c->prm.n_fft;
+    if (d.frame_stride <= 0 && (d.n_frames > 1 || R > 1)) return OFDM_ERR_INVALID;
+    InnerPlan ip;
+    int rc;
+    if ((rc = inner_plan(c, d, ip))) return rc;
+    const int llr_unit = c->carriers() * c->prm.modulation;
+    const int64_t llr_row = (int64_t)d.max_symbols * llr_unit;
+    if (llr_row > 0x7fffffffll - (1 << 13)) return OFDM_ERR_UNSUPPORTED; // k_llr_combine's column indices are ints
+    if (!d.n_frames) return OFDM_OK;
+    c->trace.reset();
+    const int64_t rows = d.n_frames * R;
+    void *w_bst = nullptr, *w_q = nullptr, *w_ns, *w_llr;
+    if (!cc.branch_status && (rc = ws_get(c, kWsBranchStatus, sizeof(int32_t) * (size_t)rows, &w_bst))) return rc;
+    if (!cc.quality && (rc = ws_get(c, kWsBranchQuality, sizeof(float) * kQualityFields * (size_t)rows, &w_q))) return rc;
+    if ((rc = ws_get(c, kWsCombinedNsym, sizeof(int32_t) * (size_t)d.n_frames, &w_ns))) return rc;
+    int32_t *const bst = cc.branch_status ? cc.branch_status : (int32_t *)w_bst;
+    float *const quality = cc.quality ? cc.quality : (float *)w_q;
+    // 1. the front end over the branch rows
+    DecodeCall b = d;
+    b.n_frames = rows; b.out = nullptr; b.out_len = nullptr; b.status = bst;
+    FrontEnd fe;
+    if ((rc = rx_front_end(c, b, ip.bps_bytes, fe))) return rc;
+    const float2 *hk = nullptr;
+    if ((rc = rx_channel_estimate(c, b, fe, &hk))) return rc;
+    // 2. link quality from the training blocks
+    if ((rc = linkq_run(c, b.in, rows, b.frame_stride, b.frame_len, 10, 0, nullptr, fe.offs, fe.fd, hk, N, bst, quality))) return rc;
+    // 3 - 5. per chunk of frames: LLRs of the branch rows, the combined rows behind them, the finishing kernel
+    const int64_t llr_stride = (llr_row + 15) & ~(int64_t)15;
+    int64_t chunk = c->tune.soft_chunk_frames > 0 ? c->tune.soft_chunk_frames : kSoftLlrBytes / llr_stride;
+    if (chunk < 1) chunk = 1;
+    if (chunk > d.n_frames) chunk = d.n_frames;
+    if ((rc = ws_get(c, kWsLlr, (size_t)(llr_stride * chunk) * (size_t)(R + 1), &w_llr))) return rc;
+    int8_t *const branch_llr = (int8_t *)w_llr, *const combined = branch_llr + llr_stride * chunk * R;
+    ViterbiParams vp;
+    long long v_blocks = 0;
+    if (m.conv()) {
+        if ((rc = viterbi_survivors(c, chunk, ip.body_steps, vp, &v_blocks))) return rc;
+        vp.llr = combined; vp.llr_stride = llr_stride; vp.out_stride = d.out_stride;
+        vp.raw_stride = 0; vp.bytes_per_symbol = ip.bps_bytes;
+    }
+    for (int64_t f0 = 0; f0 < d.n_frames; f0 += chunk) {
+        const int64_t nf = d.n_frames - f0 < chunk ? d.n_frames - f0 : chunk, r0 = f0 * R;
+        rc = llr_run(c, b.in + r0 * b.frame_stride, nf * R, b.frame_stride, b.frame_len, 10, d.max_symbols, fe.offs + r0, fe.fd + r0, fe.nsym + r0,
+                     hk + r0 * N, N, OFDM_SOFT_LLR_SCALE, branch_llr, llr_stride, nullptr, 0, f0 == 0);
+        if (rc) return rc;
+        CombineParams p;
+        p.tune = &c->tune; p.trace = f0 == 0 ? &c->trace : nullptr;
+        p.llr = branch_llr; p.n_frames = nf; p.llr_stride = llr_stride; p.n_branches = R; p.n_llr = (int)llr_row;
+        p.quality = quality + r0 * kQualityFields; p.status = bst + r0; p.n_live = fe.nsym + r0; p.live_unit = llr_unit;
+        p.out = combined; p.out_stride = llr_stride; p.weight = cc.weight ? cc.weight + r0 : nullptr;
+        p.status_out = d.status + f0; p.nsym_out = (int32_t *)w_ns + f0;
+        HIP_TRY(c, run_llr_combine(p, c->num_cu, c->stream));
+        if (f0 == 0) c->trace.add(soft_finish_name(m));
+        // (the framed Viterbi kernel takes chain mode from its status array; no mode supported here reads hard bytes: raw = nullptr)
+        if ((rc = soft_finish_chunk(c, d, f0, nf, combined, llr_stride, (const int32_t *)w_ns + f0, nullptr, 0, vp, v_blocks))) return rc;
+    }
+    return OFDM_OK;
+}
+
+int ofdm_rx_decode_combine_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int32_t n_branches, int64_t frame_stride, int64_t frame_len,
+                                 int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len, int32_t *status,
+                                 int32_t *branch_status, int32_t *offset, double *f_delta, float *metric, int32_t *weight, float *quality) {
+    if (!c || n_branches < 1 || n_branches > OFDM_COMBINE_MAX_BRANCHES) return OFDM_ERR_INVALID;
+    // the inner code must read nothing from one capture's hard bytes: the framed convolutional modes and the LDPC modes
+    if (!(c->mode.rate() >= 0 || c->mode.ldpc())) return OFDM_ERR_UNSUPPORTED;
+    const DecodeCall d{reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, n_lags, max_symbols, out, out_stride, out_len,
+                       status, offset, f_delta, metric, nullptr};
+    const CombineCall cc{n_branches, branch_status, weight, quality};
+    return rx_decode(c, d, &cc);
 }
 int ofdm_abi_rx_decode_known(ofdm_ctx *c, const ofdm_fc32 *in, int64_t frame_len, int32_t d_hat, double f_delta, float metric,
                              int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len, int32_t *status, int32_t *offset,

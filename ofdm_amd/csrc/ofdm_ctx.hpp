@@ -78,6 +78,7 @@ enum WsRole {
     kWsSearch, kWsSearchD1,      // the timing search's scratch (k_sc_*, k_scb_*, k_xcorr: one at a time) and the tiled search's first crossings
     kWsChestTaps,                // EXT-5: the solve's zeroed rows
     kWsRxFcsRows, kWsRxRsRows,   // decode: the dword rows an outer layer reads
+    kWsBranchStatus, kWsBranchQuality, kWsCombinedNsym, // EXT-7 combine chain: per branch row status and quality rows, per frame merged live symbols
     kWsTxFcsRows, kWsTxFcsLen, kWsTxRsRows, kWsTxRsLen, kWsTxCoded, kWsTxCodedLen, // encode: rows and ragged lengths out of every layer
     kWsFrameMax,                 // per-frame maxima (ofdm_tx_encode_batch, ofdm_normalize_batch)
     kWsProbeSink,                // ofdm_hbm_read_probe

@@ -51,6 +51,16 @@ def link(ecc, n, mod, n_frames, payload, snr, seed, guard=True, **ctx_kw):
     return c, pay, rx, c.data_symbols(payload)
 
 
+def branch_link_on(c, n_frames, payload, snrs, seed):
+    """(pay, rx [n_frames, R, span]): R = len(snrs) captures of every frame (EXT-7 soft combining) -- the payloads drawn as link_on draws
+    them, ONE transmit frame each, then branch r through seeded_channel at snrs[r] with the channel seed `seed + r`, its delays and
+    CFOs drawn from the generator branch after branch"""
+    g = generator(c, seed)
+    pay = torch.randint(0, 256, (n_frames, max(payload, 1)), dtype=torch.uint8, device=c.device, generator=g)[:, :payload].contiguous()
+    tx = c.encode_batch(pay)
+    return pay, torch.stack([seeded_channel(c, tx, snr, seed + r, g) for r, snr in enumerate(snrs)], dim=1).contiguous()
+
+
 # ---------------------------------------------------------------------------------------------------------- what was delivered
 def delivered(r, pay, want_len, exact=True):
     """(right, ok) masks over the frames of a decode_batch result: ok = status 0, right = ok with the length want_len (exact=False: at
