@@ -452,11 +452,13 @@ struct FcsCheckParams {
 };
 hipError_t run_fcs_check(FcsCheckParams p, int num_cu, const Tuning *tune, hipStream_t st);
 
-// ---- LDPC(648,324) (OFDM_ECC_LDPC648, ofdm_ldpc648_encode_batch / _decode_batch; kernels_ldpc.hip, definition: tests/ldpc_ref.py,
-// ldpc_code.hip)
-// k_ldpc_encode.  Stage mode (framed == 0): rows of n_cw blocks of 40 info bytes -> n_cw blocks of 80 code bytes.  Chain mode: rows of
+// ---- LDPC(648) (OFDM_ECC_LDPC648 / _R23 / _R34 / _R56, ofdm_ldpc648_encode_batch / _decode_batch and their _rate_batch forms;
+// kernels_ldpc.hip, definition: tests/ldpc_ref.py, tests/ldpc_rates_ref.py, ldpc_code.hip).  rate 0 .. 3 = 1/2, 2/3, 3/4, 5/6 with
+// K = 40 / 53 / 60 / 67 info bytes a code word, kernels k_ldpc_encode / k_ldpc_decode and k_ldpc_encode<r23|r34|r56> /
+// k_ldpc_decode<r23|r34|r56>; any other rate: hipErrorInvalidValue.
+// k_ldpc_encode.  Stage mode (framed == 0): rows of n_cw blocks of K info bytes -> n_cw blocks of 80 code bytes.  Chain mode: rows of
 // n_bytes payload bytes (row f: in_len[f], clamped, when in_len is given) -> the code of [u32 LE len][u32 LE ~len] ++ payload, zeros
-// behind the row's own code words up to n_cw = ceil((n_bytes + 8) / 40); out_len (optional): 80 times the row's own count.
+// behind the row's own code words up to n_cw = ceil((n_bytes + 8) / K); out_len (optional): 80 times the row's own count.
 struct LdpcEncodeParams {
     const uint8_t *in = nullptr;
     long long n_frames = 0, in_stride = 0, n_bytes = 0, n_cw = 0;
@@ -466,8 +468,8 @@ struct LdpcEncodeParams {
     long long out_stride = 0;
     int32_t *out_len = nullptr;
 };
-hipError_t run_ldpc_encode(const LdpcEncodeParams &p, int num_cu, const Tuning *tune, hipStream_t st);
-// k_ldpc_decode.  Stage mode (status_rw == nullptr): rows of n_cw code words of 640 LLRs -> 40 n_cw bytes, iters (optional, n_frames *
+hipError_t run_ldpc_encode(const LdpcEncodeParams &p, int rate, int num_cu, const Tuning *tune, hipStream_t st);
+// k_ldpc_decode.  Stage mode (status_rw == nullptr): rows of n_cw code words of 640 LLRs -> K n_cw bytes, iters (optional, n_frames *
 // n_cw: the iteration a code word converged at, 0 = not within max_iter).  Chain mode (status_rw, nsym, out_len required): the frame
 // rule of include/ofdm_hip.h on the LLRs from 128 on; rows with status != 0 are skipped with out_len 0, status may become
 // OFDM_FRAME_HEADER or OFDM_FRAME_UNCORRECTABLE.
@@ -482,13 +484,9 @@ struct LdpcDecodeParams {
     const int32_t *nsym = nullptr;
     int bytes_per_symbol = 0;
 };
-hipError_t run_ldpc_decode(const LdpcDecodeParams &p, int num_cu, const Tuning *tune, hipStream_t st);
-// The family (kernels_ldpc_rates.hip): rate 0 = the two kernels above, 1 / 2 / 3 = k_ldpc_encode<r23|r34|r56> and k_ldpc_decode<r23|r34|r56>,
-// the same parameters with K = 53 / 60 / 67 info bytes a code word in place of 40; any other rate: hipErrorInvalidValue.
-hipError_t run_ldpc_rate_encode(const LdpcEncodeParams &p, int rate, int num_cu, const Tuning *tune, hipStream_t st);
-hipError_t run_ldpc_rate_decode(const LdpcDecodeParams &p, int rate, int num_cu, const Tuning *tune, hipStream_t st);
-const char *ldpc_rate_encode_name(int rate); // the dispatch name of the kernel a rate launches
-const char *ldpc_rate_decode_name(int rate);
+hipError_t run_ldpc_decode(const LdpcDecodeParams &p, int rate, int num_cu, const Tuning *tune, hipStream_t st);
+const char *ldpc_encode_name(int rate); // the dispatch name of the kernel a rate launches
+const char *ldpc_decode_name(int rate);
 
 // ---- EXT-5 channel-estimate denoising (OFDM_CHEST_WLS, ofdm_chest_smooth_batch; kernels_chest.hip, definition: tests/chest_ref.py)
 // rows of n_fft bins times the per-bin weight w (a weight of exactly 0 gives 0 whatever the bin holds); in == out allowed

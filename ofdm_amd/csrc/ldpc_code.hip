@@ -1,22 +1,21 @@
-// ldpc_code.hip -- the LDPC(648,324) code of OFDM_ECC_LDPC648 on the host: ofdm_ldpc648_coded_len / _encode / _decode.
-// Parity unpinned by the reference (it has no LDPC code): tests/ldpc_ref.py (numpy, exact integers) is the definition, this file is
-// its executable form in the library, and k_ldpc_encode / k_ldpc_decode (kernels_ldpc.hip) are held to both bit for bit.
+// ldpc_code.hip -- the LDPC(648) codes of OFDM_ECC_LDPC648 / _R23 / _R34 / _R56 on the host: ofdm_ldpc648_coded_len / _encode /
+// _decode (rate 1/2) and ofdm_ldpc648_*_rate (rate 0 = 1/2, 1 = 2/3, 2 = 3/4, 3 = 5/6), one encoder and one decoder over
+// ldpc_table.h's LdpcCode.  Parity unpinned by the reference (it has no LDPC code): tests/ldpc_ref.py and tests/ldpc_rates_ref.py
+// (numpy, exact integers) are the definition, this file is its executable form in the library, and k_ldpc_encode / k_ldpc_decode
+// (kernels_ldpc.hip) are held to both bit for bit.
 //
-// Code word.  x[0 .. 319] = the 40 info bytes, each LSB first; x[320 .. 323] = 0 (shortened); x[324 .. 647] = the unique parity with
-// H x = 0 (H: ldpc_table.h).  Sent: x[0 .. 319] ++ x[324 .. 643], packed LSB first into 80 bytes; x[644 .. 647] are punctured.
+// Code word of a rate, K info bytes, M = 27 * rows checks.  x[0 .. 8 K - 1] = the info bytes, each LSB first; x[8 K .. 647 - M] = 0 (shortened);
+// x[648 - M .. 647] = the unique parity with H x = 0 (H: ldpc_table.h).  Sent: x[0 .. 8 K - 1] ++ the first 640 - 8 K parity bits,
+// packed LSB first into 80 bytes; the parity bits behind them are punctured.  Rate 1/2: K = 40, x[320 .. 323] = 0, x[324 .. 643] sent.
 //
 // Decoder: layered normalised min-sum (factor 3/4) in exact integers.  Input 640 int8 LLRs a code word, positive = bit 1 (as everywhere
-// in the library); inside, positive = bit 0.  Q_v = -L_v (v < 320), +2047 (v = 320 .. 323), -L_{v-4} (v = 324 .. 643), 0 (v = 644 ..
-// 647); every R = 0.  Iteration it = 1, 2, ...: block rows l = 0 .. 11 in order; for check z of the row with its edges e in table
-// order, v_e = 27 c_e + (z + s_e) mod 27:
+// in the library); inside, positive = bit 0.  Q_v = -L of a sent bit, +2047 of a shortened one, 0 of a punctured one (LdpcCode::
+// llr_index); every R = 0.  Iteration it = 1, 2, ...: block rows l = 0 .. rows - 1 in order; for check z of the row with its edges e
+// in table order, v_e = 27 c_e + (z + s_e) mod 27:
 //     T_e = clamp(Q_{v_e} - R_e, +-2047);  m_e = min_{e' != e} |T_e'|;  sign_e = prod_{e' != e} (T_e' < 0 ? -1 : +1);
 //     R_e = sign_e min((3 m_e) >> 2, 127);  Q_{v_e} = clamp(T_e + R_e, +-2047).
-// After each whole iteration x_v = (Q_v < 0); if all 324 checks hold the code word has CONVERGED at iteration it and stops, otherwise
-// up to max_iter iterations run.  Output: x[0 .. 319] of the last iteration run; iters = it when converged, 0 when not.
-//
-// The family (ofdm_ldpc648_*_rate, rate 0 = 1/2, 1 = 2/3, 2 = 3/4, 3 = 5/6; definition: tests/ldpc_rates_ref.py): the same rule over
-// the table, the K info bytes and the sent map of ldpc_table.h's LdpcCode.  Rate 0 is the code above, and through the _rate functions
-// it gives what the functions above give, byte for byte.
+// After each whole iteration x_v = (Q_v < 0); if all checks hold the code word has CONVERGED at iteration it and stops, otherwise
+// up to max_iter iterations run.  Output: x[0 .. 8 K - 1] of the last iteration run; iters = it when converged, 0 when not.
 #include "../../include/ofdm_hip.h"
 #include "ldpc_table.h"
 
@@ -28,79 +27,6 @@ namespace {
 
 inline int clampi(int v, int lim) { return v > lim ? lim : (v < -lim ? -lim : v); }
 
-void encode_codeword(const uint8_t *info, uint8_t *code) {
-    uint32_t u[kLdpcRows] = {0}, par[kLdpcRows] = {0};
-    for (int v = 0; v < kLdpcInfoBits; v++)
-        if ((info[v >> 3] >> (v & 7)) & 1) u[v / kLdpcZ] |= 1u << (v % kLdpcZ);
-    uint32_t lam[kLdpcRows], p0 = 0;
-    for (int l = 0; l < kLdpcRows; l++) {
-        lam[l] = 0;
-        for (int c = 0; c < kLdpcRows; c++)
-            if (kLdpcShift[l][c] >= 0) lam[l] ^= ldpc_rot(u[c], kLdpcShift[l][c]);
-        p0 ^= lam[l];
-    }
-    par[0] = p0;
-    for (int l = 0; l + 1 < kLdpcRows; l++)
-        par[l + 1] = lam[l] ^ (l ? par[l] : 0u) ^ (kLdpcShift[l][kLdpcRows] >= 0 ? ldpc_rot(p0, kLdpcShift[l][kLdpcRows]) : 0u);
-    std::memcpy(code, info, kLdpcInfoBytes);
-    std::memset(code + kLdpcInfoBytes, 0, kLdpcInfoBytes);
-    for (int t = 0; t < kLdpcInfoBits; t++) // parity bit t = x[324 + t]; the last four of the 324 are not sent
-        if ((par[t / kLdpcZ] >> (t % kLdpcZ)) & 1) code[kLdpcInfoBytes + (t >> 3)] |= (uint8_t)(1u << (t & 7));
-}
-
-// -> the iteration at which the code word converged, 0 if it did not within max_iter
-int decode_codeword(const int8_t *llr, int max_iter, uint8_t *out) {
-    const LdpcEdgeList &E = kLdpcEdgeList;
-    int16_t Q[kLdpcN];
-    int8_t R[kLdpcEdges][kLdpcZ];
-    for (int v = 0; v < kLdpcN; v++) {
-        if (v < kLdpcInfoBits) Q[v] = (int16_t)-(int)llr[v];
-        else if (v < kLdpcChecks) Q[v] = kLdpcQMax;
-        else if (v < kLdpcChecks + kLdpcInfoBits) Q[v] = (int16_t)-(int)llr[v - 4];
-        else Q[v] = 0;
-    }
-    std::memset(R, 0, sizeof(R));
-    int iters = 0;
-    for (int it = 1; it <= max_iter && !iters; it++) {
-        for (int l = 0; l < kLdpcRows; l++) {
-            const int e0 = E.first[l], deg = E.first[l + 1] - e0;
-            for (int z = 0; z < kLdpcZ; z++) {
-                int T[kLdpcCols], var[kLdpcCols];
-                for (int i = 0; i < deg; i++) {
-                    var[i] = kLdpcZ * E.col[e0 + i] + (z + E.shift[e0 + i]) % kLdpcZ;
-                    T[i] = clampi(Q[var[i]] - R[e0 + i][z], kLdpcQMax);
-                }
-                for (int i = 0; i < deg; i++) {
-                    int m = 1 << 30, sign = 1;
-                    for (int j = 0; j < deg; j++) {
-                        if (j == i) continue;
-                        const int a = T[j] < 0 ? -T[j] : T[j];
-                        if (a < m) m = a;
-                        if (T[j] < 0) sign = -sign;
-                    }
-                    int r = (3 * m) >> 2;
-                    if (r > kLdpcRMax) r = kLdpcRMax;
-                    R[e0 + i][z] = (int8_t)(sign * r);
-                    Q[var[i]] = (int16_t)clampi(T[i] + sign * r, kLdpcQMax);
-                }
-            }
-        }
-        bool ok = true;
-        for (int l = 0; l < kLdpcRows && ok; l++)
-            for (int z = 0; z < kLdpcZ && ok; z++) {
-                int par = 0;
-                for (int e = E.first[l]; e < E.first[l + 1]; e++) par ^= Q[kLdpcZ * E.col[e] + (z + E.shift[e]) % kLdpcZ] < 0;
-                ok = !par;
-            }
-        if (ok) iters = it;
-    }
-    std::memset(out, 0, kLdpcInfoBytes);
-    for (int v = 0; v < kLdpcInfoBits; v++)
-        if (Q[v] < 0) out[v >> 3] |= (uint8_t)(1u << (v & 7));
-    return iters;
-}
-
-// ---- the family, over one LdpcCode
 void encode_codeword(const LdpcCode &C, const uint8_t *info, uint8_t *code) {
     const int k = C.info_cols();
     uint32_t u[kLdpcCols] = {0}, par[kLdpcRows] = {0}, lam[kLdpcRows], p0 = 0;
@@ -121,6 +47,7 @@ void encode_codeword(const LdpcCode &C, const uint8_t *info, uint8_t *code) {
         if ((par[t / kLdpcZ] >> (t % kLdpcZ)) & 1) code[C.info_bytes + (t >> 3)] |= (uint8_t)(1u << (t & 7));
 }
 
+// -> the iteration at which the code word converged, 0 if it did not within max_iter
 int decode_codeword(const LdpcCode &C, const int8_t *llr, int max_iter, uint8_t *out) {
     int16_t Q[kLdpcN];
     int8_t R[kLdpcEdges][kLdpcZ];
@@ -173,24 +100,11 @@ int decode_codeword(const LdpcCode &C, const int8_t *llr, int max_iter, uint8_t 
 
 extern "C" {
 
-int64_t ofdm_ldpc648_coded_len(int64_t payload_bytes) {
-    if (payload_bytes < 0) return OFDM_ERR_INVALID;
-    return kLdpcCodeBytes * ldpc_stream_codewords(payload_bytes);
-}
-
-int ofdm_ldpc648_encode(const uint8_t *info, int64_t n_cw, uint8_t *code) {
-    if (n_cw < 0 || (n_cw > 0 && (!info || !code))) return OFDM_ERR_INVALID;
-    for (int64_t k = 0; k < n_cw; k++) encode_codeword(info + k * kLdpcInfoBytes, code + k * kLdpcCodeBytes);
-    return OFDM_OK;
-}
-
+// rate 1/2 by its own names
+int64_t ofdm_ldpc648_coded_len(int64_t payload_bytes) { return ofdm_ldpc648_coded_len_rate(payload_bytes, 0); }
+int ofdm_ldpc648_encode(const uint8_t *info, int64_t n_cw, uint8_t *code) { return ofdm_ldpc648_encode_rate(info, n_cw, 0, code); }
 int ofdm_ldpc648_decode(const int8_t *llr, int64_t n_cw, int32_t max_iter, uint8_t *out, int32_t *iters) {
-    if (n_cw < 0 || max_iter < 1 || max_iter > kLdpcMaxIterLimit || (n_cw > 0 && (!llr || !out))) return OFDM_ERR_INVALID;
-    for (int64_t k = 0; k < n_cw; k++) {
-        const int it = decode_codeword(llr + k * kLdpcSentBits, max_iter, out + k * kLdpcInfoBytes);
-        if (iters) iters[k] = it;
-    }
-    return OFDM_OK;
+    return ofdm_ldpc648_decode_rate(llr, n_cw, max_iter, 0, out, iters);
 }
 
 int32_t ofdm_ldpc648_info_bytes(int32_t rate) {
@@ -200,7 +114,7 @@ int32_t ofdm_ldpc648_info_bytes(int32_t rate) {
 
 int64_t ofdm_ldpc648_coded_len_rate(int64_t payload_bytes, int32_t rate) {
     if (payload_bytes < 0 || rate < 0 || rate >= kLdpcRates) return OFDM_ERR_INVALID;
-    return kLdpcCodeBytes * ldpc_stream_codewords_k(payload_bytes, kLdpcCodes[rate].info_bytes);
+    return kLdpcCodeBytes * ldpc_stream_codewords(payload_bytes, kLdpcCodes[rate].info_bytes);
 }
 
 int ofdm_ldpc648_encode_rate(const uint8_t *info, int64_t n_cw, int32_t rate, uint8_t *code) {

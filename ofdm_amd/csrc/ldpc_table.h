@@ -1,5 +1,7 @@
-// ldpc_table.h -- the one copy of the LDPC(648,324) code of OFDM_ECC_LDPC648, shared by the host code (ldpc_code.hip) and the
-// kernels (kernels_ldpc.hip).  include/ofdm_hip.h "LDPC(648,324)" and tests/ldpc_ref.py state the same table; this one is what runs.
+// ldpc_table.h -- the one copy of the LDPC(648) codes of OFDM_ECC_LDPC648 / _R23 / _R34 / _R56, shared by the host code
+// (ldpc_code.hip) and the kernels (kernels_ldpc.hip): the four shift tables, and kLdpcCodes[rate] built from them (LdpcCode: a code's
+// edge list, its sent map and the check of its dual diagonal).  First the rate-1/2 table, the LDPC(648,324) code of OFDM_ECC_LDPC648;
+// include/ofdm_hip.h "LDPC(648,324)" and tests/ldpc_ref.py state the same table; this one is what runs.
 // Quasi-cyclic, Z = 27, 12 x 24 blocks, 88 non-zero: entry s >= 0 is the 27 x 27 identity shifted so that check z of block row l
 // touches variable 27 c + (z + s) mod 27 of block column c, -1 a zero block.  Intended to be the n = 648, rate-1/2 matrix of
 // 802.11n, written from memory and UNVERIFIED against the standard (as ofdm_stdrng_pilots is): the table is the definition.
@@ -9,9 +11,8 @@
 namespace ofdm {
 
 constexpr int kLdpcZ = 27, kLdpcRows = 12, kLdpcCols = 24, kLdpcEdges = 88;
-constexpr int kLdpcN = kLdpcZ * kLdpcCols, kLdpcChecks = kLdpcZ * kLdpcRows;   // 648 variables, 324 checks
-constexpr int kLdpcInfoBytes = 40, kLdpcCodeBytes = 80;                        // 320 info bits, 320 info + 320 parity bits sent
-constexpr int kLdpcInfoBits = 8 * kLdpcInfoBytes, kLdpcSentBits = 8 * kLdpcCodeBytes;
+constexpr int kLdpcN = kLdpcZ * kLdpcCols;                                     // 648 variables
+constexpr int kLdpcCodeBytes = 80, kLdpcSentBits = 8 * kLdpcCodeBytes;         // every rate sends 640 bits of a code word
 constexpr int kLdpcQMax = 2047, kLdpcRMax = 127;                               // clamps of the decoder's posteriors and check messages
 constexpr int kLdpcMaxIterLimit = 64;
 
@@ -30,60 +31,19 @@ constexpr int8_t kLdpcShift[kLdpcRows][kLdpcCols] = {
     { 3, -1, -1, -1, 16, -1, -1,  2, 25,  5, -1, -1,  1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1,  0},
 };
 
-// the non-zero blocks in table order (row by row, left to right): edge e of block row l is first[l] <= e < first[l + 1]
-struct LdpcEdgeList {
-    uint8_t col[kLdpcEdges], shift[kLdpcEdges], first[kLdpcRows + 1];
-    int count;
-};
-constexpr LdpcEdgeList make_ldpc_edges() {
-    LdpcEdgeList t{};
-    int e = 0;
-    for (int l = 0; l < kLdpcRows; l++) {
-        t.first[l] = (uint8_t)e;
-        for (int c = 0; c < kLdpcCols; c++)
-            if (kLdpcShift[l][c] >= 0) {
-                if (e < kLdpcEdges) { t.col[e] = (uint8_t)c; t.shift[e] = (uint8_t)kLdpcShift[l][c]; }
-                e++;
-            }
-    }
-    t.first[kLdpcRows] = (uint8_t)e;
-    t.count = e;
-    return t;
-}
-constexpr LdpcEdgeList kLdpcEdgeList = make_ldpc_edges();
-static_assert(kLdpcEdgeList.count == kLdpcEdges, "88 non-zero blocks");
-
-// The parity half is dual-diagonal behind column 12: block column 12 + j (j >= 1) has the unshifted identity in rows j - 1 and j and
-// nothing else, column 12 has three blocks whose first and last shifts agree.  Summed over the rows every column from 13 on cancels
-// and column 12 leaves its middle block, so with lambda_l the info part of row l:  p_0 = rot(xor_l lambda_l, -middle shift), then
-// p_{l+1} = lambda_l ^ p_l [l > 0] ^ rot(p_0, shift of column 12 in row l), l = 0 .. 10.
-constexpr bool ldpc_parity_is_dual_diagonal() {
-    for (int l = 0; l < kLdpcRows; l++)
-        for (int j = 1; j < kLdpcRows; j++)
-            if (kLdpcShift[l][kLdpcRows + j] != ((l == j - 1 || l == j) ? 0 : -1)) return false;
-    int n = 0, s[3] = {0, 0, 0};
-    for (int l = 0; l < kLdpcRows; l++)
-        if (kLdpcShift[l][kLdpcRows] >= 0) { if (n < 3) s[n] = kLdpcShift[l][kLdpcRows]; n++; }
-    return n == 3 && s[0] == s[2] && s[1] == 0 && kLdpcShift[0][kLdpcRows] >= 0 && kLdpcShift[kLdpcRows - 1][kLdpcRows] >= 0;
-}
-static_assert(ldpc_parity_is_dual_diagonal(), "the encoders back-substitute along the dual diagonal");
-
 // bit z of the result = bit (z + s) mod 27 of the 27-bit word w: what check z of a block with shift s sees of its block column
 #if defined(__HIPCC__)
 __host__ __device__
 #endif
 inline uint32_t ldpc_rot(uint32_t w, int s) { return s ? ((w >> s) | (w << (kLdpcZ - s))) & ((1u << kLdpcZ) - 1u) : w; }
 
-// codewords of p payload bytes behind the two length words
-constexpr int64_t ldpc_stream_codewords(int64_t p) { return (p + 8 + kLdpcInfoBytes - 1) / kLdpcInfoBytes; }
 
-
-// ---- the family: rates 1/2 (the table above), 2/3, 3/4 and 5/6 (OFDM_ECC_LDPC648_R23 / _R34 / _R56; kernels_ldpc_rates.hip).
+// ---- the family: rates 1/2 (the table above), 2/3, 3/4 and 5/6 (OFDM_ECC_LDPC648_R23 / _R34 / _R56).
 // The three tables below are THE PROJECT'S OWN, found by a seeded greedy search (block placement that balances the row degrees,
 // shifts drawn so that no 4-cycle arises, the draw with the fewest 6-cycles of 30 kept).  They are NOT the matrices of 802.11n; the
 // tables are the definition.  Same conventions as kLdpcShift; Z = 27 and 24 block columns throughout, 8 / 6 / 4 block rows.
 constexpr int kLdpcRates = 4;          // rate index 0 = 1/2, 1 = 2/3, 2 = 3/4, 3 = 5/6
-constexpr int kLdpcMaxRowDegree = 22;  // a row's sign bits fit one dword beside nothing else (kernels_ldpc_rates.hip)
+constexpr int kLdpcMaxRowDegree = 22;  // a row's sign bits fit one dword beside nothing else (kernels_ldpc.hip)
 
 constexpr int8_t kLdpcShiftR23[8][kLdpcCols] = {
     {15,  5, 24, -1,  3, 14, -1, -1,  8, 23, -1,  4, -1, -1, 13, -1,  1,  0, -1, -1, -1, -1, -1, -1},
@@ -110,7 +70,8 @@ constexpr int8_t kLdpcShiftR56[4][kLdpcCols] = {
     {22, 15, 22, 11, 21,  3, 21, 25, 12, 19,  8, 23,  8, 22, -1, 23, 19,  4,  6, -1,  1, -1, -1,  0},
 };
 
-// One code of the family: its table (the first `rows` rows), its edges in table order and what of a code word travels.
+// One code of the family: its table (the first `rows` rows), its non-zero blocks in table order (row by row, left to right: edge e of
+// block row l is first[l] <= e < first[l + 1], block column col[e], shift sh[e]) and what of a code word travels.
 // x[0 .. 8 K - 1] = the K info bytes, LSB first; x[8 K .. 647 - M] = 0 (shortened, not sent), M = 27 rows; x[648 - M .. 647] = the
 // parity.  Sent, 640 bits: x[0 .. 8 K - 1] ++ x[648 - M .. 648 - M + (640 - 8 K) - 1]; the parity bits behind them are punctured.
 struct LdpcCode {
@@ -128,7 +89,11 @@ struct LdpcCode {
         if (v < first_parity()) return -1;
         return v < first_parity() + parity_sent() ? v - first_parity() + info_bits() : -2;
     }
-    // the dual diagonal of ldpc_parity_is_dual_diagonal() above, behind column info_cols() with the middle block in row rows / 2
+    // The parity part is dual-diagonal behind column k = info_cols(): block column k + j (j >= 1) has the unshifted identity in rows
+    // j - 1 and j and nothing else, column k has three blocks (rows 0, rows / 2 and rows - 1) whose first and last shifts agree and
+    // whose middle one is unshifted.  Summed over the rows every column from k + 1 on cancels and column k leaves its middle block, so
+    // with lambda_l the info part of row l:  p_0 = xor_l lambda_l, then p_{l+1} = lambda_l ^ p_l [l > 0] ^ rot(p_0, shift of column k
+    // in row l), l = 0 .. rows - 2.
     constexpr bool dual_diagonal() const {
         const int k = info_cols();
         for (int l = 0; l < rows; l++)
@@ -159,7 +124,7 @@ constexpr LdpcCode make_ldpc_code(const int8_t (&table)[R][kLdpcCols], int info_
     t.count = e;
     return t;
 }
-constexpr LdpcCode kLdpcCodes[kLdpcRates] = {make_ldpc_code(kLdpcShift, kLdpcInfoBytes), make_ldpc_code(kLdpcShiftR23, 53),
+constexpr LdpcCode kLdpcCodes[kLdpcRates] = {make_ldpc_code(kLdpcShift, 40), make_ldpc_code(kLdpcShiftR23, 53),
                                              make_ldpc_code(kLdpcShiftR34, 60), make_ldpc_code(kLdpcShiftR56, 67)};
 static_assert(kLdpcCodes[0].count == 88 && kLdpcCodes[1].count == 87 && kLdpcCodes[2].count == 85 && kLdpcCodes[3].count == 81,
               "the non-zero blocks of the four tables");
@@ -175,6 +140,6 @@ static_assert(kLdpcCodes[0].llr_index(319) == 319 && kLdpcCodes[0].llr_index(320
               kLdpcCodes[0].llr_index(643) == 639 && kLdpcCodes[0].llr_index(644) == -2, "rate 1/2 keeps its sent map");
 
 // codewords of p payload bytes behind the two length words, K info bytes a code word
-constexpr int64_t ldpc_stream_codewords_k(int64_t p, int k) { return (p + 8 + k - 1) / k; }
+constexpr int64_t ldpc_stream_codewords(int64_t p, int k) { return (p + 8 + k - 1) / k; }
 
 } // namespace ofdm

@@ -858,36 +858,8 @@ int ofdm_rs255_decode_batch(ofdm_ctx *c, const uint8_t *code, int64_t n_frames, 
     return OFDM_OK;
 }
 
-// LDPC(648,324) on device rows (kernels_ldpc.hip): rows of n_cw plain code words, no frame rule
-int ofdm_ldpc648_encode_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_t in_stride, int64_t n_cw, uint8_t *out, int64_t out_stride) {
-    if (!c || n_frames < 0 || n_cw < 0 || n_cw > (int64_t)1 << 40) return OFDM_ERR_INVALID;
-    if (in_stride < kLdpcInfoBytes * n_cw || out_stride < kLdpcCodeBytes * n_cw) return OFDM_ERR_INVALID;
-    if (n_frames && n_cw && (!in || !out)) return OFDM_ERR_INVALID;
-    if (!n_frames || !n_cw) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
-    LdpcEncodeParams p;
-    p.in = in; p.n_frames = n_frames; p.in_stride = in_stride; p.n_cw = n_cw; p.out = out; p.out_stride = out_stride;
-    c->trace.add("k_ldpc_encode");
-    HIP_TRY(c, run_ldpc_encode(p, c->num_cu, &c->tune, c->stream));
-    return OFDM_OK;
-}
-int ofdm_ldpc648_decode_batch(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, int64_t llr_stride, int64_t n_cw, int32_t max_iter,
-                              uint8_t *out, int64_t out_stride, int32_t *iters) {
-    if (!c || n_frames < 0 || n_cw < 0 || n_cw > (int64_t)1 << 40 || max_iter < 1 || max_iter > kLdpcMaxIterLimit) return OFDM_ERR_INVALID;
-    if (llr_stride < kLdpcSentBits * n_cw || out_stride < kLdpcInfoBytes * n_cw) return OFDM_ERR_INVALID;
-    if (n_frames && n_cw && (!llr || !out)) return OFDM_ERR_INVALID;
-    if (!n_frames || !n_cw) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
-    LdpcDecodeParams p;
-    p.llr = llr; p.n_frames = n_frames; p.llr_stride = llr_stride; p.n_cw = n_cw; p.max_iter = max_iter; p.out = out; p.out_stride = out_stride;
-    p.iters = iters;
-    c->trace.add("k_ldpc_decode");
-    HIP_TRY(c, run_ldpc_decode(p, c->num_cu, &c->tune, c->stream));
-    return OFDM_OK;
-}
-// ... and the family (kernels_ldpc_rates.hip): K = ofdm_ldpc648_info_bytes(rate) info bytes a code word; rate 0 launches the kernels above
+// LDPC(648) on device rows (kernels_ldpc.hip): rows of n_cw plain code words of K = ofdm_ldpc648_info_bytes(rate) info bytes, no
+// frame rule
 int ofdm_ldpc648_encode_rate_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_t in_stride, int64_t n_cw, int32_t rate, uint8_t *out,
                                    int64_t out_stride) {
     if (!c || rate < 0 || rate >= kLdpcRates || n_frames < 0 || n_cw < 0 || n_cw > (int64_t)1 << 40) return OFDM_ERR_INVALID;
@@ -898,8 +870,8 @@ int ofdm_ldpc648_encode_rate_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_fra
     c->trace.reset();
     LdpcEncodeParams p;
     p.in = in; p.n_frames = n_frames; p.in_stride = in_stride; p.n_cw = n_cw; p.out = out; p.out_stride = out_stride;
-    c->trace.add(ldpc_rate_encode_name(rate));
-    HIP_TRY(c, run_ldpc_rate_encode(p, rate, c->num_cu, &c->tune, c->stream));
+    c->trace.add(ldpc_encode_name(rate));
+    HIP_TRY(c, run_ldpc_encode(p, rate, c->num_cu, &c->tune, c->stream));
     return OFDM_OK;
 }
 int ofdm_ldpc648_decode_rate_batch(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, int64_t llr_stride, int64_t n_cw, int32_t max_iter,
@@ -914,9 +886,18 @@ int ofdm_ldpc648_decode_rate_batch(ofdm_ctx *c, const int8_t *llr, int64_t n_fra
     LdpcDecodeParams p;
     p.llr = llr; p.n_frames = n_frames; p.llr_stride = llr_stride; p.n_cw = n_cw; p.max_iter = max_iter; p.out = out; p.out_stride = out_stride;
     p.iters = iters;
-    c->trace.add(ldpc_rate_decode_name(rate));
-    HIP_TRY(c, run_ldpc_rate_decode(p, rate, c->num_cu, &c->tune, c->stream));
+    c->trace.add(ldpc_decode_name(rate));
+    HIP_TRY(c, run_ldpc_decode(p, rate, c->num_cu, &c->tune, c->stream));
     return OFDM_OK;
+}
+
+// rate 1/2 by its own names
+int ofdm_ldpc648_encode_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_t in_stride, int64_t n_cw, uint8_t *out, int64_t out_stride) {
+    return ofdm_ldpc648_encode_rate_batch(c, in, n_frames, in_stride, n_cw, 0, out, out_stride);
+}
+int ofdm_ldpc648_decode_batch(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, int64_t llr_stride, int64_t n_cw, int32_t max_iter,
+                              uint8_t *out, int64_t out_stride, int32_t *iters) {
+    return ofdm_ldpc648_decode_rate_batch(c, llr, n_frames, llr_stride, n_cw, max_iter, 0, out, out_stride, iters);
 }
 
 // CRC-32 frame check on device rows (kernels_fcs.hip)
@@ -1274,8 +1255,8 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
             LdpcEncodeParams lp;
             lp.in = src; lp.n_frames = n_frames; lp.in_stride = src_stride; lp.n_bytes = src_bytes; lp.in_len = src_len; lp.framed = 1;
             lp.n_cw = coded / kLdpcCodeBytes; lp.out = (uint8_t *)cw; lp.out_stride = coded; lp.out_len = (int32_t *)cl;
-            c->trace.add(ldpc_rate_encode_name(m.ldpc_rate()));
-            HIP_TRY(c, run_ldpc_rate_encode(lp, m.ldpc_rate(), c->num_cu, &c->tune, c->stream));
+            c->trace.add(ldpc_encode_name(m.ldpc_rate()));
+            HIP_TRY(c, run_ldpc_encode(lp, m.ldpc_rate(), c->num_cu, &c->tune, c->stream));
         } else {
             HIP_TRY(c, run_ham_encode(src, n_frames, src_stride, src_len, src_bytes, (uint8_t *)cw, coded, (int32_t *)cl, c->stream));
         }
@@ -1335,7 +1316,7 @@ static int soft_finish_chunk(ofdm_ctx *c, const DecodeCall &d, int64_t f0, int64
         lp.llr = llr; lp.n_frames = nf; lp.llr_stride = llr_stride; lp.max_iter = OFDM_LDPC_MAX_ITER;
         lp.out = out; lp.out_stride = d.out_stride; lp.status_rw = d.status + f0; lp.out_len = d.out_len + f0;
         lp.nsym = nsym; lp.bytes_per_symbol = bps_bytes;
-        HIP_TRY(c, run_ldpc_rate_decode(lp, m.ldpc_rate(), c->num_cu, &c->tune, c->stream));
+        HIP_TRY(c, run_ldpc_decode(lp, m.ldpc_rate(), c->num_cu, &c->tune, c->stream));
     } else if (m.conv()) {
         vp.n_frames = nf; vp.out = out; vp.raw = raw; vp.status = d.status + f0; vp.nsym = nsym; vp.out_len = d.out_len + f0;
         if (m.rate() < 0) {
@@ -1351,7 +1332,7 @@ static int soft_finish_chunk(ofdm_ctx *c, const DecodeCall &d, int64_t f0, int64
     return OFDM_OK;
 }
 static const char *soft_finish_name(const ModePlan &m) {
-    return m.ldpc() ? ldpc_rate_decode_name(m.ldpc_rate()) : !m.conv() ? "k_rx_finish_soft" : m.rate() < 0 ? "k_viterbi_k7" : "k_viterbi_k7f";
+    return m.ldpc() ? ldpc_decode_name(m.ldpc_rate()) : !m.conv() ? "k_rx_finish_soft" : m.rate() < 0 ? "k_viterbi_k7" : "k_viterbi_k7f";
 }
 // The LLR workspace holds one chunk: at most kSoftLlrBytes whatever n_frames is.
 static int rx_finish_soft(ofdm_ctx *c, const DecodeCall &d, const SoftInput &s) {

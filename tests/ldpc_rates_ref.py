@@ -1,7 +1,7 @@
 """numpy restatement of the LDPC(648) family (OFDM_ECC_LDPC648 / _R23 / _R34 / _R56, include/ofdm_hip.h "LDPC(648), rates 2/3, 3/4 and
 5/6").  Nothing in the reference corresponds to it (parity unpinned by the reference): this file is the definition, in exact integers,
 and the host functions (ofdm_ldpc648_*_rate in ofdm_amd/csrc/ldpc_code.hip) and the kernels (k_ldpc_encode<r..>, k_ldpc_decode<r..>
-in ofdm_amd/csrc/kernels_ldpc_rates.hip) are compared with it bit for bit, iteration counts included.
+in ofdm_amd/csrc/kernels_ldpc.hip) are compared with it bit for bit, iteration counts included.
 
 It generalises tests/ldpc_ref.py by the table and the sent map; for rate 0 it is that file again (tests/test_ldpc_rates_cpu.py holds
 the two together).  The tables of rates 2/3, 3/4 and 5/6 are the project's own, found by a seeded greedy search (row degrees balanced,

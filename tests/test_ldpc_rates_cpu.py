@@ -343,5 +343,5 @@ def test_new_surface_is_on_every_layer(lib):
     import inspect
     assert inspect.signature(api.Context.ldpc_encode).parameters["rate"].default == 0
     assert inspect.signature(api.Context.ldpc_decode).parameters["rate"].default == 0
-    assert "kernels_ldpc_rates.hip" in ofdm_amd.build.SOURCES
-    assert ofdm_amd.build.EXTRA_FLAGS["kernels_ldpc_rates.hip"] == ["-fno-slp-vectorize"]
+    assert "kernels_ldpc.hip" in ofdm_amd.build.SOURCES
+    assert ofdm_amd.build.EXTRA_FLAGS["kernels_ldpc.hip"] == ["-fno-slp-vectorize"]

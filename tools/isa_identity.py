@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Is the gfx950 device code of two source trees the same, kernel by kernel?  Needs hipcc, no GPU.
 
-    python tools/isa_identity.py OLD NEW [--jobs 4] [--work DIR]
+    python tools/isa_identity.py OLD NEW [--jobs 4] [--work DIR] [--rename OLD_SYMBOL=NEW_SYMBOL ...]
 
 OLD and NEW are each a checkout (a directory holding ofdm_amd/build.py) or a git revision of this repository, which is
 exported into the work directory.  Every entry of each tree's own SOURCES is compiled with its own FLAGS + EXTRA_FLAGS plus
@@ -10,7 +10,9 @@ exported into the work directory.  Every entry of each tree's own SOURCES is com
               directives in DROP, local labels without their per-file function counter (it moves when a file is split)
   descriptor  the lines between `.amdhsa_kernel NAME` and `.end_amdhsa_kernel`
 Exit status 0 only if both trees have the same set of kernel names and every kernel's text and descriptor are equal.
-With --work the .s files are kept there and reused while they are newer than csrc/.
+With --work the .s files are kept there and reused while they are newer than csrc/.  --rename (repeatable, mangled names) says
+that a kernel of OLD has another name in NEW: it is compared under the new name, with its own old name replaced in its text and
+descriptor; without it such a kernel is reported once as "only in old" and once as "only in new".
 """
 import argparse
 import os
@@ -89,13 +91,21 @@ def main():
     ap.add_argument("new")
     ap.add_argument("--jobs", type=int, default=4)
     ap.add_argument("--work", help="keep exported trees and .s files here (default: a temporary directory)")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD_SYMBOL=NEW_SYMBOL", help="a kernel of OLD is NEW_SYMBOL in NEW")
     a = ap.parse_args()
+    rename = dict(r.split("=", 1) for r in a.rename)
     tmp = None if a.work else tempfile.TemporaryDirectory()
     work = os.path.abspath(a.work or tmp.name)
     os.makedirs(work, exist_ok=True)
     old = compile_tree(tree_of(a.old, work, "old"), os.path.join(work, "old_s"), a.jobs)
     new = compile_tree(tree_of(a.new, work, "new"), os.path.join(work, "new_s"), a.jobs)
+    for ks in old.values():
+        for k in [k for k in ks if k in rename]:
+            text, desc = ks.pop(k)
+            ks[rename[k]] = ([s.replace(k, rename[k]) for s in text], [s.replace(k, rename[k]) for s in desc])
     print(subprocess.check_output(["hipcc", "--version"], text=True).splitlines()[0])
+    for k, v in rename.items():
+        print(f"renamed: `{k}` -> `{v}`")
     print("| build | source file (new tree) | kernels | identical | different |\n|---|---|---|---|---|")
     bad = []
     for build in ("plain", "profile"):
