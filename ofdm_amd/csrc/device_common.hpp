@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "wave_ops.hpp"
 
 extern "C" __device__ float __ocml_atan2pi_f32(float, float); // atan2(y, x) / pi (ROCm device library)
 
@@ -93,7 +94,7 @@ __device__ __forceinline__ int swz(int i) { return i ^ ((i >> 3) & 7); }
 
 template <int T> __device__ __forceinline__ void group_sync() {
     if (T > 64) __syncthreads();
-    else __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    else wave_fence();
 }
 
 // Sum over the T threads of one symbol (slot `slot` of the workgroup, thread t of the symbol).  red: G * (T / 64) floats of LDS for T > 64,
@@ -368,13 +369,10 @@ __device__ __forceinline__ unsigned ham_dec(unsigned c, unsigned &fixed) {
     return c & 0xFu;
 }
 
-template <int CTRL> __device__ __forceinline__ float dpp8_f(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
-}
 __device__ __forceinline__ float sum8_lanes(float x) { // sum over the 8 lanes of a symbol group (lanes 8s .. 8s+7)
-    x += dpp8_f<0xB1>(x);  // quad_perm [1,0,3,2]
-    x += dpp8_f<0x4E>(x);  // quad_perm [2,3,0,1]
-    x += dpp8_f<0x141>(x); // row_half_mirror
+    x += dpp_f<0xB1>(x);  // quad_perm [1,0,3,2]
+    x += dpp_f<0x4E>(x);  // quad_perm [2,3,0,1]
+    x += dpp_f<0x141>(x); // row_half_mirror
     return x;
 }
 
@@ -382,7 +380,7 @@ __device__ __forceinline__ float sum8_lanes(float x) { // sum over the 8 lanes o
 // x[n] and leaves with X[bitrev6(n)].  ~12 VALU per stage instead of a whole 8-symbol group iteration, which is what
 // makes the per-frame channel estimate cheap (one transform per frame).  tws[st] = this lane's twiddle of stage st
 // (1 for the lanes that take the sum).
-template <int CTRL> __device__ __forceinline__ cf dpp_cf(cf v) { return make_float2(dpp8_f<CTRL>(v.x), dpp8_f<CTRL>(v.y)); }
+template <int CTRL> __device__ __forceinline__ cf dpp_cf(cf v) { return make_float2(dpp_f<CTRL>(v.x), dpp_f<CTRL>(v.y)); }
 __device__ __forceinline__ cf lane_fft64(cf x, int lane, const cf *tws) {
 #pragma unroll
     for (int st = 0; st < 6; ++st) {

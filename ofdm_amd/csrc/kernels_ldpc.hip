@@ -56,7 +56,6 @@ template <int RATE, int L> struct Row {
     using Edges = std::make_integer_sequence<int, degree>;
 };
 
-__device__ __forceinline__ void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
 __device__ __forceinline__ int clamp_q(int v) { return v > kLdpcQMax ? kLdpcQMax : (v < -kLdpcQMax ? -kLdpcQMax : v); }
 __device__ __forceinline__ int scale_r(int m) { const int r = (3 * m) >> 2; return r > kLdpcRMax ? kLdpcRMax : r; }
 

@@ -665,7 +665,7 @@ __global__ __launch_bounds__(256, (R <= 8 && KEEP == 0) ? 4 : 3) void k_txframe_
         group_sync<LPS>();
 #pragma unroll
         for (int m = 0; m < 8; ++m) v[m] = T[rs * TS + t + 8 * m];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the row reads above precede stage B's in-place writes
+        wave_fence();   // the row reads above precede stage B's in-place writes
         stage_b<true>(v, buf, t, wr, w);
         group_sync<LPS>(); // T and the byte window are free again
     };
@@ -808,7 +808,7 @@ __global__ __launch_bounds__(256, (R <= 8 && KEEP == 0) ? 4 : 3) void k_txframe_
                 emit(valid, f0, fl, k, v, std::true_type{});
             }
             __syncthreads(); // every maximum of the round is final (and this thread's stores are acknowledged: s_waitcnt vmcnt(0))
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             emit_headers(f0);
             for (int step = 0; step < steps; ++step) {
                 long long f; int fl, k; bool valid;

@@ -100,8 +100,7 @@ __global__ __launch_bounds__(512, 4) void k_demod4096(Big4096Params p) { // 4 wa
     // prefetch starts: read where they were used, each was followed by s_waitcnt vmcnt(0) -- the start offset ahead of the sample
     // prefetch, the symbol count right behind it (draining it), the CFO, then the channel in four more round trips (round-5 ISA scan).
     struct FS { int off, ns; double fd; };
-    int vzero = 0;
-    asm volatile("" : "+v"(vzero));   // keeps the workgroup-uniform scalar loads vector loads (as scalar loads they are waited for where they are issued)
+    const int vzero = pinned(0);   // keeps the workgroup-uniform scalar loads vector loads (as scalar loads they are waited for where they are issued)
     auto load_scalars = [&](bool in, long long fr_) -> FS {
         const long long fr = (in ? fr_ : 0) + vzero;
         FS r;
@@ -288,7 +287,7 @@ __global__ __launch_bounds__(512, 4) void k_demod4096(Big4096Params p) { // 4 wa
                 const bool data = live && (all_data || bo >= 0); // a dead symbol writes nothing into the image
                 unsigned val = (GUARD ? demap_point_rot(v[q], rot, BPS) : demap_point(v[q], BPS)) << (BPS * (s & (32 / BPS - 1)));
                 val = data ? val : 0u;
-                val |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)val, 0x128, 0xF, 0xF, true);          // row_ror:8   : s ^ 1
+                val |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)val, 0x128, 0xF, 0xF, true);          // row_ror:8   : s ^ 1 (dpp_i<0x128> written out: as a call the v_or operands swap)
                 val |= (unsigned)__builtin_amdgcn_ds_swizzle((int)val, 0x401F);                               // xor 16      : s ^ 2
                 if (BPS == 4) val |= (unsigned)__shfl_xor((int)val, 32, 64);                                  // s ^ 4
                 img[(data && (s & (32 / BPS - 1)) == 0) ? (bo >> 5) : 1024 + 8] = val;

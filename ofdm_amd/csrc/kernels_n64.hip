@@ -28,10 +28,6 @@ namespace ofdm {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) f32x2 *lds_cf_ptr; // LDS pointer built from a 32-bit offset held in a VGPR
 typedef __attribute__((address_space(3))) unsigned *lds_u32_ptr;
-// A per-lane constant the compiler must KEEP in a register: without the empty asm it rematerialises the XOR / shift / mask
-// that produced it inside the loop (to stay under 96 VGPRs), once per use and iteration.
-__device__ __forceinline__ unsigned pinned(unsigned v) { asm volatile("" : "+v"(v)); return v; }
-
 // BURST (4, 8 or 16): a wavefront takes BURST consecutive 8-symbol groups per step and stores their packed images together -- for the
 // 288-byte images of 64-QAM with guard bands, 4 groups = 1152 bytes = nine WHOLE 128-byte lines (one group's image starts at
 // a multiple of 288 bytes: 2.25 lines, shared with the neighbours).  Needs a contiguous output (rows back to back).
@@ -231,7 +227,7 @@ struct RxFrame64Params {
 };
 
 __device__ __forceinline__ cf lane_xor_sum(cf v) { // sum over the 8 symbol slots: lanes with equal (lane & 7)
-    v.x += dpp8_f<0x128>(v.x); v.y += dpp8_f<0x128>(v.y);          // row_ror:8  : lane ^ 8
+    v.x += dpp_f<0x128>(v.x); v.y += dpp_f<0x128>(v.y);          // row_ror:8  : lane ^ 8
     v.x += __shfl_xor(v.x, 16, 64); v.y += __shfl_xor(v.y, 16, 64);
     v.x += __shfl_xor(v.x, 32, 64); v.y += __shfl_xor(v.y, 32, 64);
     return v;
@@ -296,8 +292,7 @@ __global__ __launch_bounds__(256, (MODE == 0 && GUARD) ? 4 : 3) void k_rxframe64
     const long long istep = (long long)gridDim.x * 4;
     // (A VGPR zero the compiler cannot fold keeps these wave-uniform loads per-lane loads: as scalar values they would be moved to
     // SGPRs, and waited for, right where they are issued.)
-    int vzero = 0;
-    asm volatile("" : "+v"(vzero));
+    const int vzero = pinned(0);
     long long f_n = 0; int ns_v = 0, off_v = 0; double fd_v = 0.0;
     auto fetch_scalars = [&](long long item) {
         if (item < n_items) {
@@ -354,8 +349,7 @@ __global__ __launch_bounds__(256, (MODE == 0 && GUARD) ? 4 : 3) void k_rxframe64
         unsigned zm = 0u;
         {
             cf tws[6]; // twiddles of the one-point-per-lane transform
-            int lq = lane;
-            asm volatile("" : "+v"(lq)); // per frame: keeps the six LDS addresses out of the loop-invariant registers (they spilled)
+            const int lq = pinned(lane); // per frame: keeps the six LDS addresses out of the loop-invariant registers (they spilled)
 #pragma unroll
             for (int q = 0; q < 6; ++q) {
                 const int h = 32 >> q;
@@ -385,9 +379,9 @@ __global__ __launch_bounds__(256, (MODE == 0 && GUARD) ? 4 : 3) void k_rxframe64
             h = make_float2(h.x * 0.2f, h.y * 0.2f);
             if (p.hk) p.hk[f * 64 + bin] = h;
             const float rn = __builtin_amdgcn_rcpf(h.x * h.x + h.y * h.y);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");    // the previous frame's last reads of this table are done
+            wave_fence();    // the previous frame's last reads of this table are done
             ginv[bin] = make_float2(h.x * rn, -h.y * rn);            // 1 / H
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            wave_fence();
         }
         for (int k0 = 0; k0 < ns; k0 += 8) { // data symbols, 8 at a time (chunks 10..)
             const int count = ns - k0 < 8 ? ns - k0 : 8;
@@ -440,7 +434,7 @@ __global__ __launch_bounds__(256, (MODE == 0 && GUARD) ? 4 : 3) void k_rxframe64
             zm = zn;
             const int ndw = (count * SYM_BYTES + 3) / 4;   // (6-byte symbols: an odd count ends in half a dword; its upper half is zero in the image and lies inside the row)
             if (p.final_out) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the image is complete
+                wave_fence(); // the image is complete
                 if (k0 == 0) { // bincode fixint little-endian u128 length (src/packets/mod.rs:20-32), then Vec::truncate
                     const unsigned long long lo = (unsigned long long)img[0] | ((unsigned long long)img[1] << 32);
                     const unsigned long long hi = (unsigned long long)img[2] | ((unsigned long long)img[3] << 32);
@@ -593,8 +587,7 @@ __global__ __launch_bounds__(256, 4) void k_txframe64(TxFrame64Params p) {
     // the registers; the ragged last dword of a row whose size is not a multiple of 4 is rebuilt byte by byte there.
     // payload_len[f] itself travels with them as a per-lane load (a VGPR zero the compiler cannot fold keeps it off the
     // scalar unit, whose loads are waited for at the next LDS wait).
-    int vzero = 0;
-    asm volatile("" : "+v"(vzero));
+    const int vzero = pinned(0);
     const bool row0 = aligned && 4LL * tid + 4 <= p.payload_bytes, row1 = aligned && 4LL * (tid + nthr) + 4 <= p.payload_bytes;
     auto issue = [&](long long fr, unsigned &d0, unsigned &d1, int &ln) {
         const long long fc = fr < p.n_frames ? fr : p.n_frames - 1; // past the batch: any mapped row, the values are never used
@@ -671,7 +664,7 @@ __global__ __launch_bounds__(256, 4) void k_txframe64(TxFrame64Params p) {
                 v[q] = y;
                 lmax = fmaxf(lmax, fmaxf(y.x, y.y));
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the slab reads above precede the overwrites below
+            wave_fence(); // the slab reads above precede the overwrites below
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 buf[CP + t + 8 * q] = v[q];

@@ -62,7 +62,6 @@ __device__ __forceinline__ void rs_load_tables(uint8_t *ex, uint8_t *lg, int tid
     lg[tid] = kRsTab.log[tid];
     __syncthreads();
 }
-__device__ __forceinline__ void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
 __device__ __forceinline__ unsigned wave_xor(unsigned v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v ^= (unsigned)__shfl_xor((int)v, o, 64);

@@ -51,8 +51,6 @@ struct RxFrame1024Params {
 
 constexpr int RX_RAW_DW = 896;   // LDS image of a frame's packed bytes (3.5 KB): fused finish for frames up to that size
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 struct Cur {          // a position in this workgroup's stream of (frame, step) items; step -5 .. -1 = training blocks, 0 .. ns-1 = data
     long long f;      // n_frames = end of the stream
     long long rel;    // offset[f]
@@ -100,8 +98,7 @@ __global__ __launch_bounds__(128, 3) void k_rxframe1024(RxFrame1024Params p) {
 
     // Per-frame scalars: the three loads of a frame go out together and are waited for once (as wave-uniform scalar values each
     // would be moved to SGPRs, and waited for, right where it is issued: three dependent round trips to HBM per frame).
-    int vzero = 0;
-    asm volatile("" : "+v"(vzero));   // a VGPR zero the compiler cannot fold: keeps the loads per-lane
+    const int vzero = pinned(0);   // a VGPR zero the compiler cannot fold: keeps the loads per-lane
     auto open_frame = [&](Cur &c, long long f) {
         for (;;) {
             c.f = f; c.step = -5; c.rel = 0; c.ns = 0; c.turns = 0.0;
@@ -231,7 +228,7 @@ __global__ __launch_bounds__(128, 3) void k_rxframe1024(RxFrame1024Params p) {
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             const cf e = cmul(v[c], w16tab[2 * c + u]);
-            const cf o = make_float2(dpp8_f<0xB1>(e.x), dpp8_f<0xB1>(e.y));   // the partner's value (lane ^ 1)
+            const cf o = make_float2(dpp_f<0xB1>(e.x), dpp_f<0xB1>(e.y));   // the partner's value (lane ^ 1)
             const cf y = u ? make_float2(o.x - e.x, o.y - e.y) : make_float2(e.x + o.x, e.y + o.y);
             T[(c + 8 * u) * TS + b] = cmul(y, z[c]);                          // Y_b[c' + 8 u] * W1024^(b c)
         }
@@ -241,7 +238,7 @@ __global__ __launch_bounds__(128, 3) void k_rxframe1024(RxFrame1024Params p) {
 #pragma unroll
         for (int m = 0; m < 8; ++m) v[m] = buf[t + 8 * m];
         bfly8<false>(v);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the row reads above precede the in-place writes below (in-order LDS pipe)
+        wave_fence(); // the row reads above precede the in-place writes below (in-order LDS pipe)
 #pragma unroll
         for (int r = 0; r < 8; ++r) buf[wr ^ r] = v[r];
 #pragma unroll

@@ -39,7 +39,7 @@
 // Ordinary captures do not reach the list: the metric of a lag in front of the crossing would have to lie within ~1e-13 of the
 // threshold, or the window's two best metrics within ~3e-7 of each other (none of 1 M config-3 slots does); all-zero lead-ins stay here.
 // Roofline: HBM, 8 B per sample actually needed (the slot up to d1 + 2 W + L, rounded up to pieces).
-#include "device_common.hpp"
+#include "sc_common.hpp"
 #include "kernels.hpp"
 #include <limits.h>
 #include <cmath>
@@ -61,47 +61,19 @@ struct S80Params {
     int32_t *slow_list, *slow_count;
 };
 
-template <int CTRL> __device__ __forceinline__ double s8_dpp(double x) {   // lanes without a source lane read 0
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL> __device__ __forceinline__ int s8_dpp_i(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, true); }
-// inclusive prefix sum over the 16 lanes of a row
-__device__ __forceinline__ double s8_row_scan(double x) {
-    x += s8_dpp<0x111>(x);   // row_shr:1
-    x += s8_dpp<0x112>(x);   // row_shr:2
-    x += s8_dpp<0x114>(x);   // row_shr:4
-    x += s8_dpp<0x118>(x);   // row_shr:8
-    return x;
-}
-__device__ __forceinline__ double s8_row_last(double x) { return s8_dpp<0x15F>(x); }   // row_newbcast:15
-template <int N> __device__ __forceinline__ void s8_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void s8_wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void s8_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
-
-struct S8Cand { double num, den, pr, pi; int lag; };
-// first maximum wins, whatever the order of discovery: strictly greater replaces; equal replaces only from a lower lag
-__device__ __forceinline__ S8Cand s8_pick(S8Cand a, S8Cand b) {
-    const double lhs = b.num * a.den, rhs = a.num * b.den;
-    return (lhs > rhs || (lhs == rhs && b.lag < a.lag)) ? b : a;
-}
-template <int CTRL> __device__ __forceinline__ S8Cand s8_cand_dpp(S8Cand c) {
-    return S8Cand{s8_dpp<CTRL>(c.num), s8_dpp<CTRL>(c.den), s8_dpp<CTRL>(c.pr), s8_dpp<CTRL>(c.pi), s8_dpp_i<CTRL>(c.lag)};
-}
+__device__ __forceinline__ double s8_row_last(double x) { return dpp_d<0x15F>(x); }   // row_newbcast:15
 // best candidate of the row, in every lane of the row (xor 1, xor 2, the other quad of the half, the other half)
-__device__ __forceinline__ S8Cand s8_row_best(S8Cand c) {
-    c = s8_pick(c, s8_cand_dpp<0xB1>(c));    // quad_perm [1,0,3,2]
-    c = s8_pick(c, s8_cand_dpp<0x4E>(c));    // quad_perm [2,3,0,1]
-    c = s8_pick(c, s8_cand_dpp<0x141>(c));   // row_half_mirror
-    c = s8_pick(c, s8_cand_dpp<0x140>(c));   // row_mirror
+__device__ __forceinline__ ScCand s8_row_best(ScCand c) {
+    c = cand_pick(c, cand_dpp<0xB1>(c));    // quad_perm [1,0,3,2]
+    c = cand_pick(c, cand_dpp<0x4E>(c));    // quad_perm [2,3,0,1]
+    c = cand_pick(c, cand_dpp<0x141>(c));   // row_half_mirror
+    c = cand_pick(c, cand_dpp<0x140>(c));   // row_mirror
     return c;
 }
 // the runner-up of a peak window needs no lag and no P: only how close it came
 struct S8Sec { double num, den; };
 template <int CTRL> __device__ __forceinline__ S8Sec s8_sec_max(S8Sec a) {
-    const S8Sec b = S8Sec{s8_dpp<CTRL>(a.num), s8_dpp<CTRL>(a.den)};
+    const S8Sec b = S8Sec{dpp_d<CTRL>(a.num), dpp_d<CTRL>(a.den)};
     return b.num * a.den > a.num * b.den ? b : a;
 }
 __device__ __forceinline__ S8Sec s8_row_sec(S8Sec c) {
@@ -112,10 +84,10 @@ __device__ __forceinline__ S8Sec s8_row_sec(S8Sec c) {
     return c;
 }
 __device__ __forceinline__ int s8_row_min(int x) {
-    x = min(x, s8_dpp_i<0xB1>(x));
-    x = min(x, s8_dpp_i<0x4E>(x));
-    x = min(x, s8_dpp_i<0x141>(x));
-    x = min(x, s8_dpp_i<0x140>(x));
+    x = min(x, dpp_i<0xB1>(x));
+    x = min(x, dpp_i<0x4E>(x));
+    x = min(x, dpp_i<0x141>(x));
+    x = min(x, dpp_i<0x140>(x));
     return x;
 }
 
@@ -130,7 +102,7 @@ struct S8State {
     bool okp;                     // last step's differences were trusted in this lane
     int d1, hi;                   // first crossing (-1: none yet), last lag of the peak window
     bool done, amb;
-    S8Cand best;                  // this lane's first maximum among its own lags of the window
+    ScCand best;                  // this lane's first maximum among its own lags of the window
     S8Sec second;                 // ... and the best of its other lags that came close to the best of their time
 };
 
@@ -195,7 +167,7 @@ __global__ __launch_bounds__(64, 2) void k_sc80(S80Params p) {
         s.okp = false;
         s.d1 = -1; s.hi = n - 1;
         s.done = !live; s.amb = false;
-        s.best = S8Cand{-1.0, 1.0, 0.0, 0.0, INT_MAX};
+        s.best = ScCand{-1.0, 1.0, 0.0, 0.0, INT_MAX};
         s.second = S8Sec{-1.0, 1.0};
 
         unsigned round_byte = 0;   // stream byte of ring slot 0 in this round
@@ -207,14 +179,14 @@ __global__ __launch_bounds__(64, 2) void k_sc80(S80Params p) {
             constexpr int S = decltype(S_)::value;
             const int t = t0 + S;
             // this period's samples have landed; the younger pieces may still be in flight (their number is fixed by the schedule)
-            s8_wait_vm<D == 1 ? 9 + (S & 1) : 7>();
-            s8_fence();
+            wait_vm<D == 1 ? 9 + (S & 1) : 7>();
+            wave_fence();
             cf x[5];
 #pragma unroll
             for (int j = 0; j < 5; ++j)
                 x[j] = *reinterpret_cast<const cf *>(ring + ra[S & 1][j] + 5120u * (S >> 1));
-            s8_wait_lgkm();
-            s8_fence();
+            wait_lgkm();
+            wave_fence();
             // refill the pieces whose last byte was read D steps ago (a step of the previous round: with this round's stream)
             {
                 constexpr int SF = (S - D + 6) % 6;
@@ -237,7 +209,7 @@ __global__ __launch_bounds__(64, 2) void k_sc80(S80Params p) {
                 ti = fma(-ai, br[j], fma(ar, bi[j], ti));
                 s.xp[j] = x[j];
             }
-            const double ie = s8_row_scan(te), ir = s8_row_scan(tr), ii = s8_row_scan(ti);
+            const double ie = row_scan(te), ir = row_scan(tr), ii = row_scan(ti);
             const double oe = s.base_e + (ie - te), orr = s.base_qr + (ir - tr), oi = s.base_qi + (ii - ti);
             s.base_e += s8_row_last(ie); s.base_qr += s8_row_last(ir); s.base_qi += s8_row_last(ii);
             constexpr int KE = S % 3, KQ = (S + 2) % 3;   // ring slots of SE_{t-3} and SQ_{t-4} (overwritten by SE_t, SQ_{t-1})
@@ -338,7 +310,7 @@ __global__ __launch_bounds__(64, 2) void k_sc80(S80Params p) {
                         const bool in = live_lane && j < cnt && j >= lo;
                         const double lhs = num[j] * s.best.den, rhs = s.best.num * den[j];
                         any_near |= in && s.best.num >= 0.0 && fabs(lhs - rhs) <= tie * fabs(rhs);
-                        if (in && lhs > rhs) s.best = S8Cand{num[j], den[j], Pr[j], Pi[j], d0 + j};
+                        if (in && lhs > rhs) s.best = ScCand{num[j], den[j], Pr[j], Pi[j], d0 + j};
                     }
                     if (__builtin_amdgcn_ballot_w64(any_near)) {   // (rare) the same walk again from the step's first best, keeping the losers
                         S8Sec b0 = start;
@@ -378,8 +350,8 @@ __global__ __launch_bounds__(64, 2) void k_sc80(S80Params p) {
         //      in flight lands first (clamped addresses once the crossing is known: cache hits), so that no older piece can arrive
         //      in a ring slot after a newer one.
         const long long gn = g + gridDim.x;
-        s8_wait_vm<0>();
-        s8_fence();
+        wait_vm<0>();
+        wave_fence();
         if (gn < groups) {
             sb = reinterpret_cast<const char *>(p.in + 4 * gn * p.frame_stride);
             rowoff = row_offset(gn);
@@ -387,7 +359,7 @@ __global__ __launch_bounds__(64, 2) void k_sc80(S80Params p) {
             for (int k = 0; k < AHEAD; ++k) issue_at(sb, rowoff, limit0, k, 256u * k);
         }
         // ---- the row's verdict: first maximum over its lanes; a row that met an untrusted lag goes to the slow list
-        const S8Cand b = s8_row_best(s.best);
+        const ScCand b = s8_row_best(s.best);
         // ... which must beat the best of all other lags of the window (the other lanes' bests, the winner lane's runner-up) by more
         // than the metrics of trusted lanes can be wrong: a maximum inside that bound is the oracle's to pick
         S8Sec mine2 = S8Sec{s.best.num, s.best.den};
@@ -413,7 +385,7 @@ __global__ __launch_bounds__(64, 2) void k_sc80(S80Params p) {
         if (gn >= groups) break;
         g = gn;
     }
-    s8_wait_vm<0>();
+    wait_vm<0>();
 }
 
 // L = 80, W = 240, frames of even length (LDS-DMA in 16-byte units), four frames' row offsets in 32 bits

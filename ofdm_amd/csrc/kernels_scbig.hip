@@ -25,7 +25,7 @@
 // in question): with the threshold within 1e-9 of a lag's metric every case is the oracle's, also behind a burst that leaves the
 // windows 2^-17 of the capture's energy; within 1e-12 every case is down to windows of 2^-15, and 2 of 4 decisions differ behind the
 // burst that leaves 2^-17.  Ties below f64 resolution aside.  Works for any N in 128..4096 (the LDS footprint does not depend on L) and any capture of up to 2047 chunks.
-#include "device_common.hpp"
+#include "sc_common.hpp"
 #include "kernels.hpp"
 #include <limits.h>
 
@@ -36,19 +36,6 @@ namespace {
 constexpr int B_TILE = 2560;   // samples per chunk-sum tile (256 threads x 10)
 constexpr int F_WG = 64;        // one wavefront per frame; tiles of 5 or 10 lags per thread (run_sc_big): 11 / 21 KB of LDS, 12 / 7 frames
                                 // in flight per CU (128 threads / 1280 lags: 3 per CU, 25 % slower)
-
-struct BSums { double pr, pi, e, r; };
-__device__ __forceinline__ BSums bs_add(BSums a, BSums b) { return BSums{a.pr + b.pr, a.pi + b.pi, a.e + b.e, a.r + b.r}; }
-struct BCand { double num, den, pr, pi; int lag; };
-// first maximum wins, whatever the order of discovery: strictly greater replaces; equal replaces only from a lower lag
-__device__ __forceinline__ BCand bc_pick(BCand a, BCand b) {
-    const double lhs = b.num * a.den, rhs = a.num * b.den;
-    return (lhs > rhs || (lhs == rhs && b.lag < a.lag)) ? b : a;
-}
-__device__ __forceinline__ BCand bc_shfl_xor(BCand a, int d) {
-    return BCand{__shfl_xor(a.num, d, 64), __shfl_xor(a.den, d, 64), __shfl_xor(a.pr, d, 64), __shfl_xor(a.pi, d, 64),
-                 __shfl_xor(a.lag, d, 64)};
-}
 
 // Coalesced staging of NSEG segments of PER * nthr * 2 samples each into LDS, zero past the capture.  All loads of all
 // segments are issued before the first LDS store (a load -> store -> load chain would expose the memory latency once per
@@ -165,8 +152,8 @@ __global__ __launch_bounds__(F_WG, LPT == 10 ? 2 : 3) void k_scb_fine(ScBigParam
     cf *s2 = s1 + F_TILE + 16;                   // ... at d0 + W
     cf *s3 = s2 + F_TILE + 16;                   // ... at d0 + W + L
     float *mub = reinterpret_cast<float *>(s3 + F_TILE + 16);    // [nch_pad] upper bound of M over the chunk's lags (rounded up)
-    BSums *wsum = reinterpret_cast<BSums *>(mub + p.nch_pad);    // [2] wave totals
-    BCand *wcand = reinterpret_cast<BCand *>(wsum + 2);          // [2]
+    ScSums *wsum = reinterpret_cast<ScSums *>(mub + p.nch_pad);    // [2] wave totals
+    ScCand *wcand = reinterpret_cast<ScCand *>(wsum + 2);          // [2]
     int *wmin = reinterpret_cast<int *>(wcand + 2);              // [2]
     int *shi = wmin + 2;                                         // [2] scratch
 
@@ -205,12 +192,12 @@ __global__ __launch_bounds__(F_WG, LPT == 10 ? 2 : 3) void k_scb_fine(ScBigParam
         // total (120 dB down, a thousand times the worst residue) therefore counts as the zero it stands for: no metric defined there.
         const double zfloor = Ep[nch] * 9.094947017729282e-13;
         // exact sums at chunk boundary c (lag c C)
-        auto boundary = [&](int c) -> BSums {
-            return BSums{Qr[c + cW] - Qr[c], Qi[c + cW] - Qi[c], Ep[c + cW] - Ep[c], Ep[c + cW + cL] - Ep[c + cL]};
+        auto boundary = [&](int c) -> ScSums {
+            return ScSums{Qr[c + cW] - Qr[c], Qi[c + cW] - Qi[c], Ep[c + cW] - Ep[c], Ep[c + cW + cL] - Ep[c + cL]};
         };
         // ---- upper bound of the metric over each chunk's lags
         for (int c = tid; c < n_bound; c += F_WG) {
-            const BSums b = boundary(c);
+            const ScSums b = boundary(c);
             const double te0 = Ep[c + 1] - Ep[c], teL = Ep[c + cL + 1] - Ep[c + cL], teW = Ep[c + cW + 1] - Ep[c + cW],
                          teWL = Ep[c + cW + cL + 1] - Ep[c + cW + cL];
             const double ub = sqrt(b.pr * b.pr + b.pi * b.pi) * (1.0 + 1e-12) + 0.5 * (te0 + teL + teW + teWL);
@@ -224,7 +211,7 @@ __global__ __launch_bounds__(F_WG, LPT == 10 ? 2 : 3) void k_scb_fine(ScBigParam
 
         // Exact evaluation of the F_TILE lags from d0 (a chunk boundary): first crossing in [lo, hi] (if want_cross), then the
         // first maximum over [max(lo, crossing), hi].  Returns the crossing (INT_MAX: none) through *cross_out.
-        auto eval_tile = [&](long long d0, long long lo, long long hi, bool want_cross, long long &cross_out, BCand &best) {
+        auto eval_tile = [&](long long d0, long long lo, long long hi, bool want_cross, long long &cross_out, ScCand &best) {
             __syncthreads();
             {
                 cf *const dsts[4] = {s0, s1, s2, s3};
@@ -247,9 +234,9 @@ __global__ __launch_bounds__(F_WG, LPT == 10 ? 2 : 3) void k_scb_fine(ScBigParam
             }
             __syncthreads();
             const int a0 = tid * LPT;
-            BSums pre[LPT];
+            ScSums pre[LPT];
             {
-                BSums run = BSums{0, 0, 0, 0};
+                ScSums run = ScSums{0, 0, 0, 0};
 #pragma unroll
                 for (int j = 0; j < LPT; ++j) {
                     const cf x0 = s0[a0 + j], x1 = s1[a0 + j], x2 = s2[a0 + j], x3 = s3[a0 + j];
@@ -261,19 +248,19 @@ __global__ __launch_bounds__(F_WG, LPT == 10 ? 2 : 3) void k_scb_fine(ScBigParam
                     pre[j] = run;
                 }
             }
-            BSums inc = pre[LPT - 1];
+            ScSums inc = pre[LPT - 1];
 #pragma unroll
             for (int sft = 1; sft < 64; sft <<= 1) {
-                const BSums o = BSums{__shfl_up(inc.pr, sft, 64), __shfl_up(inc.pi, sft, 64), __shfl_up(inc.e, sft, 64), __shfl_up(inc.r, sft, 64)};
-                if (lane >= sft) inc = bs_add(inc, o);
+                const ScSums o = s_shfl_up(inc, sft);
+                if (lane >= sft) inc = s_add(inc, o);
             }
             if (lane == 63) wsum[wave] = inc;
             __syncthreads();
-            BSums base = boundary((int)(d0 / C));
-            for (int wv = 0; wv < wave; ++wv) base = bs_add(base, wsum[wv]);
+            ScSums base = boundary((int)(d0 / C));
+            for (int wv = 0; wv < wave; ++wv) base = s_add(base, wsum[wv]);
             {
-                const BSums ex = BSums{__shfl_up(inc.pr, 1, 64), __shfl_up(inc.pi, 1, 64), __shfl_up(inc.e, 1, 64), __shfl_up(inc.r, 1, 64)};
-                if (lane > 0) base = bs_add(base, ex);
+                const ScSums ex = s_shfl_up(inc, 1);
+                if (lane > 0) base = s_add(base, ex);
             }
             // base = sums at lag d0 + a0
             long long cross = LLONG_MAX;
@@ -281,7 +268,7 @@ __global__ __launch_bounds__(F_WG, LPT == 10 ? 2 : 3) void k_scb_fine(ScBigParam
                 int mine = INT_MAX;
 #pragma unroll
                 for (int j = LPT - 1; j >= 0; --j) {
-                    const BSums x = j ? bs_add(base, pre[j - 1]) : base;
+                    const ScSums x = j ? s_add(base, pre[j - 1]) : base;
                     const double num = x.pr * x.pr + x.pi * x.pi, den = x.e * x.r;
                     const long long lag = d0 + a0 + j;
                     if (lag >= lo && lag <= hi && x.e > zfloor && x.r > zfloor && num >= thr * den) mine = a0 + j;
@@ -296,24 +283,24 @@ __global__ __launch_bounds__(F_WG, LPT == 10 ? 2 : 3) void k_scb_fine(ScBigParam
                 cross_out = cross;
                 if (m == INT_MAX) return; // wave-uniform: no crossing in this tile, nothing to maximise yet
             }
-            BCand mineb = BCand{-1.0, 1.0, 0.0, 0.0, INT_MAX};
+            ScCand mineb = ScCand{-1.0, 1.0, 0.0, 0.0, INT_MAX};
 #pragma unroll
             for (int j = 0; j < LPT; ++j) {
-                const BSums x = j ? bs_add(base, pre[j - 1]) : base;
+                const ScSums x = j ? s_add(base, pre[j - 1]) : base;
                 const double num = x.pr * x.pr + x.pi * x.pi, den = x.e * x.r;
                 const long long lag = d0 + a0 + j;
-                if (lag >= lo && lag <= hi && x.e > zfloor && x.r > zfloor) mineb = bc_pick(mineb, BCand{num, den, x.pr, x.pi, (int)lag});
+                if (lag >= lo && lag <= hi && x.e > zfloor && x.r > zfloor) mineb = cand_pick(mineb, ScCand{num, den, x.pr, x.pi, (int)lag});
             }
 #pragma unroll
-            for (int sft = 32; sft >= 1; sft >>= 1) mineb = bc_pick(mineb, bc_shfl_xor(mineb, sft));
+            for (int sft = 32; sft >= 1; sft >>= 1) mineb = cand_pick(mineb, cand_shfl_xor(mineb, sft));
             if (lane == 0) wcand[wave] = mineb;
             __syncthreads();
-            for (int wv = 0; wv < F_WG / 64; ++wv) best = bc_pick(best, wcand[wv]);
+            for (int wv = 0; wv < F_WG / 64; ++wv) best = cand_pick(best, wcand[wv]);
         };
 
         // ---- first crossing: chunks whose bound reaches the threshold, in lag order
         long long d1 = LLONG_MAX, tile0 = 0;
-        BCand best = BCand{-1.0, 1.0, 0.0, 0.0, INT_MAX};
+        ScCand best = ScCand{-1.0, 1.0, 0.0, 0.0, INT_MAX};
         const float thr_f = (float)thr * 0.999999f;
         int c = 0;
         for (;;) {
@@ -343,17 +330,17 @@ __global__ __launch_bounds__(F_WG, LPT == 10 ? 2 : 3) void k_scb_fine(ScBigParam
         const long long dend = d1 + W < n - 1 ? d1 + W : n - 1;
         {
             __syncthreads(); // every thread has merged the crossing tile's candidates out of wcand
-            BCand bb = BCand{-1.0, 1.0, 0.0, 0.0, INT_MAX};
+            ScCand bb = ScCand{-1.0, 1.0, 0.0, 0.0, INT_MAX};
             for (int cb = (int)((d1 + C - 1) / C) + tid; (long long)cb * C <= dend; cb += F_WG) {
-                const BSums x = boundary(cb);
+                const ScSums x = boundary(cb);
                 const double num = x.pr * x.pr + x.pi * x.pi, den = x.e * x.r;
-                if (x.e > zfloor && x.r > zfloor) bb = bc_pick(bb, BCand{num, den, x.pr, x.pi, cb * C});
+                if (x.e > zfloor && x.r > zfloor) bb = cand_pick(bb, ScCand{num, den, x.pr, x.pi, cb * C});
             }
 #pragma unroll
-            for (int sft = 32; sft >= 1; sft >>= 1) bb = bc_pick(bb, bc_shfl_xor(bb, sft));
+            for (int sft = 32; sft >= 1; sft >>= 1) bb = cand_pick(bb, cand_shfl_xor(bb, sft));
             if (lane == 0) wcand[wave] = bb;
             __syncthreads();
-            for (int wv = 0; wv < F_WG / 64; ++wv) best = bc_pick(best, wcand[wv]);
+            for (int wv = 0; wv < F_WG / 64; ++wv) best = cand_pick(best, wcand[wv]);
             __syncthreads();
         }
         for (long long t = tile0 + F_TILE; t <= dend; t += F_TILE) {
@@ -420,8 +407,8 @@ hipError_t run_sc_big(const ScParams &p, void *workspace, int num_cu, hipStream_
     // frames in flight per CU) at twice the number of tiles.
     const bool small = q.C <= 320 && (320 % q.C) == 0 && !tu.scb_big_tiles;
     const int f_tile = small ? 5 * F_WG : 10 * F_WG;
-    const size_t lds = (size_t)4 * (f_tile + 16) * sizeof(float2) + (size_t)q.nch_pad * sizeof(float) + 2 * sizeof(BSums) +
-                       2 * sizeof(BCand) + 4 * sizeof(int) + 64;
+    const size_t lds = (size_t)4 * (f_tile + 16) * sizeof(float2) + (size_t)q.nch_pad * sizeof(float) + 2 * sizeof(ScSums) +
+                       2 * sizeof(ScCand) + 4 * sizeof(int) + 64;
     long long per_cu = (long long)(160 * 1024) / (long long)lds;
     const long long cap = small ? 12 : 8; // 3 / 2 waves per SIMD (163 / 236 VGPRs; 4 waves spill 22 registers for +2 %)
     if (per_cu > cap) per_cu = cap;

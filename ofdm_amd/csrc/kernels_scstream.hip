@@ -27,7 +27,7 @@
 // energy; within 1e-12 every case is while the windows hold 2^-9 of the energy or more, and 2 of 8 decisions differ behind each of the
 // bursts that leave 2^-15 and 2^-17.  Ties below f64 resolution aside.
 // Roofline: HBM, 8 B per sample actually needed; the bench reports achieved rates against the WHOLE capture.
-#include "device_common.hpp"
+#include "sc_common.hpp"
 #include "kernels.hpp"
 #include <limits.h>
 
@@ -54,69 +54,7 @@ struct StParams {
                  // crossing, 5 barrier waits, 6 closing the window; 7 the whole frame (consumer)
 };
 
-struct SSums { double pr, pi, e, r; };
-struct SCand { double num, den, pr, pi; int lag; };
-// first maximum wins, whatever the order of discovery: strictly greater replaces; equal replaces only from a lower lag
-__device__ __forceinline__ SCand sc_pick(SCand a, SCand b) {
-    const double lhs = b.num * a.den, rhs = a.num * b.den;
-    return (lhs > rhs || (lhs == rhs && b.lag < a.lag)) ? b : a;
-}
-__device__ __forceinline__ SCand sc_shfl_xor(SCand a, int d) {
-    return SCand{__shfl_xor(a.num, d, 64), __shfl_xor(a.den, d, 64), __shfl_xor(a.pr, d, 64), __shfl_xor(a.pi, d, 64),
-                 __shfl_xor(a.lag, d, 64)};
-}
-__device__ __forceinline__ SCand sc_wave_best(SCand c) {
-#pragma unroll
-    for (int sft = 32; sft >= 1; sft >>= 1) c = sc_pick(c, sc_shfl_xor(c, sft));
-    return c;
-}
-
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ double st_dpp(double x) {
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xF, true); // out-of-range / masked lanes read 0
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-// inclusive prefix sum over the 64 lanes of a wavefront
-__device__ __forceinline__ double st_scan(double x) {
-    x += st_dpp<0x111, 0xF>(x); // row_shr:1
-    x += st_dpp<0x112, 0xF>(x); // row_shr:2
-    x += st_dpp<0x114, 0xF>(x); // row_shr:4
-    x += st_dpp<0x118, 0xF>(x); // row_shr:8
-    x += st_dpp<0x142, 0xA>(x); // row_bcast:15 into rows 1 and 3
-    x += st_dpp<0x143, 0xC>(x); // row_bcast:31 into rows 2 and 3
-    return x;
-}
-__device__ __forceinline__ double st_readlane(double x, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
-}
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ float st_dpp_f(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, ROW_MASK, 0xF, true));
-}
-// maximum of a non-negative float over the wavefront (DPP only: no LDS round trips), returned wave-uniform
-__device__ __forceinline__ float st_wave_max(float x) {
-    x = fmaxf(x, st_dpp_f<0x111, 0xF>(x));
-    x = fmaxf(x, st_dpp_f<0x112, 0xF>(x));
-    x = fmaxf(x, st_dpp_f<0x114, 0xF>(x));
-    x = fmaxf(x, st_dpp_f<0x118, 0xF>(x));
-    x = fmaxf(x, st_dpp_f<0x142, 0xA>(x));
-    x = fmaxf(x, st_dpp_f<0x143, 0xC>(x));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
-}
-__device__ __forceinline__ SCand sc_readlane(SCand c, int l) {
-    auto rd = [&](double v) { return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l)); };
-    return SCand{rd(c.num), rd(c.den), rd(c.pr), rd(c.pi), __builtin_amdgcn_readlane(c.lag, l)};
-}
-template <int N> __device__ __forceinline__ void st_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ int st_wrap(int x, int m) { return x >= m ? x - m : x; }   // ring index of x in [0, 2 m): no integer division in the loop
-// values that ARE wave-uniform but derive from cross-lane operations (which the compiler's divergence analysis cannot see through)
-__device__ __forceinline__ int st_uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
-__device__ __forceinline__ const char *st_uni_ptr(const char *q) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(q);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-    return reinterpret_cast<const char *>(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ void st_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
 
 } // namespace
 
@@ -169,8 +107,8 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
             const long long t0 = (long long)s * ST_T;
             const unsigned slot = (unsigned)slot_idx * (unsigned)(ST_T * sizeof(cf));
             if (t0 + ST_T <= p.frame_len) {
-                const char *sb = st_uni_ptr(reinterpret_cast<const char *>(frame + t0));
-                const unsigned l0 = (unsigned)st_uni((int)(ring_lds + slot));
+                const char *sb = uniform_ptr(reinterpret_cast<const char *>(frame + t0));
+                const unsigned l0 = (unsigned)uniform((int)(ring_lds + slot));
 #pragma unroll
                 for (int j = 0; j < ST_PIECES; ++j) glds16(sb, (unsigned)j * 1024u + (unsigned)lane * 16u, l0 + (unsigned)j * 1024u);
                 return true;
@@ -202,11 +140,11 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
         {
             // the first two tiles go out before the frame's barrier: the ring belongs to the producer alone, and the consumer may
             // still be closing the previous frame's window
-            st_wait_vm<0>();                              // (tiles of the previous frame issued beyond its last step)
+            wait_vm<0>();                              // (tiles of the previous frame issued beyond its last step)
             if (s_max > 0) { dma0 = issue(0, 0); issued = 1; }
             if (s_max > 1) { dma1 = issue(1, 1 % ring_tiles); issued = 2; }
             if (lane == 0) { Ep[0] = 0.0; Qr[0] = 0.0; Qi[0] = 0.0; }   // (the consumer left the rings at the last barrier of the previous frame)
-            st_fence();
+            wave_fence();
             long long pt0 = 0, pt1 = 0, pt2 = 0;
 #pragma clang loop unroll(disable)
             for (int i = 0;; ++i) {
@@ -214,8 +152,8 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
                 long long tb = ta;
                 if (i < s_stop) {
                 // ---- PRODUCER, tile i: it has landed (this wavefront issued every piece of it); the next one stays in flight
-                if (dma0) { if (issued > i + 1 && dma1) st_wait_vm<ST_PIECES>(); else st_wait_vm<0>(); }
-                st_fence();
+                if (dma0) { if (issued > i + 1 && dma1) wait_vm<ST_PIECES>(); else wait_vm<0>(); }
+                wave_fence();
                 tb = now();
                 // Tile i + 2 is requested two tiles ahead.  DELAY == 0: into a slot of the L + 3-tile ring that nobody reads any more.
                 // DELAY > 0: the ring has TWO slots (25 instead of 30 KB of LDS per frame: six frames per CU), so it goes into tile i's own
@@ -243,7 +181,7 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
                         for (int j = 0; j < 5; ++j) y[j] = make_float4(0.f, 0.f, 0.f, 0.f);
                     }
                     if (DELAY > 0) {
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // every lane's reads of tile i are done (one wavefront owns the ring)
+                        wait_lgkm();   // every lane's reads of tile i are done (one wavefront owns the ring)
                         if (issued == i + 2 && issued < s_stop) { dma2 = issue(issued, slot_i); ++issued; }
                     }
                     dma0 = dma1; dma1 = dma2;
@@ -265,11 +203,11 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
                     }
                 }
                 // inclusive scans -> prefix entries ke + 1 (Ep) and kq + 1 (Q)
-                const double pe_ = st_scan(se) + run_e, pqr = st_scan(sqr) + run_qr, pqi = st_scan(sqi) + run_qi;
+                const double pe_ = wave_scan(se) + run_e, pqr = wave_scan(sqr) + run_qr, pqi = wave_scan(sqi) + run_qi;
                 Ep[st_wrap(e_new + lane + 1, p.epn)] = pe_;
                 if (kq >= 0) { const int j = st_wrap(q_new + lane + 1, p.qn); Qr[j] = pqr; Qi[j] = pqi; }
-                run_e = st_readlane(pe_, 63);
-                if (64 * i + 63 - cL >= 0) { run_qr = st_readlane(pqr, 63); run_qi = st_readlane(pqi, 63); }
+                run_e = readlane_d(pe_, 63);
+                if (64 * i + 63 - cL >= 0) { run_qr = readlane_d(pqr, 63); run_qi = readlane_d(pqi, 63); }
                 slot_s = st_wrap(slot_s + 1, ring_tiles); slot_i = st_wrap(slot_i + 1, ring_tiles);
                 e_new = st_wrap(e_new + 64, p.epn); q_new = st_wrap(q_new + 64, p.qn);
             }
@@ -283,9 +221,9 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
             }
             if (prof && lane == 0) { ptk[0] = pt0; ptk[1] = pt1; ptk[2] = pt2; }
         }
-        st_fence();
+        wave_fence();
     }
-    st_wait_vm<0>();
+    wait_vm<0>();
     } else {
     for (long long f = blockIdx.x; f < p.n_frames; f += gridDim.x) {
         const cf *frame = p.in + f * p.frame_stride;
@@ -294,9 +232,9 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
         // M >= threshold (INT_MAX: none) and the first maximum.  from_cross: the maximum only counts lags from this interval's own
         // first crossing on (the search before the crossing: the lane that holds the wavefront's lowest crossing then already has
         // the candidates of the peak window's first interval).
-        auto eval_interval = [&](bool active, int k, SSums x, long long lo, long long hi, bool from_cross, int &cross, SCand &best) {
+        auto eval_interval = [&](bool active, int k, ScSums x, long long lo, long long hi, bool from_cross, int &cross, ScCand &best) {
             cross = INT_MAX;
-            best = SCand{-1.0, 1.0, 0.0, 0.0, INT_MAX};
+            best = ScCand{-1.0, 1.0, 0.0, 0.0, INT_MAX};
             const long long d0 = 10LL * k;
             // The loads are UNCONDITIONAL, from an address that is always valid (the sample itself, or sample 0 of the frame for a
             // lane / an index that must read as zero), and the zeros are selected afterwards: written as `cond ? frame[i] : 0` the
@@ -329,7 +267,7 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
                     const double num = x.pr * x.pr + x.pi * x.pi, den = x.e * x.r;
                     if (active && lag >= lo && lag <= hi && den > 0.0) {
                         if (cross == INT_MAX && num >= thr * den) cross = (int)lag;
-                        if (!from_cross || cross != INT_MAX) best = sc_pick(best, SCand{num, den, x.pr, x.pi, (int)lag});
+                        if (!from_cross || cross != INT_MAX) best = cand_pick(best, ScCand{num, den, x.pr, x.pi, (int)lag});
                     }
                     const double r0 = s0[jj].x, i0 = s0[jj].y, r1 = s1[jj].x, i1 = s1[jj].y, r2 = s2[jj].x, i2 = s2[jj].y, r3 = s3[jj].x, i3 = s3[jj].y;
                     x.pr += (r2 * r3 + i2 * i3) - (r0 * r1 + i0 * i1);
@@ -343,7 +281,7 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
                 const double num = x.pr * x.pr + x.pi * x.pi, den = x.e * x.r;
                 if (active && lag >= lo && lag <= hi && den > 0.0) {
                     if (cross == INT_MAX && num >= thr * den) cross = (int)lag;
-                    if (!from_cross || cross != INT_MAX) best = sc_pick(best, SCand{num, den, x.pr, x.pi, (int)lag});
+                    if (!from_cross || cross != INT_MAX) best = cand_pick(best, ScCand{num, den, x.pr, x.pi, (int)lag});
                 }
             }
         };
@@ -352,22 +290,22 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
         long long d1 = -1, hi = n - 1;                    // first crossing; last lag of the peak window
         int k1 = 0, kE = INT_MAX;                         // interval of d1; interval of hi
         int n_live = 0;
-        SCand best = SCand{-1.0, 1.0, 0.0, 0.0, INT_MAX};     // the crossing's interval and every flushed list
-        SCand mybest = SCand{-1.0, 1.0, 0.0, 0.0, INT_MAX};   // per lane: the exact boundary candidates this lane has met (merged once, at the end)
+        ScCand best = ScCand{-1.0, 1.0, 0.0, 0.0, INT_MAX};     // the crossing's interval and every flushed list
+        ScCand mybest = ScCand{-1.0, 1.0, 0.0, 0.0, INT_MAX};   // per lane: the exact boundary candidates this lane has met (merged once, at the end)
         float best_lo = 0.f;                                  // LOWER bound of the best metric met so far (f32, rounded down): prunes the list
         bool done = false;
         // evaluate every interval on the live list exactly, fold the result into `best`, empty the list
         auto flush_live = [&]() {
-            st_fence();
+            wave_fence();
             const bool act = lane < n_live;
             const int k = act ? lk[lane] : 0;
-            const SSums x = act ? SSums{lsum[4 * lane], lsum[4 * lane + 1], lsum[4 * lane + 2], lsum[4 * lane + 3]} : SSums{0, 0, 0, 0};
-            int cr; SCand c;
+            const ScSums x = act ? ScSums{lsum[4 * lane], lsum[4 * lane + 1], lsum[4 * lane + 2], lsum[4 * lane + 3]} : ScSums{0, 0, 0, 0};
+            int cr; ScCand c;
             eval_interval(act, k, x, d1, hi, false, cr, c);
-            best = sc_pick(best, sc_wave_best(c));
+            best = cand_pick(best, cand_wave_best(c));
             if (best.lag != INT_MAX) best_lo = fmaxf(best_lo, (float)(best.num / best.den) * 0.99999f);
             n_live = 0;
-            st_fence();
+            wave_fence();
         };
 
         int s_stop = s_max;                               // tiles beyond this one are not needed (the consumer learns it with d1)
@@ -390,14 +328,14 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
                 const int s = i - 1;
                 const int k = 64 * s - cWL + lane;
                 const bool valid = k >= 0 && 10LL * k < n;
-                SSums b = SSums{0, 0, 0, 0};
+                ScSums b = ScSums{0, 0, 0, 0};
                 float ub = 0.f;
                 if (valid) {
                     // ring positions of k, k + cL, k + cW, k + cWL (each offset is below the ring size: one conditional wrap each)
                     const int e0 = st_wrap(e_k + lane, p.epn), eL = st_wrap(e0 + cL, p.epn), eW = st_wrap(e0 + cW, p.epn), eWL = st_wrap(eW + cL, p.epn);
                     const int q0 = st_wrap(q_k + lane, p.qn), qW = st_wrap(q0 + cW, p.qn);
                     const double E0 = Ep[e0], EL = Ep[eL], EW = Ep[eW], EWL = Ep[eWL];
-                    b = SSums{Qr[qW] - Qr[q0], Qi[qW] - Qi[q0], EW - E0, EWL - EL};   // exact sums at lag 10 k
+                    b = ScSums{Qr[qW] - Qr[q0], Qi[qW] - Qi[q0], EW - E0, EWL - EL};   // exact sums at lag 10 k
                     const double te0 = Ep[st_wrap(e0 + 1, p.epn)] - E0, teL = Ep[st_wrap(eL + 1, p.epn)] - EL,
                                  teW = Ep[st_wrap(eW + 1, p.epn)] - EW, teWL = Ep[st_wrap(eWL + 1, p.epn)] - EWL;
                     // The bound only has to be an UPPER bound: the exact f64 sums are rounded to f32 (6e-8 each), the square root, the
@@ -414,14 +352,14 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
                     // ---- before the crossing: intervals whose bound reaches the threshold are evaluated lag by lag
                     const bool flag = valid && ub >= thr_f;
                     if (__builtin_amdgcn_ballot_w64(flag)) {
-                        int cr; SCand c;
+                        int cr; ScCand c;
                         const long long te_ = now();
                         eval_interval(flag, k, b, 0, n - 1, true, cr, c);
-                        if (prof) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); tev = now() - te_; }
+                        if (prof) { wait_vm<0>(); tev = now() - te_; }
                         int cmin = cr;
 #pragma unroll
                         for (int sft = 32; sft >= 1; sft >>= 1) { const int o = __shfl_xor(cmin, sft, 64); cmin = o < cmin ? o : cmin; }
-                        cmin = st_uni(cmin);
+                        cmin = uniform(cmin);
                         if (cmin != INT_MAX) {
                             d1 = cmin; k1 = (int)(d1 / 10);
                             hi = d1 + W < n - 1 ? d1 + W : n - 1;
@@ -432,7 +370,7 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
                             // the crossing's own interval, from the crossing on: held by the one lane whose first crossing is d1
                             // (hi >= d1 + 9 unless the search ends inside this interval, where eval_interval's own range [0, n - 1] agrees)
                             const int src = __builtin_ctzll(__builtin_amdgcn_ballot_w64(cr == cmin));
-                            best = sc_readlane(c, src);
+                            best = cand_readlane(c, src);
                             best_lo = (float)(best.num / best.den) * 0.99999f;
                         }
                     }
@@ -444,25 +382,25 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
                     float mf = 0.f;
                     if (inwin) {
                         const double num = b.pr * b.pr + b.pi * b.pi, den = b.e * b.r;
-                        if (den > 0.0) { mybest = sc_pick(mybest, SCand{num, den, b.pr, b.pi, 10 * k}); mf = (float)num * __builtin_amdgcn_rcpf((float)den); }
+                        if (den > 0.0) { mybest = cand_pick(mybest, ScCand{num, den, b.pr, b.pi, 10 * k}); mf = (float)num * __builtin_amdgcn_rcpf((float)den); }
                     }
-                    best_lo = fmaxf(best_lo, st_wave_max(mf) * 0.99999f);
+                    best_lo = fmaxf(best_lo, wave_max_nonneg(mf) * 0.99999f);
                     const float need = best_lo;
                     if (n_live > 0) {   // old entries that can still matter, compacted in place
-                        st_fence();
+                        wave_fence();
                         const bool old = lane < n_live;
                         const int ok_ = old ? lk[lane] : 0;
                         const float oub = old ? lub[lane] : 0.f;
-                        SSums os = SSums{0, 0, 0, 0};
-                        if (old) os = SSums{lsum[4 * lane], lsum[4 * lane + 1], lsum[4 * lane + 2], lsum[4 * lane + 3]};
+                        ScSums os = ScSums{0, 0, 0, 0};
+                        if (old) os = ScSums{lsum[4 * lane], lsum[4 * lane + 1], lsum[4 * lane + 2], lsum[4 * lane + 3]};
                         const bool keep = old && oub >= need;
                         const unsigned long long km = __builtin_amdgcn_ballot_w64(keep);
                         if (__builtin_popcountll(km) != n_live) {
                             const int pos = __builtin_popcountll(km & ((1ull << lane) - 1ull));
-                            st_fence();
+                            wave_fence();
                             if (keep) { lk[pos] = ok_; lub[pos] = oub; lsum[4 * pos] = os.pr; lsum[4 * pos + 1] = os.pi; lsum[4 * pos + 2] = os.e; lsum[4 * pos + 3] = os.r; }
                             n_live = __builtin_popcountll(km);
-                            st_fence();
+                            wave_fence();
                         }
                     }
                     // new intervals (their interior lags 10 k + 1 .. 10 k + 9, as far as they lie in the window)
@@ -480,7 +418,7 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
                         const unsigned long long tm = __builtin_amdgcn_ballot_w64(take);
                         n_live += __builtin_popcountll(tm);
                         am &= ~tm;
-                        st_fence();
+                        wave_fence();
                     }
                     if (k_hi >= kE) done = true;   // every interval up to kE has been seen: the producer may stop and start the next frame
                 }
@@ -498,7 +436,7 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
             }
             // ---- close the window: what is left on the list is evaluated lag by lag (the producer is already fetching the next frame)
             const long long tcl = now();
-            if (d1 >= 0) { flush_live(); best = sc_pick(best, sc_wave_best(mybest)); }
+            if (d1 >= 0) { flush_live(); best = cand_pick(best, cand_wave_best(mybest)); }
             const long long tend = now();
             if (lane == 0) {
                 if (best.lag == INT_MAX || d1 < 0) { p.d_hat[f] = -1; if (p.f_delta) p.f_delta[f] = 0.0; if (p.metric) p.metric[f] = 0.f; }
@@ -513,7 +451,7 @@ __global__ __launch_bounds__(128, 3) void k_sc_stream(StParams p) {
                 }
             }
         }
-        st_fence();
+        wave_fence();
     }
     }
 }

@@ -16,7 +16,7 @@
 //
 // Roofline: HBM.  Algorithmic traffic is 8 B per input sample + 16 B per frame of results; the halo of W + L
 // samples per tile is re-read from L2.  ~45 f64-rate VALU ops per lag (MI355X: f64 vector = 1/2 f32 rate).
-#include "device_common.hpp"
+#include "sc_common.hpp"
 #include "kernels.hpp"
 #include <limits.h>
 #include <stdlib.h>
@@ -27,49 +27,23 @@ constexpr int SC_C = 10;            // lags per thread
 constexpr int SC_WG = 256;
 constexpr int SC_CH = SC_C * SC_WG; // lags per tile
 
-struct Sums { double pr, pi, e, r; };
-__device__ __forceinline__ Sums s_add(Sums a, Sums b) { return Sums{a.pr + b.pr, a.pi + b.pi, a.e + b.e, a.r + b.r}; }
-__device__ __forceinline__ Sums s_shfl_up(Sums a, int d) {
-    return Sums{__shfl_up(a.pr, d, 64), __shfl_up(a.pi, d, 64), __shfl_up(a.e, d, 64), __shfl_up(a.r, d, 64)};
-}
-__device__ __forceinline__ Sums s_shfl_xor(Sums a, int d) {
-    return Sums{__shfl_xor(a.pr, d, 64), __shfl_xor(a.pi, d, 64), __shfl_xor(a.e, d, 64), __shfl_xor(a.r, d, 64)};
-}
-
-struct Cand { double num, den, pr, pi; int lag; };
-// a covers lower lags than b: b wins only if strictly greater (first maximum wins)
-__device__ __forceinline__ Cand c_pick(Cand a, Cand b) { return (b.num * a.den > a.num * b.den) ? b : a; }
-__device__ __forceinline__ Cand c_shfl_down(Cand a, int d) {
-    return Cand{__shfl_down(a.num, d, 64), __shfl_down(a.den, d, 64), __shfl_down(a.pr, d, 64),
-                __shfl_down(a.pi, d, 64), __shfl_down(a.lag, d, 64)};
-}
-
-// The oracle's own sums at one lag (orc_sc_sync's sc_at): one thread, the W products in order.  Products of f32 samples are exact in
-// f64, so every step rounds as the oracle's does (fused or not): P, E, R come out bit for bit.
-__device__ __forceinline__ Sums sc_direct(const cf *raw, int lag, int L, int W) {
-    Sums y = Sums{0, 0, 0, 0};
-    for (int m = 0; m < W; ++m) {
-        const cf a = raw[lag + m], b = raw[lag + m + L];
-        const double ar = a.x, ai = a.y, br = b.x, bi = b.y;
-        y.pr += ar * br + ai * bi;
-        y.pi += ar * bi - ai * br;
-        y.e += ar * ar + ai * ai;
-        y.r += br * br + bi * bi;
-    }
+// The oracle's own sums at one lag (orc_sc_sync's sc_at): one thread, the W products in order (acc): P, E, R come out bit for bit;
+// sc_num is its num.
+__device__ __forceinline__ ScSums sc_direct(const cf *raw, int lag, int L, int W) {
+    ScSums y = ScSums{0, 0, 0, 0};
+    for (int m = 0; m < W; ++m) y = acc(y, raw[lag + m], raw[lag + m + L]);
     return y;
 }
-// ... and its num and den (no fused multiply-add: the oracle is compiled without contraction)
-__device__ __forceinline__ double sc_num(Sums y) { return __dadd_rn(__dmul_rn(y.pr, y.pr), __dmul_rn(y.pi, y.pi)); }
 
 __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int span = SC_CH + p.W + p.L;
     cf *raw = reinterpret_cast<cf *>(smem);
-    Sums *wsum = reinterpret_cast<Sums *>(smem + (size_t)span * sizeof(cf)); // [4] wave totals
-    Cand *wcand = reinterpret_cast<Cand *>(wsum + 4);                          // [4]
-    int *wmin = reinterpret_cast<int *>(wcand + 4);                            // [4]
-    double *wtot = reinterpret_cast<double *>(wmin + 4);                       // [4] wave totals of the staged energy, then [2] the peak's bounds
-    int *wnz = reinterpret_cast<int *>(wtot + 4);                              // [8] per wave: first and last staged sample that is not zero
+    ScSums *wsum = reinterpret_cast<ScSums *>(smem + (size_t)span * sizeof(cf)); // [4] wave totals
+    ScCand *wcand = reinterpret_cast<ScCand *>(wsum + 4);                          // [4]
+    int *wmin = reinterpret_cast<int *>(wcand + 4);                                // [4]
+    double *wtot = reinterpret_cast<double *>(wmin + 4);                           // [4] wave totals of the staged energy, then [2] the peak's bounds
+    int *wnz = reinterpret_cast<int *>(wtot + 4);                                  // [8] per wave: first and last staged sample that is not zero
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int L = p.L, W = p.W;
@@ -136,15 +110,8 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
     }
     if (lane == 0) { wtot[wave] = tot; wnz[wave] = nz0; wnz[4 + wave] = nz1; }
     // ---- sums at the tile's first lag: WG reduction over the W products
-    Sums x0 = Sums{0, 0, 0, 0};
-    for (int m = tid; m < W; m += SC_WG) {
-        cf a = raw[m], b = raw[m + L];
-        double ar = a.x, ai = a.y, br = b.x, bi = b.y;
-        x0.pr += ar * br + ai * bi;
-        x0.pi += ar * bi - ai * br;
-        x0.e += ar * ar + ai * ai;
-        x0.r += br * br + bi * bi;
-    }
+    ScSums x0 = ScSums{0, 0, 0, 0};
+    for (int m = tid; m < W; m += SC_WG) x0 = acc(x0, raw[m], raw[m + L]);
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) x0 = s_add(x0, s_shfl_xor(x0, s));
     if (lane == 0) wsum[wave] = x0;
@@ -158,9 +125,9 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
 
     // ---- per-thread updates for its C lags, local inclusive prefix
     const int a0 = tid * SC_C;
-    Sums pre[SC_C];
+    ScSums pre[SC_C];
     {
-        Sums run = Sums{0, 0, 0, 0};
+        ScSums run = ScSums{0, 0, 0, 0};
 #pragma unroll
         for (int j = 0; j < SC_C; ++j) {
             cf s0 = raw[a0 + j], s1 = raw[a0 + j + L], s2 = raw[a0 + j + W], s3 = raw[a0 + j + W + L];
@@ -174,18 +141,18 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
         }
     }
     // ---- exclusive scan of the thread totals over the workgroup (wave shuffles + 4 wave totals in LDS)
-    Sums inc = pre[SC_C - 1];
+    ScSums inc = pre[SC_C - 1];
 #pragma unroll
     for (int s = 1; s < 64; s <<= 1) {
-        Sums o = s_shfl_up(inc, s);
+        ScSums o = s_shfl_up(inc, s);
         if (lane >= s) inc = s_add(inc, o);
     }
     if (lane == 63) wsum[wave] = inc;
     __syncthreads();
-    Sums base = x0;
+    ScSums base = x0;
     for (int wv = 0; wv < wave; ++wv) base = s_add(base, wsum[wv]);
     {
-        Sums excl = s_shfl_up(inc, 1);
+        ScSums excl = s_shfl_up(inc, 1);
         if (lane > 0) base = s_add(base, excl);
     }
     // base = sums at lag a0
@@ -198,7 +165,7 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
         int mine = INT_MAX;
 #pragma unroll
         for (int j = SC_C - 1; j >= 0; --j) {
-            Sums x = j ? s_add(base, pre[j - 1]) : base;
+            ScSums x = j ? s_add(base, pre[j - 1]) : base;
             double num = x.pr * x.pr + x.pi * x.pi;
             const double pa = fabs(x.pr) + fabs(x.pi), el = x.e - dl, rl = x.r - dl;
             const bool pos = el > 0.0 && rl > 0.0;
@@ -206,7 +173,7 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
             const bool never = pos && num + 4.0 * dl * (pa + dl) < thr * (el * rl);
             // (rare) inside the bound: the oracle's sums decide
             if (a0 + j < n && !cross && !never && !zero_window(a0 + j)) {
-                const Sums y = sc_direct(raw, a0 + j, L, W);
+                const ScSums y = sc_direct(raw, a0 + j, L, W);
                 const double den = __dmul_rn(y.e, y.r);
                 cross = den > 0.0 && sc_num(y) >= __dmul_rn(thr, den);
             }
@@ -230,31 +197,31 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
     // ---- (B) first maximum of M over [d1, d1 + W]: on the sliding sums first.  Then every lag whose metric, with dl in its favour on
     //      every sum, still reaches that maximum's with dl against it is a contender; where there is one besides the maximum itself
     //      (rare), the contenders are summed again as the oracle sums them and the first maximum among those is the answer.
-    Cand best = Cand{-1.0, 1.0, 0.0, 0.0, -1};
+    ScCand best = ScCand{-1.0, 1.0, 0.0, 0.0, -1};
 #pragma unroll
     for (int j = 0; j < SC_C; ++j) {
         const int lag = a0 + j;
-        Sums x = j ? s_add(base, pre[j - 1]) : base;
+        ScSums x = j ? s_add(base, pre[j - 1]) : base;
         double num = x.pr * x.pr + x.pi * x.pi, den = x.e * x.r;
-        if (lag < n && lag >= d1 && lag <= d1 + W && den > 0.0 && !zero_window(lag)) best = c_pick(best, Cand{num, den, x.pr, x.pi, lag});
+        if (lag < n && lag >= d1 && lag <= d1 + W && den > 0.0 && !zero_window(lag)) best = cand_pick_ordered(best, ScCand{num, den, x.pr, x.pi, lag});
     }
-    auto wg_best = [&](Cand c) {   // first maximum over the workgroup, in every thread
+    auto wg_best = [&](ScCand c) {   // first maximum over the workgroup, in every thread
 #pragma unroll
         for (int s = 1; s < 64; s <<= 1) {
-            Cand o = c_shfl_down(c, s);
-            if (lane + s < 64) c = c_pick(c, o);
+            ScCand o = cand_shfl_down(c, s);
+            if (lane + s < 64) c = cand_pick_ordered(c, o);
         }
         __syncthreads();
         if (lane == 0) wcand[wave] = c;
         __syncthreads();
-        return c_pick(c_pick(wcand[0], wcand[1]), c_pick(wcand[2], wcand[3]));
+        return cand_pick_ordered(cand_pick_ordered(wcand[0], wcand[1]), cand_pick_ordered(wcand[2], wcand[3]));
     };
-    Cand b = wg_best(best);
+    ScCand b = wg_best(best);
     {
         // the maximum's owner publishes its bounds: num from below, den from above
 #pragma unroll
         for (int j = 0; j < SC_C; ++j) {
-            Sums x = j ? s_add(base, pre[j - 1]) : base;
+            ScSums x = j ? s_add(base, pre[j - 1]) : base;
             if (a0 + j == b.lag) {
                 wtot[0] = b.num - 4.0 * dl * (fabs(x.pr) + fabs(x.pi));
                 wtot[1] = (x.e + dl) * (x.r + dl);
@@ -266,7 +233,7 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
 #pragma unroll
         for (int j = 0; j < SC_C; ++j) {
             const int lag = a0 + j;
-            Sums x = j ? s_add(base, pre[j - 1]) : base;
+            ScSums x = j ? s_add(base, pre[j - 1]) : base;
             const double num = x.pr * x.pr + x.pi * x.pi, el = x.e - dl, rl = x.r - dl;
             const bool pos = el > 0.0 && rl > 0.0;
             const bool out = pos && (num + 4.0 * dl * (fabs(x.pr) + fabs(x.pi) + dl)) * ref_dhi < ref_nlo * (el * rl);
@@ -274,13 +241,13 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
         }
         const unsigned others = b.lag >= a0 && b.lag < a0 + SC_C ? contend & ~(1u << (b.lag - a0)) : contend;
         if (__syncthreads_or(others != 0u)) {
-            Cand exact = Cand{-1.0, 1.0, 0.0, 0.0, -1};
+            ScCand exact = ScCand{-1.0, 1.0, 0.0, 0.0, -1};
 #pragma unroll
             for (int j = 0; j < SC_C; ++j)
                 if (contend >> j & 1u) {
-                    const Sums y = sc_direct(raw, a0 + j, L, W);
+                    const ScSums y = sc_direct(raw, a0 + j, L, W);
                     const double den = __dmul_rn(y.e, y.r);
-                    if (den > 0.0) exact = c_pick(exact, Cand{sc_num(y), den, y.pr, y.pi, a0 + j});
+                    if (den > 0.0) exact = cand_pick_ordered(exact, ScCand{sc_num(y), den, y.pr, y.pi, a0 + j});
                 }
             b = wg_best(exact);
         }
@@ -298,7 +265,7 @@ __global__ __launch_bounds__(SC_WG) void k_sc_tile(ScParams p) {
 
 size_t sc_lds_bytes(const ScParams &p) {
     // samples, wsum[4], wcand[4], wmin[4], wtot[4], wnz[8]
-    return (size_t)(SC_CH + p.W + p.L) * sizeof(float2) + 4 * sizeof(Sums) + 4 * sizeof(Cand) + 4 * sizeof(int) + 4 * sizeof(double) + 8 * sizeof(int);
+    return (size_t)(SC_CH + p.W + p.L) * sizeof(float2) + 4 * sizeof(ScSums) + 4 * sizeof(ScCand) + 4 * sizeof(int) + 4 * sizeof(double) + 8 * sizeof(int);
 }
 
 hipError_t run_sc(const ScParams &p, hipStream_t st) {
@@ -336,74 +303,6 @@ constexpr float SC_EPS = 1e-3f;         // relative guard band of the f32 filter
 constexpr float SC_UNSAFE_RATIO = 20.f; // prefix energy / window energy above which a lag is never trusted
 constexpr float SC_PREFIX_ERR = 1.6e-5f; // bound on |f32 window sum - exact| / prefix magnitude when PROVING a lag below the threshold (the scans and slides stay below 4e-6; x 4 for margin)
 constexpr int SC_MAXCAND = 4;
-
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ double dpp_d(double x) {
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xF, true); // out-of-range / masked lanes read 0
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-// inclusive prefix sum over the 64 lanes of a wavefront (lane 63 ends up with the wave total)
-__device__ __forceinline__ double wave_scan(double x) {
-    x += dpp_d<0x111, 0xF>(x); // row_shr:1
-    x += dpp_d<0x112, 0xF>(x); // row_shr:2
-    x += dpp_d<0x114, 0xF>(x); // row_shr:4
-    x += dpp_d<0x118, 0xF>(x); // row_shr:8
-    x += dpp_d<0x142, 0xA>(x); // row_bcast:15 into rows 1 and 3
-    x += dpp_d<0x143, 0xC>(x); // row_bcast:31 into rows 2 and 3
-    return x;
-}
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ float dpp_s(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, ROW_MASK, 0xF, true));
-}
-__device__ __forceinline__ float wave_scan_f(float x) {
-    x += dpp_s<0x111, 0xF>(x);
-    x += dpp_s<0x112, 0xF>(x);
-    x += dpp_s<0x114, 0xF>(x);
-    x += dpp_s<0x118, 0xF>(x);
-    x += dpp_s<0x142, 0xA>(x);
-    x += dpp_s<0x143, 0xC>(x);
-    return x;
-}
-__device__ __forceinline__ float readlane_f(float x, int l) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l));
-}
-__device__ __forceinline__ double readlane_d(double x, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
-}
-
-// Totals of FOUR f64 values over the wavefront, every lane receiving all four -- a transpose-reduce instead of four scans: the first
-// two steps trade values between lane pairs (lane ^ 1: even lanes keep a and c, odd lanes b and d; lane ^ 2: one value per lane,
-// quantity = lane & 3), two row rotations add the four lanes of a row that hold the same quantity, and gfx950's
-// v_permlane16_swap / v_permlane32_swap add the rows.  Eight 64-bit additions and 14 lane movements instead of 24 and 48.
-template <int CTRL> __device__ __forceinline__ double dpp_q(double x) { // quad / row permutation of a double, every lane valid
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false);
-    hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double rows_sum16(double x) { // [r0, r1, r2, r3] -> [r0 + r1, r0 + r1, r2 + r3, r2 + r3], lane for lane
-    const auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(x), __double2loint(x), false, false);
-    const auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(x), __double2hiint(x), false, false);
-    return __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
-}
-__device__ __forceinline__ double halves_sum32(double x) { // [lower, upper] -> lower + upper in both halves, lane for lane
-    const auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(x), __double2loint(x), false, false);
-    const auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(x), __double2hiint(x), false, false);
-    return __hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1]);
-}
-__device__ __forceinline__ void wave_sum4(double &a, double &b, double &c, double &d, int lane) {
-    const bool o1 = (lane & 1) != 0, o2 = (lane & 2) != 0;
-    double k0 = o1 ? b : a, k1 = o1 ? d : c;            // kept; the partner receives the other two
-    k0 += dpp_q<0xB1>(o1 ? a : b);                       // quad_perm [1,0,3,2]: lane ^ 1
-    k1 += dpp_q<0xB1>(o1 ? c : d);
-    double k = o2 ? k1 : k0;
-    k += dpp_q<0x4E>(o2 ? k0 : k1);                      // quad_perm [2,3,0,1]: lane ^ 2 -> quantity (lane & 3) summed over the quad
-    k += dpp_q<0x124>(k);                                // row_ror:4
-    k += dpp_q<0x128>(k);                                // row_ror:8 -> ... over the row
-    k = halves_sum32(rows_sum16(k));                     // ... over the wavefront
-    a = readlane_d(k, 0); b = readlane_d(k, 1); c = readlane_d(k, 2); d = readlane_d(k, 3);
-}
 
 struct ScFastParams {
     const float2 *in;
@@ -448,23 +347,12 @@ struct ScFastParams {
 // tools/lab/sc_sections.py): per frame the DMA wait, phase 1, bases, coarse and fine sections take about 1.0 / 2.0 / 0.7 /
 // 1.3 / 6.0 thousand s_memtime ticks; the fine wavefront is the critical path, which is why its LDS reads are issued
 // up front (one round trip per stage) and its reductions never touch LDS.
-//
-// maximum of non-negative values over the wavefront, DPP only (no LDS round trips): a max-scan leaves it in lane 63
-__device__ __forceinline__ float wave_max_nonneg(float x) {
-    x = fmaxf(x, dpp_s<0x111, 0xF>(x));
-    x = fmaxf(x, dpp_s<0x112, 0xF>(x));
-    x = fmaxf(x, dpp_s<0x114, 0xF>(x));
-    x = fmaxf(x, dpp_s<0x118, 0xF>(x));
-    x = fmaxf(x, dpp_s<0x142, 0xA>(x));
-    x = fmaxf(x, dpp_s<0x143, 0xC>(x));
-    return readlane_f(x, 63);
-}
 
 // Exact decision among <= 4 candidate lags of one frame (one wavefront; samples in LDS): f64 sums over the window,
 // first maximum wins.  All of a candidate's LDS reads are issued together and the four sums are reduced with DPP
 // scans, so a candidate costs one LDS round trip.  The result is wave-uniform (lag == INT_MAX: none).
-__device__ __forceinline__ Cand sc_exact_pick(const cf *raw, int c0, int c1, int c2, int c3, int cnt, int L, int W, int lane) {
-    Cand best = Cand{-1.0, 1.0, 0.0, 0.0, INT_MAX};
+__device__ __forceinline__ ScCand sc_exact_pick(const cf *raw, int c0, int c1, int c2, int c3, int cnt, int L, int W, int lane) {
+    ScCand best = ScCand{-1.0, 1.0, 0.0, 0.0, INT_MAX};
     for (int i = 0; i < cnt; ++i) {
         const int d = i == 0 ? c0 : i == 1 ? c1 : i == 2 ? c2 : c3;
         cf sa[4], sb[4];
@@ -473,29 +361,22 @@ __device__ __forceinline__ Cand sc_exact_pick(const cf *raw, int c0, int c1, int
             const int m = lane + 64 * t < W ? lane + 64 * t : 0;
             sa[t] = raw[d + m]; sb[t] = raw[d + m + L];
         }
-        double xr = 0, xi = 0, xe = 0, xq = 0;
+        ScSums x = ScSums{0, 0, 0, 0};
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const bool v = lane + 64 * t < W;
             const double ar = v ? sa[t].x : 0.f, ai = v ? sa[t].y : 0.f, br = v ? sb[t].x : 0.f, bi = v ? sb[t].y : 0.f;
-            xr += ar * br + ai * bi;
-            xi += ar * bi - ai * br;
-            xe += ar * ar + ai * ai;
-            xq += br * br + bi * bi;
+            x.pr += ar * br + ai * bi;
+            x.pi += ar * bi - ai * br;
+            x.e += ar * ar + ai * ai;
+            x.r += br * br + bi * bi;
         }
-        for (int m = lane + 256; m < W; m += 64) {
-            const cf a = raw[d + m], b = raw[d + m + L];
-            const double ar = a.x, ai = a.y, br = b.x, bi = b.y;
-            xr += ar * br + ai * bi;
-            xi += ar * bi - ai * br;
-            xe += ar * ar + ai * ai;
-            xq += br * br + bi * bi;
-        }
-        wave_sum4(xr, xi, xe, xq, lane);
-        const double xn = xr * xr + xi * xi, xd = xe * xq;
-        if (xd > 0.0) { // first maximum wins: strictly greater replaces, ties go to the lower lag
+        for (int m = lane + 256; m < W; m += 64) x = acc(x, raw[d + m], raw[d + m + L]);
+        wave_sum4(x.pr, x.pi, x.e, x.r, lane);
+        const double xn = x.pr * x.pr + x.pi * x.pi, xd = x.e * x.r;
+        if (xd > 0.0) { // cand_pick(best, {xn, xd, x.pr, x.pi, d}) written out: as a call it is a select, and k_sc_cf's code moves
             const double lhs = xn * best.den, rhs = best.num * xd;
-            if (lhs > rhs || (lhs == rhs && d < best.lag)) best = Cand{xn, xd, xr, xi, d};
+            if (lhs > rhs || (lhs == rhs && d < best.lag)) best = ScCand{xn, xd, x.pr, x.pi, d};
         }
     }
     return best;
@@ -580,7 +461,7 @@ __global__ __launch_bounds__(NCH / CPT, OCC) void k_sc_cf(ScFastParams p) {
     for (; item < n_items; item += fstep, ++it) {
         const long long f = frame_of(item);
         const long long t0 = (dbg >= 10) ? (long long)__builtin_amdgcn_s_memtime() : 0;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's pieces of the CURRENT frame have landed
+        wait_vm<0>(); // this wave's pieces of the CURRENT frame have landed
         lds_barrier();                                   // B0: ... and everyone else's
         const long long t1 = (dbg >= 10) ? (long long)__builtin_amdgcn_s_memtime() : 0;
         const bool more = item + fstep < n_items;
@@ -675,7 +556,7 @@ __global__ __launch_bounds__(NCH / CPT, OCC) void k_sc_cf(ScFastParams p) {
             const float sgn = hh ? -1.f : 1.f;
             long long u0 = (dbg >= 15) ? (long long)__builtin_amdgcn_s_memtime() : 0, u1 = 0, u2 = 0;
             int res_d = -1;          // wave-uniform outcome: lag >= 0, -1 no packet, -2 slow list, -3 debug exit, -4 redo list
-            Cand best = Cand{0.0, 1.0, 1.0, 0.0, INT_MAX};
+            ScCand best = ScCand{0.0, 1.0, 1.0, 0.0, INT_MAX};
             for (;;) {
                 const int c = gs + (lane >> 1), m0 = c * C;
                 const bool lv = m0 + 5 * hh < n; // implies c + hh + cW + cL <= NCH
