@@ -72,6 +72,17 @@ pub const OFDM_SOFT_LLR_SCALE: f32 = 32.0;
 // cp_len taps -- opt-in, receive side only; parity unpinned by the reference, tests/chest_ref.py is the definition (include/ofdm_hip.h)
 pub const OFDM_CHEST_LS: i32 = 0;
 pub const OFDM_CHEST_WLS: i32 = 1;
+// ofdm_params.cfo_mode.  OFF, SIGNED (default) and ABS work with the Schmidl-Cox phase alone, which is defined modulo 2 pi / S
+// rad/sample: an acquisition range of +-pi / S, +-0.4 sub-carrier spacings.  WIDE resolves the whole multiples of 2 pi / S from the
+// training blocks (ofdm_cfo_wide_batch with span = OFDM_CFO_WIDE_SPAN behind the Schmidl-Cox search of every decode entry point):
+// +-6.8 sub-carrier spacings.  OFDM_SYNC_SCHMIDL_COX only; opt-in, receive side only; parity unpinned by the reference,
+// tests/cfo_wide_ref.py is the definition (include/ofdm_hip.h)
+pub const OFDM_CFO_OFF: i32 = 0;
+pub const OFDM_CFO_SIGNED: i32 = 1;
+pub const OFDM_CFO_ABS: i32 = 2;
+pub const OFDM_CFO_WIDE: i32 = 3;
+pub const OFDM_CFO_WIDE_SPAN: i32 = 8;
+pub const OFDM_CFO_WIDE_MAX_SPAN: i32 = 32;
 // ofdm_rx_quality_batch: indices into a frame's row of OFDM_QUALITY_FIELDS floats (noise variance, gain, linear SNR, LLR unit, linear
 // EVM^2, counted points); parity unpinned by the reference, tests/quality_ref.py is the definition (include/ofdm_hip.h)
 pub const OFDM_Q_VALID: usize = 0;
@@ -196,6 +207,10 @@ extern "C" {
                                  first_symbol: i32, syms_per_frame: i32, n_points_dev: *const i32, offset_dev: *const i32,
                                  f_delta_dev: *const f64, hk_dev: *const ofdm_fc32, hk_stride: i64, status_dev: *const i32,
                                  quality_dev: *mut f32) -> c_int;
+    // in/out f_delta_dev: f0 -> f0 + 2 pi m / S; status_dev, m_dev and metric_dev (2 floats per frame) may be null; 1 <= span <= 32
+    pub fn ofdm_cfo_wide_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,
+                               offset_dev: *const i32, status_dev: *const i32, span: i32, f_delta_dev: *mut f64, m_dev: *mut i32,
+                               metric_dev: *mut f32) -> c_int;
     pub fn ofdm_llr_combine_batch(ctx: *mut ofdm_ctx, llr_dev: *const i8, n_frames: i64, n_branches: i32, llr_stride: i64, n_llr: i64,
                                   quality_dev: *const f32, status_dev: *const i32, n_live_dev: *const i32, out_dev: *mut i8,
                                   out_stride: i64, weight_dev: *mut i32) -> c_int;

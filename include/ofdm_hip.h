@@ -99,7 +99,15 @@ enum { OFDM_CONV_RATE_1_2 = 0, OFDM_CONV_RATE_2_3 = 1, OFDM_CONV_RATE_3_4 = 2 };
 /* llr_scale of the OFDM_ECC_HAMMING74_SOFT and OFDM_ECC_CONV_K7 decode chains (chosen from the measured BER curves);
  * the OFDM_ECC_CONV_K7F_* chains inherit it from OFDM_ECC_CONV_K7 */
 #define OFDM_SOFT_LLR_SCALE 32.0f
-enum { OFDM_CFO_OFF = 0, OFDM_CFO_SIGNED = 1, OFDM_CFO_ABS = 2 }; /* ABS = reference's abs() (receiver.rs:239) */
+/* cfo_mode.  OFF, SIGNED and ABS work with the Schmidl-Cox phase alone, which is defined modulo 2 pi / S rad/sample, S = n_fft + cp_len:
+ * with cp_len = n_fft / 4 an acquisition range of +-pi / S, +-0.4 sub-carrier spacings.  WIDE resolves the whole multiples of 2 pi / S
+ * from the training blocks (see "wide CFO acquisition" below): +-(OFDM_CFO_WIDE_SPAN + 0.5) 2 pi / S, +-6.8 sub-carrier spacings.
+ * OFDM_SYNC_SCHMIDL_COX only; opt-in, receive side only, nothing on the wire changes.  4 and above are rejected. */
+enum { OFDM_CFO_OFF = 0, OFDM_CFO_SIGNED = 1, OFDM_CFO_ABS = 2 /* ABS = reference's abs() (receiver.rs:239) */, OFDM_CFO_WIDE = 3 };
+/* hypotheses m in [-SPAN, SPAN] the OFDM_CFO_WIDE decode chains test: a definition, not a tuned number */
+#define OFDM_CFO_WIDE_SPAN 8
+/* the largest span ofdm_cfo_wide_batch takes (m and m + S are the same hypothesis: a span near S / 2 would be meaningless) */
+#define OFDM_CFO_WIDE_MAX_SPAN 32
 /* timing / CFO detector of decode: the north star's Schmidl-Cox (default), or the reference's own pair -- cross-correlation
  * with the locking signal (xcorr_fft, src/signals/mod.rs:186-217; offset = idx_max - N = lag - 1, src/receiver.rs:20-25) and
  * frequency_correction on preamble repetitions 3 and 4 (src/receiver.rs:39, 231-240; always |.|) */
@@ -243,6 +251,8 @@ int ofdm_rs255_decode(const uint8_t *code, int64_t n_code, uint8_t *out, int32_t
  * Frame f occupies in_dev[f*frame_stride .. +frame_len).  Lags d in [0, n_lags) (n_lags <= 0: every lag with
  * d + W + L <= frame_len).  d_hat = first max of M over [d1, d1+W], d1 = first lag with M >= threshold;
  * d_hat[f] = -1 if none.  f_delta[f] = arg P(d_hat)/L (signed, rad/sample), metric[f] = M(d_hat).
+ * That estimate is defined modulo 2 pi / L only: f_delta lies in [-pi / L, pi / L], +-0.4 sub-carrier spacings with cp_len = n_fft / 4,
+ * and an offset beyond it comes back wrapped into that range with the same metric ("wide CFO acquisition" below resolves it).
  * n_lags bounds the peak window too: it is [d1, min(d1 + W, n_lags - 1)], so a bounded search returns an earlier lag than the
  * full one whenever the true peak lies beyond n_lags - 1 (same rule in the oracle; tests: test_bounded_search_clips_the_peak_window).
  * Any n_fft is served: L = 80 by the one-tile f32-filter / f64-decision kernel, L >= 160 by streaming chunk sums and a bounded
@@ -389,6 +399,40 @@ int ofdm_rx_quality_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_fram
                           int32_t first_symbol, int32_t syms_per_frame, const int32_t *n_points_dev,
                           const int32_t *offset_dev, const double *f_delta_dev, const ofdm_fc32 *hk_dev, int64_t hk_stride,
                           const int32_t *status_dev, float *quality_dev);
+
+/* ------------------------------------------------------------------ wide CFO acquisition (north-star extension)
+ * The Schmidl-Cox phase gives the carrier offset modulo 2 pi / S rad/sample, S = n_fft + cp_len: an acquisition range of +-pi / S,
+ * +-0.4 sub-carrier spacings.  A capture whose offset is f0 + 2 pi m / S with m != 0 is detected with a perfect timing metric, derotated
+ * by f0 alone and demodulated into garbage.  The frame already carries what resolves m: the five training blocks are identical and one
+ * symbol long, so a hypothesis m rotates every block alike, and for the right m their sum, matched against the known training table,
+ * puts its energy into the cp_len delays a channel can occupy; for a wrong m the energy spreads over all n_fft delays.
+ * Parity unpinned by the reference (its frequency_correction has the same ambiguity and drops the sign as well): tests/cfo_wide_ref.py
+ * is the definition.  Per frame f, with o = offset_dev[f], f0 = f_delta_dev[f] on entry, N = n_fft, cp = cp_len, samples at or beyond
+ * frame_len reading as zero and the derotation of ofdm_estimate_channel_batch (sample id counted from o):
+ *   tested     iff status_dev[f] == 0 (or no status_dev), o >= 0 and o + 10 S <= frame_len (all five training blocks inside the capture);
+ *              a frame that is not tested gets m = 0 and both metrics 0, and its f_delta is untouched
+ *   ybar[n]    sum_{b < 5} x[o + (5 + b) S + cp + n] e^{-i f0 ((5 + b) S + cp + n)}, n < N: the SUM ofdm_estimate_channel_batch forms
+ *   z_m[n]     ybar[n] e^{-2 pi i m (cp + n) / S}
+ *   g_m        IFFT_N(conj(t) o FFT_N(z_m)), t = the context's training table.  Scaling: the forward transform unnormalised, the inverse
+ *              one carrying the 1 / N, ybar the sum (not the mean) of the blocks
+ *   G_m        sum of |g_m[n]|^2 over the delays n in [-pre, L_h - pre) mod N, L_h = cp_len, pre = cp_len / 4: ofdm_chest_window's
+ *   decision   the hypotheses are visited in the order 0, -1, +1, -2, +2, ..., -span, +span; one is kept only if its G is strictly
+ *              greater than the best so far.  m = the kept one, metric[0] = G_m, metric[1] = the largest G among the others
+ *   result     f_delta_dev[f] = f0 + 2 pi m / S, formed in f64; for m = 0 the value is f0 bit for bit
+ * A non-finite sample in a training block gives m = 0 and non-finite metrics, in that frame only.  Arithmetic on the device is f32 (the
+ * phases are reduced in f64); measured over the oracle's frames the winner's G is at least twice the runner-up's wherever Schmidl-Cox
+ * detects the frame at all, so the f32 decision is the f64 one.
+ * cfo_mode = OFDM_CFO_WIDE: every decode entry point (ofdm_rx_decode_batch, _host, _long, _long_host, _combine_batch) runs the stage
+ * with span = OFDM_CFO_WIDE_SPAN directly behind the Schmidl-Cox search, for every ecc and chest_mode; everything behind it derotates
+ * with the total offset, and the f_delta it returns is the total offset: +-(OFDM_CFO_WIDE_SPAN + 0.5) 2 pi / S, +-6.8 sub-carrier
+ * spacings instead of +-0.4.  ofdm_last_dispatch shows k_cfo_wide behind k_rx_prepare. */
+/* The stage on its own, on any context whatever its cfo_mode.  1 <= span <= OFDM_CFO_WIDE_MAX_SPAN.  status_dev, m_dev and metric_dev
+ * (2 floats per frame) are optional.  OFDM_ERR_INVALID: a NULL context, NULL in_dev, offset_dev or f_delta_dev (with n_frames > 0), a
+ * negative size, frame_len <= 0 or a span outside its range.  n_frames == 0: OFDM_OK.  One launch (k_cfo_wide), no workspace. */
+int ofdm_cfo_wide_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                        const int32_t *offset_dev, const int32_t *status_dev /* optional */, int32_t span,
+                        double *f_delta_dev /* in: f0, out: f0 + 2 pi m / S */, int32_t *m_dev /* optional */,
+                        float *metric_dev /* optional, 2 per frame */);
 
 /* ------------------------------------------------------------------ convolutional code (north-star extension; DESIGN.md 3, EXT-2 convolutional code)
  * K = 7, rate 1/2, generators 133 / 171 octal; the definition shared by the kernels and tests/conv_ref.py.
@@ -645,6 +689,8 @@ int ofdm_tx_encode_batch(ofdm_ctx *ctx, const uint8_t *payload_dev, int64_t n_fr
  * OFDM_FRAME_HEADER.  With avail = max(max_symbols * bytes_per_symbol - 16 - 18, 0), out_stride >= floor(T' / 8) for the largest T'
  * with kept(T', rate) <= 8 avail (at most 3 avail / 4); a T' above 2^20: OFDM_ERR_UNSUPPORTED.
  * chest_mode = OFDM_CHEST_WLS (likewise in every wrapper, every ecc): "channel estimate" above is H' of "channel-estimate denoising".
+ * cfo_mode = OFDM_CFO_WIDE (likewise in every wrapper, every ecc): "CFO derotation" above uses f_delta + 2 pi m / S of "wide CFO
+ * acquisition", and f_delta_dev receives that total offset.
  * ecc = OFDM_ECC_LDPC648 (likewise in every wrapper): the frame rule of "LDPC(648,324)" above; status may become OFDM_FRAME_HEADER or
  * OFDM_FRAME_UNCORRECTABLE; out_stride >= max(40 floor(body_max / 80) - 8, 0).
  * ecc = OFDM_ECC_FCS + mode (likewise in every wrapper): mode's rule above, then the check of "frame check sequence": out_len = the

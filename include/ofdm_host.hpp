@@ -152,6 +152,25 @@ class Context {
         if (q.points > 0.f) q.evm_db = 10.0f * std::log10(row[OFDM_Q_EVM2]);
         return q;
     }
+    // wide CFO acquisition (EXT-8, include/ofdm_hip.h; cfo_mode = OFDM_CFO_WIDE applies it inside decode with span = OFDM_CFO_WIDE_SPAN; this
+    // is the bare stage): the whole multiples of 2 pi / S that the Schmidl-Cox estimate f_delta (+-pi / S, +-0.4 sub-carrier spacings) cannot
+    // see, from the five training blocks of the frame that starts at sample `offset` of the capture
+    struct CfoWide { int32_t m = 0; double f_delta = 0.0; float metric[2] = {0.f, 0.f}; };
+    CfoWide cfo_wide(const ofdm_fc32 *fc, int64_t n, int32_t offset, double f_delta, int32_t span = OFDM_CFO_WIDE_SPAN) {
+        CfoWide r;
+        r.f_delta = f_delta;
+        DevBuf din(ctx_, (size_t)n * sizeof(ofdm_fc32)), doff(ctx_, sizeof(int32_t)), dfd(ctx_, sizeof(double)), dm(ctx_, sizeof(int32_t)),
+            dg(ctx_, 2 * sizeof(float));
+        check(ofdm_memcpy_h2d(ctx_, din.p, fc, (size_t)n * sizeof(ofdm_fc32)), "h2d");
+        check(ofdm_memcpy_h2d(ctx_, doff.p, &offset, sizeof(int32_t)), "h2d");
+        check(ofdm_memcpy_h2d(ctx_, dfd.p, &f_delta, sizeof(double)), "h2d");
+        check(ofdm_cfo_wide_batch(ctx_, (const ofdm_fc32 *)din.p, 1, n, n, (const int32_t *)doff.p, nullptr, span, (double *)dfd.p, (int32_t *)dm.p,
+                                  (float *)dg.p), "ofdm_cfo_wide_batch");
+        check(ofdm_memcpy_d2h(ctx_, &r.m, dm.p, sizeof(int32_t)), "d2h");
+        check(ofdm_memcpy_d2h(ctx_, &r.f_delta, dfd.p, sizeof(double)), "d2h");
+        check(ofdm_memcpy_d2h(ctx_, r.metric, dg.p, sizeof(r.metric)), "d2h");
+        return r;
+    }
     // batches on host memory: H2D / kernels / D2H pipelined inside the library (ofdm_rx_decode_host, ofdm_tx_encode_host)
     struct BatchResult { std::vector<uint8_t> bytes; int64_t row = 0; std::vector<int32_t> len, status, offset; std::vector<double> f_delta; };
     BatchResult decode_batch(const ofdm_fc32 *frames, int64_t n_frames, int64_t frame_stride, int64_t frame_len, int32_t max_symbols,

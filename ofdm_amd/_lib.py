@@ -99,6 +99,7 @@ SIGNATURES = {
     "ofdm_fcs_check_batch": (C.c_int, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp]),
     "ofdm_rx_llr_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, i64, C.c_float, vp, i64]),
     "ofdm_rx_quality_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, vp, i64, vp, vp]),
+    "ofdm_cfo_wide_batch": (C.c_int, [vp, vp, i64, i64, i64, vp, vp, i32, vp, vp, vp]),
     "ofdm_llr_combine_batch": (C.c_int, [vp, vp, i64, i32, i64, i64, vp, vp, vp, vp, i64, vp]),
     "ofdm_rx_decode_combine_batch": (C.c_int, [vp, vp, i64, i32, i64, i64, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ofdm_sc_correlate_batch": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp, vp]),

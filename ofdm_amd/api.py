@@ -40,6 +40,11 @@ FCS_OVERHEAD = 8  # OFDM_FCS_OVERHEAD: the envelope's length word and check word
 CONV_RATE_1_2, CONV_RATE_2_3, CONV_RATE_3_4 = 0, 1, 2
 SOFT_LLR_SCALE = 32.0  # OFDM_SOFT_LLR_SCALE (include/ofdm_hip.h): the llr_scale of the soft decode chain
 CFO_OFF, CFO_SIGNED, CFO_ABS = 0, 1, 2
+# EXT-8 (tests/cfo_wide_ref.py is the definition): the Schmidl-Cox phase alone acquires +-pi / S rad/sample, +-0.4 sub-carrier spacings;
+# CFO_WIDE resolves the whole multiples of 2 pi / S from the training blocks: +-6.8 spacings with the chain's span of 8
+CFO_WIDE = 3
+CFO_WIDE_SPAN = 8       # OFDM_CFO_WIDE_SPAN: hypotheses m in [-8, 8] in the decode chains
+CFO_WIDE_MAX_SPAN = 32  # OFDM_CFO_WIDE_MAX_SPAN: the largest span Context.cfo_wide takes
 FRAME_OK, FRAME_SHORT, FRAME_NOSYNC, FRAME_BADTIMING, FRAME_HEADER = 0, -1, -2, -3, -4
 FRAME_UNCORRECTABLE = -5  # ECC_RS255*: an outer RS block with more than 16 byte errors (the reference returns None); ECC_LDPC648: a code word did not converge
 FRAME_FCS = -6  # ECC_FCS + mode: the delivered row is not a valid envelope (length word or CRC-32 wrong)
@@ -724,6 +729,26 @@ class Context:
                                                 syms_per_frame, _dev(n_points), _dev(offset), _dev(f_delta), _dev(hk), hk_stride,
                                                 _dev(status), _dev(out)), "rx_quality")
         return out
+
+    def cfo_wide(self, frames: torch.Tensor, offset: torch.Tensor, f_delta: torch.Tensor, span: int = CFO_WIDE_SPAN,
+                 status: Optional[torch.Tensor] = None, frame_len: Optional[int] = None) -> dict:
+        """ofdm_cfo_wide_batch: the whole multiples of 2 pi / S the Schmidl-Cox estimate f_delta cannot see, from the five training blocks
+        at offset -> {m: int32 [n_frames], f_delta: float64 [n_frames] = f_delta + 2 pi m / S, metric: float32 [n_frames, 2] = the window
+        energy of m and the largest among the other hypotheses}.  The f_delta passed in is left as it is.  status (optional): frames with
+        status != 0 are not read (m = 0, metrics 0, f_delta unchanged).  Works whatever the context's cfo_mode.  Definition:
+        include/ofdm_hip.h, tests/cfo_wide_ref.py."""
+        frames = self._cx(frames)
+        f2 = frames.view(-1, frames.shape[-1])
+        n, stride = f2.shape
+        for name, t, dt in (("offset", offset, torch.int32), ("f_delta", f_delta, torch.float64), ("status", status, torch.int32)):
+            if (t is None and name != "status") or (t is not None and (t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.numel() != n)):
+                raise OfdmError(f"cfo_wide: {name} must be a contiguous {dt} tensor of n_frames elements on the context's device")
+        fd = f_delta.clone()
+        m = self.empty((n,), torch.int32)
+        metric = self.empty((n, 2), torch.float32)
+        self._ck(self.lib.ofdm_cfo_wide_batch(self.h, _dev(f2), n, stride, stride if frame_len is None else frame_len, _dev(offset),
+                                              _dev(status), int(span), _dev(fd), _dev(m), _dev(metric)), "cfo_wide")
+        return {"m": m, "f_delta": fd, "metric": metric}
 
     def link_quality(self, frames: torch.Tensor, decoded: dict, payload_bytes: Optional[int] = None, n_points=None) -> dict:
         """What the link was like for the frames decode_batch just decoded: `decoded` is the dict it returned for `frames`.  Runs

@@ -235,6 +235,29 @@ struct CombineParams {
 };
 hipError_t run_llr_combine(const CombineParams &p, int num_cu, hipStream_t st);
 
+// ---- EXT-8 wide CFO acquisition (ofdm_cfo_wide_batch and the OFDM_CFO_WIDE receive mode; kernels_cfowide.hip, definition:
+// tests/cfo_wide_ref.py)
+// k_cfo_wide: per frame the hypothesis m in [-span, span] whose training blocks, derotated by f_delta[f] + 2 pi m / S and matched against
+// the training table, put the most energy into the channel window; f_delta[f] becomes that sum (untouched for m = 0 and for a frame
+// that is not tested: status[f] != 0, or the five training blocks not wholly inside the capture).
+constexpr int kCfoWideMaxSpan = 32;
+struct CfoWideParams {
+    const Tuning *tune = nullptr;
+    Trace *trace = nullptr;
+    const float2 *in = nullptr;
+    long long n_frames = 0, frame_stride = 0, frame_len = 0;
+    int sym_len = 0;                     // S = N + CP
+    int span = 0;                        // 1 .. kCfoWideMaxSpan
+    const int32_t *offset = nullptr;
+    const int32_t *status = nullptr;     // optional
+    double *f_delta = nullptr;           // in: f0, out: f0 + 2 pi m / S
+    const float2 *tw = nullptr;
+    const float2 *trn = nullptr;         // the training table t_k
+    int32_t *m = nullptr;                // optional
+    float *metric = nullptr;             // optional: [n_frames][2] = G of m, the largest G among the other hypotheses
+};
+hipError_t run_cfo_wide(int n, const CfoWideParams &p, hipStream_t st, int num_cu);
+
 // ---- Schmidl-Cox (kernels_sync.hip)
 struct ScParams {
     const Tuning *tune = nullptr;

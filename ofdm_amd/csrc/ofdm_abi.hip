@@ -167,6 +167,19 @@ static int chest_tables(ofdm_ctx *c) {
     return OFDM_OK;
 }
 
+// ---- EXT-8 wide CFO acquisition: the training table t_k on the device (d_inv_trn holds 1 / t_k, k_cfo_wide matches against conj(t_k))
+static int cfo_wide_table(ofdm_ctx *c) {
+    if (c->d_trn) return OFDM_OK;
+    const int N = c->prm.n_fft;
+    std::vector<float2> t(N);
+    for (int k = 0; k < N; k++) t[k] = make_float2((float)c->training[2 * k], (float)c->training[2 * k + 1]);
+    float2 *dt = nullptr;
+    if (hipMalloc(&dt, sizeof(float2) * N) != hipSuccess) return OFDM_ERR_NOMEM;
+    if (hipMemcpy(dt, t.data(), sizeof(float2) * N, hipMemcpyHostToDevice) != hipSuccess) { hipFree(dt); return OFDM_ERR_HIP; }
+    c->d_trn = dt;
+    return OFDM_OK;
+}
+
 // rows of N bins `in` -> `out` (in == out allowed), per frame chunk: weight -> inverse FFT -> k_chest_solve -> forward FFT.  The
 // one workspace (the solve's zeroed rows) holds a chunk, at most kChestChunkBytes whatever n_frames is.
 static const int64_t kChestChunkBytes = 64ll << 20;
@@ -366,6 +379,7 @@ int ofdm_destroy(ofdm_ctx *c) {
     if (c->d_header) hipFree(c->d_header);
     if (c->d_chest_w) hipFree(c->d_chest_w);
     if (c->d_chest_mt) hipFree(c->d_chest_mt);
+    if (c->d_trn) hipFree(c->d_trn);
     if (c->d_stats) hipFree(c->d_stats);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
@@ -389,9 +403,10 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
     if (!mode_plan(p->ecc, &mode)) return OFDM_ERR_INVALID;
     if (p->sync_window_reps < 1 || p->sync_window_reps > 3) return OFDM_ERR_INVALID;
     if (p->sync_backoff < 0 || p->sync_backoff > p->cp_len) return OFDM_ERR_INVALID;
-    if (p->cfo_mode < OFDM_CFO_OFF || p->cfo_mode > OFDM_CFO_ABS) return OFDM_ERR_INVALID;
+    if (p->cfo_mode < OFDM_CFO_OFF || p->cfo_mode > OFDM_CFO_WIDE) return OFDM_ERR_INVALID;
     if (!(p->sync_threshold > 0.f && p->sync_threshold <= 1.f)) return OFDM_ERR_INVALID;
     if (p->sync_mode != OFDM_SYNC_SCHMIDL_COX && p->sync_mode != OFDM_SYNC_REFERENCE) return OFDM_ERR_INVALID;
+    if (p->cfo_mode == OFDM_CFO_WIDE && p->sync_mode != OFDM_SYNC_SCHMIDL_COX) return OFDM_ERR_INVALID; // the hypotheses refine the Schmidl-Cox phase
     if (p->rx_path != OFDM_RX_AUTO && p->rx_path != OFDM_RX_STAGED) return OFDM_ERR_INVALID; // (2 was the one-pass kernel of rounds 2-4: removed)
     if (p->chest_mode != OFDM_CHEST_LS && p->chest_mode != OFDM_CHEST_WLS) return OFDM_ERR_INVALID;
     for (int r : p->reserved) if (r != 0) return OFDM_ERR_INVALID;
@@ -457,6 +472,7 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
             hipMemcpy(c->d_inv_trn, inv.data(), sizeof(float2) * N, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(c->d_header, hdr.data(), sizeof(float2) * 10 * S, hipMemcpyHostToDevice) != hipSuccess) { rc = OFDM_ERR_HIP; break; }
         if (p->chest_mode == OFDM_CHEST_WLS) rc = chest_tables(c); // the host solve (its time per N)
+        if (rc == OFDM_OK && p->cfo_mode == OFDM_CFO_WIDE) rc = cfo_wide_table(c);
     } while (0);
     if (rc != OFDM_OK) { ofdm_destroy(c); return rc; }
     *out = c;
@@ -1190,6 +1206,33 @@ int ofdm_rx_quality_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
                      f_delta, reinterpret_cast<const float2 *>(hk), hk_stride, status, quality);
 }
 
+// EXT-8 wide CFO acquisition: one launch of k_cfo_wide over the caller's offset / f_delta / status arrays (include/ofdm_hip.h,
+// tests/cfo_wide_ref.py)
+static int cfo_wide_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len, const int32_t *offset,
+                        const int32_t *status, int32_t span, double *f_delta, int32_t *m, float *metric) {
+    int rc = cfo_wide_table(c);
+    if (rc) return rc;
+    CfoWideParams p;
+    p.tune = &c->tune; p.trace = &c->trace;
+    p.in = in; p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
+    p.sym_len = c->S(); p.span = span;
+    p.offset = offset; p.status = status; p.f_delta = f_delta;
+    p.tw = c->d_tw; p.trn = c->d_trn;
+    p.m = m; p.metric = metric;
+    HIP_TRY(c, run_cfo_wide(c->prm.n_fft, p, c->stream, c->num_cu));
+    return OFDM_OK;
+}
+int ofdm_cfo_wide_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len, const int32_t *offset,
+                        const int32_t *status, int32_t span, double *f_delta, int32_t *m, float *metric) {
+    if (!c || n_frames < 0 || frame_len <= 0 || frame_stride < 0) return OFDM_ERR_INVALID;
+    if (span < 1 || span > OFDM_CFO_WIDE_MAX_SPAN) return OFDM_ERR_INVALID;
+    if (n_frames && (!in || !offset || !f_delta)) return OFDM_ERR_INVALID;
+    if (!n_frames) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    return cfo_wide_run(c, reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, offset, status, span, f_delta, m, metric);
+}
+
 // EXT-7 soft combining, the stage: one launch of k_llr_combine (include/ofdm_hip.h, tests/combine_ref.py)
 int ofdm_llr_combine_batch(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, int32_t n_branches, int64_t llr_stride, int64_t n_llr,
                            const float *quality, const int32_t *status, const int32_t *n_live, int8_t *out, int64_t out_stride,
@@ -1413,6 +1456,7 @@ static int rx_front_end(ofdm_ctx *c, const DecodeCall &d, int bps_bytes, FrontEn
         HIP_TRY(c, run_set_sync((int32_t *)w_dhat, fd, metric, known->d_hat, known->f_delta, known->metric, c->stream));
         HIP_TRY(c, run_rx_prepare(n_frames, (const int32_t *)w_dhat, fd, frame_len, c->S(), c->prm.sync_backoff,
                                   c->prm.cfo_mode, max_symbols, bps_bytes, status, offs, (int32_t *)w_nsym, c->stream));
+        if (c->prm.cfo_mode == OFDM_CFO_WIDE && (rc = cfo_wide_run(c, x, n_frames, frame_stride, frame_len, offs, status, OFDM_CFO_WIDE_SPAN, fd, nullptr, nullptr))) return rc;
     } else if (c->prm.sync_mode == OFDM_SYNC_REFERENCE) {
         // 1r. the reference's own detector (src/receiver.rs:20-25): cross-correlation with the locking signal, offset =
         //     idx_max - N (= lag - 1), then frequency_correction on chunks 3 and 4 (receiver.rs:39; always |.|)
@@ -1438,6 +1482,8 @@ static int rx_front_end(ofdm_ctx *c, const DecodeCall &d, int bps_bytes, FrontEn
         c->trace.add("k_rx_prepare");
         HIP_TRY(c, run_rx_prepare(n_frames, (const int32_t *)w_dhat, fd, frame_len, c->S(), c->prm.sync_backoff,
                                   c->prm.cfo_mode, max_symbols, bps_bytes, status, offs, (int32_t *)w_nsym, c->stream));
+        // 2w. EXT-8: the offset's whole multiples of 2 pi / S, from the training blocks; every kernel behind reads the same fd
+        if (c->prm.cfo_mode == OFDM_CFO_WIDE && (rc = cfo_wide_run(c, x, n_frames, frame_stride, frame_len, offs, status, OFDM_CFO_WIDE_SPAN, fd, nullptr, nullptr))) return rc;
     }
     fe.offs = offs; fe.fd = fd; fe.nsym = (int32_t *)w_nsym;
     return OFDM_OK;

@@ -104,6 +104,8 @@ struct ofdm_ctx {
     std::vector<double> training;       // the context's training table (interleaved re, im): what the tables below are made from
     float *d_chest_w = nullptr;         // W_k = |t_k|^2
     float2 *d_chest_mt = nullptr;       // N R^-1, transposed: [L_h][L_h]
+    // EXT-8 wide CFO acquisition: built by ofdm_create when cfo_mode is OFDM_CFO_WIDE, else by the first ofdm_cfo_wide_batch
+    float2 *d_trn = nullptr;            // training[k]
     ofdm::Tuning tune;                  // ofdm_set_tuning: per-context A/B switches and grid shapes (no environment variable is read)
     double sync_threshold_f64 = 0.0;    // ofdm_set_tuning "sync_threshold_bits": the packet-detect threshold as a double (0 = prm.sync_threshold, a float)
     ofdm::Trace trace;                  // ofdm_last_dispatch: the kernels the last entry point launched

@@ -34,6 +34,28 @@ def seeded_channel(c, tx, snr, seed, g):
     return c.channel_batch(tx, snr_db=snr, seed=seed, delay=d, f_delta=fd, span=tx.shape[1] + 160)
 
 
+def wide_channel(c, tx, snr, seed, g, span=8, m=None):
+    """(rx, m, f_delta): seeded_channel for EXT-8, wide CFO acquisition -- per frame a delay of 1 .. 32 samples, then m uniform in
+    [-span, span] (m given: that tensor, nothing drawn for it), then a fractional part within +-0.95 pi / S, drawn from g in that order;
+    the channel turns by f_delta = the fractional part + 2 pi m / S, which no Schmidl-Cox phase alone can report for m != 0.  The capture
+    is 160 samples longer than the frame.  seeded_channel's own draws are untouched."""
+    n_frames = tx.shape[0]
+    d = torch.randint(1, 33, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
+    if m is None:
+        m = torch.randint(-span, span + 1, (n_frames,), dtype=torch.int32, device=c.device, generator=g)
+    frac = (torch.rand((n_frames,), dtype=torch.float64, device=c.device, generator=g) * 1.9 - 0.95) * math.pi / c.S
+    fd = frac + 2.0 * math.pi * m.to(torch.float64) / c.S
+    return c.channel_batch(tx, snr_db=snr, seed=seed, delay=d, f_delta=fd, span=tx.shape[1] + 160), m, fd
+
+
+def wide_link_on(c, n_frames, payload, snr, seed, span=8, m=None):
+    """(pay, rx, m, f_delta): link_on through wide_channel"""
+    g = generator(c, seed)
+    pay = torch.randint(0, 256, (n_frames, max(payload, 1)), dtype=torch.uint8, device=c.device, generator=g)[:, :payload].contiguous()
+    rx, m, fd = wide_channel(c, c.encode_batch(pay), snr, seed, g, span, m)
+    return pay, rx, m, fd
+
+
 def link_on(c, n_frames, payload, snr, seed):
     """(pay, rx): seeded payloads [n_frames, payload] encoded by context c and sent through seeded_channel; `seed` seeds both the
     generator and the channel.  The payloads are drawn max(payload, 1) wide, so a payload of 0 bytes draws what one of 1 byte does."""
