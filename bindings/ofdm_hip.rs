@@ -14,6 +14,12 @@ pub struct ofdm_ctx { _private: [u8; 0] }
 #[derive(Clone, Copy)]
 pub struct ofdm_fc32 { pub re: f32, pub im: f32 }
 
+// EXT-9: interleaved little-endian int16 I/Q (UHD's sc16); x = v as f32 * scale, one rounded f32 product (include/ofdm_hip.h)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ofdm_sc16 { pub re: i16, pub im: i16 }
+pub const OFDM_SC16_DEFAULT_SCALE: f32 = 1.0 / 32768.0;
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct ofdm_params {
@@ -248,6 +254,24 @@ extern "C" {
     pub fn ofdm_rx_decode_long_host(ctx: *mut ofdm_ctx, in_host: *const ofdm_fc32, n_samples: i64, max_symbols: i32, out_host: *mut u8,
                                     out_cap: i64, out_len: *mut i32, status: *mut i32, offset: *mut i64, f_delta: *mut f64,
                                     metric: *mut f32) -> c_int;
+    pub fn ofdm_sc16_widen(input: *const ofdm_sc16, n: i64, scale: f32, out: *mut ofdm_fc32) -> c_int;
+    pub fn ofdm_sc16_narrow(input: *const ofdm_fc32, n: i64, scale: f32, out: *mut ofdm_sc16, clipped: *mut i64) -> c_int;
+    pub fn ofdm_sc16_widen_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_sc16, n_frames: i64, in_stride: i64, frame_len: i64, scale: f32,
+                                 out_dev: *mut ofdm_fc32, out_stride: i64) -> c_int;
+    pub fn ofdm_sc16_narrow_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, in_stride: i64, frame_len: i64, scale: f32,
+                                  out_dev: *mut ofdm_sc16, out_stride: i64, clipped_dev: *mut i32) -> c_int;
+    pub fn ofdm_rx_demod_sc16_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_sc16, n_frames: i64, frame_stride: i64, frame_len: i64, scale: f32,
+                                    first_symbol: i32, syms_per_frame: i32, offset_dev: *const i32, f_delta_dev: *const f64,
+                                    hk_dev: *const ofdm_fc32, hk_stride: i64, out_dev: *mut u8, out_stride: i64, soft_dev: *mut ofdm_fc32) -> c_int;
+    pub fn ofdm_rx_decode_sc16_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_sc16, n_frames: i64, frame_stride: i64, frame_len: i64, scale: f32,
+                                     n_lags: i64, max_symbols: i32, out_dev: *mut u8, out_stride: i64, out_len_dev: *mut i32,
+                                     status_dev: *mut i32, offset_dev: *mut i32, f_delta_dev: *mut f64, metric_dev: *mut f32) -> c_int;
+    pub fn ofdm_rx_demod_sc16_host(ctx: *mut ofdm_ctx, in_host: *const ofdm_sc16, n_frames: i64, frame_stride: i64, frame_len: i64, scale: f32,
+                                   first_symbol: i32, syms_per_frame: i32, out_host: *mut u8, out_stride: i64, chunk_frames: i64) -> c_int;
+    pub fn ofdm_rx_decode_sc16_host(ctx: *mut ofdm_ctx, in_host: *const ofdm_sc16, n_frames: i64, frame_stride: i64, frame_len: i64, scale: f32,
+                                    n_lags: i64, max_symbols: i32, out_host: *mut u8, out_stride: i64, out_len_host: *mut i32,
+                                    status_host: *mut i32, offset_host: *mut i32, f_delta_host: *mut f64, metric_host: *mut f32,
+                                    chunk_frames: i64) -> c_int;
     pub fn ofdm_timer_start(ctx: *mut ofdm_ctx) -> c_int;
     pub fn ofdm_timer_stop_ms(ctx: *mut ofdm_ctx, elapsed_ms: *mut f32) -> c_int;
 }

@@ -802,6 +802,55 @@ int ofdm_rx_decode_long(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_sample
 int ofdm_rx_decode_long_host(ofdm_ctx *ctx, const ofdm_fc32 *in_host, int64_t n_samples, int32_t max_symbols, uint8_t *out_host,
                              int64_t out_cap, int32_t *out_len, int32_t *status, int64_t *offset, double *f_delta, float *metric);
 
+/* ------------------------------------------------------------------ sc16 receive input (EXT-9)
+ * Radios deliver sc16 -- interleaved little-endian int16 I and Q, 4 bytes a sample: UHD's wire format and that of most recorded
+ * captures -- not fc32.  The sample format is a property of a CALL, not of a context: the same context decodes fc32 and sc16.
+ *
+ * Widen:   x = (float)v * scale for each component v.  The conversion is exact; the product is ONE f32 multiplication, rounded to
+ *          nearest even, and it is rounded before anything else uses it: it is never contracted into a following add or FMA.  (HIP
+ *          compiles with -ffp-contract=fast, under which __fmul_rn is a plain `*`; the kernels issue the product as its own
+ *          v_mul_f32 instruction from inline assembly, which is equivalent to a non-contracted __fmul_rn.)  numpy's
+ *          i16.astype(np.float32) * np.float32(scale) is the same number for every input and every scale, so every sc16 entry
+ *          point returns bit for bit what its fc32 twin returns on the widened samples.
+ * Narrow:  (the transmit side, for a DAC)  y = x * scale, the same single rounded product; q = rint(y), ties to even, clamped to
+ *          [-32767, 32767] (-32768 is never produced); a NaN gives 0.  A component COUNTS AS CLIPPED when y is not finite or rint(y)
+ *          lies outside [-32767, 32767]; the count is one int32 a frame.
+ * scale must be finite and > 0, otherwise OFDM_ERR_INVALID. */
+typedef struct { int16_t re, im; } ofdm_sc16;   /* interleaved, little-endian: UHD's sc16 */
+#define OFDM_SC16_DEFAULT_SCALE (1.0f / 32768.0f)
+/* The definition in C, on the host (no device, no context): n samples.  clipped (optional): clipped components of the whole call. */
+int ofdm_sc16_widen(const ofdm_sc16 *in, int64_t n, float scale, ofdm_fc32 *out);
+int ofdm_sc16_narrow(const ofdm_fc32 *in, int64_t n, float scale, ofdm_sc16 *out, int64_t *clipped);
+/* The same on the device (k_sc16_widen / k_sc16_narrow): n_frames rows of frame_len samples, strides in samples, stride >= frame_len
+ * on both sides; rows may start at any sample (4-byte alignment on the sc16 side, 8 on the fc32 side; 16-byte accesses are used when
+ * bases and strides allow them).  Nothing behind frame_len in an output row is written.  clipped_dev (optional): int32 per frame.
+ * Negative sizes, or NULL buffers with work to do: OFDM_ERR_INVALID; n_frames == 0: OFDM_OK and nothing is written. */
+int ofdm_sc16_widen_batch(ofdm_ctx *ctx, const ofdm_sc16 *in_dev, int64_t n_frames, int64_t in_stride, int64_t frame_len, float scale,
+                          ofdm_fc32 *out_dev, int64_t out_stride);
+int ofdm_sc16_narrow_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t in_stride, int64_t frame_len, float scale,
+                           ofdm_sc16 *out_dev, int64_t out_stride, int32_t *clipped_dev);
+/* ofdm_rx_demod_batch on sc16 samples (in_dev 4-byte aligned).  N = 64 inside the fast path's envelope -- no offset / f_delta / soft
+ * output, H shared or absent, a multiple of 8 symbols wholly inside frame_len, out_dev and out_stride multiples of 4 -- runs
+ * k_demod64_sc16, which reads the int16 pairs itself (half the bytes of k_demod64).  Everything else is widened by k_sc16_widen, a chunk
+ * of frames (about 48 MB of widened samples) at a time, into a workspace and goes through ofdm_rx_demod_batch's own dispatch. */
+int ofdm_rx_demod_sc16_batch(ofdm_ctx *ctx, const ofdm_sc16 *in_dev, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                             float scale, int32_t first_symbol, int32_t syms_per_frame, const int32_t *offset_dev,
+                             const double *f_delta_dev, const ofdm_fc32 *hk_dev, int64_t hk_stride, uint8_t *out_dev,
+                             int64_t out_stride, ofdm_fc32 *soft_dev);
+/* ofdm_rx_decode_batch on sc16 captures: k_sc16_widen per chunk of frames into the same workspace, then the unchanged chain on the chunk
+ * (every ecc, chest_mode, cfo_mode and sync_mode of the context); per-frame outputs land at the chunk's offset. */
+int ofdm_rx_decode_sc16_batch(ofdm_ctx *ctx, const ofdm_sc16 *in_dev, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                              float scale, int64_t n_lags, int32_t max_symbols, uint8_t *out_dev, int64_t out_stride,
+                              int32_t *out_len_dev, int32_t *status_dev, int32_t *offset_dev, double *f_delta_dev, float *metric_dev);
+/* The two host-buffer calls (see "host buffers") on sc16 host arrays: half the H2D bytes of their fc32 twins, the same outputs. */
+int ofdm_rx_demod_sc16_host(ofdm_ctx *ctx, const ofdm_sc16 *in_host, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                            float scale, int32_t first_symbol, int32_t syms_per_frame, uint8_t *out_host, int64_t out_stride,
+                            int64_t chunk_frames);
+int ofdm_rx_decode_sc16_host(ofdm_ctx *ctx, const ofdm_sc16 *in_host, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                             float scale, int64_t n_lags, int32_t max_symbols, uint8_t *out_host, int64_t out_stride,
+                             int32_t *out_len_host, int32_t *status_host, int32_t *offset_host, double *f_delta_host,
+                             float *metric_host, int64_t chunk_frames);
+
 /* ------------------------------------------------------------------ loop-back test bench
  * channel (src/channel.rs:33-74), per frame:
  *     y = convolve(tx, CHANNEL)                          tx_len + 63 samples (CHANNEL: the 64 taps of channel.rs:26-31)

@@ -183,6 +183,50 @@ class Context {
                                   r.status.data(), r.offset.data(), r.f_delta.data(), nullptr, chunk_frames), "ofdm_rx_decode_host");
         return r;
     }
+    // EXT-9: the same on sc16 host samples (interleaved int16 I/Q as a radio delivers them; x = int16 * scale): half the H2D bytes
+    BatchResult decode_batch_sc16(const ofdm_sc16 *frames, int64_t n_frames, int64_t frame_stride, int64_t frame_len, int32_t max_symbols,
+                                  float scale = OFDM_SC16_DEFAULT_SCALE, int64_t n_lags = 0, int64_t chunk_frames = 0) {
+        BatchResult r;
+        r.row = std::max<int64_t>((int64_t)max_symbols * ofdm_bytes_per_symbol(ctx_) - 16, 4);
+        r.bytes.resize((size_t)(n_frames * r.row));
+        r.len.resize((size_t)n_frames); r.status.resize((size_t)n_frames); r.offset.resize((size_t)n_frames); r.f_delta.resize((size_t)n_frames);
+        check(ofdm_rx_decode_sc16_host(ctx_, frames, n_frames, frame_stride, frame_len, scale, n_lags, max_symbols, r.bytes.data(), r.row,
+                                       r.len.data(), r.status.data(), r.offset.data(), r.f_delta.data(), nullptr, chunk_frames),
+              "ofdm_rx_decode_sc16_host");
+        return r;
+    }
+    // rx_demod of regular sc16 streams on host memory -> n_frames rows of syms_per_frame * bytes_per_symbol bytes
+    std::vector<uint8_t> demod_batch_sc16(const ofdm_sc16 *frames, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                                          int32_t syms_per_frame, int32_t first_symbol = 0, float scale = OFDM_SC16_DEFAULT_SCALE,
+                                          int64_t chunk_frames = 0) {
+        const int64_t nb = (int64_t)syms_per_frame * ofdm_bytes_per_symbol(ctx_);
+        std::vector<uint8_t> out((size_t)(n_frames * nb));
+        check(ofdm_rx_demod_sc16_host(ctx_, frames, n_frames, frame_stride, frame_len, scale, first_symbol, syms_per_frame, out.data(), nb,
+                                      chunk_frames), "ofdm_rx_demod_sc16_host");
+        return out;
+    }
+    // the two stages on the device (k_sc16_widen / k_sc16_narrow), host vectors in and out; *clipped (optional): clipped components
+    std::vector<ofdm_fc32> sc16_widen(const std::vector<ofdm_sc16> &in, float scale = OFDM_SC16_DEFAULT_SCALE) {
+        const int64_t n = (int64_t)in.size();
+        DevBuf din(ctx_, in.size() * sizeof(ofdm_sc16)), dout(ctx_, in.size() * sizeof(ofdm_fc32));
+        std::vector<ofdm_fc32> out(in.size());
+        if (n) check(ofdm_memcpy_h2d(ctx_, din.p, in.data(), in.size() * sizeof(ofdm_sc16)), "h2d");
+        check(ofdm_sc16_widen_batch(ctx_, (const ofdm_sc16 *)din.p, n ? 1 : 0, n, n, scale, (ofdm_fc32 *)dout.p, n), "ofdm_sc16_widen_batch");
+        if (n) check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size() * sizeof(ofdm_fc32)), "d2h");
+        return out;
+    }
+    std::vector<ofdm_sc16> sc16_narrow(const std::vector<ofdm_fc32> &in, float scale = 1.0f / OFDM_SC16_DEFAULT_SCALE, int32_t *clipped = nullptr) {
+        const int64_t n = (int64_t)in.size();
+        DevBuf din(ctx_, in.size() * sizeof(ofdm_fc32)), dout(ctx_, in.size() * sizeof(ofdm_sc16)), dclip(ctx_, sizeof(int32_t));
+        std::vector<ofdm_sc16> out(in.size());
+        if (clipped) *clipped = 0;
+        if (!n) return out;
+        check(ofdm_memcpy_h2d(ctx_, din.p, in.data(), in.size() * sizeof(ofdm_fc32)), "h2d");
+        check(ofdm_sc16_narrow_batch(ctx_, (const ofdm_fc32 *)din.p, 1, n, n, scale, (ofdm_sc16 *)dout.p, n, (int32_t *)dclip.p), "ofdm_sc16_narrow_batch");
+        check(ofdm_memcpy_d2h(ctx_, out.data(), dout.p, out.size() * sizeof(ofdm_sc16)), "d2h");
+        if (clipped) check(ofdm_memcpy_d2h(ctx_, clipped, dclip.p, sizeof(int32_t)), "d2h");
+        return out;
+    }
     // soft combining (EXT-7, include/ofdm_hip.h): frames of n_branches captures each, capture r of frame f at frames[(f * n_branches + r) *
     // frame_stride ..] -- two antennas, or a frame received twice -- decoded once per frame from the captures' LLRs weighted by link quality.
     // The captures are copied to the device and the results back by this call (the chain itself works on device buffers).  Modes: the
@@ -548,6 +592,18 @@ class ShardedContext {
 };
 
 // outer Reed-Solomon(255,223) framing of the demos (src/utils.rs:97-180), host side
+// EXT-9: sc16 <-> fc32 on the host (the definition in C: include/ofdm_hip.h).  narrow: *clipped (optional) = clipped components.
+inline std::vector<ofdm_fc32> sc16_widen(const std::vector<ofdm_sc16> &in, float scale = OFDM_SC16_DEFAULT_SCALE) {
+    std::vector<ofdm_fc32> out(in.size());
+    check(ofdm_sc16_widen(in.data(), (int64_t)in.size(), scale, out.data()), "ofdm_sc16_widen");
+    return out;
+}
+inline std::vector<ofdm_sc16> sc16_narrow(const std::vector<ofdm_fc32> &in, float scale = 1.0f / OFDM_SC16_DEFAULT_SCALE, int64_t *clipped = nullptr) {
+    std::vector<ofdm_sc16> out(in.size());
+    check(ofdm_sc16_narrow(in.data(), (int64_t)in.size(), scale, out.data(), clipped), "ofdm_sc16_narrow");
+    return out;
+}
+
 inline std::vector<uint8_t> create_transmission_bytes(const std::vector<uint8_t> &data) { // utils.rs:97-136
     std::vector<uint8_t> out((size_t)ofdm_rs255_encoded_len((int64_t)data.size()));
     check(ofdm_rs255_encode(data.data(), (int64_t)data.size(), out.data()), "ofdm_rs255_encode");

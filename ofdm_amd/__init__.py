@@ -14,7 +14,7 @@ def __getattr__(name):
                 "ECC_NONE", "ECC_HAMMING74", "ECC_HAMMING74_SOFT", "ECC_CONV_K7", "ECC_CONV_K7F_R12", "ECC_CONV_K7F_R23", "ECC_CONV_K7F_R34",
                 "ECC_RS255", "ECC_RS255_K7F_R12", "ECC_RS255_K7F_R23", "ECC_RS255_K7F_R34", "FRAME_UNCORRECTABLE", "ECC_FCS", "ECC_LDPC648", "ECC_LDPC648_R23", "ECC_LDPC648_R34", "ECC_LDPC648_R56", "LDPC_RATE_1_2", "LDPC_RATE_2_3", "LDPC_RATE_3_4", "LDPC_RATE_5_6", "LDPC_INFO_BYTES", "LDPC_MAX_ITER", "FCS_OVERHEAD", "FRAME_FCS", "crc32",
                 "CONV_RATE_1_2", "CONV_RATE_2_3", "CONV_RATE_3_4", "SOFT_LLR_SCALE", "CFO_OFF", "CFO_SIGNED", "CFO_ABS", "CFO_WIDE", "CFO_WIDE_SPAN", "CFO_WIDE_MAX_SPAN", "SYNC_SCHMIDL_COX", "SYNC_REFERENCE",
-                "CHEST_LS", "CHEST_WLS", "Q_VALID", "Q_NOISE_VAR", "Q_GAIN", "Q_SNR", "Q_LLR_UNIT", "Q_EVM2", "Q_POINTS", "QUALITY_FIELDS"):
+                "CHEST_LS", "CHEST_WLS", "SC16_DEFAULT_SCALE", "sc16_widen", "sc16_narrow", "Q_VALID", "Q_NOISE_VAR", "Q_GAIN", "Q_SNR", "Q_LLR_UNIT", "Q_EVM2", "Q_POINTS", "QUALITY_FIELDS"):
         import importlib
 
         api = importlib.import_module(".api", __name__)

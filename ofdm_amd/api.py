@@ -56,6 +56,9 @@ CHEST_LS, CHEST_WLS = 0, 1
 # ofdm_rx_quality_batch: indices into a frame's row of QUALITY_FIELDS floats (EXT-6; tests/quality_ref.py is the definition)
 Q_VALID, Q_NOISE_VAR, Q_GAIN, Q_SNR, Q_LLR_UNIT, Q_EVM2, Q_POINTS = 0, 1, 2, 3, 4, 5, 6
 QUALITY_FIELDS = 8
+# EXT-9: sc16 = interleaved little-endian int16 I/Q (UHD's wire format), int16 arrays / tensors of shape [..., 2]; x = int16 * scale as ONE
+# rounded f32 product (tests/sc16_ref.py is the definition)
+SC16_DEFAULT_SCALE = 1.0 / 32768.0  # OFDM_SC16_DEFAULT_SCALE
 DEFAULT_TUNING: dict = {}  # merged under every Context's `tuning=` (tools/tune_env.py fills it; empty in tests, bench and smoke)
 
 
@@ -165,6 +168,32 @@ def pinned_empty(shape, dtype) -> np.ndarray:
     arr = np.frombuffer(buf, dtype=np.uint8, count=n).view(dt).reshape(shape)
     weakref.finalize(buf, lib.ofdm_host_free, C.c_void_p(ptr.value))
     return arr
+
+
+def _sc16_host(a, what: str) -> np.ndarray:
+    a = np.asarray(a)
+    if a.dtype != np.int16 or a.ndim < 1 or a.shape[-1] != 2:
+        raise OfdmError(f"{what}: expected an int16 array of shape [..., 2]")
+    return np.ascontiguousarray(a)
+
+
+def sc16_widen(samples, scale: float = SC16_DEFAULT_SCALE) -> np.ndarray:
+    """ofdm_sc16_widen on the host (no device): int16 [..., 2] -> complex64 [...], x = int16 * scale per component."""
+    a = _sc16_host(samples, "sc16_widen")
+    out = np.empty(a.shape[:-1], np.complex64)
+    lib = _lib.load()
+    _check(lib, lib.ofdm_sc16_widen(_host(a), out.size, scale, _host(out)), "ofdm_sc16_widen")
+    return out
+
+
+def sc16_narrow(samples, scale: float = 1.0 / SC16_DEFAULT_SCALE):
+    """ofdm_sc16_narrow on the host (no device): complex64 [...] -> (int16 [..., 2], clipped components); q = clamp(rint(x * scale))."""
+    x = np.ascontiguousarray(samples, dtype=np.complex64)
+    out = np.empty(x.shape + (2,), np.int16)
+    clipped = C.c_int64()
+    lib = _lib.load()
+    _check(lib, lib.ofdm_sc16_narrow(_host(x), x.size, scale, _host(out), C.byref(clipped)), "ofdm_sc16_narrow")
+    return out, int(clipped.value)
 
 
 def _host(a: Optional[np.ndarray]):
@@ -297,6 +326,24 @@ class Context:
 
     def empty(self, shape, dtype) -> torch.Tensor:
         return torch.empty(shape, dtype=dtype, device=self.device)
+
+    def _sc16(self, t: torch.Tensor) -> torch.Tensor:
+        """[n_frames, stride, 2] (or [stride, 2]) int16 on the device; rows may be views with a stride of their own (a row start at
+        any sample), the samples of a row are contiguous."""
+        if t.dtype != torch.int16 or t.device != self.device or t.dim() < 2 or t.shape[-1] != 2 or t.stride(-1) != 1 or \
+                (t.shape[-2] > 1 and t.stride(-2) != 2):
+            raise OfdmError("expected an int16 tensor of shape [..., 2] on the context's device, samples of a row contiguous")
+        if t.dim() == 2:
+            t = t.unsqueeze(0)
+        if t.dim() != 3 or (t.shape[0] > 1 and t.stride(0) % 2):
+            raise OfdmError("expected int16 rows [n_frames, samples, 2] a whole number of samples apart")
+        return t
+
+    @staticmethod
+    def _rows(t: torch.Tensor):
+        """(n_frames, samples per row, row stride in samples) of a _sc16 tensor"""
+        n, ln = t.shape[0], t.shape[1]
+        return n, ln, (t.stride(0) // 2 if n > 1 else ln)
 
     # ---------------------------------------------------------------- stage level
     def fft(self, x: torch.Tensor, inverse: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -668,6 +715,90 @@ class Context:
                                               hk_stride, _dev(out), nb, _dev(soft)), "rx_demod")
         return (out, soft) if want_soft else out
 
+    # ---------------------------------------------------------------- EXT-9: sc16 input
+    def sc16_widen(self, samples: torch.Tensor, scale: float = SC16_DEFAULT_SCALE, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ofdm_sc16_widen_batch (k_sc16_widen): int16 [n_frames, len, 2] -> complex64 [n_frames, len] (out: rows may be longer)."""
+        t = self._sc16(samples)
+        n, ln, stride = self._rows(t)
+        out = self.empty((n, ln), torch.complex64) if out is None else out
+        o2 = out if out.dim() == 2 else out.unsqueeze(0)
+        self._ck(self.lib.ofdm_sc16_widen_batch(self.h, _dev(t), n, stride, ln, scale, _dev(o2), o2.stride(0) if n > 1 else max(o2.shape[1], ln)),
+                 "sc16_widen")
+        return out
+
+    def sc16_narrow(self, samples: torch.Tensor, scale: float = 1.0 / SC16_DEFAULT_SCALE, out: Optional[torch.Tensor] = None):
+        """ofdm_sc16_narrow_batch (k_sc16_narrow): complex64 [n_frames, len] -> (int16 [n_frames, len, 2], clipped int32 [n_frames])."""
+        x = samples if samples.dim() == 2 else samples.unsqueeze(0)
+        if x.dtype != torch.complex64 or x.device != self.device or x.stride(-1) != 1:
+            raise OfdmError("expected complex64 rows on the context's device")
+        n, ln = x.shape
+        out = self.empty((n, ln, 2), torch.int16) if out is None else self._sc16(out)
+        clipped = self.empty((n,), torch.int32)
+        self._ck(self.lib.ofdm_sc16_narrow_batch(self.h, _dev(x), n, x.stride(0) if n > 1 else ln, ln, scale, _dev(out),
+                                                 out.stride(0) // 2 if n > 1 else max(out.shape[1], ln), _dev(clipped)), "sc16_narrow")
+        return out, clipped
+
+    def rx_demod_sc16(self, frames: torch.Tensor, syms_per_frame: int, first_symbol: int = 0, offset: Optional[torch.Tensor] = None,
+                      f_delta: Optional[torch.Tensor] = None, hk: Optional[torch.Tensor] = None, frame_len: Optional[int] = None,
+                      want_soft: bool = False, out: Optional[torch.Tensor] = None, scale: float = SC16_DEFAULT_SCALE):
+        """ofdm_rx_demod_sc16_batch: rx_demod of int16 [n_frames, stride, 2]; N = 64 regular streams run k_demod64_sc16."""
+        t = self._sc16(frames)
+        n, ln, stride = self._rows(t)
+        nb = syms_per_frame * self.bytes_per_symbol
+        out = self.empty((n, nb), torch.uint8) if out is None else self._u8(out)
+        soft = self.empty((n, syms_per_frame * self.data_carriers), torch.complex64) if want_soft else None
+        hk_stride = 0
+        if hk is not None:
+            hk = self._cx(hk)
+            hk_stride = self.n_fft if hk.dim() == 2 else 0
+            assert hk.shape[-1] == self.n_fft and (hk.dim() == 1 or hk.shape[0] == n)
+        self._ck(self.lib.ofdm_rx_demod_sc16_batch(self.h, _dev(t), n, stride, ln if frame_len is None else frame_len, scale, first_symbol,
+                                                   syms_per_frame, _dev(offset), _dev(f_delta), _dev(hk), hk_stride, _dev(out), nb,
+                                                   _dev(soft)), "rx_demod_sc16")
+        return (out, soft) if want_soft else out
+
+    def decode_batch_sc16(self, frames: torch.Tensor, max_symbols: int, n_lags: int = 0, frame_len: Optional[int] = None,
+                          scale: float = SC16_DEFAULT_SCALE):
+        """ofdm_rx_decode_sc16_batch: decode_batch of int16 captures [n_frames, stride, 2]."""
+        t = self._sc16(frames)
+        n, ln, stride = self._rows(t)
+        ob = self.decode_row_bytes(max_symbols)
+        out = self.empty((n, ob), torch.uint8)
+        res = {
+            "bytes": out, "len": self.empty((n,), torch.int32), "status": self.empty((n,), torch.int32),
+            "offset": self.empty((n,), torch.int32), "f_delta": self.empty((n,), torch.float64),
+            "metric": self.empty((n,), torch.float32),
+        }
+        self._ck(self.lib.ofdm_rx_decode_sc16_batch(self.h, _dev(t), n, stride, ln if frame_len is None else frame_len, scale, n_lags,
+                                                    max_symbols, _dev(out), ob, _dev(res["len"]), _dev(res["status"]),
+                                                    _dev(res["offset"]), _dev(res["f_delta"]), _dev(res["metric"])), "rx_decode_sc16")
+        return res
+
+    def decode_host_sc16(self, frames: np.ndarray, max_symbols: int, n_lags: int = 0, frame_len: Optional[int] = None,
+                         chunk_frames: int = 0, out: Optional[dict] = None, scale: float = SC16_DEFAULT_SCALE):
+        """ofdm_rx_decode_sc16_host: decode_host for a host array [n_frames, stride, 2] of int16 (half the H2D bytes)."""
+        x = _sc16_host(frames, "decode_host_sc16")
+        n, stride = x.shape[0], x.shape[1]
+        ob = self.decode_row_bytes(max_symbols)
+        res = out or {"bytes": np.zeros((n, ob), np.uint8), "len": np.zeros(n, np.int32), "status": np.zeros(n, np.int32),
+                      "offset": np.zeros(n, np.int32), "f_delta": np.zeros(n, np.float64), "metric": np.zeros(n, np.float32)}
+        self._ck(self.lib.ofdm_rx_decode_sc16_host(self.h, _host(x), n, stride, stride if frame_len is None else frame_len, scale, n_lags,
+                                                   max_symbols, _host(res["bytes"]), res["bytes"].shape[1], _host(res["len"]),
+                                                   _host(res["status"]), _host(res["offset"]), _host(res["f_delta"]),
+                                                   _host(res["metric"]), chunk_frames), "rx_decode_sc16_host")
+        return res
+
+    def demod_host_sc16(self, frames: np.ndarray, syms_per_frame: int, first_symbol: int = 0, chunk_frames: int = 0,
+                        out: Optional[np.ndarray] = None, scale: float = SC16_DEFAULT_SCALE) -> np.ndarray:
+        """ofdm_rx_demod_sc16_host: demod_host for a host array [n_frames, stride, 2] of int16 (half the H2D bytes)."""
+        x = _sc16_host(frames, "demod_host_sc16")
+        n, stride = x.shape[0], x.shape[1]
+        nb = syms_per_frame * self.bytes_per_symbol
+        out = np.zeros((n, nb), np.uint8) if out is None else out
+        self._ck(self.lib.ofdm_rx_demod_sc16_host(self.h, _host(x), n, stride, stride, scale, first_symbol, syms_per_frame, _host(out),
+                                                  out.shape[1], chunk_frames), "rx_demod_sc16_host")
+        return out
+
     def rx_llr(self, frames: torch.Tensor, syms_per_frame: int, first_symbol: int = 0, offset: Optional[torch.Tensor] = None,
                f_delta: Optional[torch.Tensor] = None, hk: Optional[torch.Tensor] = None, frame_len: Optional[int] = None,
                scale: float = SOFT_LLR_SCALE, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1029,14 +1160,17 @@ def channel(transmission, snr: Optional[float] = None, timing_error: Optional[bo
 
 
 def decode(samples, guard_bands: Optional[bool] = None, modulation: Optional[int] = None, n_fft: int = 64,
-           ecc: int = ECC_NONE, fcs: bool = False, **sync) -> bytes:
+           ecc: int = ECC_NONE, fcs: bool = False, scale: float = SC16_DEFAULT_SCALE, **sync) -> bytes:
     """`ofdm::decode!(samples, guard_bands, modulation)` (src/receiver.rs:8-96): Vec<Complex64> -> Result<Vec<u8>>.
     Raises DecodeError("Input not long enough, bailing early") where the reference returns Err.  fcs: the frame was sent with
-    encode(..., fcs=True): exactly the payload comes back, or DecodeError when the check fails."""
+    encode(..., fcs=True): exactly the payload comes back, or DecodeError when the check fails.  An int16 array of shape [n, 2] is an
+    sc16 capture (EXT-9), widened with `scale` on the device."""
     ctx = _ctx(n_fft, BPSK if modulation is None else modulation, bool(guard_bands), _with_fcs(ecc, fcs), **sync)
-    x = ctx.to_device(np.asarray(samples)).reshape(1, -1)
+    arr = np.asarray(samples)
+    sc16 = arr.dtype == np.int16
+    x = ctx.to_device(_sc16_host(arr, "decode")).unsqueeze(0) if sc16 else ctx.to_device(arr).reshape(1, -1)
     max_symbols = max((x.shape[1] + ctx.S - 1) // ctx.S - 10, 1)
-    res = ctx.decode_batch(x, max_symbols=max_symbols)
+    res = ctx.decode_batch_sc16(x, max_symbols=max_symbols, scale=scale) if sc16 else ctx.decode_batch(x, max_symbols=max_symbols)
     ctx.synchronize()
     status = int(res["status"][0])
     if status == FRAME_SHORT:

@@ -573,4 +573,16 @@ __device__ __forceinline__ unsigned lds_addr(const void *p) {
     return (unsigned)(unsigned long)((const __attribute__((address_space(3))) char *)p);
 }
 
+// EXT-9 (sc16): x * scale as ONE rounded f32 product that nothing can contract into a following add or FMA.  HIP compiles with
+// -ffp-contract=fast, under which __fmul_rn is a plain `*`; an instruction written out is not a candidate for contraction.
+__device__ __forceinline__ float sc16_mul(float x, float scale) {
+    float y;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(y) : "s"(scale), "v"(x));
+    return y;
+}
+// one sc16 sample (low half: re, high half: im) -> fc32
+__device__ __forceinline__ cf sc16_widen1(unsigned d, float scale) {
+    return make_float2(sc16_mul((float)(short)(d & 0xFFFFu), scale), sc16_mul((float)((int)d >> 16), scale));
+}
+
 } // namespace ofdm

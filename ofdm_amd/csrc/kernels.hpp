@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include <mutex>
 
 #ifndef OFDM_PROFILE_BUILD
 #define OFDM_PROFILE_BUILD 0 // 1 (ofdm_amd/build.py, profile=True): libofdm_hip_profile.so with the ablation / section-timing branches
@@ -46,6 +47,8 @@ struct Tuning {
     int chest_solve_only = 0;      // ofdm_chest_smooth_batch: 1 = launch k_chest_solve alone on the rows given (into the workspace; nothing is delivered): its time on its own
     int soft_chunk_frames = 0;     // OFDM_ECC_HAMMING74_SOFT / OFDM_ECC_CONV_K7 decode: frames per k_sym<llr> + k_rx_finish_soft / k_viterbi_k7 step (0 = the LLR workspace's 256 MB bound)
     int fcs_bitserial = 0;         // k_fcs_wrap / k_fcs_check: every lane reduces its chunk bit by bit in registers instead of through the slice-by-4 tables in LDS (A/B)
+    int no_demod64_sc16 = 0;       // EXT-9: ofdm_rx_demod_sc16_batch at N = 64 widens into the workspace and runs the fc32 path instead of k_demod64_sc16 (A/B)
+    int sc16_chunk_frames = 0;     // EXT-9: frames per k_sc16_widen + fc32 chain step of the sc16 entry points (0 = about 48 MB of widened samples)
 };
 inline const Tuning &tuning_or_default(const Tuning *t) { static const Tuning d; return t ? *t : d; }
 
@@ -76,6 +79,28 @@ template <class F> hipError_t with_bps(int bps, F &&f) { return with_int<1, 2, 4
 inline long long persistent_grid(long long units, long long resident, const Tuning &tu) {
     if (tu.grid_cap > 0 && tu.grid_cap < resident) resident = tu.grid_cap;
     return units < resident ? units : resident;
+}
+
+// Persistent grid: resident workgroups per CU from the occupancy API (per instantiation and device, cached), doubled up
+// to the 8 the round-1 launcher used -- measured (OFDM_DEMOD64_WG_PER_CU sweep, 1 M frames): 3 -> 1.77 ms, 4 -> 1.70,
+// 5 -> 1.81, 8 -> 1.68: a second, queued round of workgroups evens out the tail.
+// The cache is keyed by the kernel's ADDRESS: every k_demod64 instantiation has the same function type, so a static inside a
+// template over that type would be shared by all of them (the BURST = 16 variant holds 37 KB of LDS per workgroup, the others 11).
+template <typename K> inline int resident_blocks(K kernel, int block) {
+    struct Entry { const void *fn; int dev, n; };
+    static Entry cache[64];
+    static int used = 0;
+    static std::mutex mtx;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    const void *fn = reinterpret_cast<const void *>(kernel);
+    std::lock_guard<std::mutex> lock(mtx);
+    for (int i = 0; i < used; ++i) if (cache[i].fn == fn && cache[i].dev == dev) return cache[i].n;
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, block, 0) != hipSuccess || n < 1) n = 4;
+    n = n > 8 ? 8 : n;
+    if (used < 64) cache[used++] = Entry{fn, dev, n};
+    return n;
 }
 
 // Counters of the last Schmidl-Cox search on a context (ofdm_get_tuning "stat_sc_slow_frames" / "stat_sc_redo_frames"): how many
@@ -149,6 +174,33 @@ struct Fast64Params {
     int debug = 0;              // profiling aid (OFDM_DEMOD64_DEBUG): 1 no stores, 2 no packing either, 3 loads + first butterfly only
 };
 hipError_t run_demod64_fast(const SymParams &p, hipStream_t st, int num_cu);
+// EXT-9: the same kernel body fed with sc16 samples (kernels_n64_sc16.hip).  One dword = (int16 re, int16 im), little-endian; every
+// component is widened as (float)v * scale, one rounded f32 product (include/ofdm_hip.h).  p.in is not read.
+struct Fast64Sc16Params : Fast64Params {
+    const uint32_t *in16 = nullptr;
+    float scale = 0.f;
+};
+// run_demod64_fast's envelope with a 4-byte aligned input; hipErrorNotSupported outside it (caller widens and takes the fc32 path)
+hipError_t run_demod64_sc16(const SymParams &p, const uint32_t *in16, float scale, hipStream_t st, int num_cu);
+
+// ---- EXT-9 sc16 <-> fc32 (ofdm_sc16_widen_batch / ofdm_sc16_narrow_batch and the widen step of the sc16 receive entry points;
+// kernels_sc16.hip, definition: include/ofdm_hip.h, tests/sc16_ref.py).  Rows of frame_len samples, strides in samples.
+struct Sc16Params {
+    const Tuning *tune = nullptr;
+    Trace *trace = nullptr;
+    long long n_frames = 0, frame_len = 0, in_stride = 0, out_stride = 0;
+    float scale = 0.f;
+    const uint32_t *sc_in = nullptr;     // widen: sc16 in, fc32 out
+    float2 *fc_out = nullptr;
+    const float2 *fc_in = nullptr;       // narrow: fc32 in, sc16 out
+    uint32_t *sc_out = nullptr;
+    int32_t *clipped = nullptr;          // narrow, optional: clipped components per row
+};
+hipError_t run_sc16_widen(const Sc16Params &p, int num_cu, hipStream_t st);
+hipError_t run_sc16_narrow(const Sc16Params &p, int num_cu, hipStream_t st);
+// the two host functions behind ofdm_sc16_widen / ofdm_sc16_narrow (scale already checked)
+void sc16_widen_host(const int16_t *in, long long n, float scale, float *out);
+long long sc16_narrow_host(const float *in, long long n, float scale, int16_t *out);
 // N = 4096 RX demod as 64 x 64 (regular streams: no offset / CFO / per-frame symbol counts / soft output)
 hipError_t run_demod4096(const SymParams &p, hipStream_t st, int num_cu);
 // fused estimate_channel + per-symbol demod [+ finish] for N = 1024 frames (16 x 64 FFT, kernels_rx1024.hip), the N = 1024

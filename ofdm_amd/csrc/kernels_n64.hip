@@ -3,7 +3,7 @@
 //   k_rxframe64    N = 64 per-frame receive body after timing (config 3): channel estimate + demod [+ finish]
 //   k_txframe64    N = 64 encode: frame built in LDS, one HBM pass
 //   (k_rxframe1024, the N = 1024 per-frame receive body of config 4, lives in kernels_rx1024.hip; k_demod4096 / k_tx4096 /
-//    k_txframe4096, N = 4096 as 64 x 64, in kernels_n4096.hip)
+//    k_txframe4096, N = 4096 as 64 x 64, in kernels_n4096.hip; k_demod64_sc16, k_demod64 fed with int16 samples, in kernels_n64_sc16.hip)
 //
 // k_demod64: CP strip + FFT64 + [equalise] + pilot phase + hard demap + LSB-first bit packing, for regularly spaced,
 // HBM-resident symbols.
@@ -20,7 +20,6 @@
 #include "device_common.hpp"
 #include "kernels.hpp"
 #include <type_traits>
-#include <mutex>
 #include <stdlib.h>
 
 namespace ofdm {
@@ -740,27 +739,6 @@ hipError_t run_txframe64(const SymParams &sp, const float2 *header, float header
         return launch_txframe<decltype(B)::value, decltype(G)::value>(p, grid, lds, st); }); });
 }
 
-// Persistent grid: resident workgroups per CU from the occupancy API (per instantiation and device, cached), doubled up
-// to the 8 the round-1 launcher used -- measured (OFDM_DEMOD64_WG_PER_CU sweep, 1 M frames): 3 -> 1.77 ms, 4 -> 1.70,
-// 5 -> 1.81, 8 -> 1.68: a second, queued round of workgroups evens out the tail.
-// The cache is keyed by the kernel's ADDRESS: every k_demod64 instantiation has the same function type, so a static inside a
-// template over that type would be shared by all of them (the BURST = 16 variant holds 37 KB of LDS per workgroup, the others 11).
-template <typename K> static int resident_blocks(K kernel, int block) {
-    struct Entry { const void *fn; int dev, n; };
-    static Entry cache[64];
-    static int used = 0;
-    static std::mutex mtx;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    const void *fn = reinterpret_cast<const void *>(kernel);
-    std::lock_guard<std::mutex> lock(mtx);
-    for (int i = 0; i < used; ++i) if (cache[i].fn == fn && cache[i].dev == dev) return cache[i].n;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, block, 0) != hipSuccess || n < 1) n = 4;
-    n = n > 8 ? 8 : n;
-    if (used < 64) cache[used++] = Entry{fn, dev, n};
-    return n;
-}
 template <int BPS, bool GUARD, bool HK> static hipError_t launch_demod64(Fast64Params p, hipStream_t st, int num_cu, const Tuning &tu, Trace *trace) {
     p.debug = kProfile ? tu.debug_demod64 : 0;
     constexpr int region_bytes = (GUARD ? 48 : 64) * BPS;

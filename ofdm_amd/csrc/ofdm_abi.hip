@@ -1619,6 +1619,147 @@ int ofdm_rx_decode_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int
                        status, offset, f_delta, metric, nullptr};
     return rx_decode(c, d);
 }
+
+// ------------------------------------------------------------------ EXT-9: sc16 input
+static bool sc16_scale_ok(float scale) { return std::isfinite(scale) && scale > 0.f; }
+
+int ofdm_sc16_widen(const ofdm_sc16 *in, int64_t n, float scale, ofdm_fc32 *out) {
+    if (n < 0 || !sc16_scale_ok(scale) || (n && (!in || !out))) return OFDM_ERR_INVALID;
+    sc16_widen_host(&in->re, n, scale, &out->re);
+    return OFDM_OK;
+}
+int ofdm_sc16_narrow(const ofdm_fc32 *in, int64_t n, float scale, ofdm_sc16 *out, int64_t *clipped) {
+    if (n < 0 || !sc16_scale_ok(scale) || (n && (!in || !out))) return OFDM_ERR_INVALID;
+    const long long k = sc16_narrow_host(&in->re, n, scale, &out->re);
+    if (clipped) *clipped = k;
+    return OFDM_OK;
+}
+// the checks both stages share; *work: there is something to launch
+static int sc16_stage_check(const ofdm_ctx *c, const void *in, int64_t n_frames, int64_t in_stride, int64_t frame_len, float scale,
+                            const void *out, int64_t out_stride, const void *sc_side, bool *work) {
+    if (!c || n_frames < 0 || frame_len < 0 || !sc16_scale_ok(scale)) return OFDM_ERR_INVALID;
+    if (in_stride < frame_len || out_stride < frame_len) return OFDM_ERR_INVALID;
+    *work = n_frames > 0 && frame_len > 0;
+    if (*work && (!in || !out || (reinterpret_cast<uintptr_t>(sc_side) & 3))) return OFDM_ERR_INVALID;
+    return OFDM_OK;
+}
+int ofdm_sc16_widen_batch(ofdm_ctx *c, const ofdm_sc16 *in, int64_t n_frames, int64_t in_stride, int64_t frame_len, float scale,
+                          ofdm_fc32 *out, int64_t out_stride) {
+    bool work = false;
+    const int rc = sc16_stage_check(c, in, n_frames, in_stride, frame_len, scale, out, out_stride, in, &work);
+    if (rc || !work) return rc;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    Sc16Params p;
+    p.tune = &c->tune; p.trace = &c->trace; p.n_frames = n_frames; p.frame_len = frame_len; p.in_stride = in_stride; p.out_stride = out_stride;
+    p.scale = scale; p.sc_in = reinterpret_cast<const uint32_t *>(in); p.fc_out = reinterpret_cast<float2 *>(out);
+    HIP_TRY(c, run_sc16_widen(p, c->num_cu, c->stream));
+    return OFDM_OK;
+}
+int ofdm_sc16_narrow_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t in_stride, int64_t frame_len, float scale,
+                           ofdm_sc16 *out, int64_t out_stride, int32_t *clipped) {
+    bool work = false;
+    const int rc = sc16_stage_check(c, in, n_frames, in_stride, frame_len, scale, out, out_stride, out, &work);
+    if (rc || !n_frames) return rc;
+    if (!work && !clipped) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    Sc16Params p;
+    p.tune = &c->tune; p.trace = &c->trace; p.n_frames = n_frames; p.frame_len = frame_len; p.in_stride = in_stride; p.out_stride = out_stride;
+    p.scale = scale; p.fc_in = reinterpret_cast<const float2 *>(in); p.sc_out = reinterpret_cast<uint32_t *>(out); p.clipped = clipped;
+    HIP_TRY(c, run_sc16_narrow(p, c->num_cu, c->stream));
+    return OFDM_OK;
+}
+
+// The widen path of the sc16 receive entry points: frames [f0, f0 + m) of the caller's rows -> kWsSc16, rows of frame_len samples
+// ws_stride apart.  ws_stride keeps the parity of the caller's stride, so that the fc32 path sees rows aligned as the caller's
+// widened rows would be; the chunk is the host pipe's (auto_chunk, ofdm_host_path.hip): about 48 MB of widened samples.
+struct Sc16Chunks {
+    int64_t chunk, ws_stride;
+    float2 *ws;
+};
+static int sc16_chunks(ofdm_ctx *c, int64_t n_frames, int64_t frame_stride, int64_t frame_len, Sc16Chunks &k) {
+    k.ws_stride = frame_len + ((frame_len ^ frame_stride) & 1);
+    int64_t chunk = c->tune.sc16_chunk_frames;
+    if (chunk <= 0) {
+        chunk = (int64_t)((size_t)48 << 20) / std::max<int64_t>(k.ws_stride * (int64_t)sizeof(float2), 1);
+        if (chunk > 4) chunk &= ~(int64_t)3;
+    }
+    k.chunk = std::min(std::max<int64_t>(chunk, 1), std::max<int64_t>(n_frames, 1));
+    void *w;
+    const int rc = ws_get(c, kWsSc16, (size_t)k.chunk * (size_t)k.ws_stride * sizeof(float2), &w);
+    k.ws = static_cast<float2 *>(w);
+    return rc;
+}
+static int sc16_widen_chunk(ofdm_ctx *c, const ofdm_sc16 *in, int64_t f0, int64_t m, int64_t frame_stride, int64_t frame_len, float scale,
+                            const Sc16Chunks &k) {
+    Sc16Params p;
+    p.tune = &c->tune; p.n_frames = m; p.frame_len = frame_len; p.in_stride = frame_stride; p.out_stride = k.ws_stride; p.scale = scale;
+    p.sc_in = reinterpret_cast<const uint32_t *>(in + f0 * frame_stride); p.fc_out = k.ws;
+    HIP_TRY(c, run_sc16_widen(p, c->num_cu, c->stream));
+    return OFDM_OK;
+}
+
+int ofdm_rx_demod_sc16_batch(ofdm_ctx *c, const ofdm_sc16 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len, float scale,
+                             int32_t first_symbol, int32_t syms_per_frame, const int32_t *offset, const double *f_delta,
+                             const ofdm_fc32 *hk, int64_t hk_stride, uint8_t *out, int64_t out_stride, ofdm_fc32 *soft) {
+    if (!c || n_frames < 0 || syms_per_frame < 0 || first_symbol < 0 || frame_len <= 0 || !sc16_scale_ok(scale)) return OFDM_ERR_INVALID;
+    if (n_frames && syms_per_frame && (!in || !out || (reinterpret_cast<uintptr_t>(in) & 3))) return OFDM_ERR_INVALID;
+    if (out_stride < (int64_t)syms_per_frame * c->bytes_per_symbol()) return OFDM_ERR_INVALID;
+    if (hk && hk_stride != 0 && hk_stride != c->prm.n_fft) return OFDM_ERR_INVALID;
+    if (!n_frames || !syms_per_frame) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    if (c->prm.n_fft == 64) { // the fused kernel reads the int16 pairs itself
+        SymParams p = rx_params(c, nullptr, n_frames, frame_stride, frame_len, offset, f_delta, nullptr, out, out_stride);
+        p.first_symbol = first_symbol; p.syms_per_frame = syms_per_frame; p.in_sym_stride = c->S(); p.in_skip = c->prm.cp_len;
+        p.hk = reinterpret_cast<const float2 *>(hk); p.hk_stride = hk_stride; p.soft = reinterpret_cast<float2 *>(soft);
+        FAST_PATH(c, c->tune.no_demod64_sc16 || c->tune.no_fast64,
+                  run_demod64_sc16(p, reinterpret_cast<const uint32_t *>(in), scale, c->stream, c->num_cu));
+    }
+    Sc16Chunks k;
+    int rc;
+    if ((rc = sc16_chunks(c, n_frames, frame_stride, frame_len, k))) return rc;
+    c->trace.add("k_sc16_widen");
+    Trace first;
+    for (int64_t f0 = 0; f0 < n_frames; f0 += k.chunk) {
+        const int64_t m = std::min(k.chunk, n_frames - f0);
+        if ((rc = sc16_widen_chunk(c, in, f0, m, frame_stride, frame_len, scale, k))) return rc;
+        rc = demod_run(c, k.ws, m, k.ws_stride, frame_len, first_symbol, syms_per_frame, offset ? offset + f0 : nullptr,
+                       f_delta ? f_delta + f0 : nullptr, nullptr, hk ? reinterpret_cast<const float2 *>(hk) + f0 * hk_stride : nullptr, hk_stride,
+                       out + f0 * out_stride, out_stride,
+                       soft ? reinterpret_cast<float2 *>(soft) + f0 * (int64_t)syms_per_frame * c->carriers() : nullptr);
+        if (rc) return rc;
+        if (!f0) first = c->trace; // the dispatch string names what a chunk ran, once
+    }
+    c->trace = first;
+    return OFDM_OK;
+}
+
+int ofdm_rx_decode_sc16_batch(ofdm_ctx *c, const ofdm_sc16 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len, float scale,
+                              int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len, int32_t *status,
+                              int32_t *offset, double *f_delta, float *metric) {
+    if (!c || n_frames < 0 || frame_len <= 0 || max_symbols <= 0 || !sc16_scale_ok(scale)) return OFDM_ERR_INVALID;
+    if (n_frames && (!in || !out || !out_len || !status || (reinterpret_cast<uintptr_t>(in) & 3))) return OFDM_ERR_INVALID;
+    if (!n_frames) return rx_decode(c, DecodeCall{nullptr, 0, frame_stride, frame_len, n_lags, max_symbols, out, out_stride, out_len, status,
+                                                  offset, f_delta, metric, nullptr}); // the chain's own argument checks
+    DeviceGuard dev_guard(c->device);
+    Sc16Chunks k;
+    int rc;
+    if ((rc = sc16_chunks(c, n_frames, frame_stride, frame_len, k))) return rc;
+    Trace first;
+    for (int64_t f0 = 0; f0 < n_frames; f0 += k.chunk) {
+        const int64_t m = std::min(k.chunk, n_frames - f0);
+        if ((rc = sc16_widen_chunk(c, in, f0, m, frame_stride, frame_len, scale, k))) return rc;
+        const DecodeCall d{k.ws, m, k.ws_stride, frame_len, n_lags, max_symbols, out + f0 * out_stride, out_stride, out_len + f0, status + f0,
+                           offset ? offset + f0 : nullptr, f_delta ? f_delta + f0 : nullptr, metric ? metric + f0 : nullptr, nullptr};
+        if ((rc = rx_decode(c, d))) return rc;
+        if (!f0) { first.reset(); first.add("k_sc16_widen"); first.add(c->trace.buf); }
+    }
+    c->trace = first;
+    return OFDM_OK;
+}
+
 // EXT-7: the inner chain over frames of R captures.  d: the call per FRAME (out, out_len, status), its offset / f_delta / metric per BRANCH
 // ROW.  Front end, link quality and LLRs per branch row, k_llr_combine, then the mode's finishing kernel on the combined rows.
 // The LLR workspace holds one chunk of frames: R branch rows and the combined row each.

@@ -82,6 +82,7 @@ enum WsRole {
     kWsTxFcsRows, kWsTxFcsLen, kWsTxRsRows, kWsTxRsLen, kWsTxCoded, kWsTxCodedLen, // encode: rows and ragged lengths out of every layer
     kWsFrameMax,                 // per-frame maxima (ofdm_tx_encode_batch, ofdm_normalize_batch)
     kWsProbeSink,                // ofdm_hbm_read_probe
+    kWsSc16,                     // EXT-9: one chunk of frames widened from sc16, the input of the fc32 path behind the sc16 entry points
     kWsRoles
 };
 

@@ -28,6 +28,11 @@
 //   frame check (OFDM_ECC_FCS + mode)
 //     fcs_bitserial       k_fcs_wrap / k_fcs_check reduce every lane's chunk bit by bit in registers instead of through the slice-by-4
 //                         tables in LDS (tools/bench_fcs.py times both)
+//   sc16 receive input (EXT-9)
+//     no_demod64_sc16     ofdm_rx_demod_sc16_batch at N = 64 inside the fused kernel's envelope: k_sc16_widen into the workspace + the fc32
+//                         path instead of k_demod64_sc16 (tools/bench_sc16.py times both)
+//     sc16_chunk_frames   frames per k_sc16_widen + fc32 chain step of ofdm_rx_demod_sc16_batch's widen path and of
+//                         ofdm_rx_decode_sc16_batch (0 = about 48 MB of widened samples; the tests put chunk boundaries inside five frames)
 //   Schmidl-Cox threshold in full precision (handled by name in ofdm_abi.hip, 64 bits: not in the table below)
 //     sync_threshold_bits the bit pattern of a double in (0, 1] that replaces ofdm_params.sync_threshold (a float: 6e-8 apart) in every
 //                         search of the context; 0 = the float again.  The margin tests set the threshold within 1e-12 of a lag's own metric
@@ -63,6 +68,8 @@ OFDM_TUNE_KEY("scb_big_tiles", scb_big_tiles, false)
 OFDM_TUNE_KEY("soft_chunk_frames", soft_chunk_frames, false)
 OFDM_TUNE_KEY("chest_solve_only", chest_solve_only, false)
 OFDM_TUNE_KEY("fcs_bitserial", fcs_bitserial, false)
+OFDM_TUNE_KEY("no_demod64_sc16", no_demod64_sc16, false)
+OFDM_TUNE_KEY("sc16_chunk_frames", sc16_chunk_frames, false)
 OFDM_TUNE_KEY("debug_demod64", debug_demod64, true)
 OFDM_TUNE_KEY("debug_sc", debug_sc, true)
 OFDM_TUNE_KEY("debug_tx", debug_tx, true)

@@ -14,6 +14,7 @@
 #include "ofdm_ctx.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <new>
 
@@ -185,7 +186,8 @@ size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // ---------------------------------------------------------------- decode(host) = ofdm_rx_decode_batch per chunk
 struct DecodeJob : PipeJob {
     ofdm_ctx *c;
-    const ofdm_fc32 *in;
+    const void *in;
+    size_t ss = sizeof(ofdm_fc32); // bytes a sample
     int64_t n_frames, stride, frame_len, n_lags, chunk;
     int32_t max_symbols;
     uint8_t *out; int64_t out_stride;
@@ -196,11 +198,12 @@ struct DecodeJob : PipeJob {
     int64_t m(int64_t k) const { return std::min(chunk, n_frames - k * chunk); }
     size_t in_bytes(int64_t k) const override {
         const int64_t last = f0(k) + m(k) == n_frames; // only the batch's last frame may end before its stride does
-        return (size_t)((m(k) - (last ? 1 : 0)) * stride + (last ? frame_len : 0)) * sizeof(ofdm_fc32);
+        return (size_t)((m(k) - (last ? 1 : 0)) * stride + (last ? frame_len : 0)) * ss;
     }
     size_t out_bytes(int64_t k) const override { return (size_t)m(k) * (24 + ob); }
-    const void *in_direct(int64_t k) const override { return pinned_in ? in + f0(k) * stride : nullptr; }
-    void fill_in(int64_t k, void *p) const override { std::memcpy(p, in + f0(k) * stride, in_bytes(k)); }
+    const void *row(int64_t k) const { return static_cast<const char *>(in) + (size_t)(f0(k) * stride) * ss; }
+    const void *in_direct(int64_t k) const override { return pinned_in ? row(k) : nullptr; }
+    void fill_in(int64_t k, void *p) const override { std::memcpy(p, row(k), in_bytes(k)); }
     int launch(int64_t k, void *d_in, void *d_out) override {
         const int64_t n = m(k);
         char *o = static_cast<char *>(d_out); // [f_delta f64 | len | status | offset i32 | metric f32 | rows]
@@ -226,10 +229,24 @@ struct DecodeJob : PipeJob {
     }
 };
 
+// ... and ofdm_rx_decode_sc16_batch per chunk (EXT-9): 4 bytes a sample over the link, the same outputs
+struct DecodeSc16Job : DecodeJob {
+    float scale;
+    int launch(int64_t k, void *d_in, void *d_out) override {
+        const int64_t n = m(k);
+        char *o = static_cast<char *>(d_out);
+        return ofdm_rx_decode_sc16_batch(c, static_cast<const ofdm_sc16 *>(d_in), n, stride, frame_len, scale, n_lags, max_symbols,
+                                         reinterpret_cast<uint8_t *>(o + 24 * n), (int64_t)ob, reinterpret_cast<int32_t *>(o + 8 * n),
+                                         reinterpret_cast<int32_t *>(o + 12 * n), reinterpret_cast<int32_t *>(o + 16 * n),
+                                         reinterpret_cast<double *>(o), reinterpret_cast<float *>(o + 20 * n));
+    }
+};
+
 // ---------------------------------------------------------------- rx_demod(host) = ofdm_rx_demod_batch per chunk (regular streams)
 struct DemodJob : PipeJob {
     ofdm_ctx *c;
-    const ofdm_fc32 *in;
+    const void *in;
+    size_t ss = sizeof(ofdm_fc32); // bytes a sample
     int64_t n_frames, stride, frame_len, chunk;
     int32_t first_symbol, syms;
     uint8_t *out; int64_t out_stride;
@@ -239,11 +256,12 @@ struct DemodJob : PipeJob {
     int64_t m(int64_t k) const { return std::min(chunk, n_frames - k * chunk); }
     size_t in_bytes(int64_t k) const override {
         const int64_t last = f0(k) + m(k) == n_frames;
-        return (size_t)((m(k) - (last ? 1 : 0)) * stride + (last ? frame_len : 0)) * sizeof(ofdm_fc32);
+        return (size_t)((m(k) - (last ? 1 : 0)) * stride + (last ? frame_len : 0)) * ss;
     }
     size_t out_bytes(int64_t k) const override { return (size_t)m(k) * nb; }
-    const void *in_direct(int64_t k) const override { return pinned_in ? in + f0(k) * stride : nullptr; }
-    void fill_in(int64_t k, void *p) const override { std::memcpy(p, in + f0(k) * stride, in_bytes(k)); }
+    const void *row(int64_t k) const { return static_cast<const char *>(in) + (size_t)(f0(k) * stride) * ss; }
+    const void *in_direct(int64_t k) const override { return pinned_in ? row(k) : nullptr; }
+    void fill_in(int64_t k, void *p) const override { std::memcpy(p, row(k), in_bytes(k)); }
     void *out_direct(int64_t k) const override { return pinned_out ? out + f0(k) * out_stride : nullptr; }
     int launch(int64_t k, void *d_in, void *d_out) override {
         return ofdm_rx_demod_batch(c, static_cast<const ofdm_fc32 *>(d_in), m(k), stride, frame_len, first_symbol, syms, nullptr, nullptr,
@@ -253,6 +271,14 @@ struct DemodJob : PipeJob {
         const uint8_t *rows = static_cast<const uint8_t *>(p);
         if ((size_t)out_stride == nb) { std::memcpy(out + f0(k) * out_stride, rows, (size_t)m(k) * nb); return; }
         for (int64_t f = 0; f < m(k); f++) std::memcpy(out + (f0(k) + f) * out_stride, rows + (size_t)f * nb, nb);
+    }
+};
+
+struct DemodSc16Job : DemodJob { // EXT-9
+    float scale;
+    int launch(int64_t k, void *d_in, void *d_out) override {
+        return ofdm_rx_demod_sc16_batch(c, static_cast<const ofdm_sc16 *>(d_in), m(k), stride, frame_len, scale, first_symbol, syms, nullptr,
+                                        nullptr, nullptr, 0, static_cast<uint8_t *>(d_out), (int64_t)nb, nullptr);
     }
 };
 
@@ -514,9 +540,10 @@ int ofdm_host_unregister(void *host) {
 }
 int ofdm_host_is_pinned(const void *host, size_t bytes) { return host_pinned(host, bytes) ? 1 : 0; }
 
-int ofdm_rx_decode_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_frames, int64_t frame_stride, int64_t frame_len, int64_t n_lags,
-                        int32_t max_symbols, uint8_t *out_host, int64_t out_stride, int32_t *out_len_host, int32_t *status_host,
-                        int32_t *offset_host, double *f_delta_host, float *metric_host, int64_t chunk_frames) {
+// the bodies of the fc32 and sc16 (EXT-9) host calls: j carries the sample size and the launch
+static int decode_host_run(ofdm_ctx *c, DecodeJob &j, const void *in_host, int64_t n_frames, int64_t frame_stride, int64_t frame_len, int64_t n_lags,
+                           int32_t max_symbols, uint8_t *out_host, int64_t out_stride, int32_t *out_len_host, int32_t *status_host,
+                           int32_t *offset_host, double *f_delta_host, float *metric_host, int64_t chunk_frames) {
     if (!c || n_frames < 0 || frame_len <= 0 || max_symbols <= 0 || frame_stride < 0) return OFDM_ERR_INVALID;
     if (n_frames && (!in_host || !out_host || !out_len_host || !status_host)) return OFDM_ERR_INVALID;
     if (n_frames > 1 && frame_stride < frame_len) return OFDM_ERR_INVALID; // rows of a host batch do not overlap
@@ -526,19 +553,34 @@ int ofdm_rx_decode_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_frames,
     if (out_stride < need) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
     DeviceGuard dev_guard(c->device);
-    DecodeJob j;
     j.c = c; j.in = in_host; j.n_frames = n_frames; j.stride = n_frames > 1 ? frame_stride : frame_len; j.frame_len = frame_len;
     j.n_lags = n_lags; j.max_symbols = max_symbols; j.out = out_host; j.out_stride = out_stride; j.out_len = out_len_host;
     j.status = status_host; j.offset = offset_host; j.fd = f_delta_host; j.metric = metric_host;
     j.ob = round_up((size_t)std::max<int64_t>(need, 4), 4);
-    j.chunk = auto_chunk(n_frames, (size_t)j.stride * sizeof(ofdm_fc32), chunk_frames);
+    j.chunk = auto_chunk(n_frames, (size_t)j.stride * j.ss, chunk_frames);
     j.n_chunks = (n_frames + j.chunk - 1) / j.chunk;
-    j.pinned_in = host_pinned(in_host, (size_t)((n_frames - 1) * j.stride + frame_len) * sizeof(ofdm_fc32));
+    j.pinned_in = host_pinned(in_host, (size_t)((n_frames - 1) * j.stride + frame_len) * j.ss);
     return run_pipe(c, j);
 }
+int ofdm_rx_decode_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_frames, int64_t frame_stride, int64_t frame_len, int64_t n_lags,
+                        int32_t max_symbols, uint8_t *out_host, int64_t out_stride, int32_t *out_len_host, int32_t *status_host,
+                        int32_t *offset_host, double *f_delta_host, float *metric_host, int64_t chunk_frames) {
+    DecodeJob j;
+    return decode_host_run(c, j, in_host, n_frames, frame_stride, frame_len, n_lags, max_symbols, out_host, out_stride, out_len_host, status_host,
+                           offset_host, f_delta_host, metric_host, chunk_frames);
+}
+int ofdm_rx_decode_sc16_host(ofdm_ctx *c, const ofdm_sc16 *in_host, int64_t n_frames, int64_t frame_stride, int64_t frame_len, float scale,
+                             int64_t n_lags, int32_t max_symbols, uint8_t *out_host, int64_t out_stride, int32_t *out_len_host,
+                             int32_t *status_host, int32_t *offset_host, double *f_delta_host, float *metric_host, int64_t chunk_frames) {
+    if (!(std::isfinite(scale) && scale > 0.f)) return OFDM_ERR_INVALID;
+    DecodeSc16Job j;
+    j.ss = sizeof(ofdm_sc16); j.scale = scale;
+    return decode_host_run(c, j, in_host, n_frames, frame_stride, frame_len, n_lags, max_symbols, out_host, out_stride, out_len_host, status_host,
+                           offset_host, f_delta_host, metric_host, chunk_frames);
+}
 
-int ofdm_rx_demod_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
-                       int32_t first_symbol, int32_t syms_per_frame, uint8_t *out_host, int64_t out_stride, int64_t chunk_frames) {
+static int demod_host_run(ofdm_ctx *c, DemodJob &j, const void *in_host, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                          int32_t first_symbol, int32_t syms_per_frame, uint8_t *out_host, int64_t out_stride, int64_t chunk_frames) {
     if (!c || n_frames < 0 || frame_len <= 0 || syms_per_frame < 0 || first_symbol < 0 || frame_stride < 0) return OFDM_ERR_INVALID;
     if (n_frames && syms_per_frame && (!in_host || !out_host)) return OFDM_ERR_INVALID;
     if (n_frames > 1 && frame_stride < frame_len) return OFDM_ERR_INVALID;
@@ -546,14 +588,25 @@ int ofdm_rx_demod_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_frames, 
     if (out_stride < nb) return OFDM_ERR_INVALID;
     if (!n_frames || !syms_per_frame) return OFDM_OK;
     DeviceGuard dev_guard(c->device);
-    DemodJob j;
     j.c = c; j.in = in_host; j.n_frames = n_frames; j.stride = n_frames > 1 ? frame_stride : frame_len; j.frame_len = frame_len;
     j.first_symbol = first_symbol; j.syms = syms_per_frame; j.out = out_host; j.out_stride = out_stride; j.nb = (size_t)nb;
-    j.chunk = auto_chunk(n_frames, (size_t)j.stride * sizeof(ofdm_fc32), chunk_frames);
+    j.chunk = auto_chunk(n_frames, (size_t)j.stride * j.ss, chunk_frames);
     j.n_chunks = (n_frames + j.chunk - 1) / j.chunk;
-    j.pinned_in = host_pinned(in_host, (size_t)((n_frames - 1) * j.stride + frame_len) * sizeof(ofdm_fc32));
+    j.pinned_in = host_pinned(in_host, (size_t)((n_frames - 1) * j.stride + frame_len) * j.ss);
     j.pinned_out = out_stride == nb && host_pinned(out_host, (size_t)(n_frames * nb));
     return run_pipe(c, j);
+}
+int ofdm_rx_demod_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                       int32_t first_symbol, int32_t syms_per_frame, uint8_t *out_host, int64_t out_stride, int64_t chunk_frames) {
+    DemodJob j;
+    return demod_host_run(c, j, in_host, n_frames, frame_stride, frame_len, first_symbol, syms_per_frame, out_host, out_stride, chunk_frames);
+}
+int ofdm_rx_demod_sc16_host(ofdm_ctx *c, const ofdm_sc16 *in_host, int64_t n_frames, int64_t frame_stride, int64_t frame_len, float scale,
+                            int32_t first_symbol, int32_t syms_per_frame, uint8_t *out_host, int64_t out_stride, int64_t chunk_frames) {
+    if (!(std::isfinite(scale) && scale > 0.f)) return OFDM_ERR_INVALID;
+    DemodSc16Job j;
+    j.ss = sizeof(ofdm_sc16); j.scale = scale;
+    return demod_host_run(c, j, in_host, n_frames, frame_stride, frame_len, first_symbol, syms_per_frame, out_host, out_stride, chunk_frames);
 }
 
 int ofdm_tx_encode_host(ofdm_ctx *c, const uint8_t *payload_host, int64_t n_frames, int64_t payload_stride, const int32_t *payload_len_host,

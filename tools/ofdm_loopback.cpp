@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <string>
 
 using namespace ofdm;
 
@@ -63,10 +64,37 @@ static bool read_fc32(const char *path, std::vector<Complex64> &x, long start, l
     return true;
 }
 
+// sc16 wire format (--sc16; UHD's --type short): little-endian int16 pairs (re, im), in PATH.sc16 next to the fc32 file.  A frame is
+// normalised to a peak of 1, so it is written at full scale (ofdm_sc16_narrow, scale 32767) and read back with x = v / 32768
+// (ofdm_sc16_widen, OFDM_SC16_DEFAULT_SCALE) -- the receiver does not care about the factor 32767 / 32768.
+static bool write_sc16(const std::string &path, const std::vector<Complex64> &x, int64_t *clipped) {
+    FILE *fh = std::fopen(path.c_str(), "wb");
+    if (!fh) return false;
+    const std::vector<ofdm_sc16> q = sc16_narrow(Context::to_fc32(x), 32767.0f, clipped);
+    std::fwrite(q.data(), sizeof(ofdm_sc16), q.size(), fh);
+    std::fclose(fh);
+    return true;
+}
+static bool read_sc16(const std::string &path, std::vector<Complex64> &x, long start, long stop) {
+    FILE *fh = std::fopen(path.c_str(), "rb");
+    if (!fh) return false;
+    std::vector<ofdm_sc16> q;
+    ofdm_sc16 v;
+    long i = 0;
+    while (std::fread(&v, sizeof(v), 1, fh) == 1) { // a trailing partial sample is dropped
+        if (i >= start && (stop < 0 || i < stop)) q.push_back(v);
+        ++i;
+    }
+    std::fclose(fh);
+    x = Context::from_fc32(sc16_widen(q));
+    return true;
+}
+
 int main(int argc, char **argv) {
     const char *corpus = "I met a traveller from an antique land, Who said: Two vast and trunkless legs of stone Stand in the desert. ";
     size_t num_bytes = 400;
     bool guard_bands = false, timing_error = false, ecc = false; // ecc: lab3c's ecc_enabled (outer RS(255,223), utils.rs:97-180)
+    bool sc16 = false; // --sc16: --transmit also writes FILE.sc16, --receive reads FILE.sc16 instead of FILE (EXT-9)
     bool fcs = false; // --fcs: the CRC-32 frame check inside encode / decode (ecc = OFDM_ECC_FCS): exactly the payload back, or an error
     ModulationScheme modulation = ModulationScheme::Qpsk;
     const char *tx_file = nullptr, *rx_file = nullptr; // examples/lab3c.rs: --transmit f / --receive f [--start a --stop b]
@@ -77,6 +105,7 @@ int main(int argc, char **argv) {
         else if (!std::strcmp(argv[i], "--guard")) guard_bands = true;
         else if (!std::strcmp(argv[i], "--ecc")) ecc = true;
         else if (!std::strcmp(argv[i], "--fcs")) fcs = true;
+        else if (!std::strcmp(argv[i], "--sc16")) sc16 = true;
         else if (!std::strcmp(argv[i], "--bpsk")) modulation = ModulationScheme::Bpsk;
         else if (!std::strcmp(argv[i], "--qam64")) modulation = ModulationScheme::Qam64;
         else if (!std::strcmp(argv[i], "--bytes") && i + 1 < argc) num_bytes = (size_t)std::atol(argv[++i]);
@@ -144,7 +173,7 @@ int main(int argc, char **argv) {
         }
         if (rx_file) { // decode a stored capture (or a slice of it)
             std::vector<Complex64> cap;
-            if (!read_fc32(rx_file, cap, start, stop)) { std::printf("cannot read %s\n", rx_file); return 4; }
+            if (!(sc16 ? read_sc16(std::string(rx_file) + ".sc16", cap, start, stop) : read_fc32(rx_file, cap, start, stop))) { std::printf("cannot read %s%s\n", rx_file, sc16 ? ".sc16" : ""); return 4; }
             auto received = finish(decode(std::move(cap), guard_bands, modulation, fcs));
             std::printf("received %zu bytes\n%.*s\n", received.size(), (int)std::min<size_t>(received.size(), 100), (const char *)received.data());
             if (received.size() != text.size()) return 2;
@@ -154,6 +183,11 @@ int main(int argc, char **argv) {
         if (tx_file) { // write the frame for tx_samples_from_file
             if (!write_fc32(tx_file, tx)) { std::printf("cannot write %s\n", tx_file); return 4; }
             std::printf("wrote %zu samples (%zu bytes) to %s\n", tx.size(), tx.size() * 8, tx_file);
+            if (sc16) {
+                int64_t clipped = 0;
+                if (!write_sc16(std::string(tx_file) + ".sc16", tx, &clipped)) { std::printf("cannot write %s.sc16\n", tx_file); return 4; }
+                std::printf("wrote %zu samples (%zu bytes, %lld clipped components) to %s.sc16\n", tx.size(), tx.size() * 4, (long long)clipped, tx_file);
+            }
             return 0;
         }
         double fd = 0;
