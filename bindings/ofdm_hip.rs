@@ -272,6 +272,18 @@ extern "C" {
                                     n_lags: i64, max_symbols: i32, out_host: *mut u8, out_stride: i64, out_len_host: *mut i32,
                                     status_host: *mut i32, offset_host: *mut i32, f_delta_host: *mut f64, metric_host: *mut f32,
                                     chunk_frames: i64) -> c_int;
+    // EXT-10: sc16 transmit output (clipped_*: optional, int32 per frame) and sc16 long captures
+    pub fn ofdm_tx_encode_sc16_batch(ctx: *mut ofdm_ctx, payload_dev: *const u8, n_frames: i64, payload_stride: i64, payload_len_dev: *const i32,
+                                     payload_bytes: i32, scale: f32, out_dev: *mut ofdm_sc16, out_stride: i64, clipped_dev: *mut i32) -> c_int;
+    pub fn ofdm_tx_encode_sc16_host(ctx: *mut ofdm_ctx, payload_host: *const u8, n_frames: i64, payload_stride: i64, payload_len_host: *const i32,
+                                    payload_bytes: i32, scale: f32, out_host: *mut ofdm_sc16, out_stride: i64, clipped_host: *mut i32,
+                                    chunk_frames: i64) -> c_int;
+    pub fn ofdm_rx_decode_long_sc16(ctx: *mut ofdm_ctx, in_dev: *const ofdm_sc16, n_samples: i64, scale: f32, lag_lo: i64, lag_hi: i64,
+                                    d_hat_known: i64, max_symbols: i32, out_dev: *mut u8, out_cap: i64, out_len: *mut i32, status: *mut i32,
+                                    offset: *mut i64, f_delta: *mut f64, metric: *mut f32) -> c_int;
+    pub fn ofdm_rx_decode_long_sc16_host(ctx: *mut ofdm_ctx, in_host: *const ofdm_sc16, n_samples: i64, scale: f32, max_symbols: i32,
+                                         out_host: *mut u8, out_cap: i64, out_len: *mut i32, status: *mut i32, offset: *mut i64,
+                                         f_delta: *mut f64, metric: *mut f32) -> c_int;
     pub fn ofdm_timer_start(ctx: *mut ofdm_ctx) -> c_int;
     pub fn ofdm_timer_stop_ms(ctx: *mut ofdm_ctx, elapsed_ms: *mut f32) -> c_int;
 }

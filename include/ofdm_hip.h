@@ -851,6 +851,41 @@ int ofdm_rx_decode_sc16_host(ofdm_ctx *ctx, const ofdm_sc16 *in_host, int64_t n_
                              int32_t *out_len_host, int32_t *status_host, int32_t *offset_host, double *f_delta_host,
                              float *metric_host, int64_t chunk_frames);
 
+/* ------------------------------------------------------------------ sc16 transmit output and sc16 long captures (EXT-10)
+ * ofdm_tx_encode_batch writing sc16 for a DAC: row f of out_dev is, bit for bit, ofdm_sc16_narrow(frame f of ofdm_tx_encode_batch on the
+ * same arguments, scale) -- every component is formed exactly as the fc32 entry point forms it and then narrowed by the rule above --
+ * and clipped_dev[f] (optional, int32 per frame) is that function's count for the frame.  Samples of an output row behind
+ * ofdm_frame_samples(payload_bytes) are not written.  Every ecc, every N, ragged payload_len.
+ * A NORMALISED FRAME IS NOT BOUNDED BY +-1.  normalize (src/transmitter.rs:183-194) divides by the SIGNED maximum of the frame's
+ * components: the positive peak is 1, the negative peak is whatever it is -- about -2 for BPSK and QPSK without guard bands (the
+ * reference's default shape), where EVERY frame has a component that clips at scale 32767; about -1.2 for 16-QAM with guard bands; inside
+ * +-1 for 64-QAM and 256-QAM with guard bands.  clipped_dev is how a caller learns that its scale is too large for the frames it sends;
+ * the library does not choose a scale.
+ * Argument rules: those of ofdm_tx_encode_batch, and scale finite and > 0 (OFDM_ERR_INVALID); out_dev needs 4-byte alignment only.
+ * N = 64 frames of 1 .. 56 data symbols into a 16-byte aligned out_dev with out_stride a multiple of 4 samples run k_txframe64_sc16,
+ * which narrows in its store phase (4 bytes a sample written, nothing else).  Everything else -- longer frames, N != 64, an unaligned
+ * output -- runs ofdm_tx_encode_batch's own kernels on a chunk of frames (about 48 MB of fc32 samples) into a workspace and then
+ * k_sc16_narrow into the caller's rows. */
+int ofdm_tx_encode_sc16_batch(ofdm_ctx *ctx, const uint8_t *payload_dev, int64_t n_frames, int64_t payload_stride,
+                              const int32_t *payload_len_dev, int32_t payload_bytes, float scale,
+                              ofdm_sc16 *out_dev, int64_t out_stride, int32_t *clipped_dev /* optional, per frame */);
+/* The same on host buffers (see "host buffers"; ofdm_tx_encode_host's rules): half the D2H bytes of the fc32 call.  clipped_host
+ * (optional): int32 per frame, brought back with each chunk's frames. */
+int ofdm_tx_encode_sc16_host(ofdm_ctx *ctx, const uint8_t *payload_host, int64_t n_frames, int64_t payload_stride,
+                             const int32_t *payload_len_host, int32_t payload_bytes, float scale,
+                             ofdm_sc16 *out_host, int64_t out_stride, int32_t *clipped_host /* optional */, int64_t chunk_frames);
+/* ofdm_rx_decode_long / ofdm_rx_decode_long_host (see "one long capture") on an sc16 capture: every output -- status, length, offset,
+ * the bits of f_delta and metric, the bytes -- equals the fc32 call on ofdm_sc16_widen(capture, scale), for every ecc, chest_mode,
+ * cfo_mode, sync_mode, lag range and d_hat_known.  in_dev is 4-byte aligned.  The capture is widened on the device by k_sc16_widen into
+ * a buffer the context keeps (8 bytes a sample), and the chain runs on that: the host call uploads 4 bytes a sample instead of 8, and
+ * the device then holds 12 bytes a sample (the int16 capture and its widened copy) where the fc32 call holds 8. */
+int ofdm_rx_decode_long_sc16(ofdm_ctx *ctx, const ofdm_sc16 *in_dev, int64_t n_samples, float scale, int64_t lag_lo, int64_t lag_hi,
+                             int64_t d_hat_known, int32_t max_symbols, uint8_t *out_dev, int64_t out_cap, int32_t *out_len,
+                             int32_t *status, int64_t *offset, double *f_delta, float *metric);
+int ofdm_rx_decode_long_sc16_host(ofdm_ctx *ctx, const ofdm_sc16 *in_host, int64_t n_samples, float scale, int32_t max_symbols,
+                                  uint8_t *out_host, int64_t out_cap, int32_t *out_len, int32_t *status, int64_t *offset,
+                                  double *f_delta, float *metric);
+
 /* ------------------------------------------------------------------ loop-back test bench
  * channel (src/channel.rs:33-74), per frame:
  *     y = convolve(tx, CHANNEL)                          tx_len + 63 samples (CHANNEL: the 64 taps of channel.rs:26-31)

@@ -93,11 +93,36 @@ class Context {
                                   host.data(), n, 0), "ofdm_tx_encode_host");
         return from_fc32(host);
     }
+    // EXT-10: the same frame as sc16 for a DAC (ofdm_tx_encode_sc16_host): ofdm_sc16_narrow(encode(data), scale), made on the device and
+    // brought back at 4 bytes a sample.  *clipped (optional): components that clipped -- a normalised frame's negative peak is not
+    // bounded by -1 (include/ofdm_hip.h), so a count above 0 means the scale is too large for this frame.
+    std::vector<ofdm_sc16> encode_sc16(const std::vector<uint8_t> &data, float scale, int32_t *clipped = nullptr) {
+        const int64_t n = ofdm_frame_samples(ctx_, (int64_t)data.size());
+        std::vector<ofdm_sc16> host((size_t)n);
+        const uint8_t none = 0;
+        check(ofdm_tx_encode_sc16_host(ctx_, data.empty() ? &none : data.data(), 1, (int64_t)data.size(), nullptr, (int32_t)data.size(), scale,
+                                       host.data(), n, clipped, 0), "ofdm_tx_encode_sc16_host");
+        return host;
+    }
     // decode (src/receiver.rs:9-96) of ONE capture of any length -- the 2 M-sample buffers of examples/jetson_rx.rs:15-17,84-86
     // included: ofdm_rx_decode_long_host searches a long capture as a batch of overlapping slices.  Takes the samples by value
     // like the reference (which consumes its Vec).  max_symbols <= 0: every symbol up to the capture's end, as the reference.
     struct Decoded { std::vector<uint8_t> bytes; int32_t status = 0; int64_t offset = 0; double f_delta = 0.0; float metric = 0.f; };
     Decoded decode_capture(const ofdm_fc32 *fc, int64_t n, int32_t max_symbols = 0) {
+        return decode_capture_as(n, max_symbols, [&](int32_t ms, Decoded &r, int64_t ob, int32_t *len) {
+            check(ofdm_rx_decode_long_host(ctx_, fc, n, ms, r.bytes.data(), ob, len, &r.status, &r.offset, &r.f_delta, &r.metric),
+                  "ofdm_rx_decode_long_host");
+        });
+    }
+    // EXT-10: the same of an sc16 capture as a radio delivers it (ofdm_rx_decode_long_sc16_host): half the bytes over the link, the
+    // result of decode_capture on ofdm_sc16_widen(capture, scale)
+    Decoded decode_capture_sc16(const ofdm_sc16 *sc, int64_t n, int32_t max_symbols = 0, float scale = OFDM_SC16_DEFAULT_SCALE) {
+        return decode_capture_as(n, max_symbols, [&](int32_t ms, Decoded &r, int64_t ob, int32_t *len) {
+            check(ofdm_rx_decode_long_sc16_host(ctx_, sc, n, scale, ms, r.bytes.data(), ob, len, &r.status, &r.offset, &r.f_delta, &r.metric),
+                  "ofdm_rx_decode_long_sc16_host");
+        });
+    }
+    template <class Call> Decoded decode_capture_as(int64_t n, int32_t max_symbols, Call &&call) { // the row both calls size the same way
         const int S = symbol_len();
         if (max_symbols <= 0) max_symbols = (int32_t)std::max<int64_t>((n + S - 1) / S - 10, 1);
         int64_t ob = std::max<int64_t>((int64_t)max_symbols * ofdm_bytes_per_symbol(ctx_), 4);
@@ -106,14 +131,19 @@ class Context {
         Decoded r;
         r.bytes.resize((size_t)ob);
         int32_t len = 0;
-        check(ofdm_rx_decode_long_host(ctx_, fc, n, max_symbols, r.bytes.data(), ob, &len, &r.status, &r.offset, &r.f_delta, &r.metric),
-              "ofdm_rx_decode_long_host");
+        call(max_symbols, r, ob, &len);
         r.bytes.resize(r.status == OFDM_FRAME_OK ? (size_t)len : 0);
         return r;
     }
     std::vector<uint8_t> decode(std::vector<Complex64> samples, int32_t max_symbols = 0) {
         const auto fc = to_fc32(samples);
-        Decoded r = decode_capture(fc.data(), (int64_t)fc.size(), max_symbols);
+        return bytes_or_throw(decode_capture(fc.data(), (int64_t)fc.size(), max_symbols));
+    }
+    // EXT-10: decode of an sc16 capture (x = int16 * scale, widened on the device)
+    std::vector<uint8_t> decode_sc16(const std::vector<ofdm_sc16> &samples, int32_t max_symbols = 0, float scale = OFDM_SC16_DEFAULT_SCALE) {
+        return bytes_or_throw(decode_capture_sc16(samples.data(), (int64_t)samples.size(), max_symbols, scale));
+    }
+    static std::vector<uint8_t> bytes_or_throw(Decoded r) { // the reference's Err / None as exceptions
         if (r.status == OFDM_FRAME_SHORT) throw Error("Input not long enough, bailing early"); // src/receiver.rs:27-29
         if (r.status == OFDM_FRAME_UNCORRECTABLE) throw Error("uncorrectable block"); // RS: the reference returns None; LDPC: a code word did not converge
         if (r.status == OFDM_FRAME_FCS) throw Error("frame check failed: the payload is damaged"); // OFDM_ECC_FCS + mode

@@ -136,6 +136,12 @@ SIGNATURES = {
     "ofdm_rx_decode_sc16_batch": (C.c_int, [vp, vp, i64, i64, i64, C.c_float, i64, i32, vp, i64, vp, vp, vp, vp, vp]),
     "ofdm_rx_demod_sc16_host": (C.c_int, [vp, vp, i64, i64, i64, C.c_float, i32, i32, vp, i64, i64]),
     "ofdm_rx_decode_sc16_host": (C.c_int, [vp, vp, i64, i64, i64, C.c_float, i64, i32, vp, i64, vp, vp, vp, vp, vp, i64]),
+    "ofdm_tx_encode_sc16_batch": (C.c_int, [vp, vp, i64, i64, vp, i32, C.c_float, vp, i64, vp]),
+    "ofdm_tx_encode_sc16_host": (C.c_int, [vp, vp, i64, i64, vp, i32, C.c_float, vp, i64, vp, i64]),
+    "ofdm_rx_decode_long_sc16": (C.c_int, [vp, vp, i64, C.c_float, i64, i64, i64, i32, vp, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64),
+                                           C.POINTER(C.c_double), C.POINTER(C.c_float)]),
+    "ofdm_rx_decode_long_sc16_host": (C.c_int, [vp, vp, i64, C.c_float, i32, vp, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64),
+                                                C.POINTER(C.c_double), C.POINTER(C.c_float)]),
     "ofdm_hbm_read_probe": (C.c_int, [vp, vp, i64, i32]),
     "ofdm_timer_start": (C.c_int, [vp]),
     "ofdm_timer_stop_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),

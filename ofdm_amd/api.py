@@ -799,6 +799,68 @@ class Context:
                                                   out.shape[1], chunk_frames), "rx_demod_sc16_host")
         return out
 
+    # ---------------------------------------------------------------- EXT-10: sc16 output, sc16 long captures
+    def encode_batch_sc16(self, payload: torch.Tensor, scale: float, out: Optional[torch.Tensor] = None,
+                          lens: Optional[torch.Tensor] = None, want_clipped: bool = False):
+        """ofdm_tx_encode_sc16_batch: encode_batch writing int16 [n_frames, frame, 2] = sc16_narrow(encode_batch(...), scale) row by row
+        (out: rows may be longer, what lies behind the frame is not written).  want_clipped: also the clipped components per frame
+        (int32 [n_frames]); a normalised frame's negative peak is not bounded by -1, so a count above 0 says the scale is too large."""
+        payload = self._u8(payload)
+        n, nbytes = payload.shape
+        frame = self.frame_samples(nbytes)
+        out = self.empty((n, frame, 2), torch.int16) if out is None else out
+        o3 = self._sc16(out)
+        if o3.shape[0] != n or o3.shape[1] < frame:
+            raise OfdmError("encode_batch_sc16: out must hold n_frames rows of at least frame_samples(payload_bytes) samples")
+        if lens is not None:
+            lens = lens.to(device=self.device, dtype=torch.int32).contiguous()
+            assert lens.numel() == n
+        clipped = self.empty((n,), torch.int32) if want_clipped else None
+        self._ck(self.lib.ofdm_tx_encode_sc16_batch(self.h, _dev(payload), n, nbytes, _dev(lens), nbytes, scale, _dev(o3),
+                                                    self._rows(o3)[2], _dev(clipped)), "tx_encode_sc16")
+        return (out, clipped) if want_clipped else out
+
+    def encode_host_sc16(self, payload: np.ndarray, scale: float, lens: Optional[np.ndarray] = None, chunk_frames: int = 0,
+                         out: Optional[np.ndarray] = None, want_clipped: bool = False):
+        """ofdm_tx_encode_sc16_host: encode_host writing int16 [n_frames, frame (or more), 2] (half the D2H bytes)."""
+        pay = np.ascontiguousarray(payload, dtype=np.uint8)
+        n, nbytes = pay.shape
+        frame = self.frame_samples(nbytes)
+        out = np.zeros((n, frame, 2), np.int16) if out is None else out
+        if out.dtype != np.int16 or out.ndim != 3 or out.shape[2] != 2 or not out.flags.c_contiguous or out.shape[0] != n:
+            raise OfdmError("encode_host_sc16: out must be a contiguous int16 array [n_frames, samples, 2]")
+        if lens is not None:
+            lens = np.ascontiguousarray(lens, dtype=np.int32)
+        clipped = np.zeros(n, np.int32) if want_clipped else None
+        self._ck(self.lib.ofdm_tx_encode_sc16_host(self.h, _host(pay), n, nbytes, _host(lens), nbytes, scale, _host(out), out.shape[1],
+                                                   _host(clipped), chunk_frames), "tx_encode_sc16_host")
+        return (out, clipped) if want_clipped else out
+
+    def decode_long_sc16(self, capture: torch.Tensor, max_symbols: int, scale: float = SC16_DEFAULT_SCALE, lag_lo: int = 0, lag_hi: int = 0,
+                         d_hat_known: int = -1):
+        """ofdm_rx_decode_long_sc16: decode_long of ONE int16 capture [n, 2] on the device, widened there with `scale`."""
+        t = self._sc16(capture)
+        if t.shape[0] != 1:
+            raise OfdmError("decode_long_sc16: expected one capture [n, 2]")
+        ob = self.decode_row_bytes(max_symbols)
+        out = self.empty((ob,), torch.uint8)
+        ln, st, off, fd, m = C.c_int32(), C.c_int32(), C.c_int64(), C.c_double(), C.c_float()
+        self._ck(self.lib.ofdm_rx_decode_long_sc16(self.h, _dev(t), t.shape[1], scale, lag_lo, lag_hi, d_hat_known, max_symbols, _dev(out),
+                                                   ob, C.byref(ln), C.byref(st), C.byref(off), C.byref(fd), C.byref(m)), "rx_decode_long_sc16")
+        return {"bytes": out, "len": int(ln.value), "status": int(st.value), "offset": int(off.value), "f_delta": float(fd.value),
+                "metric": float(m.value)}
+
+    def decode_long_host_sc16(self, capture: np.ndarray, max_symbols: int, scale: float = SC16_DEFAULT_SCALE):
+        """ofdm_rx_decode_long_sc16_host: the same from a host array of int16 [n, 2] (pinned_empty() memory is DMA-ed in place)."""
+        x = _sc16_host(capture, "decode_long_host_sc16").reshape(-1, 2)
+        ob = self.decode_row_bytes(max_symbols)
+        out = np.zeros(ob, np.uint8)
+        ln, st, off, fd, m = C.c_int32(), C.c_int32(), C.c_int64(), C.c_double(), C.c_float()
+        self._ck(self.lib.ofdm_rx_decode_long_sc16_host(self.h, _host(x), x.shape[0], scale, max_symbols, _host(out), ob, C.byref(ln),
+                                                        C.byref(st), C.byref(off), C.byref(fd), C.byref(m)), "rx_decode_long_sc16_host")
+        return {"bytes": out, "len": int(ln.value), "status": int(st.value), "offset": int(off.value), "f_delta": float(fd.value),
+                "metric": float(m.value)}
+
     def rx_llr(self, frames: torch.Tensor, syms_per_frame: int, first_symbol: int = 0, offset: Optional[torch.Tensor] = None,
                f_delta: Optional[torch.Tensor] = None, hk: Optional[torch.Tensor] = None, frame_len: Optional[int] = None,
                scale: float = SOFT_LLR_SCALE, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1138,12 +1200,17 @@ _FRAME_ERRORS = {FRAME_NOSYNC: "no preamble found", FRAME_HEADER: "no length hea
 
 
 def encode(data: bytes, guard_bands: Optional[bool] = None, modulation: Optional[int] = None, n_fft: int = 64,
-           ecc: int = ECC_NONE, fcs: bool = False, **kw) -> np.ndarray:
+           ecc: int = ECC_NONE, fcs: bool = False, sc16_scale: Optional[float] = None, **kw) -> np.ndarray:
     """`ofdm::encode!(data, guard_bands, modulation)` (src/transmitter.rs:10-58): bytes -> Vec<Complex64>.
-    Defaults as the reference: guard_bands=false, modulation=Bpsk.  fcs: the CRC-32 frame check around the payload (ecc + ECC_FCS)."""
+    Defaults as the reference: guard_bands=false, modulation=Bpsk.  fcs: the CRC-32 frame check around the payload (ecc + ECC_FCS).
+    sc16_scale: the frame as sc16 for a DAC (EXT-10) -- an int16 array [n, 2] = sc16_narrow(frame, sc16_scale)[0], made on the device."""
     ctx = _ctx(n_fft, BPSK if modulation is None else modulation, bool(guard_bands), _with_fcs(ecc, fcs), **kw)
     pay = torch.frombuffer(bytearray(data) if len(data) else bytearray(1), dtype=torch.uint8)[: len(data)]
     pay = pay.reshape(1, len(data)).to(ctx.device)
+    if sc16_scale is not None:
+        q = ctx.encode_batch_sc16(pay, sc16_scale)
+        ctx.synchronize()
+        return q[0].cpu().numpy()
     frames = ctx.encode_batch(pay)
     ctx.synchronize()
     return frames[0].cpu().numpy().astype(np.complex128)
@@ -1182,19 +1249,29 @@ def decode(samples, guard_bands: Optional[bool] = None, modulation: Optional[int
 
 
 def decode_long(samples, guard_bands: Optional[bool] = None, modulation: Optional[int] = None, n_fft: int = 64,
-                ecc: int = ECC_NONE, world: int = 1, max_symbols: Optional[int] = None, device: int = 0, fcs: bool = False, **sync):
+                ecc: int = ECC_NONE, world: int = 1, max_symbols: Optional[int] = None, device: int = 0, fcs: bool = False,
+                scale: float = SC16_DEFAULT_SCALE, **sync):
     """`ofdm::decode!` of ONE long capture (the 2 M-sample buffers of examples/jetson_rx.rs:15-17,48-49,84-86) on the HIP path.
     world > 1 rehearses the multi-GPU halo split on one device: `world` contexts, context r searching the lags
     dist.lag_ranges(...)[r] of the shared capture (ofdm_sc_correlate_long), the lowest range with a detection wins
     (dist.merge_first_detection), and that context runs the receive chain (ofdm_rx_decode_long with the merged detection).
     Returns dict(bytes, len, status, offset, f_delta, metric); raises DecodeError where the reference returns Err, and, with fcs (the
-    frame was sent with encode(..., fcs=True)), when the frame check fails."""
+    frame was sent with encode(..., fcs=True)), when the frame check fails.  An int16 array of shape [n, 2] is an sc16 capture (EXT-10),
+    widened with `scale` on the device (ofdm_rx_decode_long_sc16; world = 1 only)."""
     from . import dist
 
     mod = BPSK if modulation is None else modulation
     ecc = _with_fcs(ecc, fcs)
     ctxs = [_ctx(n_fft, mod, bool(guard_bands), ecc, device=device, _replica=r, **sync) for r in range(max(world, 1))]
     c0 = ctxs[0]
+    sc16 = samples.dtype == torch.int16 if isinstance(samples, torch.Tensor) else np.asarray(samples).dtype == np.int16
+    if sc16:
+        if world > 1:
+            raise OfdmError("decode_long: an sc16 capture is decoded by one context (world = 1)")
+        x = samples if isinstance(samples, torch.Tensor) else c0.to_device(_sc16_host(samples, "decode_long"))
+        if max_symbols is None:
+            max_symbols = max((x.shape[-2] + c0.S - 1) // c0.S - 10, 1)
+        return _long_result(c0.decode_long_sc16(x, max_symbols, scale=scale), fcs)
     x = samples if isinstance(samples, torch.Tensor) else c0.to_device(np.asarray(samples))
     x = x.reshape(-1)
     if max_symbols is None:
@@ -1211,6 +1288,11 @@ def decode_long(samples, guard_bands: Optional[bool] = None, modulation: Optiona
         winner = next((c for c, det in zip(ctxs, dets) if det[2] >= 0), c0)
         res = winner.decode_long(x, max_symbols, d_hat_known=d) if d >= 0 else {
             "bytes": c0.empty((4,), torch.uint8), "len": 0, "status": FRAME_NOSYNC, "offset": 0, "f_delta": 0.0, "metric": 0.0}
+    return _long_result(res, fcs)
+
+
+def _long_result(res: dict, fcs: bool) -> dict:
+    """decode_long's result, or the DecodeError the reference's Err stands for"""
     if res["status"] == FRAME_SHORT:
         raise DecodeError("Input not long enough, bailing early")
     if fcs and res["status"] == FRAME_FCS:

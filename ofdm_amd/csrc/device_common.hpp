@@ -584,5 +584,17 @@ __device__ __forceinline__ float sc16_mul(float x, float scale) {
 __device__ __forceinline__ cf sc16_widen1(unsigned d, float scale) {
     return make_float2(sc16_mul((float)(short)(d & 0xFFFFu), scale), sc16_mul((float)((int)d >> 16), scale));
 }
+// fc32 -> sc16 (k_sc16_narrow, k_txframe64_sc16).  One component: the int16 in the low 16 bits, 1 added to *clipped when it counts
+// as clipped
+__device__ __forceinline__ unsigned sc16_narrow1(float x, float scale, int *clipped) {
+    const float r = rintf(sc16_mul(x, scale)); // ties to even; not finite stays not finite
+    const bool in_range = fabsf(r) <= 32767.f; // false for NaN
+    *clipped += in_range ? 0 : 1;
+    const float q = r != r ? 0.f : fminf(fmaxf(r, -32767.f), 32767.f);
+    return (unsigned)(int)q & 0xFFFFu;
+}
+__device__ __forceinline__ unsigned sc16_narrow2(float2 z, float scale, int *clipped) {
+    return sc16_narrow1(z.x, scale, clipped) | (sc16_narrow1(z.y, scale, clipped) << 16);
+}
 
 } // namespace ofdm

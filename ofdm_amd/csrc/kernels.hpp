@@ -48,7 +48,9 @@ struct Tuning {
     int soft_chunk_frames = 0;     // OFDM_ECC_HAMMING74_SOFT / OFDM_ECC_CONV_K7 decode: frames per k_sym<llr> + k_rx_finish_soft / k_viterbi_k7 step (0 = the LLR workspace's 256 MB bound)
     int fcs_bitserial = 0;         // k_fcs_wrap / k_fcs_check: every lane reduces its chunk bit by bit in registers instead of through the slice-by-4 tables in LDS (A/B)
     int no_demod64_sc16 = 0;       // EXT-9: ofdm_rx_demod_sc16_batch at N = 64 widens into the workspace and runs the fc32 path instead of k_demod64_sc16 (A/B)
-    int sc16_chunk_frames = 0;     // EXT-9: frames per k_sc16_widen + fc32 chain step of the sc16 entry points (0 = about 48 MB of widened samples)
+    int sc16_chunk_frames = 0;     // EXT-9 / EXT-10: frames per k_sc16_widen + fc32 chain step of the sc16 receive entry points and per fc32 encode + k_sc16_narrow
+                                   // step of ofdm_tx_encode_sc16_batch's two-pass path (0 = about 48 MB of fc32 samples)
+    int no_txframe64_sc16 = 0;     // EXT-10: ofdm_tx_encode_sc16_batch at N = 64 encodes fc32 frames into the workspace and narrows them instead of k_txframe64_sc16 (A/B)
 };
 inline const Tuning &tuning_or_default(const Tuning *t) { static const Tuning d; return t ? *t : d; }
 
@@ -227,6 +229,13 @@ hipError_t run_rxframe64(const SymParams &p, float2 *hk_out, hipStream_t st, int
                          const int32_t *frame_count = nullptr, int32_t *cut_ws = nullptr);
 // fused encode for N = 64 (map + IFFT + CP + header + normalise, one HBM pass); hipErrorNotSupported outside its envelope
 hipError_t run_txframe64(const SymParams &p, const float2 *header, float header_max, hipStream_t st, int num_cu);
+// EXT-10: the same frame loop storing sc16 samples (kernels_n64_tx_sc16.hip): row f = ofdm_sc16_narrow(frame f of run_txframe64, scale),
+// clipped (optional) = its count per frame.  p.out / p.out_stride_s are not read.  run_txframe64's envelope with out16 16-byte aligned
+// and out_stride (samples) a multiple of 4 -- txframe64_sc16_takes, which the caller asks before it codes the rows; outside it the
+// caller encodes fc32 frames and runs k_sc16_narrow
+bool txframe64_sc16_takes(int n_sym, const void *out16, long long out_stride);
+hipError_t run_txframe64_sc16(const SymParams &p, const float2 *header, float header_max, uint32_t *out16, long long out_stride, float scale,
+                              int32_t *clipped, hipStream_t st, int num_cu);
 
 hipError_t run_fft(int n, const SymParams &p, bool inverse, hipStream_t st, int num_cu);
 hipError_t run_ifft_cp(int n, const SymParams &p, hipStream_t st, int num_cu);

@@ -14,18 +14,7 @@ namespace ofdm {
 
 constexpr int kSc16Tile = 1024; // samples per workgroup step
 
-// one component: the int16 in the low 16 bits, 1 added to *clipped when it counts as clipped
-__device__ __forceinline__ unsigned sc16_narrow1(float x, float scale, int *clipped) {
-    const float r = rintf(sc16_mul(x, scale)); // ties to even; not finite stays not finite
-    const bool in_range = fabsf(r) <= 32767.f; // false for NaN
-    *clipped += in_range ? 0 : 1;
-    const float q = r != r ? 0.f : fminf(fmaxf(r, -32767.f), 32767.f);
-    return (unsigned)(int)q & 0xFFFFu;
-}
-__device__ __forceinline__ unsigned sc16_narrow2(float2 z, float scale, int *clipped) {
-    return sc16_narrow1(z.x, scale, clipped) | (sc16_narrow1(z.y, scale, clipped) << 16);
-}
-
+// (sc16_narrow1 / sc16_narrow2, the rule of one component and of one sample, are in device_common.hpp: k_txframe64_sc16 uses them too)
 struct Sc16Launch {
     Sc16Params p;
     long long units = 0, tiles_per_row = 1;

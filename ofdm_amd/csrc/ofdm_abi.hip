@@ -1253,21 +1253,24 @@ int ofdm_llr_combine_batch(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, int
 }
 
 // ------------------------------------------------------------------ pipelines
-int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, int64_t payload_stride,
-                         const int32_t *payload_len, int32_t payload_bytes, ofdm_fc32 *out, int64_t out_stride) {
+// The argument rules ofdm_tx_encode_batch and ofdm_tx_encode_sc16_batch share; *frame = ofdm_frame_samples(payload_bytes)
+static int tx_encode_check(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, int64_t payload_stride, int32_t payload_bytes, const void *out,
+                           int64_t out_stride, int64_t *frame) {
     if (!c || n_frames < 0 || payload_bytes < 0 || payload_stride < 0) return OFDM_ERR_INVALID;
     if (n_frames && (!out || (payload_bytes && !payload))) return OFDM_ERR_INVALID;
     if (n_frames > 1 && payload_stride < payload_bytes) return OFDM_ERR_INVALID; // rows are prefetched for payload_bytes (include/ofdm_hip.h)
+    if (c->mode.has(kLayerFcs) && payload_bytes > 0x7fffffff - OFDM_FCS_OVERHEAD) return OFDM_ERR_UNSUPPORTED;
+    *frame = ofdm_frame_samples(c, payload_bytes);
+    return out_stride < *frame ? OFDM_ERR_INVALID : OFDM_OK;
+}
+// The rows the frame kernels map: the caller's payload rows, or what the coding layers made of them
+struct TxRows { const uint8_t *src; int64_t stride; const int32_t *len; int32_t bytes; };
+// The outer layers (kOuter[...], outside-in) and the inner code (conv / LDPC / Hamming) of the context's mode over n_frames payload rows,
+// each into its named workspace.  Shared by the fc32 and the sc16 (EXT-10) encode.
+static int tx_code_layers(ofdm_ctx *c, int64_t n_frames, TxRows &r) {
     const ModePlan &m = c->mode;
-    if (m.has(kLayerFcs) && payload_bytes > 0x7fffffff - OFDM_FCS_OVERHEAD) return OFDM_ERR_UNSUPPORTED;
-    const int64_t frame = ofdm_frame_samples(c, payload_bytes);
-    if (out_stride < frame) return OFDM_ERR_INVALID;
-    if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
-    const int S = c->S();
-    const uint8_t *src = payload; int64_t src_stride = payload_stride; const int32_t *src_len = payload_len;
-    int32_t src_bytes = payload_bytes;
+    const uint8_t *src = r.src; int64_t src_stride = r.stride; const int32_t *src_len = r.len;
+    int32_t src_bytes = r.bytes;
     int rc;
     for (int i = 0; i < m.n_outer; i++) { // outside-in: the next layer's frame of this layer's rows
         const OuterStage &s = kOuter[m.outer[i]];
@@ -1306,10 +1309,25 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
         src = (const uint8_t *)cw; src_stride = coded; src_len = src_len ? (const int32_t *)cl : nullptr;
         src_bytes = (int32_t)coded;
     }
+    r = TxRows{src, src_stride, src_len, src_bytes};
+    return OFDM_OK;
+}
+// the frame kernels' arguments for coded rows r of frames laid out for payload_bytes
+static SymParams tx_frame_params(ofdm_ctx *c, const TxRows &r, int64_t n_frames, int32_t payload_bytes) {
     SymParams p = base_params(c);
     p.n_frames = n_frames; p.syms_per_frame = (int)ofdm_data_symbols(c, payload_bytes);
-    p.payload = src; p.payload_stride = src_stride; p.payload_len = src_len; p.payload_bytes = src_bytes;
-    p.out = reinterpret_cast<float2 *>(out); p.out_stride_s = out_stride;
+    p.payload = r.src; p.payload_stride = r.stride; p.payload_len = r.len; p.payload_bytes = r.bytes;
+    return p;
+}
+// ofdm_tx_encode_batch behind its argument checks: the coding layers, then the frames (the trace is appended to)
+static int tx_encode_fc32(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, int64_t payload_stride, const int32_t *payload_len,
+                          int32_t payload_bytes, float2 *out, int64_t out_stride, int64_t frame) {
+    TxRows r{payload, payload_stride, payload_len, payload_bytes};
+    int rc;
+    if ((rc = tx_code_layers(c, n_frames, r))) return rc;
+    const int S = c->S();
+    SymParams p = tx_frame_params(c, r, n_frames, payload_bytes);
+    p.out = out; p.out_stride_s = out_stride;
     // one workgroup per frame, frame built in LDS, single pass over HBM (kernels_n64.hip)
     if (c->prm.n_fft == 64) FAST_PATH(c, c->tune.no_txframe64, run_txframe64(p, c->d_header, c->header_max, c->stream, c->num_cu));
     // R x 64 two-stage kernel, frames built twice: one pass over HBM (kernels_mid.hip)
@@ -1322,9 +1340,17 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
     p.frame_max = (unsigned *)mx;
     HIP_TRY(c, run_tx_symbols(c->prm.n_fft, p, c->stream, c->num_cu));
     c->trace.add("k_tx_finish");
-    HIP_TRY(c, run_tx_finish(reinterpret_cast<float2 *>(out), n_frames, out_stride, 10 * S, frame, c->d_header,
-                             c->header_max, (const unsigned *)mx, c->stream));
+    HIP_TRY(c, run_tx_finish(out, n_frames, out_stride, 10 * S, frame, c->d_header, c->header_max, (const unsigned *)mx, c->stream));
     return OFDM_OK;
+}
+int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, int64_t payload_stride,
+                         const int32_t *payload_len, int32_t payload_bytes, ofdm_fc32 *out, int64_t out_stride) {
+    int64_t frame = 0;
+    const int rc = tx_encode_check(c, payload, n_frames, payload_stride, payload_bytes, out, out_stride, &frame);
+    if (rc || !n_frames) return rc;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    return tx_encode_fc32(c, payload, n_frames, payload_stride, payload_len, payload_bytes, reinterpret_cast<float2 *>(out), out_stride, frame);
 }
 
 namespace {
@@ -1678,7 +1704,7 @@ struct Sc16Chunks {
     int64_t chunk, ws_stride;
     float2 *ws;
 };
-static int sc16_chunks(ofdm_ctx *c, int64_t n_frames, int64_t frame_stride, int64_t frame_len, Sc16Chunks &k) {
+static int sc16_chunks(ofdm_ctx *c, WsRole role, int64_t n_frames, int64_t frame_stride, int64_t frame_len, Sc16Chunks &k) {
     k.ws_stride = frame_len + ((frame_len ^ frame_stride) & 1);
     int64_t chunk = c->tune.sc16_chunk_frames;
     if (chunk <= 0) {
@@ -1687,7 +1713,7 @@ static int sc16_chunks(ofdm_ctx *c, int64_t n_frames, int64_t frame_stride, int6
     }
     k.chunk = std::min(std::max<int64_t>(chunk, 1), std::max<int64_t>(n_frames, 1));
     void *w;
-    const int rc = ws_get(c, kWsSc16, (size_t)k.chunk * (size_t)k.ws_stride * sizeof(float2), &w);
+    const int rc = ws_get(c, role, (size_t)k.chunk * (size_t)k.ws_stride * sizeof(float2), &w);
     k.ws = static_cast<float2 *>(w);
     return rc;
 }
@@ -1719,7 +1745,7 @@ int ofdm_rx_demod_sc16_batch(ofdm_ctx *c, const ofdm_sc16 *in, int64_t n_frames,
     }
     Sc16Chunks k;
     int rc;
-    if ((rc = sc16_chunks(c, n_frames, frame_stride, frame_len, k))) return rc;
+    if ((rc = sc16_chunks(c, kWsSc16, n_frames, frame_stride, frame_len, k))) return rc;
     c->trace.add("k_sc16_widen");
     Trace first;
     for (int64_t f0 = 0; f0 < n_frames; f0 += k.chunk) {
@@ -1746,7 +1772,7 @@ int ofdm_rx_decode_sc16_batch(ofdm_ctx *c, const ofdm_sc16 *in, int64_t n_frames
     DeviceGuard dev_guard(c->device);
     Sc16Chunks k;
     int rc;
-    if ((rc = sc16_chunks(c, n_frames, frame_stride, frame_len, k))) return rc;
+    if ((rc = sc16_chunks(c, kWsSc16, n_frames, frame_stride, frame_len, k))) return rc;
     Trace first;
     for (int64_t f0 = 0; f0 < n_frames; f0 += k.chunk) {
         const int64_t m = std::min(k.chunk, n_frames - f0);
@@ -1757,6 +1783,47 @@ int ofdm_rx_decode_sc16_batch(ofdm_ctx *c, const ofdm_sc16 *in, int64_t n_frames
         if (!f0) { first.reset(); first.add("k_sc16_widen"); first.add(c->trace.buf); }
     }
     c->trace = first;
+    return OFDM_OK;
+}
+
+// ------------------------------------------------------------------ EXT-10: sc16 output
+// Row f = ofdm_sc16_narrow(frame f of ofdm_tx_encode_batch, scale).  N = 64 frames of up to 56 data symbols into a 16-byte aligned
+// output with rows a multiple of 4 samples apart: the coding layers, then k_txframe64_sc16, which narrows in its store phase.  Everything
+// else: the unchanged fc32 encode on a chunk of frames into kWsTxSc16 (rows an even number of samples apart, 16-byte aligned: what the
+// fc32 frame kernels like best), then k_sc16_narrow with per-row counts into the caller's rows.
+int ofdm_tx_encode_sc16_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, int64_t payload_stride, const int32_t *payload_len,
+                              int32_t payload_bytes, float scale, ofdm_sc16 *out, int64_t out_stride, int32_t *clipped) {
+    if (!sc16_scale_ok(scale)) return OFDM_ERR_INVALID;
+    int64_t frame = 0;
+    int rc = tx_encode_check(c, payload, n_frames, payload_stride, payload_bytes, out, out_stride, &frame);
+    if (rc || !n_frames) return rc;
+    if (reinterpret_cast<uintptr_t>(out) & 3) return OFDM_ERR_INVALID;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    // the launcher's own envelope (kernels_n64_tx_sc16.hip), asked before the rows are coded: they are coded once on either path
+    if (c->prm.n_fft == 64 && !c->tune.no_txframe64_sc16 && !c->tune.no_txframe64 &&
+        txframe64_sc16_takes((int)ofdm_data_symbols(c, payload_bytes), out, out_stride)) {
+        TxRows r{payload, payload_stride, payload_len, payload_bytes};
+        if ((rc = tx_code_layers(c, n_frames, r))) return rc;
+        const SymParams p = tx_frame_params(c, r, n_frames, payload_bytes);
+        HIP_TRY(c, run_txframe64_sc16(p, c->d_header, c->header_max, reinterpret_cast<uint32_t *>(out), out_stride, scale, clipped, c->stream,
+                                      c->num_cu));
+        return OFDM_OK;
+    }
+    Sc16Chunks k;
+    if ((rc = sc16_chunks(c, kWsTxSc16, n_frames, 0, frame, k))) return rc;
+    for (int64_t f0 = 0; f0 < n_frames; f0 += k.chunk) {
+        const int64_t m = std::min(k.chunk, n_frames - f0);
+        c->trace.reset(); // the dispatch string names what the last chunk ran
+        rc = tx_encode_fc32(c, payload ? payload + f0 * payload_stride : nullptr, m, payload_stride, payload_len ? payload_len + f0 : nullptr,
+                            payload_bytes, k.ws, k.ws_stride, frame);
+        if (rc) return rc;
+        Sc16Params p;
+        p.tune = &c->tune; p.trace = &c->trace; p.n_frames = m; p.frame_len = frame; p.in_stride = k.ws_stride; p.out_stride = out_stride;
+        p.scale = scale; p.fc_in = k.ws; p.sc_out = reinterpret_cast<uint32_t *>(out + f0 * out_stride);
+        p.clipped = clipped ? clipped + f0 : nullptr;
+        HIP_TRY(c, run_sc16_narrow(p, c->num_cu, c->stream));
+    }
     return OFDM_OK;
 }
 

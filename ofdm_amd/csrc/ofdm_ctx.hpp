@@ -83,6 +83,8 @@ enum WsRole {
     kWsFrameMax,                 // per-frame maxima (ofdm_tx_encode_batch, ofdm_normalize_batch)
     kWsProbeSink,                // ofdm_hbm_read_probe
     kWsSc16,                     // EXT-9: one chunk of frames widened from sc16, the input of the fc32 path behind the sc16 entry points
+    kWsTxSc16,                   // EXT-10: one chunk of fc32 frames out of the encode chain, the input of k_sc16_narrow (ofdm_tx_encode_sc16_batch)
+    kWsLongSc16,                 // EXT-10: one long sc16 capture widened, the input of the fc32 long decode (ofdm_rx_decode_long_sc16[_host])
     kWsRoles
 };
 

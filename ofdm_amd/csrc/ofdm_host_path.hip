@@ -34,6 +34,7 @@ struct HostPipe {
     Buf d_in[kSlots], d_out[kSlots]; // device slots
     Buf h_in[kSlots], h_out[kSlots]; // pinned bounce slots
     Buf d_long;                      // device copy of one long capture (ofdm_rx_decode_long_host)
+    Buf d_long16;                    // device copy of one long sc16 capture (ofdm_rx_decode_long_sc16_host)
     Buf d_scal, h_scal;              // per-slice detector outputs / per-frame scalars (device, pinned)
 };
 
@@ -106,11 +107,13 @@ struct PipeJob {
     virtual ~PipeJob() {}
     virtual size_t in_bytes(int64_t k) const = 0;
     virtual size_t out_bytes(int64_t k) const = 0;
+    virtual size_t dev_out_bytes(int64_t k) const { return out_bytes(k); } // the device slot may hold more than the block that travels
     virtual const void *in_direct(int64_t) const { return nullptr; } // non-null: pinned source, DMA-ed in place
     virtual void fill_in(int64_t, void *) const {}                   // else: pack the chunk's input into the pinned bounce slot
     virtual void *out_direct(int64_t) const { return nullptr; }      // non-null: pinned destination of the whole output block
     virtual void drain_out(int64_t, const void *) const {}           // else: scatter the bounce slot into the caller's arrays
     virtual int launch(int64_t k, void *d_in, void *d_out) = 0;      // enqueue chunk k's kernels on the context's stream
+    virtual int extra_d2h(int64_t, const void *, hipStream_t) { return OFDM_OK; } // a second, small D2H of chunk k behind the block's (same stream)
 };
 
 int run_pipe(ofdm_ctx *c, PipeJob &job) {
@@ -118,18 +121,19 @@ int run_pipe(ofdm_ctx *c, PipeJob &job) {
     HostPipe *hp;
     int rc = pipe_get(c, &hp);
     if (rc) return rc;
-    size_t max_in = 0, max_out = 0;
+    size_t max_in = 0, max_out = 0, max_dev_out = 0;
     bool bounce_in = false, bounce_out = false;
     for (int64_t k : {(int64_t)0, job.n_chunks - 1}) { // every chunk but the last has chunk 0's shape
         max_in = std::max(max_in, job.in_bytes(k));
         max_out = std::max(max_out, job.out_bytes(k));
+        max_dev_out = std::max(max_dev_out, job.dev_out_bytes(k));
         bounce_in = bounce_in || !job.in_direct(k);
         bounce_out = bounce_out || !job.out_direct(k);
     }
     const int slots = (int)std::min<int64_t>(HostPipe::kSlots, job.n_chunks);
     for (int s = 0; s < slots; s++) {
         if ((rc = dev_grow(c, hp, hp->d_in[s], max_in + 64))) return rc; // + 64: the frame kernels' branch-free prefetches may read a little past a row
-        if ((rc = dev_grow(c, hp, hp->d_out[s], max_out + 64))) return rc;
+        if ((rc = dev_grow(c, hp, hp->d_out[s], max_dev_out + 64))) return rc;
         if (bounce_in && (rc = pin_grow(c, hp, hp->h_in[s], max_in))) return rc;
         if (bounce_out && (rc = pin_grow(c, hp, hp->h_out[s], max_out))) return rc;
     }
@@ -160,6 +164,7 @@ int run_pipe(ofdm_ctx *c, PipeJob &job) {
             void *dst = job.out_direct(k);
             if (!dst) dst = hp->h_out[s].p;
             HIP_TRY(c, hipMemcpyAsync(dst, hp->d_out[s].p, job.out_bytes(k), hipMemcpyDeviceToHost, hp->s_out));
+            if ((r = job.extra_d2h(k, hp->d_out[s].p, hp->s_out))) return r;
             HIP_TRY(c, hipEventRecord(hp->out_done[s], hp->s_out));
         }
         for (int64_t k = drained; k < job.n_chunks; k++) {
@@ -317,6 +322,40 @@ struct EncodeJob : PipeJob {
         const ofdm_fc32 *rows = static_cast<const ofdm_fc32 *>(p);
         if (out_stride == frame) { std::memcpy(out + f0(k) * out_stride, rows, out_bytes(k)); return; }
         for (int64_t f = 0; f < m(k); f++) std::memcpy(out + (f0(k) + f) * out_stride, rows + f * frame, (size_t)frame * sizeof(ofdm_fc32));
+    }
+};
+
+// ... and ofdm_tx_encode_sc16_batch per chunk (EXT-10): 4 bytes a sample over the link.  The device slot holds [rows of `frame` sc16
+// samples | pad to 16 bytes | clipped int32 per frame].  Pageable rows: the whole block comes back through the bounce slot.  Pinned rows
+// are DMA-ed in place, and the counts follow on the same stream into pinned scratch (pin_clip, the whole batch) that the caller's array is
+// filled from when the pipe has drained.
+struct EncodeSc16Job : EncodeJob {
+    float scale;
+    ofdm_sc16 *out16;
+    int32_t *clipped, *pin_clip;
+    size_t rows_bytes(int64_t k) const { return (size_t)m(k) * (size_t)frame * sizeof(ofdm_sc16); }
+    size_t clip_off(int64_t k) const { return round_up(rows_bytes(k), 16); }
+    size_t dev_out_bytes(int64_t k) const override { return clip_off(k) + 4 * (size_t)m(k); }
+    size_t out_bytes(int64_t k) const override { return pinned_out || !clipped ? rows_bytes(k) : dev_out_bytes(k); }
+    void *out_direct(int64_t k) const override { return pinned_out ? out16 + f0(k) * out_stride : nullptr; }
+    int launch(int64_t k, void *d_in, void *d_out) override {
+        const char *b = static_cast<const char *>(d_in);
+        char *o = static_cast<char *>(d_out);
+        return ofdm_tx_encode_sc16_batch(c, reinterpret_cast<const uint8_t *>(b + lens_bytes(k)), m(k), payload_bytes,
+                                         lens ? reinterpret_cast<const int32_t *>(b) : nullptr, payload_bytes, scale,
+                                         reinterpret_cast<ofdm_sc16 *>(o), frame, clipped ? reinterpret_cast<int32_t *>(o + clip_off(k)) : nullptr);
+    }
+    int extra_d2h(int64_t k, const void *d_out, hipStream_t st) override {
+        if (!pinned_out || !clipped) return OFDM_OK;
+        HIP_TRY(c, hipMemcpyAsync(pin_clip + f0(k), static_cast<const char *>(d_out) + clip_off(k), 4 * (size_t)m(k), hipMemcpyDeviceToHost, st));
+        return OFDM_OK;
+    }
+    void drain_out(int64_t k, const void *p) const override {
+        const ofdm_sc16 *rows = static_cast<const ofdm_sc16 *>(p);
+        if (out_stride == frame) std::memcpy(out16 + f0(k) * out_stride, rows, rows_bytes(k));
+        else
+            for (int64_t f = 0; f < m(k); f++) std::memcpy(out16 + (f0(k) + f) * out_stride, rows + f * frame, (size_t)frame * sizeof(ofdm_sc16));
+        if (clipped) std::memcpy(clipped + f0(k), static_cast<const char *>(p) + clip_off(k), 4 * (size_t)m(k));
     }
 };
 
@@ -491,6 +530,54 @@ int decode_long_dev(ofdm_ctx *c, const float2 *in, int64_t n, int64_t lag_lo, in
     return OFDM_OK;
 }
 
+// One long capture, host -> dst on the device, ordered in front of the context's stream: in place from pinned memory, else in 8 MB
+// pieces through two pinned bounce slots (the copy of piece k + 1 overlaps the DMA of piece k)
+int long_upload(ofdm_ctx *c, HostPipe *hp, void *dst, const void *in_host, size_t bytes) {
+    int rc;
+    if (host_pinned(in_host, bytes)) {
+        HIP_TRY(c, hipMemcpyAsync(dst, in_host, bytes, hipMemcpyHostToDevice, hp->s_in));
+    } else {
+        const size_t piece = (size_t)8 << 20;
+        for (int s = 0; s < 2; s++)
+            if ((rc = pin_grow(c, hp, hp->h_in[s], std::min(piece, bytes)))) return rc;
+        int k = 0;
+        for (size_t off = 0; off < bytes; off += piece, k++) {
+            const int s = k & 1;
+            const size_t nb = std::min(piece, bytes - off);
+            if (k >= 2) HIP_TRY(c, hipEventSynchronize(hp->in_done[s]));
+            std::memcpy(hp->h_in[s].p, static_cast<const char *>(in_host) + off, nb);
+            HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(dst) + off, hp->h_in[s].p, nb, hipMemcpyHostToDevice, hp->s_in));
+            HIP_TRY(c, hipEventRecord(hp->in_done[s], hp->s_in));
+        }
+    }
+    HIP_TRY(c, hipEventRecord(hp->in_done[2], hp->s_in));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, hp->in_done[2], 0));
+    return OFDM_OK;
+}
+
+// EXT-10: ofdm_rx_decode_long on an sc16 capture that is on the device: k_sc16_widen into the context's workspace kWsLongSc16 (8 bytes a
+// sample beside the capture's 4; + 64: the frame kernels' branch-free prefetches may read a little past a row), then decode_long_dev
+// unchanged.  The dispatch string is k_sc16_widen+ + the fc32 call's: the entry points decode_long_dev runs reset the context's trace,
+// so the widen launch is not traced (p.trace stays null) and its name is put in front afterwards.
+int decode_long_sc16_dev(ofdm_ctx *c, const ofdm_sc16 *in, int64_t n, float scale, int64_t lag_lo, int64_t lag_hi, int64_t d_known,
+                         int32_t max_symbols, uint8_t *out_dev, int64_t out_cap, int32_t *out_len, int32_t *status, int64_t *offset,
+                         double *f_delta, float *metric) {
+    int rc;
+    void *wide;
+    if ((rc = ws_get(c, kWsLongSc16, (size_t)n * sizeof(ofdm_fc32) + 64, &wide))) return rc;
+    Sc16Params p;
+    p.tune = &c->tune; p.n_frames = 1; p.frame_len = n; p.in_stride = n; p.out_stride = n; p.scale = scale;
+    p.sc_in = reinterpret_cast<const uint32_t *>(in); p.fc_out = static_cast<float2 *>(wide);
+    HIP_TRY(c, run_sc16_widen(p, c->num_cu, c->stream));
+    rc = decode_long_dev(c, static_cast<const float2 *>(wide), n, lag_lo, lag_hi, d_known, max_symbols, out_dev, out_cap, out_len, status, offset,
+                         f_delta, metric);
+    Trace t;
+    t.reset(); t.add("k_sc16_widen");
+    if (c->trace.len) t.add(c->trace.buf);
+    c->trace = t;
+    return rc;
+}
+
 } // namespace
 
 extern "C" {
@@ -510,6 +597,7 @@ void ofdm_host_pipe_destroy(ofdm_ctx *c) {
         if (hp->out_done[s]) hipEventDestroy(hp->out_done[s]);
     }
     if (hp->d_long.p) hipFree(hp->d_long.p);
+    if (hp->d_long16.p) hipFree(hp->d_long16.p);
     if (hp->d_scal.p) hipFree(hp->d_scal.p);
     if (hp->h_scal.p) hipHostFree(hp->h_scal.p);
     if (hp->s_in) hipStreamDestroy(hp->s_in);
@@ -626,6 +714,34 @@ int ofdm_tx_encode_host(ofdm_ctx *c, const uint8_t *payload_host, int64_t n_fram
     return run_pipe(c, j);
 }
 
+int ofdm_tx_encode_sc16_host(ofdm_ctx *c, const uint8_t *payload_host, int64_t n_frames, int64_t payload_stride, const int32_t *payload_len_host,
+                             int32_t payload_bytes, float scale, ofdm_sc16 *out_host, int64_t out_stride, int32_t *clipped_host,
+                             int64_t chunk_frames) {
+    if (!c || n_frames < 0 || payload_bytes < 0 || payload_stride < 0 || !(std::isfinite(scale) && scale > 0.f)) return OFDM_ERR_INVALID;
+    if (n_frames && (!out_host || (payload_bytes && !payload_host))) return OFDM_ERR_INVALID;
+    const int64_t frame = ofdm_frame_samples(c, payload_bytes);
+    if (out_stride < frame) return OFDM_ERR_INVALID;
+    if (!n_frames) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    EncodeSc16Job j;
+    j.c = c; j.payload = payload_host; j.n_frames = n_frames; j.payload_stride = payload_stride; j.lens = payload_len_host;
+    j.payload_bytes = payload_bytes; j.out = nullptr; j.out16 = out_host; j.out_stride = out_stride; j.frame = frame;
+    j.scale = scale; j.clipped = clipped_host; j.pin_clip = nullptr;
+    j.chunk = auto_chunk(n_frames, (size_t)frame * sizeof(ofdm_sc16), chunk_frames);
+    j.n_chunks = (n_frames + j.chunk - 1) / j.chunk;
+    j.pinned_out = out_stride == frame && host_pinned(out_host, (size_t)(n_frames * frame) * sizeof(ofdm_sc16));
+    if (j.pinned_out && clipped_host) {
+        HostPipe *hp;
+        int rc = pipe_get(c, &hp);
+        if (!rc) rc = pin_grow(c, hp, hp->h_scal, 4 * (size_t)n_frames);
+        if (rc) return rc;
+        j.pin_clip = static_cast<int32_t *>(hp->h_scal.p);
+    }
+    const int rc = run_pipe(c, j);
+    if (!rc && j.pin_clip) std::memcpy(clipped_host, j.pin_clip, 4 * (size_t)n_frames);
+    return rc;
+}
+
 int ofdm_sc_correlate_long(ofdm_ctx *c, const ofdm_fc32 *in_dev, int64_t n_samples, int64_t lag_lo, int64_t lag_hi, int64_t slice_lags,
                            int64_t *d_hat, double *f_delta, float *metric) {
     if (!c || !d_hat || n_samples < 0 || lag_lo < 0 || slice_lags < 0 || (n_samples && !in_dev)) return OFDM_ERR_INVALID;
@@ -658,28 +774,49 @@ int ofdm_rx_decode_long_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_sa
         const size_t bytes = (size_t)n_samples * sizeof(ofdm_fc32);
         if ((rc = dev_grow(c, hp, hp->d_long, bytes + 64))) return rc;
         if ((rc = dev_grow(c, hp, hp->d_out[0], (size_t)std::max<int64_t>(out_cap, 4) + 64))) return rc;
-        // upload: in place from pinned memory, else in 8 MB pieces through two pinned bounce slots (the copy of piece k + 1 overlaps
-        // the DMA of piece k)
-        if (host_pinned(in_host, bytes)) {
-            HIP_TRY(c, hipMemcpyAsync(hp->d_long.p, in_host, bytes, hipMemcpyHostToDevice, hp->s_in));
-        } else {
-            const size_t piece = (size_t)8 << 20;
-            for (int s = 0; s < 2; s++)
-                if ((rc = pin_grow(c, hp, hp->h_in[s], std::min(piece, bytes)))) return rc;
-            int k = 0;
-            for (size_t off = 0; off < bytes; off += piece, k++) {
-                const int s = k & 1;
-                const size_t nb = std::min(piece, bytes - off);
-                if (k >= 2) HIP_TRY(c, hipEventSynchronize(hp->in_done[s]));
-                std::memcpy(hp->h_in[s].p, reinterpret_cast<const char *>(in_host) + off, nb);
-                HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(hp->d_long.p) + off, hp->h_in[s].p, nb, hipMemcpyHostToDevice, hp->s_in));
-                HIP_TRY(c, hipEventRecord(hp->in_done[s], hp->s_in));
-            }
-        }
-        HIP_TRY(c, hipEventRecord(hp->in_done[2], hp->s_in));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, hp->in_done[2], 0));
+        if ((rc = long_upload(c, hp, hp->d_long.p, in_host, bytes))) return rc;
         rc = decode_long_dev(c, static_cast<const float2 *>(hp->d_long.p), n_samples, 0, 0, -1, max_symbols, static_cast<uint8_t *>(hp->d_out[0].p),
                              out_cap, out_len, status, offset, f_delta, metric);
+        if (rc) return rc;
+        if (*status == OFDM_FRAME_OK && *out_len > 0) {
+            HIP_TRY(c, hipMemcpyAsync(out_host, hp->d_out[0].p, (size_t)*out_len, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+        return OFDM_OK;
+    };
+    rc = work();
+    if (rc) sync_all(c, hp);
+    return rc;
+}
+
+// EXT-10: the two long-capture calls on sc16 samples
+int ofdm_rx_decode_long_sc16(ofdm_ctx *c, const ofdm_sc16 *in_dev, int64_t n_samples, float scale, int64_t lag_lo, int64_t lag_hi,
+                             int64_t d_hat_known, int32_t max_symbols, uint8_t *out_dev, int64_t out_cap, int32_t *out_len, int32_t *status,
+                             int64_t *offset, double *f_delta, float *metric) {
+    if (!c || n_samples <= 0 || lag_lo < 0 || max_symbols <= 0 || !in_dev || !out_dev || !out_len || !status) return OFDM_ERR_INVALID;
+    if (!(std::isfinite(scale) && scale > 0.f) || (reinterpret_cast<uintptr_t>(in_dev) & 3)) return OFDM_ERR_INVALID;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    return decode_long_sc16_dev(c, in_dev, n_samples, scale, lag_lo, lag_hi, d_hat_known, max_symbols, out_dev, out_cap, out_len, status, offset,
+                                f_delta, metric);
+}
+
+int ofdm_rx_decode_long_sc16_host(ofdm_ctx *c, const ofdm_sc16 *in_host, int64_t n_samples, float scale, int32_t max_symbols, uint8_t *out_host,
+                                  int64_t out_cap, int32_t *out_len, int32_t *status, int64_t *offset, double *f_delta, float *metric) {
+    if (!c || n_samples <= 0 || max_symbols <= 0 || !in_host || !out_host || !out_len || !status) return OFDM_ERR_INVALID;
+    if (!(std::isfinite(scale) && scale > 0.f)) return OFDM_ERR_INVALID;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    HostPipe *hp;
+    int rc = pipe_get(c, &hp);
+    if (rc) return rc;
+    auto work = [&]() -> int { // as ofdm_rx_decode_long_host: half the bytes over the link, then the widen in front of the chain
+        const size_t bytes = (size_t)n_samples * sizeof(ofdm_sc16);
+        if ((rc = dev_grow(c, hp, hp->d_long16, bytes + 64))) return rc;
+        if ((rc = dev_grow(c, hp, hp->d_out[0], (size_t)std::max<int64_t>(out_cap, 4) + 64))) return rc;
+        if ((rc = long_upload(c, hp, hp->d_long16.p, in_host, bytes))) return rc;
+        rc = decode_long_sc16_dev(c, static_cast<const ofdm_sc16 *>(hp->d_long16.p), n_samples, scale, 0, 0, -1, max_symbols,
+                                  static_cast<uint8_t *>(hp->d_out[0].p), out_cap, out_len, status, offset, f_delta, metric);
         if (rc) return rc;
         if (*status == OFDM_FRAME_OK && *out_len > 0) {
             HIP_TRY(c, hipMemcpyAsync(out_host, hp->d_out[0].p, (size_t)*out_len, hipMemcpyDeviceToHost, c->stream));

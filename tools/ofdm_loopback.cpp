@@ -64,21 +64,21 @@ static bool read_fc32(const char *path, std::vector<Complex64> &x, long start, l
     return true;
 }
 
-// sc16 wire format (--sc16; UHD's --type short): little-endian int16 pairs (re, im), in PATH.sc16 next to the fc32 file.  A frame is
-// normalised to a peak of 1, so it is written at full scale (ofdm_sc16_narrow, scale 32767) and read back with x = v / 32768
-// (ofdm_sc16_widen, OFDM_SC16_DEFAULT_SCALE) -- the receiver does not care about the factor 32767 / 32768.
-static bool write_sc16(const std::string &path, const std::vector<Complex64> &x, int64_t *clipped) {
+// sc16 wire format (--sc16; UHD's --type short): little-endian int16 pairs (re, im), in PATH.sc16 next to the fc32 file.  The library
+// makes them (Context::encode_sc16 = ofdm_tx_encode_sc16_host) and reads them (Context::decode_sc16 = ofdm_rx_decode_long_sc16_host,
+// x = v / 32768).  A frame is normalised by its SIGNED maximum: its positive peak is 1, its negative peak is not bounded by -1 (about
+// -2 for BPSK and QPSK without guard bands), so full scale 32767 clips such a frame.  The frame is therefore encoded at 32767 first, and
+// while the library's clipped count is not 0 again at half the scale; the receiver does not care about the factor.
+static bool write_sc16(const std::string &path, const std::vector<ofdm_sc16> &q) {
     FILE *fh = std::fopen(path.c_str(), "wb");
     if (!fh) return false;
-    const std::vector<ofdm_sc16> q = sc16_narrow(Context::to_fc32(x), 32767.0f, clipped);
     std::fwrite(q.data(), sizeof(ofdm_sc16), q.size(), fh);
     std::fclose(fh);
     return true;
 }
-static bool read_sc16(const std::string &path, std::vector<Complex64> &x, long start, long stop) {
+static bool read_sc16(const std::string &path, std::vector<ofdm_sc16> &q, long start, long stop) {
     FILE *fh = std::fopen(path.c_str(), "rb");
     if (!fh) return false;
-    std::vector<ofdm_sc16> q;
     ofdm_sc16 v;
     long i = 0;
     while (std::fread(&v, sizeof(v), 1, fh) == 1) { // a trailing partial sample is dropped
@@ -86,7 +86,6 @@ static bool read_sc16(const std::string &path, std::vector<Complex64> &x, long s
         ++i;
     }
     std::fclose(fh);
-    x = Context::from_fc32(sc16_widen(q));
     return true;
 }
 
@@ -94,7 +93,7 @@ int main(int argc, char **argv) {
     const char *corpus = "I met a traveller from an antique land, Who said: Two vast and trunkless legs of stone Stand in the desert. ";
     size_t num_bytes = 400;
     bool guard_bands = false, timing_error = false, ecc = false; // ecc: lab3c's ecc_enabled (outer RS(255,223), utils.rs:97-180)
-    bool sc16 = false; // --sc16: --transmit also writes FILE.sc16, --receive reads FILE.sc16 instead of FILE (EXT-9)
+    bool sc16 = false; // --sc16: --transmit also writes FILE.sc16, --receive reads FILE.sc16 instead of FILE (EXT-9; EXT-10: through the library)
     bool fcs = false; // --fcs: the CRC-32 frame check inside encode / decode (ecc = OFDM_ECC_FCS): exactly the payload back, or an error
     ModulationScheme modulation = ModulationScheme::Qpsk;
     const char *tx_file = nullptr, *rx_file = nullptr; // examples/lab3c.rs: --transmit f / --receive f [--start a --stop b]
@@ -173,8 +172,10 @@ int main(int argc, char **argv) {
         }
         if (rx_file) { // decode a stored capture (or a slice of it)
             std::vector<Complex64> cap;
-            if (!(sc16 ? read_sc16(std::string(rx_file) + ".sc16", cap, start, stop) : read_fc32(rx_file, cap, start, stop))) { std::printf("cannot read %s%s\n", rx_file, sc16 ? ".sc16" : ""); return 4; }
-            auto received = finish(decode(std::move(cap), guard_bands, modulation, fcs));
+            std::vector<ofdm_sc16> cap16;
+            if (!(sc16 ? read_sc16(std::string(rx_file) + ".sc16", cap16, start, stop) : read_fc32(rx_file, cap, start, stop))) { std::printf("cannot read %s%s\n", rx_file, sc16 ? ".sc16" : ""); return 4; }
+            auto received = finish(sc16 ? cached_context(guard_bands, modulation, 64, fcs ? OFDM_ECC_FCS : OFDM_ECC_NONE, OFDM_CFO_ABS).decode_sc16(cap16)
+                                        : decode(std::move(cap), guard_bands, modulation, fcs));
             std::printf("received %zu bytes\n%.*s\n", received.size(), (int)std::min<size_t>(received.size(), 100), (const char *)received.data());
             if (received.size() != text.size()) return 2;
             return Analysis(text, received).num_errs == 0 ? 0 : 1;
@@ -184,9 +185,14 @@ int main(int argc, char **argv) {
             if (!write_fc32(tx_file, tx)) { std::printf("cannot write %s\n", tx_file); return 4; }
             std::printf("wrote %zu samples (%zu bytes) to %s\n", tx.size(), tx.size() * 8, tx_file);
             if (sc16) {
-                int64_t clipped = 0;
-                if (!write_sc16(std::string(tx_file) + ".sc16", tx, &clipped)) { std::printf("cannot write %s.sc16\n", tx_file); return 4; }
-                std::printf("wrote %zu samples (%zu bytes, %lld clipped components) to %s.sc16\n", tx.size(), tx.size() * 4, (long long)clipped, tx_file);
+                Context &ctx = cached_context(guard_bands, modulation, 64, fcs ? OFDM_ECC_FCS : OFDM_ECC_NONE);
+                float scale = 32767.0f;
+                int32_t clipped = 0, clipped_full = 0;
+                std::vector<ofdm_sc16> q = ctx.encode_sc16(source, scale, &clipped_full);
+                for (clipped = clipped_full; clipped > 0 && scale > 1.0f;) q = ctx.encode_sc16(source, scale *= 0.5f, &clipped);
+                if (!write_sc16(std::string(tx_file) + ".sc16", q)) { std::printf("cannot write %s.sc16\n", tx_file); return 4; }
+                std::printf("wrote %zu samples (%zu bytes) to %s.sc16 at scale %g: %d clipped components (%d at scale 32767)\n", q.size(), q.size() * 4,
+                            tx_file, (double)scale, (int)clipped, (int)clipped_full);
             }
             return 0;
         }
