@@ -22,6 +22,22 @@
  *     (src/transmitter.rs:75-96), which cannot be verified offline; ofdm_default_pilots() supplies the
  *     documented SplitMix64 defaults and ofdm_stdrng_pilots() a restatement of the StdRng tables.
  *
+ * Input amplitude
+ *   Every receive-side definition below is homogeneous in the capture, and the library keeps it so: no threshold, trust
+ *   test or slack constant in a kernel is absolute, each is relative to an energy the kernel has already summed.  Scaling
+ *   a capture by a real g != 0 leaves every result what it was -- timing, status, m, CFO, the Schmidl-Cox metric, equalised
+ *   points, w_k, LLRs, snr, llr_unit, evm2 and the delivered bytes -- and for g = +-2^k, where the scaling is exact in
+ *   f32, bit for bit.  What scales is what is an amplitude or a power by definition: H (ofdm_estimate_channel_batch,
+ *   ofdm_chest_smooth_batch) by g, the xcorr peak |out[idx_max]| (also the `metric` of a decode under OFDM_SYNC_REFERENCE)
+ *   by |g|, noise_var, gain and both wide-CFO metrics by g^2.  A channel estimate passed in must belong to the capture it
+ *   is passed with (hk of g x is g hk); a stage call WITHOUT one (ofdm_rx_demod_batch / ofdm_rx_llr_batch with hk = NULL,
+ *   which is all the burst forms of k_demod64 serve) demaps unequalised points, which scale with g: its bytes, soft
+ *   points and LLRs are not invariant.  The range the tests pin (tests/test_gpu_gain.py) is 2^-20 .. 2^20 around a
+ *   frame whose peak is 1, for every kernel; beyond it f32 squares of window sums approach the subnormal / overflow ends.
+ *   The `scale` of the sc16 entry points is such a gain: scale = 1.0 (raw counts, amplitudes up to 2^15) and the default
+ *   2^-15 give the same results.  The transmit side normalises its own frames; ofdm_channel_batch is a test bench and
+ *   is homogeneous to rounding only (the complex square root of its pseudo-variance).
+ *
  * Extensions named by the north star that the reference lacks (64/256-QAM, Hamming(7,4), Schmidl-Cox,
  * N != 64) are defined in DESIGN.md section 3 and restated on the CPU in oracle/ofdm_oracle.c.
  */

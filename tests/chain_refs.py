@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv_ref as cr  # noqa: E402
 import fcs_ref  # noqa: E402
 import framed_ref as fr  # noqa: E402
-import ldpc_ref as lr  # noqa: E402
+import ldpc_rates_ref as lrr  # noqa: E402
 import rs_vectors as rv  # noqa: E402
 import soft_ref as sr  # noqa: E402
 
@@ -101,8 +101,10 @@ def rs_composition(c, rx, max_symbols):
 
 
 # ---- a mode as a whole (tests/test_gpu_modes.py): ecc = [64 +] [20 +] inner, the lengths composed layer by layer from the references
-BASE_MODES = (0, 1, 2, 5, 10, 11, 12, 16, 20, 30, 31, 32)
+# every ecc value ofdm_create takes (tests/test_gpu_modes.py holds the list to the library); fcs_ref.BASE_MODES is the same list
+BASE_MODES = (0, 1, 2, 5, 10, 11, 12, 16, 20, 30, 31, 32, 41, 42, 43)
 ALL_MODES = BASE_MODES + tuple(fcs_ref.ECC_FCS + m for m in BASE_MODES)
+assert fcs_ref.BASE_MODES == BASE_MODES and len(ALL_MODES) == 30
 
 
 def mode_layers(ecc):
@@ -126,7 +128,7 @@ def mode_coded_len(ecc, p):
         return 7 * -(-p // 4)
     if inner == 5:
         return 2 * (p + 1)
-    return lr.coded_len(p) if inner == 16 else fr.coded_len(p, inner - 10)
+    return lrr.code_of_ecc(inner).coded_len(p) if inner in lrr.ECC else fr.coded_len(p, inner - 10)
 
 
 def mode_row_bytes(ecc, body):
@@ -138,8 +140,8 @@ def mode_row_bytes(ecc, body):
         row = 4 * (body // 7)
     elif inner == 5:
         row = max(body // 2 - 1, 0)
-    elif inner == 16:
-        row = lr.row_bytes(body)
+    elif inner in lrr.ECC:
+        row = lrr.code_of_ecc(inner).row_bytes(body)
     else:
         row = fr.max_steps(8 * (body - fr.LENGTH_BLOCK), inner - 10) // 8 if body >= fr.LENGTH_BLOCK else 0
     if rs:

@@ -11,7 +11,7 @@ import zlib
 OVERHEAD = 8
 ECC_FCS = 64
 FRAME_FCS = -6
-BASE_MODES = (0, 1, 2, 5, 10, 11, 12, 20, 30, 31, 32)
+BASE_MODES = (0, 1, 2, 5, 10, 11, 12, 16, 20, 30, 31, 32, 41, 42, 43)   # every mode the frame check wraps: all of them
 
 
 def wrap(payload: bytes) -> bytes:

@@ -115,13 +115,13 @@ def _create(lib, ecc):
     return rc
 
 
-def test_create_accepts_the_eleven_fcs_values_and_no_other(lib):
+def test_create_accepts_every_fcs_value_and_no_other(lib):
     base = _create(lib, 0)
     assert base in (0, -3)                                        # -3: no GPU here
     for m in fcs_ref.BASE_MODES:
         assert _create(lib, m) == base, m
         assert _create(lib, fcs_ref.ECC_FCS + m) == base, m
-    assert sorted(fcs_ref.ECC_FCS + m for m in fcs_ref.BASE_MODES) == [64, 65, 66, 69, 74, 75, 76, 84, 94, 95, 96]
+    assert sorted(fcs_ref.ECC_FCS + m for m in fcs_ref.BASE_MODES) == [64, 65, 66, 69, 74, 75, 76, 80, 84, 94, 95, 96, 105, 106, 107]
     for bad in (63, 67, 68, 70, 77, 85, 93, 97, 128, 64 + 64):
         assert _create(lib, bad) == -1, bad
     for bad in (3, 4, 6, 7, 8, 9, 13, 14, 21, 29, 33, 40, 99, 100, -1):   # what was rejected stays rejected

@@ -1,6 +1,7 @@
-"""The modes as a whole: every one of the 24 ecc values composes its lengths and its row size from its layers (tests/chain_refs.py:
+"""The modes as a whole: every one of the 30 ecc values composes its lengths and its row size from its layers (tests/chain_refs.py:
 mode_coded_len, mode_row_bytes over framed_ref, ldpc_ref and fcs_ref), and a context that encodes and decodes in turn keeps the
-buffers of the two apart.  The files of the modes pin the same rules one mode at a time; only the last test launches a kernel."""
+buffers of the two apart.  The files of the modes pin the same rules one mode at a time; only
+test_encode_and_decode_take_turns_on_one_context launches a kernel.  The last test holds the list of modes itself to the library."""
 import functools
 import os
 import sys
@@ -72,3 +73,19 @@ def test_encode_and_decode_take_turns_on_one_context(ecc):
         assert r["status"].tolist() == [0, 0, 0] and r["len"].tolist() == [want_len] * 3
         assert torch.equal(r["bytes"][:, :40], pay) and not bool(r["bytes"][:, 40:want_len].any())
     assert seen[0] == seen[1] and seen[0]
+
+
+def test_the_library_takes_exactly_the_listed_modes():
+    """ALL_MODES is the library's own list: ofdm_create takes an ecc of 0 .. 127 exactly when the list has it, so a mode added to the
+    library without the list (and with it without the chain tests that run over the list) turns this red"""
+    from ofdm_amd import api
+
+    taken = []
+    for ecc in range(0, 128):
+        if ecc in ALL_MODES:
+            api.Context(n_fft=N_FFT, modulation=2, guard_bands=True, ecc=ecc).close()
+            taken.append(ecc)
+        else:
+            with pytest.raises(api.OfdmError):
+                api.Context(n_fft=N_FFT, modulation=2, guard_bands=True, ecc=ecc)
+    assert sorted(taken) == sorted(ALL_MODES) and len(taken) == 30
