@@ -189,8 +189,14 @@ int ofdm_last_hip_error(const ofdm_ctx *ctx); /* raw hipError_t of the last fail
 /* Which kernels served the LAST stage-level / pipeline entry point on this context: the names of the kernels its launchers
  * really enqueued, in order, joined by '+' (e.g. "k_sc_stream<regs>+k_rx_prepare+k_rxframe1024<finish>").
  * Every shape-specialised launcher has a generic fallback (k_sym<...>) for requests outside its envelope -- output rows that are not
- * 4- / 16-byte aligned, soft outputs -- with the same results (captures need only their natural 8-byte alignment, any row stride); this call is how a caller (and the parity tests) tell which
- * one ran.  Returns the full length of the string (like snprintf), buf receives at most n - 1 characters. Host call. */
+ * 4- / 16-byte aligned, soft outputs -- with the same results; this call is how a caller (and the parity tests) tell which one ran.
+ * The row contract of every batch entry point: rows are (base, stride, length); a base needs only the natural alignment of its
+ * element (8 bytes for fc32 rows, 1 for byte rows), a stride is any 64-bit count of elements no smaller than the row where the entry
+ * point says so, and neither changes a result: byte outputs are the same for every base and stride, float outputs the same bits
+ * wherever this call names the same kernels and within the stated tolerance of the definition otherwise; nothing outside the rows is
+ * written, nothing behind an input row's length is read into a result (tests/test_gpu_rows.py: padded and unaligned rows, loud
+ * slack behind every input row, rows 2^31 + 8 samples and 2^32 + 48 bytes apart).
+ * Returns the full length of the string (like snprintf), buf receives at most n - 1 characters. Host call. */
 int ofdm_last_dispatch(const ofdm_ctx *ctx, char *buf, size_t n);
 /* Per-context knobs and counters.  The library reads NO environment variable.  Keys a host legitimately needs:
  *   "grid_cap"             set/get, > 0 caps every persistent grid (0 = sized from the device); the parity tests use it to make small
