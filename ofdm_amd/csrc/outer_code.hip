@@ -8,7 +8,8 @@
 // which is unique decoding: any correct decoder returns the same bytes.  Beyond 16 errors correct_block checks that what it
 // corrected is a code word, so a block's outcome is "the code word within 16 byte errors of the input if there is one, failure
 // otherwise" -- a function of the input alone.  tests/test_rs_modes_cpu.py holds it to the oracle on such inputs too, and
-// k_rs255_decode (kernels_rs.hip) is held to this file.
+// k_rs255_decode (kernels_rs.hip) is held to this file.  tests/test_rs_contract_cpu.py and tests/test_gpu_rs_contract.py hold both to
+// that sentence itself, on blocks whose answer is known from how they were built (tests/rs_cases.py): no decoder judges them.
 // This is off the roofline by design: tens of bytes per OFDM symbol, on the host.
 #include "../../include/ofdm_hip.h"
 #include <cstring>
