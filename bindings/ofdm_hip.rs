@@ -89,6 +89,10 @@ pub const OFDM_CFO_ABS: i32 = 2;
 pub const OFDM_CFO_WIDE: i32 = 3;
 pub const OFDM_CFO_WIDE_SPAN: i32 = 8;
 pub const OFDM_CFO_WIDE_MAX_SPAN: i32 = 32;
+// ofdm_set_llr_weight (EXT-11): what the decode chains weigh their LLRs by -- the channel weight alone (default), or that times the
+// per-carrier noise weight q_k measured from the training blocks
+pub const OFDM_LLRW_CHANNEL: i32 = 0;
+pub const OFDM_LLRW_NOISE: i32 = 1;
 // ofdm_rx_quality_batch: indices into a frame's row of OFDM_QUALITY_FIELDS floats (noise variance, gain, linear SNR, LLR unit, linear
 // EVM^2, counted points); parity unpinned by the reference, tests/quality_ref.py is the definition (include/ofdm_hip.h)
 pub const OFDM_Q_VALID: usize = 0;
@@ -217,6 +221,17 @@ extern "C" {
     pub fn ofdm_cfo_wide_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,
                                offset_dev: *const i32, status_dev: *const i32, span: i32, f_delta_dev: *mut f64, m_dev: *mut i32,
                                metric_dev: *mut f32) -> c_int;
+    // EXT-11 noise-aware LLR weights (tests/noise_weight_ref.py is the definition): per-bin noise variance s_k and weight q_k from the
+    // scatter of the five training blocks; ofdm_rx_llr_batch with per-bin weights; the per-context mode of the decode chains
+    pub fn ofdm_rx_noise_bins_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,
+                                    offset_dev: *const i32, f_delta_dev: *const f64, status_dev: *const i32, nvar_dev: *mut f32,
+                                    weight_dev: *mut f32) -> c_int;
+    pub fn ofdm_rx_llr_weighted_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_frames: i64, frame_stride: i64, frame_len: i64,
+                                      first_symbol: i32, syms_per_frame: i32, offset_dev: *const i32, f_delta_dev: *const f64,
+                                      hk_dev: *const ofdm_fc32, hk_stride: i64, llr_scale: f32, llr_dev: *mut i8, llr_stride: i64,
+                                      bin_weight_dev: *const f32, bin_weight_stride: i64) -> c_int;
+    pub fn ofdm_set_llr_weight(ctx: *mut ofdm_ctx, mode: i32) -> c_int;
+    pub fn ofdm_get_llr_weight(ctx: *const ofdm_ctx, mode: *mut i32) -> c_int;
     pub fn ofdm_llr_combine_batch(ctx: *mut ofdm_ctx, llr_dev: *const i8, n_frames: i64, n_branches: i32, llr_stride: i64, n_llr: i64,
                                   quality_dev: *const f32, status_dev: *const i32, n_live_dev: *const i32, out_dev: *mut i8,
                                   out_stride: i64, weight_dev: *mut i32) -> c_int;

@@ -456,6 +456,58 @@ int ofdm_cfo_wide_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames
                         double *f_delta_dev /* in: f0, out: f0 + 2 pi m / S */, int32_t *m_dev /* optional */,
                         float *metric_dev /* optional, 2 per frame */);
 
+/* ------------------------------------------------------------------ noise-aware LLR weights (EXT-11) (north-star extension)
+ * The channel weight w_k of "soft decisions" above assumes the same noise on every carrier.  A narrow-band interferer, an LO spur or a
+ * DC offset puts a few carriers far under the rest, and those then hand the decoder confident wrong LLRs.  The five training blocks are
+ * identical, so their scatter is the noise; "link quality" sums it over all bins into one noise_var, here it is kept per bin.
+ * Parity unpinned by the reference, which has nothing of the kind: tests/noise_weight_ref.py is the definition.  Per frame f, with
+ * o = offset_dev[f], S = n_fft + cp_len, N = n_fft, samples at or beyond frame_len reading as zero and the derotation of
+ * ofdm_estimate_channel_batch (sample id counted from o):
+ *   tested     iff status_dev[f] == 0 (or no status_dev), o >= 0 and o + 10 S <= frame_len (all five training blocks inside the capture);
+ *              a frame that is not tested is not read and gets s_k = 0 and q_k = 1 for every k
+ *   y_b[n]     the derotated sample o + (5 + b) S + cp_len + n, b < 5, n < N, as "link quality" forms it;  ybar = mean_b y_b;
+ *              d_b = y_b - ybar, formed in the time domain, before any transform, as (1/5) sum_c (y_b - y_c): five identical blocks
+ *              give exactly 0
+ *   s_k        (1/4) sum_b |FFT_N(d_b)[k]|^2, the transform unnormalised: the unbiased estimate of the complex noise variance of
+ *              received bin k.  The mean of s_k over all N bins is OFDM_Q_NOISE_VAR.
+ *   sbar       the mean of s_k over all N bins
+ *   q_k        sbar / s_k if s_k > sbar, else 1 (the comparison is false for NaN).  0 <= q_k <= 1; a noiseless frame has q = 1 everywhere.
+ *              The estimate has four degrees of freedom per bin, which is why it may only lower a carrier's weight, never raise it.
+ *   LLR        L = clamp(rint(((llr_scale nd / sum |H|^2) |H_k|^2) q_k Lambda), -127, 127), the f32 products formed in that order
+ *              (the scale of ofdm_rx_llr_batch, one more multiply, then Lambda); 0 when the product is not finite.  Hard decisions,
+ *              equalisation and pilot phase are those of ofdm_rx_llr_batch.
+ * q is homogeneous of degree 0 in the capture and s of degree 2: under a gain +-2^k, q keeps its bits and s is scaled by 4^k exactly.
+ * What the scatter cannot see: an interferer whose phase advances a whole number of turns per symbol (a tone at bin x with x S / N an
+ * integer) is the same in all five blocks and counts as signal; and a tone within ~5 dB of the frame's own power hits the timing
+ * search, the pilots and the channel estimate, which this feature leaves as they are. */
+enum { OFDM_LLRW_CHANNEL = 0, /* w_k alone: the default, bit for bit what the library did before the mode existed */
+       OFDM_LLRW_NOISE = 1    /* w_k q_k */ };
+/* The estimate on its own.  nvar_dev (optional) receives n_frames rows of n_fft floats s_k, weight_dev (optional) as many q_k; bin k of
+ * frame f is element f * n_fft + k.  status_dev and f_delta_dev (NULL: no derotation) are optional.  OFDM_ERR_INVALID: a NULL context,
+ * NULL in_dev or offset_dev (with n_frames > 0), a negative size or frame_len <= 0.  n_frames == 0: OFDM_OK.  One launch
+ * (k_noise_bins), no workspace; the rows' bits do not depend on the grid. */
+int ofdm_rx_noise_bins_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                             const int32_t *offset_dev, const double *f_delta_dev, const int32_t *status_dev /* optional */,
+                             float *nvar_dev /* optional, n_frames * n_fft */, float *weight_dev /* optional, n_frames * n_fft */);
+/* ofdm_rx_llr_batch with the LLR scale of bin k multiplied by bin_weight_dev[f * bin_weight_stride + k] (k_sym<llrw>): arguments and
+ * checks as there; bin_weight_stride must be 0 (one row of n_fft floats shared by every frame) or n_fft (OFDM_ERR_INVALID otherwise).
+ * The weights are taken as they are: nothing holds them to [0, 1].  bin_weight_dev == NULL is ofdm_rx_llr_batch itself: the same
+ * kernel, the same bytes. */
+int ofdm_rx_llr_weighted_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                               int32_t first_symbol, int32_t syms_per_frame, const int32_t *offset_dev, const double *f_delta_dev,
+                               const ofdm_fc32 *hk_dev, int64_t hk_stride, float llr_scale, int8_t *llr_dev, int64_t llr_stride,
+                               const float *bin_weight_dev, int64_t bin_weight_stride);
+/* The mode of a context: OFDM_LLRW_CHANNEL (the default) or OFDM_LLRW_NOISE; any other value is OFDM_ERR_INVALID and changes nothing.
+ * It is not part of ofdm_params.  Under OFDM_LLRW_NOISE every decode entry point that forms LLRs (ofdm_rx_decode_batch, _host, _long,
+ * _long_host, their sc16 forms and ofdm_rx_decode_combine_batch, for every soft ecc, chest_mode and cfo_mode) runs k_noise_bins behind
+ * the channel estimate, over the chain's own offset, f_delta and status, into a workspace of the context, and k_sym<llrw> in place of
+ * k_sym<llr>: the chain is the composition of ofdm_rx_noise_bins_batch, ofdm_rx_llr_weighted_batch and the mode's decoder, bit for bit,
+ * and ofdm_last_dispatch shows both kernels.  A mode that forms no LLRs (ecc 0, 1, 20, 64, 65, 84) is untouched: the same kernels, the
+ * same bytes.  The link-quality rows and the combine weights of ofdm_rx_decode_combine_batch do not change with the mode.  The rule
+ * costs a little in a clean channel near the decoder's waterfall, which is why it is opt-in. */
+int ofdm_set_llr_weight(ofdm_ctx *ctx, int32_t mode);
+int ofdm_get_llr_weight(const ofdm_ctx *ctx, int32_t *mode);
+
 /* ------------------------------------------------------------------ convolutional code (north-star extension; DESIGN.md 3, EXT-2 convolutional code)
  * K = 7, rate 1/2, generators 133 / 171 octal; the definition shared by the kernels and tests/conv_ref.py.
  * Encoder: input bits u_t, t in [0, T): the payload bytes followed by ONE 0x00 tail byte, each byte LSB first, T = 8 (p + 1).

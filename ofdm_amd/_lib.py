@@ -100,6 +100,10 @@ SIGNATURES = {
     "ofdm_rx_llr_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, i64, C.c_float, vp, i64]),
     "ofdm_rx_quality_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, vp, i64, vp, vp]),
     "ofdm_cfo_wide_batch": (C.c_int, [vp, vp, i64, i64, i64, vp, vp, i32, vp, vp, vp]),
+    "ofdm_rx_noise_bins_batch": (C.c_int, [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
+    "ofdm_rx_llr_weighted_batch": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, vp, vp, i64, C.c_float, vp, i64, vp, i64]),
+    "ofdm_set_llr_weight": (C.c_int, [vp, i32]),
+    "ofdm_get_llr_weight": (C.c_int, [vp, C.POINTER(i32)]),
     "ofdm_llr_combine_batch": (C.c_int, [vp, vp, i64, i32, i64, i64, vp, vp, vp, vp, i64, vp]),
     "ofdm_rx_decode_combine_batch": (C.c_int, [vp, vp, i64, i32, i64, i64, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ofdm_sc_correlate_batch": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp, vp]),

@@ -56,6 +56,9 @@ CHEST_LS, CHEST_WLS = 0, 1
 # ofdm_rx_quality_batch: indices into a frame's row of QUALITY_FIELDS floats (EXT-6; tests/quality_ref.py is the definition)
 Q_VALID, Q_NOISE_VAR, Q_GAIN, Q_SNR, Q_LLR_UNIT, Q_EVM2, Q_POINTS = 0, 1, 2, 3, 4, 5, 6
 QUALITY_FIELDS = 8
+# EXT-11 (tests/noise_weight_ref.py is the definition): what the decode chains weigh their LLRs by -- the channel weight alone, or that
+# times q_k = min(1, mean noise / noise of carrier k), measured per frame from the scatter of the five training blocks
+LLRW_CHANNEL, LLRW_NOISE = 0, 1
 # EXT-9: sc16 = interleaved little-endian int16 I/Q (UHD's wire format), int16 arrays / tensors of shape [..., 2]; x = int16 * scale as ONE
 # rounded f32 product (tests/sc16_ref.py is the definition)
 SC16_DEFAULT_SCALE = 1.0 / 32768.0  # OFDM_SC16_DEFAULT_SCALE
@@ -217,7 +220,7 @@ class Context:
                  sync_window_reps: int = 3, sync_backoff: int = 4, cfo_mode: int = CFO_SIGNED,
                  sync_threshold: float = 0.5, use_torch_stream: bool = True, pilots: str = "default",
                  sync_mode: int = SYNC_SCHMIDL_COX, rx_path: int = RX_AUTO, tuning: Optional[dict] = None,
-                 chest_mode: int = CHEST_LS):
+                 chest_mode: int = CHEST_LS, llr_weight: int = LLRW_CHANNEL):
         self.lib = _lib.load()
         if pilots == "stdrng":  # the reference's own tables (restated, unverified) unless explicit tables are given
             sp, st = stdrng_pilots(n_fft)
@@ -259,6 +262,8 @@ class Context:
         if float(np.float32(sync_threshold)) != float(sync_threshold):
             # ofdm_params carries the threshold as a float; a double that a float cannot hold goes through the laboratory key
             self.set_tuning("sync_threshold_bits", int(np.float64(sync_threshold).view(np.int64)))
+        if llr_weight != LLRW_CHANNEL:
+            self.set_llr_weight(llr_weight)
 
     def close(self):
         if getattr(self, "h", None):
@@ -285,6 +290,16 @@ class Context:
     def get_tuning(self, key: str) -> int:
         v = C.c_int64()
         self._ck(self.lib.ofdm_get_tuning(self.h, key.encode(), C.byref(v)), f"ofdm_get_tuning({key})")
+        return int(v.value)
+
+    def set_llr_weight(self, mode: int):
+        """ofdm_set_llr_weight: LLRW_CHANNEL (the default) or LLRW_NOISE -- under it every decode entry point that forms LLRs multiplies
+        them by the per-carrier noise weight of noise_bins (EXT-11)."""
+        self._ck(self.lib.ofdm_set_llr_weight(self.h, int(mode)), "ofdm_set_llr_weight")
+
+    def get_llr_weight(self) -> int:
+        v = C.c_int32()
+        self._ck(self.lib.ofdm_get_llr_weight(self.h, C.byref(v)), "ofdm_get_llr_weight")
         return int(v.value)
 
     def last_dispatch(self) -> str:
@@ -863,11 +878,13 @@ class Context:
 
     def rx_llr(self, frames: torch.Tensor, syms_per_frame: int, first_symbol: int = 0, offset: Optional[torch.Tensor] = None,
                f_delta: Optional[torch.Tensor] = None, hk: Optional[torch.Tensor] = None, frame_len: Optional[int] = None,
-               scale: float = SOFT_LLR_SCALE, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               scale: float = SOFT_LLR_SCALE, out: Optional[torch.Tensor] = None, bin_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
         """ofdm_rx_llr_batch: rx_demod with int8 max-log LLRs out -> [n_frames, syms_per_frame * data_carriers * bps], LLR j = bit j
         of the stream rx_demod packs LSB-first (positive = bit 1; definition in include/ofdm_hip.h).
         out (optional): an int8 [n_frames, that many] tensor or view whose rows are contiguous; its row stride (llr_stride) may exceed
-        the row, and neither it nor the base needs any alignment."""
+        the row, and neither it nor the base needs any alignment.
+        bin_weight (optional, EXT-11): float32 [n_fft] (shared) or [n_frames, n_fft] -- ofdm_rx_llr_weighted_batch: the LLR scale of
+        bin k is multiplied by the frame's weight at k (noise_bins' q)."""
         frames = self._cx(frames)
         f2 = frames.view(-1, frames.shape[-1])
         n, stride = f2.shape
@@ -883,10 +900,37 @@ class Context:
             hk = self._cx(hk)
             hk_stride = self.n_fft if hk.dim() == 2 else 0  # [n_frames, N] per frame, [N] shared
             assert hk.shape[-1] == self.n_fft and (hk.dim() == 1 or hk.shape[0] == n)
+        if bin_weight is not None:
+            bw = bin_weight
+            if bw.dtype != torch.float32 or bw.device != self.device or not bw.is_contiguous() or bw.shape not in ((self.n_fft,), (n, self.n_fft)):
+                raise OfdmError("rx_llr: bin_weight must be a contiguous float32 [n_fft] or [n_frames, n_fft] tensor on the context's device")
+            self._ck(self.lib.ofdm_rx_llr_weighted_batch(self.h, _dev(f2), n, stride, stride if frame_len is None else frame_len, first_symbol,
+                                                         syms_per_frame, _dev(offset), _dev(f_delta), _dev(hk), hk_stride, float(scale),
+                                                         _dev(out), llr_stride, _dev(bw), self.n_fft if bw.dim() == 2 else 0), "rx_llr_weighted")
+            return out
         self._ck(self.lib.ofdm_rx_llr_batch(self.h, _dev(f2), n, stride, stride if frame_len is None else frame_len, first_symbol,
                                             syms_per_frame, _dev(offset), _dev(f_delta), _dev(hk), hk_stride, float(scale), _dev(out), llr_stride),
                  "rx_llr")
         return out
+
+    def noise_bins(self, frames: torch.Tensor, offset: torch.Tensor, f_delta: Optional[torch.Tensor] = None,
+                   status: Optional[torch.Tensor] = None, frame_len: Optional[int] = None) -> dict:
+        """ofdm_rx_noise_bins_batch (EXT-11): per frame the noise variance of every received bin from the scatter of the five training
+        blocks at offset, and the LLR weight it gives -> {nvar: float32 [n_frames, n_fft] = s_k, weight: float32 [n_frames, n_fft] =
+        q_k = mean(s) / s_k where s_k > mean(s), else 1}.  status (optional): frames with status != 0 are not read (s = 0, q = 1), as are
+        frames whose training blocks the capture cuts.  Works whatever the context's llr_weight.  Definition: include/ofdm_hip.h,
+        tests/noise_weight_ref.py."""
+        frames = self._cx(frames)
+        f2 = frames.view(-1, frames.shape[-1])
+        n, stride = f2.shape
+        for name, t, dt in (("offset", offset, torch.int32), ("f_delta", f_delta, torch.float64), ("status", status, torch.int32)):
+            if (t is None and name == "offset") or (t is not None and (t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.numel() != n)):
+                raise OfdmError(f"noise_bins: {name} must be a contiguous {dt} tensor of n_frames elements on the context's device")
+        nvar = self.empty((n, self.n_fft), torch.float32)
+        weight = self.empty((n, self.n_fft), torch.float32)
+        self._ck(self.lib.ofdm_rx_noise_bins_batch(self.h, _dev(f2), n, stride, stride if frame_len is None else frame_len, _dev(offset),
+                                                   _dev(f_delta), _dev(status), _dev(nvar), _dev(weight)), "rx_noise_bins")
+        return {"nvar": nvar, "weight": weight}
 
     def frame_points(self, payload_bytes: int) -> int:
         """Occupied constellation points of a frame of payload_bytes: ceil(8 (16 + coded_len(payload_bytes)) / bps), the 16-byte length

@@ -144,8 +144,10 @@ struct SymParams {
     // modulation / TX
     int bps = 1;
     int guard = 0;
-    const uint8_t *payload = nullptr;
-    long long payload_stride = 0;
+    // (k_sym<llrw> reads no payload: there the two words hold the rows of per-bin LLR weights, EXT-11.  The struct keeps its layout,
+    // and with it every kernel that takes it keeps its kernel descriptor.)
+    union { const uint8_t *payload = nullptr; const float *bin_weight; };
+    union { long long payload_stride = 0; long long bin_weight_stride; }; // bin_weight_stride: floats between the frames' rows, 0 = one shared row
     const int32_t *payload_len = nullptr;
     int payload_bytes = 0;
     unsigned *frame_max = nullptr; // per-frame max(0, re, im) as float bits
@@ -244,6 +246,8 @@ hipError_t run_chest(int n, const SymParams &p, hipStream_t st, int num_cu);
 hipError_t run_tx_symbols(int n, const SymParams &p, hipStream_t st, int num_cu);
 // LLR demod: the RX demod chain with int8 max-log LLRs out (p.llr) and, when p.out_bytes is set, the hard bytes too
 hipError_t run_llr(int n, const SymParams &p, hipStream_t st, int num_cu);
+// EXT-11: run_llr with the LLR scale of bin k multiplied by p.bin_weight[f * p.bin_weight_stride + k] (k_sym<llrw>)
+hipError_t run_llrw(int n, const SymParams &p, hipStream_t st, int num_cu);
 
 // ---- EXT-6 link quality (ofdm_rx_quality_batch; kernels_quality.hip, definition: tests/quality_ref.py)
 // k_linkq: one row of kQualityFields floats per frame from the five training blocks (noise variance, gain, SNR, LLR unit) and the
@@ -318,6 +322,26 @@ struct CfoWideParams {
     float *metric = nullptr;             // optional: [n_frames][2] = G of m, the largest G among the other hypotheses
 };
 hipError_t run_cfo_wide(int n, const CfoWideParams &p, hipStream_t st, int num_cu);
+
+// ---- EXT-11 noise-aware LLR weights (ofdm_rx_noise_bins_batch and the OFDM_LLRW_NOISE receive mode; kernels_noise.hip, definition:
+// tests/noise_weight_ref.py)
+// k_noise_bins: per frame the noise variance of every received bin from the scatter of the five training blocks, s_k = (1/4) sum_b
+// |FFT(y_b - ybar)[k]|^2, and the weight q_k = mean(s) / s_k where s_k > mean(s), else 1.  A frame that is not tested (status[f] != 0, or
+// the five training blocks not wholly inside the capture) is not read and gets s = 0, q = 1.
+struct NoiseBinsParams {
+    const Tuning *tune = nullptr;
+    Trace *trace = nullptr;
+    const float2 *in = nullptr;
+    long long n_frames = 0, frame_stride = 0, frame_len = 0;
+    int sym_len = 0;                     // S = N + CP
+    const int32_t *offset = nullptr;
+    const double *f_delta = nullptr;     // optional
+    const int32_t *status = nullptr;     // optional
+    const float2 *tw = nullptr;
+    float *nvar = nullptr;               // optional: [n_frames][N] = s_k
+    float *weight = nullptr;             // optional: [n_frames][N] = q_k
+};
+hipError_t run_noise_bins(int n, const NoiseBinsParams &p, hipStream_t st, int num_cu);
 
 // ---- Schmidl-Cox (kernels_sync.hip)
 struct ScParams {

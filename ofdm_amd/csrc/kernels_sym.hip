@@ -14,7 +14,7 @@
 
 namespace ofdm {
 
-enum { M_FFT = 0, M_IFFT = 1, M_IFFT_CP = 2, M_DEMOD = 3, M_CHEST = 4, M_TX = 5, M_LLR = 6 };
+enum { M_FFT = 0, M_IFFT = 1, M_IFFT_CP = 2, M_DEMOD = 3, M_CHEST = 4, M_TX = 5, M_LLR = 6, M_LLRW = 7 };
 
 template <int N, int MODE>
 __global__ __launch_bounds__(Plan<N>::WG) void k_sym(SymParams p) {
@@ -24,9 +24,10 @@ __global__ __launch_bounds__(Plan<N>::WG) void k_sym(SymParams p) {
     constexpr int K = N / 64; // carrier-map tiling factor (EXT-4)
 
     __shared__ cf lds[G * P::LDS_SYM];
-    constexpr bool RX = (MODE == M_DEMOD || MODE == M_LLR); // the receive body; M_LLR adds the LLR epilogue
+    constexpr bool LLR = (MODE == M_LLR || MODE == M_LLRW); // M_LLRW (EXT-11): M_LLR with the scale of every bin times the frame's q at that bin
+    constexpr bool RX = (MODE == M_DEMOD || LLR);           // the receive body; M_LLR adds the LLR epilogue
     __shared__ unsigned char idx_lds[RX ? G * N : 4];
-    __shared__ __align__(16) int8_t llr_lds[(MODE == M_LLR) ? G * N * 8 : 16]; // M_LLR: a symbol's LLRs (<= N points x 8 bits)
+    __shared__ __align__(16) int8_t llr_lds[LLR ? G * N * 8 : 16]; // M_LLR: a symbol's LLRs (<= N points x 8 bits)
     __shared__ float red[(T > 64) ? G * (T / 64) : 1];
     __shared__ __align__(4) unsigned char txb[(MODE == M_TX) ? G * (N + 8) : 4]; // TX: the symbol's slice of the byte stream
 
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(Plan<N>::WG) void k_sym(SymParams p) {
         } else if (RX) {
             const bool live = valid && !(p.nsym_frame && k >= p.nsym_frame[f]);
             const int nd = p.guard ? 48 * K : N;
-            float hn[MODE == M_LLR ? 8 : 1]; // M_LLR: |H|^2 of the eight bins
+            float hn[LLR ? 8 : 1]; // M_LLR: |H|^2 of the eight bins
             // equalise: Y[k] /= H[k] (src/receiver.rs:68-70)
             if (p.hk && live) {
                 const cf *h = p.hk + f * p.hk_stride;
@@ -259,15 +260,15 @@ __global__ __launch_bounds__(Plan<N>::WG) void k_sym(SymParams p) {
                 for (int m = 0; m < 8; ++m) {
                     cf hh = h[t + m * T];
                     const float n2 = hh.x * hh.x + hh.y * hh.y;
-                    if (MODE == M_LLR) hn[m] = n2;
+                    if (LLR) hn[m] = n2;
                     const float rn = __builtin_amdgcn_rcpf(n2); // as k_rxframe64 (1 ulp)
                     cf q = cmulc(v[m], hh);
                     v[m] = make_float2(q.x * rn, q.y * rn);
                 }
             }
             // M_LLR: s_k = scale w_k, w_k = |H_k|^2 / mean over the data bins of |H|^2 (1 without H); one symbol_sum per symbol
-            float sk[MODE == M_LLR ? 8 : 1];
-            if (MODE == M_LLR) {
+            float sk[LLR ? 8 : 1];
+            if (LLR) {
                 if (p.hk) {
                     float acc = 0.f;
 #pragma unroll
@@ -282,6 +283,11 @@ __global__ __launch_bounds__(Plan<N>::WG) void k_sym(SymParams p) {
 #pragma unroll
                     for (int m = 0; m < 8; ++m) sk[m] = p.llr_scale;
                 }
+            }
+            if (MODE == M_LLRW && live) { // one more f32 multiply, behind the channel weight
+                const float *bw = p.bin_weight + f * p.bin_weight_stride;
+#pragma unroll
+                for (int m = 0; m < 8; ++m) sk[m] *= bw[t + m * T];
             }
             // decode_block (src/receiver.rs:106-145): mean pilot angle, rotate the data points by -phase
             if (p.guard) {
@@ -306,11 +312,11 @@ __global__ __launch_bounds__(Plan<N>::WG) void k_sym(SymParams p) {
                     int q = p.guard ? data_classes_below64(c) * K + (t % K) : (t + m * T);
                     ib[q] = (unsigned char)demap_point(v[m], p.bps);
                     if (p.soft && live) p.soft[(f * p.syms_per_frame + k) * (long long)nd + q] = v[m];
-                    if (MODE == M_LLR) llr_point(v[m], p.bps, sk[m], lb + q * p.bps);
+                    if (LLR) llr_point(v[m], p.bps, sk[m], lb + q * p.bps);
                 }
             }
             group_sync<T>();
-            if (MODE == M_LLR && live) {
+            if (LLR && live) {
                 // the symbol's nd * bps LLRs (a multiple of 16 bytes) leave in 16-byte stores when the rows allow it
                 const int nl = nd * p.bps;
                 int8_t *dst = p.llr + f * p.llr_stride + (long long)k * nl;
@@ -362,7 +368,7 @@ template <int N, int MODE> static hipError_t launch_sym(const SymParams &p, hipS
     if (total <= 0) return hipSuccess;
     // persistent: ~8 workgroups per CU, grid-stride over symbol groups
     const int grid = (int)persistent_grid((total + P::G - 1) / P::G, (long long)num_cu * 8, tuning_or_default(p.tune));
-    static const char *const names[] = {"k_sym<fft>", "k_sym<ifft>", "k_sym<ifft_cp>", "k_sym<demod>", "k_sym<chest>", "k_sym<tx>", "k_sym<llr>"};
+    static const char *const names[] = {"k_sym<fft>", "k_sym<ifft>", "k_sym<ifft_cp>", "k_sym<demod>", "k_sym<chest>", "k_sym<tx>", "k_sym<llr>", "k_sym<llrw>"};
     trace_add(p.trace, names[MODE]);
     hipLaunchKernelGGL((k_sym<N, MODE>), dim3(grid), dim3(P::WG), 0, st, p);
     return hipGetLastError();
@@ -381,5 +387,6 @@ hipError_t run_demod(int n, const SymParams &p, hipStream_t st, int cu) { return
 hipError_t run_chest(int n, const SymParams &p, hipStream_t st, int cu) { return dispatch_n<M_CHEST>(n, p, st, cu); }
 hipError_t run_tx_symbols(int n, const SymParams &p, hipStream_t st, int cu) { return dispatch_n<M_TX>(n, p, st, cu); }
 hipError_t run_llr(int n, const SymParams &p, hipStream_t st, int cu) { return dispatch_n<M_LLR>(n, p, st, cu); }
+hipError_t run_llrw(int n, const SymParams &p, hipStream_t st, int cu) { return dispatch_n<M_LLRW>(n, p, st, cu); }
 
 } // namespace ofdm

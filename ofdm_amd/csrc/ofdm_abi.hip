@@ -1150,28 +1150,91 @@ int ofdm_rx_demod_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int6
 // int8 max-log LLRs in place of the hard bytes of ofdm_rx_demod_batch: k_sym<llr> (no shape-specialised kernel has the epilogue yet)
 static int llr_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len, int first_symbol,
                    int syms_per_frame, const int32_t *offset, const double *f_delta, const int32_t *nsym_frame, const float2 *hk,
-                   int64_t hk_stride, float llr_scale, int8_t *llr, int64_t llr_stride, uint8_t *hard, int64_t hard_stride, bool trace) {
+                   int64_t hk_stride, float llr_scale, int8_t *llr, int64_t llr_stride, uint8_t *hard, int64_t hard_stride, bool trace,
+                   const float *bin_weight = nullptr, int64_t bin_weight_stride = 0) {
     SymParams p = rx_params(c, in, n_frames, frame_stride, frame_len, offset, f_delta, nsym_frame, hard, hard_stride);
     if (!trace) p.trace = nullptr;
     p.first_symbol = first_symbol; p.syms_per_frame = syms_per_frame; p.in_sym_stride = c->S(); p.in_skip = c->prm.cp_len;
     p.hk = hk; p.hk_stride = hk_stride;
     p.llr = llr; p.llr_scale = llr_scale; p.llr_stride = llr_stride;
+    if (bin_weight) { // EXT-11: k_sym<llrw>
+        p.bin_weight = bin_weight; p.bin_weight_stride = bin_weight_stride;
+        HIP_TRY(c, run_llrw(c->prm.n_fft, p, c->stream, c->num_cu));
+        return OFDM_OK;
+    }
     HIP_TRY(c, run_llr(c->prm.n_fft, p, c->stream, c->num_cu));
     return OFDM_OK;
 }
 int ofdm_rx_llr_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
                       int32_t first_symbol, int32_t syms_per_frame, const int32_t *offset, const double *f_delta,
                       const ofdm_fc32 *hk, int64_t hk_stride, float llr_scale, int8_t *llr, int64_t llr_stride) {
+    return ofdm_rx_llr_weighted_batch(c, in, n_frames, frame_stride, frame_len, first_symbol, syms_per_frame, offset, f_delta, hk, hk_stride,
+                                      llr_scale, llr, llr_stride, nullptr, 0);
+}
+// EXT-11: the same with per-bin weights (k_sym<llrw>); without them it is ofdm_rx_llr_batch
+int ofdm_rx_llr_weighted_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                               int32_t first_symbol, int32_t syms_per_frame, const int32_t *offset, const double *f_delta,
+                               const ofdm_fc32 *hk, int64_t hk_stride, float llr_scale, int8_t *llr, int64_t llr_stride,
+                               const float *bin_weight, int64_t bin_weight_stride) {
     if (!c || n_frames < 0 || syms_per_frame < 0 || first_symbol < 0 || frame_len <= 0) return OFDM_ERR_INVALID;
     if (!(llr_scale > 0.f && llr_scale <= 3.402823466e38f)) return OFDM_ERR_INVALID; // finite and > 0 (NaN fails both)
     if (n_frames && syms_per_frame && (!in || !llr)) return OFDM_ERR_INVALID;
     if (llr_stride < (int64_t)syms_per_frame * c->carriers() * c->prm.modulation) return OFDM_ERR_INVALID;
     if (hk && hk_stride != 0 && hk_stride != c->prm.n_fft) return OFDM_ERR_INVALID;
+    if (bin_weight && bin_weight_stride != 0 && bin_weight_stride != c->prm.n_fft) return OFDM_ERR_INVALID;
     if (!n_frames || !syms_per_frame) return OFDM_OK;
     DeviceGuard dev_guard(c->device);
     c->trace.reset();
     return llr_run(c, reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, first_symbol, syms_per_frame, offset,
-                   f_delta, nullptr, reinterpret_cast<const float2 *>(hk), hk_stride, llr_scale, llr, llr_stride, nullptr, 0, true);
+                   f_delta, nullptr, reinterpret_cast<const float2 *>(hk), hk_stride, llr_scale, llr, llr_stride, nullptr, 0, true,
+                   bin_weight, bin_weight_stride);
+}
+
+// EXT-11 noise-aware LLR weights: one launch of k_noise_bins, a row of n_fft floats per frame (include/ofdm_hip.h,
+// tests/noise_weight_ref.py)
+static int noise_bins_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len, const int32_t *offset,
+                          const double *f_delta, const int32_t *status, float *nvar, float *weight) {
+    NoiseBinsParams p;
+    p.tune = &c->tune; p.trace = &c->trace;
+    p.in = in; p.n_frames = n_frames; p.frame_stride = frame_stride; p.frame_len = frame_len;
+    p.sym_len = c->S();
+    p.offset = offset; p.f_delta = f_delta; p.status = status;
+    p.tw = c->d_tw;
+    p.nvar = nvar; p.weight = weight;
+    HIP_TRY(c, run_noise_bins(c->prm.n_fft, p, c->stream, c->num_cu));
+    return OFDM_OK;
+}
+int ofdm_rx_noise_bins_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len, const int32_t *offset,
+                             const double *f_delta, const int32_t *status, float *nvar, float *weight) {
+    if (!c || n_frames < 0 || frame_len <= 0 || frame_stride < 0) return OFDM_ERR_INVALID;
+    if (n_frames && (!in || !offset)) return OFDM_ERR_INVALID;
+    if (!n_frames) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    return noise_bins_run(c, reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, offset, f_delta, status, nvar, weight);
+}
+int ofdm_set_llr_weight(ofdm_ctx *c, int32_t mode) {
+    if (!c || (mode != OFDM_LLRW_CHANNEL && mode != OFDM_LLRW_NOISE)) return OFDM_ERR_INVALID;
+    c->llr_weight = mode;
+    return OFDM_OK;
+}
+int ofdm_get_llr_weight(const ofdm_ctx *c, int32_t *mode) {
+    if (!c || !mode) return OFDM_ERR_INVALID;
+    *mode = c->llr_weight;
+    return OFDM_OK;
+}
+// The weights of the decode chains under OFDM_LLRW_NOISE: k_noise_bins over the chain's rows (offset, f_delta and status as the front
+// end left them), behind the channel estimate, into the context's workspace; *q stays nullptr under OFDM_LLRW_CHANNEL
+static int rx_noise_weights(ofdm_ctx *c, const float2 *in, int64_t n_rows, int64_t frame_stride, int64_t frame_len, const int32_t *offset,
+                            const double *f_delta, const int32_t *status, const float **q) {
+    *q = nullptr;
+    if (c->llr_weight != OFDM_LLRW_NOISE) return OFDM_OK;
+    void *w_q;
+    int rc;
+    if ((rc = ws_get(c, kWsNoiseWeight, sizeof(float) * (size_t)c->prm.n_fft * (size_t)n_rows, &w_q))) return rc;
+    if ((rc = noise_bins_run(c, in, n_rows, frame_stride, frame_len, offset, f_delta, status, nullptr, (float *)w_q))) return rc;
+    *q = (const float *)w_q;
+    return OFDM_OK;
 }
 
 // EXT-6 link quality: one launch of k_linkq, a row per frame (include/ofdm_hip.h, tests/quality_ref.py)
@@ -1363,7 +1426,7 @@ struct DecodeCall {
     const KnownSync *known;
 };
 // What steps 1 - 4 of the chain leave to the soft finishing kernels (raw: the hard bytes, for the length header)
-struct SoftInput { int32_t *offs; double *fd; const int32_t *nsym; const float2 *hk; uint8_t *raw; int64_t raw_stride, body_steps; };
+struct SoftInput { int32_t *offs; double *fd; const int32_t *nsym; const float2 *hk; uint8_t *raw; int64_t raw_stride, body_steps; const float *q; };
 } // namespace
 // OFDM_ECC_HAMMING74_SOFT decode: the LLR workspace (one frame chunk of LLR rows) never exceeds this
 static const int64_t kSoftLlrBytes = 256ll << 20;
@@ -1429,7 +1492,8 @@ static int rx_finish_soft(ofdm_ctx *c, const DecodeCall &d, const SoftInput &s) 
         const int32_t *nsym = s.nsym + f0;
         const uint8_t *raw = s.raw + f0 * s.raw_stride;
         rc = llr_run(c, d.in + f0 * d.frame_stride, nf, d.frame_stride, d.frame_len, 10, d.max_symbols, s.offs + f0, s.fd + f0, nsym,
-                     s.hk + f0 * N, N, OFDM_SOFT_LLR_SCALE, (int8_t *)w_llr, llr_stride, s.raw + f0 * s.raw_stride, s.raw_stride, f0 == 0);
+                     s.hk + f0 * N, N, OFDM_SOFT_LLR_SCALE, (int8_t *)w_llr, llr_stride, s.raw + f0 * s.raw_stride, s.raw_stride, f0 == 0,
+                     s.q ? s.q + f0 * N : nullptr, N);
         if (rc) return rc;
         if (f0 == 0) c->trace.add(name);
         if ((rc = soft_finish_chunk(c, d, f0, nf, llr, llr_stride, nsym, raw, s.raw_stride, vp, v_blocks))) return rc;
@@ -1585,7 +1649,9 @@ static int rx_decode_inner(ofdm_ctx *c, const DecodeCall &d) {
         const float2 *hk = nullptr;
         if ((rc = rx_channel_estimate(c, d, fe, &hk))) return rc;
         if (soft) {
-            const SoftInput si{offs, fd, (const int32_t *)w_nsym, hk, (uint8_t *)w_raw, raw_stride, body_steps};
+            const float *q = nullptr; // EXT-11: the per-bin LLR weights under OFDM_LLRW_NOISE
+            if ((rc = rx_noise_weights(c, x, n_frames, frame_stride, frame_len, offs, fd, status, &q))) return rc;
+            const SoftInput si{offs, fd, (const int32_t *)w_nsym, hk, (uint8_t *)w_raw, raw_stride, body_steps, q};
             return rx_finish_soft(c, d, si);
         }
         rc = demod_run(c, x, n_frames, frame_stride, frame_len, 10, max_symbols, offs, fd, (const int32_t *)w_nsym,
@@ -1858,6 +1924,8 @@ static int rx_decode_combine_inner(ofdm_ctx *c, const DecodeCall &d, const Combi
     if ((rc = rx_channel_estimate(c, b, fe, &hk))) return rc;
     // 2. link quality from the training blocks
     if ((rc = linkq_run(c, b.in, rows, b.frame_stride, b.frame_len, 10, 0, nullptr, fe.offs, fe.fd, hk, N, bst, quality))) return rc;
+    const float *q = nullptr; // EXT-11: the per-bin LLR weights of every branch row under OFDM_LLRW_NOISE
+    if ((rc = rx_noise_weights(c, b.in, rows, b.frame_stride, b.frame_len, fe.offs, fe.fd, bst, &q))) return rc;
     // 3 - 5. per chunk of frames: LLRs of the branch rows, the combined rows behind them, the finishing kernel
     const int64_t llr_stride = (llr_row + 15) & ~(int64_t)15;
     int64_t chunk = c->tune.soft_chunk_frames > 0 ? c->tune.soft_chunk_frames : kSoftLlrBytes / llr_stride;
@@ -1875,7 +1943,7 @@ static int rx_decode_combine_inner(ofdm_ctx *c, const DecodeCall &d, const Combi
     for (int64_t f0 = 0; f0 < d.n_frames; f0 += chunk) {
         const int64_t nf = d.n_frames - f0 < chunk ? d.n_frames - f0 : chunk, r0 = f0 * R;
         rc = llr_run(c, b.in + r0 * b.frame_stride, nf * R, b.frame_stride, b.frame_len, 10, d.max_symbols, fe.offs + r0, fe.fd + r0, fe.nsym + r0,
-                     hk + r0 * N, N, OFDM_SOFT_LLR_SCALE, branch_llr, llr_stride, nullptr, 0, f0 == 0);
+                     hk + r0 * N, N, OFDM_SOFT_LLR_SCALE, branch_llr, llr_stride, nullptr, 0, f0 == 0, q ? q + r0 * N : nullptr, N);
         if (rc) return rc;
         CombineParams p;
         p.tune = &c->tune; p.trace = f0 == 0 ? &c->trace : nullptr;

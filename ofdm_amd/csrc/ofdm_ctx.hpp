@@ -85,6 +85,7 @@ enum WsRole {
     kWsSc16,                     // EXT-9: one chunk of frames widened from sc16, the input of the fc32 path behind the sc16 entry points
     kWsTxSc16,                   // EXT-10: one chunk of fc32 frames out of the encode chain, the input of k_sc16_narrow (ofdm_tx_encode_sc16_batch)
     kWsLongSc16,                 // EXT-10: one long sc16 capture widened, the input of the fc32 long decode (ofdm_rx_decode_long_sc16[_host])
+    kWsNoiseWeight,              // EXT-11: per row of the decode chain the n_fft LLR weights q_k of k_noise_bins, read by k_sym<llrw> (OFDM_LLRW_NOISE)
     kWsRoles
 };
 
@@ -109,6 +110,7 @@ struct ofdm_ctx {
     float2 *d_chest_mt = nullptr;       // N R^-1, transposed: [L_h][L_h]
     // EXT-8 wide CFO acquisition: built by ofdm_create when cfo_mode is OFDM_CFO_WIDE, else by the first ofdm_cfo_wide_batch
     float2 *d_trn = nullptr;            // training[k]
+    int llr_weight = OFDM_LLRW_CHANNEL; // EXT-11 (ofdm_set_llr_weight): what the decode chains weigh their LLRs by
     ofdm::Tuning tune;                  // ofdm_set_tuning: per-context A/B switches and grid shapes (no environment variable is read)
     double sync_threshold_f64 = 0.0;    // ofdm_set_tuning "sync_threshold_bits": the packet-detect threshold as a double (0 = prm.sync_threshold, a float)
     ofdm::Trace trace;                  // ofdm_last_dispatch: the kernels the last entry point launched
