@@ -876,6 +876,39 @@ int ofdm_rx_decode_long(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_sample
 int ofdm_rx_decode_long_host(ofdm_ctx *ctx, const ofdm_fc32 *in_host, int64_t n_samples, int32_t max_symbols, uint8_t *out_host,
                              int64_t out_cap, int32_t *out_len, int32_t *status, int64_t *offset, double *f_delta, float *metric);
 
+/* ------------------------------------------------------------------ every packet of one long capture (EXT-12)
+ * A capture holds many packets; the calls above find the first one of a lag range.  ofdm_sc_scan_long finds every detection of
+ * [lag_lo, lag_hi) in one pass (k_sc_mark + k_sc_walk + k_sc_peaks: three launches and one synchronisation whatever the count).
+ * OFDM_SYNC_SCHMIDL_COX only; any other sync mode: OFDM_ERR_UNSUPPORTED.
+ *
+ * The rule, in the notation of the oracle's orc_sc_sync (L = S, W = sync_window_reps L, num = |P|^2, den = E R, thr the context's
+ * threshold, valid = n_samples - W - L + 1, lag_hi <= 0 or > valid: valid):
+ *     lo_0 = lag_lo
+ *     detection k:  d1_k = the first lag d in [lo_k, lag_hi) with den(d) > 0 and num(d) >= thr den(d)      (none: the scan ends)
+ *                   d_hat_k = the first maximum of M = num / den over [d1_k, min(d1_k + W, valid - 1)], compared as orc_sc_sync
+ *                             compares (num bden > bnum den); the window may reach past lag_hi
+ *                   f_delta_k = atan2(P(d_hat_k)) / L,  metric_k = num / den at d_hat_k
+ *     lo_{k+1} = d1_k + holdoff                                                                              (holdoff >= 1)
+ *     the scan ends after max_det detections; *more = 1 iff a further detection exists
+ * For every k this is orc_sc_sync(capture[lo_k:]) re-based by lo_k, and, whenever lag_hi > d1_k, the answer of
+ * ofdm_sc_correlate_long(lag_lo = lo_k, lag_hi).  Every lag's sums are the oracle's own, bit for bit (the W products of that window,
+ * in order), so d1 and d_hat are the oracle's at any margin; they depend on the capture and the rule only, never on the grid.
+ *
+ * holdoff is the caller's knowledge of the traffic: with fixed-size frames ofdm_frame_samples(payload) - W or a little less; without
+ * that knowledge a small value, and the decode's status sorts out a false detection inside a payload (the framed, LDPC and frame-check
+ * modes report it as OFDM_FRAME_HEADER / OFDM_FRAME_FCS).  holdoff = 1 on a plateau yields one detection per crossing lag.
+ *
+ * in_dev is a DEVICE pointer; d1, d_hat (int64), f_delta, metric (max_det entries each; d1, f_delta, metric optional), n_det and more
+ * (optional) are HOST pointers; entries at or beyond *n_det are not written.  Synchronous.  The next search would start at
+ * d1[n_det - 1] + holdoff: with *more set, call again with that lag_lo.  Decode packet k with ofdm_rx_decode_long(lag_lo = lo_k, lag_hi).
+ * OFDM_ERR_INVALID: holdoff < 1, max_det < 0, n_samples < 0, lag_lo < 0, a NULL in_dev with n_samples > 0, a NULL d_hat or n_det.
+ * OFDM_ERR_UNSUPPORTED: n_samples > 2^40.  A capture with no valid lag: *n_det = 0 and OFDM_OK. */
+int ofdm_sc_scan_long(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_samples, int64_t lag_lo, int64_t lag_hi, int64_t holdoff,
+                      int64_t max_det, int64_t *d1, int64_t *d_hat, double *f_delta, float *metric, int64_t *n_det, int32_t *more);
+/* the same on a capture in host memory (uploaded as ofdm_rx_decode_long_host uploads its capture; pinned memory is DMA-ed in place) */
+int ofdm_sc_scan_long_host(ofdm_ctx *ctx, const ofdm_fc32 *in_host, int64_t n_samples, int64_t lag_lo, int64_t lag_hi, int64_t holdoff,
+                           int64_t max_det, int64_t *d1, int64_t *d_hat, double *f_delta, float *metric, int64_t *n_det, int32_t *more);
+
 /* ------------------------------------------------------------------ sc16 receive input (EXT-9)
  * Radios deliver sc16 -- interleaved little-endian int16 I and Q, 4 bytes a sample: UHD's wire format and that of most recorded
  * captures -- not fc32.  The sample format is a property of a CALL, not of a context: the same context decodes fc32 and sc16.

@@ -53,6 +53,7 @@ class Context {
         p.chest_mode = chest_mode; // OFDM_CHEST_WLS: decode works with the denoised channel estimate (include/ofdm_hip.h, EXT-5)
         n_fft_ = n_fft;
         ecc_ = ecc;
+        window_reps_ = p.sync_window_reps;
         if (pilots == Pilots::StdRng) {
             std::vector<double> pre(2 * (size_t)(n_fft + n_fft / 4)), trn(2 * (size_t)n_fft);
             check(ofdm_stdrng_pilots(n_fft, n_fft / 4, pre.data(), trn.data()), "ofdm_stdrng_pilots");
@@ -142,6 +143,56 @@ class Context {
     // EXT-10: decode of an sc16 capture (x = int16 * scale, widened on the device)
     std::vector<uint8_t> decode_sc16(const std::vector<ofdm_sc16> &samples, int32_t max_symbols = 0, float scale = OFDM_SC16_DEFAULT_SCALE) {
         return bytes_or_throw(decode_capture_sc16(samples.data(), (int64_t)samples.size(), max_symbols, scale));
+    }
+    // EXT-12: every detection of one long capture under the holdoff rule (ofdm_sc_scan_long_host, include/ofdm_hip.h): detection k has
+    // its first crossing at d1[k] and its peak at d_hat[k]; the search for it started at lo(k).  more: max_det stopped the scan.
+    struct Detections {
+        std::vector<int64_t> d1, d_hat; std::vector<double> f_delta; std::vector<float> metric;
+        int64_t lag_lo = 0, holdoff = 1; bool more = false;
+        size_t size() const { return d_hat.size(); }
+        int64_t lo(size_t k) const { return k ? d1[k - 1] + holdoff : lag_lo; }
+    };
+    Detections scan_capture(const ofdm_fc32 *fc, int64_t n, int64_t holdoff, int64_t max_det, int64_t lag_lo = 0, int64_t lag_hi = 0) {
+        Detections r;
+        scan_sized(r, holdoff, max_det, lag_lo, [&](int64_t *nd, int32_t *more) {
+            check(ofdm_sc_scan_long_host(ctx_, fc, n, lag_lo, lag_hi, holdoff, max_det, r.d1.data(), r.d_hat.data(), r.f_delta.data(),
+                                         r.metric.data(), nd, more), "ofdm_sc_scan_long_host");
+        });
+        return r;
+    }
+    // the shortest frame's holdoff: 11 S - W, at least 1 (a header and one data symbol; pass frame_samples(payload) - W for fixed-size frames)
+    int64_t default_holdoff() const { return std::max<int64_t>((int64_t)(11 - window_reps_) * symbol_len(), 1); }
+    // Every packet of one long capture: one upload, one scan, then ofdm_rx_decode_long(lag_lo = lo(k)) per detection.  Nothing is thrown
+    // for a packet that fails: its status is in the result (a false detection inside a payload shows as OFDM_FRAME_HEADER /
+    // OFDM_FRAME_FCS in the framed, LDPC and frame-check modes).  holdoff <= 0: default_holdoff().  max_symbols: the data symbols of the
+    // longest frame expected (<= 0: up to the capture's end, as decode_capture -- a demod of everything behind every packet).
+    std::vector<Decoded> decode_all(const ofdm_fc32 *fc, int64_t n, int64_t holdoff = 0, int64_t max_packets = 4096, int32_t max_symbols = 0) {
+        if (holdoff <= 0) holdoff = default_holdoff();
+        DevBuf din(ctx_, (size_t)std::max<int64_t>(n, 1) * sizeof(ofdm_fc32) + 64);
+        if (n > 0) check(ofdm_memcpy_h2d(ctx_, din.p, fc, (size_t)n * sizeof(ofdm_fc32)), "h2d");
+        Detections det;
+        scan_sized(det, holdoff, max_packets, 0, [&](int64_t *nd, int32_t *more) {
+            check(ofdm_sc_scan_long(ctx_, (const ofdm_fc32 *)din.p, n, 0, 0, holdoff, max_packets, det.d1.data(), det.d_hat.data(),
+                                    det.f_delta.data(), det.metric.data(), nd, more), "ofdm_sc_scan_long");
+        });
+        std::vector<Decoded> out;
+        for (size_t k = 0; k < det.size(); ++k)
+            out.push_back(decode_capture_as(n, max_symbols, [&](int32_t ms, Decoded &r, int64_t ob, int32_t *len) {
+                DevBuf dout(ctx_, (size_t)ob + 64);
+                check(ofdm_rx_decode_long(ctx_, (const ofdm_fc32 *)din.p, n, det.lo(k), 0, -1, ms, (uint8_t *)dout.p, ob, len, &r.status, &r.offset,
+                                          &r.f_delta, &r.metric), "ofdm_rx_decode_long");
+                if (r.status == OFDM_FRAME_OK && *len > 0) check(ofdm_memcpy_d2h(ctx_, r.bytes.data(), dout.p, (size_t)*len), "d2h");
+            }));
+        return out;
+    }
+    template <class Call> void scan_sized(Detections &r, int64_t holdoff, int64_t max_det, int64_t lag_lo, Call &&call) {
+        const size_t cap = (size_t)std::max<int64_t>(max_det, 1);
+        r.d1.resize(cap); r.d_hat.resize(cap); r.f_delta.resize(cap); r.metric.resize(cap);
+        r.lag_lo = lag_lo; r.holdoff = holdoff;
+        int64_t nd = 0; int32_t more = 0;
+        call(&nd, &more);
+        r.d1.resize((size_t)nd); r.d_hat.resize((size_t)nd); r.f_delta.resize((size_t)nd); r.metric.resize((size_t)nd);
+        r.more = more != 0;
     }
     static std::vector<uint8_t> bytes_or_throw(Decoded r) { // the reference's Err / None as exceptions
         if (r.status == OFDM_FRAME_SHORT) throw Error("Input not long enough, bailing early"); // src/receiver.rs:27-29
@@ -513,6 +564,7 @@ class Context {
     ofdm_ctx *ctx_ = nullptr;
     int ecc_ = OFDM_ECC_NONE;
     int n_fft_ = 64;
+    int window_reps_ = 3;
 };
 
 // One context per (thread, parameter set), created on first use and kept: the reference's free functions are called once per

@@ -9,7 +9,7 @@ from ._lib import load, LIB_PATH, Params, SIGNATURES  # noqa: F401
 
 def __getattr__(name):
     # api imports torch and touches the GPU lazily; keep `import ofdm_amd` cheap
-    if name in ("api", "Context", "encode", "decode", "decode_long", "pinned_empty", "channel", "default_pilots", "locking_signal", "preamble",
+    if name in ("api", "Context", "encode", "decode", "decode_long", "decode_all", "pinned_empty", "channel", "default_pilots", "locking_signal", "preamble",
                 "training_signals", "OfdmError", "DecodeError", "BPSK", "QPSK", "QAM16", "QAM64", "QAM256",
                 "ECC_NONE", "ECC_HAMMING74", "ECC_HAMMING74_SOFT", "ECC_CONV_K7", "ECC_CONV_K7F_R12", "ECC_CONV_K7F_R23", "ECC_CONV_K7F_R34",
                 "ECC_RS255", "ECC_RS255_K7F_R12", "ECC_RS255_K7F_R23", "ECC_RS255_K7F_R34", "FRAME_UNCORRECTABLE", "ECC_FCS", "ECC_LDPC648", "ECC_LDPC648_R23", "ECC_LDPC648_R34", "ECC_LDPC648_R56", "LDPC_RATE_1_2", "LDPC_RATE_2_3", "LDPC_RATE_3_4", "LDPC_RATE_5_6", "LDPC_INFO_BYTES", "LDPC_MAX_ITER", "FCS_OVERHEAD", "FRAME_FCS", "crc32",

@@ -1138,6 +1138,36 @@ class Context:
                                                  C.byref(m)), "sc_correlate_long")
         return int(d.value), float(fd.value), float(m.value)
 
+    def _scan_result(self, call, what: str, lag_lo: int, holdoff: int, max_det: int) -> dict:
+        cap = max(int(max_det), 1)
+        d1, dh = np.zeros(cap, np.int64), np.zeros(cap, np.int64)
+        fd, m = np.zeros(cap, np.float64), np.zeros(cap, np.float32)
+        nd, more = C.c_int64(), C.c_int32()
+        self._ck(call(_host(d1), _host(dh), _host(fd), _host(m), C.byref(nd), C.byref(more)), what)
+        n = int(nd.value)
+        lo = np.concatenate([[int(lag_lo)], d1[:n] + int(holdoff)]).astype(np.int64)
+        return {"d1": d1[:n], "d_hat": dh[:n], "f_delta": fd[:n], "metric": m[:n], "lag_lo": lo[:n], "next_lag_lo": int(lo[n]),
+                "more": bool(more.value)}
+
+    def default_holdoff(self) -> int:
+        """The holdoff of the shortest frame (a header and one data symbol): 11 S - W, at least 1."""
+        return max(11 * self.S - self.params.sync_window_reps * self.S, 1)
+
+    def sc_scan_long(self, capture: torch.Tensor, holdoff: int, max_det: int, lag_lo: int = 0, lag_hi: int = 0) -> dict:
+        """ofdm_sc_scan_long (EXT-12): EVERY Schmidl-Cox detection of ONE capture whose first crossing lies in [lag_lo, lag_hi), in one
+        pass: detection k + 1 is the first crossing at or after d1[k] + holdoff.  -> dict of numpy arrays d1, d_hat (int64), f_delta,
+        metric and lag_lo (where the search for detection k started: decode_long(lag_lo=lag_lo[k]) decodes packet k), next_lag_lo
+        (where a further scan would start) and more (max_det stopped the scan while a further detection exists)."""
+        x = self._cx(capture).reshape(-1)
+        return self._scan_result(lambda *out: self.lib.ofdm_sc_scan_long(self.h, _dev(x), x.numel(), lag_lo, lag_hi, holdoff, max_det, *out),
+                                 "sc_scan_long", lag_lo, holdoff, max_det)
+
+    def sc_scan_long_host(self, capture: np.ndarray, holdoff: int, max_det: int, lag_lo: int = 0, lag_hi: int = 0) -> dict:
+        """ofdm_sc_scan_long_host: the same from a host array of complex64 (pinned_empty() memory is DMA-ed in place)."""
+        x = np.ascontiguousarray(capture, dtype=np.complex64).reshape(-1)
+        return self._scan_result(lambda *out: self.lib.ofdm_sc_scan_long_host(self.h, _host(x), x.size, lag_lo, lag_hi, holdoff, max_det, *out),
+                                 "sc_scan_long_host", lag_lo, holdoff, max_det)
+
     def decode_long(self, capture: torch.Tensor, max_symbols: int, lag_lo: int = 0, lag_hi: int = 0, d_hat_known: int = -1):
         """ofdm_rx_decode_long: decode (src/receiver.rs:9-96) of ONE long capture on the device -> dict(bytes, len, status, offset,
         f_delta, metric), the result of decode_batch on the whole capture as a single frame."""
@@ -1333,6 +1363,40 @@ def decode_long(samples, guard_bands: Optional[bool] = None, modulation: Optiona
         res = winner.decode_long(x, max_symbols, d_hat_known=d) if d >= 0 else {
             "bytes": c0.empty((4,), torch.uint8), "len": 0, "status": FRAME_NOSYNC, "offset": 0, "f_delta": 0.0, "metric": 0.0}
     return _long_result(res, fcs)
+
+
+def decode_all(samples, guard_bands: Optional[bool] = None, modulation: Optional[int] = None, n_fft: int = 64, ecc: int = ECC_NONE,
+               fcs: bool = False, holdoff: Optional[int] = None, max_packets: int = 4096, max_symbols: Optional[int] = None,
+               lag_lo: int = 0, lag_hi: int = 0, device: int = 0, **sync) -> list:
+    """EVERY packet of one long capture (EXT-12): one scan for all detections (Context.sc_scan_long: three launches, one
+    synchronisation), then decode_long(lag_lo = where the search for packet k started) per detection.  -> a list of per-packet dicts
+    (bytes: the payload as `bytes`, empty unless status == FRAME_OK; len, status, offset into the capture, f_delta, metric, d1, d_hat),
+    in the order of the capture.  Nothing is raised for a packet that fails: its status is in its dict.
+
+    holdoff: samples from one packet's first threshold crossing to where the search for the next one starts.  None = the shortest
+    frame, 11 S - W (at least 1): safe for any traffic, but inside a longer frame's payload the metric may cross the threshold again, and
+    every such crossing comes back as a packet of its own (status FRAME_HEADER / FRAME_FCS in the framed, LDPC and frame-check modes;
+    with ECC_NONE nothing tells it from a packet).  With frames of ONE size pass the real one: ctx.frame_samples(payload_bytes) - W, or a
+    little less.  max_symbols: the data symbols of the longest frame expected (None: up to the capture's end, which costs a demod of
+    everything behind every packet).  max_packets stops the scan; a capture with more is cut there (the last dict carries more=True)."""
+    ctx = _ctx(n_fft, BPSK if modulation is None else modulation, bool(guard_bands), _with_fcs(ecc, fcs), device=device, **sync)
+    x = samples if isinstance(samples, torch.Tensor) else ctx.to_device(np.asarray(samples))
+    x = x.reshape(-1)
+    if holdoff is None:
+        holdoff = ctx.default_holdoff()
+    if max_symbols is None:
+        max_symbols = max((x.numel() + ctx.S - 1) // ctx.S - 10, 1)
+    det = ctx.sc_scan_long(x, holdoff, max_packets, lag_lo, lag_hi)
+    out = []
+    for k in range(det["d_hat"].size):
+        res = ctx.decode_long(x, max_symbols, lag_lo=int(det["lag_lo"][k]), lag_hi=lag_hi)
+        ok = res["status"] == FRAME_OK
+        res["bytes"] = bytes(res["bytes"][: res["len"]].cpu().numpy()) if ok else b""
+        res.update(d1=int(det["d1"][k]), d_hat=int(det["d_hat"][k]), more=False)
+        out.append(res)
+    if out and det["more"]:
+        out[-1]["more"] = True
+    return out
 
 
 def _long_result(res: dict, fcs: bool) -> dict:

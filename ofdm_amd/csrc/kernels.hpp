@@ -51,6 +51,7 @@ struct Tuning {
     int sc16_chunk_frames = 0;     // EXT-9 / EXT-10: frames per k_sc16_widen + fc32 chain step of the sc16 receive entry points and per fc32 encode + k_sc16_narrow
                                    // step of ofdm_tx_encode_sc16_batch's two-pass path (0 = about 48 MB of fc32 samples)
     int no_txframe64_sc16 = 0;     // EXT-10: ofdm_tx_encode_sc16_batch at N = 64 encodes fc32 frames into the workspace and narrows them instead of k_txframe64_sc16 (A/B)
+    int scan_mark_only = 0;        // EXT-12: ofdm_sc_scan_long launches k_sc_mark alone and reports no detection: the kernel's time on its own
 };
 inline const Tuning &tuning_or_default(const Tuning *t) { static const Tuning d; return t ? *t : d; }
 
@@ -397,6 +398,26 @@ bool sc_big_ok(const ScParams &p);
 size_t sc_big_workspace_bytes(const ScParams &p);
 hipError_t run_sc_big(const ScParams &p, void *workspace, int num_cu, hipStream_t st);
 hipError_t run_sc_min_cross(const long long *cross, int tiles_per_frame, long long n_frames, int32_t *d1, hipStream_t st);
+// ---- EXT-12 every detection of one long capture (ofdm_sc_scan_long; kernels_scscan.hip, definition: tests/scan_ref.py)
+// k_sc_mark: bit j of `bits` = lag lag_lo + j crosses the threshold (den > 0 && num >= threshold den), j < n_lags; k_sc_walk: d1[0] =
+// the first crossing, d1[k + 1] = the first crossing at or after d1[k] + holdoff, at most det_cap of them, head = {n_det, more}; k_sc_peaks:
+// row k of d_hat / f_delta / metric = the first maximum of the metric over [d1[k], min(d1[k] + W, valid - 1)].
+// The caller guarantees 0 <= lag_lo, n_lags >= 1 and lag_lo + n_lags <= valid = n_samples - W - L + 1.
+struct ScScanParams {
+    const Tuning *tune = nullptr;
+    Trace *trace = nullptr;
+    const float2 *in = nullptr;
+    long long valid = 0, lag_lo = 0, n_lags = 0, holdoff = 1, det_cap = 0;
+    int L = 0, W = 0;
+    double threshold = 0.5;
+    unsigned long long *bits = nullptr;  // ceil(n_lags / 64) words
+    long long *head = nullptr;           // [2]
+    long long *d1 = nullptr, *d_hat = nullptr; // [det_cap]
+    double *f_delta = nullptr;
+    float *metric = nullptr;
+};
+hipError_t run_sc_mark(const ScScanParams &p, int num_cu, hipStream_t st);  // k_sc_mark alone
+hipError_t run_sc_scan(const ScScanParams &p, int num_cu, hipStream_t st);  // k_sc_mark + k_sc_walk + k_sc_peaks
 // base (optional): per-pair sample offset added to the pair's start; status (optional): pairs with status != 0 get 0
 hipError_t run_freq_correction(const float2 *in, long long n_pairs, long long stride, long long right_offset, int L,
                                double *f_delta, hipStream_t st, const int32_t *base = nullptr, const int32_t *status = nullptr);

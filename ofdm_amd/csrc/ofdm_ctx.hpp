@@ -86,6 +86,7 @@ enum WsRole {
     kWsTxSc16,                   // EXT-10: one chunk of fc32 frames out of the encode chain, the input of k_sc16_narrow (ofdm_tx_encode_sc16_batch)
     kWsLongSc16,                 // EXT-10: one long sc16 capture widened, the input of the fc32 long decode (ofdm_rx_decode_long_sc16[_host])
     kWsNoiseWeight,              // EXT-11: per row of the decode chain the n_fft LLR weights q_k of k_noise_bins, read by k_sym<llrw> (OFDM_LLRW_NOISE)
+    kWsScanBits, kWsScanRows,    // EXT-12: ofdm_sc_scan_long's bitmap of crossings; its head {n_det, more} and the rows d1 | d_hat | f_delta | metric
     kWsRoles
 };
 

@@ -37,6 +37,9 @@
 //   sc16 transmit output (EXT-10)
 //     no_txframe64_sc16   ofdm_tx_encode_sc16_batch at N = 64 inside the fused kernel's envelope: the fc32 encode chain into the workspace +
 //                         k_sc16_narrow instead of k_txframe64_sc16 (tools/bench_sc16_tx.py times both)
+//   every detection of a long capture (EXT-12)
+//     scan_mark_only      ofdm_sc_scan_long launches k_sc_mark alone over its lag range and reports no detection: the kernel's time on
+//                         its own (tools/bench_scan.py)
 //   Schmidl-Cox threshold in full precision (handled by name in ofdm_abi.hip, 64 bits: not in the table below)
 //     sync_threshold_bits the bit pattern of a double in (0, 1] that replaces ofdm_params.sync_threshold (a float: 6e-8 apart) in every
 //                         search of the context; 0 = the float again.  The margin tests set the threshold within 1e-12 of a lag's own metric
@@ -75,6 +78,7 @@ OFDM_TUNE_KEY("fcs_bitserial", fcs_bitserial, false)
 OFDM_TUNE_KEY("no_demod64_sc16", no_demod64_sc16, false)
 OFDM_TUNE_KEY("sc16_chunk_frames", sc16_chunk_frames, false)
 OFDM_TUNE_KEY("no_txframe64_sc16", no_txframe64_sc16, false)
+OFDM_TUNE_KEY("scan_mark_only", scan_mark_only, false)
 OFDM_TUNE_KEY("debug_demod64", debug_demod64, true)
 OFDM_TUNE_KEY("debug_sc", debug_sc, true)
 OFDM_TUNE_KEY("debug_tx", debug_tx, true)

@@ -462,6 +462,60 @@ int sc_long(ofdm_ctx *c, const float2 *in, int64_t n, int64_t lag_lo, int64_t la
     return OFDM_OK;
 }
 
+// EXT-12: every detection of [lag_lo, lag_hi) under the holdoff rule (include/ofdm_hip.h): k_sc_mark + k_sc_walk + k_sc_peaks, one D2H of
+// the head and the rows into pinned memory, one synchronisation.  The rows live in kWsScanRows as head {n_det, more} | d1 | d_hat |
+// f_delta | metric, `cap` entries each: cap = max_det clipped to the most detections the lag range can hold.
+constexpr int64_t kScanMaxSamples = (int64_t)1 << 40; // what the kernels' 64-bit sample and bit indices are held to
+int sc_scan_dev(ofdm_ctx *c, const float2 *in, int64_t n, int64_t lag_lo, int64_t lag_hi, int64_t holdoff, int64_t max_det, int64_t *d1,
+                int64_t *d_hat, double *f_delta, float *metric, int64_t *n_det, int32_t *more) {
+    *n_det = 0;
+    if (more) *more = 0;
+    ScScanParams p;
+    p.L = c->S(); p.W = c->prm.sync_window_reps * p.L;
+    p.valid = n - p.W - p.L + 1;
+    p.lag_lo = lag_lo;
+    const int64_t hi = (lag_hi <= 0 || lag_hi > p.valid) ? p.valid : lag_hi;
+    if (p.valid <= 0 || lag_lo >= hi) return OFDM_OK; // no valid lag: nothing can be detected
+    p.n_lags = hi - lag_lo;
+    p.holdoff = holdoff;
+    p.det_cap = std::min<int64_t>(max_det, (p.n_lags - 1) / holdoff + 1);
+    p.threshold = c->sync_threshold_f64 > 0.0 ? c->sync_threshold_f64 : (double)c->prm.sync_threshold;
+    p.in = in; p.tune = &c->tune; p.trace = &c->trace;
+    HostPipe *hp;
+    int rc = pipe_get(c, &hp);
+    if (rc) return rc;
+    void *bits, *rows;
+    const size_t cap = (size_t)p.det_cap, rows_bytes = 16 + cap * 28;
+    if ((rc = ws_get(c, kWsScanBits, (size_t)((p.n_lags + 63) >> 6) * 8, &bits))) return rc;
+    if ((rc = ws_get(c, kWsScanRows, rows_bytes, &rows))) return rc;
+    if ((rc = pin_grow(c, hp, hp->h_scal, rows_bytes))) return rc;
+    p.bits = static_cast<unsigned long long *>(bits);
+    p.head = static_cast<long long *>(rows);
+    p.d1 = p.head + 2;
+    p.d_hat = p.d1 + cap;
+    p.f_delta = reinterpret_cast<double *>(p.d_hat + cap);
+    p.metric = reinterpret_cast<float *>(p.f_delta + cap);
+    if (c->tune.scan_mark_only) { // laboratory key: the kernel's time on its own, nothing is reported
+        HIP_TRY(c, run_sc_mark(p, c->num_cu, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return OFDM_OK;
+    }
+    HIP_TRY(c, run_sc_scan(p, c->num_cu, c->stream));
+    const char *h = static_cast<const char *>(hp->h_scal.p);
+    HIP_TRY(c, hipMemcpyAsync(hp->h_scal.p, rows, rows_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int64_t head[2];
+    std::memcpy(head, h, 16);
+    const size_t nd = (size_t)std::min<int64_t>(std::max<int64_t>(head[0], 0), p.det_cap);
+    *n_det = (int64_t)nd;
+    if (more) *more = head[1] != 0;
+    if (d1) std::memcpy(d1, h + 16, 8 * nd);
+    std::memcpy(d_hat, h + 16 + 8 * cap, 8 * nd);
+    if (f_delta) std::memcpy(f_delta, h + 16 + 16 * cap, 8 * nd);
+    if (metric) std::memcpy(metric, h + 16 + 24 * cap, 4 * nd);
+    return OFDM_OK;
+}
+
 int decode_long_dev(ofdm_ctx *c, const float2 *in, int64_t n, int64_t lag_lo, int64_t lag_hi, int64_t d_known, int32_t max_symbols,
                     uint8_t *out_dev, int64_t out_cap, int32_t *out_len, int32_t *status, int64_t *offset, double *f_delta,
                     float *metric) {
@@ -748,6 +802,45 @@ int ofdm_sc_correlate_long(ofdm_ctx *c, const ofdm_fc32 *in_dev, int64_t n_sampl
     DeviceGuard dev_guard(c->device);
     c->trace.reset();
     return sc_long(c, reinterpret_cast<const float2 *>(in_dev), n_samples, lag_lo, lag_hi, slice_lags, d_hat, f_delta, metric);
+}
+
+// EXT-12.  What both forms check before anything touches the device
+static int sc_scan_check(const ofdm_ctx *c, const void *in, int64_t n_samples, int64_t lag_lo, int64_t holdoff, int64_t max_det,
+                         const int64_t *d_hat, const int64_t *n_det) {
+    if (!c || !d_hat || !n_det || n_samples < 0 || lag_lo < 0 || holdoff < 1 || max_det < 0 || (n_samples && !in)) return OFDM_ERR_INVALID;
+    if (c->prm.sync_mode != OFDM_SYNC_SCHMIDL_COX || n_samples > kScanMaxSamples) return OFDM_ERR_UNSUPPORTED;
+    return OFDM_OK;
+}
+int ofdm_sc_scan_long(ofdm_ctx *c, const ofdm_fc32 *in_dev, int64_t n_samples, int64_t lag_lo, int64_t lag_hi, int64_t holdoff,
+                      int64_t max_det, int64_t *d1, int64_t *d_hat, double *f_delta, float *metric, int64_t *n_det, int32_t *more) {
+    const int rc = sc_scan_check(c, in_dev, n_samples, lag_lo, holdoff, max_det, d_hat, n_det);
+    if (rc) return rc;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    return sc_scan_dev(c, reinterpret_cast<const float2 *>(in_dev), n_samples, lag_lo, lag_hi, holdoff, max_det, d1, d_hat, f_delta, metric,
+                       n_det, more);
+}
+int ofdm_sc_scan_long_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_samples, int64_t lag_lo, int64_t lag_hi, int64_t holdoff,
+                           int64_t max_det, int64_t *d1, int64_t *d_hat, double *f_delta, float *metric, int64_t *n_det, int32_t *more) {
+    int rc = sc_scan_check(c, in_host, n_samples, lag_lo, holdoff, max_det, d_hat, n_det);
+    if (rc) return rc;
+    *n_det = 0;
+    if (more) *more = 0;
+    if (!n_samples) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    HostPipe *hp;
+    if ((rc = pipe_get(c, &hp))) return rc;
+    auto work = [&]() -> int { // as ofdm_rx_decode_long_host: once the upload has started, a failure waits for it before it is returned
+        const size_t bytes = (size_t)n_samples * sizeof(ofdm_fc32);
+        if ((rc = dev_grow(c, hp, hp->d_long, bytes + 64))) return rc;
+        if ((rc = long_upload(c, hp, hp->d_long.p, in_host, bytes))) return rc;
+        return sc_scan_dev(c, static_cast<const float2 *>(hp->d_long.p), n_samples, lag_lo, lag_hi, holdoff, max_det, d1, d_hat, f_delta,
+                           metric, n_det, more);
+    };
+    rc = work();
+    if (rc) sync_all(c, hp);
+    return rc;
 }
 
 int ofdm_rx_decode_long(ofdm_ctx *c, const ofdm_fc32 *in_dev, int64_t n_samples, int64_t lag_lo, int64_t lag_hi, int64_t d_hat_known,
