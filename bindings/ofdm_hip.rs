@@ -275,6 +275,15 @@ extern "C" {
     pub fn ofdm_sc_scan_long_host(ctx: *mut ofdm_ctx, in_host: *const ofdm_fc32, n_samples: i64, lag_lo: i64, lag_hi: i64, holdoff: i64,
                                   max_det: i64, d1: *mut i64, d_hat: *mut i64, f_delta: *mut f64, metric: *mut f32, n_det: *mut i64,
                                   more: *mut i32) -> c_int;
+    // EXT-13: every packet of one long capture in ONE run of the receive chain, from the scan's (d_hat, f_delta, metric) triples (host
+    // arrays); outputs on the device, offset / f_delta / metric may be null.  _all_long_host: upload + scan + decode into host arrays
+    pub fn ofdm_rx_decode_packets(ctx: *mut ofdm_ctx, in_dev: *const ofdm_fc32, n_samples: i64, n_det: i64, d_hat: *const i64, f_delta: *const f64,
+                                  metric: *const f32, max_symbols: i32, out_dev: *mut u8, out_stride: i64, out_len_dev: *mut i32,
+                                  status_dev: *mut i32, offset_dev: *mut i64, f_delta_dev: *mut f64, metric_dev: *mut f32) -> c_int;
+    pub fn ofdm_rx_decode_all_long_host(ctx: *mut ofdm_ctx, in_host: *const ofdm_fc32, n_samples: i64, lag_lo: i64, lag_hi: i64, holdoff: i64,
+                                        max_det: i64, max_symbols: i32, out_host: *mut u8, out_stride: i64, out_len: *mut i32,
+                                        status: *mut i32, offset: *mut i64, f_delta: *mut f64, metric: *mut f32, d1: *mut i64,
+                                        d_hat: *mut i64, n_det: *mut i64, more: *mut i32) -> c_int;
     pub fn ofdm_sc16_widen(input: *const ofdm_sc16, n: i64, scale: f32, out: *mut ofdm_fc32) -> c_int;
     pub fn ofdm_sc16_narrow(input: *const ofdm_fc32, n: i64, scale: f32, out: *mut ofdm_sc16, clipped: *mut i64) -> c_int;
     pub fn ofdm_sc16_widen_batch(ctx: *mut ofdm_ctx, in_dev: *const ofdm_sc16, n_frames: i64, in_stride: i64, frame_len: i64, scale: f32,

@@ -909,6 +909,44 @@ int ofdm_sc_scan_long(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_samples,
 int ofdm_sc_scan_long_host(ofdm_ctx *ctx, const ofdm_fc32 *in_host, int64_t n_samples, int64_t lag_lo, int64_t lag_hi, int64_t holdoff,
                            int64_t max_det, int64_t *d1, int64_t *d_hat, double *f_delta, float *metric, int64_t *n_det, int32_t *more);
 
+/* ------------------------------------------------------------------ every packet of one long capture in one batched decode (EXT-13)
+ * ofdm_rx_decode_packets decodes the packets k = 0 .. n_det - 1 of a capture of n samples in ONE run of the receive chain, given the
+ * triples (d_hat_k, f_delta_k, M_k) exactly as ofdm_sc_scan_long returns them.  Nothing here refers to the slice search of
+ * ofdm_rx_decode_long: the timing IS the scan's values (in-order sums, the oracle's bit for bit, independent of grid and lag_lo).
+ *
+ * The rule (L = S, b = sync_backoff; numpy restatement: tests/packets_ref.py).  Packet k is steps 2 - 5 of ofdm_rx_decode_batch on the
+ * sub-capture capture[r_k:] with known timing:
+ *     row start      r_k = max(d_hat_k - L - b, 0) & ~1; the row-relative peak is d_hat_k - r_k, the row's own length n - r_k
+ *     timing fields  off = max(d_hat - L - b, 0) (row-relative); OFDM_FRAME_SHORT below 10 L samples behind it;
+ *                    ns = min(ceil(len / L) - 10, max_symbols) live symbols; status -4 if ns bytes_per_symbol < 16
+ *     CFO            f_delta_k through the context's cfo_mode as the chain puts it through: OFDM_CFO_OFF -> 0, OFDM_CFO_ABS -> |.|,
+ *                    OFDM_CFO_WIDE -> plus 2 pi m / S from k_cfo_wide; chest_mode, the LLR weight and every ecc apply unchanged
+ *     outputs        bytes, out_len, status: the chain's; offset (int64, into the capture) = r_k + the row's offset (0 + the row's
+ *                    where the chain reports OFDM_FRAME_BADTIMING, as ofdm_rx_decode_long); f_delta = the value the chain derotated
+ *                    with; metric = M_k, passed through bit for bit
+ * On the device the rows are an ordinary batch: k_gather_rows copies capture[r_k : r_k + R] into row k of a workspace,
+ * R = min((10 + max_symbols) S + 2, n rounded up to even), zeros at and beyond sample n, and k_rx_prepare_rows gives a row cut by the
+ * capture's end the live symbols of its true length.  The packets are walked in chunks whose rows stay within 256 MiB.  A row depends
+ * on its own triple and the capture only: not on the other packets, their order, the chunking or the grid.
+ *
+ * in_dev (8-byte aligned) and the outputs are DEVICE pointers (offset_dev, f_delta_dev, metric_dev optional); d_hat, f_delta, metric
+ * are HOST arrays of n_det entries, read before the call returns unless they are page-locked (then: unchanged until the stream
+ * reaches the end of the call).  Asynchronous on the context's stream, like ofdm_rx_decode_batch; out_stride: its rule.
+ * OFDM_ERR_INVALID: a d_hat entry outside [0, n_samples) (checked on the host before any launch), n_det < 0, n_samples < 0,
+ * max_symbols <= 0, a NULL required pointer, an out_stride below the row size.  OFDM_ERR_UNSUPPORTED: a sync mode other than
+ * OFDM_SYNC_SCHMIDL_COX, n_samples > 2^40, n_det >= 2^31.  n_det = 0: OFDM_OK with no launch. */
+int ofdm_rx_decode_packets(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_samples, int64_t n_det, const int64_t *d_hat,
+                           const double *f_delta, const float *metric, int32_t max_symbols, uint8_t *out_dev, int64_t out_stride,
+                           int32_t *out_len_dev, int32_t *status_dev, int64_t *offset_dev, double *f_delta_dev, float *metric_dev);
+/* A capture in host memory (uploaded as ofdm_rx_decode_long_host uploads its capture): ofdm_sc_scan_long(lag_lo, lag_hi, holdoff,
+ * max_det), then ofdm_rx_decode_packets with the scan's rows, into HOST arrays: out_host = max_det rows of out_stride bytes, out_len,
+ * status, offset (optional), f_delta, metric per packet, and d1 (optional), d_hat, *n_det, *more (optional) as the scan reports them.
+ * Two synchronisations whatever the packet count.  Errors: those of the two calls. */
+int ofdm_rx_decode_all_long_host(ofdm_ctx *ctx, const ofdm_fc32 *in_host, int64_t n_samples, int64_t lag_lo, int64_t lag_hi,
+                                 int64_t holdoff, int64_t max_det, int32_t max_symbols, uint8_t *out_host, int64_t out_stride,
+                                 int32_t *out_len, int32_t *status, int64_t *offset, double *f_delta, float *metric, int64_t *d1,
+                                 int64_t *d_hat, int64_t *n_det, int32_t *more);
+
 /* ------------------------------------------------------------------ sc16 receive input (EXT-9)
  * Radios deliver sc16 -- interleaved little-endian int16 I and Q, 4 bytes a sample: UHD's wire format and that of most recorded
  * captures -- not fc32.  The sample format is a property of a CALL, not of a context: the same context decodes fc32 and sc16.

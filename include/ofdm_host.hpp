@@ -166,7 +166,12 @@ class Context {
     // for a packet that fails: its status is in the result (a false detection inside a payload shows as OFDM_FRAME_HEADER /
     // OFDM_FRAME_FCS in the framed, LDPC and frame-check modes).  holdoff <= 0: default_holdoff().  max_symbols: the data symbols of the
     // longest frame expected (<= 0: up to the capture's end, as decode_capture -- a demod of everything behind every packet).
-    std::vector<Decoded> decode_all(const ofdm_fc32 *fc, int64_t n, int64_t holdoff = 0, int64_t max_packets = 4096, int32_t max_symbols = 0) {
+    // batched (EXT-13): the detections go through ONE run of the receive chain (decode_packets) instead of one ofdm_rx_decode_long each;
+    // it needs max_symbols > 0 (the default "up to the capture's end" would gather the capture once per packet).  Its f_delta is the
+    // scan's (within 1e-9 of the loop's), everything else is the loop's.
+    std::vector<Decoded> decode_all(const ofdm_fc32 *fc, int64_t n, int64_t holdoff = 0, int64_t max_packets = 4096, int32_t max_symbols = 0,
+                                    bool batched = false) {
+        if (batched && max_symbols <= 0) throw Error("decode_all(batched): max_symbols is required");
         if (holdoff <= 0) holdoff = default_holdoff();
         DevBuf din(ctx_, (size_t)std::max<int64_t>(n, 1) * sizeof(ofdm_fc32) + 64);
         if (n > 0) check(ofdm_memcpy_h2d(ctx_, din.p, fc, (size_t)n * sizeof(ofdm_fc32)), "h2d");
@@ -175,6 +180,7 @@ class Context {
             check(ofdm_sc_scan_long(ctx_, (const ofdm_fc32 *)din.p, n, 0, 0, holdoff, max_packets, det.d1.data(), det.d_hat.data(),
                                     det.f_delta.data(), det.metric.data(), nd, more), "ofdm_sc_scan_long");
         });
+        if (batched) return decode_packets((const ofdm_fc32 *)din.p, n, det, max_symbols);
         std::vector<Decoded> out;
         for (size_t k = 0; k < det.size(); ++k)
             out.push_back(decode_capture_as(n, max_symbols, [&](int32_t ms, Decoded &r, int64_t ob, int32_t *len) {
@@ -183,6 +189,34 @@ class Context {
                                           &r.f_delta, &r.metric), "ofdm_rx_decode_long");
                 if (r.status == OFDM_FRAME_OK && *len > 0) check(ofdm_memcpy_d2h(ctx_, r.bytes.data(), dout.p, (size_t)*len), "d2h");
             }));
+        return out;
+    }
+    // EXT-13: every detection of `det` (as scan_capture / ofdm_sc_scan_long returned it) of the capture in_dev[0 .. n) on the device, in
+    // one run of the receive chain (ofdm_rx_decode_packets): packet k's bytes, status, offset into the capture, the f_delta the chain
+    // derotated with and the scan's metric.  Nothing is thrown for a packet that fails.
+    std::vector<Decoded> decode_packets(const ofdm_fc32 *in_dev, int64_t n, const Detections &det, int32_t max_symbols) {
+        const size_t nd = det.size();
+        std::vector<Decoded> out(nd);
+        if (!nd) return out;
+        int64_t ob = 0;
+        decode_capture_as(n, max_symbols, [&](int32_t, Decoded &r, int64_t row, int32_t *) { ob = row; r.status = OFDM_FRAME_NOSYNC; });
+        DevBuf rows(ctx_, nd * (size_t)ob + 64), scal(ctx_, nd * 28 + 64);
+        char *sp = (char *)scal.p; // offset i64 | f_delta f64 | len | status i32 | metric f32
+        check(ofdm_rx_decode_packets(ctx_, in_dev, n, (int64_t)nd, det.d_hat.data(), det.f_delta.data(), det.metric.data(), max_symbols,
+                                     (uint8_t *)rows.p, ob, (int32_t *)(sp + 16 * nd), (int32_t *)(sp + 20 * nd), (int64_t *)sp,
+                                     (double *)(sp + 8 * nd), (float *)(sp + 24 * nd)), "ofdm_rx_decode_packets");
+        std::vector<char> h(nd * 28);
+        std::vector<uint8_t> b(nd * (size_t)ob);
+        check(ofdm_memcpy_d2h(ctx_, h.data(), sp, h.size()), "d2h");
+        check(ofdm_memcpy_d2h(ctx_, b.data(), rows.p, b.size()), "d2h");
+        for (size_t k = 0; k < nd; ++k) {
+            Decoded &r = out[k];
+            int32_t len = 0;
+            std::memcpy(&r.offset, h.data() + 8 * k, 8); std::memcpy(&r.f_delta, h.data() + 8 * nd + 8 * k, 8);
+            std::memcpy(&len, h.data() + 16 * nd + 4 * k, 4); std::memcpy(&r.status, h.data() + 20 * nd + 4 * k, 4);
+            std::memcpy(&r.metric, h.data() + 24 * nd + 4 * k, 4);
+            if (r.status == OFDM_FRAME_OK && len > 0) r.bytes.assign(b.begin() + k * (size_t)ob, b.begin() + k * (size_t)ob + len);
+        }
         return out;
     }
     template <class Call> void scan_sized(Detections &r, int64_t holdoff, int64_t max_det, int64_t lag_lo, Call &&call) {

@@ -134,6 +134,9 @@ SIGNATURES = {
                                            C.POINTER(C.c_double), C.POINTER(C.c_float)]),
     "ofdm_sc_scan_long": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i32)]),
     "ofdm_sc_scan_long_host": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i32)]),
+    "ofdm_rx_decode_packets": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp]),
+    "ofdm_rx_decode_all_long_host": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64),
+                                               C.POINTER(i32)]),
     "ofdm_sc16_widen": (C.c_int, [vp, i64, C.c_float, vp]),
     "ofdm_sc16_narrow": (C.c_int, [vp, i64, C.c_float, vp, C.POINTER(i64)]),
     "ofdm_sc16_widen_batch": (C.c_int, [vp, vp, i64, i64, i64, C.c_float, vp, i64]),

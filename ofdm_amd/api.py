@@ -1191,6 +1191,45 @@ class Context:
         return {"bytes": out, "len": int(ln.value), "status": int(st.value), "offset": int(off.value), "f_delta": float(fd.value),
                 "metric": float(m.value)}
 
+    def decode_packets(self, capture: torch.Tensor, det: dict, max_symbols: int, out_stride: Optional[int] = None) -> dict:
+        """ofdm_rx_decode_packets (EXT-13): every detection of `det` (sc_scan_long's dict, or any dict of numpy d_hat / f_delta / metric)
+        through ONE run of the receive chain -> dict of device tensors bytes [n_det, out_stride], len, status (int32), offset (int64,
+        into the capture), f_delta (the value the chain derotated with) and metric (the scan's, bit for bit).  Asynchronous."""
+        x = self._cx(capture).reshape(-1)
+        dh = np.ascontiguousarray(det["d_hat"], dtype=np.int64)
+        fd = np.ascontiguousarray(det["f_delta"], dtype=np.float64)
+        m = np.ascontiguousarray(det["metric"], dtype=np.float32)
+        n = dh.size
+        if fd.size != n or m.size != n:
+            raise OfdmError("decode_packets: d_hat, f_delta and metric must have one entry per detection")
+        ob = self.decode_row_bytes(max_symbols) if out_stride is None else int(out_stride)
+        res = {"bytes": self.empty((n, ob), torch.uint8), "len": self.empty((n,), torch.int32), "status": self.empty((n,), torch.int32),
+               "offset": self.empty((n,), torch.int64), "f_delta": self.empty((n,), torch.float64), "metric": self.empty((n,), torch.float32)}
+        self._ck(self.lib.ofdm_rx_decode_packets(self.h, _dev(x), x.numel(), n, _host(dh), _host(fd), _host(m), max_symbols, _dev(res["bytes"]), ob,
+                                                 _dev(res["len"]), _dev(res["status"]), _dev(res["offset"]), _dev(res["f_delta"]),
+                                                 _dev(res["metric"])), "rx_decode_packets")
+        return res
+
+    def decode_all_host(self, capture: np.ndarray, holdoff: int, max_det: int, max_symbols: int, lag_lo: int = 0, lag_hi: int = 0) -> dict:
+        """ofdm_rx_decode_all_long_host (EXT-13): upload, scan and batched decode of a host array of complex64 (pinned_empty() memory is
+        DMA-ed in place) -> dict of numpy arrays: bytes [n_det, row], len, status, offset, f_delta, metric per packet and the scan's d1,
+        d_hat, lag_lo, next_lag_lo, more.  Two synchronisations whatever the packet count."""
+        x = np.ascontiguousarray(capture, dtype=np.complex64).reshape(-1)
+        cap = max(int(max_det), 1)
+        ob = self.decode_row_bytes(max_symbols)
+        out = np.zeros((cap, ob), np.uint8)
+        ln, st, off = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int64)
+        fd, m = np.zeros(cap, np.float64), np.zeros(cap, np.float32)
+        d1, dh = np.zeros(cap, np.int64), np.zeros(cap, np.int64)
+        nd, more = C.c_int64(), C.c_int32()
+        self._ck(self.lib.ofdm_rx_decode_all_long_host(self.h, _host(x), x.size, lag_lo, lag_hi, holdoff, max_det, max_symbols, _host(out), ob,
+                                                       _host(ln), _host(st), _host(off), _host(fd), _host(m), _host(d1), _host(dh),
+                                                       C.byref(nd), C.byref(more)), "rx_decode_all_long_host")
+        n = int(nd.value)
+        lo = np.concatenate([[int(lag_lo)], d1[:n] + int(holdoff)]).astype(np.int64)
+        return {"bytes": out[:n], "len": ln[:n], "status": st[:n], "offset": off[:n], "f_delta": fd[:n], "metric": m[:n], "d1": d1[:n],
+                "d_hat": dh[:n], "lag_lo": lo[:n], "next_lag_lo": int(lo[n]), "more": bool(more.value)}
+
     # ---------------------------------------------------------------- host buffers (H2D / kernels / D2H pipelined in the library)
     def decode_host(self, frames: np.ndarray, max_symbols: int, n_lags: int = 0, frame_len: Optional[int] = None,
                     chunk_frames: int = 0, out: Optional[dict] = None):
@@ -1367,7 +1406,7 @@ def decode_long(samples, guard_bands: Optional[bool] = None, modulation: Optiona
 
 def decode_all(samples, guard_bands: Optional[bool] = None, modulation: Optional[int] = None, n_fft: int = 64, ecc: int = ECC_NONE,
                fcs: bool = False, holdoff: Optional[int] = None, max_packets: int = 4096, max_symbols: Optional[int] = None,
-               lag_lo: int = 0, lag_hi: int = 0, device: int = 0, **sync) -> list:
+               lag_lo: int = 0, lag_hi: int = 0, device: int = 0, batched: bool = False, **sync) -> list:
     """EVERY packet of one long capture (EXT-12): one scan for all detections (Context.sc_scan_long: three launches, one
     synchronisation), then decode_long(lag_lo = where the search for packet k started) per detection.  -> a list of per-packet dicts
     (bytes: the payload as `bytes`, empty unless status == FRAME_OK; len, status, offset into the capture, f_delta, metric, d1, d_hat),
@@ -1378,7 +1417,14 @@ def decode_all(samples, guard_bands: Optional[bool] = None, modulation: Optional
     every such crossing comes back as a packet of its own (status FRAME_HEADER / FRAME_FCS in the framed, LDPC and frame-check modes;
     with ECC_NONE nothing tells it from a packet).  With frames of ONE size pass the real one: ctx.frame_samples(payload_bytes) - W, or a
     little less.  max_symbols: the data symbols of the longest frame expected (None: up to the capture's end, which costs a demod of
-    everything behind every packet).  max_packets stops the scan; a capture with more is cut there (the last dict carries more=True)."""
+    everything behind every packet).  max_packets stops the scan; a capture with more is cut there (the last dict carries more=True).
+
+    batched=True (EXT-13): the same list from one scan and ONE batched decode (Context.decode_packets) instead of a decode_long per
+    packet.  Its f_delta is the scan's own (within 1e-9 of the default path's, whose slice search sums in another order) and its metric
+    within 1e-6; every other field is equal.  It requires max_symbols (OfdmError without it: the default "up to the capture's end" would
+    gather the capture once per packet)."""
+    if batched and max_symbols is None:
+        raise OfdmError("decode_all(batched=True) requires max_symbols: the data symbols of the longest frame expected")
     ctx = _ctx(n_fft, BPSK if modulation is None else modulation, bool(guard_bands), _with_fcs(ecc, fcs), device=device, **sync)
     x = samples if isinstance(samples, torch.Tensor) else ctx.to_device(np.asarray(samples))
     x = x.reshape(-1)
@@ -1388,6 +1434,19 @@ def decode_all(samples, guard_bands: Optional[bool] = None, modulation: Optional
         max_symbols = max((x.numel() + ctx.S - 1) // ctx.S - 10, 1)
     det = ctx.sc_scan_long(x, holdoff, max_packets, lag_lo, lag_hi)
     out = []
+    if batched:
+        res = ctx.decode_packets(x, det, max_symbols)
+        ctx.synchronize()
+        rows = res["bytes"].cpu().numpy()
+        col = {k: res[k].cpu().numpy() for k in ("len", "status", "offset", "f_delta", "metric")}
+        for k in range(det["d_hat"].size):
+            ok = int(col["status"][k]) == FRAME_OK
+            out.append({"bytes": bytes(rows[k, : int(col["len"][k])]) if ok else b"", "len": int(col["len"][k]), "status": int(col["status"][k]),
+                        "offset": int(col["offset"][k]), "f_delta": float(col["f_delta"][k]), "metric": float(col["metric"][k]),
+                        "d1": int(det["d1"][k]), "d_hat": int(det["d_hat"][k]), "more": False})
+        if out and det["more"]:
+            out[-1]["more"] = True
+        return out
     for k in range(det["d_hat"].size):
         res = ctx.decode_long(x, max_symbols, lag_lo=int(det["lag_lo"][k]), lag_hi=lag_hi)
         ok = res["status"] == FRAME_OK

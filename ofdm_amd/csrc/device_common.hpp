@@ -597,4 +597,31 @@ __device__ __forceinline__ unsigned sc16_narrow2(float2 z, float scale, int *cli
     return sc16_narrow1(z.x, scale, clipped) | (sc16_narrow1(z.y, scale, clipped) << 16);
 }
 
+
+// decode bookkeeping (src/receiver.rs:21-39): timing -> trimmed offset, length check, live symbol count.  Shared by k_rx_prepare
+// (kernels_bytes.hip: one frame_len for the batch) and k_rx_prepare_rows (kernels_packets.hip: a frame_len per row)
+__device__ __forceinline__ void rx_prepare_one(long long f, const int32_t *d_hat, double *f_delta, long long frame_len, int L,
+                                               int backoff, int cfo_mode, int max_symbols, int bytes_per_symbol,
+                                               int32_t *status, int32_t *offset, int32_t *nsym) {
+    int st = 0, off = 0, ns = 0;
+    const int d = d_hat[f];
+    if (d < 0) st = -2; // OFDM_FRAME_NOSYNC
+    else {
+        off = d - L - backoff;
+        if (off < 0) off = 0;
+        long long len = frame_len - off;
+        if (len < 10LL * L) st = -1; // "Input not long enough, bailing early"
+        else {
+            long long chunks = (len + L - 1) / L - 10; // split_into_chunks pads the tail chunk
+            ns = (int)(chunks < max_symbols ? chunks : max_symbols);
+            if ((long long)ns * bytes_per_symbol < 16) { st = -4; ns = 0; }
+        }
+    }
+    if (cfo_mode == 0) f_delta[f] = 0.0;
+    else if (cfo_mode == 2) f_delta[f] = fabs(f_delta[f]);
+    status[f] = st;
+    offset[f] = off;
+    nsym[f] = st == 0 ? ns : 0;
+}
+
 } // namespace ofdm

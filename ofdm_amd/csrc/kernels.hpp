@@ -52,6 +52,8 @@ struct Tuning {
                                    // step of ofdm_tx_encode_sc16_batch's two-pass path (0 = about 48 MB of fc32 samples)
     int no_txframe64_sc16 = 0;     // EXT-10: ofdm_tx_encode_sc16_batch at N = 64 encodes fc32 frames into the workspace and narrows them instead of k_txframe64_sc16 (A/B)
     int scan_mark_only = 0;        // EXT-12: ofdm_sc_scan_long launches k_sc_mark alone and reports no detection: the kernel's time on its own
+    int packets_chunk_rows = 0;    // EXT-13: packets per k_gather_rows + chain step of ofdm_rx_decode_packets (0 = as many as keep the gathered rows within 256 MiB)
+    int packets_gather_only = 0;   // EXT-13: ofdm_rx_decode_packets launches k_pkt_rows + k_gather_rows alone and delivers nothing: the kernel's time on its own
 };
 inline const Tuning &tuning_or_default(const Tuning *t) { static const Tuning d; return t ? *t : d; }
 
@@ -418,6 +420,34 @@ struct ScScanParams {
 };
 hipError_t run_sc_mark(const ScScanParams &p, int num_cu, hipStream_t st);  // k_sc_mark alone
 hipError_t run_sc_scan(const ScScanParams &p, int num_cu, hipStream_t st);  // k_sc_mark + k_sc_walk + k_sc_peaks
+// ---- EXT-13 every packet of one long capture as rows of one batch (ofdm_rx_decode_packets; kernels_packets.hip, definition:
+// tests/packets_ref.py).  k_pkt_rows: per packet k < n_det the row start r_k = max(d_hat[k] - L - backoff, 0) & ~1, row_dhat = d_hat[k] -
+// r_k, row_len = min(R, n - r_k), f_delta[k] = f_delta_in[k], metric[k] = metric_in[k] (metric optional).  k_gather_rows: rows[j] =
+// capture[r : r + R] for r = row_start[row0 + j], j < n_rows, zeros at and beyond sample n; R even, rows 16-byte aligned, in 8-byte aligned.
+struct PktParams {
+    const Tuning *tune = nullptr;
+    Trace *trace = nullptr;
+    const float2 *in = nullptr;
+    long long n = 0, n_det = 0, R = 0, row0 = 0, n_rows = 0;
+    int L = 0, backoff = 0;
+    const long long *d_hat = nullptr;    // [n_det] on the device, each in [0, n)
+    const double *f_delta_in = nullptr;
+    const float *metric_in = nullptr;
+    long long *row_start = nullptr;      // [n_det]
+    int32_t *row_dhat = nullptr, *row_len = nullptr;
+    double *f_delta = nullptr;
+    float *metric = nullptr;
+    float2 *rows = nullptr;              // [n_rows][R]
+};
+hipError_t run_pkt_rows(const PktParams &p, hipStream_t st);
+hipError_t run_gather_rows(const PktParams &p, int num_cu, hipStream_t st);
+// k_rx_prepare with a frame_len per row (row_len[f]): status / offset / live symbols / CFO of row f from its own length
+hipError_t run_rx_prepare_rows(long long n_rows, const int32_t *d_hat, double *f_delta, const int32_t *row_len, int L, int backoff,
+                               int cfo_mode, int max_symbols, int bytes_per_symbol, int32_t *status, int32_t *offset, int32_t *nsym,
+                               hipStream_t st);
+// offset[k] = row_start[k] + row_offset[k] (0 + row_offset[k] where status[k] is OFDM_FRAME_BADTIMING)
+hipError_t run_pkt_finish(long long n_det, const long long *row_start, const int32_t *row_offset, const int32_t *status, long long *offset,
+                          hipStream_t st);
 // base (optional): per-pair sample offset added to the pair's start; status (optional): pairs with status != 0 get 0
 hipError_t run_freq_correction(const float2 *in, long long n_pairs, long long stride, long long right_offset, int L,
                                double *f_delta, hipStream_t st, const int32_t *base = nullptr, const int32_t *status = nullptr);

@@ -184,30 +184,7 @@ hipError_t run_tx_finish(float2 *out, long long n_frames, long long out_stride, 
     return hipGetLastError();
 }
 
-// decode bookkeeping (src/receiver.rs:21-39): timing -> trimmed offset, length check, live symbol count
-__device__ __forceinline__ void rx_prepare_one(long long f, const int32_t *d_hat, double *f_delta, long long frame_len, int L,
-                                               int backoff, int cfo_mode, int max_symbols, int bytes_per_symbol,
-                                               int32_t *status, int32_t *offset, int32_t *nsym) {
-    int st = 0, off = 0, ns = 0;
-    const int d = d_hat[f];
-    if (d < 0) st = -2; // OFDM_FRAME_NOSYNC
-    else {
-        off = d - L - backoff;
-        if (off < 0) off = 0;
-        long long len = frame_len - off;
-        if (len < 10LL * L) st = -1; // "Input not long enough, bailing early"
-        else {
-            long long chunks = (len + L - 1) / L - 10; // split_into_chunks pads the tail chunk
-            ns = (int)(chunks < max_symbols ? chunks : max_symbols);
-            if ((long long)ns * bytes_per_symbol < 16) { st = -4; ns = 0; }
-        }
-    }
-    if (cfo_mode == 0) f_delta[f] = 0.0;
-    else if (cfo_mode == 2) f_delta[f] = fabs(f_delta[f]);
-    status[f] = st;
-    offset[f] = off;
-    nsym[f] = st == 0 ? ns : 0;
-}
+// decode bookkeeping (src/receiver.rs:21-39): rx_prepare_one (device_common.hpp) per frame
 __global__ __launch_bounds__(256) void k_rx_prepare(long long n_frames, const int32_t *d_hat, double *f_delta,
                                                     long long frame_len, int L, int backoff, int cfo_mode,
                                                     int max_symbols, int bytes_per_symbol, int32_t *status,

@@ -1417,8 +1417,11 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
 }
 
 namespace {
-struct KnownSync { int32_t d_hat; double f_delta; float metric; };
-// The arguments of a decode call: ofdm_rx_decode_batch's own, or one capture with its timing (ofdm_abi_rx_decode_known)
+// Timing the caller brings.  One capture: d_hat / f_delta / metric by value (ofdm_abi_rx_decode_known).  Rows (EXT-13, row_dhat != NULL):
+// device arrays of the row-relative peaks and of the rows' own lengths; the call's f_delta and offset arrays are not optional, f_delta
+// (and metric, if wanted) already hold the rows' values
+struct KnownSync { int32_t d_hat; double f_delta; float metric; const int32_t *row_dhat = nullptr, *row_len = nullptr; };
+// The arguments of a decode call: ofdm_rx_decode_batch's own, or captures with their timing (ofdm_abi_rx_decode_known, ofdm_rx_decode_packets)
 struct DecodeCall {
     const float2 *in; int64_t n_frames, frame_stride, frame_len, n_lags; int32_t max_symbols;
     uint8_t *out; int64_t out_stride;                          // rows of out_stride bytes
@@ -1540,12 +1543,22 @@ static int rx_front_end(ofdm_ctx *c, const DecodeCall &d, int bps_bytes, FrontEn
     double *fd = d.f_delta ? d.f_delta : (double *)w_fd;
     const float2 *x = d.in;
     if (const KnownSync *known = d.known) {
-        // 1k. the caller brings the timing of the one capture (ofdm_rx_decode_long with lag_lo > 0)
-        if (n_frames != 1 || c->prm.sync_mode != OFDM_SYNC_SCHMIDL_COX) return OFDM_ERR_INVALID;
-        c->trace.add("k_set_sync+k_rx_prepare");
-        HIP_TRY(c, run_set_sync((int32_t *)w_dhat, fd, metric, known->d_hat, known->f_delta, known->metric, c->stream));
-        HIP_TRY(c, run_rx_prepare(n_frames, (const int32_t *)w_dhat, fd, frame_len, c->S(), c->prm.sync_backoff,
-                                  c->prm.cfo_mode, max_symbols, bps_bytes, status, offs, (int32_t *)w_nsym, c->stream));
+        // 1k. the caller brings the timing: of the one capture (ofdm_rx_decode_long with lag_lo > 0), or of every row with the row's own
+        //     length (ofdm_rx_decode_packets: a row cut by the capture's end is zeros from there on, which every kernel behind reads
+        //     as pad_chunk's padding under the scalar frame_len)
+        if (c->prm.sync_mode != OFDM_SYNC_SCHMIDL_COX) return OFDM_ERR_INVALID;
+        if (known->row_dhat) {
+            if (!known->row_len || !d.f_delta || !offset) return OFDM_ERR_INVALID;
+            c->trace.add("k_rx_prepare_rows");
+            HIP_TRY(c, run_rx_prepare_rows(n_frames, known->row_dhat, fd, known->row_len, c->S(), c->prm.sync_backoff, c->prm.cfo_mode,
+                                           max_symbols, bps_bytes, status, offs, (int32_t *)w_nsym, c->stream));
+        } else {
+            if (n_frames != 1) return OFDM_ERR_INVALID;
+            c->trace.add("k_set_sync+k_rx_prepare");
+            HIP_TRY(c, run_set_sync((int32_t *)w_dhat, fd, metric, known->d_hat, known->f_delta, known->metric, c->stream));
+            HIP_TRY(c, run_rx_prepare(n_frames, (const int32_t *)w_dhat, fd, frame_len, c->S(), c->prm.sync_backoff,
+                                      c->prm.cfo_mode, max_symbols, bps_bytes, status, offs, (int32_t *)w_nsym, c->stream));
+        }
         if (c->prm.cfo_mode == OFDM_CFO_WIDE && (rc = cfo_wide_run(c, x, n_frames, frame_stride, frame_len, offs, status, OFDM_CFO_WIDE_SPAN, fd, nullptr, nullptr))) return rc;
     } else if (c->prm.sync_mode == OFDM_SYNC_REFERENCE) {
         // 1r. the reference's own detector (src/receiver.rs:20-25): cross-correlation with the locking signal, offset =
@@ -1977,6 +1990,86 @@ int ofdm_abi_rx_decode_known(ofdm_ctx *c, const ofdm_fc32 *in, int64_t frame_len
     const DecodeCall d{reinterpret_cast<const float2 *>(in), 1, frame_len, frame_len, 0, max_symbols, out, out_stride, out_len, status, offset,
                        f_delta_out, metric_out, &k};
     return rx_decode(c, d);
+}
+
+// ---- EXT-13: every packet of one long capture in one batched decode (include/ofdm_hip.h; tests/packets_ref.py)
+// The gathered rows of one chunk never exceed this (at least one row a chunk)
+static const int64_t kPacketRowsBytes = 256ll << 20;
+static const int64_t kPacketsMaxSamples = (int64_t)1 << 40; // ofdm_sc_scan_long's bound: what the 64-bit sample indices are held to
+
+int ofdm_abi_rx_decode_packets(ofdm_ctx *c, const float2 *in, int64_t n, int64_t n_det, const int64_t *d_hat, const double *f_delta,
+                               const float *metric, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len, int32_t *status,
+                               int64_t *offset, double *f_delta_out, float *metric_out) {
+    const int S = c->S();
+    const int64_t R = std::min<int64_t>((10 + (int64_t)max_symbols) * S + 2, (n + 1) & ~(int64_t)1);
+    int64_t chunk = c->tune.packets_chunk_rows > 0 ? c->tune.packets_chunk_rows : kPacketRowsBytes / (R * (int64_t)sizeof(float2));
+    chunk = std::min(std::max<int64_t>(chunk, 1), n_det);
+    const size_t nd = (size_t)n_det;
+    void *w_det, *w_geom, *w_rows, *w_fd = nullptr, *w_off;
+    int rc;
+    if ((rc = ws_get(c, kWsPktDet, nd * 20 + 16, &w_det))) return rc;
+    if ((rc = ws_get(c, kWsPktGeom, nd * 16 + 16, &w_geom))) return rc;
+    if ((rc = ws_get(c, kWsPktRows, (size_t)chunk * (size_t)R * sizeof(float2) + 256, &w_rows))) return rc;
+    if (!f_delta_out && (rc = ws_get(c, kWsPktFdelta, nd * sizeof(double), &w_fd))) return rc;
+    if ((rc = ws_get(c, kWsPktOffset, nd * sizeof(int32_t), &w_off))) return rc;
+    PktParams p;
+    p.tune = &c->tune; p.trace = &c->trace;
+    p.in = in; p.n = n; p.n_det = n_det; p.R = R; p.L = S; p.backoff = c->prm.sync_backoff;
+    long long *up_d = static_cast<long long *>(w_det);          // d_hat i64 | f_delta f64 | metric f32
+    double *up_fd = reinterpret_cast<double *>(up_d + nd);
+    float *up_m = reinterpret_cast<float *>(up_fd + nd);
+    p.d_hat = up_d; p.f_delta_in = up_fd; p.metric_in = up_m;
+    p.row_start = static_cast<long long *>(w_geom);             // row_start i64 | row_dhat i32 | row_len i32
+    p.row_dhat = reinterpret_cast<int32_t *>(p.row_start + nd);
+    p.row_len = p.row_dhat + nd;
+    p.f_delta = f_delta_out ? f_delta_out : static_cast<double *>(w_fd);
+    p.metric = metric_out;
+    p.rows = static_cast<float2 *>(w_rows);
+    HIP_TRY(c, hipMemcpyAsync(up_d, d_hat, nd * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(up_fd, f_delta, nd * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(up_m, metric, nd * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, run_pkt_rows(p, c->stream));
+    int32_t *row_off = static_cast<int32_t *>(w_off);
+    Trace head = c->trace, first; // (the chain's entry resets the context's trace: the names are put together at the end)
+    first.reset();
+    for (int64_t k0 = 0; k0 < n_det; k0 += chunk) {
+        const int64_t m = std::min(chunk, n_det - k0);
+        p.row0 = k0; p.n_rows = m;
+        p.trace = k0 == 0 ? &head : nullptr;
+        HIP_TRY(c, run_gather_rows(p, c->num_cu, c->stream));
+        if (c->tune.packets_gather_only) continue; // laboratory key: the gather's time on its own, nothing is delivered
+        const KnownSync k{0, 0.0, 0.f, p.row_dhat + k0, p.row_len + k0};
+        const DecodeCall d{p.rows, m, R, R, 0, max_symbols, out + k0 * out_stride, out_stride, out_len + k0, status + k0, row_off + k0,
+                           p.f_delta + k0, nullptr, &k};
+        if ((rc = rx_decode(c, d))) return rc;
+        if (k0 == 0) first = c->trace;
+    }
+    c->trace = head;
+    if (first.len) c->trace.add(first.buf);
+    if (offset && !c->tune.packets_gather_only) {
+        c->trace.add("k_pkt_finish");
+        HIP_TRY(c, run_pkt_finish(n_det, p.row_start, row_off, status, reinterpret_cast<long long *>(offset), c->stream));
+    }
+    return OFDM_OK;
+}
+
+int ofdm_rx_decode_packets(ofdm_ctx *c, const ofdm_fc32 *in_dev, int64_t n_samples, int64_t n_det, const int64_t *d_hat, const double *f_delta,
+                           const float *metric, int32_t max_symbols, uint8_t *out_dev, int64_t out_stride, int32_t *out_len_dev,
+                           int32_t *status_dev, int64_t *offset_dev, double *f_delta_dev, float *metric_dev) {
+    if (!c || n_det < 0 || n_samples < 0 || max_symbols <= 0) return OFDM_ERR_INVALID;
+    if (n_det && (!in_dev || !d_hat || !f_delta || !metric || !out_dev || !out_len_dev || !status_dev)) return OFDM_ERR_INVALID;
+    if (c->prm.sync_mode != OFDM_SYNC_SCHMIDL_COX || n_samples > kPacketsMaxSamples || n_det > 0x7fffffff) return OFDM_ERR_UNSUPPORTED;
+    for (int64_t k = 0; k < n_det; k++)
+        if (d_hat[k] < 0 || d_hat[k] >= n_samples) return OFDM_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(in_dev) & 7) return OFDM_ERR_INVALID;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    if (!n_det) return OFDM_OK;
+    // (the row-size rule of ofdm_rx_decode_batch is checked by the chain before its first launch, but behind the upload: check it here)
+    const int64_t raw_bytes = (int64_t)max_symbols * c->bytes_per_symbol();
+    if (out_stride < row_bytes(c->mode, raw_bytes > 16 ? raw_bytes - 16 : 0)) return OFDM_ERR_INVALID;
+    return ofdm_abi_rx_decode_packets(c, reinterpret_cast<const float2 *>(in_dev), n_samples, n_det, d_hat, f_delta, metric, max_symbols, out_dev,
+                                      out_stride, out_len_dev, status_dev, offset_dev, f_delta_dev, metric_dev);
 }
 
 // CHANNEL (src/channel.rs:26-31): 64 taps, the non-zero ones are 8..16 and 18

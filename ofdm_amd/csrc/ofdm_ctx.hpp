@@ -87,6 +87,9 @@ enum WsRole {
     kWsLongSc16,                 // EXT-10: one long sc16 capture widened, the input of the fc32 long decode (ofdm_rx_decode_long_sc16[_host])
     kWsNoiseWeight,              // EXT-11: per row of the decode chain the n_fft LLR weights q_k of k_noise_bins, read by k_sym<llrw> (OFDM_LLRW_NOISE)
     kWsScanBits, kWsScanRows,    // EXT-12: ofdm_sc_scan_long's bitmap of crossings; its head {n_det, more} and the rows d1 | d_hat | f_delta | metric
+    kWsPktDet, kWsPktGeom,       // EXT-13: ofdm_rx_decode_packets' uploaded detections d_hat | f_delta | metric; per packet row_start | row d_hat | row length
+    kWsPktRows,                  // EXT-13: one chunk of gathered rows (R samples each), the input of the chain
+    kWsPktFdelta, kWsPktOffset,  // EXT-13: per packet the chain's f_delta when the caller takes none; the chain's int32 row offsets
     kWsRoles
 };
 
@@ -170,4 +173,9 @@ __attribute__((visibility("hidden"))) int ofdm_abi_sc_run(ofdm_ctx *c, const flo
 __attribute__((visibility("hidden"))) int ofdm_abi_rx_decode_known(ofdm_ctx *c, const ofdm_fc32 *in, int64_t frame_len, int32_t d_hat, double f_delta, float metric,
                     int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len, int32_t *status, int32_t *offset, double *f_delta_out,
                     float *metric_out);
+// EXT-13 (ofdm_rx_decode_packets without the argument checks, the device guard and the trace reset: ofdm_rx_decode_all_long_host runs it
+// behind its scan)
+__attribute__((visibility("hidden"))) int ofdm_abi_rx_decode_packets(ofdm_ctx *c, const float2 *in, int64_t n, int64_t n_det, const int64_t *d_hat,
+                    const double *f_delta, const float *metric, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
+                    int32_t *status, int64_t *offset, double *f_delta_out, float *metric_out);
 }

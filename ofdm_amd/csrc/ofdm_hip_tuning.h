@@ -40,6 +40,11 @@
 //   every detection of a long capture (EXT-12)
 //     scan_mark_only      ofdm_sc_scan_long launches k_sc_mark alone over its lag range and reports no detection: the kernel's time on
 //                         its own (tools/bench_scan.py)
+//   every packet of a long capture in one batched decode (EXT-13)
+//     packets_chunk_rows  packets per k_gather_rows + chain step of ofdm_rx_decode_packets (0 = as many as keep the gathered rows within
+//                         256 MiB; the tests force chunks of 2 rows)
+//     packets_gather_only ofdm_rx_decode_packets launches k_pkt_rows + k_gather_rows alone and delivers nothing: the gather's time on its
+//                         own (tools/bench_packets.py)
 //   Schmidl-Cox threshold in full precision (handled by name in ofdm_abi.hip, 64 bits: not in the table below)
 //     sync_threshold_bits the bit pattern of a double in (0, 1] that replaces ofdm_params.sync_threshold (a float: 6e-8 apart) in every
 //                         search of the context; 0 = the float again.  The margin tests set the threshold within 1e-12 of a lag's own metric
@@ -79,6 +84,8 @@ OFDM_TUNE_KEY("no_demod64_sc16", no_demod64_sc16, false)
 OFDM_TUNE_KEY("sc16_chunk_frames", sc16_chunk_frames, false)
 OFDM_TUNE_KEY("no_txframe64_sc16", no_txframe64_sc16, false)
 OFDM_TUNE_KEY("scan_mark_only", scan_mark_only, false)
+OFDM_TUNE_KEY("packets_chunk_rows", packets_chunk_rows, false)
+OFDM_TUNE_KEY("packets_gather_only", packets_gather_only, false)
 OFDM_TUNE_KEY("debug_demod64", debug_demod64, true)
 OFDM_TUNE_KEY("debug_sc", debug_sc, true)
 OFDM_TUNE_KEY("debug_tx", debug_tx, true)

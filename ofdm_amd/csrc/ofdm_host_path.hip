@@ -843,6 +843,58 @@ int ofdm_sc_scan_long_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_samp
     return rc;
 }
 
+// EXT-13: upload, ofdm_sc_scan_long, ofdm_rx_decode_packets with the scan's rows, one D2H of everything.  Two synchronisations whatever
+// the packet count: the scan's (its rows size the decode) and the one behind the last copy.  The device results live in d_out[0] as
+// offset i64 | f_delta f64 | out_len | status i32 | metric f32 (n_det each) | the output rows.
+int ofdm_rx_decode_all_long_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_samples, int64_t lag_lo, int64_t lag_hi, int64_t holdoff,
+                                 int64_t max_det, int32_t max_symbols, uint8_t *out_host, int64_t out_stride, int32_t *out_len, int32_t *status,
+                                 int64_t *offset, double *f_delta, float *metric, int64_t *d1, int64_t *d_hat, int64_t *n_det, int32_t *more) {
+    int rc = sc_scan_check(c, in_host, n_samples, lag_lo, holdoff, max_det, d_hat, n_det);
+    if (rc) return rc;
+    if (max_symbols <= 0 || out_stride <= 0 || (max_det && (!out_host || !out_len || !status || !f_delta || !metric))) return OFDM_ERR_INVALID;
+    const int64_t raw_bytes = (int64_t)max_symbols * c->bytes_per_symbol();
+    if (out_stride < row_bytes(c->mode, raw_bytes > 16 ? raw_bytes - 16 : 0)) return OFDM_ERR_INVALID;
+    *n_det = 0;
+    if (more) *more = 0;
+    if (!n_samples) return OFDM_OK;
+    DeviceGuard dev_guard(c->device);
+    c->trace.reset();
+    HostPipe *hp;
+    if ((rc = pipe_get(c, &hp))) return rc;
+    auto work = [&]() -> int { // as ofdm_rx_decode_long_host: once the upload has started, a failure waits for it before it is returned
+        const size_t bytes = (size_t)n_samples * sizeof(ofdm_fc32);
+        if ((rc = dev_grow(c, hp, hp->d_long, bytes + 64))) return rc;
+        if ((rc = long_upload(c, hp, hp->d_long.p, in_host, bytes))) return rc;
+        const float2 *x = static_cast<const float2 *>(hp->d_long.p);
+        // (f_delta and metric receive the scan's rows first: they are the decode's input, and its outputs overwrite them)
+        if ((rc = sc_scan_dev(c, x, n_samples, lag_lo, lag_hi, holdoff, max_det, d1, d_hat, f_delta, metric, n_det, more))) return rc;
+        const size_t nd = (size_t)*n_det;
+        if (!nd) return OFDM_OK;
+        const size_t scal = (nd * 28 + 15) & ~(size_t)15, rows = nd * (size_t)out_stride;
+        if ((rc = dev_grow(c, hp, hp->d_out[0], scal + rows + 64))) return rc;
+        char *o = static_cast<char *>(hp->d_out[0].p);
+        int64_t *o_off = reinterpret_cast<int64_t *>(o);
+        double *o_fd = reinterpret_cast<double *>(o + 8 * nd);
+        int32_t *o_len = reinterpret_cast<int32_t *>(o + 16 * nd), *o_st = o_len + nd;
+        float *o_m = reinterpret_cast<float *>(o + 24 * nd);
+        // (the decode keeps what the trace holds in front of it: the dispatch string is the scan's kernels, then the decode's)
+        rc = ofdm_abi_rx_decode_packets(c, x, n_samples, (int64_t)nd, d_hat, f_delta, metric, max_symbols, reinterpret_cast<uint8_t *>(o + scal),
+                                        out_stride, o_len, o_st, o_off, o_fd, o_m);
+        if (rc) return rc;
+        if (offset) HIP_TRY(c, hipMemcpyAsync(offset, o_off, 8 * nd, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(f_delta, o_fd, 8 * nd, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(out_len, o_len, 4 * nd, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(status, o_st, 4 * nd, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(metric, o_m, 4 * nd, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(out_host, o + scal, rows, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return OFDM_OK;
+    };
+    rc = work();
+    if (rc) sync_all(c, hp);
+    return rc;
+}
+
 int ofdm_rx_decode_long(ofdm_ctx *c, const ofdm_fc32 *in_dev, int64_t n_samples, int64_t lag_lo, int64_t lag_hi, int64_t d_hat_known,
                         int32_t max_symbols, uint8_t *out_dev, int64_t out_cap, int32_t *out_len, int32_t *status, int64_t *offset,
                         double *f_delta, float *metric) {
