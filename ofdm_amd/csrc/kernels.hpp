@@ -57,16 +57,28 @@ struct Tuning {
 };
 inline const Tuning &tuning_or_default(const Tuning *t) { static const Tuning d; return t ? *t : d; }
 
-// Which kernels served the last entry point (ofdm_last_dispatch): every launcher appends the kernel it really launched.
+// Which kernels served the last entry point (ofdm_last_dispatch): every launcher appends the kernel it really launched, in launch
+// order.  Only an entry point's scope resets it (EntryScope, ofdm_ctx.hpp); launches the string leaves out on purpose -- the chunks
+// behind the first of a chunk loop -- run under a Mute.
 struct Trace {
-    char buf[256];
+    char buf[256] = {};
     int len = 0;
+    int muted = 0;
     void reset() { len = 0; buf[0] = 0; }
     void add(const char *name) {
+        if (muted) return;
         if (len && len < (int)sizeof(buf) - 1) buf[len++] = '+';
         while (*name && len < (int)sizeof(buf) - 1) buf[len++] = *name++;
         buf[len] = 0;
     }
+    struct Mute { // add() does nothing while one is alive (on = false: a guard that does nothing, for `Mute later(trace, f0 > 0)`)
+        Trace &t;
+        const bool on;
+        explicit Mute(Trace &t, bool on = true) : t(t), on(on) { t.muted += on; }
+        ~Mute() { t.muted -= on; }
+        Mute(const Mute &) = delete;
+        Mute &operator=(const Mute &) = delete;
+    };
 };
 inline void trace_add(Trace *t, const char *name) { if (t) t->add(name); }
 
@@ -483,7 +495,7 @@ hipError_t run_rx_prepare(long long n_frames, const int32_t *d_hat, double *f_de
                           int backoff, int cfo_mode, int max_symbols, int bytes_per_symbol, int32_t *status,
                           int32_t *offset, int32_t *nsym, hipStream_t st, const int32_t *frame_list = nullptr,
                           const int32_t *frame_count = nullptr);
-// one capture's timing written where the search would have left it (ofdm_abi_rx_decode_known)
+// one capture's timing written where the search would have left it (DecodeCall::known: ofdm_rx_decode_long with lag_lo > 0)
 hipError_t run_set_sync(int32_t *d_hat, double *f_delta, float *metric, int32_t d, double fd, float m, hipStream_t st);
 // RX finish: header parse + truncate [+ Hamming decode] (receiver.rs:85-95)
 hipError_t run_rx_finish(const uint8_t *raw, long long raw_stride, long long n_frames, const int32_t *status,

@@ -183,7 +183,7 @@ static int cfo_wide_table(ofdm_ctx *c) {
 // rows of N bins `in` -> `out` (in == out allowed), per frame chunk: weight -> inverse FFT -> k_chest_solve -> forward FFT.  The
 // one workspace (the solve's zeroed rows) holds a chunk, at most kChestChunkBytes whatever n_frames is.
 static const int64_t kChestChunkBytes = 64ll << 20;
-static int chest_smooth_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, float2 *out, bool trace) {
+static int chest_smooth_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, float2 *out) {
     int rc = chest_tables(c);
     if (rc) return rc;
     const int N = c->prm.n_fft;
@@ -193,25 +193,24 @@ static int chest_smooth_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, flo
     if ((rc = ws_get(c, kWsChestTaps, sizeof(float2) * (size_t)N * (size_t)chunk, &w_taps))) return rc;
     for (int64_t f0 = 0; f0 < n_frames; f0 += chunk) {
         const int64_t nf = n_frames - f0 < chunk ? n_frames - f0 : chunk;
-        const bool tr = trace && f0 == 0;
+        const Trace::Mute later(c->trace, f0 > 0); // the dispatch string names what a chunk ran, once
         float2 *rows = out + f0 * N;
         if (c->tune.chest_solve_only) { // laboratory key: the contraction alone, timed by tools/bench_chest.py
             ChestSolveParams sp;
             sp.g = in + f0 * N; sp.out = (float2 *)w_taps; sp.mt = c->d_chest_mt; sp.n_frames = nf; sp.n_fft = N; sp.n_taps = N / 4; sp.pre = N / 16;
-            if (tr) c->trace.add("k_chest_solve");
+            c->trace.add("k_chest_solve");
             HIP_TRY(c, run_chest_solve(sp, c->num_cu, &c->tune, c->stream));
             continue;
         }
-        if (tr) c->trace.add("k_chest_weight");
+        c->trace.add("k_chest_weight");
         HIP_TRY(c, run_chest_weight(in + f0 * N, c->d_chest_w, rows, nf, N, c->num_cu, &c->tune, c->stream));
         SymParams p = base_params(c);
-        if (!tr) p.trace = nullptr;
         p.n_frames = nf; p.frame_stride = N; p.frame_len = N; p.syms_per_frame = 1; p.in_sym_stride = N; p.in_skip = 0;
         p.in = rows; p.out = rows;
         HIP_TRY(c, run_fft(N, p, true, c->stream, c->num_cu));
         ChestSolveParams sp;
         sp.g = rows; sp.out = (float2 *)w_taps; sp.mt = c->d_chest_mt; sp.n_frames = nf; sp.n_fft = N; sp.n_taps = N / 4; sp.pre = N / 16;
-        if (tr) c->trace.add("k_chest_solve");
+        c->trace.add("k_chest_solve");
         HIP_TRY(c, run_chest_solve(sp, c->num_cu, &c->tune, c->stream));
         p.in = (const float2 *)w_taps; p.out = rows;
         HIP_TRY(c, run_fft(N, p, false, c->stream, c->num_cu));
@@ -424,7 +423,6 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
     c->prm = *p;
     c->mode = mode;
     c->device = device;
-    c->trace.reset();
     c->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     int rc = OFDM_OK;
     do {
@@ -620,8 +618,7 @@ int64_t ofdm_frame_samples(const ofdm_ctx *c, int64_t payload_bytes) {
 // ------------------------------------------------------------------ stage level
 int ofdm_fft_batch(ofdm_ctx *c, const ofdm_fc32 *in, ofdm_fc32 *out, int64_t n_vec, int inverse) {
     if (!c || n_vec < 0 || (n_vec && (!in || !out))) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     SymParams p = base_params(c);
     const int N = c->prm.n_fft;
     p.in = reinterpret_cast<const float2 *>(in); p.out = reinterpret_cast<float2 *>(out);
@@ -631,8 +628,7 @@ int ofdm_fft_batch(ofdm_ctx *c, const ofdm_fc32 *in, ofdm_fc32 *out, int64_t n_v
 }
 int ofdm_ifft_cp_batch(ofdm_ctx *c, const ofdm_fc32 *freq, ofdm_fc32 *out, int64_t n_sym) {
     if (!c || n_sym < 0 || (n_sym && (!freq || !out))) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     SymParams p = base_params(c);
     const int N = c->prm.n_fft;
     p.in = reinterpret_cast<const float2 *>(freq); p.out = reinterpret_cast<float2 *>(out);
@@ -645,8 +641,7 @@ int ofdm_tx_symbols_batch(ofdm_ctx *c, const uint8_t *bytes, int64_t n_bytes, of
     const int bps_bytes = c->bytes_per_symbol();
     if (n_sym * (int64_t)bps_bytes < n_bytes) return OFDM_ERR_INVALID; // every byte must land in a symbol
     if (!n_sym) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     SymParams p = base_params(c);
     p.n_frames = n_sym; p.syms_per_frame = 1;
     p.payload = bytes; p.payload_stride = bps_bytes; p.payload_len = nullptr; p.payload_bytes = bps_bytes;
@@ -661,8 +656,7 @@ int ofdm_tx_symbols_batch(ofdm_ctx *c, const uint8_t *bytes, int64_t n_bytes, of
 }
 int ofdm_unprefix_batch(ofdm_ctx *c, const ofdm_fc32 *in, ofdm_fc32 *out, int64_t n_sym) {
     if (!c || n_sym < 0 || (n_sym && (!in || !out))) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     SymParams p = base_params(c);
     const int N = c->prm.n_fft, S = c->S();
     p.in = reinterpret_cast<const float2 *>(in); p.out = reinterpret_cast<float2 *>(out);
@@ -672,31 +666,27 @@ int ofdm_unprefix_batch(ofdm_ctx *c, const ofdm_fc32 *in, ofdm_fc32 *out, int64_
 }
 int ofdm_qam_map_batch(ofdm_ctx *c, const uint8_t *bytes, int64_t n_bytes, ofdm_fc32 *out) {
     if (!c || n_bytes < 0 || (n_bytes && (!bytes || !out))) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     HIP_TRY(c, run_qam_map(bytes, n_bytes, c->prm.modulation, reinterpret_cast<float2 *>(out), c->stream));
     return OFDM_OK;
 }
 int ofdm_qam_demap_batch(ofdm_ctx *c, const ofdm_fc32 *sym, int64_t n_sym, uint8_t *bytes, uint8_t *idx) {
     if (!c || n_sym < 0 || (n_sym && !sym)) return OFDM_ERR_INVALID;
     if (n_sym % 8 != 0) return OFDM_ERR_INVALID; // assert_eq!(remainder.len(), 0), src/receiver.rs:153
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     HIP_TRY(c, run_qam_demap(reinterpret_cast<const float2 *>(sym), n_sym, c->prm.modulation, bytes, idx, c->stream));
     return OFDM_OK;
 }
 int ofdm_encode_block_batch(ofdm_ctx *c, const ofdm_fc32 *data, ofdm_fc32 *bins, int64_t n_sym) {
     if (!c || n_sym < 0 || (n_sym && (!data || !bins))) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     HIP_TRY(c, run_encode_block(reinterpret_cast<const float2 *>(data), reinterpret_cast<float2 *>(bins), n_sym,
                                 c->prm.n_fft, c->prm.guard_bands, c->stream));
     return OFDM_OK;
 }
 int ofdm_normalize_batch(ofdm_ctx *c, ofdm_fc32 *x, int64_t n_frames, int64_t frame_stride, int64_t frame_len) {
     if (!c || n_frames < 0 || frame_len < 0 || frame_stride < frame_len || (n_frames && !x)) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     if (!n_frames) return OFDM_OK;
     void *mx;
     int rc = ws_get(c, kWsFrameMax, sizeof(unsigned) * (size_t)n_frames, &mx);
@@ -708,22 +698,19 @@ int ofdm_normalize_batch(ofdm_ctx *c, ofdm_fc32 *x, int64_t n_frames, int64_t fr
 }
 int ofdm_hamming74_encode(ofdm_ctx *c, const uint8_t *in, int64_t n_bytes, uint8_t *out) {
     if (!c || n_bytes < 0 || (n_bytes && (!in || !out))) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     HIP_TRY(c, run_ham_encode(in, 1, 0, nullptr, n_bytes, out, 0, nullptr, c->stream));
     return OFDM_OK;
 }
 int ofdm_hamming74_decode(ofdm_ctx *c, const uint8_t *in, int64_t n_bytes, uint8_t *out, uint32_t *corrected) {
     if (!c || n_bytes < 0 || (n_bytes >= 7 && (!in || !out))) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     HIP_TRY(c, run_ham_decode(in, n_bytes, out, corrected, c->stream));
     return OFDM_OK;
 }
 int ofdm_hamming74_decode_soft(ofdm_ctx *c, const int8_t *llr, int64_t n_bits, uint8_t *out) {
     if (!c || n_bits < 0 || (n_bits >= 56 && (!llr || !out))) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     c->trace.add("k_ham_decode_soft");
     HIP_TRY(c, run_ham_decode_soft(llr, n_bits, out, c->stream));
     return OFDM_OK;
@@ -744,8 +731,7 @@ int ofdm_conv_k7_encode(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_
     if (!c || n_frames < 0 || n_bytes < 0 || in_stride < n_bytes || out_stride < 2 * (n_bytes + 1)) return OFDM_ERR_INVALID;
     if (n_frames && (!out || (n_bytes && !in))) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     c->trace.add("k_conv_encode");
     HIP_TRY(c, run_conv_encode(in, n_frames, in_stride, nullptr, n_bytes, out, out_stride, nullptr, c->stream));
     return OFDM_OK;
@@ -756,8 +742,7 @@ int ofdm_conv_k7_decode_soft(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, i
     if (n_steps > kViterbiMaxSteps) return OFDM_ERR_UNSUPPORTED;
     if (n_frames && n_steps && (!llr || (n_steps >= 8 && !out))) return OFDM_ERR_INVALID;
     if (!n_frames || !n_steps) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     ViterbiParams p;
     long long blocks;
     int rc = viterbi_survivors(c, n_frames, n_steps, p, &blocks);
@@ -779,8 +764,7 @@ int ofdm_conv_k7_encode_punctured(ofdm_ctx *c, const uint8_t *in, int64_t n_fram
     if (in_stride < n_bytes || out_stride < conv_body_len(n_bytes, rate)) return OFDM_ERR_INVALID;
     if (n_frames && (!out || (n_bytes && !in))) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     c->trace.add("k_conv_encode_p");
     HIP_TRY(c, run_conv_encode_p(in, n_frames, in_stride, nullptr, n_bytes, rate, 0, out, out_stride, nullptr, c->stream));
     return OFDM_OK;
@@ -792,8 +776,7 @@ int ofdm_conv_k7_decode_punctured(ofdm_ctx *c, const int8_t *llr, int64_t n_fram
     if (llr_stride < conv_kept_bits(n_steps, rate) || out_stride < n_steps / 8) return OFDM_ERR_INVALID;
     if (n_frames && n_steps && (!llr || (n_steps >= 8 && !out))) return OFDM_ERR_INVALID;
     if (!n_frames || !n_steps) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     ViterbiFParams p;
     long long blocks;
     int rc = viterbi_survivors(c, n_frames, n_steps, p, &blocks);
@@ -856,8 +839,7 @@ int ofdm_rs255_encode_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, in
     if (!c || n_frames < 0 || n_bytes < 0 || in_stride < n_bytes || out_stride < ofdm_rs255_encoded_len(n_bytes)) return OFDM_ERR_INVALID;
     if (n_frames && (!out || (n_bytes && !in))) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     c->trace.add("k_rs255_encode");
     HIP_TRY(c, rs_encode(c, LayerCall{in, n_frames, in_stride, n_bytes, in_len, out, out_stride, nullptr, nullptr, nullptr}));
     return OFDM_OK;
@@ -867,8 +849,7 @@ int ofdm_rs255_decode_batch(ofdm_ctx *c, const uint8_t *code, int64_t n_frames, 
     if (!c || n_frames < 0 || n_code < 0 || code_stride < n_code || out_stride < ofdm_rs255_decoded_len(n_code)) return OFDM_ERR_INVALID;
     if (n_frames && (!out || (n_code && !code))) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     c->trace.add("k_rs255_decode");
     HIP_TRY(c, rs_decode(c, LayerCall{code, n_frames, code_stride, n_code, code_len, out, out_stride, out_len, corrected, nullptr}));
     return OFDM_OK;
@@ -882,8 +863,7 @@ int ofdm_ldpc648_encode_rate_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_fra
     if (in_stride < kLdpcCodes[rate].info_bytes * n_cw || out_stride < kLdpcCodeBytes * n_cw) return OFDM_ERR_INVALID;
     if (n_frames && n_cw && (!in || !out)) return OFDM_ERR_INVALID;
     if (!n_frames || !n_cw) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     LdpcEncodeParams p;
     p.in = in; p.n_frames = n_frames; p.in_stride = in_stride; p.n_cw = n_cw; p.out = out; p.out_stride = out_stride;
     c->trace.add(ldpc_encode_name(rate));
@@ -897,8 +877,7 @@ int ofdm_ldpc648_decode_rate_batch(ofdm_ctx *c, const int8_t *llr, int64_t n_fra
     if (llr_stride < kLdpcSentBits * n_cw || out_stride < kLdpcCodes[rate].info_bytes * n_cw) return OFDM_ERR_INVALID;
     if (n_frames && n_cw && (!llr || !out)) return OFDM_ERR_INVALID;
     if (!n_frames || !n_cw) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     LdpcDecodeParams p;
     p.llr = llr; p.n_frames = n_frames; p.llr_stride = llr_stride; p.n_cw = n_cw; p.max_iter = max_iter; p.out = out; p.out_stride = out_stride;
     p.iters = iters;
@@ -923,8 +902,7 @@ int ofdm_fcs_wrap_batch(ofdm_ctx *c, const uint8_t *in, int64_t n_frames, int64_
     if (n_bytes > 0x7fffffffll - OFDM_FCS_OVERHEAD) return OFDM_ERR_UNSUPPORTED; // the length word and out_len are 32 bits
     if (n_frames && (!out || (n_bytes && !in))) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     c->trace.add("k_fcs_wrap");
     HIP_TRY(c, fcs_wrap(c, LayerCall{in, n_frames, in_stride, n_bytes, in_len, out, out_stride, out_len, nullptr, nullptr}));
     return OFDM_OK;
@@ -935,8 +913,7 @@ int ofdm_fcs_check_batch(ofdm_ctx *c, const uint8_t *row, int64_t n_frames, int6
     if (n_row > 0x7fffffffll) return OFDM_ERR_UNSUPPORTED;
     if (n_frames && ((n_row > OFDM_FCS_OVERHEAD && !out) || (n_row && !row))) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     c->trace.add("k_fcs_check");
     HIP_TRY(c, fcs_check(c, LayerCall{row, n_frames, row_stride, n_row, row_len, out, out_stride, out_len, ok, nullptr}));
     return OFDM_OK;
@@ -1041,8 +1018,7 @@ int ofdm_sc_correlate_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, 
     if (!c || n_frames < 0 || frame_len <= 0 || frame_stride < 0 || (n_frames && (!in || !d_hat))) return OFDM_ERR_INVALID;
     if (n_frames > 1 && frame_stride <= 0) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     return ofdm_abi_sc_run(c, reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, n_lags, d_hat, f_delta, metric);
 }
 int ofdm_xcorr_batch(ofdm_ctx *c, const ofdm_fc32 *a, int64_t n_frames, int64_t a_stride, int64_t a_len, const ofdm_fc32 *b,
@@ -1052,8 +1028,7 @@ int ofdm_xcorr_batch(ofdm_ctx *c, const ofdm_fc32 *a, int64_t n_frames, int64_t 
     if (n_frames > 1 && a_stride <= 0) return OFDM_ERR_INVALID;
     if (out && out_stride < 2 * a_len - 1) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     void *w;
     int rc = ws_get(c, kWsSearch, xcorr_workspace_bytes(n_frames, a_len, nb), &w);
     if (rc) return rc;
@@ -1065,28 +1040,25 @@ int ofdm_xcorr_batch(ofdm_ctx *c, const ofdm_fc32 *a, int64_t n_frames, int64_t 
 int ofdm_frequency_correction_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_pairs, int64_t stride,
                                     int64_t right_offset, double *f_delta) {
     if (!c || n_pairs < 0 || (n_pairs && (!in || !f_delta))) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     HIP_TRY(c, run_freq_correction(reinterpret_cast<const float2 *>(in), n_pairs, stride, right_offset, c->S(), f_delta, c->stream));
     return OFDM_OK;
 }
 int ofdm_cfo_rotate_batch(ofdm_ctx *c, ofdm_fc32 *x, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
                           const double *f_delta, const int32_t *first_index) {
     if (!c || n_frames < 0 || frame_len < 0 || (n_frames && (!x || !f_delta))) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     HIP_TRY(c, run_cfo_rotate(reinterpret_cast<float2 *>(x), n_frames, frame_stride, frame_len, f_delta, first_index, c->stream));
     return OFDM_OK;
 }
 int ofdm_estimate_channel_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride,
                                 int64_t frame_len, const int32_t *offset, const double *f_delta, ofdm_fc32 *hk) {
     if (!c || n_frames < 0 || frame_len <= 0 || (n_frames && (!in || !hk))) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     SymParams p = rx_params(c, reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, offset, f_delta);
     p.out = reinterpret_cast<float2 *>(hk);
     HIP_TRY(c, run_chest(c->prm.n_fft, p, c->stream, c->num_cu));
-    if (c->prm.chest_mode == OFDM_CHEST_WLS && n_frames) return chest_smooth_run(c, p.out, n_frames, p.out, true);
+    if (c->prm.chest_mode == OFDM_CHEST_WLS && n_frames) return chest_smooth_run(c, p.out, n_frames, p.out);
     return OFDM_OK;
 }
 
@@ -1109,9 +1081,8 @@ int ofdm_chest_window(const ofdm_ctx *c, int32_t *first_tap, int32_t *n_taps) {
 int ofdm_chest_smooth_batch(ofdm_ctx *c, const ofdm_fc32 *hk_in, int64_t n_frames, ofdm_fc32 *hk_out) {
     if (!c || n_frames < 0 || (n_frames && (!hk_in || !hk_out))) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
-    return chest_smooth_run(c, reinterpret_cast<const float2 *>(hk_in), n_frames, reinterpret_cast<float2 *>(hk_out), true);
+    EntryScope scope(c);
+    return chest_smooth_run(c, reinterpret_cast<const float2 *>(hk_in), n_frames, reinterpret_cast<float2 *>(hk_out));
 }
 
 static int demod_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
@@ -1140,8 +1111,7 @@ int ofdm_rx_demod_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int6
     if (out_stride < (int64_t)syms_per_frame * c->bytes_per_symbol()) return OFDM_ERR_INVALID;
     if (hk && hk_stride != 0 && hk_stride != c->prm.n_fft) return OFDM_ERR_INVALID;
     if (!n_frames || !syms_per_frame) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     return demod_run(c, reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, first_symbol,
                      syms_per_frame, offset, f_delta, nullptr, reinterpret_cast<const float2 *>(hk), hk_stride, out,
                      out_stride, reinterpret_cast<float2 *>(soft));
@@ -1150,10 +1120,9 @@ int ofdm_rx_demod_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int6
 // int8 max-log LLRs in place of the hard bytes of ofdm_rx_demod_batch: k_sym<llr> (no shape-specialised kernel has the epilogue yet)
 static int llr_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len, int first_symbol,
                    int syms_per_frame, const int32_t *offset, const double *f_delta, const int32_t *nsym_frame, const float2 *hk,
-                   int64_t hk_stride, float llr_scale, int8_t *llr, int64_t llr_stride, uint8_t *hard, int64_t hard_stride, bool trace,
+                   int64_t hk_stride, float llr_scale, int8_t *llr, int64_t llr_stride, uint8_t *hard, int64_t hard_stride,
                    const float *bin_weight = nullptr, int64_t bin_weight_stride = 0) {
     SymParams p = rx_params(c, in, n_frames, frame_stride, frame_len, offset, f_delta, nsym_frame, hard, hard_stride);
-    if (!trace) p.trace = nullptr;
     p.first_symbol = first_symbol; p.syms_per_frame = syms_per_frame; p.in_sym_stride = c->S(); p.in_skip = c->prm.cp_len;
     p.hk = hk; p.hk_stride = hk_stride;
     p.llr = llr; p.llr_scale = llr_scale; p.llr_stride = llr_stride;
@@ -1183,10 +1152,9 @@ int ofdm_rx_llr_weighted_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frame
     if (hk && hk_stride != 0 && hk_stride != c->prm.n_fft) return OFDM_ERR_INVALID;
     if (bin_weight && bin_weight_stride != 0 && bin_weight_stride != c->prm.n_fft) return OFDM_ERR_INVALID;
     if (!n_frames || !syms_per_frame) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     return llr_run(c, reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, first_symbol, syms_per_frame, offset,
-                   f_delta, nullptr, reinterpret_cast<const float2 *>(hk), hk_stride, llr_scale, llr, llr_stride, nullptr, 0, true,
+                   f_delta, nullptr, reinterpret_cast<const float2 *>(hk), hk_stride, llr_scale, llr, llr_stride, nullptr, 0,
                    bin_weight, bin_weight_stride);
 }
 
@@ -1209,8 +1177,7 @@ int ofdm_rx_noise_bins_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames,
     if (!c || n_frames < 0 || frame_len <= 0 || frame_stride < 0) return OFDM_ERR_INVALID;
     if (n_frames && (!in || !offset)) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     return noise_bins_run(c, reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, offset, f_delta, status, nvar, weight);
 }
 int ofdm_set_llr_weight(ofdm_ctx *c, int32_t mode) {
@@ -1263,8 +1230,7 @@ int ofdm_rx_quality_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, in
     if (hk && hk_stride != 0 && hk_stride != c->prm.n_fft) return OFDM_ERR_INVALID;
     if ((int64_t)syms_per_frame * c->carriers() > (1ll << 24)) return OFDM_ERR_INVALID; // OFDM_Q_POINTS is a float
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     return linkq_run(c, reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, first_symbol, syms_per_frame, n_points, offset,
                      f_delta, reinterpret_cast<const float2 *>(hk), hk_stride, status, quality);
 }
@@ -1291,8 +1257,7 @@ int ofdm_cfo_wide_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int6
     if (span < 1 || span > OFDM_CFO_WIDE_MAX_SPAN) return OFDM_ERR_INVALID;
     if (n_frames && (!in || !offset || !f_delta)) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     return cfo_wide_run(c, reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, offset, status, span, f_delta, m, metric);
 }
 
@@ -1304,8 +1269,7 @@ int ofdm_llr_combine_batch(ofdm_ctx *c, const int8_t *llr, int64_t n_frames, int
     if (llr_stride < n_llr || out_stride < n_llr || (n_frames && (!llr || !out))) return OFDM_ERR_INVALID;
     if (n_llr > 0x7fffffffll - (1 << 13)) return OFDM_ERR_UNSUPPORTED; // the kernel's column indices are ints
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     CombineParams p;
     p.tune = &c->tune; p.trace = &c->trace;
     p.llr = llr; p.n_frames = n_frames; p.llr_stride = llr_stride; p.n_branches = n_branches; p.n_llr = (int)n_llr;
@@ -1411,23 +1375,11 @@ int ofdm_tx_encode_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_frames, 
     int64_t frame = 0;
     const int rc = tx_encode_check(c, payload, n_frames, payload_stride, payload_bytes, out, out_stride, &frame);
     if (rc || !n_frames) return rc;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     return tx_encode_fc32(c, payload, n_frames, payload_stride, payload_len, payload_bytes, reinterpret_cast<float2 *>(out), out_stride, frame);
 }
 
 namespace {
-// Timing the caller brings.  One capture: d_hat / f_delta / metric by value (ofdm_abi_rx_decode_known).  Rows (EXT-13, row_dhat != NULL):
-// device arrays of the row-relative peaks and of the rows' own lengths; the call's f_delta and offset arrays are not optional, f_delta
-// (and metric, if wanted) already hold the rows' values
-struct KnownSync { int32_t d_hat; double f_delta; float metric; const int32_t *row_dhat = nullptr, *row_len = nullptr; };
-// The arguments of a decode call: ofdm_rx_decode_batch's own, or captures with their timing (ofdm_abi_rx_decode_known, ofdm_rx_decode_packets)
-struct DecodeCall {
-    const float2 *in; int64_t n_frames, frame_stride, frame_len, n_lags; int32_t max_symbols;
-    uint8_t *out; int64_t out_stride;                          // rows of out_stride bytes
-    int32_t *out_len, *status, *offset; double *f_delta; float *metric; // per frame (offset, f_delta, metric: optional)
-    const KnownSync *known;
-};
 // What steps 1 - 4 of the chain leave to the soft finishing kernels (raw: the hard bytes, for the length header)
 struct SoftInput { int32_t *offs; double *fd; const int32_t *nsym; const float2 *hk; uint8_t *raw; int64_t raw_stride, body_steps; const float *q; };
 } // namespace
@@ -1469,15 +1421,17 @@ static int soft_finish_chunk(ofdm_ctx *c, const DecodeCall &d, int64_t f0, int64
 static const char *soft_finish_name(const ModePlan &m) {
     return m.ldpc() ? ldpc_decode_name(m.ldpc_rate()) : !m.conv() ? "k_rx_finish_soft" : m.rate() < 0 ? "k_viterbi_k7" : "k_viterbi_k7f";
 }
-// The LLR workspace holds one chunk: at most kSoftLlrBytes whatever n_frames is.
+// The frames of one chunk of the soft chains: the LLR workspace holds at most kSoftLlrBytes of rows whatever n_frames is
+static int64_t soft_chunk_frames(const ofdm_ctx *c, int64_t llr_row_bytes, int64_t n_frames) {
+    const int64_t chunk = c->tune.soft_chunk_frames > 0 ? c->tune.soft_chunk_frames : kSoftLlrBytes / llr_row_bytes;
+    return std::min(std::max<int64_t>(chunk, 1), n_frames);
+}
 static int rx_finish_soft(ofdm_ctx *c, const DecodeCall &d, const SoftInput &s) {
     const ModePlan &m = c->mode;
     const int N = c->prm.n_fft, bps_bytes = c->bytes_per_symbol();
     const int64_t llr_row = (int64_t)d.max_symbols * c->carriers() * c->prm.modulation;
     const int64_t llr_stride = (llr_row + 15) & ~(int64_t)15;
-    int64_t chunk = c->tune.soft_chunk_frames > 0 ? c->tune.soft_chunk_frames : kSoftLlrBytes / llr_stride;
-    if (chunk < 1) chunk = 1;
-    if (chunk > d.n_frames) chunk = d.n_frames;
+    const int64_t chunk = soft_chunk_frames(c, llr_stride, d.n_frames);
     void *w_llr;
     int rc;
     if ((rc = ws_get(c, kWsLlr, (size_t)(llr_stride * chunk), &w_llr))) return rc;
@@ -1492,13 +1446,14 @@ static int rx_finish_soft(ofdm_ctx *c, const DecodeCall &d, const SoftInput &s) 
     const char *name = soft_finish_name(m);
     for (int64_t f0 = 0; f0 < d.n_frames; f0 += chunk) {
         const int64_t nf = d.n_frames - f0 < chunk ? d.n_frames - f0 : chunk;
+        const Trace::Mute later(c->trace, f0 > 0); // the dispatch string names what a chunk ran, once
         const int32_t *nsym = s.nsym + f0;
         const uint8_t *raw = s.raw + f0 * s.raw_stride;
         rc = llr_run(c, d.in + f0 * d.frame_stride, nf, d.frame_stride, d.frame_len, 10, d.max_symbols, s.offs + f0, s.fd + f0, nsym,
-                     s.hk + f0 * N, N, OFDM_SOFT_LLR_SCALE, (int8_t *)w_llr, llr_stride, s.raw + f0 * s.raw_stride, s.raw_stride, f0 == 0,
+                     s.hk + f0 * N, N, OFDM_SOFT_LLR_SCALE, (int8_t *)w_llr, llr_stride, s.raw + f0 * s.raw_stride, s.raw_stride,
                      s.q ? s.q + f0 * N : nullptr, N);
         if (rc) return rc;
-        if (f0 == 0) c->trace.add(name);
+        c->trace.add(name);
         if ((rc = soft_finish_chunk(c, d, f0, nf, llr, llr_stride, nsym, raw, s.raw_stride, vp, v_blocks))) return rc;
     }
     return OFDM_OK;
@@ -1514,7 +1469,7 @@ static int inner_plan(ofdm_ctx *c, const DecodeCall &d, InnerPlan &ip) {
     ip.raw_stride = (ip.raw_bytes + 3) & ~(int64_t)3;   // rows of the raw-byte workspace start on dwords (6-byte BPSK symbols: odd counts)
     // rows must hold what k_rx_finish can write: the whole body without an outer code, floor(body / 7) * 4 bytes after
     // Hamming(7,4) decoding, body / 2 - 1 after Viterbi decoding (include/ofdm_hip.h)
-    ip.body_max = ip.raw_bytes > 16 ? ip.raw_bytes - 16 : 0;
+    ip.body_max = decode_body_bytes(c, d.max_symbols);
     if (d.out_stride < inner_row_limit(m, ip.body_max)) return OFDM_ERR_INVALID;
     const int f_rate = m.rate();
     // the longest trellis a frame can ask for (framed: the 72-step length block, then a body cut at the end of the capture)
@@ -1601,27 +1556,22 @@ static int rx_channel_estimate(ofdm_ctx *c, const DecodeCall &d, const FrontEnd 
     SymParams p = rx_params(c, d.in, d.n_frames, d.frame_stride, d.frame_len, fe.offs, fe.fd);
     p.out = (float2 *)w_hk;
     HIP_TRY(c, run_chest(N, p, c->stream, c->num_cu));
-    if (c->prm.chest_mode == OFDM_CHEST_WLS && (rc = chest_smooth_run(c, (const float2 *)w_hk, d.n_frames, (float2 *)w_hk, true))) return rc;
+    if (c->prm.chest_mode == OFDM_CHEST_WLS && (rc = chest_smooth_run(c, (const float2 *)w_hk, d.n_frames, (float2 *)w_hk))) return rc;
     *hk = (const float2 *)w_hk;
     return OFDM_OK;
 }
 
 // The chain of the plan's inner mode into the rows d.out / d.out_stride: the caller's, or the innermost outer layer's workspace
-static int rx_decode_inner(ofdm_ctx *c, const DecodeCall &d) {
+static int rx_decode_inner(ofdm_ctx *c, const DecodeCall &d, const InnerPlan &ip) {
     const ModePlan &m = c->mode;
     const int64_t n_frames = d.n_frames, frame_stride = d.frame_stride, frame_len = d.frame_len, out_stride = d.out_stride;
     const int32_t max_symbols = d.max_symbols;
     uint8_t *const out = d.out;
     int32_t *const out_len = d.out_len, *const status = d.status;
-    if (n_frames > 1 && frame_stride <= 0) return OFDM_ERR_INVALID;
-    InnerPlan ip;
     int rc;
-    if ((rc = inner_plan(c, d, ip))) return rc;
     const int bps_bytes = ip.bps_bytes;
     const int64_t raw_stride = ip.raw_stride, body_steps = ip.body_steps;
     const int ecc = m.inner;
-    if (!n_frames) return OFDM_OK;
-    c->trace.reset();
     const int N = c->prm.n_fft;
     void *w_raw = nullptr;
     const float2 *x = d.in;
@@ -1684,50 +1634,74 @@ static int rx_decode_inner(ofdm_ctx *c, const DecodeCall &d) {
 // kernels and the layer inside write there as they write to a caller's rows), then every outer layer's kernel inside-out over what
 // every frame delivered, in place on out_len / status
 struct CombineCall { int32_t n_branches; int32_t *branch_status, *weight; float *quality; };
-static int rx_decode_combine_inner(ofdm_ctx *c, const DecodeCall &d, const CombineCall &cc);
-// (combine: the inner chain of ofdm_rx_decode_combine_batch in place of rx_decode_inner)
-static int rx_decode(ofdm_ctx *c, const DecodeCall &d, const CombineCall *combine = nullptr) {
+static int rx_decode_combine_inner(ofdm_ctx *c, const DecodeCall &d, const CombineCall &cc, const InnerPlan &ip);
+// Everything that refuses a decode call, before anything is launched: the arguments, and per layer the longest row it can be given
+// (n_row[i]) against the stride of the rows it writes (stride[i]; stride[n_outer]: the inner chain's).  combine: the call is
+// ofdm_rx_decode_combine_batch's
+struct DecodePlan { InnerPlan ip; int64_t n_row[2], stride[3]; };
+static int rx_decode_plan(ofdm_ctx *c, const DecodeCall &d, const CombineCall *combine, DecodePlan &pl) {
     if (!c || d.n_frames < 0 || d.frame_len <= 0 || d.max_symbols <= 0) return OFDM_ERR_INVALID;
     if (d.n_frames && (!d.in || !d.out || !d.out_len || !d.status)) return OFDM_ERR_INVALID;
     const ModePlan &m = c->mode;
-    const int64_t raw_bytes = (int64_t)d.max_symbols * c->bytes_per_symbol();
-    int64_t n_row[2], row = inner_row_limit(m, raw_bytes > 16 ? raw_bytes - 16 : 0); // n_row[i]: the longest row layer i can be given
-    for (int i = m.n_outer - 1; i >= 0; i--) { n_row[i] = row; row = outer_row_limit(m.outer[i], row); }
-    DeviceGuard dev_guard(c->device);
-    struct { uint8_t *rows; int64_t stride; } to[3] = {{d.out, d.out_stride}}; // to[i]: where layer i writes; to[n_outer]: the inner chain
+    int64_t row = inner_row_limit(m, decode_body_bytes(c, d.max_symbols));
+    for (int i = m.n_outer - 1; i >= 0; i--) { pl.n_row[i] = row; row = outer_row_limit(m.outer[i], row); }
+    pl.stride[0] = d.out_stride;
+    for (int i = 0; i < m.n_outer; i++) {
+        if (pl.n_row[i] > kOuter[m.outer[i]].rx_max_row) return OFDM_ERR_UNSUPPORTED;
+        if (pl.stride[i] < outer_row_limit(m.outer[i], pl.n_row[i])) return OFDM_ERR_INVALID;
+        pl.stride[i + 1] = (std::max<int64_t>(pl.n_row[i], 4) + 3) & ~(int64_t)3;
+    }
+    if (m.n_outer && !d.n_frames) return OFDM_OK; // (an empty call of an outer-coded mode is not held to the inner chain's limits)
+    if (d.frame_stride <= 0 && (d.n_frames > 1 || (combine && combine->n_branches > 1))) return OFDM_ERR_INVALID;
+    DecodeCall inner = d;
+    inner.out_stride = pl.stride[m.n_outer];
+    int rc;
+    if ((rc = inner_plan(c, inner, pl.ip))) return rc;
+    // k_llr_combine's column indices are ints
+    if (combine && (int64_t)d.max_symbols * c->carriers() * c->prm.modulation > 0x7fffffffll - (1 << 13)) return OFDM_ERR_UNSUPPORTED;
+    return OFDM_OK;
+}
+static int rx_decode_run(ofdm_ctx *c, const DecodeCall &d, const DecodePlan &pl, const CombineCall *combine) {
+    const ModePlan &m = c->mode;
+    uint8_t *to[3] = {d.out}; // to[i]: where layer i writes; to[n_outer]: the inner chain
     int rc;
     for (int i = 0; i < m.n_outer; i++) {
-        const OuterStage &s = kOuter[m.outer[i]];
-        if (n_row[i] > s.rx_max_row) return OFDM_ERR_UNSUPPORTED;
-        if (to[i].stride < outer_row_limit(m.outer[i], n_row[i])) return OFDM_ERR_INVALID;
-        if (!d.n_frames) return OFDM_OK;
         void *w_rows;
-        to[i + 1].stride = (std::max<int64_t>(n_row[i], 4) + 3) & ~(int64_t)3;
-        if ((rc = ws_get(c, s.rx_rows, (size_t)to[i + 1].stride * (size_t)d.n_frames, &w_rows))) return rc;
-        to[i + 1].rows = (uint8_t *)w_rows;
+        if ((rc = ws_get(c, kOuter[m.outer[i]].rx_rows, (size_t)pl.stride[i + 1] * (size_t)d.n_frames, &w_rows))) return rc;
+        to[i + 1] = (uint8_t *)w_rows;
     }
     DecodeCall inner = d;
-    inner.out = to[m.n_outer].rows; inner.out_stride = to[m.n_outer].stride;
-    if ((rc = combine ? rx_decode_combine_inner(c, inner, *combine) : rx_decode_inner(c, inner))) return rc;
+    inner.out = to[m.n_outer]; inner.out_stride = pl.stride[m.n_outer];
+    if ((rc = combine ? rx_decode_combine_inner(c, inner, *combine, pl.ip) : rx_decode_inner(c, inner, pl.ip))) return rc;
     for (int i = m.n_outer - 1; i >= 0; i--) {
         const OuterStage &s = kOuter[m.outer[i]];
         c->trace.add(s.rx_name);
-        HIP_TRY(c, s.decode(c, LayerCall{to[i + 1].rows, d.n_frames, to[i + 1].stride, n_row[i], d.out_len, to[i].rows, to[i].stride, d.out_len, nullptr, d.status}));
+        HIP_TRY(c, s.decode(c, LayerCall{to[i + 1], d.n_frames, pl.stride[i + 1], pl.n_row[i], d.out_len, to[i], pl.stride[i], d.out_len, nullptr, d.status}));
     }
     return OFDM_OK;
+}
+// A decode entry point: the checks, then -- at the same place for every one of them -- the entry scope and the chain
+static int rx_decode_entry(ofdm_ctx *c, const DecodeCall &d, const CombineCall *combine = nullptr) {
+    DecodePlan pl;
+    const int rc = rx_decode_plan(c, d, combine, pl);
+    if (rc || !d.n_frames) return rc;
+    EntryScope scope(c);
+    return rx_decode_run(c, d, pl, combine);
+}
+int ofdm_abi_rx_decode(ofdm_ctx *c, const DecodeCall &d) {
+    DecodePlan pl;
+    const int rc = rx_decode_plan(c, d, nullptr, pl);
+    return rc || !d.n_frames ? rc : rx_decode_run(c, d, pl, nullptr);
 }
 
 int ofdm_rx_decode_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
                          int64_t n_lags, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
                          int32_t *status, int32_t *offset, double *f_delta, float *metric) {
-    const DecodeCall d{reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, n_lags, max_symbols, out, out_stride, out_len,
-                       status, offset, f_delta, metric, nullptr};
-    return rx_decode(c, d);
+    return rx_decode_entry(c, DecodeCall{reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, n_lags, max_symbols, out,
+                                         out_stride, out_len, status, offset, f_delta, metric, nullptr});
 }
 
 // ------------------------------------------------------------------ EXT-9: sc16 input
-static bool sc16_scale_ok(float scale) { return std::isfinite(scale) && scale > 0.f; }
-
 int ofdm_sc16_widen(const ofdm_sc16 *in, int64_t n, float scale, ofdm_fc32 *out) {
     if (n < 0 || !sc16_scale_ok(scale) || (n && (!in || !out))) return OFDM_ERR_INVALID;
     sc16_widen_host(&in->re, n, scale, &out->re);
@@ -1753,11 +1727,9 @@ int ofdm_sc16_widen_batch(ofdm_ctx *c, const ofdm_sc16 *in, int64_t n_frames, in
     bool work = false;
     const int rc = sc16_stage_check(c, in, n_frames, in_stride, frame_len, scale, out, out_stride, in, &work);
     if (rc || !work) return rc;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
-    Sc16Params p;
-    p.tune = &c->tune; p.trace = &c->trace; p.n_frames = n_frames; p.frame_len = frame_len; p.in_stride = in_stride; p.out_stride = out_stride;
-    p.scale = scale; p.sc_in = reinterpret_cast<const uint32_t *>(in); p.fc_out = reinterpret_cast<float2 *>(out);
+    EntryScope scope(c);
+    Sc16Params p = sc16_params(c, n_frames, frame_len, in_stride, out_stride, scale);
+    p.sc_in = reinterpret_cast<const uint32_t *>(in); p.fc_out = reinterpret_cast<float2 *>(out);
     HIP_TRY(c, run_sc16_widen(p, c->num_cu, c->stream));
     return OFDM_OK;
 }
@@ -1767,11 +1739,9 @@ int ofdm_sc16_narrow_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_frames, i
     const int rc = sc16_stage_check(c, in, n_frames, in_stride, frame_len, scale, out, out_stride, out, &work);
     if (rc || !n_frames) return rc;
     if (!work && !clipped) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
-    Sc16Params p;
-    p.tune = &c->tune; p.trace = &c->trace; p.n_frames = n_frames; p.frame_len = frame_len; p.in_stride = in_stride; p.out_stride = out_stride;
-    p.scale = scale; p.fc_in = reinterpret_cast<const float2 *>(in); p.sc_out = reinterpret_cast<uint32_t *>(out); p.clipped = clipped;
+    EntryScope scope(c);
+    Sc16Params p = sc16_params(c, n_frames, frame_len, in_stride, out_stride, scale);
+    p.fc_in = reinterpret_cast<const float2 *>(in); p.sc_out = reinterpret_cast<uint32_t *>(out); p.clipped = clipped;
     HIP_TRY(c, run_sc16_narrow(p, c->num_cu, c->stream));
     return OFDM_OK;
 }
@@ -1798,8 +1768,7 @@ static int sc16_chunks(ofdm_ctx *c, WsRole role, int64_t n_frames, int64_t frame
 }
 static int sc16_widen_chunk(ofdm_ctx *c, const ofdm_sc16 *in, int64_t f0, int64_t m, int64_t frame_stride, int64_t frame_len, float scale,
                             const Sc16Chunks &k) {
-    Sc16Params p;
-    p.tune = &c->tune; p.n_frames = m; p.frame_len = frame_len; p.in_stride = frame_stride; p.out_stride = k.ws_stride; p.scale = scale;
+    Sc16Params p = sc16_params(c, m, frame_len, frame_stride, k.ws_stride, scale);
     p.sc_in = reinterpret_cast<const uint32_t *>(in + f0 * frame_stride); p.fc_out = k.ws;
     HIP_TRY(c, run_sc16_widen(p, c->num_cu, c->stream));
     return OFDM_OK;
@@ -1813,8 +1782,7 @@ int ofdm_rx_demod_sc16_batch(ofdm_ctx *c, const ofdm_sc16 *in, int64_t n_frames,
     if (out_stride < (int64_t)syms_per_frame * c->bytes_per_symbol()) return OFDM_ERR_INVALID;
     if (hk && hk_stride != 0 && hk_stride != c->prm.n_fft) return OFDM_ERR_INVALID;
     if (!n_frames || !syms_per_frame) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     if (c->prm.n_fft == 64) { // the fused kernel reads the int16 pairs itself
         SymParams p = rx_params(c, nullptr, n_frames, frame_stride, frame_len, offset, f_delta, nullptr, out, out_stride);
         p.first_symbol = first_symbol; p.syms_per_frame = syms_per_frame; p.in_sym_stride = c->S(); p.in_skip = c->prm.cp_len;
@@ -1825,19 +1793,16 @@ int ofdm_rx_demod_sc16_batch(ofdm_ctx *c, const ofdm_sc16 *in, int64_t n_frames,
     Sc16Chunks k;
     int rc;
     if ((rc = sc16_chunks(c, kWsSc16, n_frames, frame_stride, frame_len, k))) return rc;
-    c->trace.add("k_sc16_widen");
-    Trace first;
     for (int64_t f0 = 0; f0 < n_frames; f0 += k.chunk) {
         const int64_t m = std::min(k.chunk, n_frames - f0);
+        const Trace::Mute later(c->trace, f0 > 0); // the dispatch string names what a chunk ran, once
         if ((rc = sc16_widen_chunk(c, in, f0, m, frame_stride, frame_len, scale, k))) return rc;
         rc = demod_run(c, k.ws, m, k.ws_stride, frame_len, first_symbol, syms_per_frame, offset ? offset + f0 : nullptr,
                        f_delta ? f_delta + f0 : nullptr, nullptr, hk ? reinterpret_cast<const float2 *>(hk) + f0 * hk_stride : nullptr, hk_stride,
                        out + f0 * out_stride, out_stride,
                        soft ? reinterpret_cast<float2 *>(soft) + f0 * (int64_t)syms_per_frame * c->carriers() : nullptr);
         if (rc) return rc;
-        if (!f0) first = c->trace; // the dispatch string names what a chunk ran, once
     }
-    c->trace = first;
     return OFDM_OK;
 }
 
@@ -1846,22 +1811,23 @@ int ofdm_rx_decode_sc16_batch(ofdm_ctx *c, const ofdm_sc16 *in, int64_t n_frames
                               int32_t *offset, double *f_delta, float *metric) {
     if (!c || n_frames < 0 || frame_len <= 0 || max_symbols <= 0 || !sc16_scale_ok(scale)) return OFDM_ERR_INVALID;
     if (n_frames && (!in || !out || !out_len || !status || (reinterpret_cast<uintptr_t>(in) & 3))) return OFDM_ERR_INVALID;
-    if (!n_frames) return rx_decode(c, DecodeCall{nullptr, 0, frame_stride, frame_len, n_lags, max_symbols, out, out_stride, out_len, status,
-                                                  offset, f_delta, metric, nullptr}); // the chain's own argument checks
-    DeviceGuard dev_guard(c->device);
+    // the chain's own argument checks, on the call as the widened rows present it (their stride is the workspace's: never refused)
+    const DecodeCall all{reinterpret_cast<const float2 *>(in), n_frames, 1, frame_len, n_lags, max_symbols, out, out_stride, out_len, status, offset,
+                         f_delta, metric, nullptr};
+    DecodePlan pl;
+    int rc = rx_decode_plan(c, all, nullptr, pl);
+    if (rc || !n_frames) return rc;
+    EntryScope scope(c);
     Sc16Chunks k;
-    int rc;
     if ((rc = sc16_chunks(c, kWsSc16, n_frames, frame_stride, frame_len, k))) return rc;
-    Trace first;
     for (int64_t f0 = 0; f0 < n_frames; f0 += k.chunk) {
         const int64_t m = std::min(k.chunk, n_frames - f0);
+        const Trace::Mute later(c->trace, f0 > 0); // the dispatch string names what a chunk ran, once
         if ((rc = sc16_widen_chunk(c, in, f0, m, frame_stride, frame_len, scale, k))) return rc;
         const DecodeCall d{k.ws, m, k.ws_stride, frame_len, n_lags, max_symbols, out + f0 * out_stride, out_stride, out_len + f0, status + f0,
                            offset ? offset + f0 : nullptr, f_delta ? f_delta + f0 : nullptr, metric ? metric + f0 : nullptr, nullptr};
-        if ((rc = rx_decode(c, d))) return rc;
-        if (!f0) { first.reset(); first.add("k_sc16_widen"); first.add(c->trace.buf); }
+        if ((rc = ofdm_abi_rx_decode(c, d))) return rc;
     }
-    c->trace = first;
     return OFDM_OK;
 }
 
@@ -1877,8 +1843,7 @@ int ofdm_tx_encode_sc16_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_fra
     int rc = tx_encode_check(c, payload, n_frames, payload_stride, payload_bytes, out, out_stride, &frame);
     if (rc || !n_frames) return rc;
     if (reinterpret_cast<uintptr_t>(out) & 3) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     // the launcher's own envelope (kernels_n64_tx_sc16.hip), asked before the rows are coded: they are coded once on either path
     if (c->prm.n_fft == 64 && !c->tune.no_txframe64_sc16 && !c->tune.no_txframe64 &&
         txframe64_sc16_takes((int)ofdm_data_symbols(c, payload_bytes), out, out_stride)) {
@@ -1893,13 +1858,13 @@ int ofdm_tx_encode_sc16_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_fra
     if ((rc = sc16_chunks(c, kWsTxSc16, n_frames, 0, frame, k))) return rc;
     for (int64_t f0 = 0; f0 < n_frames; f0 += k.chunk) {
         const int64_t m = std::min(k.chunk, n_frames - f0);
-        c->trace.reset(); // the dispatch string names what the last chunk ran
+        // Kept on purpose: this path names what its LAST chunk ran, where every other chunk loop names the first
+        const Trace::Mute earlier(c->trace, f0 + m < n_frames);
         rc = tx_encode_fc32(c, payload ? payload + f0 * payload_stride : nullptr, m, payload_stride, payload_len ? payload_len + f0 : nullptr,
                             payload_bytes, k.ws, k.ws_stride, frame);
         if (rc) return rc;
-        Sc16Params p;
-        p.tune = &c->tune; p.trace = &c->trace; p.n_frames = m; p.frame_len = frame; p.in_stride = k.ws_stride; p.out_stride = out_stride;
-        p.scale = scale; p.fc_in = k.ws; p.sc_out = reinterpret_cast<uint32_t *>(out + f0 * out_stride);
+        Sc16Params p = sc16_params(c, m, frame, k.ws_stride, out_stride, scale);
+        p.fc_in = k.ws; p.sc_out = reinterpret_cast<uint32_t *>(out + f0 * out_stride);
         p.clipped = clipped ? clipped + f0 : nullptr;
         HIP_TRY(c, run_sc16_narrow(p, c->num_cu, c->stream));
     }
@@ -1909,18 +1874,12 @@ int ofdm_tx_encode_sc16_batch(ofdm_ctx *c, const uint8_t *payload, int64_t n_fra
 // EXT-7: the inner chain over frames of R captures.  d: the call per FRAME (out, out_len, status), its offset / f_delta / metric per BRANCH
 // ROW.  Front end, link quality and LLRs per branch row, k_llr_combine, then the mode's finishing kernel on the combined rows.
 // The LLR workspace holds one chunk of frames: R branch rows and the combined row each.
-static int rx_decode_combine_inner(ofdm_ctx *c, const DecodeCall &d, const CombineCall &cc) {
+static int rx_decode_combine_inner(ofdm_ctx *c, const DecodeCall &d, const CombineCall &cc, const InnerPlan &ip) {
     const ModePlan &m = c->mode;
     const int R = cc.n_branches, N = c->prm.n_fft;
-    if (d.frame_stride <= 0 && (d.n_frames > 1 || R > 1)) return OFDM_ERR_INVALID;
-    InnerPlan ip;
     int rc;
-    if ((rc = inner_plan(c, d, ip))) return rc;
     const int llr_unit = c->carriers() * c->prm.modulation;
     const int64_t llr_row = (int64_t)d.max_symbols * llr_unit;
-    if (llr_row > 0x7fffffffll - (1 << 13)) return OFDM_ERR_UNSUPPORTED; // k_llr_combine's column indices are ints
-    if (!d.n_frames) return OFDM_OK;
-    c->trace.reset();
     const int64_t rows = d.n_frames * R;
     void *w_bst = nullptr, *w_q = nullptr, *w_ns, *w_llr;
     if (!cc.branch_status && (rc = ws_get(c, kWsBranchStatus, sizeof(int32_t) * (size_t)rows, &w_bst))) return rc;
@@ -1941,9 +1900,7 @@ static int rx_decode_combine_inner(ofdm_ctx *c, const DecodeCall &d, const Combi
     if ((rc = rx_noise_weights(c, b.in, rows, b.frame_stride, b.frame_len, fe.offs, fe.fd, bst, &q))) return rc;
     // 3 - 5. per chunk of frames: LLRs of the branch rows, the combined rows behind them, the finishing kernel
     const int64_t llr_stride = (llr_row + 15) & ~(int64_t)15;
-    int64_t chunk = c->tune.soft_chunk_frames > 0 ? c->tune.soft_chunk_frames : kSoftLlrBytes / llr_stride;
-    if (chunk < 1) chunk = 1;
-    if (chunk > d.n_frames) chunk = d.n_frames;
+    const int64_t chunk = soft_chunk_frames(c, llr_stride, d.n_frames);
     if ((rc = ws_get(c, kWsLlr, (size_t)(llr_stride * chunk) * (size_t)(R + 1), &w_llr))) return rc;
     int8_t *const branch_llr = (int8_t *)w_llr, *const combined = branch_llr + llr_stride * chunk * R;
     ViterbiParams vp;
@@ -1955,17 +1912,18 @@ static int rx_decode_combine_inner(ofdm_ctx *c, const DecodeCall &d, const Combi
     }
     for (int64_t f0 = 0; f0 < d.n_frames; f0 += chunk) {
         const int64_t nf = d.n_frames - f0 < chunk ? d.n_frames - f0 : chunk, r0 = f0 * R;
+        const Trace::Mute later(c->trace, f0 > 0); // the dispatch string names what a chunk ran, once
         rc = llr_run(c, b.in + r0 * b.frame_stride, nf * R, b.frame_stride, b.frame_len, 10, d.max_symbols, fe.offs + r0, fe.fd + r0, fe.nsym + r0,
-                     hk + r0 * N, N, OFDM_SOFT_LLR_SCALE, branch_llr, llr_stride, nullptr, 0, f0 == 0, q ? q + r0 * N : nullptr, N);
+                     hk + r0 * N, N, OFDM_SOFT_LLR_SCALE, branch_llr, llr_stride, nullptr, 0, q ? q + r0 * N : nullptr, N);
         if (rc) return rc;
         CombineParams p;
-        p.tune = &c->tune; p.trace = f0 == 0 ? &c->trace : nullptr;
+        p.tune = &c->tune; p.trace = &c->trace;
         p.llr = branch_llr; p.n_frames = nf; p.llr_stride = llr_stride; p.n_branches = R; p.n_llr = (int)llr_row;
         p.quality = quality + r0 * kQualityFields; p.status = bst + r0; p.n_live = fe.nsym + r0; p.live_unit = llr_unit;
         p.out = combined; p.out_stride = llr_stride; p.weight = cc.weight ? cc.weight + r0 : nullptr;
         p.status_out = d.status + f0; p.nsym_out = (int32_t *)w_ns + f0;
         HIP_TRY(c, run_llr_combine(p, c->num_cu, c->stream));
-        if (f0 == 0) c->trace.add(soft_finish_name(m));
+        c->trace.add(soft_finish_name(m));
         // (the framed Viterbi kernel takes chain mode from its status array; no mode supported here reads hard bytes: raw = nullptr)
         if ((rc = soft_finish_chunk(c, d, f0, nf, combined, llr_stride, (const int32_t *)w_ns + f0, nullptr, 0, vp, v_blocks))) return rc;
     }
@@ -1981,15 +1939,7 @@ int ofdm_rx_decode_combine_batch(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_fra
     const DecodeCall d{reinterpret_cast<const float2 *>(in), n_frames, frame_stride, frame_len, n_lags, max_symbols, out, out_stride, out_len,
                        status, offset, f_delta, metric, nullptr};
     const CombineCall cc{n_branches, branch_status, weight, quality};
-    return rx_decode(c, d, &cc);
-}
-int ofdm_abi_rx_decode_known(ofdm_ctx *c, const ofdm_fc32 *in, int64_t frame_len, int32_t d_hat, double f_delta, float metric,
-                             int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len, int32_t *status, int32_t *offset,
-                             double *f_delta_out, float *metric_out) {
-    const KnownSync k{d_hat, f_delta, metric};
-    const DecodeCall d{reinterpret_cast<const float2 *>(in), 1, frame_len, frame_len, 0, max_symbols, out, out_stride, out_len, status, offset,
-                       f_delta_out, metric_out, &k};
-    return rx_decode(c, d);
+    return rx_decode_entry(c, d, &cc);
 }
 
 // ---- EXT-13: every packet of one long capture in one batched decode (include/ofdm_hip.h; tests/packets_ref.py)
@@ -2007,45 +1957,37 @@ int ofdm_abi_rx_decode_packets(ofdm_ctx *c, const float2 *in, int64_t n, int64_t
     const size_t nd = (size_t)n_det;
     void *w_det, *w_geom, *w_rows, *w_fd = nullptr, *w_off;
     int rc;
-    if ((rc = ws_get(c, kWsPktDet, nd * 20 + 16, &w_det))) return rc;
-    if ((rc = ws_get(c, kWsPktGeom, nd * 16 + 16, &w_geom))) return rc;
+    if ((rc = ws_get(c, kWsPktDet, PktDetections(nullptr, nd).bytes + 16, &w_det))) return rc;
+    if ((rc = ws_get(c, kWsPktGeom, PktGeometry(nullptr, nd).bytes + 16, &w_geom))) return rc;
     if ((rc = ws_get(c, kWsPktRows, (size_t)chunk * (size_t)R * sizeof(float2) + 256, &w_rows))) return rc;
     if (!f_delta_out && (rc = ws_get(c, kWsPktFdelta, nd * sizeof(double), &w_fd))) return rc;
     if ((rc = ws_get(c, kWsPktOffset, nd * sizeof(int32_t), &w_off))) return rc;
     PktParams p;
     p.tune = &c->tune; p.trace = &c->trace;
     p.in = in; p.n = n; p.n_det = n_det; p.R = R; p.L = S; p.backoff = c->prm.sync_backoff;
-    long long *up_d = static_cast<long long *>(w_det);          // d_hat i64 | f_delta f64 | metric f32
-    double *up_fd = reinterpret_cast<double *>(up_d + nd);
-    float *up_m = reinterpret_cast<float *>(up_fd + nd);
-    p.d_hat = up_d; p.f_delta_in = up_fd; p.metric_in = up_m;
-    p.row_start = static_cast<long long *>(w_geom);             // row_start i64 | row_dhat i32 | row_len i32
-    p.row_dhat = reinterpret_cast<int32_t *>(p.row_start + nd);
-    p.row_len = p.row_dhat + nd;
+    const PktDetections up(w_det, nd);
+    const PktGeometry geom(w_geom, nd);
+    p.d_hat = up.d_hat; p.f_delta_in = up.f_delta; p.metric_in = up.metric;
+    p.row_start = geom.row_start; p.row_dhat = geom.row_dhat; p.row_len = geom.row_len;
     p.f_delta = f_delta_out ? f_delta_out : static_cast<double *>(w_fd);
     p.metric = metric_out;
     p.rows = static_cast<float2 *>(w_rows);
-    HIP_TRY(c, hipMemcpyAsync(up_d, d_hat, nd * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(up_fd, f_delta, nd * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(up_m, metric, nd * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(up.d_hat, d_hat, nd * sizeof(*d_hat), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(up.f_delta, f_delta, nd * sizeof(*f_delta), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(up.metric, metric, nd * sizeof(*metric), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, run_pkt_rows(p, c->stream));
     int32_t *row_off = static_cast<int32_t *>(w_off);
-    Trace head = c->trace, first; // (the chain's entry resets the context's trace: the names are put together at the end)
-    first.reset();
     for (int64_t k0 = 0; k0 < n_det; k0 += chunk) {
         const int64_t m = std::min(chunk, n_det - k0);
+        const Trace::Mute later(c->trace, k0 > 0); // the dispatch string names what a chunk ran, once
         p.row0 = k0; p.n_rows = m;
-        p.trace = k0 == 0 ? &head : nullptr;
         HIP_TRY(c, run_gather_rows(p, c->num_cu, c->stream));
         if (c->tune.packets_gather_only) continue; // laboratory key: the gather's time on its own, nothing is delivered
         const KnownSync k{0, 0.0, 0.f, p.row_dhat + k0, p.row_len + k0};
         const DecodeCall d{p.rows, m, R, R, 0, max_symbols, out + k0 * out_stride, out_stride, out_len + k0, status + k0, row_off + k0,
                            p.f_delta + k0, nullptr, &k};
-        if ((rc = rx_decode(c, d))) return rc;
-        if (k0 == 0) first = c->trace;
+        if ((rc = ofdm_abi_rx_decode(c, d))) return rc;
     }
-    c->trace = head;
-    if (first.len) c->trace.add(first.buf);
     if (offset && !c->tune.packets_gather_only) {
         c->trace.add("k_pkt_finish");
         HIP_TRY(c, run_pkt_finish(n_det, p.row_start, row_off, status, reinterpret_cast<long long *>(offset), c->stream));
@@ -2062,12 +2004,10 @@ int ofdm_rx_decode_packets(ofdm_ctx *c, const ofdm_fc32 *in_dev, int64_t n_sampl
     for (int64_t k = 0; k < n_det; k++)
         if (d_hat[k] < 0 || d_hat[k] >= n_samples) return OFDM_ERR_INVALID;
     if (reinterpret_cast<uintptr_t>(in_dev) & 7) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     if (!n_det) return OFDM_OK;
     // (the row-size rule of ofdm_rx_decode_batch is checked by the chain before its first launch, but behind the upload: check it here)
-    const int64_t raw_bytes = (int64_t)max_symbols * c->bytes_per_symbol();
-    if (out_stride < row_bytes(c->mode, raw_bytes > 16 ? raw_bytes - 16 : 0)) return OFDM_ERR_INVALID;
+    if (out_stride < decode_row_bytes(c, max_symbols)) return OFDM_ERR_INVALID;
     return ofdm_abi_rx_decode_packets(c, reinterpret_cast<const float2 *>(in_dev), n_samples, n_det, d_hat, f_delta, metric, max_symbols, out_dev,
                                       out_stride, out_len_dev, status_dev, offset_dev, f_delta_dev, metric_dev);
 }
@@ -2091,8 +2031,7 @@ int ofdm_channel_batch(ofdm_ctx *c, const ofdm_fc32 *tx, int64_t n_frames, int64
     if (n_frames > 1 && tx_stride <= 0) return OFDM_ERR_INVALID;
     if (!(snr_db == snr_db)) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     ChannelParams p;
     p.tx = reinterpret_cast<const float2 *>(tx); p.n_frames = n_frames; p.tx_stride = tx_stride; p.tx_len = tx_len;
     p.snr_lin = std::pow(10.0, snr_db / 10.0); // channel.rs:40
@@ -2106,8 +2045,7 @@ int ofdm_channel_batch(ofdm_ctx *c, const ofdm_fc32 *tx, int64_t n_frames, int64
 
 int ofdm_hbm_read_probe(ofdm_ctx *c, const ofdm_fc32 *in, int64_t n_symbols, int32_t pattern) {
     if (!c || n_symbols < 0 || pattern < 0 || pattern > 2 || (n_symbols && !in)) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     void *sink;
     int rc = ws_get(c, kWsProbeSink, 64, &sink);
     if (rc) return rc;

@@ -4,6 +4,7 @@
 #include "../../include/ofdm_hip.h"
 #include "kernels.hpp"
 
+#include <cmath>
 #include <cstddef>
 #include <vector>
 
@@ -142,6 +143,12 @@ struct DeviceGuard {
     DeviceGuard(const DeviceGuard &) = delete;
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
+// The scope of an entry point that launches kernels: the context's device, and an empty dispatch trace.  The one place the trace is
+// reset: everything below an entry point appends to it in launch order (Trace, kernels.hpp).
+struct EntryScope {
+    DeviceGuard dev;
+    explicit EntryScope(ofdm_ctx *c) : dev(c->device) { c->trace.reset(); }
+};
 
 #define HIP_TRY(ctx, expr)                                   \
     do {                                                     \
@@ -162,19 +169,116 @@ inline int ws_get(ofdm_ctx *c, WsRole role, size_t bytes, void **out) {
     return OFDM_OK;
 }
 
+// ---- rules both translation units spell the same way
+inline bool sc16_scale_ok(float scale) { return std::isfinite(scale) && scale > 0.f; }
+// The bytes behind the 16-byte length header of max_symbols demodulated symbols, and the row size every decode entry point asks of its
+// caller for them (include/ofdm_hip.h)
+inline int64_t decode_body_bytes(const ofdm_ctx *c, int32_t max_symbols) {
+    const int64_t raw = (int64_t)max_symbols * c->bytes_per_symbol();
+    return raw > 16 ? raw - 16 : 0;
+}
+inline int64_t decode_row_bytes(const ofdm_ctx *c, int32_t max_symbols) { return row_bytes(c->mode, decode_body_bytes(c, max_symbols)); }
+// k_sc16_widen / k_sc16_narrow over n_frames rows of frame_len samples; the caller adds the two pointers of its direction
+inline ofdm::Sc16Params sc16_params(ofdm_ctx *c, int64_t n_frames, int64_t frame_len, int64_t in_stride, int64_t out_stride, float scale) {
+    ofdm::Sc16Params p;
+    p.tune = &c->tune; p.trace = &c->trace;
+    p.n_frames = n_frames; p.frame_len = frame_len; p.in_stride = in_stride; p.out_stride = out_stride; p.scale = scale;
+    return p;
+}
+
+// ---- packed records: the blocks that travel between device, pinned memory and caller as ONE allocation or copy.  A layout is a struct
+// whose constructor takes its columns from a Carver in order; built on no memory (base = nullptr) the same walk gives the size alone.
+struct Carver {
+    char *base;
+    size_t at = 0; // bytes taken so far
+    explicit Carver(const void *b) : base(static_cast<char *>(const_cast<void *>(b))) {}
+    // the next column: n entries of T, on T's alignment (or the larger `align`, a power of two)
+    template <class T> T *col(size_t n, size_t align = alignof(T)) {
+        at = (at + align - 1) & ~(align - 1);
+        T *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
+        at += n * sizeof(T);
+        return p;
+    }
+};
+// what a decode call leaves per frame: the pipe's device and bounce slots (ofdm_rx_decode_host), the one frame of ofdm_rx_decode_long
+struct DecodeBlock {
+    double *f_delta; int32_t *len, *status, *offset; float *metric; uint8_t *rows; size_t bytes;
+    DecodeBlock(const void *base, size_t n, size_t row_bytes) {
+        Carver k(base);
+        f_delta = k.col<double>(n); len = k.col<int32_t>(n); status = k.col<int32_t>(n); offset = k.col<int32_t>(n); metric = k.col<float>(n);
+        rows = k.col<uint8_t>(n * row_bytes);
+        bytes = k.at;
+    }
+};
+// ... per packet (ofdm_rx_decode_all_long_host): the offsets are 64-bit, the rows start on 16 bytes
+struct PacketsBlock {
+    int64_t *offset; double *f_delta; int32_t *len, *status; float *metric; uint8_t *rows; size_t bytes;
+    PacketsBlock(const void *base, size_t n, size_t row_bytes) {
+        Carver k(base);
+        offset = k.col<int64_t>(n); f_delta = k.col<double>(n); len = k.col<int32_t>(n); status = k.col<int32_t>(n); metric = k.col<float>(n);
+        rows = k.col<uint8_t>(n * row_bytes, 16);
+        bytes = k.at;
+    }
+};
+// ofdm_sc_scan_long's result (kWsScanRows and its pinned copy): the head {n_det, more}, then `cap` entries a column
+struct ScanRows {
+    long long *head, *d1, *d_hat; double *f_delta; float *metric; size_t bytes;
+    ScanRows(const void *base, size_t cap) {
+        Carver k(base);
+        head = k.col<long long>(2); d1 = k.col<long long>(cap); d_hat = k.col<long long>(cap); f_delta = k.col<double>(cap); metric = k.col<float>(cap);
+        bytes = k.at;
+    }
+};
+// ofdm_rx_decode_packets: the uploaded detections (kWsPktDet) and what k_pkt_rows makes of them (kWsPktGeom)
+struct PktDetections {
+    long long *d_hat; double *f_delta; float *metric; size_t bytes;
+    PktDetections(const void *base, size_t n) {
+        Carver k(base);
+        d_hat = k.col<long long>(n); f_delta = k.col<double>(n); metric = k.col<float>(n);
+        bytes = k.at;
+    }
+};
+struct PktGeometry {
+    long long *row_start; int32_t *row_dhat, *row_len; size_t bytes;
+    PktGeometry(const void *base, size_t n) {
+        Carver k(base);
+        row_start = k.col<long long>(n); row_dhat = k.col<int32_t>(n); row_len = k.col<int32_t>(n);
+        bytes = k.at;
+    }
+};
+// the long search's per-slice detector outputs (HostPipe::d_scal)
+struct SliceRows {
+    double *f_delta; int32_t *d_hat; float *metric; size_t bytes;
+    SliceRows(const void *base, size_t n) {
+        Carver k(base);
+        f_delta = k.col<double>(n); d_hat = k.col<int32_t>(n); metric = k.col<float>(n);
+        bytes = k.at;
+    }
+};
+
+// ---- a decode call, as the chain takes it (ofdm_abi.hip)
+// Timing the caller brings.  One capture: d_hat / f_delta / metric by value (ofdm_rx_decode_long with lag_lo > 0).  Rows (EXT-13,
+// row_dhat != NULL): device arrays of the row-relative peaks and of the rows' own lengths; the call's f_delta and offset arrays are not
+// optional, f_delta (and metric, if wanted) already hold the rows' values
+struct KnownSync { int32_t d_hat; double f_delta; float metric; const int32_t *row_dhat = nullptr, *row_len = nullptr; };
+// The arguments of a decode call: ofdm_rx_decode_batch's own, or captures with their timing
+struct DecodeCall {
+    const float2 *in; int64_t n_frames, frame_stride, frame_len, n_lags; int32_t max_symbols;
+    uint8_t *out; int64_t out_stride;                          // rows of out_stride bytes
+    int32_t *out_len, *status, *offset; double *f_delta; float *metric; // per frame (offset, f_delta, metric: optional)
+    const KnownSync *known;
+};
+
 // internal cross-file helpers (C linkage only because their definitions sit inside the extern "C" blocks; not in ofdm_hip.h)
 extern "C" {
 __attribute__((visibility("hidden"))) void ofdm_host_pipe_destroy(ofdm_ctx *c); // ofdm_host_path.hip; the context's device is current
 // Schmidl-Cox over a batch (the dispatcher behind ofdm_sc_correlate_batch and step 1 of ofdm_rx_decode_batch; ofdm_abi.hip)
 __attribute__((visibility("hidden"))) int ofdm_abi_sc_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len, int64_t n_lags,
                     int32_t *d_hat, double *f_delta, float *metric);
-// ofdm_rx_decode_batch for ONE capture whose timing is already known (peak lag d_hat, arg P / L and metric at it): steps 2-5 of the
-// chain without its own search (ofdm_rx_decode_long with lag_lo > 0: the search must not look at lags in front of lag_lo)
-__attribute__((visibility("hidden"))) int ofdm_abi_rx_decode_known(ofdm_ctx *c, const ofdm_fc32 *in, int64_t frame_len, int32_t d_hat, double f_delta, float metric,
-                    int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len, int32_t *status, int32_t *offset, double *f_delta_out,
-                    float *metric_out);
-// EXT-13 (ofdm_rx_decode_packets without the argument checks, the device guard and the trace reset: ofdm_rx_decode_all_long_host runs it
-// behind its scan)
+// ofdm_rx_decode_batch behind its entry scope: the argument checks and the chain of d, appended to the context's trace (the long
+// capture calls run it on a sub-capture, with the chain's own search or, d.known, with the slice search's timing)
+__attribute__((visibility("hidden"))) int ofdm_abi_rx_decode(ofdm_ctx *c, const DecodeCall &d);
+// EXT-13 (ofdm_rx_decode_packets behind its argument checks and its entry scope: ofdm_rx_decode_all_long_host runs it behind its scan)
 __attribute__((visibility("hidden"))) int ofdm_abi_rx_decode_packets(ofdm_ctx *c, const float2 *in, int64_t n, int64_t n_det, const int64_t *d_hat,
                     const double *f_delta, const float *metric, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
                     int32_t *status, int64_t *offset, double *f_delta_out, float *metric_out);

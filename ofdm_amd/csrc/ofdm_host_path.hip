@@ -205,32 +205,29 @@ struct DecodeJob : PipeJob {
         const int64_t last = f0(k) + m(k) == n_frames; // only the batch's last frame may end before its stride does
         return (size_t)((m(k) - (last ? 1 : 0)) * stride + (last ? frame_len : 0)) * ss;
     }
-    size_t out_bytes(int64_t k) const override { return (size_t)m(k) * (24 + ob); }
+    size_t out_bytes(int64_t k) const override { return DecodeBlock(nullptr, (size_t)m(k), ob).bytes; }
     const void *row(int64_t k) const { return static_cast<const char *>(in) + (size_t)(f0(k) * stride) * ss; }
     const void *in_direct(int64_t k) const override { return pinned_in ? row(k) : nullptr; }
     void fill_in(int64_t k, void *p) const override { std::memcpy(p, row(k), in_bytes(k)); }
+    // The pipe's jobs run the device ENTRY POINT per chunk (kept on purpose): a _host call's dispatch string is its last chunk's
     int launch(int64_t k, void *d_in, void *d_out) override {
-        const int64_t n = m(k);
-        char *o = static_cast<char *>(d_out); // [f_delta f64 | len | status | offset i32 | metric f32 | rows]
-        return ofdm_rx_decode_batch(c, static_cast<const ofdm_fc32 *>(d_in), n, stride, frame_len, n_lags, max_symbols,
-                                    reinterpret_cast<uint8_t *>(o + 24 * n), (int64_t)ob, reinterpret_cast<int32_t *>(o + 8 * n),
-                                    reinterpret_cast<int32_t *>(o + 12 * n), reinterpret_cast<int32_t *>(o + 16 * n),
-                                    reinterpret_cast<double *>(o), reinterpret_cast<float *>(o + 20 * n));
+        const DecodeBlock o(d_out, (size_t)m(k), ob);
+        return ofdm_rx_decode_batch(c, static_cast<const ofdm_fc32 *>(d_in), m(k), stride, frame_len, n_lags, max_symbols, o.rows, (int64_t)ob, o.len,
+                                    o.status, o.offset, o.f_delta, o.metric);
     }
     void drain_out(int64_t k, const void *p) const override {
-        const int64_t n = m(k), a = f0(k);
-        const char *o = static_cast<const char *>(p);
-        const int32_t *len = reinterpret_cast<const int32_t *>(o + 8 * n);
-        if (fd) std::memcpy(fd + a, o, 8 * (size_t)n);
-        std::memcpy(out_len + a, len, 4 * (size_t)n);
-        std::memcpy(status + a, o + 12 * n, 4 * (size_t)n);
-        if (offset) std::memcpy(offset + a, o + 16 * n, 4 * (size_t)n);
-        if (metric) std::memcpy(metric + a, o + 20 * n, 4 * (size_t)n);
-        const uint8_t *rows = reinterpret_cast<const uint8_t *>(o + 24 * n);
-        if ((size_t)out_stride == ob) std::memcpy(out + a * out_stride, rows, (size_t)n * ob);
+        const size_t n = (size_t)m(k);
+        const int64_t a = f0(k);
+        const DecodeBlock o(p, n, ob);
+        if (fd) std::memcpy(fd + a, o.f_delta, n * sizeof(*fd));
+        std::memcpy(out_len + a, o.len, n * sizeof(*out_len));
+        std::memcpy(status + a, o.status, n * sizeof(*status));
+        if (offset) std::memcpy(offset + a, o.offset, n * sizeof(*offset));
+        if (metric) std::memcpy(metric + a, o.metric, n * sizeof(*metric));
+        if ((size_t)out_stride == ob) std::memcpy(out + a * out_stride, o.rows, n * ob);
         else
-            for (int64_t f = 0; f < n; f++) // a row holds out_len[f] meaningful bytes
-                std::memcpy(out + (a + f) * out_stride, rows + (size_t)f * ob, (size_t)std::min<int64_t>(std::max(len[f], 0), out_stride));
+            for (size_t f = 0; f < n; f++) // a row holds out_len[f] meaningful bytes
+                std::memcpy(out + (a + (int64_t)f) * out_stride, o.rows + f * ob, (size_t)std::min<int64_t>(std::max(o.len[f], 0), out_stride));
     }
 };
 
@@ -238,12 +235,9 @@ struct DecodeJob : PipeJob {
 struct DecodeSc16Job : DecodeJob {
     float scale;
     int launch(int64_t k, void *d_in, void *d_out) override {
-        const int64_t n = m(k);
-        char *o = static_cast<char *>(d_out);
-        return ofdm_rx_decode_sc16_batch(c, static_cast<const ofdm_sc16 *>(d_in), n, stride, frame_len, scale, n_lags, max_symbols,
-                                         reinterpret_cast<uint8_t *>(o + 24 * n), (int64_t)ob, reinterpret_cast<int32_t *>(o + 8 * n),
-                                         reinterpret_cast<int32_t *>(o + 12 * n), reinterpret_cast<int32_t *>(o + 16 * n),
-                                         reinterpret_cast<double *>(o), reinterpret_cast<float *>(o + 20 * n));
+        const DecodeBlock o(d_out, (size_t)m(k), ob);
+        return ofdm_rx_decode_sc16_batch(c, static_cast<const ofdm_sc16 *>(d_in), m(k), stride, frame_len, scale, n_lags, max_symbols, o.rows,
+                                         (int64_t)ob, o.len, o.status, o.offset, o.f_delta, o.metric);
     }
 };
 
@@ -398,23 +392,22 @@ int sc_long_find(ofdm_ctx *c, HostPipe *hp, const float2 *in, int64_t n, const L
     h.ns = ns;
     if (ns > 0x7fffffff) return OFDM_ERR_INVALID;
     int rc;
-    if ((rc = dev_grow(c, hp, hp->d_scal, (size_t)ns * 16 + 64))) return rc;
-    if ((rc = pin_grow(c, hp, hp->h_scal, (size_t)ns * 4 + 64))) return rc;
-    double *s_fd = static_cast<double *>(hp->d_scal.p);                       // [ns] f64 | [ns] i32 | [ns] f32
-    int32_t *s_d = reinterpret_cast<int32_t *>(s_fd + ns);
-    float *s_m = reinterpret_cast<float *>(s_d + ns);
+    if ((rc = dev_grow(c, hp, hp->d_scal, SliceRows(nullptr, (size_t)ns).bytes + 64))) return rc;
+    if ((rc = pin_grow(c, hp, hp->h_scal, (size_t)ns * sizeof(int32_t) + 64))) return rc;
+    const SliceRows s(hp->d_scal.p, (size_t)ns);
     // n_lags = own clips the peak window, so only "d_hat >= 0" and the bracket above are used.  One launch over every lag: a long
     // capture is mostly noise, where the two-launch search of the batch path would read everything twice.
     const int first_lags = c->tune.sc_first_lags;
     c->tune.sc_first_lags = 0;
     rc = OFDM_OK;
-    if (g.n_full) rc = ofdm_abi_sc_run(c, in + g.lo, g.n_full, g.own, g.own + g.halo, g.own, s_d, s_fd, s_m);
+    if (g.n_full) rc = ofdm_abi_sc_run(c, in + g.lo, g.n_full, g.own, g.own + g.halo, g.own, s.d_hat, s.f_delta, s.metric);
     if (!rc && g.tail_len > 0)
-        rc = ofdm_abi_sc_run(c, in + g.tail_lo, 1, g.tail_len, g.tail_len, g.hi - g.tail_lo, s_d + g.n_full, s_fd + g.n_full, s_m + g.n_full);
+        rc = ofdm_abi_sc_run(c, in + g.tail_lo, 1, g.tail_len, g.tail_len, g.hi - g.tail_lo, s.d_hat + g.n_full, s.f_delta + g.n_full,
+                             s.metric + g.n_full);
     c->tune.sc_first_lags = first_lags;
     if (rc) return rc;
     int32_t *h_d = static_cast<int32_t *>(hp->h_scal.p);
-    HIP_TRY(c, hipMemcpyAsync(h_d, s_d, 4 * (size_t)ns, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_d, s.d_hat, (size_t)ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int64_t i = 0; i < ns; i++)
         if (h_d[i] >= 0) { h.hit = i; break; }
@@ -442,18 +435,16 @@ int sc_long(ofdm_ctx *c, const float2 *in, int64_t n, int64_t lag_lo, int64_t la
     LongHit hit;
     if ((rc = sc_long_find(c, hp, in, n, g, hit))) return rc;
     if (hit.hit < 0) return OFDM_OK;
-    double *s_fd = static_cast<double *>(hp->d_scal.p);
-    int32_t *s_d = reinterpret_cast<int32_t *>(s_fd + hit.ns);
-    float *s_m = reinterpret_cast<float *>(s_d + hit.ns);
+    const SliceRows s(hp->d_scal.p, (size_t)hit.ns);
     // pass 2: that slice again with its whole peak window (a slice that ends with the capture's last lag had it in pass 1 already)
     struct { double fd; int32_t d; float m; } h;
     h.d = (int32_t)(hit.d_clip - hit.start);
     const bool again = hit.lags2 > hit.own;
     const int64_t at = again ? 0 : hit.hit;
-    if (again && (rc = ofdm_abi_sc_run(c, in + hit.start, 1, hit.flen, hit.flen, hit.lags2, s_d, s_fd, s_m))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(&h.fd, s_fd + at, 8, hipMemcpyDeviceToHost, c->stream));
-    if (again) HIP_TRY(c, hipMemcpyAsync(&h.d, s_d, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(&h.m, s_m + at, 4, hipMemcpyDeviceToHost, c->stream));
+    if (again && (rc = ofdm_abi_sc_run(c, in + hit.start, 1, hit.flen, hit.flen, hit.lags2, s.d_hat, s.f_delta, s.metric))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(&h.fd, s.f_delta + at, sizeof(h.fd), hipMemcpyDeviceToHost, c->stream));
+    if (again) HIP_TRY(c, hipMemcpyAsync(&h.d, s.d_hat, sizeof(h.d), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&h.m, s.metric + at, sizeof(h.m), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (h.d < 0) return OFDM_OK; // cannot happen (pass 1 saw a crossing among these lags); keep "no detection" rather than a wrong lag
     *d_hat = hit.start + h.d;
@@ -485,34 +476,29 @@ int sc_scan_dev(ofdm_ctx *c, const float2 *in, int64_t n, int64_t lag_lo, int64_
     int rc = pipe_get(c, &hp);
     if (rc) return rc;
     void *bits, *rows;
-    const size_t cap = (size_t)p.det_cap, rows_bytes = 16 + cap * 28;
+    const size_t cap = (size_t)p.det_cap, rows_bytes = ScanRows(nullptr, cap).bytes;
     if ((rc = ws_get(c, kWsScanBits, (size_t)((p.n_lags + 63) >> 6) * 8, &bits))) return rc;
     if ((rc = ws_get(c, kWsScanRows, rows_bytes, &rows))) return rc;
     if ((rc = pin_grow(c, hp, hp->h_scal, rows_bytes))) return rc;
     p.bits = static_cast<unsigned long long *>(bits);
-    p.head = static_cast<long long *>(rows);
-    p.d1 = p.head + 2;
-    p.d_hat = p.d1 + cap;
-    p.f_delta = reinterpret_cast<double *>(p.d_hat + cap);
-    p.metric = reinterpret_cast<float *>(p.f_delta + cap);
+    const ScanRows dev(rows, cap);
+    p.head = dev.head; p.d1 = dev.d1; p.d_hat = dev.d_hat; p.f_delta = dev.f_delta; p.metric = dev.metric;
     if (c->tune.scan_mark_only) { // laboratory key: the kernel's time on its own, nothing is reported
         HIP_TRY(c, run_sc_mark(p, c->num_cu, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return OFDM_OK;
     }
     HIP_TRY(c, run_sc_scan(p, c->num_cu, c->stream));
-    const char *h = static_cast<const char *>(hp->h_scal.p);
+    const ScanRows h(hp->h_scal.p, cap);
     HIP_TRY(c, hipMemcpyAsync(hp->h_scal.p, rows, rows_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    int64_t head[2];
-    std::memcpy(head, h, 16);
-    const size_t nd = (size_t)std::min<int64_t>(std::max<int64_t>(head[0], 0), p.det_cap);
+    const size_t nd = (size_t)std::min<int64_t>(std::max<int64_t>(h.head[0], 0), p.det_cap);
     *n_det = (int64_t)nd;
-    if (more) *more = head[1] != 0;
-    if (d1) std::memcpy(d1, h + 16, 8 * nd);
-    std::memcpy(d_hat, h + 16 + 8 * cap, 8 * nd);
-    if (f_delta) std::memcpy(f_delta, h + 16 + 16 * cap, 8 * nd);
-    if (metric) std::memcpy(metric, h + 16 + 24 * cap, 4 * nd);
+    if (more) *more = h.head[1] != 0;
+    if (d1) std::memcpy(d1, h.d1, nd * sizeof(*d1));
+    std::memcpy(d_hat, h.d_hat, nd * sizeof(*d_hat));
+    if (f_delta) std::memcpy(f_delta, h.f_delta, nd * sizeof(*f_delta));
+    if (metric) std::memcpy(metric, h.metric, nd * sizeof(*metric));
     return OFDM_OK;
 }
 
@@ -533,6 +519,7 @@ int decode_long_dev(ofdm_ctx *c, const float2 *in, int64_t n, int64_t lag_lo, in
     const bool whole = lag_lo == 0 && (lag_hi <= 0 || lag_hi >= n - (int64_t)(c->prm.sync_window_reps + 1) * c->S() + 1);
     const bool one_frame = whole && d_known < 0 && (!long_geometry(c, n, 0, 0, 0, g) || g.n_full == 0);
     if (c->prm.sync_mode == OFDM_SYNC_SCHMIDL_COX && !one_frame) { // (a capture no longer than one slice is one frame of the batch path)
+        const Trace::Mute search(c->trace); // the dispatch string is the chain's: the slice search in front of it is left out
         // Decode from a SUB-CAPTURE that starts at or before both the first crossing d1 and the trimmed frame start
         // (peak - L - backoff): its own search finds the same crossing, window, peak and offset as the whole capture's, and every
         // length the chain derives from "samples after the trimmed start" is unchanged.  A known peak d gives d1 >= d - W; pass 1 of
@@ -564,23 +551,19 @@ int decode_long_dev(ofdm_ctx *c, const float2 *in, int64_t n, int64_t lag_lo, in
         return OFDM_ERR_UNSUPPORTED; // the reference's detector is an argmax over the whole capture (src/receiver.rs:20-25)
     }
     if ((rc = dev_grow(c, hp, hp->d_scal, 64))) return rc;
-    char *sc = static_cast<char *>(hp->d_scal.p); // f_delta f64 | len | status | offset i32 | metric f32
-    if (have_sync)
-        rc = ofdm_abi_rx_decode_known(c, reinterpret_cast<const ofdm_fc32 *>(in + start), n - start, (int32_t)(k_d - start), k_fd, k_m, max_symbols,
-                                      out_dev, out_cap, reinterpret_cast<int32_t *>(sc + 8), reinterpret_cast<int32_t *>(sc + 12),
-                                      reinterpret_cast<int32_t *>(sc + 16), reinterpret_cast<double *>(sc), reinterpret_cast<float *>(sc + 20));
-    else
-    rc = ofdm_rx_decode_batch(c, reinterpret_cast<const ofdm_fc32 *>(in + start), 1, n - start, n - start, sub_lags, max_symbols, out_dev,
-                              out_cap, reinterpret_cast<int32_t *>(sc + 8), reinterpret_cast<int32_t *>(sc + 12),
-                              reinterpret_cast<int32_t *>(sc + 16), reinterpret_cast<double *>(sc), reinterpret_cast<float *>(sc + 20));
-    if (rc) return rc;
-    struct { double fd; int32_t len, status, offset; float metric; } h;
-    HIP_TRY(c, hipMemcpyAsync(&h, sc, 24, hipMemcpyDeviceToHost, c->stream));
+    const DecodeBlock sc(hp->d_scal.p, 1, 0); // the one frame's scalars; its row is the caller's
+    const KnownSync known{(int32_t)(k_d - start), k_fd, k_m};
+    const DecodeCall d{in + start, 1, n - start, n - start, have_sync ? 0 : sub_lags, max_symbols, out_dev, out_cap, sc.len, sc.status, sc.offset,
+                       sc.f_delta, sc.metric, have_sync ? &known : nullptr};
+    if ((rc = ofdm_abi_rx_decode(c, d))) return rc;
+    alignas(8) char back[32];
+    const DecodeBlock h(back, 1, 0);
+    HIP_TRY(c, hipMemcpyAsync(back, hp->d_scal.p, sc.bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *out_len = h.len; *status = h.status;
-    if (offset) *offset = (h.status == OFDM_FRAME_BADTIMING ? 0 : start) + h.offset;
-    if (f_delta) *f_delta = h.fd;
-    if (metric) *metric = h.metric;
+    *out_len = *h.len; *status = *h.status;
+    if (offset) *offset = (*h.status == OFDM_FRAME_BADTIMING ? 0 : start) + *h.offset;
+    if (f_delta) *f_delta = *h.f_delta;
+    if (metric) *metric = *h.metric;
     return OFDM_OK;
 }
 
@@ -611,25 +594,45 @@ int long_upload(ofdm_ctx *c, HostPipe *hp, void *dst, const void *in_host, size_
 
 // EXT-10: ofdm_rx_decode_long on an sc16 capture that is on the device: k_sc16_widen into the context's workspace kWsLongSc16 (8 bytes a
 // sample beside the capture's 4; + 64: the frame kernels' branch-free prefetches may read a little past a row), then decode_long_dev
-// unchanged.  The dispatch string is k_sc16_widen+ + the fc32 call's: the entry points decode_long_dev runs reset the context's trace,
-// so the widen launch is not traced (p.trace stays null) and its name is put in front afterwards.
+// unchanged.  The dispatch string is k_sc16_widen+ + the fc32 call's.
 int decode_long_sc16_dev(ofdm_ctx *c, const ofdm_sc16 *in, int64_t n, float scale, int64_t lag_lo, int64_t lag_hi, int64_t d_known,
                          int32_t max_symbols, uint8_t *out_dev, int64_t out_cap, int32_t *out_len, int32_t *status, int64_t *offset,
                          double *f_delta, float *metric) {
     int rc;
     void *wide;
     if ((rc = ws_get(c, kWsLongSc16, (size_t)n * sizeof(ofdm_fc32) + 64, &wide))) return rc;
-    Sc16Params p;
-    p.tune = &c->tune; p.n_frames = 1; p.frame_len = n; p.in_stride = n; p.out_stride = n; p.scale = scale;
+    Sc16Params p = sc16_params(c, 1, n, n, n, scale);
     p.sc_in = reinterpret_cast<const uint32_t *>(in); p.fc_out = static_cast<float2 *>(wide);
     HIP_TRY(c, run_sc16_widen(p, c->num_cu, c->stream));
-    rc = decode_long_dev(c, static_cast<const float2 *>(wide), n, lag_lo, lag_hi, d_known, max_symbols, out_dev, out_cap, out_len, status, offset,
-                         f_delta, metric);
-    Trace t;
-    t.reset(); t.add("k_sc16_widen");
-    if (c->trace.len) t.add(c->trace.buf);
-    c->trace = t;
+    return decode_long_dev(c, static_cast<const float2 *>(wide), n, lag_lo, lag_hi, d_known, max_symbols, out_dev, out_cap, out_len, status, offset,
+                           f_delta, metric);
+}
+
+// The long-capture _host calls: the capture into `slot` on the device (and out_bytes of d_out[0], if the call delivers a row), then
+// body(hp, the device copy).  Once the upload has started, DMA reads the caller's buffer (and later writes its outputs): every failure
+// waits for all of it before the error goes back, as run_pipe does
+template <class Body>
+int with_long_upload(ofdm_ctx *c, Buf HostPipe::*slot, const void *in_host, size_t bytes, size_t out_bytes, Body body) {
+    HostPipe *hp;
+    int rc = pipe_get(c, &hp);
+    if (rc) return rc;
+    auto work = [&]() -> int {
+        if ((rc = dev_grow(c, hp, hp->*slot, bytes + 64))) return rc;
+        if (out_bytes && (rc = dev_grow(c, hp, hp->d_out[0], out_bytes + 64))) return rc;
+        if ((rc = long_upload(c, hp, (hp->*slot).p, in_host, bytes))) return rc;
+        return body(hp, (hp->*slot).p);
+    };
+    rc = work();
+    if (rc) sync_all(c, hp);
     return rc;
+}
+// ... and the one row of ofdm_rx_decode_long[_sc16]_host back from d_out[0]
+int long_row_back(ofdm_ctx *c, HostPipe *hp, uint8_t *out_host, const int32_t *out_len, const int32_t *status) {
+    if (*status == OFDM_FRAME_OK && *out_len > 0) {
+        HIP_TRY(c, hipMemcpyAsync(out_host, hp->d_out[0].p, (size_t)*out_len, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return OFDM_OK;
 }
 
 } // namespace
@@ -689,9 +692,7 @@ static int decode_host_run(ofdm_ctx *c, DecodeJob &j, const void *in_host, int64
     if (!c || n_frames < 0 || frame_len <= 0 || max_symbols <= 0 || frame_stride < 0) return OFDM_ERR_INVALID;
     if (n_frames && (!in_host || !out_host || !out_len_host || !status_host)) return OFDM_ERR_INVALID;
     if (n_frames > 1 && frame_stride < frame_len) return OFDM_ERR_INVALID; // rows of a host batch do not overlap
-    const int64_t raw = (int64_t)max_symbols * c->bytes_per_symbol();
-    const int64_t body = raw > 16 ? raw - 16 : 0;
-    const int64_t need = row_bytes(c->mode, body);
+    const int64_t need = decode_row_bytes(c, max_symbols);
     if (out_stride < need) return OFDM_ERR_INVALID;
     if (!n_frames) return OFDM_OK;
     DeviceGuard dev_guard(c->device);
@@ -714,7 +715,7 @@ int ofdm_rx_decode_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_frames,
 int ofdm_rx_decode_sc16_host(ofdm_ctx *c, const ofdm_sc16 *in_host, int64_t n_frames, int64_t frame_stride, int64_t frame_len, float scale,
                              int64_t n_lags, int32_t max_symbols, uint8_t *out_host, int64_t out_stride, int32_t *out_len_host,
                              int32_t *status_host, int32_t *offset_host, double *f_delta_host, float *metric_host, int64_t chunk_frames) {
-    if (!(std::isfinite(scale) && scale > 0.f)) return OFDM_ERR_INVALID;
+    if (!sc16_scale_ok(scale)) return OFDM_ERR_INVALID;
     DecodeSc16Job j;
     j.ss = sizeof(ofdm_sc16); j.scale = scale;
     return decode_host_run(c, j, in_host, n_frames, frame_stride, frame_len, n_lags, max_symbols, out_host, out_stride, out_len_host, status_host,
@@ -745,7 +746,7 @@ int ofdm_rx_demod_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_frames, 
 }
 int ofdm_rx_demod_sc16_host(ofdm_ctx *c, const ofdm_sc16 *in_host, int64_t n_frames, int64_t frame_stride, int64_t frame_len, float scale,
                             int32_t first_symbol, int32_t syms_per_frame, uint8_t *out_host, int64_t out_stride, int64_t chunk_frames) {
-    if (!(std::isfinite(scale) && scale > 0.f)) return OFDM_ERR_INVALID;
+    if (!sc16_scale_ok(scale)) return OFDM_ERR_INVALID;
     DemodSc16Job j;
     j.ss = sizeof(ofdm_sc16); j.scale = scale;
     return demod_host_run(c, j, in_host, n_frames, frame_stride, frame_len, first_symbol, syms_per_frame, out_host, out_stride, chunk_frames);
@@ -771,7 +772,7 @@ int ofdm_tx_encode_host(ofdm_ctx *c, const uint8_t *payload_host, int64_t n_fram
 int ofdm_tx_encode_sc16_host(ofdm_ctx *c, const uint8_t *payload_host, int64_t n_frames, int64_t payload_stride, const int32_t *payload_len_host,
                              int32_t payload_bytes, float scale, ofdm_sc16 *out_host, int64_t out_stride, int32_t *clipped_host,
                              int64_t chunk_frames) {
-    if (!c || n_frames < 0 || payload_bytes < 0 || payload_stride < 0 || !(std::isfinite(scale) && scale > 0.f)) return OFDM_ERR_INVALID;
+    if (!c || n_frames < 0 || payload_bytes < 0 || payload_stride < 0 || !sc16_scale_ok(scale)) return OFDM_ERR_INVALID;
     if (n_frames && (!out_host || (payload_bytes && !payload_host))) return OFDM_ERR_INVALID;
     const int64_t frame = ofdm_frame_samples(c, payload_bytes);
     if (out_stride < frame) return OFDM_ERR_INVALID;
@@ -799,8 +800,7 @@ int ofdm_tx_encode_sc16_host(ofdm_ctx *c, const uint8_t *payload_host, int64_t n
 int ofdm_sc_correlate_long(ofdm_ctx *c, const ofdm_fc32 *in_dev, int64_t n_samples, int64_t lag_lo, int64_t lag_hi, int64_t slice_lags,
                            int64_t *d_hat, double *f_delta, float *metric) {
     if (!c || !d_hat || n_samples < 0 || lag_lo < 0 || slice_lags < 0 || (n_samples && !in_dev)) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     return sc_long(c, reinterpret_cast<const float2 *>(in_dev), n_samples, lag_lo, lag_hi, slice_lags, d_hat, f_delta, metric);
 }
 
@@ -815,8 +815,7 @@ int ofdm_sc_scan_long(ofdm_ctx *c, const ofdm_fc32 *in_dev, int64_t n_samples, i
                       int64_t max_det, int64_t *d1, int64_t *d_hat, double *f_delta, float *metric, int64_t *n_det, int32_t *more) {
     const int rc = sc_scan_check(c, in_dev, n_samples, lag_lo, holdoff, max_det, d_hat, n_det);
     if (rc) return rc;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     return sc_scan_dev(c, reinterpret_cast<const float2 *>(in_dev), n_samples, lag_lo, lag_hi, holdoff, max_det, d1, d_hat, f_delta, metric,
                        n_det, more);
 }
@@ -827,20 +826,10 @@ int ofdm_sc_scan_long_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_samp
     *n_det = 0;
     if (more) *more = 0;
     if (!n_samples) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
-    HostPipe *hp;
-    if ((rc = pipe_get(c, &hp))) return rc;
-    auto work = [&]() -> int { // as ofdm_rx_decode_long_host: once the upload has started, a failure waits for it before it is returned
-        const size_t bytes = (size_t)n_samples * sizeof(ofdm_fc32);
-        if ((rc = dev_grow(c, hp, hp->d_long, bytes + 64))) return rc;
-        if ((rc = long_upload(c, hp, hp->d_long.p, in_host, bytes))) return rc;
-        return sc_scan_dev(c, static_cast<const float2 *>(hp->d_long.p), n_samples, lag_lo, lag_hi, holdoff, max_det, d1, d_hat, f_delta,
-                           metric, n_det, more);
-    };
-    rc = work();
-    if (rc) sync_all(c, hp);
-    return rc;
+    EntryScope scope(c);
+    return with_long_upload(c, &HostPipe::d_long, in_host, (size_t)n_samples * sizeof(ofdm_fc32), 0, [&](HostPipe *, const void *x) {
+        return sc_scan_dev(c, static_cast<const float2 *>(x), n_samples, lag_lo, lag_hi, holdoff, max_det, d1, d_hat, f_delta, metric, n_det, more);
+    });
 }
 
 // EXT-13: upload, ofdm_sc_scan_long, ofdm_rx_decode_packets with the scan's rows, one D2H of everything.  Two synchronisations whatever
@@ -852,55 +841,39 @@ int ofdm_rx_decode_all_long_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t 
     int rc = sc_scan_check(c, in_host, n_samples, lag_lo, holdoff, max_det, d_hat, n_det);
     if (rc) return rc;
     if (max_symbols <= 0 || out_stride <= 0 || (max_det && (!out_host || !out_len || !status || !f_delta || !metric))) return OFDM_ERR_INVALID;
-    const int64_t raw_bytes = (int64_t)max_symbols * c->bytes_per_symbol();
-    if (out_stride < row_bytes(c->mode, raw_bytes > 16 ? raw_bytes - 16 : 0)) return OFDM_ERR_INVALID;
+    if (out_stride < decode_row_bytes(c, max_symbols)) return OFDM_ERR_INVALID;
     *n_det = 0;
     if (more) *more = 0;
     if (!n_samples) return OFDM_OK;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
-    HostPipe *hp;
-    if ((rc = pipe_get(c, &hp))) return rc;
-    auto work = [&]() -> int { // as ofdm_rx_decode_long_host: once the upload has started, a failure waits for it before it is returned
-        const size_t bytes = (size_t)n_samples * sizeof(ofdm_fc32);
-        if ((rc = dev_grow(c, hp, hp->d_long, bytes + 64))) return rc;
-        if ((rc = long_upload(c, hp, hp->d_long.p, in_host, bytes))) return rc;
-        const float2 *x = static_cast<const float2 *>(hp->d_long.p);
+    EntryScope scope(c);
+    return with_long_upload(c, &HostPipe::d_long, in_host, (size_t)n_samples * sizeof(ofdm_fc32), 0, [&](HostPipe *hp, const void *dev) -> int {
+        const float2 *x = static_cast<const float2 *>(dev);
         // (f_delta and metric receive the scan's rows first: they are the decode's input, and its outputs overwrite them)
         if ((rc = sc_scan_dev(c, x, n_samples, lag_lo, lag_hi, holdoff, max_det, d1, d_hat, f_delta, metric, n_det, more))) return rc;
-        const size_t nd = (size_t)*n_det;
+        const size_t nd = (size_t)*n_det, row = (size_t)out_stride;
         if (!nd) return OFDM_OK;
-        const size_t scal = (nd * 28 + 15) & ~(size_t)15, rows = nd * (size_t)out_stride;
-        if ((rc = dev_grow(c, hp, hp->d_out[0], scal + rows + 64))) return rc;
-        char *o = static_cast<char *>(hp->d_out[0].p);
-        int64_t *o_off = reinterpret_cast<int64_t *>(o);
-        double *o_fd = reinterpret_cast<double *>(o + 8 * nd);
-        int32_t *o_len = reinterpret_cast<int32_t *>(o + 16 * nd), *o_st = o_len + nd;
-        float *o_m = reinterpret_cast<float *>(o + 24 * nd);
-        // (the decode keeps what the trace holds in front of it: the dispatch string is the scan's kernels, then the decode's)
-        rc = ofdm_abi_rx_decode_packets(c, x, n_samples, (int64_t)nd, d_hat, f_delta, metric, max_symbols, reinterpret_cast<uint8_t *>(o + scal),
-                                        out_stride, o_len, o_st, o_off, o_fd, o_m);
+        if ((rc = dev_grow(c, hp, hp->d_out[0], PacketsBlock(nullptr, nd, row).bytes + 64))) return rc;
+        const PacketsBlock o(hp->d_out[0].p, nd, row);
+        // (the dispatch string is the scan's kernels, then the decode's)
+        rc = ofdm_abi_rx_decode_packets(c, x, n_samples, (int64_t)nd, d_hat, f_delta, metric, max_symbols, o.rows, out_stride, o.len, o.status,
+                                        o.offset, o.f_delta, o.metric);
         if (rc) return rc;
-        if (offset) HIP_TRY(c, hipMemcpyAsync(offset, o_off, 8 * nd, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(f_delta, o_fd, 8 * nd, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(out_len, o_len, 4 * nd, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(status, o_st, 4 * nd, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(metric, o_m, 4 * nd, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(out_host, o + scal, rows, hipMemcpyDeviceToHost, c->stream));
+        if (offset) HIP_TRY(c, hipMemcpyAsync(offset, o.offset, nd * sizeof(*offset), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(f_delta, o.f_delta, nd * sizeof(*f_delta), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(out_len, o.len, nd * sizeof(*out_len), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(status, o.status, nd * sizeof(*status), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(metric, o.metric, nd * sizeof(*metric), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(out_host, o.rows, nd * row, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return OFDM_OK;
-    };
-    rc = work();
-    if (rc) sync_all(c, hp);
-    return rc;
+    });
 }
 
 int ofdm_rx_decode_long(ofdm_ctx *c, const ofdm_fc32 *in_dev, int64_t n_samples, int64_t lag_lo, int64_t lag_hi, int64_t d_hat_known,
                         int32_t max_symbols, uint8_t *out_dev, int64_t out_cap, int32_t *out_len, int32_t *status, int64_t *offset,
                         double *f_delta, float *metric) {
     if (!c || n_samples <= 0 || lag_lo < 0 || max_symbols <= 0 || !in_dev || !out_dev || !out_len || !status) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    EntryScope scope(c);
     return decode_long_dev(c, reinterpret_cast<const float2 *>(in_dev), n_samples, lag_lo, lag_hi, d_hat_known, max_symbols, out_dev, out_cap,
                            out_len, status, offset, f_delta, metric);
 }
@@ -908,30 +881,13 @@ int ofdm_rx_decode_long(ofdm_ctx *c, const ofdm_fc32 *in_dev, int64_t n_samples,
 int ofdm_rx_decode_long_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t n_samples, int32_t max_symbols, uint8_t *out_host,
                              int64_t out_cap, int32_t *out_len, int32_t *status, int64_t *offset, double *f_delta, float *metric) {
     if (!c || n_samples <= 0 || max_symbols <= 0 || !in_host || !out_host || !out_len || !status) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
-    HostPipe *hp;
-    int rc = pipe_get(c, &hp);
-    if (rc) return rc;
-    // Once the upload has started, DMA reads the caller's buffer (and later writes out_host): every failure below waits for all of
-    // it before the error goes back, as run_pipe does
-    auto work = [&]() -> int {
-        const size_t bytes = (size_t)n_samples * sizeof(ofdm_fc32);
-        if ((rc = dev_grow(c, hp, hp->d_long, bytes + 64))) return rc;
-        if ((rc = dev_grow(c, hp, hp->d_out[0], (size_t)std::max<int64_t>(out_cap, 4) + 64))) return rc;
-        if ((rc = long_upload(c, hp, hp->d_long.p, in_host, bytes))) return rc;
-        rc = decode_long_dev(c, static_cast<const float2 *>(hp->d_long.p), n_samples, 0, 0, -1, max_symbols, static_cast<uint8_t *>(hp->d_out[0].p),
-                             out_cap, out_len, status, offset, f_delta, metric);
-        if (rc) return rc;
-        if (*status == OFDM_FRAME_OK && *out_len > 0) {
-            HIP_TRY(c, hipMemcpyAsync(out_host, hp->d_out[0].p, (size_t)*out_len, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-        }
-        return OFDM_OK;
-    };
-    rc = work();
-    if (rc) sync_all(c, hp);
-    return rc;
+    EntryScope scope(c);
+    return with_long_upload(c, &HostPipe::d_long, in_host, (size_t)n_samples * sizeof(ofdm_fc32), (size_t)std::max<int64_t>(out_cap, 4),
+                            [&](HostPipe *hp, const void *x) {
+        const int rc = decode_long_dev(c, static_cast<const float2 *>(x), n_samples, 0, 0, -1, max_symbols, static_cast<uint8_t *>(hp->d_out[0].p),
+                                       out_cap, out_len, status, offset, f_delta, metric);
+        return rc ? rc : long_row_back(c, hp, out_host, out_len, status);
+    });
 }
 
 // EXT-10: the two long-capture calls on sc16 samples
@@ -939,9 +895,8 @@ int ofdm_rx_decode_long_sc16(ofdm_ctx *c, const ofdm_sc16 *in_dev, int64_t n_sam
                              int64_t d_hat_known, int32_t max_symbols, uint8_t *out_dev, int64_t out_cap, int32_t *out_len, int32_t *status,
                              int64_t *offset, double *f_delta, float *metric) {
     if (!c || n_samples <= 0 || lag_lo < 0 || max_symbols <= 0 || !in_dev || !out_dev || !out_len || !status) return OFDM_ERR_INVALID;
-    if (!(std::isfinite(scale) && scale > 0.f) || (reinterpret_cast<uintptr_t>(in_dev) & 3)) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
+    if (!sc16_scale_ok(scale) || (reinterpret_cast<uintptr_t>(in_dev) & 3)) return OFDM_ERR_INVALID;
+    EntryScope scope(c);
     return decode_long_sc16_dev(c, in_dev, n_samples, scale, lag_lo, lag_hi, d_hat_known, max_symbols, out_dev, out_cap, out_len, status, offset,
                                 f_delta, metric);
 }
@@ -949,29 +904,15 @@ int ofdm_rx_decode_long_sc16(ofdm_ctx *c, const ofdm_sc16 *in_dev, int64_t n_sam
 int ofdm_rx_decode_long_sc16_host(ofdm_ctx *c, const ofdm_sc16 *in_host, int64_t n_samples, float scale, int32_t max_symbols, uint8_t *out_host,
                                   int64_t out_cap, int32_t *out_len, int32_t *status, int64_t *offset, double *f_delta, float *metric) {
     if (!c || n_samples <= 0 || max_symbols <= 0 || !in_host || !out_host || !out_len || !status) return OFDM_ERR_INVALID;
-    if (!(std::isfinite(scale) && scale > 0.f)) return OFDM_ERR_INVALID;
-    DeviceGuard dev_guard(c->device);
-    c->trace.reset();
-    HostPipe *hp;
-    int rc = pipe_get(c, &hp);
-    if (rc) return rc;
-    auto work = [&]() -> int { // as ofdm_rx_decode_long_host: half the bytes over the link, then the widen in front of the chain
-        const size_t bytes = (size_t)n_samples * sizeof(ofdm_sc16);
-        if ((rc = dev_grow(c, hp, hp->d_long16, bytes + 64))) return rc;
-        if ((rc = dev_grow(c, hp, hp->d_out[0], (size_t)std::max<int64_t>(out_cap, 4) + 64))) return rc;
-        if ((rc = long_upload(c, hp, hp->d_long16.p, in_host, bytes))) return rc;
-        rc = decode_long_sc16_dev(c, static_cast<const ofdm_sc16 *>(hp->d_long16.p), n_samples, scale, 0, 0, -1, max_symbols,
-                                  static_cast<uint8_t *>(hp->d_out[0].p), out_cap, out_len, status, offset, f_delta, metric);
-        if (rc) return rc;
-        if (*status == OFDM_FRAME_OK && *out_len > 0) {
-            HIP_TRY(c, hipMemcpyAsync(out_host, hp->d_out[0].p, (size_t)*out_len, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-        }
-        return OFDM_OK;
-    };
-    rc = work();
-    if (rc) sync_all(c, hp);
-    return rc;
+    if (!sc16_scale_ok(scale)) return OFDM_ERR_INVALID;
+    EntryScope scope(c);
+    // as ofdm_rx_decode_long_host: half the bytes over the link, then the widen in front of the chain
+    return with_long_upload(c, &HostPipe::d_long16, in_host, (size_t)n_samples * sizeof(ofdm_sc16), (size_t)std::max<int64_t>(out_cap, 4),
+                            [&](HostPipe *hp, const void *x) {
+        const int rc = decode_long_sc16_dev(c, static_cast<const ofdm_sc16 *>(x), n_samples, scale, 0, 0, -1, max_symbols,
+                                            static_cast<uint8_t *>(hp->d_out[0].p), out_cap, out_len, status, offset, f_delta, metric);
+        return rc ? rc : long_row_back(c, hp, out_host, out_len, status);
+    });
 }
 
 } // extern "C"
