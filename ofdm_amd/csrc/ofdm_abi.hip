@@ -522,6 +522,19 @@ int ofdm_set_tuning(ofdm_ctx *c, const char *key, int64_t value) {
         c->sync_threshold_f64 = thr;
         return OFDM_OK;
     }
+    if (std::strcmp(key, "ws_poison") == 0) { // 0 = off, 0x100 + b = fill what is held now, and every later growth, with byte b (ofdm_hip_tuning.h)
+        if (value != 0 && (value < 0x100 || value > 0x1FF)) return OFDM_ERR_INVALID;
+        if (!value) { c->ws_poison = 0; return OFDM_OK; }
+        DeviceGuard dev_guard(c->device);
+        const int fill = (int)value & 0xFF;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (const Workspace &w : c->ws)
+            if (w.ptr) { const int rc = poison_fill_dev(c, w.ptr, w.cap, fill); if (rc) return rc; }
+        const int rc = ofdm_host_pipe_poison(c, fill);
+        if (rc) return rc;
+        c->ws_poison = (int)value; // on only when everything the context holds was filled: a failed arming leaves the key as it was
+        return OFDM_OK;
+    }
     for (const TuneKey &k : kTuneKeys)
         if (std::strcmp(key, k.name) == 0) {
             if (k.profile_only && !kProfile) return OFDM_ERR_UNSUPPORTED; // the ablation branches are not in this build
@@ -551,6 +564,34 @@ int ofdm_get_tuning(const ofdm_ctx *c, const char *key, int64_t *value) {
         int32_t v = 0;
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&v, src, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return OFDM_ERR_HIP;
         *value = v;
+        return OFDM_OK;
+    }
+    if (std::strcmp(key, "ws_poison") == 0) { *value = c->ws_poison; return OFDM_OK; }
+    if (std::strcmp(key, "stat_ws_roles") == 0) { *value = kWsRoles; return OFDM_OK; }
+    if (std::strcmp(key, "stat_ws_live") == 0) { // bit r: role r holds memory
+        static_assert(kWsRoles < 63, "stat_ws_live is one int64");
+        *value = 0;
+        for (int r = 0; r < kWsRoles; r++) if (c->ws[r].ptr) *value |= (int64_t)1 << r;
+        return OFDM_OK;
+    }
+    if (std::strncmp(key, "stat_ws_ptr:", 12) == 0 || std::strncmp(key, "stat_ws_cap:", 12) == 0) { // role r's address / capacity
+        char *end = nullptr;
+        if (key[12] < '0' || key[12] > '9') return OFDM_ERR_INVALID; // digits only: no blank, no sign
+        const long r = std::strtol(key + 12, &end, 10);
+        if (*end || r >= kWsRoles) return OFDM_ERR_INVALID;
+        *value = key[8] == 'p' ? (int64_t)(uintptr_t)c->ws[r].ptr : (int64_t)c->ws[r].cap;
+        return OFDM_OK;
+    }
+    if (std::strcmp(key, "stat_pipe_bufs") == 0 || std::strncmp(key, "stat_pipe_ptr:", 14) == 0 || std::strncmp(key, "stat_pipe_cap:", 14) == 0 ||
+        std::strncmp(key, "stat_pipe_pinned:", 17) == 0) { // the host pipe's buffers, as stat_ws_* shows the roles
+        void *p = nullptr; size_t cap = 0; int pinned = 0;
+        if (key[10] == 'b') { int n = 0; while (ofdm_host_pipe_buffer(c, n, &p, &cap, &pinned)) n++; *value = n; return OFDM_OK; }
+        const char *num = std::strchr(key, ':') + 1;
+        char *end = nullptr;
+        if (*num < '0' || *num > '9') return OFDM_ERR_INVALID;
+        const long i = std::strtol(num, &end, 10);
+        if (*end || i > 1000 || !ofdm_host_pipe_buffer(c, (int)i, &p, &cap, &pinned)) return OFDM_ERR_INVALID;
+        *value = key[11] == 't' ? (int64_t)(uintptr_t)p : key[10] == 'c' ? (int64_t)cap : pinned;
         return OFDM_OK;
     }
     for (const TuneKey &k : kTuneKeys)

@@ -123,6 +123,7 @@ struct ofdm_ctx {
     int32_t *d_stats = nullptr;         // [2] their home on the device (owned by the context)
     // workspaces (grown on demand, never inside a captured region)
     Workspace ws[kWsRoles];
+    int ws_poison = 0;            // ofdm_set_tuning "ws_poison" (ofdm_hip_tuning.h): 0 = off, 0x100 + b = every growth is filled with byte b
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     HostPipe *pipe = nullptr;     // created by the first host-buffer call, freed by ofdm_destroy
 
@@ -156,6 +157,13 @@ struct EntryScope {
         if (_e != hipSuccess) { (ctx)->last_hip = (int)_e; return OFDM_ERR_HIP; } \
     } while (0)
 
+// "ws_poison" (ofdm_hip_tuning.h): fill a fresh device allocation over its whole capacity before any kernel or copy of any stream sees it
+inline int poison_fill_dev(ofdm_ctx *c, void *p, size_t cap, int fill) {
+    HIP_TRY(c, hipMemsetAsync(p, fill, cap, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return OFDM_OK;
+}
+
 inline int ws_get(ofdm_ctx *c, WsRole role, size_t bytes, void **out) {
     Workspace &w = c->ws[role];
     if (bytes > w.cap) {
@@ -164,6 +172,7 @@ inline int ws_get(ofdm_ctx *c, WsRole role, size_t bytes, void **out) {
         hipError_t e = hipMalloc(&w.ptr, want);
         if (e != hipSuccess) { c->last_hip = (int)e; w.ptr = nullptr; return OFDM_ERR_NOMEM; }
         w.cap = want;
+        if (c->ws_poison) { const int rc = poison_fill_dev(c, w.ptr, want, c->ws_poison & 0xFF); if (rc) return rc; }
     }
     *out = w.ptr;
     return OFDM_OK;
@@ -272,6 +281,11 @@ struct DecodeCall {
 // internal cross-file helpers (C linkage only because their definitions sit inside the extern "C" blocks; not in ofdm_hip.h)
 extern "C" {
 __attribute__((visibility("hidden"))) void ofdm_host_pipe_destroy(ofdm_ctx *c); // ofdm_host_path.hip; the context's device is current
+// "ws_poison" set on (ofdm_host_path.hip; the context's device is current): synchronise the pipe's streams, if a pipe exists, and fill
+// every device and pinned buffer it holds over its whole capacity with the byte `fill`
+__attribute__((visibility("hidden"))) int ofdm_host_pipe_poison(ofdm_ctx *c, int fill);
+// "stat_pipe_*": buffer i of the pipe (no pipe yet: nullptr, 0) and whether it is pinned host memory; 0 behind the last buffer
+__attribute__((visibility("hidden"))) int ofdm_host_pipe_buffer(const ofdm_ctx *c, int i, void **p, size_t *cap, int *pinned);
 // Schmidl-Cox over a batch (the dispatcher behind ofdm_sc_correlate_batch and step 1 of ofdm_rx_decode_batch; ofdm_abi.hip)
 __attribute__((visibility("hidden"))) int ofdm_abi_sc_run(ofdm_ctx *c, const float2 *in, int64_t n_frames, int64_t frame_stride, int64_t frame_len, int64_t n_lags,
                     int32_t *d_hat, double *f_delta, float *metric);

@@ -48,6 +48,21 @@
 //   Schmidl-Cox threshold in full precision (handled by name in ofdm_abi.hip, 64 bits: not in the table below)
 //     sync_threshold_bits the bit pattern of a double in (0, 1] that replaces ofdm_params.sync_threshold (a float: 6e-8 apart) in every
 //                         search of the context; 0 = the float again.  The margin tests set the threshold within 1e-12 of a lag's own metric
+//   what the workspaces hold (handled by name in ofdm_abi.hip: not in the table below; tests/test_gpu_ws_poison.py, DESIGN.md "the
+//   workspace ledger")
+//     ws_poison           0 = off: nothing is ever filled, the code of every path is what it is without the key.  0x100 + b (b = 0 .. 255) = on
+//                         with fill byte b; every other value: OFDM_ERR_INVALID.  Setting it on synchronises the context's stream (and the
+//                         host pipe's, if there is one) and fills, once, every workspace that holds memory and every device and pinned
+//                         buffer of the host pipe over its whole capacity with b.  While it is on every GROWTH (ws_get, and the pipe's dev_grow
+//                         / pin_grow) fills the new allocation over its capacity before handing it out; an ordinary ws_get fills nothing (an
+//                         entry point may take a role more than once).  A fill is a memset, no launch: the dispatch strings do not change
+//     stat_ws_roles       get: kWsRoles, the number of workspace roles (WsRole, ofdm_ctx.hpp)
+//     stat_ws_live        get: bit r is set when role r holds memory
+//     stat_ws_ptr:<r>, stat_ws_cap:<r>   get: the device address and the capacity in bytes of role r (0 and 0 when it holds nothing); with
+//                         ofdm_memcpy_d2h the tests read a workspace back whole
+//     stat_pipe_bufs, stat_pipe_ptr:<i>, stat_pipe_cap:<i>, stat_pipe_pinned:<i>   get: the same for the host pipe's buffers (the device
+//                         slots, the long-capture copies and scalars, then the pinned slots): how many there are, and of buffer i the
+//                         address, the capacity and whether it is pinned host memory (all 0 before the first host-buffer call)
 //   profile build only (libofdm_hip_profile.so): ablation exits and s_memtime section timers
 //     debug_demod64, debug_sc, debug_tx
 #ifndef OFDM_TUNE_KEY

@@ -54,6 +54,7 @@ int dev_grow(ofdm_ctx *c, HostPipe *hp, Buf &b, size_t bytes) {
     hipError_t e = hipMalloc(&b.p, want);
     if (e != hipSuccess) { c->last_hip = (int)e; b.p = nullptr; return OFDM_ERR_NOMEM; }
     b.cap = want;
+    if (c->ws_poison) return poison_fill_dev(c, b.p, want, c->ws_poison & 0xFF);
     return OFDM_OK;
 }
 int pin_grow(ofdm_ctx *c, HostPipe *hp, Buf &b, size_t bytes) {
@@ -63,6 +64,7 @@ int pin_grow(ofdm_ctx *c, HostPipe *hp, Buf &b, size_t bytes) {
     hipError_t e = hipHostMalloc(&b.p, want, hipHostMallocDefault);
     if (e != hipSuccess) { c->last_hip = (int)e; b.p = nullptr; return OFDM_ERR_NOMEM; }
     b.cap = want;
+    if (c->ws_poison) std::memset(b.p, c->ws_poison & 0xFF, want);
     return OFDM_OK;
 }
 
@@ -661,6 +663,43 @@ void ofdm_host_pipe_destroy(ofdm_ctx *c) {
     if (hp->s_out) hipStreamDestroy(hp->s_out);
     delete hp;
     c->pipe = nullptr;
+}
+
+// Buffer i of the pipe, in the one order everything that walks them uses: the device slots d_in[], d_out[], then d_long, d_long16, d_scal;
+// the pinned slots h_in[], h_out[], then h_scal.  nullptr behind the last one
+static Buf *pipe_buf(HostPipe *hp, int i, bool *pinned) {
+    constexpr int S = HostPipe::kSlots;
+    Buf *const single[] = {&hp->d_long, &hp->d_long16, &hp->d_scal};
+    *pinned = false;
+    if (i < 0) return nullptr;
+    if (i < S) return &hp->d_in[i];
+    if ((i -= S) < S) return &hp->d_out[i];
+    if ((i -= S) < 3) return single[i];
+    *pinned = true;
+    if ((i -= 3) < S) return &hp->h_in[i];
+    if ((i -= S) < S) return &hp->h_out[i];
+    return i == S ? &hp->h_scal : nullptr;
+}
+int ofdm_host_pipe_buffer(const ofdm_ctx *c, int i, void **p, size_t *cap, int *pinned) {
+    bool pin = false;
+    HostPipe empty;
+    Buf *b = pipe_buf(c->pipe ? c->pipe : &empty, i, &pin);
+    if (!b) return 0;
+    *p = c->pipe ? b->p : nullptr; *cap = c->pipe ? b->cap : 0; *pinned = pin;
+    return 1;
+}
+int ofdm_host_pipe_poison(ofdm_ctx *c, int fill) {
+    HostPipe *hp = c->pipe;
+    if (!hp) return OFDM_OK;
+    int rc = sync_all(c, hp);
+    if (rc) return rc;
+    bool pinned = false;
+    for (int i = 0; Buf *b = pipe_buf(hp, i, &pinned); i++) {
+        if (!b->p) continue;
+        if (pinned) std::memset(b->p, fill, b->cap);
+        else if ((rc = poison_fill_dev(c, b->p, b->cap, fill))) return rc;
+    }
+    return OFDM_OK;
 }
 
 int ofdm_host_alloc(size_t bytes, void **host) {
