@@ -173,7 +173,17 @@ int ofdm_chacha_block(const uint32_t *key8, const uint32_t *words12_15, int32_t 
 /* CRC-32 of IEEE 802.3 / zlib over n_bytes bytes (see "frame check sequence" below); 0 for a NULL pointer or a negative count.
  * Host call, no context: exported so that the definition can be pinned without a GPU. */
 uint32_t ofdm_crc32(const uint8_t *data, int64_t n_bytes);
-/* preamble / training: host pointers (interleaved doubles) or NULL for the defaults.
+/* preamble / training: host pointers (interleaved doubles) or NULL for the defaults.  Every kernel and host table that reads one
+ * reads the context's own (tests/pilot_cases.py, tests/test_gpu_pilots.py): the frame header and the maximum normalize starts from
+ * (signed, over re and im of the ten header blocks, wherever it lies), 1 / t_k of the channel estimate, W_k = |t_k|^2 and R^-1 of the
+ * denoised estimate, sum |t_k|^2 of the link quality, conj(t_k) of the wide CFO acquisition.
+ * A ZERO TRAINING BIN t_k = 0 carries no information about H_k.  Under OFDM_CHEST_LS its estimate is 0 / 0: H_k is non-finite in that
+ * bin and in no other, and a data carrier there demaps by the NaN rule -- a non-finite coordinate decides level 0 of its axis (BPSK
+ * and QPSK: bit 0), so the carrier's bits are all 0 -- while w_k of "soft decisions" is a mean over ALL data carriers: one dead data
+ * bin makes every LLR of the frame 0.  Under OFDM_CHEST_WLS the bin carries weight W_k = 0, H' is finite in every bin, and hard and
+ * soft decisions are those of any other frame: the mode for tables with dead bins.  A dead PILOT bin (guard bands) makes the common
+ * phase of every data symbol non-finite under OFDM_CHEST_LS.  A table that is zero on a whole band (the guard band nulled, as 802.11's
+ * is) makes R of the denoised estimate singular to rounding: outside that mode's domain, and refused (ofdm_chest_matrix below).
  * device: HIP device ordinal.  stream: a hipStream_t (as void*); NULL = the device's default (null) stream,
  * which is what torch uses as its current stream unless told otherwise. */
 int ofdm_create(const ofdm_params *p, const double *preamble, const double *training, int device, void *stream,
@@ -309,7 +319,9 @@ int ofdm_cfo_rotate_batch(ofdm_ctx *ctx, ofdm_fc32 *x_dev, int64_t n_frames, int
                           int64_t frame_len, const double *f_delta_dev, const int32_t *first_index_dev);
 /* estimate_channel (src/receiver.rs:212-229): H[k] = mean_b FFT(block_b minus CP)[k] / training[k] over the five
  * training blocks starting at sample offset_dev[f] + 5*L of frame f (offset_dev NULL: 0).
- * f_delta_dev (optional): blocks are derotated with sample_id counted from offset_dev[f]. hk_dev: n_frames*n_fft */
+ * f_delta_dev (optional): blocks are derotated with sample_id counted from offset_dev[f]. hk_dev: n_frames*n_fft
+ * Where training[k] = 0 the quotient is 0 / 0: H[k] is non-finite (NaN) in exactly those bins, as the reference's own division
+ * leaves it; see ofdm_create for what follows from it.  Under OFDM_CHEST_WLS such a bin has weight 0 and H'[k] is finite. */
 int ofdm_estimate_channel_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t n_frames, int64_t frame_stride,
                                 int64_t frame_len, const int32_t *offset_dev, const double *f_delta_dev,
                                 ofdm_fc32 *hk_dev);
@@ -333,8 +345,11 @@ int ofdm_estimate_channel_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t 
  * take no estimate from outside, so the generic chain runs (ofdm_last_dispatch shows k_chest_solve). */
 /* R^-1 as cp_len x cp_len interleaved (re, im) doubles, row-major, solved in f64 (Levinson recursion + Trench's fill of the Toeplitz
  * inverse, O(cp_len^2)).  training: n_fft interleaved doubles, NULL = the default table.  OFDM_ERR_INVALID for a bad size, a NULL
- * rinv, or a table with so many zero bins that R is singular.  Host call, no context: exported so that the solver can be pinned
- * without a GPU. */
+ * rinv, or a table with so many zero bins that R is singular -- exactly, or to rounding: what the recursion returns is verified,
+ * max |R rinv - I| <= 1e-6 over the columns checked (the device keeps the table in f32: beyond that it is no usable table), so a
+ * training table that is zero on a whole band (cond(R) 2e14 at n_fft = 256 with the guard bands nulled) is refused, not answered with
+ * rounding residue; scattered zero bins leave R well conditioned.  ofdm_create with OFDM_CHEST_WLS and ofdm_chest_smooth_batch refuse
+ * the same tables.  Host call, no context: exported so that the solver can be pinned without a GPU. */
 int ofdm_chest_matrix(int32_t n_fft, int32_t cp_len, const double *training, double *rinv);
 /* The stage on its own: n_frames rows of n_fft bins H^ -> H'.  hk_in_dev == hk_out_dev allowed.  Works on any context whatever its
  * chest_mode (the tables are built on first use; OFDM_ERR_INVALID if the context's training table makes R singular). */

@@ -1293,10 +1293,25 @@ class Context:
 _CTX_CACHE = {}
 
 
+def _ctx_key(n_fft, modulation, guard_bands, ecc=ECC_NONE, _replica: int = 0, **kw) -> tuple:
+    """The cache key of _ctx, a pure function of its arguments.  Explicit `preamble` / `training` tables are inputs of the context
+    (ofdm_create), so they are keyed by value: their complex128 bytes and shape, as Context hands them to the library.  Two different
+    tables get two contexts, the same table (whatever object or dtype carries it) reuses one; None is the default table."""
+    items = []
+    for k, v in sorted(kw.items()):
+        if k in ("preamble", "training") and v is not None:
+            a = np.ascontiguousarray(v, dtype=np.complex128)
+            v = (a.shape, a.tobytes())
+        elif k == "tuning" and v is not None:
+            v = tuple(sorted(dict(v).items()))
+        items.append((k, v))
+    return (n_fft, modulation, bool(guard_bands), ecc, _replica, tuple(items))
+
+
 def _ctx(n_fft, modulation, guard_bands, ecc=ECC_NONE, _replica: int = 0, **kw) -> Context:
     """One cached context per parameter set (and replica index): the free functions never pay ofdm_create -- table uploads,
     workspace growth -- more than once."""
-    key = (n_fft, modulation, bool(guard_bands), ecc, _replica, tuple(sorted(kw.items())))
+    key = _ctx_key(n_fft, modulation, guard_bands, ecc, _replica, **kw)
     if key not in _CTX_CACHE:
         _CTX_CACHE[key] = Context(n_fft=n_fft, modulation=modulation, guard_bands=guard_bands, ecc=ecc, **kw)
     return _CTX_CACHE[key]

@@ -102,7 +102,8 @@ static int fast_path(ofdm_ctx *c, hipError_t e) {
 //   B[i + 1][j + 1] = B[i][j] + (x[i + 1] conj(x[j + 1]) - conj(x[L - 1 - i]) x[L - 1 - j]) / x[0].
 // The recursion runs along diagonals from the first row and column only as far as the anti-diagonal; the other half follows from
 // persymmetry, B[i][j] = B[L - 1 - j][L - 1 - i], so no entry is more than L / 2 additions away from x.
-// false when R is not positive definite (fewer than L non-zero training bins).
+// false when R is not positive definite (fewer than L non-zero training bins), or when what came out is not its inverse (below).
+static const double kChestResidual = 1e-6;
 static bool chest_rinv(int N, const double *trn, std::vector<cd> &B) {
     const int L = N / 4;
     std::vector<cd> r(N);
@@ -142,6 +143,22 @@ static bool chest_rinv(int N, const double *trn, std::vector<cd> &B) {
             B[(size_t)i * L + j] = v;
             B[(size_t)(L - 1 - j) * L + (L - 1 - i)] = v;
         }
+    // The recursion only fails outright when a pivot turns non-positive.  A table that is zero on a whole band (guard bands nulled) makes
+    // R singular to rounding, and the recursion may then run to its end on pivots that are rounding residue: B is verified as an inverse,
+    // |R B - I| <= kChestResidual on at most 64 evenly spaced columns (all of them up to N = 256), and refused otherwise.  The device keeps
+    // the table in f32, so a residual beyond that is no usable table.
+    const int step = L > 64 ? L / 64 : 1;
+    std::vector<cd> col(L);
+    for (int j = 0; j < L; j += step) {
+        for (int m = 0; m < L; m++) col[m] = B[(size_t)m * L + j];
+        for (int i = 0; i < L; i++) {
+            cd s{i == j ? -1.0 : 0.0, 0.0};
+            const cd *ri = r.data() + i; // R[i][m] = r[i - m], taken mod N
+            for (int m = 0; m <= i; m++) { const cd t = cd_mul(ri[-m], col[m]); s.re += t.re; s.im += t.im; }
+            for (int m = i + 1; m < L; m++) { const cd t = cd_mul(ri[N - m], col[m]); s.re += t.re; s.im += t.im; }
+            if (!(s.re * s.re + s.im * s.im <= kChestResidual * kChestResidual)) return false;
+        }
+    }
     return true;
 }
 

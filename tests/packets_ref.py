@@ -64,9 +64,9 @@ def row_rule_is_length_rule(n, S, backoff, d_hat, max_symbols, bytes_per_symbol)
     return prepare(g.row_len, g.d_rel, S, backoff, max_symbols, bytes_per_symbol) == prepare(g.length, g.d_rel, S, backoff, max_symbols, bytes_per_symbol)
 
 
-def packet(orc, x32, d_hat, f_delta, metric, n_fft, guard, mod, max_symbols, backoff=4, cfo_mode=CFO_SIGNED):
+def packet(orc, x32, d_hat, f_delta, metric, n_fft, guard, mod, max_symbols, backoff=4, cfo_mode=CFO_SIGNED, training=None):
     """The definition for one packet -> dict(status, offset, len, bytes, f_delta, metric, ns, soft): soft = the oracle's equalised points of
-    the row (for util.assert_bytes_match; body bit b is stream bit 128 + b)"""
+    the row (for util.assert_bytes_match; body bit b is stream bit 128 + b).  training: the context's table (None: the default)"""
     S = n_fft + n_fft // 4
     nd = 48 * (n_fft // 64) if guard else n_fft
     g = geometry(len(x32), S, backoff, int(d_hat), max_symbols)
@@ -74,15 +74,15 @@ def packet(orc, x32, d_hat, f_delta, metric, n_fft, guard, mod, max_symbols, bac
     fd = cfo_through(float(f_delta), cfo_mode)
     res = {"status": p.status, "offset": g.r + p.off, "len": 0, "bytes": b"", "f_delta": fd, "metric": np.float32(metric), "ns": p.ns, "soft": None}
     if p.status == FRAME_OK:
-        w = orc.decode_given(wide(x32[g.r:]), p.off, fd, guard, mod, n_fft, max_symbols=max_symbols, want_soft=True)
+        w = orc.decode_given(wide(x32[g.r:]), p.off, fd, guard, mod, n_fft, training=training, max_symbols=max_symbols, want_soft=True)
         assert w["status"] == FRAME_OK and w["n_symbols"] == p.ns and w["offset"] == p.off, (w["status"], w["n_symbols"], p)
         res.update(len=len(w["bytes"]), bytes=w["bytes"], soft=w["soft"])
     return res
 
 
-def packets(orc, x32, det, n_fft, guard, mod, max_symbols, backoff=4, cfo_mode=CFO_SIGNED):
+def packets(orc, x32, det, n_fft, guard, mod, max_symbols, backoff=4, cfo_mode=CFO_SIGNED, training=None):
     """packet() for every row of a scan (anything with d_hat / f_delta / metric sequences)"""
-    return [packet(orc, x32, d, fd, m, n_fft, guard, mod, max_symbols, backoff, cfo_mode)
+    return [packet(orc, x32, d, fd, m, n_fft, guard, mod, max_symbols, backoff, cfo_mode, training)
             for d, fd, m in zip(det["d_hat"], det["f_delta"], det["metric"])]
 
 
