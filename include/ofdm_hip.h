@@ -342,7 +342,12 @@ int ofdm_estimate_channel_batch(ofdm_ctx *ctx, const ofdm_fc32 *in_dev, int64_t 
  * A non-finite sample in a training block spoils the frame's WHOLE estimate H', not one bin as with OFDM_CHEST_LS.
  * With chest_mode = OFDM_CHEST_WLS ofdm_estimate_channel_batch returns H' and every decode entry point (ofdm_rx_decode_batch, _host,
  * _long, _long_host, a merged detection included) equalises and forms its LLR weights with H', for every ecc; the fused frame kernels
- * take no estimate from outside, so the generic chain runs (ofdm_last_dispatch shows k_chest_solve). */
+ * take no estimate from outside, so the generic chain runs (ofdm_last_dispatch shows k_chest_solve).
+ * The window and sync_backoff: a Schmidl-Cox frame start lies sync_backoff samples in front of the detected one, which puts the
+ * channel's first tap at delay sync_backoff.  The window ends at delay 3 cp_len / 4 - 1, so with sync_backoff >= 3 cp_len / 4 not even
+ * a one-tap channel lies inside it and H' is noise: under OFDM_SYNC_SCHMIDL_COX ofdm_create refuses OFDM_CHEST_WLS, and OFDM_CFO_WIDE
+ * (whose metric sums the same window), with such a back-off (OFDM_ERR_INVALID).  A channel of T taps needs sync_backoff + T <=
+ * 3 cp_len / 4, which is the caller's to keep.  OFDM_SYNC_REFERENCE does not use sync_backoff and takes any. */
 /* R^-1 as cp_len x cp_len interleaved (re, im) doubles, row-major, solved in f64 (Levinson recursion + Trench's fill of the Toeplitz
  * inverse, O(cp_len^2)).  training: n_fft interleaved doubles, NULL = the default table.  OFDM_ERR_INVALID for a bad size, a NULL
  * rinv, or a table with so many zero bins that R is singular -- exactly, or to rounding: what the recursion returns is verified,

@@ -52,6 +52,7 @@ SYNC_SCHMIDL_COX, SYNC_REFERENCE = 0, 1
 RX_AUTO, RX_STAGED = 0, 1
 # channel estimate of the receive chain: the reference's bin-by-bin one, or that one denoised by a weighted least-squares fit of cp_len
 # taps (EXT-5; tests/chest_ref.py is the definition)
+# Under SYNC_SCHMIDL_COX ofdm_create refuses CHEST_WLS (and CFO_WIDE) with sync_backoff >= 3 cp_len / 4: the tap window ends there
 CHEST_LS, CHEST_WLS = 0, 1
 # ofdm_rx_quality_batch: indices into a frame's row of QUALITY_FIELDS floats (EXT-6; tests/quality_ref.py is the definition)
 Q_VALID, Q_NOISE_VAR, Q_GAIN, Q_SNR, Q_LLR_UNIT, Q_EVM2, Q_POINTS = 0, 1, 2, 3, 4, 5, 6

@@ -425,6 +425,10 @@ int ofdm_create(const ofdm_params *p, const double *preamble, const double *trai
     if (p->cfo_mode == OFDM_CFO_WIDE && p->sync_mode != OFDM_SYNC_SCHMIDL_COX) return OFDM_ERR_INVALID; // the hypotheses refine the Schmidl-Cox phase
     if (p->rx_path != OFDM_RX_AUTO && p->rx_path != OFDM_RX_STAGED) return OFDM_ERR_INVALID; // (2 was the one-pass kernel of rounds 2-4: removed)
     if (p->chest_mode != OFDM_CHEST_LS && p->chest_mode != OFDM_CHEST_WLS) return OFDM_ERR_INVALID;
+    // EXT-5 / EXT-8 model the channel's taps at delays [-cp/4, 3 cp/4) behind the frame start; a Schmidl-Cox frame start is
+    // sync_backoff samples early, so the first tap sits at delay sync_backoff: at 3 cp/4 or more even a one-tap channel is outside
+    if (p->sync_mode == OFDM_SYNC_SCHMIDL_COX && (p->chest_mode == OFDM_CHEST_WLS || p->cfo_mode == OFDM_CFO_WIDE) &&
+        p->sync_backoff >= p->cp_len - p->cp_len / 4) return OFDM_ERR_INVALID;
     for (int r : p->reserved) if (r != 0) return OFDM_ERR_INVALID;
 
     int ndev = 0;
