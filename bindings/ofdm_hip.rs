@@ -9,6 +9,8 @@ use std::os::raw::{c_char, c_int, c_void};
 
 #[repr(C)]
 pub struct ofdm_ctx { _private: [u8; 0] }
+#[repr(C)]
+pub struct ofdm_stream { _private: [u8; 0] }
 
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -314,6 +316,18 @@ extern "C" {
     pub fn ofdm_rx_decode_long_sc16_host(ctx: *mut ofdm_ctx, in_host: *const ofdm_sc16, n_samples: i64, scale: f32, max_symbols: i32,
                                          out_host: *mut u8, out_cap: i64, out_len: *mut i32, status: *mut i32, offset: *mut i64,
                                          f_delta: *mut f64, metric: *mut f32) -> c_int;
+    // EXT-14: a streaming receiver.  The handle comes first (create: its address, then the context); offset, d1 and more may be null
+    pub fn ofdm_stream_create(out: *mut *mut ofdm_stream, ctx: *mut ofdm_ctx, max_symbols: i32, holdoff: i64, max_chunk: i64,
+                              first_sample: i64) -> c_int;
+    pub fn ofdm_stream_destroy(s: *mut ofdm_stream) -> c_int;
+    pub fn ofdm_stream_reset(s: *mut ofdm_stream, first_sample: i64) -> c_int;
+    pub fn ofdm_stream_push(s: *mut ofdm_stream, in_host: *const ofdm_fc32, n: i64, flush: i32, max_pkt: i64, out_host: *mut u8, out_stride: i64,
+                            out_len: *mut i32, status: *mut i32, offset: *mut i64, f_delta: *mut f64, metric: *mut f32, d1: *mut i64,
+                            d_hat: *mut i64, n_pkt: *mut i64, more: *mut i32) -> c_int;
+    pub fn ofdm_stream_push_sc16(s: *mut ofdm_stream, in_host: *const ofdm_sc16, n: i64, scale: f32, flush: i32, max_pkt: i64, out_host: *mut u8,
+                                 out_stride: i64, out_len: *mut i32, status: *mut i32, offset: *mut i64, f_delta: *mut f64, metric: *mut f32,
+                                 d1: *mut i64, d_hat: *mut i64, n_pkt: *mut i64, more: *mut i32) -> c_int;
+    pub fn ofdm_stream_state(s: *const ofdm_stream, total: *mut i64, kept_from: *mut i64, next_lag: *mut i64, ended: *mut i32) -> c_int;
     pub fn ofdm_timer_start(ctx: *mut ofdm_ctx) -> c_int;
     pub fn ofdm_timer_stop_ms(ctx: *mut ofdm_ctx, elapsed_ms: *mut f32) -> c_int;
 }
@@ -348,6 +362,43 @@ impl Ctx {
     }
 }
 impl Drop for Ctx { fn drop(&mut self) { unsafe { ofdm_destroy(self.raw); } } }
+
+/// EXT-14: a streaming receiver on a context (include/ofdm_hip.h, "a streaming receiver").  `push` takes the samples as a radio hands them
+/// over and returns the packets that push made deliverable; however the stream is cut they are, bit for bit, the packets of one
+/// `ofdm_rx_decode_all_long_host` call on the concatenation, each exactly once.  Borrows its context, so it is dropped before it.
+pub struct StreamPacket { pub bytes: Vec<u8>, pub status: i32, pub offset: i64, pub d1: i64, pub d_hat: i64, pub f_delta: f64, pub metric: f32 }
+pub struct Stream<'a> { raw: *mut ofdm_stream, row: usize, _ctx: std::marker::PhantomData<&'a Ctx> }
+impl<'a> Stream<'a> {
+    pub fn new(ctx: &'a Ctx, max_symbols: i32, holdoff: i64, max_chunk: i64, first_sample: i64) -> anyhow::Result<Self> {
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { ofdm_stream_create(&mut raw, ctx.raw, max_symbols, holdoff, max_chunk, first_sample) }, "ofdm_stream_create")?;
+        Ok(Stream { raw, row: (max_symbols as usize * ctx.bytes_per_symbol).max(4) + 256, _ctx: std::marker::PhantomData })
+    }
+    /// `samples` (may be empty), then everything drained through `more`; `flush` ends the stream until `reset`
+    pub fn push(&mut self, samples: &[ofdm_fc32], flush: bool) -> anyhow::Result<Vec<StreamPacket>> {
+        const BATCH: usize = 64;
+        let mut out = Vec::new();
+        let mut rows = vec![0u8; BATCH * self.row];
+        let (mut len, mut status, mut offset, mut d1, mut d_hat) = ([0i32; BATCH], [0i32; BATCH], [0i64; BATCH], [0i64; BATCH], [0i64; BATCH]);
+        let (mut f_delta, mut metric, mut n, mut more) = ([0f64; BATCH], [0f32; BATCH], 0i64, 0i32);
+        let mut first = true;
+        loop {
+            let (p, k) = if first { (samples.as_ptr(), samples.len() as i64) } else { (std::ptr::null(), 0) };
+            check(unsafe { ofdm_stream_push(self.raw, p, k, flush as i32, BATCH as i64, rows.as_mut_ptr(), self.row as i64, len.as_mut_ptr(),
+                                            status.as_mut_ptr(), offset.as_mut_ptr(), f_delta.as_mut_ptr(), metric.as_mut_ptr(), d1.as_mut_ptr(),
+                                            d_hat.as_mut_ptr(), &mut n, &mut more) }, "ofdm_stream_push")?;
+            first = false;
+            for i in 0..n as usize {
+                let bytes = if status[i] == 0 && len[i] > 0 { rows[i * self.row..i * self.row + len[i] as usize].to_vec() } else { Vec::new() };
+                out.push(StreamPacket { bytes, status: status[i], offset: offset[i], d1: d1[i], d_hat: d_hat[i], f_delta: f_delta[i], metric: metric[i] });
+            }
+            if more == 0 { return Ok(out); }
+        }
+    }
+    pub fn flush(&mut self) -> anyhow::Result<Vec<StreamPacket>> { self.push(&[], true) }
+    pub fn reset(&mut self, first_sample: i64) -> anyhow::Result<()> { check(unsafe { ofdm_stream_reset(self.raw, first_sample) }, "ofdm_stream_reset") }
+}
+impl<'a> Drop for Stream<'a> { fn drop(&mut self) { unsafe { ofdm_stream_destroy(self.raw); } } }
 
 /// One context per (thread, parameter set), created on first use and kept for the life of the thread: the reference calls `encode!` /
 /// `decode!` once per frame (examples/lab3a.rs:24,34, jetson_rx.rs:86) and `ofdm_create` -- table uploads, streams, workspaces --

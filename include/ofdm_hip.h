@@ -1051,6 +1051,63 @@ int ofdm_rx_decode_long_sc16_host(ofdm_ctx *ctx, const ofdm_sc16 *in_host, int64
                                   uint8_t *out_host, int64_t out_cap, int32_t *out_len, int32_t *status, int64_t *offset,
                                   double *f_delta, float *metric);
 
+/* ------------------------------------------------------------------ a streaming receiver (EXT-14)
+ * A radio hands over a few thousand samples at a time, without end, and packets straddle the buffers.  A stream takes the samples as they
+ * come (ofdm_stream_push) and delivers every packet exactly once: HOWEVER THE STREAM IS CUT INTO PUSHES, THE PACKETS DELIVERED ARE, FIELD
+ * FOR FIELD AND BIT FOR BIT, THOSE OF ONE ofdm_rx_decode_all_long_host CALL ON THE CONCATENATION.  (The declarations stand behind the sc16
+ * sections because the sc16 push needs ofdm_sc16; the rules are EXT-12's and EXT-13's.)
+ *
+ * Notation: sample 0 is the first sample pushed after create or reset, T the number pushed so far; S, L = S, W, b = sync_backoff and
+ * valid = T - W - L + 1 as in the EXT-12 text; max_symbols and holdoff mean what they mean in ofdm_rx_decode_all_long_host; max_chunk is
+ * the largest number of samples the stream's buffers take at once (a larger push is walked in pieces inside the call).
+ *     reference   A(T) = ofdm_rx_decode_all_long_host(stream[0:T], lag_lo = 0, lag_hi = 0, holdoff, max_det unbounded, max_symbols):
+ *                 detections k = 0, 1, .. with d1_k, d_hat_k and per packet status, out_len, bytes, offset, f_delta, metric
+ *     horizon     H = W + (10 + max_symbols) S + 2; detection k is COMMITTED at T iff d1_k + H <= T.  Then its peak window [d1_k, d1_k + W]
+ *                 lies below valid (sync_window_reps <= 3) and its whole gathered row [r_k, r_k + R) inside the stream (0 <= b <= cp_len),
+ *                 so every field of packet k in A(T) is its field in A(T') for all T' >= T (the proof in integers: tests/test_stream_cpu.py)
+ *     push        without flush: delivers, in order, every committed detection not delivered before; a detection that is not committed
+ *                 defers itself and every later one.  So packet k arrives in the result of the first push after which T >= d1_k + H, or in
+ *                 the flush, and in no other: the delivery time is part of the contract
+ *     flush       delivers every remaining detection of A(T), a last frame cut by the end of the stream with the prefix the one-shot call
+ *                 delivers.  Then the stream is ended: a further push is OFDM_ERR_INVALID until ofdm_stream_reset
+ *     first_sample (create and reset, any int64 >= 0) is added to the reported d1, d_hat and offset and to nothing else: every rule
+ *                 above, the `& ~1` of the row start included, is in stream-relative indices.  It exists for timestamps
+ * The sums of every lag's window are the oracle's own in order and the timing triple is the scan's (EXT-12, EXT-13), "a row depends on
+ * its own triple and the capture only": that is what makes the answer exact and not merely close.
+ *
+ * Per piece of a push the stream runs k_stream_ingest<fc32> / k_stream_ingest<sc16> (ONE launch: the samples it keeps from the old window
+ * and the new chunk into the other window), ofdm_sc_scan_long's kernels over the window from the lag the walk resumes at, and
+ * ofdm_rx_decode_packets' chain over the committed detections: ofdm_last_dispatch names them in that order (a push that delivers nothing:
+ * the ingest and the scan; a window that has no valid lag yet: the ingest alone; a flush with n = 0: no ingest), once -- the pieces behind
+ * the first of a push larger than max_chunk are left out.  The window keeps the samples from (lo - L - b) & ~1 on, lo = the first lag
+ * not yet decided (a deferred detection's d1, else max(the last d1 + holdoff, valid)): never more than H + L + b + 2 + max_chunk samples,
+ * sized once at create.  The stream owns its windows, its staging buffer and its result rows (freed by ofdm_stream_destroy) and uses the
+ * context's workspaces call by call: several streams on one context are independent.  Pushes are synchronous on the context's stream; a
+ * stream is no more thread-safe than its context, and is destroyed BEFORE its context.
+ *
+ * in_host: n samples in host memory (pinned memory is DMA-ed in place).  The outputs are HOST arrays of max_pkt entries, laid out as in
+ * ofdm_rx_decode_all_long_host (out_host: rows of out_stride bytes; offset, d1 and more optional).  *n_pkt = the packets delivered by this
+ * call; *more = 1: deliverable packets remain beyond max_pkt -- call again with n = 0 and the same flush to drain them; a flush is
+ * complete when it returns more = 0.  n = 0 without flush and with nothing pending is a no-op with *n_pkt = 0.
+ * ofdm_stream_push_sc16 is ofdm_stream_push on ofdm_sc16_widen(in, scale), bit for bit, widened on the device; scale is per push and
+ * follows the rule of the other sc16 entry points.
+ * ofdm_stream_state (all outputs optional): T, the first sample the window keeps, lo, and whether the stream is ended (stream-relative).
+ * OFDM_ERR_INVALID: a NULL handle, n < 0, NULL in_host with n > 0, holdoff < 1, max_symbols <= 0, max_chunk <= 0, first_sample < 0,
+ * max_pkt < 0, a NULL required output, an out_stride below the decode row size, a bad sc16 scale, a push on an ended stream.
+ * OFDM_ERR_UNSUPPORTED: a context whose sync_mode is not OFDM_SYNC_SCHMIDL_COX or a max_chunk beyond 2^40 (at create), T beyond 2^40.
+ * A push that fails leaves the stream undefined until ofdm_stream_reset. */
+typedef struct ofdm_stream ofdm_stream;
+int ofdm_stream_create(ofdm_stream **out, ofdm_ctx *ctx, int32_t max_symbols, int64_t holdoff, int64_t max_chunk, int64_t first_sample);
+int ofdm_stream_destroy(ofdm_stream *s);
+int ofdm_stream_reset(ofdm_stream *s, int64_t first_sample);
+int ofdm_stream_push(ofdm_stream *s, const ofdm_fc32 *in_host, int64_t n, int32_t flush, int64_t max_pkt, uint8_t *out_host,
+                     int64_t out_stride, int32_t *out_len, int32_t *status, int64_t *offset, double *f_delta, float *metric, int64_t *d1,
+                     int64_t *d_hat, int64_t *n_pkt, int32_t *more);
+int ofdm_stream_push_sc16(ofdm_stream *s, const ofdm_sc16 *in_host, int64_t n, float scale, int32_t flush, int64_t max_pkt,
+                          uint8_t *out_host, int64_t out_stride, int32_t *out_len, int32_t *status, int64_t *offset, double *f_delta,
+                          float *metric, int64_t *d1, int64_t *d_hat, int64_t *n_pkt, int32_t *more);
+int ofdm_stream_state(const ofdm_stream *s, int64_t *total, int64_t *kept_from, int64_t *next_lag, int32_t *ended);
+
 /* ------------------------------------------------------------------ loop-back test bench
  * channel (src/channel.rs:33-74), per frame:
  *     y = convolve(tx, CHANNEL)                          tx_len + 63 samples (CHANNEL: the 64 taps of channel.rs:26-31)

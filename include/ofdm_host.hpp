@@ -601,6 +601,73 @@ class Context {
     int window_reps_ = 3;
 };
 
+// EXT-14: a streaming receiver on a context (ofdm_stream_create .. ofdm_stream_state, include/ofdm_hip.h "a streaming receiver").  push()
+// takes the samples as a radio hands them over and returns the packets this push made deliverable -- however the stream is cut, they are,
+// bit for bit, the packets of one ofdm_rx_decode_all_long_host call on the concatenation, each exactly once.  Destroy it before its context.
+class Stream {
+  public:
+    struct Packet { std::vector<uint8_t> bytes; int32_t status = 0; int64_t offset = 0, d1 = 0, d_hat = 0; double f_delta = 0.0; float metric = 0.f; };
+    struct State { int64_t total = 0, kept_from = 0, next_lag = 0; bool ended = false; };
+    Stream(Context &ctx, int32_t max_symbols, int64_t holdoff = 0, int64_t max_chunk = 65536, int64_t first_sample = 0) {
+        check(ofdm_stream_create(&s_, ctx.raw(), max_symbols, holdoff > 0 ? holdoff : ctx.default_holdoff(), max_chunk, first_sample),
+              "ofdm_stream_create");
+        // at least the decode row size of every mode (the RS modes deliver whole 223-byte blocks, the trailing zero block included)
+        row_ = std::max<int64_t>((int64_t)max_symbols * ofdm_bytes_per_symbol(ctx.raw()), 4) + 256;
+    }
+    ~Stream() { if (s_) ofdm_stream_destroy(s_); }
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    std::vector<Packet> push(const ofdm_fc32 *fc, int64_t n, bool flush = false) {
+        return drained([&](Out &o, bool first) {
+            return ofdm_stream_push(s_, first ? fc : nullptr, first ? n : 0, flush, kBatch, o.rows.data(), row_, o.len, o.status, o.offset, o.f_delta,
+                                    o.metric, o.d1, o.d_hat, &o.n, &o.more);
+        });
+    }
+    std::vector<Packet> push_sc16(const ofdm_sc16 *sc, int64_t n, float scale = OFDM_SC16_DEFAULT_SCALE, bool flush = false) {
+        return drained([&](Out &o, bool first) {
+            return first ? ofdm_stream_push_sc16(s_, sc, n, scale, flush, kBatch, o.rows.data(), row_, o.len, o.status, o.offset, o.f_delta, o.metric,
+                                                 o.d1, o.d_hat, &o.n, &o.more)
+                         : ofdm_stream_push(s_, nullptr, 0, flush, kBatch, o.rows.data(), row_, o.len, o.status, o.offset, o.f_delta, o.metric, o.d1,
+                                            o.d_hat, &o.n, &o.more);
+        });
+    }
+    // every remaining detection, a last frame cut by the end of the stream included; the stream is ended until reset()
+    std::vector<Packet> flush() { return push(nullptr, 0, true); }
+    void reset(int64_t first_sample = 0) { check(ofdm_stream_reset(s_, first_sample), "ofdm_stream_reset"); }
+    State state() const {
+        State st; int32_t ended = 0;
+        check(ofdm_stream_state(s_, &st.total, &st.kept_from, &st.next_lag, &ended), "ofdm_stream_state");
+        st.ended = ended != 0;
+        return st;
+    }
+
+  private:
+    static constexpr int64_t kBatch = 64; // packets taken per call; the rest is drained through `more`
+    struct Out {
+        std::vector<uint8_t> rows; int32_t len[kBatch], status[kBatch], more = 0; int64_t offset[kBatch], d1[kBatch], d_hat[kBatch], n = 0;
+        double f_delta[kBatch]; float metric[kBatch];
+    };
+    template <class Call> std::vector<Packet> drained(Call &&call) {
+        std::vector<Packet> out;
+        Out o;
+        o.rows.resize((size_t)(kBatch * row_));
+        bool first = true;
+        do {
+            check(call(o, first), "ofdm_stream_push");
+            first = false;
+            for (int64_t k = 0; k < o.n; ++k) {
+                Packet p;
+                p.status = o.status[k]; p.offset = o.offset[k]; p.d1 = o.d1[k]; p.d_hat = o.d_hat[k]; p.f_delta = o.f_delta[k]; p.metric = o.metric[k];
+                if (p.status == OFDM_FRAME_OK && o.len[k] > 0) p.bytes.assign(o.rows.begin() + k * row_, o.rows.begin() + k * row_ + o.len[k]);
+                out.push_back(std::move(p));
+            }
+        } while (o.more);
+        return out;
+    }
+    ofdm_stream *s_ = nullptr;
+    int64_t row_ = 4;
+};
+
 // One context per (thread, parameter set), created on first use and kept: the reference's free functions are called once per
 // frame (examples/lab3a.rs:24,34, jetson_rx.rs:86), and ofdm_create -- table uploads, stream and workspace set-up -- must not be
 // paid on every call.  The cache is thread_local: its contexts are destroyed (ofdm_destroy: HIP calls) when the THREAD exits.  A host

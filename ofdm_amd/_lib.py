@@ -151,6 +151,14 @@ SIGNATURES = {
                                            C.POINTER(C.c_double), C.POINTER(C.c_float)]),
     "ofdm_rx_decode_long_sc16_host": (C.c_int, [vp, vp, i64, C.c_float, i32, vp, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64),
                                                 C.POINTER(C.c_double), C.POINTER(C.c_float)]),
+    # EXT-14: a streaming receiver (the handle first; ofdm_stream_create: the handle's address, then the context)
+    "ofdm_stream_create": (C.c_int, [C.POINTER(vp), vp, i32, i64, i64, i64]),
+    "ofdm_stream_destroy": (C.c_int, [vp]),
+    "ofdm_stream_reset": (C.c_int, [vp, i64]),
+    "ofdm_stream_push": (C.c_int, [vp, vp, i64, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i32)]),
+    "ofdm_stream_push_sc16": (C.c_int, [vp, vp, i64, C.c_float, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64),
+                                        C.POINTER(i32)]),
+    "ofdm_stream_state": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]),
     "ofdm_hbm_read_probe": (C.c_int, [vp, vp, i64, i32]),
     "ofdm_timer_start": (C.c_int, [vp]),
     "ofdm_timer_stop_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),

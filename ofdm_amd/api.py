@@ -268,6 +268,8 @@ class Context:
 
     def close(self):
         if getattr(self, "h", None):
+            for s in list(getattr(self, "_streams", ())):  # a stream is destroyed before its context (include/ofdm_hip.h)
+                s.close()
             self.lib.ofdm_destroy(self.h)
             self.h = None
 
@@ -1231,6 +1233,17 @@ class Context:
         return {"bytes": out[:n], "len": ln[:n], "status": st[:n], "offset": off[:n], "f_delta": fd[:n], "metric": m[:n], "d1": d1[:n],
                 "d_hat": dh[:n], "lag_lo": lo[:n], "next_lag_lo": int(lo[n]), "more": bool(more.value)}
 
+    def stream(self, max_symbols: int, holdoff: Optional[int] = None, max_chunk: int = 65536, first_sample: int = 0) -> "Stream":
+        """ofdm_stream_create (EXT-14): a streaming receiver on this context -- push chunks as a radio hands them over, get every packet
+        exactly once, bit for bit the packets of decode_all_host on the concatenation.  holdoff None: default_holdoff()."""
+        import weakref
+
+        s = Stream(self, max_symbols, self.default_holdoff() if holdoff is None else holdoff, max_chunk, first_sample)
+        if not hasattr(self, "_streams"):
+            self._streams = weakref.WeakSet()
+        self._streams.add(s)
+        return s
+
     # ---------------------------------------------------------------- host buffers (H2D / kernels / D2H pipelined in the library)
     def decode_host(self, frames: np.ndarray, max_symbols: int, n_lags: int = 0, frame_len: Optional[int] = None,
                     chunk_frames: int = 0, out: Optional[dict] = None):
@@ -1288,6 +1301,115 @@ class Context:
         ms = C.c_float()
         self._ck(self.lib.ofdm_timer_stop_ms(self.h, C.byref(ms)), "timer_stop")
         return float(ms.value)
+
+
+class Stream:
+    """`ofdm_stream` (EXT-14, include/ofdm_hip.h "a streaming receiver"): Context.stream(...) makes one.  However the samples are cut into
+    pushes, the packets delivered are those of Context.decode_all_host on the concatenation, each exactly once; packet k arrives with the
+    first push after which d1_k + horizon samples are there, or with the flush.  Close it before its context."""
+    FIELDS = ("len", "status", "offset", "f_delta", "metric", "d1", "d_hat")
+
+    def __init__(self, ctx: Context, max_symbols: int, holdoff: int, max_chunk: int, first_sample: int = 0):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.max_symbols, self.holdoff, self.max_chunk = int(max_symbols), int(holdoff), int(max_chunk)
+        h = C.c_void_p()
+        ctx._ck(self.lib.ofdm_stream_create(C.byref(h), ctx.h, self.max_symbols, self.holdoff, self.max_chunk, int(first_sample)),
+                "ofdm_stream_create")
+        self.h = h
+        self.row_bytes = ctx.decode_row_bytes(self.max_symbols)
+        self.horizon = ctx.params.sync_window_reps * ctx.S + (10 + self.max_symbols) * ctx.S + 2
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ofdm_stream_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _call(self, samples, sc16_scale, flush: bool, max_pkt: int) -> dict:
+        cap = max(int(max_pkt), 1)
+        ob = max(self.row_bytes, 1)
+        out = np.zeros((cap, ob), np.uint8)
+        ln, st = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        off, d1, dh = np.zeros(cap, np.int64), np.zeros(cap, np.int64), np.zeros(cap, np.int64)
+        fd, m = np.zeros(cap, np.float64), np.zeros(cap, np.float32)
+        nd, more = C.c_int64(), C.c_int32()
+        tail = (int(bool(flush)), int(max_pkt), _host(out), ob, _host(ln), _host(st), _host(off), _host(fd), _host(m), _host(d1), _host(dh),
+                C.byref(nd), C.byref(more))
+        if samples is None:
+            rc = self.lib.ofdm_stream_push(self.h, None, 0, *tail)
+        elif np.asarray(samples).dtype == np.int16:
+            a = _sc16_host(samples, "Stream.push").reshape(-1, 2)
+            if sc16_scale is None:
+                raise OfdmError("Stream.push: int16 samples need sc16_scale=")
+            rc = self.lib.ofdm_stream_push_sc16(self.h, _host(a), a.shape[0], float(sc16_scale), *tail)
+        else:
+            x = np.ascontiguousarray(samples, dtype=np.complex64).reshape(-1)
+            rc = self.lib.ofdm_stream_push(self.h, _host(x), x.size, *tail)
+        self.ctx._ck(rc, "ofdm_stream_push")
+        n = int(nd.value)
+        return {"bytes": out[:n], "len": ln[:n], "status": st[:n], "offset": off[:n], "f_delta": fd[:n], "metric": m[:n], "d1": d1[:n],
+                "d_hat": dh[:n], "more": bool(more.value)}
+
+    def push(self, samples, flush: bool = False, max_pkt: int = 64, sc16_scale: Optional[float] = None) -> dict:
+        """ofdm_stream_push / ofdm_stream_push_sc16: a complex64 array goes to the fc32 form, an int16 array of shape [n, 2] with
+        sc16_scale= to the sc16 form; None (or an empty array) pushes nothing.  -> the dict of numpy arrays decode_all_host returns
+        (bytes, len, status, offset, f_delta, metric, d1, d_hat per packet delivered by THIS push) and more: packets remain beyond max_pkt
+        -- push(None, flush, max_pkt) drains them."""
+        return self._call(samples, sc16_scale, flush, max_pkt)
+
+    def push_all(self, samples, flush: bool = False, sc16_scale: Optional[float] = None, max_pkt: int = 64) -> dict:
+        """push, then drained through `more`: everything this push made deliverable, in one dict"""
+        parts = [self.push(samples, flush, max_pkt, sc16_scale)]
+        while parts[-1]["more"]:
+            parts.append(self.push(None, flush, max_pkt))
+        res = {k: np.concatenate([p[k] for p in parts]) for k in ("bytes",) + self.FIELDS}
+        res["more"] = False
+        return res
+
+    def flush(self, max_pkt: int = 64) -> dict:
+        """every remaining detection, a last frame cut by the end of the stream included; the stream is ended until reset()"""
+        return self.push_all(None, True, max_pkt=max_pkt)
+
+    def reset(self, first_sample: int = 0):
+        self.ctx._ck(self.lib.ofdm_stream_reset(self.h, int(first_sample)), "ofdm_stream_reset")
+
+    def state(self) -> dict:
+        """ofdm_stream_state -> total (samples pushed), kept_from (first sample the window keeps), next_lag (where the walk resumes),
+        ended; all stream-relative"""
+        t, k, lo, e = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int32()
+        self.ctx._ck(self.lib.ofdm_stream_state(self.h, C.byref(t), C.byref(k), C.byref(lo), C.byref(e)), "ofdm_stream_state")
+        return {"total": int(t.value), "kept_from": int(k.value), "next_lag": int(lo.value), "ended": bool(e.value)}
+
+
+def _packet_dicts(res: dict):
+    for k in range(len(res["status"])):
+        ok = int(res["status"][k]) == FRAME_OK
+        yield {"bytes": bytes(res["bytes"][k, : max(int(res["len"][k]), 0)]) if ok else b"", "status": int(res["status"][k]),
+               "offset": int(res["offset"][k]), "f_delta": float(res["f_delta"][k]), "metric": float(res["metric"][k]),
+               "d1": int(res["d1"][k]), "d_hat": int(res["d_hat"][k])}
+
+
+def receive_stream(chunks, max_symbols: int, guard_bands: bool = False, modulation: int = BPSK, n_fft: int = 64, ecc: int = ECC_NONE,
+                   holdoff: Optional[int] = None, max_chunk: int = 65536, first_sample: int = 0, sc16_scale: Optional[float] = None, **kw):
+    """A generator over an iterable of chunks (complex64 arrays, or int16 [n, 2] arrays with sc16_scale=): yields one dict per packet
+    (bytes, status, offset, f_delta, metric, d1, d_hat) as soon as the stream commits it, and flushes when the iterable ends."""
+    ctx = _ctx(n_fft, modulation, guard_bands, ecc, **kw)
+    with ctx.stream(max_symbols, holdoff, max_chunk, first_sample) as s:
+        for chunk in chunks:
+            yield from _packet_dicts(s.push_all(chunk, sc16_scale=sc16_scale))
+        yield from _packet_dicts(s.flush())
 
 
 # -------------------------------------------------------------------- reference-shaped free functions

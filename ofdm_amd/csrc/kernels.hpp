@@ -54,6 +54,7 @@ struct Tuning {
     int scan_mark_only = 0;        // EXT-12: ofdm_sc_scan_long launches k_sc_mark alone and reports no detection: the kernel's time on its own
     int packets_chunk_rows = 0;    // EXT-13: packets per k_gather_rows + chain step of ofdm_rx_decode_packets (0 = as many as keep the gathered rows within 256 MiB)
     int packets_gather_only = 0;   // EXT-13: ofdm_rx_decode_packets launches k_pkt_rows + k_gather_rows alone and delivers nothing: the kernel's time on its own
+    int stream_scan_cap = 0;       // EXT-14: detections per scan + decode round of ofdm_stream_push (0 = 256; the tests force 2, so that the round loop runs)
 };
 inline const Tuning &tuning_or_default(const Tuning *t) { static const Tuning d; return t ? *t : d; }
 
@@ -460,6 +461,19 @@ hipError_t run_rx_prepare_rows(long long n_rows, const int32_t *d_hat, double *f
 // offset[k] = row_start[k] + row_offset[k] (0 + row_offset[k] where status[k] is OFDM_FRAME_BADTIMING)
 hipError_t run_pkt_finish(long long n_det, const long long *row_start, const int32_t *row_offset, const int32_t *status, long long *offset,
                           hipStream_t st);
+// ---- EXT-14 the window of a streaming receiver (ofdm_stream_push; kernels_stream.hip, definition: tests/stream_ref.py).
+// k_stream_ingest<fc32> / <sc16>, one launch: win[i] = carry[i] for i < keep, win[keep + j] = chunk[j] (sc16: widened by `scale` as
+// k_sc16_widen widens) for j < n; nothing behind win[keep + n) is written.  carry, win and chunk are 16-byte aligned and do not overlap.
+struct StreamIngestParams {
+    const Tuning *tune = nullptr;
+    Trace *trace = nullptr;
+    const float2 *carry = nullptr;       // the old window from its first kept sample on
+    long long keep = 0, n = 0;
+    const void *chunk = nullptr;         // n samples: float2 (fc32) or int16 pairs (sc16)
+    float scale = 0.f;                   // sc16 only
+    float2 *win = nullptr;               // the new window
+};
+hipError_t run_stream_ingest(const StreamIngestParams &p, bool sc16, int num_cu, hipStream_t st);
 // base (optional): per-pair sample offset added to the pair's start; status (optional): pairs with status != 0 get 0
 hipError_t run_freq_correction(const float2 *in, long long n_pairs, long long stride, long long right_offset, int L,
                                double *f_delta, hipStream_t st, const int32_t *base = nullptr, const int32_t *status = nullptr);

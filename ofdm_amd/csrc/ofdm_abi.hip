@@ -2011,9 +2011,10 @@ static const int64_t kPacketsMaxSamples = (int64_t)1 << 40; // ofdm_sc_scan_long
 
 int ofdm_abi_rx_decode_packets(ofdm_ctx *c, const float2 *in, int64_t n, int64_t n_det, const int64_t *d_hat, const double *f_delta,
                                const float *metric, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len, int32_t *status,
-                               int64_t *offset, double *f_delta_out, float *metric_out) {
+                               int64_t *offset, double *f_delta_out, float *metric_out, int64_t n_whole) {
     const int S = c->S();
-    const int64_t R = std::min<int64_t>((10 + (int64_t)max_symbols) * S + 2, (n + 1) & ~(int64_t)1);
+    // (n_whole > n: `in` is the tail of a capture of n_whole samples -- a stream's window -- and the rows get the length that capture's rows have)
+    const int64_t R = std::min<int64_t>((10 + (int64_t)max_symbols) * S + 2, (std::max(n, n_whole) + 1) & ~(int64_t)1);
     int64_t chunk = c->tune.packets_chunk_rows > 0 ? c->tune.packets_chunk_rows : kPacketRowsBytes / (R * (int64_t)sizeof(float2));
     chunk = std::min(std::max<int64_t>(chunk, 1), n_det);
     const size_t nd = (size_t)n_det;
@@ -2071,7 +2072,7 @@ int ofdm_rx_decode_packets(ofdm_ctx *c, const ofdm_fc32 *in_dev, int64_t n_sampl
     // (the row-size rule of ofdm_rx_decode_batch is checked by the chain before its first launch, but behind the upload: check it here)
     if (out_stride < decode_row_bytes(c, max_symbols)) return OFDM_ERR_INVALID;
     return ofdm_abi_rx_decode_packets(c, reinterpret_cast<const float2 *>(in_dev), n_samples, n_det, d_hat, f_delta, metric, max_symbols, out_dev,
-                                      out_stride, out_len_dev, status_dev, offset_dev, f_delta_dev, metric_dev);
+                                      out_stride, out_len_dev, status_dev, offset_dev, f_delta_dev, metric_dev, 0);
 }
 
 // CHANNEL (src/channel.rs:26-31): 64 taps, the non-zero ones are 8..16 and 18

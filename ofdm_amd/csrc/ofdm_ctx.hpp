@@ -292,8 +292,10 @@ __attribute__((visibility("hidden"))) int ofdm_abi_sc_run(ofdm_ctx *c, const flo
 // ofdm_rx_decode_batch behind its entry scope: the argument checks and the chain of d, appended to the context's trace (the long
 // capture calls run it on a sub-capture, with the chain's own search or, d.known, with the slice search's timing)
 __attribute__((visibility("hidden"))) int ofdm_abi_rx_decode(ofdm_ctx *c, const DecodeCall &d);
-// EXT-13 (ofdm_rx_decode_packets behind its argument checks and its entry scope: ofdm_rx_decode_all_long_host runs it behind its scan)
+// EXT-13 (ofdm_rx_decode_packets behind its argument checks and its entry scope: ofdm_rx_decode_all_long_host runs it behind its scan).
+// n_whole (0: n): the samples of the capture whose last n samples `in` holds (EXT-14: a stream's window).  Only the row length R is taken
+// from it, so that a window's rows are, zeros included, the rows of the whole capture
 __attribute__((visibility("hidden"))) int ofdm_abi_rx_decode_packets(ofdm_ctx *c, const float2 *in, int64_t n, int64_t n_det, const int64_t *d_hat,
                     const double *f_delta, const float *metric, int32_t max_symbols, uint8_t *out, int64_t out_stride, int32_t *out_len,
-                    int32_t *status, int64_t *offset, double *f_delta_out, float *metric_out);
+                    int32_t *status, int64_t *offset, double *f_delta_out, float *metric_out, int64_t n_whole);
 }

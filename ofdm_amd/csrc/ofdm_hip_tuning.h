@@ -45,6 +45,9 @@
 //                         256 MiB; the tests force chunks of 2 rows)
 //     packets_gather_only ofdm_rx_decode_packets launches k_pkt_rows + k_gather_rows alone and delivers nothing: the gather's time on its
 //                         own (tools/bench_packets.py)
+//   a streaming receiver (EXT-14)
+//     stream_scan_cap     detections per scan + decode round of ofdm_stream_push (0 or above 256 = 256; the tests force 2, so that a push
+//                         walks several rounds and resumes each behind the last detection of the one before)
 //   Schmidl-Cox threshold in full precision (handled by name in ofdm_abi.hip, 64 bits: not in the table below)
 //     sync_threshold_bits the bit pattern of a double in (0, 1] that replaces ofdm_params.sync_threshold (a float: 6e-8 apart) in every
 //                         search of the context; 0 = the float again.  The margin tests set the threshold within 1e-12 of a lag's own metric
@@ -101,6 +104,7 @@ OFDM_TUNE_KEY("no_txframe64_sc16", no_txframe64_sc16, false)
 OFDM_TUNE_KEY("scan_mark_only", scan_mark_only, false)
 OFDM_TUNE_KEY("packets_chunk_rows", packets_chunk_rows, false)
 OFDM_TUNE_KEY("packets_gather_only", packets_gather_only, false)
+OFDM_TUNE_KEY("stream_scan_cap", stream_scan_cap, false)
 OFDM_TUNE_KEY("debug_demod64", debug_demod64, true)
 OFDM_TUNE_KEY("debug_sc", debug_sc, true)
 OFDM_TUNE_KEY("debug_tx", debug_tx, true)

@@ -895,7 +895,7 @@ int ofdm_rx_decode_all_long_host(ofdm_ctx *c, const ofdm_fc32 *in_host, int64_t 
         const PacketsBlock o(hp->d_out[0].p, nd, row);
         // (the dispatch string is the scan's kernels, then the decode's)
         rc = ofdm_abi_rx_decode_packets(c, x, n_samples, (int64_t)nd, d_hat, f_delta, metric, max_symbols, o.rows, out_stride, o.len, o.status,
-                                        o.offset, o.f_delta, o.metric);
+                                        o.offset, o.f_delta, o.metric, 0);
         if (rc) return rc;
         if (offset) HIP_TRY(c, hipMemcpyAsync(offset, o.offset, nd * sizeof(*offset), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipMemcpyAsync(f_delta, o.f_delta, nd * sizeof(*f_delta), hipMemcpyDeviceToHost, c->stream));
@@ -952,6 +952,262 @@ int ofdm_rx_decode_long_sc16_host(ofdm_ctx *c, const ofdm_sc16 *in_host, int64_t
                                             static_cast<uint8_t *>(hp->d_out[0].p), out_cap, out_len, status, offset, f_delta, metric);
         return rc ? rc : long_row_back(c, hp, out_host, out_len, status);
     });
+}
+
+} // extern "C"
+
+// ---- EXT-14: a streaming receiver (include/ofdm_hip.h, "a streaming receiver"; numpy restatement and the proofs: tests/stream_ref.py,
+// tests/test_stream_cpu.py).  The stream keeps the last samples of everything pushed in one of two device windows and, per piece of a
+// push: k_stream_ingest (the carry and the new chunk into the other window, one launch), ofdm_sc_scan_long's kernels over the window
+// from the lag the walk resumes at, ofdm_rx_decode_packets' chain over the detections the horizon commits.  What it allocates is its
+// own (no workspace role, no slot of the host pipe); the scan and the decode use the context's workspaces as every call does.
+struct ofdm_stream {
+    ofdm_ctx *c = nullptr;
+    int32_t max_symbols = 0;
+    int64_t holdoff = 0, max_chunk = 0, first = 0;
+    int64_t H = 0;              // the horizon W + (10 + max_symbols) S + 2
+    int64_t win_cap = 0;        // samples a window holds: H + L + b + 2 + max_chunk
+    int64_t T = 0;              // samples pushed
+    int64_t B = 0;              // the stream index of win[cur][0]; even
+    int64_t keep_from = 0;      // where the next ingest starts its carry (B <= keep_from <= T, even)
+    int64_t lo = 0;             // the lag the walk resumes at
+    int cur = 0;
+    bool ended = false;
+    float2 *win[2] = {nullptr, nullptr};
+    void *stage = nullptr;      // one chunk as it was pushed (max_chunk fc32 samples)
+    void *res_dev = nullptr, *res_pin = nullptr; // PacketsBlock of kStreamScanCap rows, device and pinned
+    size_t row = 0;             // bytes of a result row there
+    int64_t need = 0;           // decode_row_bytes: what a caller's row receives
+    std::vector<int64_t> d1, d_hat; // one scan round, window-relative
+    std::vector<double> f_delta;
+    std::vector<float> metric;
+    // decoded and not yet handed out
+    struct Packet { int64_t offset, d1, d_hat; double f_delta; float metric; int32_t len, status; };
+    std::vector<Packet> q;
+    std::vector<uint8_t> q_rows; // `need` bytes a packet
+    size_t q_head = 0;
+};
+
+namespace {
+
+constexpr int64_t kStreamScanCap = 256; // detections per scan + decode round (the laboratory key stream_scan_cap lowers it)
+
+void stream_free(ofdm_stream *s) {
+    for (float2 *&w : s->win) { if (w) hipFree(w); w = nullptr; }
+    if (s->stage) hipFree(s->stage);
+    if (s->res_dev) hipFree(s->res_dev);
+    if (s->res_pin) hipHostFree(s->res_pin);
+    s->stage = s->res_dev = s->res_pin = nullptr;
+}
+
+int stream_dev_alloc(ofdm_ctx *c, void **p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) { c->last_hip = (int)e; *p = nullptr; return OFDM_ERR_NOMEM; }
+    return c->ws_poison ? poison_fill_dev(c, *p, bytes, c->ws_poison & 0xFF) : OFDM_OK;
+}
+
+void stream_rewind(ofdm_stream *s, int64_t first_sample) {
+    s->first = first_sample;
+    s->T = s->B = s->keep_from = s->lo = 0;
+    s->ended = false;
+    s->q.clear(); s->q_rows.clear(); s->q_head = 0;
+}
+
+// Scan the window from `lo` on and decode what the horizon commits (flush: everything), round by round of at most `cap` detections;
+// leaves s->lo where the next piece resumes.  *synced: the context's stream was synchronised behind the piece's last launch
+int stream_scan_decode(ofdm_stream *s, bool flush, bool *synced) {
+    ofdm_ctx *c = s->c;
+    const float2 *win = s->win[s->cur];
+    const int64_t n_w = s->T - s->B;
+    const int64_t L = c->S(), W = c->prm.sync_window_reps * L, valid = s->T - W - L + 1;
+    const int64_t cap = c->tune.stream_scan_cap > 0 ? std::min<int64_t>(c->tune.stream_scan_cap, kStreamScanCap) : kStreamScanCap;
+    int rc;
+    for (int round = 0;; round++) {
+        if (valid <= 0 || s->lo >= valid) return OFDM_OK; // no lag to look at (sc_scan_dev would say the same without a launch)
+        const Trace::Mute later(c->trace, round > 0); // the dispatch string names what a round ran, once
+        int64_t nd = 0;
+        int32_t more = 0;
+        if ((rc = sc_scan_dev(c, win, n_w, s->lo - s->B, 0, s->holdoff, cap, s->d1.data(), s->d_hat.data(), s->f_delta.data(), s->metric.data(),
+                              &nd, &more))) return rc;
+        *synced = true;
+        int64_t nc = 0; // the committed ones: a detection that is not committed defers itself and every later one
+        while (nc < nd && (flush || s->B + s->d1[nc] + s->H <= s->T)) nc++;
+        if (nc) {
+            const PacketsBlock o(s->res_dev, (size_t)kStreamScanCap, s->row), h(s->res_pin, (size_t)kStreamScanCap, s->row);
+            const size_t k = (size_t)nc;
+            // (f_delta and metric hold the scan's rows: the decode's input; its outputs go to the pinned block)
+            if ((rc = ofdm_abi_rx_decode_packets(c, win, n_w, nc, s->d_hat.data(), s->f_delta.data(), s->metric.data(), s->max_symbols, o.rows,
+                                                 (int64_t)s->row, o.len, o.status, o.offset, o.f_delta, o.metric, s->T))) return rc;
+            HIP_TRY(c, hipMemcpyAsync(h.offset, o.offset, k * sizeof(*o.offset), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(h.f_delta, o.f_delta, k * sizeof(*o.f_delta), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(h.len, o.len, k * sizeof(*o.len), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(h.status, o.status, k * sizeof(*o.status), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(h.metric, o.metric, k * sizeof(*o.metric), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(h.rows, o.rows, k * s->row, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            const size_t at = s->q_rows.size(), need = (size_t)s->need;
+            s->q_rows.resize(at + k * need);
+            for (size_t i = 0; i < k; i++) {
+                // window-relative -> stream-relative -> reported (a BADTIMING offset is the row's own, as in ofdm_rx_decode_long)
+                const int64_t base = s->B + s->first;
+                s->q.push_back({(h.status[i] == OFDM_FRAME_BADTIMING ? s->first : base) + h.offset[i], base + s->d1[i], base + s->d_hat[i],
+                                h.f_delta[i], h.metric[i], h.len[i], h.status[i]});
+                if (need) std::memcpy(s->q_rows.data() + at + i * need, h.rows + i * s->row, need);
+            }
+        }
+        if (nc < nd) { s->lo = s->B + s->d1[nc]; return OFDM_OK; } // deferred: the first crossing at or after it is itself
+        if (nd) s->lo = s->B + s->d1[nd - 1] + s->holdoff;
+        if (!more) { s->lo = std::max(s->lo, valid); return OFDM_OK; }
+    }
+}
+
+// One piece (m <= max_chunk samples at `in`, ss bytes each) through ingest, scan and decode
+int stream_piece(ofdm_stream *s, const void *in, int64_t m, size_t ss, bool sc16, float scale, bool flush) {
+    ofdm_ctx *c = s->c;
+    bool synced = false;
+    int rc;
+    if (m > 0) {
+        const int64_t drop = s->keep_from - s->B, keep = s->T - s->keep_from;
+        if (drop < 0 || (drop & 1) || keep < 0 || keep + m > s->win_cap) return OFDM_ERR_INVALID; // the retention bound (tests/test_stream_cpu.py): never
+        HIP_TRY(c, hipMemcpyAsync(s->stage, in, (size_t)m * ss, hipMemcpyHostToDevice, c->stream));
+        StreamIngestParams p;
+        p.tune = &c->tune; p.trace = &c->trace;
+        p.carry = s->win[s->cur] + drop; p.keep = keep; p.n = m; p.chunk = s->stage; p.scale = scale; p.win = s->win[s->cur ^ 1];
+        HIP_TRY(c, run_stream_ingest(p, sc16, c->num_cu, c->stream));
+        s->cur ^= 1;
+        s->B = s->keep_from;
+        s->T += m;
+    }
+    rc = stream_scan_decode(s, flush, &synced);
+    if (!rc && !synced) { // a window without a lag to scan: the upload still reads the caller's memory
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { c->last_hip = (int)e; rc = OFDM_ERR_HIP; }
+    }
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    // retain from (lo - L - b) & ~1, clamped to what the window holds: B stays even, and every later row start lies at or behind it
+    const int64_t from = std::min(std::max<int64_t>(s->lo - c->S() - c->prm.sync_backoff, s->B), s->T) & ~(int64_t)1;
+    s->keep_from = std::max(from, s->B);
+    return OFDM_OK;
+}
+
+int stream_push(ofdm_stream *s, const void *in, int64_t n, size_t ss, bool sc16, float scale, int32_t flush, int64_t max_pkt, uint8_t *out,
+                int64_t out_stride, int32_t *out_len, int32_t *status, int64_t *offset, double *f_delta, float *metric, int64_t *d1, int64_t *d_hat,
+                int64_t *n_pkt, int32_t *more) {
+    if (!s || !s->c || !n_pkt || n < 0 || max_pkt < 0 || (n > 0 && !in)) return OFDM_ERR_INVALID;
+    if (max_pkt && (!out || !out_len || !status || !f_delta || !metric || !d_hat)) return OFDM_ERR_INVALID;
+    if (out_stride < s->need || (sc16 && !sc16_scale_ok(scale))) return OFDM_ERR_INVALID;
+    *n_pkt = 0;
+    if (more) *more = 0;
+    const bool pending = s->q_head < s->q.size();
+    if (s->ended && (n > 0 || !pending)) return OFDM_ERR_INVALID; // only the drain of a flush goes on behind it
+    if (s->T + n > kScanMaxSamples) return OFDM_ERR_UNSUPPORTED;
+    ofdm_ctx *c = s->c;
+    if (!s->ended && (n > 0 || flush)) {
+        EntryScope scope(c);
+        int64_t done = 0;
+        do {
+            const int64_t m = std::min(n - done, s->max_chunk);
+            const bool last = done + m == n;
+            const Trace::Mute later(c->trace, done > 0); // the dispatch string names what a piece ran, once
+            const int rc = stream_piece(s, static_cast<const char *>(in) + (size_t)done * ss, m, ss, sc16, scale, flush && last);
+            if (rc) return rc;
+            done += m;
+        } while (done < n);
+        if (flush) s->ended = true;
+    }
+    const int64_t k = std::min<int64_t>(max_pkt, (int64_t)(s->q.size() - s->q_head));
+    for (int64_t i = 0; i < k; i++) {
+        const ofdm_stream::Packet &p = s->q[s->q_head + (size_t)i];
+        out_len[i] = p.len; status[i] = p.status; f_delta[i] = p.f_delta; metric[i] = p.metric; d_hat[i] = p.d_hat;
+        if (offset) offset[i] = p.offset;
+        if (d1) d1[i] = p.d1;
+        if (s->need) std::memcpy(out + i * out_stride, s->q_rows.data() + (s->q_head + (size_t)i) * (size_t)s->need, (size_t)s->need);
+    }
+    s->q_head += (size_t)k;
+    *n_pkt = k;
+    if (s->q_head == s->q.size()) { s->q.clear(); s->q_rows.clear(); s->q_head = 0; }
+    else if (more) *more = 1;
+    return OFDM_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int ofdm_stream_create(ofdm_stream **out, ofdm_ctx *c, int32_t max_symbols, int64_t holdoff, int64_t max_chunk, int64_t first_sample) {
+    if (out) *out = nullptr;
+    if (!out || !c || max_symbols <= 0 || holdoff < 1 || max_chunk <= 0 || first_sample < 0) return OFDM_ERR_INVALID;
+    if (c->prm.sync_mode != OFDM_SYNC_SCHMIDL_COX || max_chunk > kScanMaxSamples) return OFDM_ERR_UNSUPPORTED;
+    ofdm_stream *s = new (std::nothrow) ofdm_stream();
+    if (!s) return OFDM_ERR_NOMEM;
+    const int64_t L = c->S(), W = c->prm.sync_window_reps * L;
+    s->c = c; s->max_symbols = max_symbols; s->holdoff = holdoff; s->max_chunk = max_chunk;
+    s->H = W + (10 + (int64_t)max_symbols) * L + 2;
+    s->win_cap = s->H + L + c->prm.sync_backoff + 2 + max_chunk;
+    s->need = decode_row_bytes(c, max_symbols);
+    s->row = round_up((size_t)std::max<int64_t>(s->need, 16), 16);
+    stream_rewind(s, first_sample);
+    DeviceGuard dev_guard(c->device);
+    auto build = [&]() -> int {
+        int rc;
+        HostPipe *hp;
+        if ((rc = pipe_get(c, &hp))) return rc; // the scan's pinned rows live there
+        const size_t win_bytes = (size_t)s->win_cap * sizeof(float2) + 256, res_bytes = PacketsBlock(nullptr, (size_t)kStreamScanCap, s->row).bytes;
+        for (float2 *&w : s->win)
+            if ((rc = stream_dev_alloc(c, reinterpret_cast<void **>(&w), win_bytes))) return rc;
+        if ((rc = stream_dev_alloc(c, &s->stage, (size_t)max_chunk * sizeof(float2) + 256))) return rc;
+        if ((rc = stream_dev_alloc(c, &s->res_dev, res_bytes))) return rc;
+        const hipError_t e = hipHostMalloc(&s->res_pin, res_bytes, hipHostMallocDefault);
+        if (e != hipSuccess) { c->last_hip = (int)e; s->res_pin = nullptr; return OFDM_ERR_NOMEM; }
+        if (c->ws_poison) std::memset(s->res_pin, c->ws_poison & 0xFF, res_bytes);
+        s->d1.resize((size_t)kStreamScanCap); s->d_hat.resize((size_t)kStreamScanCap);
+        s->f_delta.resize((size_t)kStreamScanCap); s->metric.resize((size_t)kStreamScanCap);
+        return OFDM_OK;
+    };
+    const int rc = build();
+    if (rc) { stream_free(s); delete s; return rc; }
+    *out = s;
+    return OFDM_OK;
+}
+
+int ofdm_stream_destroy(ofdm_stream *s) {
+    if (!s || !s->c) return OFDM_ERR_INVALID;
+    DeviceGuard dev_guard(s->c->device);
+    const hipError_t e = hipStreamSynchronize(s->c->stream);
+    stream_free(s);
+    const int rc = e == hipSuccess ? OFDM_OK : OFDM_ERR_HIP;
+    if (rc) s->c->last_hip = (int)e;
+    delete s;
+    return rc;
+}
+
+int ofdm_stream_reset(ofdm_stream *s, int64_t first_sample) {
+    if (!s || first_sample < 0) return OFDM_ERR_INVALID;
+    stream_rewind(s, first_sample);
+    return OFDM_OK;
+}
+
+int ofdm_stream_push(ofdm_stream *s, const ofdm_fc32 *in_host, int64_t n, int32_t flush, int64_t max_pkt, uint8_t *out_host, int64_t out_stride,
+                     int32_t *out_len, int32_t *status, int64_t *offset, double *f_delta, float *metric, int64_t *d1, int64_t *d_hat, int64_t *n_pkt,
+                     int32_t *more) {
+    return stream_push(s, in_host, n, sizeof(ofdm_fc32), false, 0.f, flush, max_pkt, out_host, out_stride, out_len, status, offset, f_delta, metric,
+                       d1, d_hat, n_pkt, more);
+}
+
+int ofdm_stream_push_sc16(ofdm_stream *s, const ofdm_sc16 *in_host, int64_t n, float scale, int32_t flush, int64_t max_pkt, uint8_t *out_host,
+                          int64_t out_stride, int32_t *out_len, int32_t *status, int64_t *offset, double *f_delta, float *metric, int64_t *d1,
+                          int64_t *d_hat, int64_t *n_pkt, int32_t *more) {
+    return stream_push(s, in_host, n, sizeof(ofdm_sc16), true, scale, flush, max_pkt, out_host, out_stride, out_len, status, offset, f_delta, metric,
+                       d1, d_hat, n_pkt, more);
+}
+
+int ofdm_stream_state(const ofdm_stream *s, int64_t *total, int64_t *kept_from, int64_t *next_lag, int32_t *ended) {
+    if (!s) return OFDM_ERR_INVALID;
+    if (total) *total = s->T;
+    if (kept_from) *kept_from = s->keep_from;
+    if (next_lag) *next_lag = s->lo;
+    if (ended) *ended = s->ended ? 1 : 0;
+    return OFDM_OK;
 }
 
 } // extern "C"
