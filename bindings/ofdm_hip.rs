@@ -11,6 +11,8 @@ use std::os::raw::{c_char, c_int, c_void};
 pub struct ofdm_ctx { _private: [u8; 0] }
 #[repr(C)]
 pub struct ofdm_stream { _private: [u8; 0] }
+#[repr(C)]
+pub struct ofdm_dcblock { _private: [u8; 0] }
 
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -328,6 +330,18 @@ extern "C" {
                                  out_stride: i64, out_len: *mut i32, status: *mut i32, offset: *mut i64, f_delta: *mut f64, metric: *mut f32,
                                  d1: *mut i64, d_hat: *mut i64, n_pkt: *mut i64, more: *mut i32) -> c_int;
     pub fn ofdm_stream_state(s: *const ofdm_stream, total: *mut i64, kept_from: *mut i64, next_lag: *mut i64, ended: *mut i32) -> c_int;
+    // EXT-15: a DC blocker.  Host definition; a handle on device buffers (its own type first); the stream option
+    pub fn ofdm_dc_block_default(n_fft: i32, cp_len: i32) -> c_int;
+    pub fn ofdm_dc_block(input: *const ofdm_fc32, n: i64, blocks: i32, out: *mut ofdm_fc32) -> c_int;
+    pub fn ofdm_dc_block_sc16(input: *const ofdm_sc16, n: i64, scale: f32, blocks: i32, out: *mut ofdm_fc32) -> c_int;
+    pub fn ofdm_dcblock_create(out: *mut *mut ofdm_dcblock, ctx: *mut ofdm_ctx, blocks: i32, max_chunk: i64) -> c_int;
+    pub fn ofdm_dcblock_destroy(f: *mut ofdm_dcblock) -> c_int;
+    pub fn ofdm_dcblock_reset(f: *mut ofdm_dcblock) -> c_int;
+    pub fn ofdm_dcblock_push(f: *mut ofdm_dcblock, in_dev: *const ofdm_fc32, n: i64, out_dev: *mut ofdm_fc32) -> c_int;
+    pub fn ofdm_dcblock_push_sc16(f: *mut ofdm_dcblock, in_dev: *const ofdm_sc16, n: i64, scale: f32, out_dev: *mut ofdm_fc32) -> c_int;
+    pub fn ofdm_dcblock_state(f: *const ofdm_dcblock, total: *mut i64, blocks: *mut i32) -> c_int;
+    pub fn ofdm_stream_set_dc_block(s: *mut ofdm_stream, blocks: i32) -> c_int;
+    pub fn ofdm_stream_get_dc_block(s: *const ofdm_stream, blocks: *mut i32) -> c_int;
     pub fn ofdm_timer_start(ctx: *mut ofdm_ctx) -> c_int;
     pub fn ofdm_timer_stop_ms(ctx: *mut ofdm_ctx, elapsed_ms: *mut f32) -> c_int;
 }
@@ -397,8 +411,57 @@ impl<'a> Stream<'a> {
     }
     pub fn flush(&mut self) -> anyhow::Result<Vec<StreamPacket>> { self.push(&[], true) }
     pub fn reset(&mut self, first_sample: i64) -> anyhow::Result<()> { check(unsafe { ofdm_stream_reset(self.raw, first_sample) }, "ofdm_stream_reset") }
+    /// EXT-15: the DC blocker in front of the window (0 = off); only before the first sample or right after `reset`, which keeps the setting
+    pub fn set_dc_block(&mut self, blocks: i32) -> anyhow::Result<()> { check(unsafe { ofdm_stream_set_dc_block(self.raw, blocks) }, "ofdm_stream_set_dc_block") }
+    pub fn dc_block(&self) -> anyhow::Result<i32> {
+        let mut m = 0i32;
+        check(unsafe { ofdm_stream_get_dc_block(self.raw, &mut m) }, "ofdm_stream_get_dc_block")?;
+        Ok(m)
+    }
 }
 impl<'a> Drop for Stream<'a> { fn drop(&mut self) { unsafe { ofdm_stream_destroy(self.raw); } } }
+
+/// EXT-15: a DC blocker on device buffers (include/ofdm_hip.h, "a DC blocker in front of detection").  Every sample leaves less the mean of
+/// the `blocks` complete 64-sample blocks in front of its own block; the pushes of one filter, concatenated, equal `ofdm_dc_block` of the
+/// concatenated inputs bit for bit.  `input` and `out` are device pointers that do not overlap.  Borrows its context.
+pub struct DcBlock<'a> { raw: *mut ofdm_dcblock, _ctx: std::marker::PhantomData<&'a Ctx> }
+impl<'a> DcBlock<'a> {
+    /// `blocks` 0: `ofdm_dc_block_default` of the context's own sizes (S = n_fft + n_fft / 4)
+    pub fn new(ctx: &'a Ctx, blocks: i32, max_chunk: i64) -> anyhow::Result<Self> {
+        let n_fft = (ctx.s * 4 / 5) as i32;
+        let m = if blocks != 0 { blocks } else { unsafe { ofdm_dc_block_default(n_fft, n_fft / 4) } };
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { ofdm_dcblock_create(&mut raw, ctx.raw, m, max_chunk) }, "ofdm_dcblock_create")?;
+        Ok(DcBlock { raw, _ctx: std::marker::PhantomData })
+    }
+    pub unsafe fn push(&mut self, input: *const ofdm_fc32, n: i64, out: *mut ofdm_fc32) -> anyhow::Result<()> {
+        check(ofdm_dcblock_push(self.raw, input, n, out), "ofdm_dcblock_push")
+    }
+    pub unsafe fn push_sc16(&mut self, input: *const ofdm_sc16, n: i64, scale: f32, out: *mut ofdm_fc32) -> anyhow::Result<()> {
+        check(ofdm_dcblock_push_sc16(self.raw, input, n, scale, out), "ofdm_dcblock_push_sc16")
+    }
+    pub fn reset(&mut self) -> anyhow::Result<()> { check(unsafe { ofdm_dcblock_reset(self.raw) }, "ofdm_dcblock_reset") }
+    /// (samples pushed since create / reset, blocks)
+    pub fn state(&self) -> anyhow::Result<(i64, i32)> {
+        let (mut t, mut m) = (0i64, 0i32);
+        check(unsafe { ofdm_dcblock_state(self.raw, &mut t, &mut m) }, "ofdm_dcblock_state")?;
+        Ok((t, m))
+    }
+}
+impl<'a> Drop for DcBlock<'a> { fn drop(&mut self) { unsafe { ofdm_dcblock_destroy(self.raw); } } }
+/// The definition on host slices, no GPU (`ofdm_dc_block` / `ofdm_dc_block_sc16`)
+pub fn dc_block_host(samples: &[ofdm_fc32], blocks: i32) -> anyhow::Result<Vec<ofdm_fc32>> {
+    let mut out: Vec<ofdm_fc32> = Vec::with_capacity(samples.len());
+    check(unsafe { ofdm_dc_block(samples.as_ptr(), samples.len() as i64, blocks, out.as_mut_ptr()) }, "ofdm_dc_block")?;
+    unsafe { out.set_len(samples.len()); }
+    Ok(out)
+}
+pub fn dc_block_sc16_host(samples: &[ofdm_sc16], scale: f32, blocks: i32) -> anyhow::Result<Vec<ofdm_fc32>> {
+    let mut out: Vec<ofdm_fc32> = Vec::with_capacity(samples.len());
+    check(unsafe { ofdm_dc_block_sc16(samples.as_ptr(), samples.len() as i64, scale, blocks, out.as_mut_ptr()) }, "ofdm_dc_block_sc16")?;
+    unsafe { out.set_len(samples.len()); }
+    Ok(out)
+}
 
 /// One context per (thread, parameter set), created on first use and kept for the life of the thread: the reference calls `encode!` /
 /// `decode!` once per frame (examples/lab3a.rs:24,34, jetson_rx.rs:86) and `ofdm_create` -- table uploads, streams, workspaces --

@@ -1108,6 +1108,59 @@ int ofdm_stream_push_sc16(ofdm_stream *s, const ofdm_sc16 *in_host, int64_t n, f
                           float *metric, int64_t *d1, int64_t *d_hat, int64_t *n_pkt, int32_t *more);
 int ofdm_stream_state(const ofdm_stream *s, int64_t *total, int64_t *kept_from, int64_t *next_lag, int32_t *ended);
 
+/* ------------------------------------------------------------------ a DC blocker in front of detection (EXT-15)
+ * A direct-conversion radio adds a constant (LO leakage) to every sample.  The Schmidl-Cox metric of a constant is 1 at every lag: a DC
+ * term 3.8 dB above the noise floor fires the detector on noise alone and no packet behind it is ever timed.  With guard bands the DC
+ * bin carries nothing, so the constant can be taken out in front of the detector.  Opt-in everywhere; off, nothing changes.
+ *
+ * Definition (numpy: tests/dcblock_ref.py; parity with the reference is unpinned: it has nothing of the kind).  x[0 .. n) is fc32 -- an
+ * sc16 stream first widened as ofdm_sc16_widen does, x = (float)v * scale, one rounded product.  blocks = M, 1 <= M <= 1024.  Real and
+ * imaginary parts are treated alike and independently.
+ *     block sums  Samples form blocks of 64, aligned at sample 0 of the filter's stream (a reset starts a new stream at 0).  A complete
+ *                 block j has the sum b_j, formed in f64 by the balanced pairwise tree: s = the block's 64 samples as f64, then six
+ *                 times s = s[0::2] + s[1::2].  A block that is not complete has no sum and is never history.
+ *     output      sample i lies in block j = i / 64; lo = max(j - M, 0).  lo == j (block 0): y[i] = x[i].  Otherwise acc = b_lo, then
+ *                 acc += b_k for k = lo + 1 .. j - 1 in ascending order, in f64; m = acc / (64 (j - lo)) in f64; m32 = (float)m, rounded
+ *                 to nearest even; y[i] = x[i] - m32 in f32.
+ * The mean never contains the sample's own block: the filter has no latency, a stream's sample count and delivery rule stay what they
+ * are.  Nothing is special-cased for non-finite samples: a NaN spoils the M blocks behind its own block, per IEEE (which NaN: unspecified).
+ * Known and accepted: the first 64 samples of a stream pass unfiltered (L >= 80: no Schmidl-Cox product has both factors in them); without
+ * guard bands the DC bin carries data, and the filter disturbs it.
+ * ofdm_dc_block_default = ceil(3 S / 64), S = n_fft + cp_len (4 blocks at n_fft = 64, 60 at 1024): the middle of the band that works --
+ * a window of S or less follows the real-valued locking block and loses the frame, one of 8 S still holds the locking block during the
+ * training blocks.  OFDM_ERR_INVALID (< 0) for sizes ofdm_create refuses.
+ *
+ * ofdm_dc_block / ofdm_dc_block_sc16: the definition on host arrays, one whole stream, no GPU (out may not alias in).
+ * OFDM_ERR_INVALID: n < 0, blocks outside 1 .. 1024, a NULL array with n > 0, a bad sc16 scale; OFDM_ERR_UNSUPPORTED: n beyond 2^40;
+ * OFDM_ERR_NOMEM: the n / 64 block sums cannot be allocated.
+ * The handle (ofdm_dcblock_*) is the filter on DEVICE buffers, enqueued on the context's stream: the pushes of a handle, concatenated,
+ * equal ofdm_dc_block of the concatenated inputs bit for bit, however the stream is cut.  One launch per piece (k_dc_block<fc32> /
+ * k_dc_block<sc16>; a push longer than max_chunk is walked in pieces, ofdm_last_dispatch names the first); the handle owns its state
+ * (the last M block sums and the open block's samples, double-buffered) and is destroyed BEFORE its context.  n = 0 is a no-op.
+ * OFDM_ERR_INVALID: a NULL handle or context, blocks outside 1 .. 1024, max_chunk <= 0, n < 0, a NULL buffer with n > 0, a bad sc16
+ * scale, in_dev and out_dev overlapping.  OFDM_ERR_UNSUPPORTED: max_chunk or n beyond 2^40.
+ *
+ * ofdm_stream_set_dc_block: the filter in front of a stream's window (0 = off, the default; blocks outside 0 .. 1024 or a NULL handle:
+ * OFDM_ERR_INVALID).  Only while the stream's total is 0, else OFDM_ERR_INVALID; ofdm_stream_reset keeps the setting and clears the
+ * history.  The first setting that is not 0 allocates the filter's state and a second staging buffer of max_chunk samples
+ * (OFDM_ERR_NOMEM), kept until ofdm_stream_destroy.  ofdm_stream_get_dc_block: the setting.  With it on, a push is bit for bit the push of the
+ * filtered samples, and the contract of EXT-14 carries over word for word: the packets are those of ONE ofdm_rx_decode_all_long_host on
+ * ofdm_dc_block(concatenation, blocks) -- ofdm_dc_block_sc16(concatenation, scale, blocks) for sc16 pushes -- each delivered exactly
+ * once, with the push EXT-14's rule names; T and H are unchanged.  Per piece k_dc_block<fc32> / <sc16> runs between the upload and
+ * k_stream_ingest<fc32> (also for sc16 pushes: the filtered chunk is fc32) and leads the dispatch string. */
+int ofdm_dc_block_default(int32_t n_fft, int32_t cp_len);
+int ofdm_dc_block(const ofdm_fc32 *in, int64_t n, int32_t blocks, ofdm_fc32 *out);
+int ofdm_dc_block_sc16(const ofdm_sc16 *in, int64_t n, float scale, int32_t blocks, ofdm_fc32 *out);
+typedef struct ofdm_dcblock ofdm_dcblock;
+int ofdm_dcblock_create(ofdm_dcblock **out, ofdm_ctx *ctx, int32_t blocks, int64_t max_chunk);
+int ofdm_dcblock_destroy(ofdm_dcblock *f);
+int ofdm_dcblock_reset(ofdm_dcblock *f);
+int ofdm_dcblock_push(ofdm_dcblock *f, const ofdm_fc32 *in_dev, int64_t n, ofdm_fc32 *out_dev);
+int ofdm_dcblock_push_sc16(ofdm_dcblock *f, const ofdm_sc16 *in_dev, int64_t n, float scale, ofdm_fc32 *out_dev);
+int ofdm_dcblock_state(const ofdm_dcblock *f, int64_t *total, int32_t *blocks);
+int ofdm_stream_set_dc_block(ofdm_stream *s, int32_t blocks);
+int ofdm_stream_get_dc_block(const ofdm_stream *s, int32_t *blocks);
+
 /* ------------------------------------------------------------------ loop-back test bench
  * channel (src/channel.rs:33-74), per frame:
  *     y = convolve(tx, CHANNEL)                          tx_len + 63 samples (CHANNEL: the 64 taps of channel.rs:26-31)

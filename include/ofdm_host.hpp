@@ -634,6 +634,14 @@ class Stream {
     // every remaining detection, a last frame cut by the end of the stream included; the stream is ended until reset()
     std::vector<Packet> flush() { return push(nullptr, 0, true); }
     void reset(int64_t first_sample = 0) { check(ofdm_stream_reset(s_, first_sample), "ofdm_stream_reset"); }
+    // EXT-15: the DC blocker in front of the window (0 = off; DcBlock::default_blocks for the usual window).  Only before the first sample
+    // or right after reset(), which keeps the setting and clears the filter's history
+    void set_dc_block(int32_t blocks) { check(ofdm_stream_set_dc_block(s_, blocks), "ofdm_stream_set_dc_block"); }
+    int32_t dc_block() const {
+        int32_t m = 0;
+        check(ofdm_stream_get_dc_block(s_, &m), "ofdm_stream_get_dc_block");
+        return m;
+    }
     State state() const {
         State st; int32_t ended = 0;
         check(ofdm_stream_state(s_, &st.total, &st.kept_from, &st.next_lag, &ended), "ofdm_stream_state");
@@ -666,6 +674,48 @@ class Stream {
     }
     ofdm_stream *s_ = nullptr;
     int64_t row_ = 4;
+};
+
+// EXT-15: a DC blocker on device buffers (ofdm_dcblock_create .. ofdm_dcblock_state, include/ofdm_hip.h "a DC blocker in front of
+// detection").  Every sample leaves less the mean of the `blocks` complete 64-sample blocks in front of its own block; the pushes of one
+// filter, concatenated, equal ofdm_dc_block of the concatenated inputs bit for bit.  in_dev and out_dev are device buffers that do not
+// overlap; the launches are enqueued on the context's stream.  Destroy it before its context.
+class DcBlock {
+  public:
+    struct State { int64_t total = 0; int32_t blocks = 0; };
+    static int32_t default_blocks(int32_t n_fft) {
+        const int m = ofdm_dc_block_default(n_fft, n_fft / 4);
+        check(m < 0 ? m : OFDM_OK, "ofdm_dc_block_default");
+        return m;
+    }
+    DcBlock(Context &ctx, int32_t blocks, int64_t max_chunk = 1 << 20) { check(ofdm_dcblock_create(&f_, ctx.raw(), blocks, max_chunk), "ofdm_dcblock_create"); }
+    ~DcBlock() { if (f_) ofdm_dcblock_destroy(f_); }
+    DcBlock(const DcBlock &) = delete;
+    DcBlock &operator=(const DcBlock &) = delete;
+    void push(const ofdm_fc32 *in_dev, int64_t n, ofdm_fc32 *out_dev) { check(ofdm_dcblock_push(f_, in_dev, n, out_dev), "ofdm_dcblock_push"); }
+    void push_sc16(const ofdm_sc16 *in_dev, int64_t n, ofdm_fc32 *out_dev, float scale = OFDM_SC16_DEFAULT_SCALE) {
+        check(ofdm_dcblock_push_sc16(f_, in_dev, n, scale, out_dev), "ofdm_dcblock_push_sc16");
+    }
+    void reset() { check(ofdm_dcblock_reset(f_), "ofdm_dcblock_reset"); }
+    State state() const {
+        State st;
+        check(ofdm_dcblock_state(f_, &st.total, &st.blocks), "ofdm_dcblock_state");
+        return st;
+    }
+    // the definition on host arrays, no GPU
+    static std::vector<ofdm_fc32> host(const ofdm_fc32 *in, int64_t n, int32_t blocks) {
+        std::vector<ofdm_fc32> out((size_t)n);
+        check(ofdm_dc_block(in, n, blocks, out.data()), "ofdm_dc_block");
+        return out;
+    }
+    static std::vector<ofdm_fc32> host_sc16(const ofdm_sc16 *in, int64_t n, int32_t blocks, float scale = OFDM_SC16_DEFAULT_SCALE) {
+        std::vector<ofdm_fc32> out((size_t)n);
+        check(ofdm_dc_block_sc16(in, n, scale, blocks, out.data()), "ofdm_dc_block_sc16");
+        return out;
+    }
+
+  private:
+    ofdm_dcblock *f_ = nullptr;
 };
 
 // One context per (thread, parameter set), created on first use and kept: the reference's free functions are called once per

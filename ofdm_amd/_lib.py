@@ -159,6 +159,18 @@ SIGNATURES = {
     "ofdm_stream_push_sc16": (C.c_int, [vp, vp, i64, C.c_float, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64),
                                         C.POINTER(i32)]),
     "ofdm_stream_state": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]),
+    # EXT-15: a DC blocker (host definition; a handle on device buffers, its own type first; the stream option)
+    "ofdm_dc_block_default": (C.c_int, [i32, i32]),
+    "ofdm_dc_block": (C.c_int, [vp, i64, i32, vp]),
+    "ofdm_dc_block_sc16": (C.c_int, [vp, i64, C.c_float, i32, vp]),
+    "ofdm_dcblock_create": (C.c_int, [C.POINTER(vp), vp, i32, i64]),
+    "ofdm_dcblock_destroy": (C.c_int, [vp]),
+    "ofdm_dcblock_reset": (C.c_int, [vp]),
+    "ofdm_dcblock_push": (C.c_int, [vp, vp, i64, vp]),
+    "ofdm_dcblock_push_sc16": (C.c_int, [vp, vp, i64, C.c_float, vp]),
+    "ofdm_dcblock_state": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i32)]),
+    "ofdm_stream_set_dc_block": (C.c_int, [vp, i32]),
+    "ofdm_stream_get_dc_block": (C.c_int, [vp, C.POINTER(i32)]),
     "ofdm_hbm_read_probe": (C.c_int, [vp, vp, i64, i32]),
     "ofdm_timer_start": (C.c_int, [vp]),
     "ofdm_timer_stop_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),

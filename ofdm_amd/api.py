@@ -200,6 +200,31 @@ def sc16_narrow(samples, scale: float = 1.0 / SC16_DEFAULT_SCALE):
     return out, int(clipped.value)
 
 
+def dc_block_default(n_fft: int = 64) -> int:
+    """ofdm_dc_block_default (EXT-15): the default window of the DC blocker in blocks of 64 samples, ceil(3 S / 64)."""
+    lib = _lib.load()
+    m = int(lib.ofdm_dc_block_default(int(n_fft), int(n_fft) // 4))
+    _check(lib, min(m, 0), "ofdm_dc_block_default")
+    return m
+
+
+def dc_block_host(samples, blocks: int, scale: Optional[float] = None) -> np.ndarray:
+    """ofdm_dc_block / ofdm_dc_block_sc16 (EXT-15): the definition of the DC blocker on one whole stream, on the host, no GPU: complex64
+    [n] in, complex64 [n] out.  An int16 array of shape [n, 2] takes scale= and is widened by ofdm_sc16_widen's rule first."""
+    lib = _lib.load()
+    if np.asarray(samples).dtype == np.int16:
+        if scale is None:
+            raise OfdmError("dc_block_host: int16 samples need scale=")
+        a = _sc16_host(samples, "dc_block_host").reshape(-1, 2)
+        out = np.empty(a.shape[0], np.complex64)
+        _check(lib, lib.ofdm_dc_block_sc16(_host(a), a.shape[0], float(scale), int(blocks), _host(out)), "ofdm_dc_block_sc16")
+        return out
+    x = np.ascontiguousarray(samples, dtype=np.complex64).reshape(-1)
+    out = np.empty(x.size, np.complex64)
+    _check(lib, lib.ofdm_dc_block(_host(x), x.size, int(blocks), _host(out)), "ofdm_dc_block")
+    return out
+
+
 def _host(a: Optional[np.ndarray]):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
@@ -1233,16 +1258,37 @@ class Context:
         return {"bytes": out[:n], "len": ln[:n], "status": st[:n], "offset": off[:n], "f_delta": fd[:n], "metric": m[:n], "d1": d1[:n],
                 "d_hat": dh[:n], "lag_lo": lo[:n], "next_lag_lo": int(lo[n]), "more": bool(more.value)}
 
-    def stream(self, max_symbols: int, holdoff: Optional[int] = None, max_chunk: int = 65536, first_sample: int = 0) -> "Stream":
+    def stream(self, max_symbols: int, holdoff: Optional[int] = None, max_chunk: int = 65536, first_sample: int = 0,
+               dc_blocks: int = 0) -> "Stream":
         """ofdm_stream_create (EXT-14): a streaming receiver on this context -- push chunks as a radio hands them over, get every packet
-        exactly once, bit for bit the packets of decode_all_host on the concatenation.  holdoff None: default_holdoff()."""
+        exactly once, bit for bit the packets of decode_all_host on the concatenation.  holdoff None: default_holdoff().
+        dc_blocks (EXT-15, 0 = off): the DC blocker in front of the window; the packets are then those of decode_all_host on
+        dc_block_host(concatenation, dc_blocks)."""
         import weakref
 
         s = Stream(self, max_symbols, self.default_holdoff() if holdoff is None else holdoff, max_chunk, first_sample)
         if not hasattr(self, "_streams"):
             self._streams = weakref.WeakSet()
         self._streams.add(s)
+        if dc_blocks:
+            s.set_dc_block(dc_blocks)
         return s
+
+    def dc_filter(self, blocks: Optional[int] = None, max_chunk: int = 1 << 20) -> "DcBlock":
+        """ofdm_dcblock_create (EXT-15): a stateful DC blocker on device buffers -- its pushes, concatenated, are dc_block_host of the
+        concatenated inputs bit for bit.  blocks None: dc_block_default(n_fft).  Close it before its context."""
+        import weakref
+
+        f = DcBlock(self, dc_block_default(self.params.n_fft) if blocks is None else blocks, max_chunk)
+        if not hasattr(self, "_streams"):
+            self._streams = weakref.WeakSet()
+        self._streams.add(f)
+        return f
+
+    def dc_block(self, samples, blocks: Optional[int] = None, scale: Optional[float] = None) -> torch.Tensor:
+        """One shot: a whole stream (complex64, or int16 [n, 2] with scale=) through a fresh DC blocker -> complex64 device tensor."""
+        with self.dc_filter(blocks) as f:
+            return f.push(samples, scale=scale)
 
     # ---------------------------------------------------------------- host buffers (H2D / kernels / D2H pipelined in the library)
     def decode_host(self, frames: np.ndarray, max_symbols: int, n_lags: int = 0, frame_len: Optional[int] = None,
@@ -1301,6 +1347,64 @@ class Context:
         ms = C.c_float()
         self._ck(self.lib.ofdm_timer_stop_ms(self.h, C.byref(ms)), "timer_stop")
         return float(ms.value)
+
+
+class DcBlock:
+    """`ofdm_dcblock` (EXT-15, include/ofdm_hip.h "a DC blocker in front of detection"): Context.dc_filter(...) makes one.  Blocks of 64
+    samples aligned at the first sample pushed; every sample leaves less the mean of the `blocks` complete blocks in front of its own
+    block.  However the stream is cut into pushes, the outputs concatenated are dc_block_host of the inputs concatenated."""
+
+    def __init__(self, ctx: "Context", blocks: int, max_chunk: int):
+        self.ctx, self.lib = ctx, ctx.lib
+        h = C.c_void_p()
+        ctx._ck(self.lib.ofdm_dcblock_create(C.byref(h), ctx.h, int(blocks), int(max_chunk)), "ofdm_dcblock_create")
+        self.h = h
+        self.blocks = int(blocks)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ofdm_dcblock_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push(self, samples, scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ofdm_dcblock_push / _push_sc16: complex64 samples (a device tensor, or a host array that is uploaded), or int16 [n, 2] with
+        scale=, -> the filtered complex64 device tensor (out=: written there; it may not overlap the input).  Asynchronous."""
+        ctx = self.ctx
+        t = samples if isinstance(samples, torch.Tensor) else ctx.to_device(np.asarray(samples))
+        if t.dtype == torch.int16:
+            if scale is None:
+                raise OfdmError("DcBlock.push: int16 samples need scale=")
+            t = ctx._sc16(t).reshape(-1, 2)
+            n = t.shape[0]
+            out = ctx.empty((n,), torch.complex64) if out is None else ctx._cx(out)
+            ctx._ck(self.lib.ofdm_dcblock_push_sc16(self.h, _dev(t), n, float(scale), _dev(out)), "ofdm_dcblock_push_sc16")
+            return out
+        t = ctx._cx(t).reshape(-1)
+        out = ctx.empty((t.numel(),), torch.complex64) if out is None else ctx._cx(out)
+        ctx._ck(self.lib.ofdm_dcblock_push(self.h, _dev(t), t.numel(), _dev(out)), "ofdm_dcblock_push")
+        return out
+
+    def reset(self):
+        self.ctx._ck(self.lib.ofdm_dcblock_reset(self.h), "ofdm_dcblock_reset")
+
+    def state(self) -> dict:
+        """ofdm_dcblock_state -> total (samples pushed since create / reset), blocks"""
+        t, m = C.c_int64(), C.c_int32()
+        self.ctx._ck(self.lib.ofdm_dcblock_state(self.h, C.byref(t), C.byref(m)), "ofdm_dcblock_state")
+        return {"total": int(t.value), "blocks": int(m.value)}
 
 
 class Stream:
@@ -1385,6 +1489,16 @@ class Stream:
     def reset(self, first_sample: int = 0):
         self.ctx._ck(self.lib.ofdm_stream_reset(self.h, int(first_sample)), "ofdm_stream_reset")
 
+    def set_dc_block(self, blocks: int):
+        """ofdm_stream_set_dc_block (EXT-15): the DC blocker in front of the window, 0 = off; only before the first sample (or right
+        after reset(), which keeps the setting and clears the filter's history)"""
+        self.ctx._ck(self.lib.ofdm_stream_set_dc_block(self.h, int(blocks)), "ofdm_stream_set_dc_block")
+
+    def get_dc_block(self) -> int:
+        m = C.c_int32()
+        self.ctx._ck(self.lib.ofdm_stream_get_dc_block(self.h, C.byref(m)), "ofdm_stream_get_dc_block")
+        return int(m.value)
+
     def state(self) -> dict:
         """ofdm_stream_state -> total (samples pushed), kept_from (first sample the window keeps), next_lag (where the walk resumes),
         ended; all stream-relative"""
@@ -1402,11 +1516,13 @@ def _packet_dicts(res: dict):
 
 
 def receive_stream(chunks, max_symbols: int, guard_bands: bool = False, modulation: int = BPSK, n_fft: int = 64, ecc: int = ECC_NONE,
-                   holdoff: Optional[int] = None, max_chunk: int = 65536, first_sample: int = 0, sc16_scale: Optional[float] = None, **kw):
+                   holdoff: Optional[int] = None, max_chunk: int = 65536, first_sample: int = 0, sc16_scale: Optional[float] = None,
+                   dc_blocks: int = 0, **kw):
     """A generator over an iterable of chunks (complex64 arrays, or int16 [n, 2] arrays with sc16_scale=): yields one dict per packet
-    (bytes, status, offset, f_delta, metric, d1, d_hat) as soon as the stream commits it, and flushes when the iterable ends."""
+    (bytes, status, offset, f_delta, metric, d1, d_hat) as soon as the stream commits it, and flushes when the iterable ends.
+    dc_blocks (EXT-15, 0 = off): the DC blocker in front of the stream's window."""
     ctx = _ctx(n_fft, modulation, guard_bands, ecc, **kw)
-    with ctx.stream(max_symbols, holdoff, max_chunk, first_sample) as s:
+    with ctx.stream(max_symbols, holdoff, max_chunk, first_sample, dc_blocks=dc_blocks) as s:
         for chunk in chunks:
             yield from _packet_dicts(s.push_all(chunk, sc16_scale=sc16_scale))
         yield from _packet_dicts(s.flush())
@@ -1544,7 +1660,7 @@ def decode_long(samples, guard_bands: Optional[bool] = None, modulation: Optiona
 
 def decode_all(samples, guard_bands: Optional[bool] = None, modulation: Optional[int] = None, n_fft: int = 64, ecc: int = ECC_NONE,
                fcs: bool = False, holdoff: Optional[int] = None, max_packets: int = 4096, max_symbols: Optional[int] = None,
-               lag_lo: int = 0, lag_hi: int = 0, device: int = 0, batched: bool = False, **sync) -> list:
+               lag_lo: int = 0, lag_hi: int = 0, device: int = 0, batched: bool = False, dc_blocks: int = 0, **sync) -> list:
     """EVERY packet of one long capture (EXT-12): one scan for all detections (Context.sc_scan_long: three launches, one
     synchronisation), then decode_long(lag_lo = where the search for packet k started) per detection.  -> a list of per-packet dicts
     (bytes: the payload as `bytes`, empty unless status == FRAME_OK; len, status, offset into the capture, f_delta, metric, d1, d_hat),
@@ -1560,12 +1676,17 @@ def decode_all(samples, guard_bands: Optional[bool] = None, modulation: Optional
     batched=True (EXT-13): the same list from one scan and ONE batched decode (Context.decode_packets) instead of a decode_long per
     packet.  Its f_delta is the scan's own (within 1e-9 of the default path's, whose slice search sums in another order) and its metric
     within 1e-6; every other field is equal.  It requires max_symbols (OfdmError without it: the default "up to the capture's end" would
-    gather the capture once per packet)."""
+    gather the capture once per packet).
+
+    dc_blocks (EXT-15, 0 = off): the capture goes through the DC blocker on the device first (Context.dc_block) -- for captures of a
+    direct-conversion radio, whose LO leakage fires the detector on noise; frames need guard bands (the DC bin then carries nothing)."""
     if batched and max_symbols is None:
         raise OfdmError("decode_all(batched=True) requires max_symbols: the data symbols of the longest frame expected")
     ctx = _ctx(n_fft, BPSK if modulation is None else modulation, bool(guard_bands), _with_fcs(ecc, fcs), device=device, **sync)
     x = samples if isinstance(samples, torch.Tensor) else ctx.to_device(np.asarray(samples))
     x = x.reshape(-1)
+    if dc_blocks:
+        x = ctx.dc_block(x, dc_blocks)
     if holdoff is None:
         holdoff = ctx.default_holdoff()
     if max_symbols is None:

@@ -474,6 +474,25 @@ struct StreamIngestParams {
     float2 *win = nullptr;               // the new window
 };
 hipError_t run_stream_ingest(const StreamIngestParams &p, bool sc16, int num_cu, hipStream_t st);
+// ---- EXT-15 the DC blocker (ofdm_dcblock_push, ofdm_stream_set_dc_block; kernels_dcblock.hip, definition: tests/dcblock_ref.py).
+// k_dc_block<fc32> / <sc16>, one launch: out[e] = x[e] - the f32 mean of the up to `blocks` complete 64-sample blocks in front of the
+// block of stream sample t0 + e (block 0: out = x), for e < n, and the state behind the piece into ring_new / open_new.  in and out do
+// not overlap; the four state buffers are distinct.
+constexpr int kDcMaxBlocks = 1024;
+struct DcBlockParams {
+    const Tuning *tune = nullptr;
+    Trace *trace = nullptr;
+    const void *in = nullptr;            // n samples: float2 (fc32) or int16 pairs (sc16)
+    float2 *out = nullptr;
+    long long n = 0, t0 = 0;             // t0: the samples of the filter's stream in front of the piece
+    float scale = 0.f;                   // sc16 only
+    int blocks = 0;                      // M, 1 .. kDcMaxBlocks
+    const double2 *ring_old = nullptr;   // [M] the sum of block k in slot k % M, for the last M complete blocks in front of the piece
+    double2 *ring_new = nullptr;         // ... behind the piece; written only when the piece completes a block
+    const float2 *open_old = nullptr;    // [64] the t0 % 64 samples of the open block in front of the piece
+    float2 *open_new = nullptr;          // ... the (t0 + n) % 64 behind it; written whenever that is not 0
+};
+hipError_t run_dc_block(const DcBlockParams &p, bool sc16, int num_cu, hipStream_t st);
 // base (optional): per-pair sample offset added to the pair's start; status (optional): pairs with status != 0 get 0
 hipError_t run_freq_correction(const float2 *in, long long n_pairs, long long stride, long long right_offset, int L,
                                double *f_delta, hipStream_t st, const int32_t *base = nullptr, const int32_t *status = nullptr);

@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <exception>
 #include <new>
 
 using namespace ofdm;
@@ -956,6 +957,165 @@ int ofdm_rx_decode_long_sc16_host(ofdm_ctx *c, const ofdm_sc16 *in_host, int64_t
 
 } // extern "C"
 
+// ---- EXT-15: a DC blocker in front of detection (include/ofdm_hip.h, "a DC blocker"; numpy restatement: tests/dcblock_ref.py).  The host
+// functions are the definition in C++; the handle carries the state of k_dc_block (kernels_dcblock.hip) from piece to piece: the sums
+// of the last M complete blocks and the raw samples of the open block, each in two copies -- a launch reads one and writes the other.
+struct ofdm_dcblock {
+    ofdm_ctx *c = nullptr;
+    int32_t M = 0;
+    int64_t max_chunk = 0;
+    int64_t T = 0;              // samples pushed since create / reset
+    void *state = nullptr;      // ONE allocation: ring[0] | ring[1] | open[0] | open[1]
+    double2 *ring[2] = {nullptr, nullptr};
+    float2 *open[2] = {nullptr, nullptr};
+    int ring_cur = 0, open_cur = 0; // the copies the next launch reads
+};
+
+namespace {
+
+int stream_dev_alloc(ofdm_ctx *c, void **p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) { c->last_hip = (int)e; *p = nullptr; return OFDM_ERR_NOMEM; }
+    return c->ws_poison ? poison_fill_dev(c, *p, bytes, c->ws_poison & 0xFF) : OFDM_OK;
+}
+
+void dcblock_free(ofdm_dcblock *f) {
+    if (f->state) hipFree(f->state);
+    f->state = nullptr;
+}
+
+// The definition, one whole stream: load(i) -> sample i as fc32.  Nothing is thrown across the C boundary: a stream beyond what the
+// handle takes is OFDM_ERR_UNSUPPORTED, block sums that cannot be allocated are OFDM_ERR_NOMEM
+template <class Load> int dc_block_host(int64_t n, int32_t M, Load load, ofdm_fc32 *out) {
+    if (n > kScanMaxSamples) return OFDM_ERR_UNSUPPORTED;
+    const int64_t nb = n / 64, n_blocks = (n + 63) / 64;
+    std::vector<double> sum;
+    try { sum.resize((size_t)nb * 2); } catch (const std::exception &) { return OFDM_ERR_NOMEM; }
+    double s[2][64];
+    for (int64_t j = 0; j < nb; j++) {
+        for (int i = 0; i < 64; i++) { const ofdm_fc32 x = load(64 * j + i); s[0][i] = (double)x.re; s[1][i] = (double)x.im; }
+        for (int w = 32; w >= 1; w >>= 1) // the balanced pairwise tree: six times s = s[0::2] + s[1::2]
+            for (int i = 0; i < w; i++) { s[0][i] = s[0][2 * i] + s[0][2 * i + 1]; s[1][i] = s[1][2 * i] + s[1][2 * i + 1]; }
+        sum[(size_t)j * 2] = s[0][0]; sum[(size_t)j * 2 + 1] = s[1][0];
+    }
+    for (int64_t j = 0; j < n_blocks; j++) {
+        const int64_t lo = std::max<int64_t>(j - M, 0), end = std::min<int64_t>(64 * j + 64, n);
+        if (lo == j) { for (int64_t i = 64 * j; i < end; i++) out[i] = load(i); continue; }
+        double re = sum[(size_t)lo * 2], im = sum[(size_t)lo * 2 + 1];
+        for (int64_t k = lo + 1; k < j; k++) { re += sum[(size_t)k * 2]; im += sum[(size_t)k * 2 + 1]; }
+        const double d = 64.0 * (double)(j - lo);
+        const float mre = (float)(re / d), mim = (float)(im / d);
+        for (int64_t i = 64 * j; i < end; i++) { const ofdm_fc32 x = load(i); out[i].re = x.re - mre; out[i].im = x.im - mim; }
+    }
+    return OFDM_OK;
+}
+
+// One piece (m samples at `in`, device memory) through k_dc_block, behind the caller's entry scope
+int dcblock_piece(ofdm_dcblock *f, const void *in, int64_t m, bool sc16, float scale, float2 *out) {
+    if (m <= 0) return OFDM_OK; // no launch: the state and the copies the next launch reads stay what they are
+    ofdm_ctx *c = f->c;
+    ofdm::DcBlockParams p;
+    p.tune = &c->tune; p.trace = &c->trace;
+    p.in = in; p.out = out; p.n = m; p.t0 = f->T; p.scale = scale; p.blocks = f->M;
+    p.ring_old = f->ring[f->ring_cur]; p.ring_new = f->ring[f->ring_cur ^ 1];
+    p.open_old = f->open[f->open_cur]; p.open_new = f->open[f->open_cur ^ 1];
+    HIP_TRY(c, run_dc_block(p, sc16, c->num_cu, c->stream));
+    if ((f->T + m) / 64 > f->T / 64) f->ring_cur ^= 1; // the launch wrote the other ring only if it completed a block
+    f->open_cur ^= 1;
+    f->T += m;
+    return OFDM_OK;
+}
+
+int dcblock_push(ofdm_dcblock *f, const void *in, int64_t n, size_t ss, bool sc16, float scale, ofdm_fc32 *out) {
+    if (!f || !f->c || n < 0 || (n > 0 && (!in || !out)) || (sc16 && !sc16_scale_ok(scale))) return OFDM_ERR_INVALID;
+    if (n == 0) return OFDM_OK;
+    if (n > kScanMaxSamples || f->T > INT64_MAX / 4 - n) return OFDM_ERR_UNSUPPORTED;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(in), a1 = a0 + (size_t)n * ss, b0 = reinterpret_cast<uintptr_t>(out), b1 = b0 + (size_t)n * sizeof(ofdm_fc32);
+    if (a0 < b1 && b0 < a1) return OFDM_ERR_INVALID; // a tile reads the blocks in front of it after another tile has written them
+    ofdm_ctx *c = f->c;
+    EntryScope scope(c);
+    for (int64_t done = 0; done < n;) {
+        const int64_t m = std::min(n - done, f->max_chunk);
+        const Trace::Mute later(c->trace, done > 0); // the dispatch string names what a piece ran, once
+        const int rc = dcblock_piece(f, static_cast<const char *>(in) + (size_t)done * ss, m, sc16, scale, reinterpret_cast<float2 *>(out) + done);
+        if (rc) return rc;
+        done += m;
+    }
+    return OFDM_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int ofdm_dc_block_default(int32_t n_fft, int32_t cp_len) {
+    if (n_fft < 64 || n_fft > 4096 || (n_fft & (n_fft - 1)) || cp_len != n_fft / 4) return OFDM_ERR_INVALID;
+    return (3 * (n_fft + cp_len) + 63) / 64;
+}
+
+int ofdm_dc_block(const ofdm_fc32 *in, int64_t n, int32_t blocks, ofdm_fc32 *out) {
+    if (n < 0 || blocks < 1 || blocks > ofdm::kDcMaxBlocks || (n > 0 && (!in || !out))) return OFDM_ERR_INVALID;
+    return dc_block_host(n, blocks, [&](int64_t i) { return in[i]; }, out);
+}
+
+int ofdm_dc_block_sc16(const ofdm_sc16 *in, int64_t n, float scale, int32_t blocks, ofdm_fc32 *out) {
+    if (n < 0 || blocks < 1 || blocks > ofdm::kDcMaxBlocks || (n > 0 && (!in || !out)) || !sc16_scale_ok(scale)) return OFDM_ERR_INVALID;
+    // widened as it is read, by EXT-9's own host rule (one rounded product, made in another translation unit: nothing contracts it)
+    return dc_block_host(n, blocks, [&](int64_t i) { ofdm_fc32 x; ofdm::sc16_widen_host(&in[i].re, 1, scale, &x.re); return x; }, out);
+}
+
+int ofdm_dcblock_create(ofdm_dcblock **out, ofdm_ctx *c, int32_t blocks, int64_t max_chunk) {
+    if (out) *out = nullptr;
+    if (!out || !c || blocks < 1 || blocks > ofdm::kDcMaxBlocks || max_chunk <= 0) return OFDM_ERR_INVALID;
+    if (max_chunk > kScanMaxSamples) return OFDM_ERR_UNSUPPORTED;
+    ofdm_dcblock *f = new (std::nothrow) ofdm_dcblock();
+    if (!f) return OFDM_ERR_NOMEM;
+    f->c = c; f->M = blocks; f->max_chunk = max_chunk;
+    DeviceGuard dev_guard(c->device);
+    const size_t ring_bytes = (size_t)blocks * sizeof(double2), open_bytes = 64 * sizeof(float2);
+    const int rc = stream_dev_alloc(c, &f->state, 2 * ring_bytes + 2 * open_bytes);
+    if (rc) { delete f; return rc; }
+    char *b = static_cast<char *>(f->state);
+    f->ring[0] = reinterpret_cast<double2 *>(b); f->ring[1] = reinterpret_cast<double2 *>(b + ring_bytes);
+    f->open[0] = reinterpret_cast<float2 *>(b + 2 * ring_bytes); f->open[1] = reinterpret_cast<float2 *>(b + 2 * ring_bytes + open_bytes);
+    *out = f;
+    return OFDM_OK;
+}
+
+int ofdm_dcblock_destroy(ofdm_dcblock *f) {
+    if (!f || !f->c) return OFDM_ERR_INVALID;
+    DeviceGuard dev_guard(f->c->device);
+    const hipError_t e = hipStreamSynchronize(f->c->stream);
+    dcblock_free(f);
+    const int rc = e == hipSuccess ? OFDM_OK : OFDM_ERR_HIP;
+    if (rc) f->c->last_hip = (int)e;
+    delete f;
+    return rc;
+}
+
+int ofdm_dcblock_reset(ofdm_dcblock *f) {
+    if (!f) return OFDM_ERR_INVALID;
+    f->T = 0; // nothing of the state is read before the launch that follows has written it
+    return OFDM_OK;
+}
+
+int ofdm_dcblock_push(ofdm_dcblock *f, const ofdm_fc32 *in_dev, int64_t n, ofdm_fc32 *out_dev) {
+    return dcblock_push(f, in_dev, n, sizeof(ofdm_fc32), false, 0.f, out_dev);
+}
+
+int ofdm_dcblock_push_sc16(ofdm_dcblock *f, const ofdm_sc16 *in_dev, int64_t n, float scale, ofdm_fc32 *out_dev) {
+    return dcblock_push(f, in_dev, n, sizeof(ofdm_sc16), true, scale, out_dev);
+}
+
+int ofdm_dcblock_state(const ofdm_dcblock *f, int64_t *total, int32_t *blocks) {
+    if (!f) return OFDM_ERR_INVALID;
+    if (total) *total = f->T;
+    if (blocks) *blocks = f->M;
+    return OFDM_OK;
+}
+
+} // extern "C"
+
 // ---- EXT-14: a streaming receiver (include/ofdm_hip.h, "a streaming receiver"; numpy restatement and the proofs: tests/stream_ref.py,
 // tests/test_stream_cpu.py).  The stream keeps the last samples of everything pushed in one of two device windows and, per piece of a
 // push: k_stream_ingest (the carry and the new chunk into the other window, one launch), ofdm_sc_scan_long's kernels over the window
@@ -975,6 +1135,11 @@ struct ofdm_stream {
     bool ended = false;
     float2 *win[2] = {nullptr, nullptr};
     void *stage = nullptr;      // one chunk as it was pushed (max_chunk fc32 samples)
+    // EXT-15 (ofdm_stream_set_dc_block): the filter in front of the ingest and the fc32 chunk it writes; both made by the first setting
+    // that is not 0 and kept until the stream is destroyed
+    ofdm_dcblock *dc = nullptr;
+    void *stage_dc = nullptr;
+    int32_t dc_blocks = 0;      // the setting: 0 = off
     void *res_dev = nullptr, *res_pin = nullptr; // PacketsBlock of kStreamScanCap rows, device and pinned
     size_t row = 0;             // bytes of a result row there
     int64_t need = 0;           // decode_row_bytes: what a caller's row receives
@@ -995,15 +1160,12 @@ constexpr int64_t kStreamScanCap = 256; // detections per scan + decode round (t
 void stream_free(ofdm_stream *s) {
     for (float2 *&w : s->win) { if (w) hipFree(w); w = nullptr; }
     if (s->stage) hipFree(s->stage);
+    if (s->stage_dc) hipFree(s->stage_dc);
+    if (s->dc) { dcblock_free(s->dc); delete s->dc; }
+    s->dc = nullptr; s->stage_dc = nullptr;
     if (s->res_dev) hipFree(s->res_dev);
     if (s->res_pin) hipHostFree(s->res_pin);
     s->stage = s->res_dev = s->res_pin = nullptr;
-}
-
-int stream_dev_alloc(ofdm_ctx *c, void **p, size_t bytes) {
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) { c->last_hip = (int)e; *p = nullptr; return OFDM_ERR_NOMEM; }
-    return c->ws_poison ? poison_fill_dev(c, *p, bytes, c->ws_poison & 0xFF) : OFDM_OK;
 }
 
 void stream_rewind(ofdm_stream *s, int64_t first_sample) {
@@ -1011,6 +1173,7 @@ void stream_rewind(ofdm_stream *s, int64_t first_sample) {
     s->T = s->B = s->keep_from = s->lo = 0;
     s->ended = false;
     s->q.clear(); s->q_rows.clear(); s->q_head = 0;
+    if (s->dc) s->dc->T = 0; // EXT-15: the setting stays, the history goes
 }
 
 // Scan the window from `lo` on and decode what the horizon commits (flush: everything), round by round of at most `cap` detections;
@@ -1073,6 +1236,11 @@ int stream_piece(ofdm_stream *s, const void *in, int64_t m, size_t ss, bool sc16
         StreamIngestParams p;
         p.tune = &c->tune; p.trace = &c->trace;
         p.carry = s->win[s->cur] + drop; p.keep = keep; p.n = m; p.chunk = s->stage; p.scale = scale; p.win = s->win[s->cur ^ 1];
+        if (s->dc_blocks) { // EXT-15: the filtered chunk, already fc32, is what the window takes in
+            if ((rc = dcblock_piece(s->dc, s->stage, m, sc16, scale, static_cast<float2 *>(s->stage_dc)))) return rc;
+            p.chunk = s->stage_dc;
+            sc16 = false;
+        }
         HIP_TRY(c, run_stream_ingest(p, sc16, c->num_cu, c->stream));
         s->cur ^= 1;
         s->B = s->keep_from;
@@ -1199,6 +1367,31 @@ int ofdm_stream_push_sc16(ofdm_stream *s, const ofdm_sc16 *in_host, int64_t n, f
                           int64_t *d_hat, int64_t *n_pkt, int32_t *more) {
     return stream_push(s, in_host, n, sizeof(ofdm_sc16), true, scale, flush, max_pkt, out_host, out_stride, out_len, status, offset, f_delta, metric,
                        d1, d_hat, n_pkt, more);
+}
+
+int ofdm_stream_set_dc_block(ofdm_stream *s, int32_t blocks) {
+    if (!s || !s->c || blocks < 0 || blocks > ofdm::kDcMaxBlocks || s->T != 0) return OFDM_ERR_INVALID;
+    ofdm_ctx *c = s->c;
+    if (blocks && (!s->dc || s->dc->M != blocks)) {
+        DeviceGuard dev_guard(c->device);
+        int rc;
+        if (!s->stage_dc && (rc = stream_dev_alloc(c, &s->stage_dc, (size_t)s->max_chunk * sizeof(float2) + 256))) return rc;
+        ofdm_dcblock *f = nullptr;
+        if ((rc = ofdm_dcblock_create(&f, c, blocks, s->max_chunk))) return rc;
+        ofdm_dcblock *old = s->dc;
+        s->dc = f;
+        // the old window's filter: what its destroy reports (a failed synchronise; last_hip is set) is this call's result
+        if (old && (rc = ofdm_dcblock_destroy(old))) return rc;
+    }
+    if (s->dc) s->dc->T = 0;
+    s->dc_blocks = blocks;
+    return OFDM_OK;
+}
+
+int ofdm_stream_get_dc_block(const ofdm_stream *s, int32_t *blocks) {
+    if (!s || !blocks) return OFDM_ERR_INVALID;
+    *blocks = s->dc_blocks;
+    return OFDM_OK;
 }
 
 int ofdm_stream_state(const ofdm_stream *s, int64_t *total, int64_t *kept_from, int64_t *next_lag, int32_t *ended) {
