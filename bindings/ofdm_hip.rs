@@ -13,6 +13,8 @@ pub struct ofdm_ctx { _private: [u8; 0] }
 pub struct ofdm_stream { _private: [u8; 0] }
 #[repr(C)]
 pub struct ofdm_dcblock { _private: [u8; 0] }
+#[repr(C)]
+pub struct ofdm_ddc_handle { _private: [u8; 0] }
 
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -342,6 +344,25 @@ extern "C" {
     pub fn ofdm_dcblock_state(f: *const ofdm_dcblock, total: *mut i64, blocks: *mut i32) -> c_int;
     pub fn ofdm_stream_set_dc_block(s: *mut ofdm_stream, blocks: i32) -> c_int;
     pub fn ofdm_stream_get_dc_block(s: *const ofdm_stream, blocks: *mut i32) -> c_int;
+    // EXT-16: a digital down-converter.  Host definition and design; a handle on device buffers (its own type first); the stream option
+    pub fn ofdm_ddc_rotor_tables(coarse: *mut f32, fine: *mut f32) -> c_int;
+    pub fn ofdm_ddc_out_len(n: i64, decim: i32, n_taps: i32) -> i64;
+    pub fn ofdm_ddc_inc_for(f0_cycles_per_sample: f64, inc: *mut i32) -> c_int;
+    pub fn ofdm_ddc_design(decim: i32, taps_per_phase: i32, taps: *mut f32) -> c_int;
+    pub fn ofdm_ddc(input: *const ofdm_fc32, n: i64, decim: i32, phase_inc: i32, taps: *const f32, n_taps: i32, out: *mut ofdm_fc32,
+                    out_cap: i64, n_out: *mut i64) -> c_int;
+    pub fn ofdm_ddc_sc16(input: *const ofdm_sc16, n: i64, scale: f32, decim: i32, phase_inc: i32, taps: *const f32, n_taps: i32,
+                         out: *mut ofdm_fc32, out_cap: i64, n_out: *mut i64) -> c_int;
+    pub fn ofdm_ddc_create(out: *mut *mut ofdm_ddc_handle, ctx: *mut ofdm_ctx, decim: i32, phase_inc: i32, taps: *const f32, n_taps: i32,
+                           max_chunk: i64) -> c_int;
+    pub fn ofdm_ddc_destroy(h: *mut ofdm_ddc_handle) -> c_int;
+    pub fn ofdm_ddc_reset(h: *mut ofdm_ddc_handle) -> c_int;
+    pub fn ofdm_ddc_push(h: *mut ofdm_ddc_handle, in_dev: *const ofdm_fc32, n: i64, out_dev: *mut ofdm_fc32, out_cap: i64, n_out: *mut i64) -> c_int;
+    pub fn ofdm_ddc_push_sc16(h: *mut ofdm_ddc_handle, in_dev: *const ofdm_sc16, n: i64, scale: f32, out_dev: *mut ofdm_fc32, out_cap: i64,
+                              n_out: *mut i64) -> c_int;
+    pub fn ofdm_ddc_state(h: *const ofdm_ddc_handle, total_in: *mut i64, total_out: *mut i64) -> c_int;
+    pub fn ofdm_stream_set_ddc(s: *mut ofdm_stream, decim: i32, phase_inc: i32, taps: *const f32, n_taps: i32) -> c_int;
+    pub fn ofdm_stream_get_ddc(s: *const ofdm_stream, decim: *mut i32, phase_inc: *mut i32, n_taps: *mut i32) -> c_int;
     pub fn ofdm_timer_start(ctx: *mut ofdm_ctx) -> c_int;
     pub fn ofdm_timer_stop_ms(ctx: *mut ofdm_ctx, elapsed_ms: *mut f32) -> c_int;
 }
@@ -418,8 +439,88 @@ impl<'a> Stream<'a> {
         check(unsafe { ofdm_stream_get_dc_block(self.raw, &mut m) }, "ofdm_stream_get_dc_block")?;
         Ok(m)
     }
+    /// EXT-16: the down-converter in front of everything else (decim 0 = off; empty taps: the default design).  Pushes are then
+    /// input-rate samples, every offset is in output samples; only before the first sample or right after `reset`
+    pub fn set_ddc(&mut self, decim: i32, phase_inc: i32, taps: &[f32]) -> anyhow::Result<()> {
+        let p = if taps.is_empty() { std::ptr::null() } else { taps.as_ptr() };
+        check(unsafe { ofdm_stream_set_ddc(self.raw, decim, phase_inc, p, taps.len() as i32) }, "ofdm_stream_set_ddc")
+    }
+    /// (decim, phase_inc, n_taps) of the setting; decim 0 = off
+    pub fn ddc(&self) -> anyhow::Result<(i32, i32, i32)> {
+        let (mut d, mut i, mut t) = (0i32, 0i32, 0i32);
+        check(unsafe { ofdm_stream_get_ddc(self.raw, &mut d, &mut i, &mut t) }, "ofdm_stream_get_ddc")?;
+        Ok((d, i, t))
+    }
 }
 impl<'a> Drop for Stream<'a> { fn drop(&mut self) { unsafe { ofdm_stream_destroy(self.raw); } } }
+
+/// EXT-16: a digital down-converter on device buffers (include/ofdm_hip.h, "a digital down-converter"): mix by the two-level 20-bit
+/// rotor, filter by real taps, keep every `decim`-th sample; the outputs of one converter's pushes, concatenated, equal `ofdm_ddc` of the
+/// concatenated inputs bit for bit.  `input` and `out` are device pointers that do not overlap.  Borrows its context.
+pub struct Ddc<'a> { raw: *mut ofdm_ddc_handle, _ctx: std::marker::PhantomData<&'a Ctx> }
+impl<'a> Ddc<'a> {
+    pub fn new(ctx: &'a Ctx, decim: i32, phase_inc: i32, taps: &[f32], max_chunk: i64) -> anyhow::Result<Self> {
+        let mut raw = std::ptr::null_mut();
+        check(unsafe { ofdm_ddc_create(&mut raw, ctx.raw, decim, phase_inc, taps.as_ptr(), taps.len() as i32, max_chunk) }, "ofdm_ddc_create")?;
+        Ok(Ddc { raw, _ctx: std::marker::PhantomData })
+    }
+    /// -> the samples written at `out`
+    pub unsafe fn push(&mut self, input: *const ofdm_fc32, n: i64, out: *mut ofdm_fc32, out_cap: i64) -> anyhow::Result<i64> {
+        let mut k = 0i64;
+        check(ofdm_ddc_push(self.raw, input, n, out, out_cap, &mut k), "ofdm_ddc_push")?;
+        Ok(k)
+    }
+    pub unsafe fn push_sc16(&mut self, input: *const ofdm_sc16, n: i64, scale: f32, out: *mut ofdm_fc32, out_cap: i64) -> anyhow::Result<i64> {
+        let mut k = 0i64;
+        check(ofdm_ddc_push_sc16(self.raw, input, n, scale, out, out_cap, &mut k), "ofdm_ddc_push_sc16")?;
+        Ok(k)
+    }
+    pub fn reset(&mut self) -> anyhow::Result<()> { check(unsafe { ofdm_ddc_reset(self.raw) }, "ofdm_ddc_reset") }
+    /// (samples taken, samples given) since create / reset
+    pub fn state(&self) -> anyhow::Result<(i64, i64)> {
+        let (mut a, mut b) = (0i64, 0i64);
+        check(unsafe { ofdm_ddc_state(self.raw, &mut a, &mut b) }, "ofdm_ddc_state")?;
+        Ok((a, b))
+    }
+}
+impl<'a> Drop for Ddc<'a> { fn drop(&mut self) { unsafe { ofdm_ddc_destroy(self.raw); } } }
+/// The Hamming-windowed sinc of `taps_per_phase * decim` taps with the cutoff 0.5 / decim (`ofdm_ddc_design`)
+pub fn ddc_design(decim: i32, taps_per_phase: i32) -> anyhow::Result<Vec<f32>> {
+    let mut h = vec![0f32; (decim.max(1) as usize) * (taps_per_phase.max(1) as usize)];
+    check(unsafe { ofdm_ddc_design(decim, taps_per_phase, h.as_mut_ptr()) }, "ofdm_ddc_design")?;
+    Ok(h)
+}
+/// The increment that brings `f0` (cycles per input sample) to 0 (`ofdm_ddc_inc_for`)
+pub fn ddc_inc_for(f0: f64) -> anyhow::Result<i32> {
+    let mut inc = 0i32;
+    check(unsafe { ofdm_ddc_inc_for(f0, &mut inc) }, "ofdm_ddc_inc_for")?;
+    Ok(inc)
+}
+/// The rotor tables the host definition uses and the device is given (`ofdm_ddc_rotor_tables`): 1024 (re, im) pairs each
+pub fn ddc_rotor_tables() -> anyhow::Result<(Vec<f32>, Vec<f32>)> {
+    let (mut c, mut f) = (vec![0f32; 2048], vec![0f32; 2048]);
+    check(unsafe { ofdm_ddc_rotor_tables(c.as_mut_ptr(), f.as_mut_ptr()) }, "ofdm_ddc_rotor_tables")?;
+    Ok((c, f))
+}
+/// The definition on host slices, no GPU (`ofdm_ddc` / `ofdm_ddc_sc16`)
+pub fn ddc_host(samples: &[ofdm_fc32], decim: i32, phase_inc: i32, taps: &[f32]) -> anyhow::Result<Vec<ofdm_fc32>> {
+    let m = unsafe { ofdm_ddc_out_len(samples.len() as i64, decim, taps.len() as i32) };
+    check(if m < 0 { m as c_int } else { 0 }, "ofdm_ddc_out_len")?;
+    let mut out: Vec<ofdm_fc32> = Vec::with_capacity(m as usize);
+    let mut k = 0i64;
+    check(unsafe { ofdm_ddc(samples.as_ptr(), samples.len() as i64, decim, phase_inc, taps.as_ptr(), taps.len() as i32, out.as_mut_ptr(), m, &mut k) }, "ofdm_ddc")?;
+    unsafe { out.set_len(k as usize); }
+    Ok(out)
+}
+pub fn ddc_sc16_host(samples: &[ofdm_sc16], scale: f32, decim: i32, phase_inc: i32, taps: &[f32]) -> anyhow::Result<Vec<ofdm_fc32>> {
+    let m = unsafe { ofdm_ddc_out_len(samples.len() as i64, decim, taps.len() as i32) };
+    check(if m < 0 { m as c_int } else { 0 }, "ofdm_ddc_out_len")?;
+    let mut out: Vec<ofdm_fc32> = Vec::with_capacity(m as usize);
+    let mut k = 0i64;
+    check(unsafe { ofdm_ddc_sc16(samples.as_ptr(), samples.len() as i64, scale, decim, phase_inc, taps.as_ptr(), taps.len() as i32, out.as_mut_ptr(), m, &mut k) }, "ofdm_ddc_sc16")?;
+    unsafe { out.set_len(k as usize); }
+    Ok(out)
+}
 
 /// EXT-15: a DC blocker on device buffers (include/ofdm_hip.h, "a DC blocker in front of detection").  Every sample leaves less the mean of
 /// the `blocks` complete 64-sample blocks in front of its own block; the pushes of one filter, concatenated, equal `ofdm_dc_block` of the

@@ -1161,6 +1161,81 @@ int ofdm_dcblock_state(const ofdm_dcblock *f, int64_t *total, int32_t *blocks);
 int ofdm_stream_set_dc_block(ofdm_stream *s, int32_t blocks);
 int ofdm_stream_get_dc_block(const ofdm_stream *s, int32_t *blocks);
 
+/* ------------------------------------------------------------------ a digital down-converter: tune, filter, decimate (EXT-16)
+ * A radio delivers a few fixed rates, is usually tuned off-centre (LO leakage, 1/f noise), and the band it hands over often holds a
+ * neighbour.  The down-converter shifts the wanted signal to 0, low-passes and keeps every D-th sample, so that everything behind it
+ * runs at the modem's own rate.  Opt-in everywhere; off, nothing changes.
+ *
+ * Definition (numpy: tests/ddc_ref.py; parity with the reference is unpinned: it has nothing of the kind).  IEEE basic operations only,
+ * so host, device and numpy agree bit for bit:
+ *     inputs      x[0 .. n) fc32 -- an sc16 stream first widened as ofdm_sc16_widen does, one rounded product; decim = D, 1 .. 64;
+ *                 h[0 .. T) real f32 taps, D <= T <= 4096; phase_inc, any int32, taken mod 2^20.
+ *     rotors      C[i] = (f32 cos(2 pi i / 1024), f32 sin(2 pi i / 1024)), F[i] = (f32 cos(2 pi i / 2^20), f32 sin(2 pi i / 2^20)), i < 1024:
+ *                 formed once in f64 on the host and rounded to f32; ofdm_ddc_rotor_tables hands out the very bytes the host definition
+ *                 uses and the device is given (coarse, fine: 2048 floats each, re and im interleaved).
+ *     a (x) b     re = fmaf(a.re, b.re, -(a.im * b.im)), im = fmaf(a.re, b.im, a.im * b.re); the inner product is ONE rounded f32
+ *                 multiply, nothing else is contracted.
+ *     mixer       sample n (the absolute index since create / reset, int64) has the phase p = (n * phase_inc) mod 2^20 in exact integer
+ *                 arithmetic; r = C[p >> 10] (x) F[p & 1023]; v[n] = x[n] (x) r.
+ *     filter      y[m] = sum_{k = 0}^{T - 1} h[k] v[m D + k] for 0 <= m < M(n); M(n) = 0 for n < T, else (n - T) / D + 1.  Each part
+ *                 starts from +0.0 and runs in ascending k as acc = fmaf(h[k], v.part, acc).  No zero padding, no latency bookkeeping:
+ *                 an output exists when its T inputs exist.
+ * Nothing is special-cased for non-finite samples: a NaN at sample n spoils exactly the outputs whose window holds n.
+ *
+ * ofdm_ddc / ofdm_ddc_sc16: the definition on host arrays, one whole stream, no GPU.  out receives M(n) samples (*n_out; out_cap < M(n):
+ * OFDM_ERR_INVALID, nothing written).  ofdm_ddc_out_len: M(n), or OFDM_ERR_INVALID (< 0) for arguments the others refuse.
+ * ofdm_ddc_inc_for: the increment that brings f0 (cycles per input sample) to 0, (-rint(f0 2^20)) mod 2^20; OFDM_ERR_INVALID for a
+ * non-finite f0 or |f0| > 0.5.  ofdm_ddc_design: a Hamming-windowed sinc of T = taps_per_phase D taps (taps_per_phase 1 .. 64) with the
+ * cutoff 0.5 / D, formed in f64, normalised to sum 1, rounded to f32: h[k] = w(k) sinc((k - (T - 1) / 2) / D), w(k) = 0.54 - 0.46
+ * cos(2 pi k / (T - 1)) (T = 1: h = [1]).  The taps are an input of everything else, as the pilot tables are: a caller may bring its own.
+ * OFDM_ERR_INVALID: n < 0, decim outside 1 .. 64, n_taps outside decim .. 4096, a NULL array that is needed, a bad sc16 scale;
+ * OFDM_ERR_UNSUPPORTED: n beyond 2^40.
+ *
+ * The handle (ofdm_ddc_create .. ofdm_ddc_state) is the converter on DEVICE buffers, enqueued on the context's stream: the outputs of
+ * a handle's pushes, concatenated, equal ofdm_ddc of the concatenated inputs bit for bit, however the stream is cut.  A push of n
+ * samples writes M(total + n) - M(total) outputs (*n_out; out_cap below that: OFDM_ERR_INVALID, nothing is launched).  One launch per
+ * piece (k_ddc<fc32> / k_ddc<sc16>; a push longer than max_chunk is walked in pieces, ofdm_last_dispatch names the first).  The handle
+ * owns its state -- the taps, the rotor tables and the last <= T - 1 raw samples, the latter double-buffered and written by the same
+ * launch -- and allocates nothing after create; destroy it BEFORE its context.  in_dev is on 8 bytes (sc16: 4), out_dev on 8, and they do
+ * not overlap.  ofdm_ddc_state: the samples taken and the samples given since create / reset.
+ * OFDM_ERR_INVALID: a NULL handle or context, the argument ranges above, max_chunk <= 0, n < 0, a NULL or misaligned buffer with n > 0,
+ * in_dev and out_dev overlapping; OFDM_ERR_UNSUPPORTED: max_chunk or n beyond 2^40.
+ *
+ * ofdm_stream_set_ddc: the converter in front of a stream (decim = 0: off, the default, and then bit for bit the stream without it;
+ * taps NULL with n_taps = 0: ofdm_ddc_design with OFDM_DDC_TAPS_PER_PHASE).  Only while the stream's total is 0, else OFDM_ERR_INVALID;
+ * ofdm_stream_reset keeps the setting and clears the history.  The first setting that is not 0 allocates the converter's state and a
+ * staging buffer (OFDM_ERR_NOMEM), kept until ofdm_stream_destroy.  Pushes are then INPUT-rate samples (at most max_chunk a piece);
+ * per piece k_ddc<fc32> / <sc16> runs between the upload and everything the stream did before, and leads the dispatch string; the DC
+ * blocker, if set, runs on the converter's output.  T, H, holdoff, first_sample, the totals of ofdm_stream_state and every offset are in
+ * OUTPUT samples, and the contract of EXT-14 carries over word for word on the converted samples: the packets are those of ONE
+ * ofdm_rx_decode_all_long_host on ofdm_ddc(concatenation) -- ofdm_ddc_sc16 for sc16 pushes, ofdm_dc_block of that if the DC blocker is
+ * set -- each delivered exactly once; packet k arrives with the first push after which the output count reaches d1_k + H, or with the
+ * flush.  ofdm_stream_get_ddc: decim, phase_inc (mod 2^20) and n_taps of the setting (any may be NULL).
+ * Not covered: several channels from one read of the input (a polyphase channeliser), rational resampling, complex taps, a phase
+ * offset, chunks already on the device, the converter on batches of rows, OFDM_SYNC_REFERENCE. */
+#define OFDM_DDC_TAPS_PER_PHASE 24
+#define OFDM_DDC_MAX_DECIM 64
+#define OFDM_DDC_MAX_TAPS 4096
+int ofdm_ddc_rotor_tables(float *coarse, float *fine);
+int64_t ofdm_ddc_out_len(int64_t n, int32_t decim, int32_t n_taps);
+int ofdm_ddc_inc_for(double f0_cycles_per_sample, int32_t *inc);
+int ofdm_ddc_design(int32_t decim, int32_t taps_per_phase, float *taps);
+int ofdm_ddc(const ofdm_fc32 *in, int64_t n, int32_t decim, int32_t phase_inc, const float *taps, int32_t n_taps, ofdm_fc32 *out,
+             int64_t out_cap, int64_t *n_out);
+int ofdm_ddc_sc16(const ofdm_sc16 *in, int64_t n, float scale, int32_t decim, int32_t phase_inc, const float *taps, int32_t n_taps,
+                  ofdm_fc32 *out, int64_t out_cap, int64_t *n_out);
+typedef struct ofdm_ddc_handle ofdm_ddc_handle;
+int ofdm_ddc_create(ofdm_ddc_handle **out, ofdm_ctx *ctx, int32_t decim, int32_t phase_inc, const float *taps, int32_t n_taps,
+                    int64_t max_chunk);
+int ofdm_ddc_destroy(ofdm_ddc_handle *h);
+int ofdm_ddc_reset(ofdm_ddc_handle *h);
+int ofdm_ddc_push(ofdm_ddc_handle *h, const ofdm_fc32 *in_dev, int64_t n, ofdm_fc32 *out_dev, int64_t out_cap, int64_t *n_out);
+int ofdm_ddc_push_sc16(ofdm_ddc_handle *h, const ofdm_sc16 *in_dev, int64_t n, float scale, ofdm_fc32 *out_dev, int64_t out_cap,
+                       int64_t *n_out);
+int ofdm_ddc_state(const ofdm_ddc_handle *h, int64_t *total_in, int64_t *total_out);
+int ofdm_stream_set_ddc(ofdm_stream *s, int32_t decim, int32_t phase_inc, const float *taps, int32_t n_taps);
+int ofdm_stream_get_ddc(const ofdm_stream *s, int32_t *decim, int32_t *phase_inc, int32_t *n_taps);
+
 /* ------------------------------------------------------------------ loop-back test bench
  * channel (src/channel.rs:33-74), per frame:
  *     y = convolve(tx, CHANNEL)                          tx_len + 63 samples (CHANNEL: the 64 taps of channel.rs:26-31)

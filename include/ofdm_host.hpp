@@ -642,6 +642,18 @@ class Stream {
         check(ofdm_stream_get_dc_block(s_, &m), "ofdm_stream_get_dc_block");
         return m;
     }
+    // EXT-16: the down-converter in front of everything else (decim 0 = off; taps empty: the default design).  Pushes are then
+    // input-rate samples; holdoff, first_sample and every offset are in OUTPUT samples.  Only before the first sample or right after
+    // reset(), which keeps the setting and clears the history
+    void set_ddc(int32_t decim, int32_t phase_inc = 0, const std::vector<float> &taps = {}) {
+        check(ofdm_stream_set_ddc(s_, decim, phase_inc, taps.empty() ? nullptr : taps.data(), (int32_t)taps.size()), "ofdm_stream_set_ddc");
+    }
+    struct DdcSetting { int32_t decim = 0, phase_inc = 0, n_taps = 0; };
+    DdcSetting ddc() const {
+        DdcSetting d;
+        check(ofdm_stream_get_ddc(s_, &d.decim, &d.phase_inc, &d.n_taps), "ofdm_stream_get_ddc");
+        return d;
+    }
     State state() const {
         State st; int32_t ended = 0;
         check(ofdm_stream_state(s_, &st.total, &st.kept_from, &st.next_lag, &ended), "ofdm_stream_state");
@@ -716,6 +728,77 @@ class DcBlock {
 
   private:
     ofdm_dcblock *f_ = nullptr;
+};
+
+// EXT-16: a digital down-converter on device buffers (ofdm_ddc_create .. ofdm_ddc_state, include/ofdm_hip.h "a digital
+// down-converter"): mix by the two-level 20-bit rotor, filter by real taps, keep every decim-th sample.  The outputs of one converter's
+// pushes, concatenated, equal ofdm_ddc of the concatenated inputs bit for bit.  in_dev and out_dev are device buffers that do not overlap;
+// the launches are enqueued on the context's stream.  Destroy it before its context.
+class Ddc {
+  public:
+    struct State { int64_t total_in = 0, total_out = 0; };
+    // the Hamming-windowed sinc of taps_per_phase * decim taps, cutoff 0.5 / decim
+    static std::vector<float> design(int32_t decim, int32_t taps_per_phase = OFDM_DDC_TAPS_PER_PHASE) {
+        std::vector<float> h(decim > 0 && taps_per_phase > 0 ? (size_t)decim * (size_t)taps_per_phase : 1);
+        check(ofdm_ddc_design(decim, taps_per_phase, h.data()), "ofdm_ddc_design");
+        return h;
+    }
+    // the increment that brings f0 (cycles per input sample) to 0
+    static int32_t inc_for(double f0) {
+        int32_t inc = 0;
+        check(ofdm_ddc_inc_for(f0, &inc), "ofdm_ddc_inc_for");
+        return inc;
+    }
+    static int64_t out_len(int64_t n, int32_t decim, int32_t n_taps) {
+        const int64_t m = ofdm_ddc_out_len(n, decim, n_taps);
+        check(m < 0 ? (int)m : OFDM_OK, "ofdm_ddc_out_len");
+        return m;
+    }
+    // the rotor tables the host definition uses and the device is given: 1024 (re, im) pairs each
+    static void rotor_tables(std::vector<float> &coarse, std::vector<float> &fine) {
+        coarse.resize(2048); fine.resize(2048);
+        check(ofdm_ddc_rotor_tables(coarse.data(), fine.data()), "ofdm_ddc_rotor_tables");
+    }
+    Ddc(Context &ctx, int32_t decim, int32_t phase_inc, const std::vector<float> &taps, int64_t max_chunk = 1 << 20) {
+        check(ofdm_ddc_create(&f_, ctx.raw(), decim, phase_inc, taps.data(), (int32_t)taps.size(), max_chunk), "ofdm_ddc_create");
+    }
+    ~Ddc() { if (f_) ofdm_ddc_destroy(f_); }
+    Ddc(const Ddc &) = delete;
+    Ddc &operator=(const Ddc &) = delete;
+    // -> the samples written at out_dev (out_cap: what it holds)
+    int64_t push(const ofdm_fc32 *in_dev, int64_t n, ofdm_fc32 *out_dev, int64_t out_cap) {
+        int64_t k = 0;
+        check(ofdm_ddc_push(f_, in_dev, n, out_dev, out_cap, &k), "ofdm_ddc_push");
+        return k;
+    }
+    int64_t push_sc16(const ofdm_sc16 *in_dev, int64_t n, ofdm_fc32 *out_dev, int64_t out_cap, float scale = OFDM_SC16_DEFAULT_SCALE) {
+        int64_t k = 0;
+        check(ofdm_ddc_push_sc16(f_, in_dev, n, scale, out_dev, out_cap, &k), "ofdm_ddc_push_sc16");
+        return k;
+    }
+    void reset() { check(ofdm_ddc_reset(f_), "ofdm_ddc_reset"); }
+    State state() const {
+        State st;
+        check(ofdm_ddc_state(f_, &st.total_in, &st.total_out), "ofdm_ddc_state");
+        return st;
+    }
+    // the definition on host arrays, no GPU
+    static std::vector<ofdm_fc32> host(const ofdm_fc32 *in, int64_t n, int32_t decim, int32_t phase_inc, const std::vector<float> &taps) {
+        std::vector<ofdm_fc32> out((size_t)out_len(n, decim, (int32_t)taps.size()));
+        int64_t k = 0;
+        check(ofdm_ddc(in, n, decim, phase_inc, taps.data(), (int32_t)taps.size(), out.data(), (int64_t)out.size(), &k), "ofdm_ddc");
+        return out;
+    }
+    static std::vector<ofdm_fc32> host_sc16(const ofdm_sc16 *in, int64_t n, int32_t decim, int32_t phase_inc, const std::vector<float> &taps,
+                                            float scale = OFDM_SC16_DEFAULT_SCALE) {
+        std::vector<ofdm_fc32> out((size_t)out_len(n, decim, (int32_t)taps.size()));
+        int64_t k = 0;
+        check(ofdm_ddc_sc16(in, n, scale, decim, phase_inc, taps.data(), (int32_t)taps.size(), out.data(), (int64_t)out.size(), &k), "ofdm_ddc_sc16");
+        return out;
+    }
+
+  private:
+    ofdm_ddc_handle *f_ = nullptr;
 };
 
 // One context per (thread, parameter set), created on first use and kept: the reference's free functions are called once per

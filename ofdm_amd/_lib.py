@@ -171,6 +171,21 @@ SIGNATURES = {
     "ofdm_dcblock_state": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i32)]),
     "ofdm_stream_set_dc_block": (C.c_int, [vp, i32]),
     "ofdm_stream_get_dc_block": (C.c_int, [vp, C.POINTER(i32)]),
+    # EXT-16: a digital down-converter (host definition and design; a handle on device buffers, its own type first; the stream option)
+    "ofdm_ddc_rotor_tables": (C.c_int, [vp, vp]),
+    "ofdm_ddc_out_len": (i64, [i64, i32, i32]),
+    "ofdm_ddc_inc_for": (C.c_int, [C.c_double, C.POINTER(i32)]),
+    "ofdm_ddc_design": (C.c_int, [i32, i32, vp]),
+    "ofdm_ddc": (C.c_int, [vp, i64, i32, i32, vp, i32, vp, i64, C.POINTER(i64)]),
+    "ofdm_ddc_sc16": (C.c_int, [vp, i64, C.c_float, i32, i32, vp, i32, vp, i64, C.POINTER(i64)]),
+    "ofdm_ddc_create": (C.c_int, [C.POINTER(vp), vp, i32, i32, vp, i32, i64]),
+    "ofdm_ddc_destroy": (C.c_int, [vp]),
+    "ofdm_ddc_reset": (C.c_int, [vp]),
+    "ofdm_ddc_push": (C.c_int, [vp, vp, i64, vp, i64, C.POINTER(i64)]),
+    "ofdm_ddc_push_sc16": (C.c_int, [vp, vp, i64, C.c_float, vp, i64, C.POINTER(i64)]),
+    "ofdm_ddc_state": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
+    "ofdm_stream_set_ddc": (C.c_int, [vp, i32, i32, vp, i32]),
+    "ofdm_stream_get_ddc": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "ofdm_hbm_read_probe": (C.c_int, [vp, vp, i64, i32]),
     "ofdm_timer_start": (C.c_int, [vp]),
     "ofdm_timer_stop_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),

@@ -225,6 +225,71 @@ def dc_block_host(samples, blocks: int, scale: Optional[float] = None) -> np.nda
     return out
 
 
+DDC_TAPS_PER_PHASE = 24
+DDC_PHASE_MOD = 1 << 20
+
+
+def ddc_rotor_tables():
+    """ofdm_ddc_rotor_tables (EXT-16): the coarse and the fine rotor table, complex64 [1024] each -- the bytes the host definition uses
+    and the device is given"""
+    lib = _lib.load()
+    c, f = np.empty(1024, np.complex64), np.empty(1024, np.complex64)
+    _check(lib, lib.ofdm_ddc_rotor_tables(_host(c), _host(f)), "ofdm_ddc_rotor_tables")
+    return c, f
+
+
+def ddc_out_len(n: int, decim: int, n_taps: int) -> int:
+    """ofdm_ddc_out_len (EXT-16): M(n), the outputs n input samples give: 0 for n < n_taps, else (n - n_taps) // decim + 1"""
+    lib = _lib.load()
+    m = int(lib.ofdm_ddc_out_len(int(n), int(decim), int(n_taps)))
+    _check(lib, min(m, 0), "ofdm_ddc_out_len")
+    return m
+
+
+def ddc_inc_for(f0: float) -> int:
+    """ofdm_ddc_inc_for (EXT-16): the phase increment that brings f0 (cycles per input sample, |f0| <= 0.5) to 0"""
+    lib = _lib.load()
+    inc = C.c_int32()
+    _check(lib, lib.ofdm_ddc_inc_for(float(f0), C.byref(inc)), "ofdm_ddc_inc_for")
+    return int(inc.value)
+
+
+def ddc_design(decim: int, taps_per_phase: int = DDC_TAPS_PER_PHASE) -> np.ndarray:
+    """ofdm_ddc_design (EXT-16): the Hamming-windowed sinc of taps_per_phase * decim taps with the cutoff 0.5 / decim, float32"""
+    lib = _lib.load()
+    if not (1 <= int(decim) <= 64 and 1 <= int(taps_per_phase) <= 64):
+        raise OfdmError("ddc_design: decim and taps_per_phase are 1 .. 64")
+    taps = np.empty(int(decim) * int(taps_per_phase), np.float32)
+    _check(lib, lib.ofdm_ddc_design(int(decim), int(taps_per_phase), _host(taps)), "ofdm_ddc_design")
+    return taps
+
+
+def _ddc_taps(decim: int, taps) -> np.ndarray:
+    return ddc_design(decim) if taps is None else np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+
+
+def ddc_host(samples, decim: int, phase_inc: int = 0, taps=None, scale: Optional[float] = None) -> np.ndarray:
+    """ofdm_ddc / ofdm_ddc_sc16 (EXT-16): the definition of the down-converter on one whole stream, on the host, no GPU: complex64 [n]
+    in, complex64 [M(n)] out.  taps None: ddc_design(decim).  An int16 array of shape [n, 2] takes scale= and is widened by
+    ofdm_sc16_widen's rule first."""
+    lib = _lib.load()
+    h = _ddc_taps(decim, taps)
+    n_out = C.c_int64()
+    inc = int(phase_inc) % DDC_PHASE_MOD
+    if np.asarray(samples).dtype == np.int16:
+        if scale is None:
+            raise OfdmError("ddc_host: int16 samples need scale=")
+        a = _sc16_host(samples, "ddc_host").reshape(-1, 2)
+        out = np.empty(max(a.shape[0] // max(int(decim), 1) + 1, 1), np.complex64)
+        _check(lib, lib.ofdm_ddc_sc16(_host(a), a.shape[0], float(scale), int(decim), inc, _host(h), h.size, _host(out), out.size,
+                                      C.byref(n_out)), "ofdm_ddc_sc16")
+        return out[: int(n_out.value)].copy()
+    x = np.ascontiguousarray(samples, dtype=np.complex64).reshape(-1)
+    out = np.empty(max(x.size // max(int(decim), 1) + 1, 1), np.complex64)
+    _check(lib, lib.ofdm_ddc(_host(x), x.size, int(decim), inc, _host(h), h.size, _host(out), out.size, C.byref(n_out)), "ofdm_ddc")
+    return out[: int(n_out.value)].copy()
+
+
 def _host(a: Optional[np.ndarray]):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
@@ -1259,11 +1324,14 @@ class Context:
                 "d_hat": dh[:n], "lag_lo": lo[:n], "next_lag_lo": int(lo[n]), "more": bool(more.value)}
 
     def stream(self, max_symbols: int, holdoff: Optional[int] = None, max_chunk: int = 65536, first_sample: int = 0,
-               dc_blocks: int = 0) -> "Stream":
+               dc_blocks: int = 0, ddc=None) -> "Stream":
         """ofdm_stream_create (EXT-14): a streaming receiver on this context -- push chunks as a radio hands them over, get every packet
         exactly once, bit for bit the packets of decode_all_host on the concatenation.  holdoff None: default_holdoff().
         dc_blocks (EXT-15, 0 = off): the DC blocker in front of the window; the packets are then those of decode_all_host on
-        dc_block_host(concatenation, dc_blocks)."""
+        dc_block_host(concatenation, dc_blocks).
+        ddc (EXT-16, None = off): (decim, f0, taps) -- the down-converter in front of everything else: pushes are input-rate samples
+        with the signal at f0 cycles per sample, the packets are those of decode_all_host on ddc_host(concatenation, decim,
+        ddc_inc_for(f0), taps) (taps None: ddc_design(decim)); holdoff, first_sample and every offset are in OUTPUT samples."""
         import weakref
 
         s = Stream(self, max_symbols, self.default_holdoff() if holdoff is None else holdoff, max_chunk, first_sample)
@@ -1272,7 +1340,26 @@ class Context:
         self._streams.add(s)
         if dc_blocks:
             s.set_dc_block(dc_blocks)
+        if ddc is not None:
+            decim, f0, taps = (tuple(ddc) + (None, None))[:3]
+            s.set_ddc(decim, ddc_inc_for(f0 or 0.0), taps)
         return s
+
+    def ddc(self, decim: int, phase_inc: int = 0, taps=None, max_chunk: int = 1 << 20) -> "Ddc":
+        """ofdm_ddc_create (EXT-16): a stateful down-converter on device buffers -- the outputs of its pushes, concatenated, are ddc_host
+        of the concatenated inputs bit for bit.  taps None: ddc_design(decim).  Close it before its context."""
+        import weakref
+
+        f = Ddc(self, decim, phase_inc, _ddc_taps(decim, taps), max_chunk)
+        if not hasattr(self, "_streams"):
+            self._streams = weakref.WeakSet()
+        self._streams.add(f)
+        return f
+
+    def ddc_once(self, samples, decim: int, phase_inc: int = 0, taps=None, scale: Optional[float] = None) -> torch.Tensor:
+        """One shot: a whole stream (complex64, or int16 [n, 2] with scale=) through a fresh down-converter -> complex64 device tensor."""
+        with self.ddc(decim, phase_inc, taps) as f:
+            return f.push(samples, scale=scale)
 
     def dc_filter(self, blocks: Optional[int] = None, max_chunk: int = 1 << 20) -> "DcBlock":
         """ofdm_dcblock_create (EXT-15): a stateful DC blocker on device buffers -- its pushes, concatenated, are dc_block_host of the
@@ -1407,6 +1494,72 @@ class DcBlock:
         return {"total": int(t.value), "blocks": int(m.value)}
 
 
+class Ddc:
+    """`ofdm_ddc_handle` (EXT-16, include/ofdm_hip.h "a digital down-converter"): Context.ddc(...) makes one.  Mix by the two-level
+    20-bit rotor, filter by real taps, keep every decim-th sample; however the stream is cut into pushes, the outputs concatenated are
+    ddc_host of the inputs concatenated."""
+
+    def __init__(self, ctx: "Context", decim: int, phase_inc: int, taps: np.ndarray, max_chunk: int):
+        self.ctx, self.lib = ctx, ctx.lib
+        h = C.c_void_p()
+        self.decim, self.phase_inc, self.n_taps = int(decim), int(phase_inc) % DDC_PHASE_MOD, int(taps.size)
+        ctx._ck(self.lib.ofdm_ddc_create(C.byref(h), ctx.h, self.decim, self.phase_inc, _host(taps), self.n_taps, int(max_chunk)),
+                "ofdm_ddc_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ofdm_ddc_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push(self, samples, scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ofdm_ddc_push / _push_sc16: complex64 samples (a device tensor, or a host array that is uploaded), or int16 [n, 2] with
+        scale=, -> the converted complex64 device tensor, as long as this push gave outputs (out=: written from its start; it may not
+        overlap the input and must hold them).  Asynchronous."""
+        ctx = self.ctx
+        t = samples if isinstance(samples, torch.Tensor) else ctx.to_device(np.asarray(samples))
+        sc16 = t.dtype == torch.int16
+        if sc16:
+            if scale is None:
+                raise OfdmError("Ddc.push: int16 samples need scale=")
+            t = ctx._sc16(t).reshape(-1, 2)
+            n = t.shape[0]
+        else:
+            t = ctx._cx(t).reshape(-1)
+            n = t.numel()
+        st = self.state()
+        want = ddc_out_len(st["total_in"] + n, self.decim, self.n_taps) - st["total_out"]
+        out = ctx.empty((want,), torch.complex64) if out is None else ctx._cx(out).reshape(-1)
+        got = C.c_int64()
+        if sc16:
+            ctx._ck(self.lib.ofdm_ddc_push_sc16(self.h, _dev(t), n, float(scale), _dev(out), out.numel(), C.byref(got)), "ofdm_ddc_push_sc16")
+        else:
+            ctx._ck(self.lib.ofdm_ddc_push(self.h, _dev(t), n, _dev(out), out.numel(), C.byref(got)), "ofdm_ddc_push")
+        return out[: int(got.value)]
+
+    def reset(self):
+        self.ctx._ck(self.lib.ofdm_ddc_reset(self.h), "ofdm_ddc_reset")
+
+    def state(self) -> dict:
+        """ofdm_ddc_state -> total_in (samples pushed since create / reset), total_out (samples given)"""
+        a, b = C.c_int64(), C.c_int64()
+        self.ctx._ck(self.lib.ofdm_ddc_state(self.h, C.byref(a), C.byref(b)), "ofdm_ddc_state")
+        return {"total_in": int(a.value), "total_out": int(b.value)}
+
+
 class Stream:
     """`ofdm_stream` (EXT-14, include/ofdm_hip.h "a streaming receiver"): Context.stream(...) makes one.  However the samples are cut into
     pushes, the packets delivered are those of Context.decode_all_host on the concatenation, each exactly once; packet k arrives with the
@@ -1499,6 +1652,22 @@ class Stream:
         self.ctx._ck(self.lib.ofdm_stream_get_dc_block(self.h, C.byref(m)), "ofdm_stream_get_dc_block")
         return int(m.value)
 
+    def set_ddc(self, decim: int, phase_inc: int = 0, taps=None):
+        """ofdm_stream_set_ddc (EXT-16): the down-converter in front of everything else, decim 0 = off; taps None: the default design;
+        only before the first sample (or right after reset(), which keeps the setting and clears the history)"""
+        if not decim:
+            self.ctx._ck(self.lib.ofdm_stream_set_ddc(self.h, 0, 0, None, 0), "ofdm_stream_set_ddc")
+            return
+        h = None if taps is None else np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        self.ctx._ck(self.lib.ofdm_stream_set_ddc(self.h, int(decim), int(phase_inc) % DDC_PHASE_MOD, _host(h), 0 if h is None else h.size),
+                     "ofdm_stream_set_ddc")
+
+    def get_ddc(self) -> dict:
+        """ofdm_stream_get_ddc -> decim (0 = off), phase_inc, n_taps"""
+        d, i, t = C.c_int32(), C.c_int32(), C.c_int32()
+        self.ctx._ck(self.lib.ofdm_stream_get_ddc(self.h, C.byref(d), C.byref(i), C.byref(t)), "ofdm_stream_get_ddc")
+        return {"decim": int(d.value), "phase_inc": int(i.value), "n_taps": int(t.value)}
+
     def state(self) -> dict:
         """ofdm_stream_state -> total (samples pushed), kept_from (first sample the window keeps), next_lag (where the walk resumes),
         ended; all stream-relative"""
@@ -1517,12 +1686,13 @@ def _packet_dicts(res: dict):
 
 def receive_stream(chunks, max_symbols: int, guard_bands: bool = False, modulation: int = BPSK, n_fft: int = 64, ecc: int = ECC_NONE,
                    holdoff: Optional[int] = None, max_chunk: int = 65536, first_sample: int = 0, sc16_scale: Optional[float] = None,
-                   dc_blocks: int = 0, **kw):
+                   dc_blocks: int = 0, ddc=None, **kw):
     """A generator over an iterable of chunks (complex64 arrays, or int16 [n, 2] arrays with sc16_scale=): yields one dict per packet
     (bytes, status, offset, f_delta, metric, d1, d_hat) as soon as the stream commits it, and flushes when the iterable ends.
-    dc_blocks (EXT-15, 0 = off): the DC blocker in front of the stream's window."""
+    dc_blocks (EXT-15, 0 = off): the DC blocker in front of the stream's window.
+    ddc (EXT-16, None = off): (decim, f0, taps) -- the chunks are input-rate samples, down-converted in front of everything else."""
     ctx = _ctx(n_fft, modulation, guard_bands, ecc, **kw)
-    with ctx.stream(max_symbols, holdoff, max_chunk, first_sample, dc_blocks=dc_blocks) as s:
+    with ctx.stream(max_symbols, holdoff, max_chunk, first_sample, dc_blocks=dc_blocks, ddc=ddc) as s:
         for chunk in chunks:
             yield from _packet_dicts(s.push_all(chunk, sc16_scale=sc16_scale))
         yield from _packet_dicts(s.flush())
@@ -1660,7 +1830,7 @@ def decode_long(samples, guard_bands: Optional[bool] = None, modulation: Optiona
 
 def decode_all(samples, guard_bands: Optional[bool] = None, modulation: Optional[int] = None, n_fft: int = 64, ecc: int = ECC_NONE,
                fcs: bool = False, holdoff: Optional[int] = None, max_packets: int = 4096, max_symbols: Optional[int] = None,
-               lag_lo: int = 0, lag_hi: int = 0, device: int = 0, batched: bool = False, dc_blocks: int = 0, **sync) -> list:
+               lag_lo: int = 0, lag_hi: int = 0, device: int = 0, batched: bool = False, dc_blocks: int = 0, ddc=None, **sync) -> list:
     """EVERY packet of one long capture (EXT-12): one scan for all detections (Context.sc_scan_long: three launches, one
     synchronisation), then decode_long(lag_lo = where the search for packet k started) per detection.  -> a list of per-packet dicts
     (bytes: the payload as `bytes`, empty unless status == FRAME_OK; len, status, offset into the capture, f_delta, metric, d1, d_hat),
@@ -1679,12 +1849,19 @@ def decode_all(samples, guard_bands: Optional[bool] = None, modulation: Optional
     gather the capture once per packet).
 
     dc_blocks (EXT-15, 0 = off): the capture goes through the DC blocker on the device first (Context.dc_block) -- for captures of a
-    direct-conversion radio, whose LO leakage fires the detector on noise; frames need guard bands (the DC bin then carries nothing)."""
+    direct-conversion radio, whose LO leakage fires the detector on noise; frames need guard bands (the DC bin then carries nothing).
+
+    ddc (EXT-16, None = off): (decim, f0, taps) -- the capture is input-rate samples with the signal at f0 cycles per sample; it goes
+    through the down-converter on the device first (Context.ddc_once; taps None: ddc_design(decim)), in front of the DC blocker, and
+    every offset and lag is in OUTPUT samples."""
     if batched and max_symbols is None:
         raise OfdmError("decode_all(batched=True) requires max_symbols: the data symbols of the longest frame expected")
     ctx = _ctx(n_fft, BPSK if modulation is None else modulation, bool(guard_bands), _with_fcs(ecc, fcs), device=device, **sync)
     x = samples if isinstance(samples, torch.Tensor) else ctx.to_device(np.asarray(samples))
     x = x.reshape(-1)
+    if ddc is not None:
+        decim, f0, taps = (tuple(ddc) + (None, None))[:3]
+        x = ctx.ddc_once(x, decim, ddc_inc_for(f0 or 0.0), taps)
     if dc_blocks:
         x = ctx.dc_block(x, dc_blocks)
     if holdoff is None:

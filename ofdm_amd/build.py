@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "libofdm_hip.so")
 # in; used by tools/ only (ofdm_amd._lib.use_profile_build()), never by the tests, the bench line or smoke()
 LIB_PROFILE = os.path.join(HERE, "libofdm_hip_profile.so")
 OBJ_PROFILE = os.path.join(CSRC, "_obj_profile")
-SOURCES = ["kernels_sym.hip", "kernels_n64.hip", "kernels_n64_sc16.hip", "kernels_n64_tx_sc16.hip", "kernels_sc16.hip", "kernels_n4096.hip", "kernels_rx1024.hip", "kernels_mid.hip", "kernels_sync.hip", "kernels_sc80.hip", "kernels_scstream.hip", "kernels_scbig.hip", "kernels_scscan.hip", "kernels_packets.hip", "kernels_stream.hip", "kernels_dcblock.hip", "kernels_bytes.hip", "kernels_conv.hip", "kernels_rs.hip", "kernels_chest.hip", "kernels_fcs.hip", "kernels_ldpc.hip", "kernels_quality.hip", "kernels_combine.hip", "kernels_cfowide.hip", "kernels_noise.hip", "ofdm_abi.hip", "ofdm_host_path.hip", "outer_code.hip", "ldpc_code.hip"]
+SOURCES = ["kernels_sym.hip", "kernels_n64.hip", "kernels_n64_sc16.hip", "kernels_n64_tx_sc16.hip", "kernels_sc16.hip", "kernels_n4096.hip", "kernels_rx1024.hip", "kernels_mid.hip", "kernels_sync.hip", "kernels_sc80.hip", "kernels_scstream.hip", "kernels_scbig.hip", "kernels_scscan.hip", "kernels_packets.hip", "kernels_stream.hip", "kernels_dcblock.hip", "kernels_ddc.hip", "kernels_bytes.hip", "kernels_conv.hip", "kernels_rs.hip", "kernels_chest.hip", "kernels_fcs.hip", "kernels_ldpc.hip", "kernels_quality.hip", "kernels_combine.hip", "kernels_cfowide.hip", "kernels_noise.hip", "ofdm_abi.hip", "ofdm_host_path.hip", "outer_code.hip", "ldpc_code.hip"]
 HEADERS = ["device_common.hpp", "wave_ops.hpp", "sc_common.hpp", "kernels.hpp", "ofdm_ctx.hpp", "ofdm_hip_tuning.h", "ldpc_table.h", os.path.join("..", "..", "include", "ofdm_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 # per-file additions.  Every kernel file but kernels_bytes.hip; measured on kernels_sync.hip: the SLP vectoriser pairs f32 ops into

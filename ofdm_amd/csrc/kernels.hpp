@@ -493,6 +493,27 @@ struct DcBlockParams {
     float2 *open_new = nullptr;          // ... the (t0 + n) % 64 behind it; written whenever that is not 0
 };
 hipError_t run_dc_block(const DcBlockParams &p, bool sc16, int num_cu, hipStream_t st);
+// ---- EXT-16 the down-converter (ofdm_ddc_push, ofdm_stream_set_ddc; kernels_ddc.hip, definition: tests/ddc_ref.py).
+// k_ddc<fc32> / <sc16>, one launch: out[m - M(t0)] = y[m] for M(t0) <= m < M(t0 + n) (M: ddc_out_len), and the raw samples behind the
+// piece's last output into carry_new.  in and out do not overlap; the two carries are distinct.
+constexpr int kDdcMaxDecim = 64, kDdcMaxTaps = 4096;
+constexpr long long kDdcPhaseMask = (1 << 20) - 1;
+inline long long ddc_out_len(long long n, int decim, int n_taps) { return n < n_taps ? 0 : (n - n_taps) / decim + 1; }
+struct DdcParams {
+    const Tuning *tune = nullptr;
+    Trace *trace = nullptr;
+    const void *in = nullptr;            // n samples: float2 (fc32, on 8 bytes) or int16 pairs (sc16, on 4 bytes)
+    float2 *out = nullptr;               // M(t0 + n) - M(t0) samples
+    long long n = 0, t0 = 0;             // t0: the samples of the converter's stream in front of the piece
+    float scale = 0.f;                   // sc16 only
+    int decim = 0, n_taps = 0;           // D, T
+    unsigned phase_inc = 0;              // mod 2^20
+    const float *taps = nullptr;         // [T]
+    const float2 *coarse = nullptr, *fine = nullptr; // [1024] each: the rotor tables
+    const float2 *carry_old = nullptr;   // the raw (widened) samples D M(t0) .. t0 - 1 of the stream
+    float2 *carry_new = nullptr;         // ... D M(t0 + n) .. t0 + n - 1; at most T - 1 of them
+};
+hipError_t run_ddc(const DdcParams &p, bool sc16, int num_cu, hipStream_t st);
 // base (optional): per-pair sample offset added to the pair's start; status (optional): pairs with status != 0 get 0
 hipError_t run_freq_correction(const float2 *in, long long n_pairs, long long stride, long long right_offset, int L,
                                double *f_delta, hipStream_t st, const int32_t *base = nullptr, const int32_t *status = nullptr);

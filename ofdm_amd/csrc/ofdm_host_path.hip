@@ -1116,6 +1116,246 @@ int ofdm_dcblock_state(const ofdm_dcblock *f, int64_t *total, int32_t *blocks) {
 
 } // extern "C"
 
+// ---- EXT-16: a digital down-converter (include/ofdm_hip.h, "a digital down-converter"; numpy restatement: tests/ddc_ref.py).  The host
+// functions are the definition in C++; the handle carries the state of k_ddc (kernels_ddc.hip) from piece to piece: the raw samples
+// behind the last output, in two copies -- a launch reads one and writes the other -- and the absolute sample index.
+struct ofdm_ddc_handle {
+    ofdm_ctx *c = nullptr;
+    int32_t D = 0, T = 0;
+    uint32_t inc = 0;           // mod 2^20
+    int64_t max_chunk = 0;
+    int64_t n_in = 0;           // samples pushed since create / reset
+    void *state = nullptr;      // ONE allocation: taps | coarse | fine | carry[0] | carry[1]
+    float *taps = nullptr;
+    float2 *coarse = nullptr, *fine = nullptr;
+    float2 *carry[2] = {nullptr, nullptr};
+    int cur = 0;                // the copy the next launch reads
+};
+
+namespace {
+
+// The rotor tables: formed once in f64, rounded to f32; these bytes are what the host definition uses and what a handle uploads
+struct DdcRotors {
+    float coarse[2048], fine[2048];
+    DdcRotors() {
+        const double two_pi = 6.283185307179586476925286766559;
+        for (int i = 0; i < 1024; i++) {
+            const double a = two_pi * (double)i / 1024.0, b = two_pi * (double)i / 1048576.0;
+            coarse[2 * i] = (float)std::cos(a); coarse[2 * i + 1] = (float)std::sin(a);
+            fine[2 * i] = (float)std::cos(b); fine[2 * i + 1] = (float)std::sin(b);
+        }
+    }
+};
+const DdcRotors &ddc_rotors() {
+    static const DdcRotors r;
+    return r;
+}
+
+bool ddc_args_ok(int32_t D, int32_t T) { return D >= 1 && D <= ofdm::kDdcMaxDecim && T >= D && T <= ofdm::kDdcMaxTaps; }
+
+// a (x) b of the definition.  The inner product is one rounded multiply: volatile keeps it out of any contraction
+inline ofdm_fc32 ddc_cmul(ofdm_fc32 a, ofdm_fc32 b) {
+    volatile float m0 = a.im * b.im, m1 = a.im * b.re;
+    ofdm_fc32 y;
+    y.re = std::fmaf(a.re, b.re, -m0);
+    y.im = std::fmaf(a.re, b.im, m1);
+    return y;
+}
+
+// The definition, one whole stream: load(i) -> sample i as fc32
+template <class Load> int ddc_host(int64_t n, int32_t D, uint32_t inc, const float *h, int32_t T, Load load, ofdm_fc32 *out, int64_t out_cap,
+                                   int64_t *n_out) {
+    if (n > kScanMaxSamples) return OFDM_ERR_UNSUPPORTED;
+    const int64_t M = ofdm::ddc_out_len(n, D, T);
+    if (n_out) *n_out = M;
+    if (M > out_cap || (M > 0 && !out)) return OFDM_ERR_INVALID;
+    if (M == 0) return OFDM_OK;
+    const DdcRotors &rot = ddc_rotors();
+    const ofdm_fc32 *C = reinterpret_cast<const ofdm_fc32 *>(rot.coarse), *F = reinterpret_cast<const ofdm_fc32 *>(rot.fine);
+    // the mixed samples under a block of outputs at a time
+    constexpr int64_t kBlock = 4096;
+    std::vector<ofdm_fc32> v;
+    try { v.resize((size_t)(kBlock * D + T)); } catch (const std::exception &) { return OFDM_ERR_NOMEM; }
+    for (int64_t m0 = 0; m0 < M; m0 += kBlock) { // outputs m0 .. m1 - 1 from the samples m0 D .. (m1 - 1) D + T - 1
+        const int64_t m1 = std::min(m0 + kBlock, M), i0 = m0 * D, span = (m1 - m0 - 1) * D + T;
+        for (int64_t s = 0; s < span; s++) {
+            const uint32_t p = ((uint32_t)(i0 + s) * inc) & (uint32_t)ofdm::kDdcPhaseMask; // 2^20 divides 2^32
+            v[(size_t)s] = ddc_cmul(load(i0 + s), ddc_cmul(C[p >> 10], F[p & 1023]));
+        }
+        for (int64_t m = m0; m < m1; m++) {
+            const ofdm_fc32 *w = v.data() + (m - m0) * D;
+            float re = 0.f, im = 0.f;
+            for (int32_t k = 0; k < T; k++) { re = std::fmaf(h[k], w[k].re, re); im = std::fmaf(h[k], w[k].im, im); }
+            out[m].re = re; out[m].im = im;
+        }
+    }
+    return OFDM_OK;
+}
+
+void ddc_free(ofdm_ddc_handle *f) {
+    if (f->state) hipFree(f->state);
+    f->state = nullptr;
+}
+
+// One piece (m samples at `in`, device memory) through k_ddc, behind the caller's entry scope; *n_out: what it wrote at `out`
+int ddc_piece(ofdm_ddc_handle *f, const void *in, int64_t m, bool sc16, float scale, float2 *out, int64_t *n_out) {
+    *n_out = 0;
+    if (m <= 0) return OFDM_OK; // no launch: the carry and the copy the next launch reads stay what they are
+    ofdm_ctx *c = f->c;
+    ofdm::DdcParams p;
+    p.tune = &c->tune; p.trace = &c->trace;
+    p.in = in; p.out = out; p.n = m; p.t0 = f->n_in; p.scale = scale; p.decim = f->D; p.n_taps = f->T; p.phase_inc = f->inc;
+    p.taps = f->taps; p.coarse = f->coarse; p.fine = f->fine;
+    p.carry_old = f->carry[f->cur]; p.carry_new = f->carry[f->cur ^ 1];
+    HIP_TRY(c, run_ddc(p, sc16, c->num_cu, c->stream));
+    f->cur ^= 1;
+    *n_out = ofdm::ddc_out_len(f->n_in + m, f->D, f->T) - ofdm::ddc_out_len(f->n_in, f->D, f->T);
+    f->n_in += m;
+    return OFDM_OK;
+}
+
+int ddc_push(ofdm_ddc_handle *f, const void *in, int64_t n, size_t ss, bool sc16, float scale, ofdm_fc32 *out, int64_t out_cap, int64_t *n_out) {
+    if (n_out) *n_out = 0;
+    if (!f || !f->c || n < 0 || out_cap < 0 || (n > 0 && !in) || (sc16 && !sc16_scale_ok(scale))) return OFDM_ERR_INVALID;
+    if (n == 0) return OFDM_OK;
+    if (n > kScanMaxSamples || f->n_in > INT64_MAX / 4 - n) return OFDM_ERR_UNSUPPORTED;
+    const int64_t M = ofdm::ddc_out_len(f->n_in + n, f->D, f->T) - ofdm::ddc_out_len(f->n_in, f->D, f->T);
+    if (M > out_cap || (M > 0 && !out)) return OFDM_ERR_INVALID;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(in), a1 = a0 + (size_t)n * ss, b0 = reinterpret_cast<uintptr_t>(out), b1 = b0 + (size_t)M * sizeof(ofdm_fc32);
+    if ((a0 & (ss - 1)) || (b0 & 7)) return OFDM_ERR_INVALID;
+    if (M > 0 && a0 < b1 && b0 < a1) return OFDM_ERR_INVALID; // a tile reads samples under its neighbour's outputs
+    ofdm_ctx *c = f->c;
+    EntryScope scope(c);
+    int64_t given = 0;
+    for (int64_t done = 0; done < n;) {
+        const int64_t m = std::min(n - done, f->max_chunk);
+        const Trace::Mute later(c->trace, done > 0); // the dispatch string names what a piece ran, once
+        int64_t k = 0;
+        const int rc = ddc_piece(f, static_cast<const char *>(in) + (size_t)done * ss, m, sc16, scale, reinterpret_cast<float2 *>(out) + given, &k);
+        if (rc) return rc;
+        done += m;
+        given += k;
+    }
+    if (n_out) *n_out = given;
+    return OFDM_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int ofdm_ddc_rotor_tables(float *coarse, float *fine) {
+    if (!coarse || !fine) return OFDM_ERR_INVALID;
+    const DdcRotors &r = ddc_rotors();
+    std::memcpy(coarse, r.coarse, sizeof(r.coarse));
+    std::memcpy(fine, r.fine, sizeof(r.fine));
+    return OFDM_OK;
+}
+
+int64_t ofdm_ddc_out_len(int64_t n, int32_t decim, int32_t n_taps) {
+    if (n < 0 || !ddc_args_ok(decim, n_taps)) return OFDM_ERR_INVALID;
+    return ofdm::ddc_out_len(n, decim, n_taps);
+}
+
+int ofdm_ddc_inc_for(double f0, int32_t *inc) {
+    if (!inc || !std::isfinite(f0) || std::fabs(f0) > 0.5) return OFDM_ERR_INVALID;
+    *inc = (int32_t)((-(int64_t)std::rint(f0 * 1048576.0)) & ofdm::kDdcPhaseMask);
+    return OFDM_OK;
+}
+
+int ofdm_ddc_design(int32_t decim, int32_t taps_per_phase, float *taps) {
+    if (decim < 1 || decim > ofdm::kDdcMaxDecim || taps_per_phase < 1 || taps_per_phase > 64 || !taps) return OFDM_ERR_INVALID;
+    const int T = decim * taps_per_phase;
+    if (T == 1) { taps[0] = 1.f; return OFDM_OK; }
+    const double pi = 3.14159265358979323846264338327950288;
+    std::vector<double> h((size_t)T);
+    double sum = 0.0;
+    for (int k = 0; k < T; k++) {
+        const double x = ((double)k - (double)(T - 1) / 2.0) / (double)decim;
+        const double s = x == 0.0 ? 1.0 : std::sin(pi * x) / (pi * x);
+        h[(size_t)k] = s * (0.54 - 0.46 * std::cos(2.0 * pi * (double)k / (double)(T - 1)));
+        sum += h[(size_t)k];
+    }
+    for (int k = 0; k < T; k++) taps[k] = (float)(h[(size_t)k] / sum);
+    return OFDM_OK;
+}
+
+int ofdm_ddc(const ofdm_fc32 *in, int64_t n, int32_t decim, int32_t phase_inc, const float *taps, int32_t n_taps, ofdm_fc32 *out, int64_t out_cap,
+             int64_t *n_out) {
+    if (n_out) *n_out = 0;
+    if (n < 0 || out_cap < 0 || !ddc_args_ok(decim, n_taps) || !taps || (n > 0 && !in)) return OFDM_ERR_INVALID;
+    return ddc_host(n, decim, (uint32_t)phase_inc & (uint32_t)ofdm::kDdcPhaseMask, taps, n_taps, [&](int64_t i) { return in[i]; }, out, out_cap, n_out);
+}
+
+int ofdm_ddc_sc16(const ofdm_sc16 *in, int64_t n, float scale, int32_t decim, int32_t phase_inc, const float *taps, int32_t n_taps, ofdm_fc32 *out,
+                  int64_t out_cap, int64_t *n_out) {
+    if (n_out) *n_out = 0;
+    if (n < 0 || out_cap < 0 || !ddc_args_ok(decim, n_taps) || !taps || (n > 0 && !in) || !sc16_scale_ok(scale)) return OFDM_ERR_INVALID;
+    // widened as it is read, by EXT-9's own host rule (one rounded product, made in another translation unit: nothing contracts it)
+    return ddc_host(n, decim, (uint32_t)phase_inc & (uint32_t)ofdm::kDdcPhaseMask, taps, n_taps,
+                    [&](int64_t i) { ofdm_fc32 x; ofdm::sc16_widen_host(&in[i].re, 1, scale, &x.re); return x; }, out, out_cap, n_out);
+}
+
+int ofdm_ddc_create(ofdm_ddc_handle **out, ofdm_ctx *c, int32_t decim, int32_t phase_inc, const float *taps, int32_t n_taps, int64_t max_chunk) {
+    if (out) *out = nullptr;
+    if (!out || !c || !ddc_args_ok(decim, n_taps) || !taps || max_chunk <= 0) return OFDM_ERR_INVALID;
+    if (max_chunk > kScanMaxSamples) return OFDM_ERR_UNSUPPORTED;
+    ofdm_ddc_handle *f = new (std::nothrow) ofdm_ddc_handle();
+    if (!f) return OFDM_ERR_NOMEM;
+    f->c = c; f->D = decim; f->T = n_taps; f->inc = (uint32_t)phase_inc & (uint32_t)ofdm::kDdcPhaseMask; f->max_chunk = max_chunk;
+    DeviceGuard dev_guard(c->device);
+    const size_t tap_bytes = round_up((size_t)n_taps * sizeof(float), 256), rot_bytes = 1024 * sizeof(float2);
+    const size_t carry_bytes = round_up((size_t)n_taps * sizeof(float2), 256);
+    int rc = stream_dev_alloc(c, &f->state, tap_bytes + 2 * rot_bytes + 2 * carry_bytes);
+    if (rc) { delete f; return rc; }
+    char *b = static_cast<char *>(f->state);
+    f->taps = reinterpret_cast<float *>(b);
+    f->coarse = reinterpret_cast<float2 *>(b + tap_bytes); f->fine = reinterpret_cast<float2 *>(b + tap_bytes + rot_bytes);
+    f->carry[0] = reinterpret_cast<float2 *>(b + tap_bytes + 2 * rot_bytes); f->carry[1] = reinterpret_cast<float2 *>(b + tap_bytes + 2 * rot_bytes + carry_bytes);
+    const DdcRotors &r = ddc_rotors();
+    hipError_t e = hipMemcpyAsync(f->taps, taps, (size_t)n_taps * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->coarse, r.coarse, rot_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(f->fine, r.fine, rot_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // the caller's taps are read here and never again
+    if (e != hipSuccess) { c->last_hip = (int)e; ddc_free(f); delete f; return OFDM_ERR_HIP; }
+    *out = f;
+    return OFDM_OK;
+}
+
+int ofdm_ddc_destroy(ofdm_ddc_handle *f) {
+    if (!f || !f->c) return OFDM_ERR_INVALID;
+    DeviceGuard dev_guard(f->c->device);
+    const hipError_t e = hipStreamSynchronize(f->c->stream);
+    ddc_free(f);
+    const int rc = e == hipSuccess ? OFDM_OK : OFDM_ERR_HIP;
+    if (rc) f->c->last_hip = (int)e;
+    delete f;
+    return rc;
+}
+
+int ofdm_ddc_reset(ofdm_ddc_handle *f) {
+    if (!f) return OFDM_ERR_INVALID;
+    f->n_in = 0; // nothing of the carry is read before the launch that follows has written it
+    return OFDM_OK;
+}
+
+int ofdm_ddc_push(ofdm_ddc_handle *f, const ofdm_fc32 *in_dev, int64_t n, ofdm_fc32 *out_dev, int64_t out_cap, int64_t *n_out) {
+    return ddc_push(f, in_dev, n, sizeof(ofdm_fc32), false, 0.f, out_dev, out_cap, n_out);
+}
+
+int ofdm_ddc_push_sc16(ofdm_ddc_handle *f, const ofdm_sc16 *in_dev, int64_t n, float scale, ofdm_fc32 *out_dev, int64_t out_cap, int64_t *n_out) {
+    return ddc_push(f, in_dev, n, sizeof(ofdm_sc16), true, scale, out_dev, out_cap, n_out);
+}
+
+int ofdm_ddc_state(const ofdm_ddc_handle *f, int64_t *total_in, int64_t *total_out) {
+    if (!f) return OFDM_ERR_INVALID;
+    if (total_in) *total_in = f->n_in;
+    if (total_out) *total_out = ofdm::ddc_out_len(f->n_in, f->D, f->T);
+    return OFDM_OK;
+}
+
+} // extern "C"
+
 // ---- EXT-14: a streaming receiver (include/ofdm_hip.h, "a streaming receiver"; numpy restatement and the proofs: tests/stream_ref.py,
 // tests/test_stream_cpu.py).  The stream keeps the last samples of everything pushed in one of two device windows and, per piece of a
 // push: k_stream_ingest (the carry and the new chunk into the other window, one launch), ofdm_sc_scan_long's kernels over the window
@@ -1140,6 +1380,11 @@ struct ofdm_stream {
     ofdm_dcblock *dc = nullptr;
     void *stage_dc = nullptr;
     int32_t dc_blocks = 0;      // the setting: 0 = off
+    // EXT-16 (ofdm_stream_set_ddc): the down-converter in front of everything else and the fc32 samples it writes; made by a setting
+    // that is not 0 and kept until the stream is destroyed.  With it on, a push is INPUT-rate samples; T, B, lo, H count its OUTPUT
+    ofdm_ddc_handle *ddc = nullptr;
+    void *stage_ddc = nullptr;
+    int32_t ddc_decim = 0;      // the setting: 0 = off
     void *res_dev = nullptr, *res_pin = nullptr; // PacketsBlock of kStreamScanCap rows, device and pinned
     size_t row = 0;             // bytes of a result row there
     int64_t need = 0;           // decode_row_bytes: what a caller's row receives
@@ -1163,6 +1408,9 @@ void stream_free(ofdm_stream *s) {
     if (s->stage_dc) hipFree(s->stage_dc);
     if (s->dc) { dcblock_free(s->dc); delete s->dc; }
     s->dc = nullptr; s->stage_dc = nullptr;
+    if (s->stage_ddc) hipFree(s->stage_ddc);
+    if (s->ddc) { ddc_free(s->ddc); delete s->ddc; }
+    s->ddc = nullptr; s->stage_ddc = nullptr;
     if (s->res_dev) hipFree(s->res_dev);
     if (s->res_pin) hipHostFree(s->res_pin);
     s->stage = s->res_dev = s->res_pin = nullptr;
@@ -1174,6 +1422,7 @@ void stream_rewind(ofdm_stream *s, int64_t first_sample) {
     s->ended = false;
     s->q.clear(); s->q_rows.clear(); s->q_head = 0;
     if (s->dc) s->dc->T = 0; // EXT-15: the setting stays, the history goes
+    if (s->ddc) s->ddc->n_in = 0; // EXT-16: likewise
 }
 
 // Scan the window from `lo` on and decode what the horizon commits (flush: everything), round by round of at most `cap` detections;
@@ -1229,15 +1478,23 @@ int stream_piece(ofdm_stream *s, const void *in, int64_t m, size_t ss, bool sc16
     ofdm_ctx *c = s->c;
     bool synced = false;
     int rc;
+    if (m > 0 && s->ddc_decim) { // EXT-16: m input samples become the 0 .. m / D + 1 converted ones that everything below takes in
+        HIP_TRY(c, hipMemcpyAsync(s->stage, in, (size_t)m * ss, hipMemcpyHostToDevice, c->stream));
+        int64_t mo = 0;
+        if ((rc = ddc_piece(s->ddc, s->stage, m, sc16, scale, static_cast<float2 *>(s->stage_ddc), &mo))) return rc;
+        m = mo;
+        sc16 = false;
+    }
     if (m > 0) {
         const int64_t drop = s->keep_from - s->B, keep = s->T - s->keep_from;
         if (drop < 0 || (drop & 1) || keep < 0 || keep + m > s->win_cap) return OFDM_ERR_INVALID; // the retention bound (tests/test_stream_cpu.py): never
-        HIP_TRY(c, hipMemcpyAsync(s->stage, in, (size_t)m * ss, hipMemcpyHostToDevice, c->stream));
+        if (!s->ddc_decim) HIP_TRY(c, hipMemcpyAsync(s->stage, in, (size_t)m * ss, hipMemcpyHostToDevice, c->stream));
+        const void *chunk = s->ddc_decim ? s->stage_ddc : s->stage;
         StreamIngestParams p;
         p.tune = &c->tune; p.trace = &c->trace;
-        p.carry = s->win[s->cur] + drop; p.keep = keep; p.n = m; p.chunk = s->stage; p.scale = scale; p.win = s->win[s->cur ^ 1];
+        p.carry = s->win[s->cur] + drop; p.keep = keep; p.n = m; p.chunk = chunk; p.scale = scale; p.win = s->win[s->cur ^ 1];
         if (s->dc_blocks) { // EXT-15: the filtered chunk, already fc32, is what the window takes in
-            if ((rc = dcblock_piece(s->dc, s->stage, m, sc16, scale, static_cast<float2 *>(s->stage_dc)))) return rc;
+            if ((rc = dcblock_piece(s->dc, chunk, m, sc16, scale, static_cast<float2 *>(s->stage_dc)))) return rc;
             p.chunk = s->stage_dc;
             sc16 = false;
         }
@@ -1391,6 +1648,41 @@ int ofdm_stream_set_dc_block(ofdm_stream *s, int32_t blocks) {
 int ofdm_stream_get_dc_block(const ofdm_stream *s, int32_t *blocks) {
     if (!s || !blocks) return OFDM_ERR_INVALID;
     *blocks = s->dc_blocks;
+    return OFDM_OK;
+}
+
+int ofdm_stream_set_ddc(ofdm_stream *s, int32_t decim, int32_t phase_inc, const float *taps, int32_t n_taps) {
+    if (!s || !s->c || s->T != 0 || (s->ddc && s->ddc->n_in != 0)) return OFDM_ERR_INVALID;
+    if (decim == 0) { s->ddc_decim = 0; return OFDM_OK; }
+    std::vector<float> own;
+    if (!taps && n_taps == 0 && decim >= 1 && decim <= ofdm::kDdcMaxDecim) { // the default design
+        try { own.resize((size_t)decim * OFDM_DDC_TAPS_PER_PHASE); } catch (const std::exception &) { return OFDM_ERR_NOMEM; }
+        n_taps = decim * OFDM_DDC_TAPS_PER_PHASE;
+        if (ofdm_ddc_design(decim, OFDM_DDC_TAPS_PER_PHASE, own.data())) return OFDM_ERR_INVALID;
+        taps = own.data();
+    }
+    if (!ddc_args_ok(decim, n_taps) || !taps) return OFDM_ERR_INVALID;
+    ofdm_ctx *c = s->c;
+    DeviceGuard dev_guard(c->device);
+    int rc;
+    // a piece of max_chunk input samples gives at most max_chunk / D + 1 outputs; held for D = 1, so that a later setting fits too
+    if (!s->stage_ddc && (rc = stream_dev_alloc(c, &s->stage_ddc, ((size_t)s->max_chunk + 2) * sizeof(float2) + 256))) return rc;
+    ofdm_ddc_handle *f = nullptr;
+    if ((rc = ofdm_ddc_create(&f, c, decim, phase_inc, taps, n_taps, s->max_chunk))) return rc;
+    ofdm_ddc_handle *old = s->ddc;
+    s->ddc = f;
+    s->ddc_decim = decim;
+    // the old setting's converter: what its destroy reports (a failed synchronise; last_hip is set) is this call's result
+    if (old && (rc = ofdm_ddc_destroy(old))) return rc;
+    return OFDM_OK;
+}
+
+int ofdm_stream_get_ddc(const ofdm_stream *s, int32_t *decim, int32_t *phase_inc, int32_t *n_taps) {
+    if (!s) return OFDM_ERR_INVALID;
+    const bool on = s->ddc_decim != 0;
+    if (decim) *decim = s->ddc_decim;
+    if (phase_inc) *phase_inc = on ? (int32_t)s->ddc->inc : 0;
+    if (n_taps) *n_taps = on ? s->ddc->T : 0;
     return OFDM_OK;
 }
 
